@@ -22,6 +22,11 @@ Prints ONE JSON line (rank 0).  `roofline` is for the dominant hand-written kern
 HIP events on the launch stream.  `cpu_baseline` times the reference-equivalent CPU path (oracle
 restatement + the same HF architectures) on the host cores, bounded by depth-scaling (see
 cpu_reference_baseline).
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: `roofline` then holds only what the
+timed steps measured themselves.  `--full` adds everything that needs work of its own after the timed steps: eager steps to time
+the dominant kernel behind a whole-step hipGraph, its HBM traffic (rocprofv3 --pmc passes), the loss path alone, the kernel back
+to back, the lm_head paths (`f1_lm_head_paths`), `cpu_baseline` (+ `loss_path`) and the `parity` step.
 """
 from __future__ import annotations
 
@@ -42,6 +47,7 @@ HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICR
 A100_README_PAIRS_PER_S = 200000.0 / (7 * 3600.0)  # reference README.md:34-40 (1x A100 80GB), BASELINE.md section 1
 
 CFG = dict(B=18, Tq=50, Tp=128, Tg=256, D=1024, V=32000, logit_scale=100)
+FULL_ONLY = "bench.py --full measures it"  # what a plain run says where a figure needs work beyond the timed steps
 
 
 GENERATORS = {
@@ -630,10 +636,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need (see the module docstring): "
+                         "probe kernels, PMC traffic, f1 lm_head paths, CPU baselines, parity step")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline, loss_path and parity")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="skip the two rocprofv3 --pmc passes (FETCH_SIZE / WRITE_SIZE of the dominant kernel, ~30 s) that fill "
-                         "roofline.traffic")
+                    help="with --full: skip the two rocprofv3 --pmc passes (FETCH_SIZE / WRITE_SIZE of the dominant kernel, ~30 s) "
+                         "that fill roofline.traffic")
     ap.add_argument("--no-graph", action="store_true", help="launch the step eagerly instead of replaying a hipGraph")
     ap.add_argument("--no-overlap", action="store_true", help="run the retriever towers on the main stream")
     ap.add_argument("--graph-collectives", action="store_true",
@@ -815,7 +824,9 @@ def main():
     probe_note = "HIP events around the launch in every timed step"
     if batches is None:                                   # loader mode: probes below use plain resident batches
         batches = [synthetic_batch(dev, 100 + 17 * rank + i, V=V) for i in range(4)]
-    if graphed:
+    if graphed and not args.full:
+        probe_note = f"not timed: the timed region replays a hipGraph ({FULL_ONLY})"
+    elif graphed:
         # the timed region replays a hipGraph; time the dominant kernel live with HIP events in a few
         # eager launches of the very same step right after it (not part of `value`)
         ops.enabled = True
@@ -847,20 +858,20 @@ def main():
         # cannot share a pass, and counters perturb timing, so they are never collected inside the timed run):
         # tools/pmc_bench.sh writes profiles/roofline_traffic.json; the value is per launch, FETCH doubled as the
         # gfx950 guide prescribes.  Only quoted for the workload/dtype it was collected on.
-        traffic, traffic_source = None, "not collected this run"
-        if args.gpus == 1 and not args.no_pmc and not args.fuse_lm_head and args.data_path in ("fixed", "loader"):
+        traffic, traffic_source = None, "not collected this run" + ("" if args.full else f" ({FULL_ONLY})")
+        if args.full and args.gpus == 1 and not args.no_pmc and not args.fuse_lm_head and args.data_path in ("fixed", "loader"):
             try:
                 traffic, traffic_source = collect_ce_traffic(args.workload, args.dtype, V)
             except Exception as e:
                 traffic, traffic_source = None, f"not collected this run: {e!r}"
-        loss_path_us, loss_path_how = None, None
-        if args.gpus == 1 and not args.fuse_lm_head:
+        loss_path_us, loss_path_how = None, (None if args.full else f"not measured ({FULL_ONLY})")
+        if args.full and args.gpus == 1 and not args.fuse_lm_head:
             try:
                 loss_path_us, loss_path_how = gpu_loss_path_probe(dev, batches[0], torch.bfloat16 if args.dtype == "bf16" else torch.float32, V)
             except Exception as e:
                 loss_path_how = f"failed: {e!r}"
         b2b_us, b2b_gbps = None, None
-        if args.gpus == 1 and not args.fuse_lm_head and args.data_path == "fixed":
+        if args.full and args.gpus == 1 and not args.fuse_lm_head and args.data_path == "fixed":
             try:
                 b2b_us, b2b_gbps = ce_back_to_back_probe(dev, batches[0], torch.bfloat16 if args.dtype == "bf16" else torch.float32, V)
             except Exception:
@@ -941,7 +952,7 @@ def main():
                                  "side); the all-ones-mask roofline point is in profiles/ (tools/kernel_bench.py)",
                          "timing": probe_note},
         }
-        if args.gpus == 1 and args.dtype == "bf16" and batches and (not args.no_pmc or args.fuse_lm_head):
+        if args.full and args.gpus == 1 and args.dtype == "bf16" and batches and (not args.no_pmc or args.fuse_lm_head):
             try:
                 out["f1_lm_head_paths"] = f1_head_paths(dev, batches[0], model)
             except Exception as e:
@@ -958,7 +969,7 @@ def main():
                                "algorithmic_flop": flop, "avg_launch_us": f1["kernels_ms"] * 1e3,
                                "note": "3 contractions of [rows, H] x [V, H] over the live rows (HIP events around eager calls, "
                                        "f1_lm_head_paths.kernels_ms); the library path of the same rows takes f1_lm_head_paths.library_ms"}
-        if args.gpus == 1 and not args.no_cpu_baseline and args.workload == "cfg3":
+        if args.full and args.gpus == 1 and not args.no_cpu_baseline and args.workload == "cfg3":
             try:
                 out["cpu_baseline"], parity = cpu_reference_baseline(parity_dev=dev)
                 if parity is not None:
@@ -1111,12 +1122,6 @@ def main_retriever_only(args):
 
 
 if __name__ == "__main__":
+    # the process ends through the interpreter's normal shutdown, so that exit handlers run (a profiler writes its output from
+    # them, TunableOp its results file)
     main()
-    # the line is out; what is left is interpreter + HIP teardown (a dozen hipGraphs, their pools, RCCL): its exit status is not the
-    # bench's (seen: status 1 after a complete bucketed run, nothing on stderr)
-    sys.stdout.flush()
-    sys.stderr.flush()
-    # ... unless a profiler rides along: rocprofv3 writes its output from exit handlers
-    if os.environ.get("DALM_BENCH_FAST_EXIT", "1") != "0" and not any(
-            k.startswith(("ROCPROF", "ROCP_", "ROCTRACER", "ROCTX")) for k in os.environ):
-        os._exit(0)

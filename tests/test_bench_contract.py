@@ -1,8 +1,9 @@
-"""bench.py contract checks that need no GPU: flags, defaults, workload shapes, JSON keys it promises."""
+"""bench.py contract checks: flags, defaults, workload shapes, JSON keys it promises (one GPU test runs it at depth 1)."""
 import ast
 import sys
 from pathlib import Path
 
+import pytest
 import torch
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -19,10 +20,59 @@ def test_bench_flags_and_defaults():
             default = next((ast.literal_eval(k.value) for k in node.keywords if k.arg == "default"), None)
             flags[name] = default
     assert flags["--gpus"] == 1 and flags["--steps"] == 10 and flags["--warmup"] == 3
+    assert "--full" in flags and flags["--full"] is None      # store_true: off unless asked for
     for key in ('"metric"', '"value"', '"unit"', '"n_gpus"', '"steps"', '"warmup"', '"ms_per_step"', '"higher_is_better"',
                 '"scaling"', '"vs_baseline"', '"dtype"', '"data"', '"config"', '"roofline"', '"cpu_baseline"',
                 '"bound"', '"achieved"', '"peak"', '"frac"', '"traffic"', '"cores"', '"kind"', '"sample"'):
         assert key in src, key
+
+
+def _full_polarity(test):
+    """(+1 if `args.full` appears in the condition, -1 if it appears under a `not`, 0 if it does not appear)."""
+    found = 0
+
+    def walk(node, negated):
+        nonlocal found
+        if isinstance(node, ast.Attribute) and node.attr == "full" and getattr(node.value, "id", None) == "args":
+            found = -1 if negated else 1
+            return
+        neg = negated ^ (isinstance(node, ast.UnaryOp) and isinstance(node.op, ast.Not))
+        for child in ast.iter_child_nodes(node):
+            walk(child, neg)
+
+    walk(test, False)
+    return found
+
+
+def test_plain_run_leaves_the_extra_measurements_to_full():
+    """A plain `bench.py` run does only what its headline line needs: every probe, PMC pass, CPU baseline and the eager steps
+    after a whole-step graph are reached only through a branch that `--full` opens."""
+    tree = ast.parse((ROOT / "bench.py").read_text())
+    main = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "main")
+    extras = {"collect_ce_traffic", "gpu_loss_path_probe", "ce_back_to_back_probe", "f1_head_paths", "cpu_reference_baseline",
+              "cpu_loss_path_baseline"}
+    seen = []
+
+    def visit(node, guarded):
+        if isinstance(node, ast.Call):
+            f = node.func
+            name = f.id if isinstance(f, ast.Name) else (f"{getattr(f.value, 'id', '')}.{f.attr}" if isinstance(f, ast.Attribute) else "")
+            if name in extras or name == "step.step":
+                seen.append((name, node.lineno, guarded))
+        if isinstance(node, ast.If):
+            pol = _full_polarity(node.test)
+            visit(node.test, guarded)
+            for child in node.body:
+                visit(child, guarded or pol > 0)
+            for child in node.orelse:
+                visit(child, guarded or pol < 0)
+            return
+        for child in ast.iter_child_nodes(node):
+            visit(child, guarded)
+
+    visit(main, False)
+    assert {n for n, _, _ in seen} == extras | {"step.step"}, seen
+    assert all(g for _, _, g in seen), [s for s in seen if not s[2]]
 
 
 def test_synthetic_batch_matches_cfg3_shapes():
@@ -126,3 +176,47 @@ def test_dump_outputs_writes_loss_and_trainable_parameters(tmp_path, monkeypatch
     assert 0 < sampled <= 1 << 16
     for n in trainable:
         assert np.array_equal(np.load(tmp_path / "a" / f"param.{n}.npy"), np.load(tmp_path / "b" / f"param.{n}.npy"))
+
+
+# runs bench.py as __main__ after registering an exit handler that writes the process's memory map to a file
+_EXIT_PROBE = ("import atexit, runpy, sys\n"
+               "out = sys.argv[1]\n"
+               "atexit.register(lambda: open(out, 'w').write(open('/proc/self/maps').read()))\n"
+               "sys.argv = sys.argv[2:]\n"
+               "runpy.run_path(sys.argv[0], run_name='__main__')\n")
+
+
+def _bench_line(maps_file, *extra):
+    """(the JSON line, the process's memory map as its exit handlers saw it - None if they never ran)."""
+    import json
+    import subprocess
+
+    cmd = [sys.executable, "-c", _EXIT_PROBE, str(maps_file), str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1",
+           "--retriever-layers", "1", "--generator-layers", "1", *extra]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+    return json.loads(r.stdout.strip().splitlines()[-1]), (maps_file.read_text() if maps_file.exists() else None)
+
+
+@pytest.mark.gpu
+def test_plain_and_full_runs_on_gpu(tmp_path):
+    """Depth-1 towers: a plain run prints the headline line without the extra measurements; `--full` adds them after the same
+    timed steps, which compute the same loss.  Both end through the interpreter's normal shutdown, with this library's HIP
+    code loaded: exit handlers (profilers, TunableOp) see the whole run."""
+    import math
+
+    plain, maps = _bench_line(tmp_path / "plain_maps.txt")
+    assert maps is not None and "libdalm_hip.so" in maps
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in plain, key
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["higher_is_better"] is True
+    for key in ("cpu_baseline", "parity", "loss_path", "f1_lm_head_paths"):
+        assert key not in plain, key
+    roof = plain["roofline"]
+    assert roof["traffic"] is None and roof["loss_path_us"] is None and roof["back_to_back_us"] is None
+    assert roof["avg_launch_us"] > 0          # HIP events around the CE launch inside the timed steps
+
+    full, maps = _bench_line(tmp_path / "full_maps.txt", "--full", "--no-cpu-baseline", "--no-pmc")
+    assert maps is not None and "libdalm_hip.so" in maps
+    assert full["roofline"]["loss_path_us"] > 0 and full["roofline"]["back_to_back_us"] > 0
+    assert math.isfinite(plain["config"]["final_loss"]) and full["config"]["final_loss"] == plain["config"]["final_loss"]

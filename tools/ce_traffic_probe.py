@@ -1,5 +1,5 @@
 """The dominant loss kernel of bench.py (marginalised CE, fused forward + gradient) launched alone at the bench's exact
-shapes and masks, for the PMC passes bench.py runs around it (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE cannot share a pass
+shapes and masks, for the PMC passes `bench.py --full` runs around it (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE cannot share a pass
 and perturb timing, so they never run inside the timed region).
     python tools/ce_traffic_probe.py [--workload cfg3|cfg5] [--dtype bf16|fp32]
 """

@@ -8,15 +8,15 @@ export TMPDIR=/tmp
 P=gpurun_out/profiles_r05; mkdir -p $P
 date -u +"# %Y-%m-%dT%H:%M:%SZ tree $(cat .tree_id 2>/dev/null)" >> $P/r05_refresh_stamp.txt
 if [ "$PART" = bench ] || [ "$PART" = all ]; then
-  python bench.py > $P/r05_bench_default.json 2> $P/bench.err
-  python bench.py --workload cfg5 --no-cpu-baseline > $P/r05_bench_cfg5.json 2>> $P/bench.err
+  python bench.py --full > $P/r05_bench_default.json 2> $P/bench.err
+  python bench.py --full --workload cfg5 --no-cpu-baseline > $P/r05_bench_cfg5.json 2>> $P/bench.err
   python bench.py --workload cfg2 --no-cpu-baseline > $P/r05_bench_cfg2.json 2>> $P/bench.err
   python bench.py --workload cfg1 --no-cpu-baseline > $P/r05_bench_cfg1.json 2>> $P/bench.err
-  python bench.py --dtype fp32 --no-cpu-baseline > $P/r05_bench_cfg3_fp32.json 2>> $P/bench.err
-  python bench.py --steps 20 --warmup 5 --data-path loader --no-cpu-baseline --no-pmc > $P/r05_bench_cfg3_loader.json 2>> $P/bench.err
-  python bench.py --steps 30 --warmup 6 --fuse-lm-head --no-cpu-baseline > $P/r05_bench_cfg3_fuse_lm_head.json 2>> $P/bench.err
-  DALM_LM_HEAD_TRAIN_KERNEL=0 python bench.py --steps 30 --warmup 6 --fuse-lm-head --no-cpu-baseline > $P/r05_bench_cfg3_fuse_lm_head_library_path.json 2>> $P/bench.err
-  python bench.py --data-path bucketed --steps 24 --warmup 12 --no-cpu-baseline > $P/r05_bench_cfg3_bucketed_trimmed.json 2>> $P/bench.err
+  python bench.py --full --dtype fp32 --no-cpu-baseline > $P/r05_bench_cfg3_fp32.json 2>> $P/bench.err
+  python bench.py --full --steps 20 --warmup 5 --data-path loader --no-cpu-baseline --no-pmc > $P/r05_bench_cfg3_loader.json 2>> $P/bench.err
+  python bench.py --full --steps 30 --warmup 6 --fuse-lm-head --no-cpu-baseline > $P/r05_bench_cfg3_fuse_lm_head.json 2>> $P/bench.err
+  DALM_LM_HEAD_TRAIN_KERNEL=0 python bench.py --full --steps 30 --warmup 6 --fuse-lm-head --no-cpu-baseline > $P/r05_bench_cfg3_fuse_lm_head_library_path.json 2>> $P/bench.err
+  python bench.py --full --data-path bucketed --steps 24 --warmup 12 --no-cpu-baseline > $P/r05_bench_cfg3_bucketed_trimmed.json 2>> $P/bench.err
   for f in $P/r05_bench_*.json; do python - "$f" <<'PY'
 import json, sys
 try:

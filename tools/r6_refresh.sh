@@ -37,19 +37,19 @@ PY
   done
 }
 if has bench; then
-  run $P/r06_bench_default.json python bench.py
-  run $P/r06_bench_cfg3_whole_step_graph.json python bench.py --whole-step-graph --steps 20 --warmup 5 --no-cpu-baseline --no-pmc
-  run $P/r06_bench_cfg3_packed_whole_step_graph.json python bench.py --data-path packed --whole-step-graph --steps 20 --warmup 5 --no-cpu-baseline --no-pmc
-  run $P/r06_bench_cfg5.json python bench.py --workload cfg5 --no-cpu-baseline
+  run $P/r06_bench_default.json python bench.py --full
+  run $P/r06_bench_cfg3_whole_step_graph.json python bench.py --full --whole-step-graph --steps 20 --warmup 5 --no-cpu-baseline --no-pmc
+  run $P/r06_bench_cfg3_packed_whole_step_graph.json python bench.py --full --data-path packed --whole-step-graph --steps 20 --warmup 5 --no-cpu-baseline --no-pmc
+  run $P/r06_bench_cfg5.json python bench.py --full --workload cfg5 --no-cpu-baseline
   run $P/r06_bench_cfg2.json python bench.py --workload cfg2 --no-cpu-baseline
   run $P/r06_bench_cfg1.json python bench.py --workload cfg1 --no-cpu-baseline
-  run $P/r06_bench_cfg3_fp32.json python bench.py --dtype fp32 --no-cpu-baseline
-  run $P/r06_bench_cfg3_loader.json python bench.py --steps 20 --warmup 5 --data-path loader --no-cpu-baseline --no-pmc
-  run $P/r06_bench_cfg3_bucketed_trimmed.json python bench.py --data-path bucketed --steps 24 --warmup 12 --no-cpu-baseline
+  run $P/r06_bench_cfg3_fp32.json python bench.py --full --dtype fp32 --no-cpu-baseline
+  run $P/r06_bench_cfg3_loader.json python bench.py --full --steps 20 --warmup 5 --data-path loader --no-cpu-baseline --no-pmc
+  run $P/r06_bench_cfg3_bucketed_trimmed.json python bench.py --full --data-path bucketed --steps 24 --warmup 12 --no-cpu-baseline
 fi
 if has packed; then
-  run $P/r06_bench_cfg3_packed.json python bench.py --data-path packed --steps 20 --warmup 4 --no-cpu-baseline
-  run $P/r06_bench_cfg5_packed.json python bench.py --workload cfg5 --data-path packed --steps 20 --warmup 4 --no-cpu-baseline
+  run $P/r06_bench_cfg3_packed.json python bench.py --full --data-path packed --steps 20 --warmup 4 --no-cpu-baseline
+  run $P/r06_bench_cfg5_packed.json python bench.py --full --workload cfg5 --data-path packed --steps 20 --warmup 4 --no-cpu-baseline
   run $P/r06_bench_cfg2_packed.json python bench.py --workload cfg2 --data-path packed --no-cpu-baseline
 fi
 if has bench || has packed; then lines $P/r06_bench_*.json | tee $P/r06_bench_lines.txt; fi
@@ -93,9 +93,9 @@ if has simpmc; then
 fi
 if has dist; then
   # the W > 1 launch mode with ONE rank (DALM_FORCE_DIST=1): torch.distributed communicator, then the library's own
-  DALM_FORCE_DIST=1 run $P/r06_bench_one_rank_dist_torch.json python bench.py --steps 20 --warmup 4 --no-cpu-baseline --no-pmc
-  DALM_FORCE_DIST=1 DALM_NATIVE_COMM=1 run $P/r06_bench_one_rank_dist_native.json python bench.py --steps 20 --warmup 4 --no-cpu-baseline --no-pmc
-  DALM_FORCE_DIST=1 run $P/r06_bench_one_rank_dist_torch_packed.json python bench.py --data-path packed --steps 20 --warmup 6 --no-cpu-baseline --no-pmc
+  DALM_FORCE_DIST=1 run $P/r06_bench_one_rank_dist_torch.json python bench.py --full --steps 20 --warmup 4 --no-cpu-baseline --no-pmc
+  DALM_FORCE_DIST=1 DALM_NATIVE_COMM=1 run $P/r06_bench_one_rank_dist_native.json python bench.py --full --steps 20 --warmup 4 --no-cpu-baseline --no-pmc
+  DALM_FORCE_DIST=1 run $P/r06_bench_one_rank_dist_torch_packed.json python bench.py --full --data-path packed --steps 20 --warmup 6 --no-cpu-baseline --no-pmc
   lines $P/r06_bench_one_rank_dist_*.json | tee $P/r06_bench_one_rank_dist_lines.txt
 fi
 find gpurun_out -name "*kernel_trace.csv" -size +4M -delete

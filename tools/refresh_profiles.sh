@@ -7,14 +7,14 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 P=gpurun_out/profiles_$TAG
 rm -rf $P; mkdir -p $P
 # 1. bench lines (HIP-event roofline inside)
-python bench.py > $P/${TAG}_bench_default.json 2> $P/bench_default.err
-python bench.py --dtype fp32 --no-cpu-baseline > $P/${TAG}_bench_cfg3_fp32.json 2>> $P/bench_default.err
-python bench.py --workload cfg5 --no-cpu-baseline > $P/${TAG}_bench_cfg5.json 2>> $P/bench_default.err
+python bench.py --full > $P/${TAG}_bench_default.json 2> $P/bench_default.err
+python bench.py --full --dtype fp32 --no-cpu-baseline > $P/${TAG}_bench_cfg3_fp32.json 2>> $P/bench_default.err
+python bench.py --full --workload cfg5 --no-cpu-baseline > $P/${TAG}_bench_cfg5.json 2>> $P/bench_default.err
 python bench.py --workload cfg2 > $P/${TAG}_bench_cfg2.json 2>> $P/bench_default.err
 python bench.py --workload cfg1 > $P/${TAG}_bench_cfg1.json 2>> $P/bench_default.err
-python bench.py --steps 20 --warmup 5 --data-path loader --no-cpu-baseline --no-pmc > $P/${TAG}_bench_cfg3_loader.json 2>> $P/bench_default.err
-python bench.py --steps 30 --warmup 6 --fuse-lm-head --no-cpu-baseline > $P/${TAG}_bench_cfg3_fuse_lm_head.json 2>> $P/bench_default.err
-python bench.py --data-path bucketed --steps 24 --warmup 12 --no-cpu-baseline > $P/${TAG}_bench_cfg3_bucketed_trimmed.json 2>> $P/bench_default.err
+python bench.py --full --steps 20 --warmup 5 --data-path loader --no-cpu-baseline --no-pmc > $P/${TAG}_bench_cfg3_loader.json 2>> $P/bench_default.err
+python bench.py --full --steps 30 --warmup 6 --fuse-lm-head --no-cpu-baseline > $P/${TAG}_bench_cfg3_fuse_lm_head.json 2>> $P/bench_default.err
+python bench.py --full --data-path bucketed --steps 24 --warmup 12 --no-cpu-baseline > $P/${TAG}_bench_cfg3_bucketed_trimmed.json 2>> $P/bench_default.err
 # 2. in-situ kernel trace + PMC traffic of the loss kernels in bench.py (cfg3 bf16 and cfg5)
 bash tools/pmc_bench.sh $TAG > $P/pmc_bench.log 2>&1
 cp gpurun_out/pmc_bench_$TAG/pmc_loss_kernels.txt $P/${TAG}_bench_pmc_loss_kernels.txt
