@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256, 2) void lm_head_lse_kernel(const LmParams p) {
   const int wm = wave >> 1, wn = wave & 1;
   // XCD-aware order: workgroup L runs on XCD L % 8 (own 4 MB L2).  Every XCD gets a contiguous run of tile ids = a range
   // of vocabulary tiles with all their row tiles, so a 1 MB W tile is pulled into ONE L2 and shared by the row tiles that
-  // use it (plain order: each W tile lands in up to 8 L2s and is shared by < 2 workgroups per XCD).  DALM_LM_HEAD_XCD=0 disables.
+  // use it (plain order: each W tile lands in up to 8 L2s and is shared by < 2 workgroups per XCD).  The launchers always set it.
   unsigned wgid = blockIdx.x;
   if (p.xcd_order) {
     const unsigned nwg = gridDim.x, L = blockIdx.x;
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(256, 2) void lm_head_lse_kernel(const LmParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Round 3: the same contraction on a structure built from measurements on the MI355X (tools/lm_head_ablate.py,
+// Round 3: the same contraction on a structure built from measurements on the MI355X (ablation builds,
 // profiles/history/r03_lm_head_*): 256 x 256 x 64 tiles, FOUR waves = one per SIMD with the whole 512-register file each,
 // operands straight from global memory into LDS (buffer_load_dwordx4 ... lds), ONE barrier per K tile, a VALU-only epilogue,
 // one workgroup per tile.  What the intermediate forms showed:
@@ -314,22 +314,9 @@ __device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rs, unsigned ch
 // one of accumulator register k and the 16 rows of a 32 x 32 tile leave in ONE store instruction.
 // Labels go through the (now free) LDS: lab_s[256] = label - c0 of the tile's rows when the label falls into the tile's 256
 // columns (and below V), else -1: no lane matches.
-// ABL & 64 (measurement only): keep the accumulators alive, skip the reduction.
-template <int ABL>
 __device__ __forceinline__ void lm_tile_epilogue(const Lm8Params& p, f32x16 (&acc)[4][4], unsigned char* lds, int r0, int c0,
                                                  int nt, int wr, int wc, int tid) {
   const int lane = tid & 63, l31 = lane & 31, lhi = lane >> 5, l15 = lane & 15;
-  if (ABL & 64) {
-    float t0 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) t0 += acc[i][j][r];
-    if (t0 == 12345.678f) p.z[0] = t0;
-    return;
-  }
   int* lab_s = reinterpret_cast<int*>(lds);
   {
     const int r = r0 + tid;
@@ -599,16 +586,14 @@ __device__ __forceinline__ void lm_tile_epilogue_cstore(const Lm8Params& p, f32x
   }
 }
 
-// N3 / N0 / N1 / N2: load pieces issued in k-step 3 (right after the barrier) / 0 / 1 / 2; measured best: 8, 8, 0, 0.
-// ABL (measurement only, results are garbage unless 0): 1 = no loads in the loop, 2 = no fragment reads, 32 = no barrier,
-// 64 = no epilogue.
 // SPLIT3 (the bf16x3 similarity, see rowstats_bf16x3 below): the operands are [rows][3 D] bf16 images holding the (hi, mid,
 // lo) bf16 thirds of an f32 matrix side by side; the contraction walks SIX segments of D - the six significant products of
 // (hi + mid + lo) x (hi + mid + lo), smallest first - and K tile u reads third segA[u / tpd] of H against third segB[u / tpd]
 // of W: the same main loop, only the K offset of a tile is looked up instead of being u * 128.
-template <int N3, int N0, int N1, int N2, int ABL = 0, bool SPLIT3 = false, bool GMAX = false, int EPI = EPI_LSE>
+template <bool SPLIT3 = false, bool GMAX = false, int EPI = EPI_LSE>
 __global__ __launch_bounds__(256, 1) void lm_head_lse4w_kernel(const Lm8Params p) {
-  static_assert(N3 + N0 + N1 + N2 == 16, "16 load pieces per K tile and wave");
+  // load pieces (16 per K tile and wave) issued in k-step 3 (right after the barrier) / 0 / 1 / 2: measured best of the placements
+  constexpr int N3 = 8, N0 = 8, N1 = 0, N2 = 0;
   __shared__ __attribute__((aligned(16))) unsigned char lds[2 * L8_BUF];
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -629,7 +614,7 @@ __global__ __launch_bounds__(256, 1) void lm_head_lse4w_kernel(const Lm8Params p
     voff[8 + q] = static_cast<unsigned>(c0 + q * 32 + srow) * p.pitchW + schunk;
   }
   const int wave_lds = wave * 1024;
-#define L4_DMA(BUF, Q, KSA, KSB) if (!(ABL & 1)) lds_dma16((Q) < 8 ? rsH : rsW, lds + (BUF) * L8_BUF + (Q) * 4096 + wave_lds, voff[Q], (Q) < 8 ? (KSA) : (KSB));
+#define L4_DMA(BUF, Q, KSA, KSB) lds_dma16((Q) < 8 ? rsH : rsW, lds + (BUF) * L8_BUF + (Q) * 4096 + wave_lds, voff[Q], (Q) < 8 ? (KSA) : (KSB));
 
   const int f = (l31 >> 1) & 7;
   int koff[4];
@@ -664,7 +649,7 @@ __global__ __launch_bounds__(256, 1) void lm_head_lse4w_kernel(const Lm8Params p
   bf16x8 fa0[4], fb0[4], fa1[4], fb1[4];
 
 #define L4_READ(BUF, KK, FA, FB)                                                                                      \
-  if (!(ABL & 2)) _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                     \
+  _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                    \
     FA[i] = *reinterpret_cast<const bf16x8*>(lds + (BUF) * L8_BUF + i * 4096 + abase + koff[KK]);                     \
     FB[i] = *reinterpret_cast<const bf16x8*>(lds + (BUF) * L8_BUF + i * 4096 + bbase + koff[KK]);                     \
   }
@@ -692,7 +677,7 @@ __global__ __launch_bounds__(256, 1) void lm_head_lse4w_kernel(const Lm8Params p
     L4_READ(BUF, 3, fa1, fb1) L4_PIECES(OTH, N3 + N0 + N1, N2, ks1a, ks1b) L4_MFMA(fa0, fb0) L4_SCHED(N2)              \
     __builtin_amdgcn_sched_barrier(0);                                                                                \
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                                       \
-    if (!(ABL & 32)) __builtin_amdgcn_s_barrier();                                                                    \
+    __builtin_amdgcn_s_barrier();                                                                                     \
     __builtin_amdgcn_sched_barrier(0);                                                                                \
     L4_READ(OTH, 0, fa0, fb0) L4_PIECES(BUF, 0, N3, ks2a, ks2b) L4_MFMA(fa1, fb1) L4_SCHED(N3)                         \
     __builtin_amdgcn_sched_barrier(0);                                                                                \
@@ -702,15 +687,6 @@ __global__ __launch_bounds__(256, 1) void lm_head_lse4w_kernel(const Lm8Params p
   _Pragma("unroll") for (int q = 0; q < 16; ++q) lds_dma16(q < 8 ? rsH : rsW, lds + q * 4096 + wave_lds, voff[q], ks(0, q < 8 ? 0 : 1));
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-  if (ABL & 2) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      fa1[i] = *reinterpret_cast<const bf16x8*>(lds + i * 4096 + abase + koff[1]);
-      fb1[i] = *reinterpret_cast<const bf16x8*>(lds + i * 4096 + bbase + koff[1]);
-      fa0[i] = *reinterpret_cast<const bf16x8*>(lds + i * 4096 + abase + koff[0]);
-      fb0[i] = *reinterpret_cast<const bf16x8*>(lds + i * 4096 + bbase + koff[0]);
-    }
-  } else
   L4_READ(0, 0, fa0, fb0)
   L4_PIECES(1, 0, N3, ks(1, 0), ks(1, 1))
   __builtin_amdgcn_sched_barrier(0);
@@ -735,7 +711,7 @@ __global__ __launch_bounds__(256, 1) void lm_head_lse4w_kernel(const Lm8Params p
   else if constexpr (EPI == EPI_LOGITS) lm_tile_epilogue_dlogits<true>(p, acc, lds, r0, c0, wr, wc, tid);
   else if constexpr (EPI == EPI_CSTORE) lm_tile_epilogue_cstore(p, acc, r0, c0, wr, wc, tid);
   else if constexpr (GMAX) lm_tile_epilogue_gmax(p, acc, r0, c0, wr, wc, tid);
-  else lm_tile_epilogue<ABL>(p, acc, lds, r0, c0, nt, wr, wc, tid);
+  else lm_tile_epilogue(p, acc, lds, r0, c0, nt, wr, wc, tid);
 }
 
 // One workgroup = 16 rows: thread t folds the partials p = t/16, t/16 + 16, .. of row t % 16 (16 consecutive rows per
@@ -904,20 +880,16 @@ extern "C" int dalm_lm_head_lse_fwd(const void* hidden, const void* weight, cons
                DALM_E_ALIGN, "hidden / weight must be 16-byte aligned");
   DALM_REQUIRE(ws_bytes >= dalm_lm_head_lse_workspace_bytes(R, V), DALM_E_SHAPE, "workspace too small");
   hipStream_t s = as_stream(stream);
-  // round-3 kernel (needs 32-bit buffer offsets); DALM_LM_HEAD_GEN=2 selects the round-2 kernel below
-  static const char* gen_env = getenv("DALM_LM_HEAD_GEN");
-  const int gen = gen_env ? atoi(gen_env) : 3;
+  // round-3 kernel (needs 32-bit buffer offsets); larger operands take the round-2 kernel below
   const uint64_t bytesH = static_cast<uint64_t>(R + 256) * K * 2, bytesW = static_cast<uint64_t>(V + 256) * K * 2;
-  if (gen >= 3 && bytesH < 0xffffff00ull && bytesW < 0xffffff00ull) {
+  if (bytesH < 0xffffff00ull && bytesW < 0xffffff00ull) {
     Lm8Params q;
     q.H = hidden; q.W = weight; q.labels = labels;
     q.R = static_cast<int>(R); q.V = static_cast<int>(V); q.K = static_cast<int>(K);
     q.MT = static_cast<int>((R + 255) / 256); q.NT = static_cast<int>((V + 255) / 256);
-    static const char* xcd_env8 = getenv("DALM_LM_HEAD_XCD");
-    q.xcd_order = xcd_env8 ? atoi(xcd_env8) != 0 : 1;
-    static const char* gh_env = getenv("DALM_LM_HEAD_GH");
+    q.xcd_order = 1;
     const int bands = (q.MT + 7) / 8;                                  // bands of <= 8 row tiles, as even as possible
-    q.gh = gh_env ? atoi(gh_env) : (q.MT + bands - 1) / bands;
+    q.gh = (q.MT + bands - 1) / bands;
     if (q.gh < 1 || q.gh > q.MT) q.gh = q.MT;
     q.bytesH = static_cast<unsigned>(static_cast<uint64_t>(R) * K * 2);
     q.bytesW = static_cast<unsigned>(static_cast<uint64_t>(V) * K * 2);
@@ -927,30 +899,14 @@ extern "C" int dalm_lm_head_lse_fwd(const void* hidden, const void* weight, cons
     const int64_t P4 = 4ll * q.NT;
     q.pm = f8; q.pl = f8 + P4 * R; q.z = f8 + 2 * P4 * R;
     const dim3 g4(static_cast<unsigned>(q.MT) * q.NT);
-    static const char* var_env = getenv("DALM_LM_HEAD_ABL");          // measurement only (tools/lm_head_ablate.py)
-    const int var = var_env ? atoi(var_env) : 0;
-    switch (var) {
-      case 0: hipLaunchKernelGGL((lm_head_lse4w_kernel<8, 8, 0, 0>), g4, dim3(256), 0, s, q); break;
-      case 1: hipLaunchKernelGGL((lm_head_lse4w_kernel<8, 8, 0, 0, 1>), g4, dim3(256), 0, s, q); break;
-      case 2: hipLaunchKernelGGL((lm_head_lse4w_kernel<8, 8, 0, 0, 2>), g4, dim3(256), 0, s, q); break;
-      case 35: hipLaunchKernelGGL((lm_head_lse4w_kernel<8, 8, 0, 0, 35>), g4, dim3(256), 0, s, q); break;
-      case 64: hipLaunchKernelGGL((lm_head_lse4w_kernel<8, 8, 0, 0, 64>), g4, dim3(256), 0, s, q); break;
-      case 99: hipLaunchKernelGGL((lm_head_lse4w_kernel<8, 8, 0, 0, 99>), g4, dim3(256), 0, s, q); break;
-      case 100: hipLaunchKernelGGL((lm_head_lse4w_kernel<6, 5, 5, 0>), g4, dim3(256), 0, s, q); break;   // load-piece placements
-      case 101: hipLaunchKernelGGL((lm_head_lse4w_kernel<4, 4, 4, 4>), g4, dim3(256), 0, s, q); break;
-      case 102: hipLaunchKernelGGL((lm_head_lse4w_kernel<12, 4, 0, 0>), g4, dim3(256), 0, s, q); break;
-      case 103: hipLaunchKernelGGL((lm_head_lse4w_kernel<0, 8, 8, 0>), g4, dim3(256), 0, s, q); break;
-      default: return fail(DALM_E_SHAPE, __func__, "unknown DALM_LM_HEAD_ABL");
-    }
+    hipLaunchKernelGGL(lm_head_lse4w_kernel<>, g4, dim3(256), 0, s, q);
     hipLaunchKernelGGL(lm_head_lse_merge_kernel, dim3(static_cast<unsigned>((R + 15) / 16)), dim3(256), 0, s, q.pm, q.pl,
                        q.z, labels, q.R, q.V, static_cast<int>(P4), row_lse, row_nll);
     return check_launch(__func__);
   }
   // 256-row tiles (fewer LDS bytes per MFMA) once they still give every CU several tiles; 128-row tiles below that
-  static const char* tm_env = getenv("DALM_LM_HEAD_TM");
   const int64_t NT = (V + LBN - 1) / LBN;
-  int tm = (((R + 255) / 256) * NT >= 1024) ? 4 : 2;
-  if (tm_env) tm = (atoi(tm_env) == 4) ? 4 : 2;
+  const int tm = (((R + 255) / 256) * NT >= 1024) ? 4 : 2;
   const int64_t LBM = 64 * tm, MT = (R + LBM - 1) / LBM;
   DALM_REQUIRE(MT * NT <= 0x7fffffffll, DALM_E_SHAPE, "too many tiles for one launch");
   LmParams p;
@@ -959,8 +915,7 @@ extern "C" int dalm_lm_head_lse_fwd(const void* hidden, const void* weight, cons
   p.labels = labels;
   p.R = static_cast<int>(R); p.V = static_cast<int>(V); p.K = static_cast<int>(K);
   p.MT = static_cast<int>(MT); p.NT = static_cast<int>(NT);
-  static const char* xcd_env = getenv("DALM_LM_HEAD_XCD");
-  p.xcd_order = xcd_env ? atoi(xcd_env) != 0 : 1;
+  p.xcd_order = 1;
   float* f = static_cast<float*>(ws);
   p.pm = f;
   p.pl = f + 2 * NT * R;
@@ -1047,7 +1002,7 @@ extern "C" int dalm_sim_rowstats_bf16x3(const float* A, const float* Bm, int64_t
   q.pm = reinterpret_cast<float*>(base + L.pm); q.pl = reinterpret_cast<float*>(base + L.pl);
   q.z = reinterpret_cast<float*>(base + L.z);
   DALM_REQUIRE(static_cast<int64_t>(q.MT) * q.NT <= 0x7fffffffll, DALM_E_SHAPE, "too many tiles for one launch");
-  hipLaunchKernelGGL((lm_head_lse4w_kernel<8, 8, 0, 0, 0, true>), dim3(static_cast<unsigned>(q.MT) * q.NT), dim3(256), 0, s, q);
+  hipLaunchKernelGGL((lm_head_lse4w_kernel<true>), dim3(static_cast<unsigned>(q.MT) * q.NT), dim3(256), 0, s, q);
   hipLaunchKernelGGL(lm_head_lse_merge_kernel, dim3(static_cast<unsigned>((m + 15) / 16)), dim3(256), 0, s, q.pm, q.pl, q.z,
                      labels, q.R, q.V, static_cast<int>(L.P4), row_lse, static_cast<float*>(nullptr), diag);
   return check_launch(__func__);
@@ -1091,7 +1046,7 @@ extern "C" int dalm_x3_group_max(const float* A, const float* Bm, int64_t m, int
   q.seg_bytes = static_cast<unsigned>(D * 2);
   q.gmax = gmax; q.ng = static_cast<int>(ng);
   DALM_REQUIRE(static_cast<int64_t>(q.MT) * q.NT <= 0x7fffffffll, DALM_E_SHAPE, "too many tiles for one launch");
-  hipLaunchKernelGGL((lm_head_lse4w_kernel<8, 8, 0, 0, 0, true, true>), dim3(static_cast<unsigned>(q.MT) * q.NT), dim3(256), 0, s, q);
+  hipLaunchKernelGGL((lm_head_lse4w_kernel<true, true>), dim3(static_cast<unsigned>(q.MT) * q.NT), dim3(256), 0, s, q);
   return check_launch(__func__);
 }
 
@@ -1101,8 +1056,7 @@ namespace {
 inline void lm8_geometry(Lm8Params& q, int64_t R, int64_t V) {
   q.R = static_cast<int>(R); q.V = static_cast<int>(V);
   q.MT = static_cast<int>((R + 255) / 256); q.NT = static_cast<int>((V + 255) / 256);
-  static const char* xcd_env8 = getenv("DALM_LM_HEAD_XCD");
-  q.xcd_order = xcd_env8 ? atoi(xcd_env8) != 0 : 1;
+  q.xcd_order = 1;
   const int bands = (q.MT + 7) / 8;
   q.gh = (q.MT + bands - 1) / bands;
   if (q.gh < 1 || q.gh > q.MT) q.gh = q.MT;
@@ -1131,7 +1085,7 @@ extern "C" int dalm_lm_head_dlogits(const void* hidden, const void* weight_chunk
   q.row_lse = row_lse; q.coef = coef; q.col_base = static_cast<int>(col_base);
   q.out = dl; q.out_pitch = pitch; q.out_cols = static_cast<int>(pitch); q.accumulate = 0;
   DALM_REQUIRE(static_cast<int64_t>(q.MT) * q.NT <= 0x7fffffffll, DALM_E_SHAPE, "too many tiles for one launch");
-  hipLaunchKernelGGL((lm_head_lse4w_kernel<8, 8, 0, 0, 0, false, false, EPI_DLOGITS>), dim3(static_cast<unsigned>(q.MT) * q.NT),
+  hipLaunchKernelGGL((lm_head_lse4w_kernel<false, false, EPI_DLOGITS>), dim3(static_cast<unsigned>(q.MT) * q.NT),
                      dim3(256), 0, as_stream(stream), q);
   return check_launch(__func__);
 }
@@ -1155,7 +1109,7 @@ extern "C" int dalm_lm_head_logits(const void* hidden, const void* weight, int64
   q.out = logits; q.out_pitch = pitch; q.out_cols = static_cast<int>(V % 2 ? V + 1 : V) <= pitch ? static_cast<int>(V % 2 ? V + 1 : V) : static_cast<int>(pitch);
   q.accumulate = 0;
   DALM_REQUIRE(static_cast<int64_t>(q.MT) * q.NT <= 0x7fffffffll, DALM_E_SHAPE, "too many tiles for one launch");
-  hipLaunchKernelGGL((lm_head_lse4w_kernel<8, 8, 0, 0, 0, false, false, EPI_LOGITS>), dim3(static_cast<unsigned>(q.MT) * q.NT),
+  hipLaunchKernelGGL((lm_head_lse4w_kernel<false, false, EPI_LOGITS>), dim3(static_cast<unsigned>(q.MT) * q.NT),
                      dim3(256), 0, as_stream(stream), q);
   return check_launch(__func__);
 }
@@ -1177,7 +1131,7 @@ extern "C" int dalm_lm_head_dhidden(const void* dl, const void* wt, int64_t R, i
   q.row_lse = nullptr; q.coef = nullptr; q.col_base = 0;
   q.out = dh; q.out_pitch = K; q.out_cols = static_cast<int>(K); q.accumulate = accumulate;
   DALM_REQUIRE(static_cast<int64_t>(q.MT) * q.NT <= 0x7fffffffll, DALM_E_SHAPE, "too many tiles for one launch");
-  hipLaunchKernelGGL((lm_head_lse4w_kernel<8, 8, 0, 0, 0, false, false, EPI_CSTORE>), dim3(static_cast<unsigned>(q.MT) * q.NT),
+  hipLaunchKernelGGL((lm_head_lse4w_kernel<false, false, EPI_CSTORE>), dim3(static_cast<unsigned>(q.MT) * q.NT),
                      dim3(256), 0, as_stream(stream), q);
   return check_launch(__func__);
 }
@@ -1214,12 +1168,11 @@ extern "C" int dalm_f32_to_bf16(const float* src, void* dst, int64_t n, dalm_str
 namespace {
 // Columns of S per block (a multiple of 256); the dS image is m x 3 x block x 2 bytes.  Larger blocks = fewer, fuller launches
 // (16384^2, profiles/r05_sim_grad_x3.txt: block 2048 163 TF f32-equivalent, 4096 179, 8192 188): as large as a 1 GiB dS image
-// allows, between 2048 and 8192.  DALM_X3_GRAD_BLOCK overrides (measurement).
+// allows, between 2048 and 8192.
 inline int64_t x3_grad_block(int64_t m) {
-  static const int64_t forced = [] { const char* e = getenv("DALM_X3_GRAD_BLOCK"); return e ? atoll(e) : 0ll; }();
-  int64_t b = forced > 0 ? forced : (int64_t(1) << 30) / (6 * (m > 0 ? m : 1));
-  if (forced <= 0) { if (b > 8192) b = 8192; if (b < 2048) b = 2048; }
-  if (b < 256) b = 256;
+  int64_t b = (int64_t(1) << 30) / (6 * (m > 0 ? m : 1));
+  if (b > 8192) b = 8192;
+  if (b < 2048) b = 2048;
   return b / 256 * 256;
 }
 struct X3GradLayout { size_t a3, b3, ds3, bt3, total; int64_t ncp; };
@@ -1288,7 +1241,7 @@ extern "C" int dalm_sim_grad_bf16x3(const float* A, const float* Bm, int64_t m, 
       q.row_lse = row_lse; q.coef = row_coef; q.col_lse = col_lse; q.col_coef = col_coef;
       q.col_base = static_cast<int>(j0); q.diag_offset = diag_offset;
       q.out = ds3; q.out_pitch = 3 * L.ncp; q.out_third = L.ncp; q.out_cols = static_cast<int>(L.ncp); q.accumulate = 0;
-      hipLaunchKernelGGL((lm_head_lse4w_kernel<8, 8, 0, 0, 0, true, false, EPI_DS3>), dim3(static_cast<unsigned>(q.MT) * q.NT),
+      hipLaunchKernelGGL((lm_head_lse4w_kernel<true, false, EPI_DS3>), dim3(static_cast<unsigned>(q.MT) * q.NT),
                          dim3(256), 0, s, q);
     }
     hipLaunchKernelGGL(split3_transpose_kernel, dim3(static_cast<unsigned>(L.ncp / 64), static_cast<unsigned>((D + 63) / 64)),
@@ -1305,7 +1258,7 @@ extern "C" int dalm_sim_grad_bf16x3(const float* A, const float* Bm, int64_t m, 
       q.seg_bytes = static_cast<unsigned>(L.ncp * 2);
       q.row_lse = nullptr; q.coef = nullptr; q.col_base = 0;
       q.out = dA; q.out_pitch = D; q.out_cols = static_cast<int>(D); q.accumulate = j0 > 0;
-      hipLaunchKernelGGL((lm_head_lse4w_kernel<8, 8, 0, 0, 0, true, false, EPI_CSTORE>), dim3(static_cast<unsigned>(q.MT) * q.NT),
+      hipLaunchKernelGGL((lm_head_lse4w_kernel<true, false, EPI_CSTORE>), dim3(static_cast<unsigned>(q.MT) * q.NT),
                          dim3(256), 0, s, q);
     }
   }

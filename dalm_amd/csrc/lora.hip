@@ -452,8 +452,7 @@ extern "C" int dalm_lora_rowdot(const void* x, int dtype, const float* W, int w_
   DALM_REQUIRE(al16(x) && al16(W) && al16(out), DALM_E_ALIGN, "x / W / out must be 16-byte aligned");
   const DropArgs d = drop_args(p, seed, salt);
   hipStream_t s = as_stream(stream);
-  static const bool valu_only = [] { const char* e = getenv("DALM_LORA_ROWDOT_VALU"); return e && atoi(e) != 0; }();
-  if (dtype == DALM_BF16 && K % 32 == 0 && !valu_only) {
+  if (dtype == DALM_BF16 && K % 32 == 0) {
     const dim3 mgrid(static_cast<unsigned>((R + 15) / 16));
 #define DALM_ROWDOT_M(RK, DR, KM) \
     hipLaunchKernelGGL((lora_rowdot_mfma_kernel<RK, DR, KM>), mgrid, dim3(512), 0, s, static_cast<const bf16_t*>(x), W, out, \

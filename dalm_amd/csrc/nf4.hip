@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void nf4_quantize_kernel(const T* __restrict__
 // One thread per 8 consecutive weights and step; a workgroup walks STEPS consecutive tiles of 2048 weights with all its loads
 // issued before the first store (22 000 single-step workgroups of one 4-byte load + one 16-byte store each were bound by
 // workgroup dispatch, not by HBM).
-template <typename T, int STEPS, bool NTL>
+template <typename T, int STEPS>
 __global__ __launch_bounds__(256) void nf4_dequantize_kernel(const unsigned char* __restrict__ packed,
                                                              const float* __restrict__ absmax, int64_t n,
                                                              T* __restrict__ out) {
@@ -112,8 +112,7 @@ __global__ __launch_bounds__(256) void nf4_dequantize_kernel(const unsigned char
     if (e0 < n) {
       a[k] = absmax[e0 >> 6];
       if (b0 + 4 <= nbytes) {
-        const unsigned int* src = reinterpret_cast<const unsigned int*>(packed + b0);
-        word[k] = NTL ? __builtin_nontemporal_load(src) : *src;
+        word[k] = *reinterpret_cast<const unsigned int*>(packed + b0);
       } else {
         for (int j = 0; j < 4; ++j)
           if (b0 + j < nbytes) word[k] |= static_cast<unsigned int>(packed[b0 + j]) << (8 * j);
@@ -185,25 +184,21 @@ extern "C" int dalm_nf4_dequantize(const uint8_t* packed, const float* absmax, i
   DALM_REQUIRE(aligned(out, 16) && aligned(packed, 4) && aligned(absmax, 4), DALM_E_ALIGN,
                "out must be 16-byte aligned, packed / absmax 4-byte aligned");
   const int64_t threads = (n + 7) / 8;
-  static const int steps_env = [] { const char* e = getenv("DALM_NF4_STEPS"); return e ? atoi(e) : 0; }();
   // measured (profiles/history/r04_nf4_steps.txt, 8 different weights in turn inside a hipGraph): bf16 out 11008x4096 28.0 / 23.0 /
   // 21.3 / 21.7 us and 4096^2 9.3 / 9.2 / 8.6 / 8.6 us for 1 / 2 / 4 / 8 tiles per workgroup; f32 out is best at 1 (46.7 us
-  // vs 48.9 at 4: twice the store bytes per tile already); a non-temporal load of the packed words is no gain (DALM_NF4_NT=1)
-  int steps = steps_env > 0 ? steps_env : ((dtype == DALM_BF16 && threads >= 256 * 4 * 2048) ? 4 : 1);
-  if (steps != 1 && steps != 2 && steps != 8) steps = 4;
+  // vs 48.9 at 4: twice the store bytes per tile already); a non-temporal load of the packed words is no gain
+  const int steps = (dtype == DALM_BF16 && threads >= 256 * 4 * 2048) ? 4 : 1;
   const int64_t blocks = (threads + 256 * steps - 1) / (256 * steps);
   DALM_REQUIRE(blocks <= 0x7fffffffLL, DALM_E_SHAPE, "n too large for one launch");
-  static const bool ntl = [] { const char* e = getenv("DALM_NF4_NT"); return e && atoi(e) != 0; }();
-#define DALM_NF4_DEQ(TT, S) \
-  if (ntl) hipLaunchKernelGGL((nf4_dequantize_kernel<TT, S, true>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, \
-                              as_stream(stream), packed, absmax, n, static_cast<TT*>(out)); \
-  else hipLaunchKernelGGL((nf4_dequantize_kernel<TT, S, false>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, \
-                          as_stream(stream), packed, absmax, n, static_cast<TT*>(out))
-#define DALM_NF4_DEQ_S(TT) \
-  switch (steps) { case 1: DALM_NF4_DEQ(TT, 1); break; case 2: DALM_NF4_DEQ(TT, 2); break; case 8: DALM_NF4_DEQ(TT, 8); break; \
-                   default: DALM_NF4_DEQ(TT, 4); break; }
-  if (dtype == DALM_F32) { DALM_NF4_DEQ_S(float) } else { DALM_NF4_DEQ_S(unsigned short) }
-#undef DALM_NF4_DEQ_S
-#undef DALM_NF4_DEQ
+  const dim3 grid(static_cast<unsigned>(blocks));
+  if (dtype == DALM_F32)
+    hipLaunchKernelGGL((nf4_dequantize_kernel<float, 1>), grid, dim3(256), 0, as_stream(stream), packed, absmax, n,
+                       static_cast<float*>(out));
+  else if (steps == 4)
+    hipLaunchKernelGGL((nf4_dequantize_kernel<unsigned short, 4>), grid, dim3(256), 0, as_stream(stream), packed, absmax, n,
+                       static_cast<unsigned short*>(out));
+  else
+    hipLaunchKernelGGL((nf4_dequantize_kernel<unsigned short, 1>), grid, dim3(256), 0, as_stream(stream), packed, absmax, n,
+                       static_cast<unsigned short*>(out));
   return check_launch(__func__);
 }

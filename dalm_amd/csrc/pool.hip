@@ -14,8 +14,6 @@ namespace dalm {
 namespace {
 
 struct bf16_t { unsigned short v; };
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 
 template <typename T> struct HV;
 template <> struct HV<float> {
@@ -31,15 +29,9 @@ template <> struct HV<float> {
       for (int e = 0; e < 4; ++e) x[e] = (e < nvalid) ? p[e] : 0.f;
     }
   }
-  template <bool NTS = false>
   __device__ static __forceinline__ void store(float* p, int nvalid, bool vec, const float (&x)[4]) {
     if (nvalid >= 4 && vec) {
-      if (NTS) {
-        v4f v = {x[0], x[1], x[2], x[3]};
-        __builtin_nontemporal_store(v, reinterpret_cast<v4f*>(p));
-      } else {
-        *reinterpret_cast<float4*>(p) = make_float4(x[0], x[1], x[2], x[3]);
-      }
+      *reinterpret_cast<float4*>(p) = make_float4(x[0], x[1], x[2], x[3]);
     } else {
 #pragma unroll
       for (int e = 0; e < 4; ++e) if (e < nvalid) p[e] = x[e];
@@ -62,19 +54,13 @@ template <> struct HV<bf16_t> {
       for (int e = 0; e < 8; ++e) x[e] = (e < nvalid) ? bf16_to_f32(p[e].v) : 0.f;
     }
   }
-  template <bool NTS = false>
   __device__ static __forceinline__ void store(bf16_t* p, int nvalid, bool vec, const float (&x)[8]) {
     if (nvalid >= 8 && vec) {
       unsigned int w[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i)
         w[i] = pack_bf16x2(x[2 * i], x[2 * i + 1]);
-      if (NTS) {
-        v4u v = {w[0], w[1], w[2], w[3]};
-        __builtin_nontemporal_store(v, reinterpret_cast<v4u*>(p));
-      } else {
-        *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-      }
+      *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
     } else {
 #pragma unroll
       for (int e = 0; e < 8; ++e) if (e < nvalid) p[e].v = f32_to_bf16(x[e]);
@@ -352,7 +338,7 @@ __global__ __launch_bounds__(256) void pool_finish_kernel(const float* __restric
 //   du = d_emb                                  (normalize == 0)
 //   du = (d_emb - e (e . d_emb)) / |u|           (|u| >= 1e-12)
 //   du = d_emb / 1e-12                           (|u| <  1e-12: clamp_min branch)
-template <typename T, bool NTS>
+template <typename T>
 __global__ __launch_bounds__(256) void pool_bwd_kernel(const float* __restrict__ d_emb,
                                                        const float* __restrict__ emb,
                                                        const float* __restrict__ norm,
@@ -396,7 +382,7 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const float* __restrict__
     float o[VEC];
 #pragma unroll
     for (int e = 0; e < VEC; ++e) o[e] = f * g[e];
-    HV<T>::template store<NTS>(hb + static_cast<int64_t>(t) * D, nvalid, vec_ok, o);
+    HV<T>::store(hb + static_cast<int64_t>(t) * D, nvalid, vec_ok, o);
   }
 }
 
@@ -404,7 +390,7 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const float* __restrict__
 // Row-major backward for large batches: grid (TZ, B), 256 threads.  TPR threads cover one token row (NCH d-chunks each), the
 // G = 256/TPR token groups write CONSECUTIVE rows, so a workgroup streams whole contiguous rows (2-4 KB per step at D = 1024)
 // and rebuilds du once per sample slice instead of once per 64*VEC-wide d-chunk.  Needs 16-byte aligned rows (vec_ok).
-template <typename T, int NCH, bool NTS>
+template <typename T, int NCH>
 __global__ __launch_bounds__(256) void pool_bwd_rows_kernel(const float* __restrict__ d_emb,
                                                             const float* __restrict__ emb,
                                                             const float* __restrict__ norm,
@@ -458,7 +444,7 @@ __global__ __launch_bounds__(256) void pool_bwd_rows_kernel(const float* __restr
             float o[VEC];
 #pragma unroll
             for (int e = 0; e < VEC; ++e) o[e] = f[u] * gv[q][e];
-            HV<T>::template store<NTS>(hb + static_cast<int64_t>(t) * D + d, VEC, true, o);
+            HV<T>::store(hb + static_cast<int64_t>(t) * D + d, VEC, true, o);
           }
         }
       }
@@ -489,8 +475,7 @@ inline PoolPlan pool_plan(int64_t B, int64_t T, int64_t D, int vec) {
   const int64_t groups = 1024 / tpr;
   int64_t tz = 1;
   // one CU streams ~50-80 GB/s on its own: slice when a sample is more than a few microseconds of that
-  static const int64_t slice_bytes = [] { const char* e = getenv("DALM_POOL_SLICE_BYTES"); return e ? atoll(e) : (1ll << 20); }();
-  if (B < 64 && T * D * (16 / vec) >= slice_bytes) {
+  if (B < 64 && T * D * (16 / vec) >= (1ll << 20)) {
     tz = (192 + B - 1) / B;
     const int64_t tz_max = (T + 4 * groups - 1) / (4 * groups);
     if (tz > tz_max) tz = tz_max;
@@ -498,8 +483,7 @@ inline PoolPlan pool_plan(int64_t B, int64_t T, int64_t D, int vec) {
     if (tz < 1) tz = 1;
   }
   p.tz = static_cast<int>(tz);
-  static const int nt_env = [] { const char* e = getenv("DALM_POOL_NT"); return e ? atoi(e) : 0; }();
-  if (tz == 1 && tpr <= 256 && (nt_env == 256 || (nt_env == 0 && B >= 512))) p.nt = 256;
+  if (tz == 1 && tpr <= 256 && B >= 512) p.nt = 256;
   return p;
 }
 template <typename T>
@@ -602,51 +586,44 @@ extern "C" int dalm_pool_l2norm_bwd(const float* d_emb, const float* emb, const 
   // (slicing large batches further does NOT help: every workgroup first rebuilds du, and at [1200,128,1024] bf16 2 / 4 / 8
   // slices measured 91 / 123 / 192 us against 81 us for one - profiles/history/r04_pool_probe_bwd_tz.txt; large batches take the
   // row-major kernel below instead)
-  static const int tz_env = [] { const char* e = getenv("DALM_POOL_BWD_TZ"); return e ? atoi(e) : 0; }();
-  if (tz_env > 0) tz = tz_env;
   const int64_t tz_max = (T + 3) / 4;
   if (tz > tz_max) tz = tz_max;
   if (tz < 1) tz = 1;
   if (tz > 64) tz = 64;
-  // cached stores: the encoder's backward reads dh next.  DALM_POOL_BWD_NT=1 selects non-temporal stores (measured alone:
-  // 17.5 -> 13.8 us at [150,128,1024] bf16, 79 -> 84 us at B = 1200; profiles/history/r04_pool_probe.txt)
-  static const int nts_env = [] { const char* e = getenv("DALM_POOL_BWD_NT"); return e ? atoi(e) : -1; }();
-  const bool nts = nts_env > 0;
-  static const int rows_env = [] { const char* e = getenv("DALM_POOL_BWD_ROWS"); return e ? atoi(e) : -1; }();
+  // cached stores: the encoder's backward reads dh next (non-temporal stores measured alone: 17.5 -> 13.8 us at
+  // [150,128,1024] bf16, 79 -> 84 us at B = 1200; profiles/history/r04_pool_probe.txt)
   PoolPlan pl{6, 1, 1, 256, true};                 // rows kernel: TPR <= 256 threads per row, up to 4 d-chunks per thread
   const int64_t row_lanes = (D + vec - 1) / vec;
   while ((1ll << pl.tpr_log2) < row_lanes && pl.tpr_log2 < 8) ++pl.tpr_log2;
   pl.nch = static_cast<int>((row_lanes + (1ll << pl.tpr_log2) - 1) >> pl.tpr_log2);
-  const bool rows_ok = vok && pl.nch <= 4;
-  const bool rows = rows_ok && (rows_env >= 0 ? rows_env != 0 : true);
-  if (rows) {
+  if (vok && pl.nch <= 4) {
     // token slices: ~768 workgroups, at most 8 slices (measured, profiles/history/r04_pool_probe_bwd_rows.txt: [18,128,1024] bf16
     // 16.8 / 10.9 / 7.9 / 6.5 / 7.5 us for 1 / 2 / 4 / 8 / 16 slices; [1200,128,1024] 71.7 / 78.6 / 86.4 / 112 us for 1 / 2 / 4 / 8)
-    int64_t rz = tz_env > 0 ? tz_env : (768 + B - 1) / B;
-    if (tz_env <= 0 && rz > 8) rz = 8;
+    int64_t rz = (768 + B - 1) / B;
+    if (rz > 8) rz = 8;
     const int64_t groups = 256 >> pl.tpr_log2;
     const int64_t rz_max = (T + 4 * groups - 1) / (4 * groups);
     if (rz > rz_max) rz = rz_max;
     if (rz < 1) rz = 1;
     const dim3 rgrid(static_cast<unsigned>(rz), static_cast<unsigned>(B));
-#define DALM_POOL_BWD_ROWS(TT, N, S) \
-    hipLaunchKernelGGL((pool_bwd_rows_kernel<TT, N, S>), rgrid, dim3(256), 0, s, d_emb, emb, norm, inv_count, mask, \
+#define DALM_POOL_BWD_ROWS(TT, N) \
+    hipLaunchKernelGGL((pool_bwd_rows_kernel<TT, N>), rgrid, dim3(256), 0, s, d_emb, emb, norm, inv_count, mask, \
                        static_cast<int>(T), static_cast<int>(D), normalize, pl.tpr_log2, static_cast<TT*>(dh))
-#define DALM_POOL_BWD_ROWS_N(TT, S) \
-    switch (pl.nch) { case 1: DALM_POOL_BWD_ROWS(TT, 1, S); break; case 2: DALM_POOL_BWD_ROWS(TT, 2, S); break; \
-                      case 3: DALM_POOL_BWD_ROWS(TT, 3, S); break; default: DALM_POOL_BWD_ROWS(TT, 4, S); break; }
-    if (dtype == DALM_F32) { if (nts) { DALM_POOL_BWD_ROWS_N(float, true) } else { DALM_POOL_BWD_ROWS_N(float, false) } }
-    else { if (nts) { DALM_POOL_BWD_ROWS_N(bf16_t, true) } else { DALM_POOL_BWD_ROWS_N(bf16_t, false) } }
+#define DALM_POOL_BWD_ROWS_N(TT) \
+    switch (pl.nch) { case 1: DALM_POOL_BWD_ROWS(TT, 1); break; case 2: DALM_POOL_BWD_ROWS(TT, 2); break; \
+                      case 3: DALM_POOL_BWD_ROWS(TT, 3); break; default: DALM_POOL_BWD_ROWS(TT, 4); break; }
+    if (dtype == DALM_F32) { DALM_POOL_BWD_ROWS_N(float) }
+    else { DALM_POOL_BWD_ROWS_N(bf16_t) }
 #undef DALM_POOL_BWD_ROWS_N
 #undef DALM_POOL_BWD_ROWS
     return check_launch(__func__);
   }
   const dim3 grid(static_cast<unsigned>(dc), static_cast<unsigned>(B), static_cast<unsigned>(tz));
-#define DALM_POOL_BWD(TT, N) \
-  hipLaunchKernelGGL((pool_bwd_kernel<TT, N>), grid, dim3(256), 0, s, d_emb, emb, norm, inv_count, mask, \
+#define DALM_POOL_BWD(TT) \
+  hipLaunchKernelGGL((pool_bwd_kernel<TT>), grid, dim3(256), 0, s, d_emb, emb, norm, inv_count, mask, \
                      static_cast<int>(T), static_cast<int>(D), normalize, vok, static_cast<TT*>(dh))
-  if (dtype == DALM_F32) { if (nts) DALM_POOL_BWD(float, true); else DALM_POOL_BWD(float, false); }
-  else { if (nts) DALM_POOL_BWD(bf16_t, true); else DALM_POOL_BWD(bf16_t, false); }
+  if (dtype == DALM_F32) DALM_POOL_BWD(float);
+  else DALM_POOL_BWD(bf16_t);
 #undef DALM_POOL_BWD
   return check_launch(__func__);
 }

@@ -405,7 +405,7 @@ struct FlashParams {
   const float* row_coef; const float* row_lse; const float* col_coef; const float* col_lse;
   float* out;            // dA (nsplit == 1) or slabs [nsplit][m][D]
   int row_blocks, nsplit, blocks_per_split;
-  int debug_hot;         // timing experiment only (DALM_FLASH_DEBUG=1): every step re-reads the same cached rows
+  int debug_hot;         // 0 from the launcher; 1 (timing experiment only) re-reads the same cached rows every step
 };
 
 constexpr int FBM = 32, FBN = 128;
@@ -981,12 +981,8 @@ inline size_t flash_copy_floats(const FlashPlan& f, int64_t D) { return static_c
 struct StreamPlan { bool ok; int rt, row_blocks, nsplit, blocks_per_split; int64_t ldm, ldn, kpad; int ks; };
 inline StreamPlan stream_plan(int64_t m, int64_t n, int64_t D, bool always = false) {
   StreamPlan f{false, 1, 0, 1, 0, 0, 0, 0, 1};
-  static const bool off = getenv("DALM_SIM_ROWSTATS") && getenv("DALM_SIM_ROWSTATS")[0] == 'g';   // "gemm": the LDS-tiled form
-  if (off && !always) return f;
   if (!always && (m * n < 512 * 512 || D < 64)) return f;
-  static const int force_rt = getenv("DALM_STREAM_RT") ? atoi(getenv("DALM_STREAM_RT")) : 0;
-  static const int force_ks = getenv("DALM_STREAM_KS") ? atoi(getenv("DALM_STREAM_KS")) : 0;
-  f.rt = force_rt ? force_rt : ((m >= 4096) ? 2 : 1);   // measured: 2048^2 86 vs 77 TF, 4096^2 100 vs 107, 16384^2 118 vs 141
+  f.rt = (m >= 4096) ? 2 : 1;   // measured: 2048^2 86 vs 77 TF, 4096^2 100 vs 107, 16384^2 118 vs 141
   const int64_t bm = 32 * f.rt;
   f.row_blocks = static_cast<int>((m + bm - 1) / bm);
   // K slices per column tile, for the sizes whose 128-column blocks give the chip only one or two workgroups per CU
@@ -997,7 +993,6 @@ inline StreamPlan stream_plan(int64_t m, int64_t n, int64_t D, bool always = fal
   if (!always && f.rt == 1) {
     const int64_t g128 = static_cast<int64_t>(f.row_blocks) * ((n + 127) / 128);
     f.ks = (g128 >= 450 && g128 < 640) ? 4 : (g128 >= 300 && g128 < 450) ? 2 : 1;
-    if (force_ks == 1 || force_ks == 2 || force_ks == 4) f.ks = force_ks;
   }
   f.kpad = (D + 16 * f.ks - 1) / (16 * f.ks) * (16 * f.ks);
   if ((n + 128) * f.kpad * 4 >= (1ll << 31) || (m + 64) * f.kpad * 4 >= (1ll << 31)) return f;   // 32-bit buffer offsets
@@ -1093,15 +1088,11 @@ extern "C" int dalm_sim_matmul(const float* A, const float* Bm, int64_t m, int64
 }
 
 // Problems large enough for the bf16x3 form (csrc/lmhead.hip: 256 x 256 tiles, a few waves of them over the 256 CUs) go to
-// the bf16 matrix cores; DALM_SIM_BF16X3=0 keeps everything on the f32 MFMA kernels, DALM_SIM_BF16X3_MIN moves the threshold.
+// the bf16 matrix cores.
 static bool use_bf16x3(int64_t m, int64_t n, int64_t D, const float* A, const float* Bm) {
-  static const int min_rows = [] {
-    const char* off = getenv("DALM_SIM_BF16X3");
-    if (off && off[0] == '0') return -1;
-    const char* e = getenv("DALM_SIM_BF16X3_MIN");
-    return e ? atoi(e) : 3072;   // measured crossover: 2048^2 64 vs 100 TF (f32 wins), 3072^2 142 vs 122 TF (profiles/history/r04_sim_midsize_merge_inlaunch.txt)
-  }();
-  if (min_rows < 0 || m < min_rows || n < min_rows) return false;
+  // measured crossover: 2048^2 64 vs 100 TF (f32 wins), 3072^2 142 vs 122 TF (profiles/history/r04_sim_midsize_merge_inlaunch.txt)
+  constexpr int64_t min_rows = 3072;
+  if (m < min_rows || n < min_rows) return false;
   if (A && (reinterpret_cast<uintptr_t>(A) % 16 || reinterpret_cast<uintptr_t>(Bm) % 16)) return false;
   return dalm_sim_rowstats_bf16x3_supported(m, n, D) != 0;
 }
@@ -1186,15 +1177,8 @@ extern "C" int dalm_sim_rowstats_f32(const float* A, const float* Bm, int64_t m,
 }
 
 
-// Which form dalm_sim_grad takes: 1 = flash (no dS panel), 0 = dS panel + NN GEMM (D > 1024 or odd D, or
-// DALM_SIM_GRAD=panel for A/B comparisons).
+// Which form dalm_sim_grad takes: 1 = flash (no dS panel), 0 = dS panel + NN GEMM (D > 1024 or odd D).
 static bool use_flash_grad(int64_t m, int64_t n, int64_t D) {
-  static const int forced = [] {
-    const char* e = getenv("DALM_SIM_GRAD");
-    if (!e) return -1;
-    return (e[0] == 'p') ? 0 : 1;
-  }();
-  if (forced == 0) return false;
   return flash_plan(m, n, D).ok;
 }
 
@@ -1242,7 +1226,7 @@ extern "C" int dalm_sim_grad(const float* A, const float* Bm, int64_t m, int64_t
     p.row_coef = row_coef; p.row_lse = row_lse; p.col_coef = col_coef; p.col_lse = col_lse;
     p.out = f.nsplit > 1 ? slabs : dA;
     p.row_blocks = f.row_blocks; p.nsplit = f.nsplit; p.blocks_per_split = f.blocks_per_split;
-    p.debug_hot = getenv("DALM_FLASH_DEBUG") ? 1 : 0;
+    p.debug_hot = 0;
     switch (f.nt) {
       case 1: launch_flash<1>(p, s); break;
       case 2: launch_flash<2>(p, s); break;

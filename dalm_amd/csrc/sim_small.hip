@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256) void small_partial_kernel(const float* __restr
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   // 4 pairs of float4 per operand per round (32 of K).  Measured and slower on every shape (round 3): 8 pairs per round
   // (+0.7 ... +1.6 us per call), a wave's whole K range (128 = 4 rounds) in flight before its first MFMA (150 x 1200: 18.9
-  // instead of 17.0 us per call, 512^2: 21.3 instead of 20.5), more split-K workgroups (DALM_SMALL_TARGET 384 - 1024), fewer (128)
+  // instead of 17.0 us per call, 512^2: 21.3 instead of 20.5), more split-K workgroups (a target of 384 - 1024), fewer (128)
   constexpr int NU = 4;
   for (int k0 = k_lo; k0 < k_hi; k0 += 8 * NU) {
     float4 av[NU], bv[NU];
@@ -731,11 +731,10 @@ __global__ __launch_bounds__(1024) void rag_loss_finalize_kernel(const float* __
 
 inline int64_t round_up(int64_t x, int64_t q) { return (x + q - 1) / q * q; }
 
-constexpr int kDefaultPipeDepth = 4;     // measured: profiles/history/r04_small_pipe.txt (512^2 -8 %, 150 x 1200 -4 %; depth 2-4 alike)
 struct SmallPlan { int sk, k_chunk; int64_t ldn, ldm; };
 inline SmallPlan small_plan(int64_t m, int64_t n, int64_t D) {
   const int64_t tiles = ((m + 31) / 32) * ((n + 31) / 32);
-  static const int64_t target = getenv("DALM_SMALL_TARGET") ? atoi(getenv("DALM_SMALL_TARGET")) : 256;   // workgroups aimed at
+  constexpr int64_t target = 256;               // workgroups aimed at
   int64_t sk = (target + tiles - 1) / tiles;
   const int64_t sk_max = (D + 31) / 32;        // every workgroup gets at least 32 of K (8 per wave)
   if (sk > SK_MAX) sk = SK_MAX;
@@ -784,17 +783,16 @@ extern "C" int dalm_sim_small_fwd(const float* A, const float* Bm, int64_t m, in
   const int tiles_m = static_cast<int>((m + 31) / 32), tiles_n = static_cast<int>((n + 31) / 32);
   const dim3 pgrid(static_cast<unsigned>(tiles_m * tiles_n), static_cast<unsigned>(pl.sk));
   // pipelined form: the split covers K exactly and a wave's share is 4 or 8 whole rounds of 32 (D = 1024 with 1 or 2
-  // slices: 512^2 ... 1024^2 on one GPU, the 150 x 1200 per-rank blocks); DALM_SMALL_PIPE = 0 (off) | 2 | 3 | 4 = rounds in flight
-  static const int pipe_depth = getenv("DALM_SMALL_PIPE") ? atoi(getenv("DALM_SMALL_PIPE")) : kDefaultPipeDepth;
+  // slices: 512^2 ... 1024^2 on one GPU, the 150 x 1200 per-rank blocks), 4 rounds in flight (measured:
+  // profiles/history/r04_small_pipe.txt, 512^2 -8 %, 150 x 1200 -4 %; depth 2-4 alike)
   const int rounds = (pl.k_chunk % 128 == 0 && static_cast<int64_t>(pl.k_chunk) * pl.sk == D) ? pl.k_chunk / 128 : 0;
   const bool fast = vec16(A, D) && vec16(Bm, D) && D % 8 == 0;
   const FusedFwd none{};
-#define DALM_PIPE(R, DP) hipLaunchKernelGGL((small_partial_pipe_kernel<R, DP>), pgrid, dim3(256), 0, s, A, Bm, static_cast<int>(m), \
+#define DALM_PIPE(R) hipLaunchKernelGGL((small_partial_pipe_kernel<R, 4>), pgrid, dim3(256), 0, s, A, Bm, static_cast<int>(m), \
     static_cast<int>(n), static_cast<int>(D), pl.k_chunk, tiles_n, slab, static_cast<int>(pl.ldn), slabT, static_cast<int>(pl.ldm), none)
-  if (fast && pipe_depth >= 2 && (rounds == 4 || rounds == 8)) {
-    if (rounds == 4) { if (pipe_depth == 2) DALM_PIPE(4, 2); else if (pipe_depth == 3) DALM_PIPE(4, 3); else DALM_PIPE(4, 4); }
-    else { if (pipe_depth == 2) DALM_PIPE(8, 2); else if (pipe_depth == 3) DALM_PIPE(8, 3); else DALM_PIPE(8, 4); }
-  } else if (fast)
+  if (fast && rounds == 4) DALM_PIPE(4);
+  else if (fast && rounds == 8) DALM_PIPE(8);
+  else if (fast)
 #undef DALM_PIPE
     hipLaunchKernelGGL(small_partial_kernel<true>, pgrid, dim3(256), 0, s, A, Bm, static_cast<int>(m),
                        static_cast<int>(n), static_cast<int>(D), pl.k_chunk, tiles_n, 1, 1, slab,

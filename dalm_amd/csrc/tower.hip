@@ -394,7 +394,7 @@ __global__ __launch_bounds__(256) void rms_norm_bwd_kernel(const T* __restrict__
   }
 }
 
-// Second form (bf16; the default since round 5, DALM_RMS_BWD_V2=0 selects the first): the three streams of a row (dy, h, and
+// Second form (bf16 rows of up to 8 chunks per lane; the first form takes wider rows): the three streams of a row (dy, h, and
 // the residual-path gradient) are requested as raw 16-byte chunks BEFORE the wave reduction - 3 NCH loads in flight per lane
 // instead of 2 NCH, then NCH after the reduction - and decoded twice (raw data in registers instead of f32 copies).
 // [4608, 4096] bf16, 151 MB: 26.2 -> 23.4 us (profiles/r05_tower_attempts.txt).
@@ -642,7 +642,7 @@ extern "C" int dalm_rms_norm_bwd(const void* dy, const void* h, const void* w, c
                                 static_cast<const float*>(w), rstd, static_cast<const float*>(dres), static_cast<float*>(dx), Ri, Di);
     else DALM_RMS_DISPATCH(rms_norm_bwd_kernel, float, false, static_cast<const float*>(dy), static_cast<const float*>(h),
                            static_cast<const float*>(w), rstd, static_cast<const float*>(nullptr), static_cast<float*>(dx), Ri, Di);
-  } else if (static const bool v2 = [] { const char* e = getenv("DALM_RMS_BWD_V2"); return !e || atoi(e) != 0; }(); v2 && nch <= 8) {
+  } else if (nch <= 8) {
 #define DALM_RMS_V2(ADDV, DRES)                                                                                           \
     do {                                                                                                                  \
       if (nch <= 1) hipLaunchKernelGGL((rms_norm_bwd_v2_kernel<1, ADDV>), grid, dim3(256), 0, as_stream(stream), static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(h), static_cast<const bf16_t*>(w), rstd, DRES, static_cast<bf16_t*>(dx), Ri, Di); \

@@ -232,7 +232,6 @@ def lora_linear(x, base: torch.nn.Linear, a: torch.Tensor, b: torch.Tensor, scal
 # round 5: stacked kernels (dalm_lora2_*), bf16 activations
 # =====================================================================================================================
 _tickets2: Dict[tuple, torch.Tensor] = {}
-_FWD_STACKED = __import__("os").environ.get("DALM_LORA_FWD_STACKED", "0") == "1"      # A/B: mode 2 in the forward
 
 
 def _colacc_tickets(dev: torch.device, words: int) -> torch.Tensor:
@@ -340,9 +339,7 @@ class _LoRAGroupFn(torch.autograd.Function):
                 # both adapters in one launch.  Mode 3 with the SAME x in both slots (16-row tiles, the second read of x comes
                 # from the caches) measured faster than mode 2's 8-row stacked tiles, which pull all of A_q and A_v through every
                 # workgroup: 37 vs 45 us at [4608, 4096] with dropout (profiles/r05_lora_bench_4608x4096.txt)
-                fwd_mode = 2 if (rank == 8 and _FWD_STACKED) else 3
-                z, bt = rowdot2([x2, x2], [As[grp[0]], As[grp[1]]], rank, 1.0 / (1.0 - p), p, [meta[grp[0]][2], meta[grp[1]][2]],
-                                fwd_mode)
+                z, bt = rowdot2([x2, x2], [As[grp[0]], As[grp[1]]], rank, 1.0 / (1.0 - p), p, [meta[grp[0]][2], meta[grp[1]][2]], 3)
                 zs[grp[0]], zs[grp[1]], bits[grp[0]], bits[grp[1]] = z[0], z[1], bt[0], bt[1]
             else:
                 for i in grp:

@@ -188,9 +188,6 @@ class HipOps:
     def sim_small_supported(self, m: int, n: int, D: int) -> bool:
         return bool(hip.load().dalm_sim_small_supported(int(m), int(n), int(D)))
 
-    # one launch (dalm_sim_small_fwd1) or two (dalm_sim_small_fwd): by shape, as measured (dalm_sim_small_fwd1_preferred,
-    # profiles/history/r04_small_one_launch.txt); DALM_SMALL_FWD1 = 1 / 0 forces either
-    small_one_launch = {"1": True, "0": False}.get(os.environ.get("DALM_SMALL_FWD1", ""), None)
     _tickets: dict = {}
 
     def _small_tickets(self, dev: torch.device, words: int) -> torch.Tensor:
@@ -208,7 +205,9 @@ class HipOps:
 
     def sim_small_fwd(self, A: torch.Tensor, Bm: torch.Tensor, scale: float, diag_offset: int, want_cols: bool,
                       one_launch: Optional[bool] = None):
-        """S = scale*A.B^T (saved), row_lse, diag and (want_cols) col_lse = logsumexp over rows."""
+        """S = scale*A.B^T (saved), row_lse, diag and (want_cols) col_lse = logsumexp over rows.  One launch
+        (dalm_sim_small_fwd1) or two (dalm_sim_small_fwd): by shape unless `one_launch` says, as measured
+        (dalm_sim_small_fwd1_preferred, profiles/history/r04_small_one_launch.txt)."""
         dev = hip.require_gpu(A, Bm)
         A, Bm = hip.as_f32c(A), hip.as_f32c(Bm)
         m, D = A.shape
@@ -218,8 +217,6 @@ class HipOps:
         row_lse = torch.empty((m,), device=dev, dtype=torch.float32)
         diag = torch.empty((m,), device=dev, dtype=torch.float32)
         col_lse = torch.empty((n,), device=dev, dtype=torch.float32) if want_cols else None
-        if one_launch is None:
-            one_launch = self.small_one_launch
         if one_launch is None:
             one_launch = bool(lib.dalm_sim_small_fwd1_preferred(m, n, D))
         if one_launch:
@@ -235,13 +232,10 @@ class HipOps:
                  hip.ptr(row_lse), hip.ptr(diag), hip.ptr(col_lse), hip.ptr(ws), ws_bytes, hip.stream())
         return S, row_lse, diag, col_lse
 
-    # sliced backward (one direction of a long contraction): slices summed in the launch (dalm_sim_small_bwd1) or by a
-    # second kernel (dalm_sim_small_bwd_ws); DALM_SMALL_BWD1 = 1 / 0, default decided by measurement
-    # (profiles/history/r04_small_one_launch.txt)
-    small_bwd_one_launch = os.environ.get("DALM_SMALL_BWD1", "1") == "1"
-
+    # sliced backward (one direction of a long contraction): slices summed in the launch (dalm_sim_small_bwd1, the default,
+    # decided by measurement: profiles/history/r04_small_one_launch.txt) or by a second kernel (dalm_sim_small_bwd_ws)
     def sim_small_bwd(self, S, A, Bm, scale: float, diag_offset: int, row_coef, row_lse, col_coef, col_lse,
-                      want_dA: bool = True, want_dB: bool = True, one_launch: Optional[bool] = None):
+                      want_dA: bool = True, want_dB: bool = True, one_launch: bool = True):
         """(dA, dB) = (scale dS.B, scale dS^T.A) from the saved S; the closed-form dS of include/dalm_hip.h."""
         dev = hip.require_gpu(S, A, Bm, row_coef, row_lse, col_coef, col_lse)
         A, Bm, S = hip.as_f32c(A), hip.as_f32c(Bm), hip.as_f32c(S)
@@ -252,8 +246,6 @@ class HipOps:
         dA = torch.empty((m, D), device=dev, dtype=torch.float32) if want_dA else None
         dB = torch.empty((n, D), device=dev, dtype=torch.float32) if want_dB else None
         lib = hip.load()
-        if one_launch is None:
-            one_launch = self.small_bwd_one_launch
         ws_bytes = lib.dalm_sim_small_bwd1_workspace_bytes(m, n, D, int(want_dA), int(want_dB)) if one_launch else 0
         if one_launch and ws_bytes:        # sliced: the last slice of every output tile adds the slices (one launch)
             ws = torch.empty((ws_bytes // 4,), device=dev, dtype=torch.float32)

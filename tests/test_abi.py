@@ -95,6 +95,19 @@ def test_package_never_imports_oracle():
         assert "dalm_oracle" not in src and "import oracle" not in src and "from oracle" not in src, py
 
 
+def test_launchers_read_only_the_reference_switches():
+    """The launchers pick every kernel by shape and dtype.  The environment reads left in the HIP sources are the switches
+    committed tests use as a reference: the first attention forms and the top-k first pass."""
+    csrc = ROOT / "dalm_amd" / "csrc"
+    names = set()
+    for src in sorted([*csrc.glob("*.hip"), *csrc.glob("*.hpp")]):
+        calls = re.findall(r"\bgetenv\s*\(([^)]*)\)", src.read_text())
+        literal = [re.fullmatch(r'\s*"([A-Za-z0-9_]+)"\s*', c) for c in calls]
+        assert all(literal), (src.name, calls)
+        names.update(m.group(1) for m in literal)
+    assert names == {"DALM_ATTN_FWD", "DALM_ATTN_DKDV", "DALM_TOPK_BF16X3"}
+
+
 def test_header_is_plain_c(tmp_path):
     """include/dalm_hip.h must be consumable by a C compiler (cgo / JNI / ctypes-style bindings): compile a C
     translation unit that includes it and takes the address of every entry point."""

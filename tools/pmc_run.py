@@ -1,5 +1,5 @@
 """Run a command under rocprofv3 --pmc, one pass per counter group, and print per-kernel means keyed on (kernel, grid).
-    python tools/pmc_run.py OUTDIR "TCC_HIT_sum TCC_MISS_sum" "FETCH_SIZE" "MfmaUtil" -- python tools/lm_head_ablate.py 0
+    python tools/pmc_run.py OUTDIR "TCC_HIT_sum TCC_MISS_sum" "FETCH_SIZE" "MfmaUtil" -- python tools/lm_head_kernel_bench.py
 Kernel names are matched against $PMC_MATCH (regex, default: everything)."""
 import csv
 import glob

@@ -26,7 +26,6 @@ def main():
     ops = default_ops()
     dev = torch.device("cuda:0")
     sizes = [int(x) for x in sys.argv[1:]] or [4096, 8192, 16384]
-    print(f"# DALM_X3_GRAD_BLOCK = {os.environ.get('DALM_X3_GRAD_BLOCK', 'adaptive: 2048 ... 8192 by the size of the dS image (default)')}")
     for m in sizes:
         n, D = m, 1024
         A = torch.nn.functional.normalize(torch.randn(m, D, device=dev), dim=1)
