@@ -15,21 +15,21 @@ Both read the mask as packed bits (packed once per mask tensor - every layer pas
 
 Attention dropout (BERT's attention_probs_dropout_prob in training mode) is applied inside the kernels, its keep mask regenerated
 from (a device seed word, a per-call salt, the element index) and never stored - this library's own generator
-(oracle/attn_dropout.py), not torch's philox stream.  DALM_ATTN_DROPOUT=0 sends dropout calls to torch (needed under activation
-recompute, torch.utils.checkpoint: the salt is a host call counter, a re-run forward would draw another mask).
+(oracle/attn_dropout.py), not torch's philox stream.  Not supported under activation recompute (torch.utils.checkpoint): the
+salt is a host call counter, a re-run forward would draw another mask.
 Everything the kernels do not take (CPU tensors, other head widths, odd T with dropout, float masks, a KV cache, no gradient wanted) goes
 to transformers' own `sdpa_attention_forward`, unchanged.  DALM_ATTN_KERNEL=0 keeps the model on "sdpa".
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Optional
 
 import torch
 
 from .. import hip
 from ..packed import packed_of
+from .fastpath import _off
 from .lora import dropout_uid
 
 NAME = "dalm_sdpa"
@@ -113,7 +113,7 @@ def _attn_forward(q, k, v, pk, scale, causal, drop=(0.0, None, 0)):
                  sq.nseq, H, sq.T, hd, float(scale), (C.c_int64 * 12)(*flat), float(drop[0]), hip.ptr(drop[1]),
                  int(drop[2]) & 0xFFFFFFFF, hip.ptr(out), hip.ptr(lse), hip.stream())
         return out, lse
-    if os.environ.get("DALM_ATTN_FWD_KERNEL", "1") == "0" and drop[0] == 0.0:    # torch's memory-efficient forward + its log-sum-exp
+    if _off("DALM_ATTN_FWD_KERNEL") and drop[0] == 0.0:    # torch's memory-efficient forward + its log-sum-exp
         out, lse, _, _ = torch.ops.aten._scaled_dot_product_efficient_attention(
             q, k, v, _torch_bias(pk, B, H, T, q.dtype, q.device), True, 0.0, causal, scale=scale)
         return out, lse
@@ -241,7 +241,7 @@ def supported(query, key, value, mask, dropout, causal, kwargs) -> bool:
         return False                                 # a KV cache (kv length != q length) or grouped heads left unexpanded
     if query.shape[2] < 2 or query.shape[2] > 2048 or kwargs.get("position_bias") is not None:
         return False
-    if dropout != 0.0 and not (0.0 < dropout < 1.0 and query.shape[2] % 2 == 0 and os.environ.get("DALM_ATTN_DROPOUT", "1") != "0"):
+    if dropout != 0.0 and not (0.0 < dropout < 1.0 and query.shape[2] % 2 == 0):
         return False                                 # the in-kernel mask pairs elements (i, j), (i, j + 1): even T
     if not (torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad)):
         return False                                 # nothing to differentiate: torch's fused forward alone is the best path
@@ -260,9 +260,9 @@ def packed_supported(query, key, value, dropout: float = 0.0) -> bool:
     if query.dim() != 4 or query.shape[0] != 1 or query.shape[-1] not in _HEAD_DIMS or key.shape != query.shape \
             or value.shape != query.shape:
         return False
-    if dropout != 0.0 and not (0.0 < dropout < 1.0 and os.environ.get("DALM_ATTN_DROPOUT", "1") != "0"):
+    if dropout != 0.0 and not 0.0 < dropout < 1.0:
         return False
-    return _views_ok(query, key, value) and os.environ.get("DALM_ATTN_KERNEL", "1") != "0"
+    return _views_ok(query, key, value) and not _off("DALM_ATTN_KERNEL")
 
 
 def _packed_sdpa_torch(query, key, value, seqs, scale: float, dropout: float):
@@ -319,7 +319,7 @@ def dalm_sdpa_attention_forward(module, query, key, value, attention_mask, dropo
     causal = bool(query.shape[2] > 1 and attention_mask is None
                   and (is_causal if is_causal is not None else getattr(module, "is_causal", True)))
     k2, v2 = (repeat_kv(key, groups), repeat_kv(value, groups)) if (groups > 1 and key.shape[1] != query.shape[1]) else (key, value)
-    if os.environ.get("DALM_ATTN_KERNEL", "1") == "0" or not supported(query, k2, v2, attention_mask, dropout, causal, kwargs):
+    if _off("DALM_ATTN_KERNEL") or not supported(query, k2, v2, attention_mask, dropout, causal, kwargs):
         return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling,
                                       is_causal=is_causal, **kwargs)
     scale = float(scaling) if scaling is not None else float(query.shape[-1]) ** -0.5
@@ -367,7 +367,7 @@ def sdpa(query, key, value, mask, scale: float, causal: bool, dropout_p: float =
 
 def use_hip_attention_backward(model: torch.nn.Module) -> bool:
     """Switch a Llama-family model (head width 64 or 128) from "sdpa" to "dalm_sdpa".  DALM_ATTN_KERNEL=0 disables."""
-    if os.environ.get("DALM_ATTN_KERNEL", "1") == "0":
+    if _off("DALM_ATTN_KERNEL"):
         return False
     cfg = getattr(model, "config", None)
     if cfg is None or getattr(cfg, "_attn_implementation", None) != "sdpa":

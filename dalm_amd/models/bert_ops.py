@@ -12,11 +12,9 @@ node, its gradient is added to y32's in the backward kernel.
 
 Dropout (BERT's hidden_dropout_prob, training mode) comes from this library's generator (seed word + salt + element index, mask
 kept as bits; oracle/lora_mask.py::keep_mask_v2) - torch's philox stream has no reference to match.  Needs its own RNG state to be
-re-run: not supported under activation recompute (DALM_BERT_KERNELS=0 restores transformers' modules).
+re-run: not supported under activation recompute.
 """
 from __future__ import annotations
-
-import os
 
 import torch
 
@@ -83,8 +81,6 @@ class _BertAddNorm(torch.autograd.Function):
 
 def supported(a: torch.Tensor, res: torch.Tensor, ln: torch.nn.Module) -> bool:
     """bf16 dense output + f32 residual (what bf16 autocast produces), a frozen affine LayerNorm over the last dimension."""
-    if os.environ.get("DALM_BERT_KERNELS", "1") == "0":
-        return False
     w, b = getattr(ln, "weight", None), getattr(ln, "bias", None)
     if not isinstance(ln, torch.nn.LayerNorm) or w is None or b is None or w.requires_grad or b.requires_grad:
         return False

@@ -5,7 +5,7 @@ chains of a Llama-family layer the step spent the most launches on (rotary embed
 ~7 eager elementwise kernels forward and ~10 backward (upcast, pow, mean, rsqrt, mul, downcast, mul).
 `torch.nn.functional.rms_norm` computes the same `w * x * rsqrt(mean(x^2) + eps)` (fp32 internally) in
 one fused kernel each way: 458 -> 124 us per norm (fwd+bwd, [4608, 4096] bf16 on MI355X), about 22 ms of
-a 230 ms cfg3 step.  Differences are bf16 rounding-order only (max 1 bf16 ulp).  DALM_NATIVE_NORM=0 disables.
+a 230 ms cfg3 step.  Differences are bf16 rounding-order only (max 1 bf16 ulp).
 """
 from __future__ import annotations
 
@@ -14,6 +14,12 @@ import types
 
 import torch
 import torch.nn.functional as F
+
+
+def _off(name: str) -> bool:
+    """True when the environment sets the reference switch `name` to "0".  Read at call time: the tests that build a
+    "kernels off" model flip these around installer calls and between two forward calls of one process."""
+    return os.environ.get(name, "1") == "0"
 
 
 _warned = set()
@@ -43,8 +49,6 @@ def _native_forward(self, hidden_states: torch.Tensor) -> torch.Tensor:
 
 def use_native_rms_norm(model: torch.nn.Module) -> int:
     """Patch every `*RMSNorm` module with a plain weight vector; returns how many were patched."""
-    if os.environ.get("DALM_NATIVE_NORM", "1") == "0":
-        return 0
     n = 0
     for mod in model.modules():
         if not type(mod).__name__.endswith("RMSNorm"):
@@ -101,7 +105,7 @@ def _rope_hip(q, k, cos, sin, position_ids=None, unsqueeze_dim=1):
     """transformers' apply_rotary_pos_emb as one HIP launch for q and k together (`dalm_rope_qk`, one more in the backward),
     rounding where the eager chain rounds: same values and gradients as transformers' own code (round 4; the roll + addcmul
     form above was 6 launches forward / 8 backward per layer and rounded once less than transformers does).
-    DALM_ROPE_KERNEL=0 keeps the roll form; CPU tensors and layouts the kernel does not take use it as well."""
+    CPU tensors and layouts the kernel does not take use the roll form."""
     from . import tower_ops
 
     if unsqueeze_dim == 1 and tower_ops.rope_supported(q, k, cos, sin):
@@ -111,9 +115,8 @@ def _rope_hip(q, k, cos, sin, position_ids=None, unsqueeze_dim=1):
 
 def use_roll_rope(model: torch.nn.Module) -> bool:
     """Swap the module-level apply_rotary_pos_emb of the model's own modeling file (Llama and Falcon)."""
-    if os.environ.get("DALM_FAST_ROPE", "1") == "0":
+    if _off("DALM_FAST_ROPE"):
         return False
-    fn = _rope_roll if os.environ.get("DALM_ROPE_KERNEL", "1") == "0" else _rope_hip
     import importlib
 
     mod_name = type(getattr(model, "base_model", model)).__module__
@@ -123,26 +126,26 @@ def use_roll_rope(model: torch.nn.Module) -> bool:
     mod = importlib.import_module(mod_name)
     if not hasattr(mod, "apply_rotary_pos_emb"):
         return False
-    if getattr(mod.apply_rotary_pos_emb, "__name__", "") not in ("_rope_roll", "_rope_hip"):
+    if getattr(mod.apply_rotary_pos_emb, "__name__", "") != "_rope_hip":
         mod._dalm_orig_apply_rotary_pos_emb = mod.apply_rotary_pos_emb
     # Run-time guard: the function being replaced must BE the formula the kernel implements.  The swap is
     # PROCESS-WIDE (transformers resolves apply_rotary_pos_emb through the modeling file's globals; there is no per-model
     # hook), so every model of this modeling file in the process takes the replacement.
     dev = next((p.device for p in model.parameters()), torch.device("cpu"))
-    if not _rope_matches(mod._dalm_orig_apply_rotary_pos_emb, fn, dev):
+    if not _rope_matches(mod._dalm_orig_apply_rotary_pos_emb, dev):
         _warn_once("rope:" + mod_name, f"{mod_name}.apply_rotary_pos_emb is not x * cos + rotate_half(x) * sin here: "
                    "transformers' own code stays in place")
         mod.apply_rotary_pos_emb = mod._dalm_orig_apply_rotary_pos_emb
         return False
-    mod.apply_rotary_pos_emb = fn
+    mod.apply_rotary_pos_emb = _rope_hip
     return True
 
 
-def _rope_matches(orig, repl, dev: torch.device) -> bool:
-    """orig(q, k, cos, sin) against the replacement on small random tensors: on the CPU against the roll form in float32 (the
+def _rope_matches(orig, dev: torch.device) -> bool:
+    """orig(q, k, cos, sin) against `_rope_hip` on small random tensors: on the CPU against the roll form in float32 (the
     same formula, one fused multiply-add apart), on a GPU additionally against the HIP kernel in bfloat16 - there the values
     must be EQUAL (tests/test_tower_ops_gpu.py asserts the same)."""
-    key = ("rope", orig, repl, dev.type)
+    key = ("rope", orig, dev.type)
     if key in _checked:
         return _checked[key]
     g = torch.Generator().manual_seed(0)
@@ -155,7 +158,7 @@ def _rope_matches(orig, repl, dev: torch.device) -> bool:
             want = orig(q, k, cos, sin)
             got = _rope_roll(q, k, cos, sin)
             ok = all(_close(a, b, 8.0) for a, b in zip(got, want))
-            if ok and dev.type == "cuda" and repl is _rope_hip:
+            if ok and dev.type == "cuda":
                 args = [t.to(dev, torch.bfloat16) for t in (q, k, cos, sin)]
                 ok = all(torch.equal(a, b) for a, b in zip(_rope_hip(*args), orig(*args)))
     except Exception:
@@ -183,7 +186,7 @@ def use_swiglu_kernel(model: torch.nn.Module) -> int:
     act = SiLU - to evaluate silu(gate) * up through `dalm_swiglu_{fwd,bwd}`: 2 eager launches forward and 4 backward
     become 1 + 1, and the [tokens, intermediate] activation is recomputed instead of saved (101 MB per layer at cfg3).
     Same rounding points as the eager chain.  DALM_SWIGLU_KERNEL=0 disables; returns how many modules were patched."""
-    if os.environ.get("DALM_SWIGLU_KERNEL", "1") == "0":
+    if _off("DALM_SWIGLU_KERNEL"):
         return 0
     n = 0
     for mod in model.modules():
@@ -250,8 +253,7 @@ def use_capturable_falcon_heads(model: torch.nn.Module) -> int:
         mod._split_heads = types.MethodType(_split_heads_sliced, mod)
         # multi-query + SDPA with [B, 1, T, hd] keys falls back to torch's unfused "math" path - f32 scores, softmax, masks:
         # ~1.5 ms per layer at cfg5, 48 ms of a 230 ms step (profiles/r05cfg5_step_by_stream_before.txt).
-        # DALM_FALCON_EXPAND_KV=0 keeps the [B, 1, T, hd] form.
-        mod._dalm_expand_kv = (os.environ.get("DALM_FALCON_EXPAND_KV", "1") != "0" and getattr(mod, "num_kv_heads", None) == 1
+        mod._dalm_expand_kv = (getattr(mod, "num_kv_heads", None) == 1
                                and getattr(getattr(mod, "config", None), "_attn_implementation", None) == "sdpa")
         n += 1
     return n
@@ -301,7 +303,7 @@ def _falcon_layer_forward(self, hidden_states, alibi, attention_mask, position_i
 def use_falcon_layer_kernels(model: torch.nn.Module) -> int:
     """Patch FalconDecoderLayer / FalconMLP modules of the 7B flavour whose code is the one this file was written against
     (signature and source checked once per class).  DALM_FALCON_KERNELS=0 disables.  Returns how many layers were patched."""
-    if os.environ.get("DALM_FALCON_KERNELS", "1") == "0":
+    if _off("DALM_FALCON_KERNELS"):
         return 0
     n = 0
     for mod in model.modules():
@@ -399,9 +401,7 @@ def _bert_output_forward(self, hidden_states: torch.Tensor, input_tensor: torch.
 
 def use_bert_layer_kernels(model: torch.nn.Module) -> int:
     """Patch BertSelfOutput / BertOutput modules whose forward is the three statements above (source checked once per class) and
-    whose LayerNorm is frozen.  DALM_BERT_KERNELS=0 disables.  Returns how many modules were patched."""
-    if os.environ.get("DALM_BERT_KERNELS", "1") == "0":
-        return 0
+    whose LayerNorm is frozen.  Returns how many modules were patched."""
     n = 0
     for mod in model.modules():
         if type(mod).__name__ not in ("BertSelfOutput", "BertOutput"):
@@ -454,7 +454,7 @@ def _falcon_attention_forward(self, hidden_states, alibi, attention_mask, positi
 
     orig = self._dalm_orig_attn_forward
     if (alibi is not None or layer_past is not None or output_attentions or position_embeddings is None
-            or getattr(self.config, "_attn_implementation", None) != "sdpa" or os.environ.get("DALM_ATTN_KERNEL", "1") == "0"):
+            or getattr(self.config, "_attn_implementation", None) != "sdpa" or _off("DALM_ATTN_KERNEL")):
         return orig(hidden_states, alibi, attention_mask, position_ids=position_ids, layer_past=layer_past, use_cache=use_cache,
                     output_attentions=output_attentions, position_embeddings=position_embeddings, **kwargs)
     fused_qkv = self.query_key_value(hidden_states)
@@ -463,9 +463,9 @@ def _falcon_attention_forward(self, hidden_states, alibi, attention_mask, positi
     batch_size, query_length, _, _ = query_layer.shape
     cos, sin = position_embeddings
     is_causal = bool(self.is_causal and attention_mask is None and query_length > 1)
-    rope_on = os.environ.get("DALM_ROPE_KERNEL", "1") != "0" and os.environ.get("DALM_FAST_ROPE", "1") != "0"
+    rope_on = not _off("DALM_FAST_ROPE")
     mqa = bool(getattr(self, "_dalm_expand_kv", False) and num_kv_heads == 1 and key_layer.shape[2] == 1)
-    if mqa and rope_on and os.environ.get("DALM_FALCON_MQA_VIEWS", "1") != "0":
+    if mqa and rope_on:
         # multi-query, THIS call only (training, no KV cache): the ONE shared key / value head stays one head in memory.  The
         # rotation runs on the single key head, the attention kernels read key / value through stride-0 head views (every head
         # the same rows, served by the caches) - the 71 copies of K and V that the broadcast-then-reshape form materialises per
@@ -531,7 +531,7 @@ def _falcon_attention_forward(self, hidden_states, alibi, attention_mask, positi
 def use_falcon_attention_kernels(model: torch.nn.Module) -> int:
     """Patch FalconAttention modules (head width 64 or 128, no alibi) whose forward is the code `_falcon_attention_forward`
     restates (signature and statements checked once per class).  DALM_ATTN_KERNEL=0 disables.  Returns the count."""
-    if os.environ.get("DALM_ATTN_KERNEL", "1") == "0":
+    if _off("DALM_ATTN_KERNEL"):
         return 0
     n = 0
     for mod in model.modules():
@@ -586,8 +586,7 @@ def _llama_attention_forward(self, hidden_states, position_embeddings=None, atte
     cfg = self.config
     if (past_key_values is not None or position_embeddings is None or getattr(cfg, "_attn_implementation", None) != attention.NAME
             or (self.training and float(getattr(self, "attention_dropout", 0.0)) != 0.0)
-            or os.environ.get("DALM_ROPE_KERNEL", "1") == "0" or os.environ.get("DALM_FAST_ROPE", "1") == "0"
-            or os.environ.get("DALM_ATTN_KERNEL", "1") == "0" or kwargs.get("output_attentions")):
+            or _off("DALM_FAST_ROPE") or _off("DALM_ATTN_KERNEL") or kwargs.get("output_attentions")):
         return self._dalm_orig_attn_forward(hidden_states, position_embeddings=position_embeddings, attention_mask=attention_mask,
                                             past_key_values=past_key_values, **kwargs)
     input_shape = hidden_states.shape[:-1]
@@ -701,7 +700,7 @@ def _llama_layer_forward(self, hidden_states, attention_mask=None, position_ids=
 def use_fused_residual_norm(model: torch.nn.Module) -> int:
     """Patch LlamaDecoderLayer modules whose forward has the signature this file was written against (transformers 5.x);
     DALM_NORM_KERNEL=0 disables.  Returns how many layers were patched."""
-    if os.environ.get("DALM_NORM_KERNEL", "1") == "0":
+    if _off("DALM_NORM_KERNEL"):
         return 0
     import inspect
 

@@ -7,24 +7,21 @@ slower than the forward's ("TN"): measured at the cfg3 shapes with the tuned sol
     down_proj 376.1 us       ->  327.3 us        gate/up_proj 349.6 us -> 334.7 us
 A frozen weight never changes, so the copy W^T [K, N] is made once (lazily, on the weight's device; +1x the frozen weights'
 bytes - 13.5 GB for Llama-2-7b in bf16, on a 288 GB GPU) and the backward becomes F.linear(g, W^T).  Same values as autograd's
-own backward up to the summation order inside the library's kernel.  DALM_DGRAD_T=0 disables (no copies are made).
+own backward up to the summation order inside the library's kernel.
 
 Nothing in transformers is patched: frozen `nn.Linear` modules get the subclass below by class swap (same parameters, same
 state_dict keys); trainable weights, CPU tensors and inference keep `nn.Linear.forward`.
 """
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import torch
 import torch.nn.functional as F
 
-_ENABLED = os.environ.get("DALM_DGRAD_T", "1") != "0"
-
 
 def enabled() -> bool:
-    return _ENABLED
+    return True
 
 
 import weakref
@@ -36,11 +33,11 @@ _WT_CACHE: dict = {}
 
 
 def dgrad_weight(w: torch.Tensor, dtype: Optional[torch.dtype] = None) -> Optional[torch.Tensor]:
-    """W^T [K, N], contiguous, in `dtype` (default: w's own); None when disabled, when w is trainable or not on a GPU, when the
+    """W^T [K, N], contiguous, in `dtype` (default: w's own); None when w is trainable or not on a GPU, when the
     copy would not fit comfortably (free HBM < 4 x its size: the backward then runs on W as stored), or when the first request
     for it comes from inside a hipGraph capture (an allocation that must outlive the graph's pool).  The cache is keyed by the
     weight's storage, version, device and dtype: a reloaded or moved weight gets a fresh copy."""
-    if not _ENABLED or w.requires_grad or not w.is_cuda or w.dim() != 2:
+    if w.requires_grad or not w.is_cuda or w.dim() != 2:
         return None
     dtype = dtype or w.dtype
     key = (w.data_ptr(), w._version, w.device, dtype, tuple(w.shape))
@@ -141,14 +138,14 @@ class _FrozenPairFn(torch.autograd.Function):
 # ---------------------------------------------------------------------------------------------------------------------
 # two frozen projections of one input as ONE forward GEMM: x [W0 | W1]^T
 # ---------------------------------------------------------------------------------------------------------------------
-_CAT = os.environ.get("DALM_CAT_GEMM", "1") != "0"
+_CAT = True            # tests clear it to build their two-GEMM reference
 
 
 def _cat_weights(m0: torch.nn.Linear, m1: torch.nn.Linear) -> Optional[torch.Tensor]:
     """[W0; W1] as ONE contiguous [N0 + N1, K] tensor that the two modules' weights are VIEWS of (no second copy of the weights:
     the parameters are re-pointed at the halves, state_dict keys and values unchanged).  Made on first use; re-made when a
     parameter was replaced or moved (its storage is then no longer the cat's).  None when the pair cannot share (devices,
-    dtypes, trainable, not on a GPU) or DALM_CAT_GEMM=0.
+    dtypes, trainable, not on a GPU).
 
     Why: hipBLASLt runs the [rows, K] x [K, N] projections on 256 x 256 tiles; one GEMM over 2 N columns fills the last wave of
     tiles better than two over N (measured, tools/gemm_concat_probe.py: gate | up forward 672 -> 621 us at 4608 rows,
@@ -222,7 +219,7 @@ class _FrozenCatPairFn(torch.autograd.Function):
 
 
 def _eligible(x: torch.Tensor, *mods) -> bool:
-    if not (_ENABLED and x.is_cuda and torch.is_grad_enabled() and x.requires_grad):
+    if not (x.is_cuda and torch.is_grad_enabled() and x.requires_grad):
         return False
     cdt = _compute_dtype(x)
     if cdt not in (torch.bfloat16, torch.float16, torch.float32):
@@ -264,8 +261,6 @@ def use_transposed_dgrad(model: torch.nn.Module) -> int:
     """Class-swap the FROZEN plain `nn.Linear` modules of `model` to FrozenLinearT (a model that is fine-tuned in full is left
     alone; the forward still checks per call that the layer is frozen); returns how many were swapped.  LoRA-wrapped projections
     and their siblings keep their own modules: the LoRA group node (models/lora_ops.py) asks `dgrad_weight` itself."""
-    if not _ENABLED:
-        return 0
     n = 0
     for name, m in model.named_modules():
         if not _is_plain_linear(m) or name.endswith("base_layer"):              # LoRALinear.base_layer: the group node's business

@@ -134,7 +134,7 @@ def dropout_uid(module: nn.Module) -> int:
 # Nothing in transformers is patched: a sibling called with another tensor (cross attention) simply computes on its own, and a
 # group whose stash is left unclaimed switches itself off.
 SHARED_INPUT_NAMES = (("q_proj", "k_proj", "v_proj"), ("query", "key", "value"))
-_GROUPS = os.environ.get("DALM_LORA_GROUP", "1") != "0"
+_GROUPS = True        # tests clear it to build their one-node-per-projection reference
 
 
 class GroupedLinear(nn.Linear):

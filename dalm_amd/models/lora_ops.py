@@ -243,10 +243,7 @@ def _colacc_tickets(dev: torch.device, words: int) -> torch.Tensor:
 
 
 def v2_supported(x2: torch.Tensor, rank: int) -> bool:
-    import os
-
-    return (x2.is_cuda and x2.dtype == torch.bfloat16 and rank in (8, 16) and x2.shape[1] % 32 == 0
-            and os.environ.get("DALM_LORA_V2", "1") != "0")
+    return x2.is_cuda and x2.dtype == torch.bfloat16 and rank in (8, 16) and x2.shape[1] % 32 == 0
 
 
 def _bt(b: torch.Tensor) -> torch.Tensor:
@@ -479,6 +476,4 @@ def group_supported(x, members) -> bool:
             if a.shape[1] % 32 != 0 or b.shape[0] % 8 != 0:
                 return False
             ranks.add(a.shape[0])
-    import os
-
-    return len(ranks) == 1 and next(iter(ranks)) in (8, 16) and os.environ.get("DALM_LORA_V2", "1") != "0"
+    return len(ranks) == 1 and next(iter(ranks)) in (8, 16)

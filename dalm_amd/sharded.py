@@ -220,9 +220,7 @@ class GradBucket:
         if any(p.dtype != torch.float32 or p.device != dev for p in self.params):
             raise ValueError("GradBucket needs fp32 trainable parameters on one device")
         self.flat = torch.zeros(sum(p.numel() for p in self.params), device=dev, dtype=torch.float32)
-        if overlap is None:
-            overlap = os.environ.get("DALM_GRAD_OVERLAP", "1") != "0"
-        self.overlap = bool(overlap) and not isinstance(comm, LocalComm)
+        self.overlap = (overlap is None or bool(overlap)) and not isinstance(comm, LocalComm)
         self.comm_stream = torch.cuda.Stream(device=dev) if (self.overlap and dev.type == "cuda") else None
         self.buckets: List[_Bucket] = []
         self._bucket_of: List[int] = []

@@ -62,12 +62,11 @@ class _StepBase:
         self.trainable = [p for p in model.parameters() if p.requires_grad]
         # W > 1: gradients live in one flat bucket (no per-step flatten / copy-back); fp32 trainables only
         self.bucket = None
-        if os.environ.get("DALM_GRAD_BUCKET", "1") != "0" and not isinstance(self.comm, LocalComm) and self.trainable and \
+        if not isinstance(self.comm, LocalComm) and self.trainable and \
                 all(p.dtype == torch.float32 for p in self.trainable) and \
                 len({p.device for p in self.trainable}) == 1:
             # bucketed all-reduce issued from post-accumulate hooks while the backward is still running
             self.bucket = GradBucket(self.trainable, self.comm, overlap=None if grad_overlap else False)
-        self.pack_pair = os.environ.get("DALM_PACK_PAIR", "1") != "0"
         # sets of tower graphs alive at once (every set keeps its own activations between its forward and backward graphs)
         self.tower_sets_cap = int(os.environ.get("DALM_TOWER_SETS", "4"))
         self.tower_stream = None
@@ -89,7 +88,7 @@ class _StepBase:
         the query tower) - or None when the batch / model does not allow it."""
         m = self.model
         enc = getattr(m, "retriever_model", None) or getattr(m, "model", None)
-        if (not self.pack_pair or not isinstance(self.comm, LocalComm)
+        if (not isinstance(self.comm, LocalComm)
                 or f"{q_prefix}_pack_rows" not in batch or f"{p_prefix}_pack_rows" not in batch
                 or getattr(m, "retriever_is_autoregressive", getattr(m, "is_autoregressive", False))
                 or not _packed.attention_is_packable(enc)):
@@ -180,7 +179,6 @@ class RagE2EStep(_StepBase):
         # (packed batches: per row-count combination), the first `graph_after` real steps eager (library warm-up, as GraphedStep)
         self.graph_towers = graph_towers and torch.cuda.is_available()
         self._tower_sets = GraphSets(cap=self.tower_sets_cap, skip=graph_after, what="the towers")
-        self.early_gather = os.environ.get("DALM_EARLY_GATHER", "1") != "0"
         self.aux: Dict[str, torch.Tensor] = {}
         # the two retriever towers are many small kernels (3204 tokens through BERT) and are independent of
         # the generator until the loss: run them on their own HIP stream so they fill the gaps between the
@@ -204,10 +202,7 @@ class RagE2EStep(_StepBase):
             key, lambda: GraphedTowers(self.model, self.autocast_dtype, batch, hidden_only=self.fuse_lm_head))
 
     def _gather(self, emb):
-        """Start the all-gather of an embedding matrix early on the side stream (overlaps the other tower) -
-        or, with early_gather off, leave it to the loss (gathered on the main stream right before use)."""
-        if not self.early_gather:
-            return None
+        """Start the all-gather of an embedding matrix early on the side stream (overlaps the other tower)."""
         return GatherHandle(emb.float(), self.comm, self.side_stream)
 
     def _retrieve(self, batch, side: str, towers: Optional[GraphedTowers]):

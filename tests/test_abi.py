@@ -108,6 +108,20 @@ def test_launchers_read_only_the_reference_switches():
     assert names == {"DALM_ATTN_FWD", "DALM_ATTN_DKDV", "DALM_TOPK_BF16X3"}
 
 
+def test_host_code_names_only_the_kept_switches():
+    """The Python host code selects every path from device, dtype, shape and its run-time guards.  The DALM_* names left in the
+    package (reads, comments and docstrings alike) are the switches tests use to build a reference model, and the settings with
+    a documented trade-off: launch structure, memory budgets, tuning, communicator bring-up and hardware queues."""
+    names = set()
+    for py in sorted((ROOT / "dalm_amd").rglob("*.py")):
+        names.update(re.findall(r"DALM_[A-Z0-9_]+", py.read_text()))
+    assert names == {
+        "DALM_ATTN_FWD_KERNEL", "DALM_ATTN_KERNEL", "DALM_BUILD_JOBS", "DALM_CLAIM_QUEUES", "DALM_COMM_BRINGUP_TIMEOUT_S",
+        "DALM_COMM_ID_FILE", "DALM_FALCON_KERNELS", "DALM_FAST_ROPE", "DALM_FORCE_DIST", "DALM_HW_QUEUES", "DALM_LM_HEAD_KERNEL",
+        "DALM_LM_HEAD_TRAIN_KERNEL", "DALM_LOGITS_BUDGET_MB", "DALM_LORA_KERNEL", "DALM_NATIVE_COMM", "DALM_NF4",
+        "DALM_NORM_KERNEL", "DALM_SIM_GRAD_X3", "DALM_STEP_GRAPHS", "DALM_SWIGLU_KERNEL", "DALM_TOWER_SETS", "DALM_TUNED_GEMMS"}
+
+
 def test_header_is_plain_c(tmp_path):
     """include/dalm_hip.h must be consumable by a C compiler (cgo / JNI / ctypes-style bindings): compile a C
     translation unit that includes it and takes the address of every entry point."""

@@ -30,7 +30,7 @@ OUT = Path(__file__).resolve().parent.parent / "gpurun_out"
 TOL_KERNELS_OFF = {"loss": 2.5e-4, "grad": 2.2e-3}   # (A) vs (B): both bf16 autocast; the kernels round where the eager chains round
 TOL_HOST_FP32 = {"loss": 4e-4, "grad": 7e-3}         # (A) vs (C): bf16 activations against float32 activations
 
-KERNEL_ENVS = ("DALM_FAST_ROPE", "DALM_ROPE_KERNEL", "DALM_SWIGLU_KERNEL", "DALM_NORM_KERNEL", "DALM_FALCON_KERNELS")
+KERNEL_ENVS = ("DALM_FAST_ROPE", "DALM_SWIGLU_KERNEL", "DALM_NORM_KERNEL", "DALM_FALCON_KERNELS")
 
 
 def _rel(a, b):
