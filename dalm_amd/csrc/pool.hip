@@ -452,6 +452,105 @@ __global__ __launch_bounds__(256) void pool_bwd_rows_kernel(const float* __restr
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Packed forward (evaluation sweeps; no backward): h [n, D] holds live token rows only, sequence s owns rows
+// cu[s] .. cu[s+1], every row weighs 1.  A wave covers a whole token row (64 lanes x VEC elements x NCH d-chunks: 16-byte
+// loads, TIF rows in flight), the 4 waves of a workgroup are 4 / wps sequences x wps row slices: short sequences (a query
+// is ~12 rows) get one wave each, 4 per workgroup; long ones are split over the 4 waves, whose sums are added in wave order
+// through LDS.  The first wave of a sequence then forms the mean, |u| and e and writes the f32 row at emb + s * ld_emb,
+// so a batch lands directly in its slice of a larger matrix.  HBM-bound: n*D*eh bytes read + nseq_out*D*4 written.
+// ---------------------------------------------------------------------------------------------------
+template <typename T, int NCH>
+__global__ __launch_bounds__(256) void pool_packed_kernel(const T* __restrict__ h, const int* __restrict__ cu, int n,
+                                                          int nseq_out, int D, int wps, float* __restrict__ emb,
+                                                          int64_t ld_emb, float* __restrict__ norm,
+                                                          float* __restrict__ inv_count) {
+  constexpr int VEC = HV<T>::VEC;
+  constexpr int TIF = (NCH <= 2) ? 4 : 2;       // token rows in flight per wave
+  constexpr int DP = 64 * VEC * NCH;
+  extern __shared__ float part[];               // [4][DP] when the waves of a sequence combine (wps > 1), nothing otherwise
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int spw = 4 / wps;                      // sequences per workgroup
+  const int s = static_cast<int>(blockIdx.x) * spw + wave / wps, sub = wave % wps;
+  const bool live = s < nseq_out;
+  int lo = 0, hi = 0;
+  if (live) {                                   // clamped: a malformed cu cannot send a load out of h
+    hi = min(max(cu[s + 1], 0), n);
+    lo = min(max(cu[s], 0), hi);
+  }
+  float acc[NCH][VEC];
+#pragma unroll
+  for (int q = 0; q < NCH; ++q)
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) acc[q][e] = 0.f;
+  // unconditional vector loads (a predicated load compiles to a branch + vmcnt(0) and serialises the rows in flight):
+  // a row past the end is redirected to an in-range row (n >= 1) and its value discarded
+  const int anchor = min(lo, n - 1);
+  for (int r0 = lo + sub; r0 < hi; r0 += TIF * wps) {
+#pragma unroll
+    for (int q = 0; q < NCH; ++q) {
+      const int d = (q * 64 + lane) * VEC;
+      const bool dok = d < D;
+      const int dd = dok ? d : 0;
+      float x[TIF][VEC];
+#pragma unroll
+      for (int u = 0; u < TIF; ++u) {
+        const int r = r0 + u * wps;
+        HV<T>::load(h + static_cast<int64_t>(r < hi ? r : anchor) * D + dd, VEC, true, x[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < TIF; ++u) {
+        const bool use = dok && (r0 + u * wps < hi);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[q][e] += use ? x[u][e] : 0.f;
+      }
+    }
+  }
+  if (wps > 1) {
+#pragma unroll
+    for (int q = 0; q < NCH; ++q)
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) part[wave * DP + (q * 64 + lane) * VEC + e] = acc[q][e];
+    __syncthreads();
+    if (sub != 0) return;
+    for (int w = 1; w < wps; ++w)               // fixed order: slice 0 + 1 + 2 + 3
+#pragma unroll
+      for (int q = 0; q < NCH; ++q)
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[q][e] += part[(wave + w) * DP + (q * 64 + lane) * VEC + e];
+  }
+  if (!live) return;
+  const float cden = fmaxf(static_cast<float>(hi - lo), 1e-9f);
+  float ss = 0.f;
+#pragma unroll
+  for (int q = 0; q < NCH; ++q)
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      const bool ok = (q * 64 + lane) * VEC + e < D;
+      acc[q][e] = ok ? acc[q][e] / cden : 0.f;
+      ss = fmaf(acc[q][e], acc[q][e], ss);
+    }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
+  const float nrm = sqrtf(ss);
+  const float denom = fmaxf(nrm, 1e-12f);
+  if (lane == 0) {
+    if (norm) norm[s] = nrm;
+    if (inv_count) inv_count[s] = 1.f / cden;
+  }
+  float* row = emb + static_cast<int64_t>(s) * ld_emb;
+#pragma unroll
+  for (int q = 0; q < NCH; ++q) {
+    const int d = (q * 64 + lane) * VEC;
+    if (d < D) {                                // D % VEC == 0: a chunk is inside the row or outside it
+#pragma unroll
+      for (int e4 = 0; e4 < VEC; e4 += 4)
+        *reinterpret_cast<float4*>(row + d + e4) =
+            make_float4(acc[q][e4] / denom, acc[q][e4 + 1] / denom, acc[q][e4 + 2] / denom, acc[q][e4 + 3] / denom);
+    }
+  }
+}
+
 }  // namespace
 }  // namespace dalm
 
@@ -625,5 +724,39 @@ extern "C" int dalm_pool_l2norm_bwd(const float* d_emb, const float* emb, const 
   if (dtype == DALM_F32) DALM_POOL_BWD(float);
   else DALM_POOL_BWD(bf16_t);
 #undef DALM_POOL_BWD
+  return check_launch(__func__);
+}
+
+extern "C" int dalm_pool_l2norm_packed_fwd(const void* h, int dtype, const int32_t* cu, int64_t n, int64_t nseq,
+                                           int64_t nseq_out, int64_t D, float* emb, int64_t ld_emb, float* norm,
+                                           float* inv_count, dalm_stream_t stream) {
+  DALM_REQUIRE(h && cu && emb, DALM_E_NULL, "null pointer argument");
+  DALM_REQUIRE(dtype == DALM_F32 || dtype == DALM_BF16, DALM_E_DTYPE, "dtype must be DALM_F32 or DALM_BF16");
+  const int vec = (dtype == DALM_F32) ? 4 : 8;
+  DALM_REQUIRE(n > 0 && nseq > 0 && nseq_out >= 0 && nseq_out <= nseq && n <= 0x7fffffffll && nseq <= 0x7ffffff0ll &&
+                   D > 0 && D % vec == 0 && D <= 64 * vec * 4 && ld_emb >= D,
+               DALM_E_SHAPE, "need n>0, 0<=nseq_out<=nseq, D a multiple of 16 bytes and <= 256 lanes of them, ld_emb>=D");
+  DALM_REQUIRE(reinterpret_cast<uintptr_t>(h) % 16 == 0 && reinterpret_cast<uintptr_t>(emb) % 16 == 0 && ld_emb % 4 == 0,
+               DALM_E_ALIGN, "h and emb rows must be 16-byte aligned");
+  if (nseq_out == 0) return 0;
+  const int64_t lanes = D / vec;
+  const int nch = static_cast<int>((lanes + 63) / 64);
+  // waves per sequence by the mean sequence length: one wave keeps TIF rows in flight, so a sequence of a few rows gains
+  // nothing from more waves, a 128-row passage does
+  const int64_t mean_rows = n / nseq;
+  const int wps = mean_rows >= 48 ? 4 : (mean_rows >= 24 ? 2 : 1);
+  const int spw = 4 / wps;
+  const dim3 grid(static_cast<unsigned>((nseq_out + spw - 1) / spw));
+  hipStream_t s = as_stream(stream);
+#define DALM_POOL_PACKED(TT, N) \
+  hipLaunchKernelGGL((pool_packed_kernel<TT, N>), grid, dim3(256), wps > 1 ? 4 * 64 * vec * N * sizeof(float) : 0, s, static_cast<const TT*>(h), cu, static_cast<int>(n), \
+                     static_cast<int>(nseq_out), static_cast<int>(D), wps, emb, ld_emb, norm, inv_count)
+#define DALM_POOL_PACKED_N(TT) \
+  switch (nch) { case 1: DALM_POOL_PACKED(TT, 1); break; case 2: DALM_POOL_PACKED(TT, 2); break; \
+                 case 3: DALM_POOL_PACKED(TT, 3); break; default: DALM_POOL_PACKED(TT, 4); break; }
+  if (dtype == DALM_F32) { DALM_POOL_PACKED_N(float) }
+  else { DALM_POOL_PACKED_N(bf16_t) }
+#undef DALM_POOL_PACKED_N
+#undef DALM_POOL_PACKED
   return check_launch(__func__);
 }

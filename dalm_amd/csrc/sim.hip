@@ -623,8 +623,15 @@ struct StreamStatsParams {
   int row_blocks, nsplit, blocks_per_split;
   // top-k modes
   float* gmax; int ng;                // MODE_GMAX: gmax[m][ng], one maximum per 32-column group
+  // MODE_RANK: rank / n_ge counters of one gold column per row
+  const float* gold_score;            // [m] score of the row's gold column (dalm_sim_gold_score)
+  const int64_t* gold;                // [m] global corpus row of the gold column
+  int64_t col_offset;                 // global corpus row of this block's column 0
+  float threshold;
+  unsigned long long* rank;           // [m] += columns of this block ranked before the gold column
+  unsigned long long* n_ge;           // [m] += columns of this block with score >= threshold
 };
-enum { MODE_STATS = 0, MODE_GMAX = 1 };
+enum { MODE_STATS = 0, MODE_GMAX = 1, MODE_RANK = 2 };
 
 // KS > 1 (MODE_STATS, mid-size problems whose 128-column blocks cannot fill the chip): the 4 waves are 4/KS column
 // tiles x KS slices of K; a workgroup then owns 32*RT rows x 128/KS columns per block, the K slices of a tile are summed
@@ -655,6 +662,25 @@ __global__ __launch_bounds__(256, KS > 1 ? 3 : 2) void sim_rowstats_stream_kerne
   for (int t = 0; t < RT; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) { rmax[t][r] = -INFINITY; rsum[t][r] = 0.f; }
+  // MODE_RANK: integer counters per (row, column lane); the rows' gold scores and block-local gold columns sit in LDS
+  // (red_m[0] / red_l[0], free until the final reduction).  A gold column before / after this block becomes -1 / n, so the
+  // tie rule "lower corpus index first" reads `col < gold` for every block.
+  int rcnt[RT][16], rge[RT][16];
+  float* gs_s = &red_m[0][0];
+  int* gc_s = reinterpret_cast<int*>(&red_l[0][0]);
+  if constexpr (MODE == MODE_RANK) {
+#pragma unroll
+    for (int t = 0; t < RT; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { rcnt[t][r] = 0; rge[t][r] = 0; }
+    if (tid < 32 * RT) {
+      const int row = min(i0 + tid, p.m - 1);
+      const int64_t gl = p.gold[row] - p.col_offset;
+      gs_s[tid] = p.gold_score[row];
+      gc_s[tid] = static_cast<int>(gl < 0 ? -1 : (gl > p.n ? p.n : gl));
+    }
+    __syncthreads();
+  }
 
 #pragma unroll 1
   for (int jb = jb_lo; jb < jb_hi; ++jb) {
@@ -753,7 +779,56 @@ __global__ __launch_bounds__(256, KS > 1 ? 3 : 2) void sim_rowstats_stream_kerne
           for (int off = 16; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
           if (l31 == 0 && row < p.m) p.gmax[static_cast<int64_t>(row) * p.ng + jb * 4 + wave] = v;
         }
+    } else if constexpr (MODE == MODE_RANK) {
+      // ---- count: columns ranked before the row's gold column (the order dalm_sim_topk sorts in) and columns at or above
+      // the threshold; the gold column itself is counted through its own gold score ----
+      if (col_ok) {
+#pragma unroll
+        for (int t = 0; t < RT; ++t)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int rl = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+            const float g = gs_s[rl];
+            const int gc = gc_s[rl];
+            const float v = __fmul_rn(p.alpha, sacc[t][r]);
+            const bool is_gold = col == gc;
+            rcnt[t][r] += (!is_gold && (v > g || (v == g && col < gc))) ? 1 : 0;
+            rge[t][r] += ((is_gold ? g : v) >= p.threshold) ? 1 : 0;
+          }
+      }
     }
+  }
+  if constexpr (MODE == MODE_RANK) {
+    // ---- reduce the counters over the 32 column lanes, then the 4 waves (LDS), then the column splits (integer vector
+    // atomics: sums of integers, the same result in any order) ----
+    __syncthreads();                      // every wave is done with gs_s / gc_s: the arrays turn into reduction scratch
+    int* red_c = reinterpret_cast<int*>(&red_m[0][0]);
+    int* red_g = reinterpret_cast<int*>(&red_l[0][0]);
+#pragma unroll
+    for (int t = 0; t < RT; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        int c = rcnt[t][r], ge = rge[t][r];
+#pragma unroll
+        for (int off = 16; off > 0; off >>= 1) {
+          c += __shfl_xor(c, off, 64);
+          ge += __shfl_xor(ge, off, 64);
+        }
+        if (l31 == 0) {
+          const int rl = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+          red_c[wave * 32 * RT + rl] = c;
+          red_g[wave * 32 * RT + rl] = ge;
+        }
+      }
+    __syncthreads();
+    if (tid < 32 * RT && i0 + tid < p.m) {
+      int c = 0, ge = 0;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) { c += red_c[w * 32 * RT + tid]; ge += red_g[w * 32 * RT + tid]; }
+      if (c) atomicAdd(p.rank + i0 + tid, static_cast<unsigned long long>(c));
+      if (ge) atomicAdd(p.n_ge + i0 + tid, static_cast<unsigned long long>(ge));
+    }
+    return;
   }
   if constexpr (MODE != MODE_STATS) return;
   // ---- reduce over the 32 column lanes of each half, then over the 4 waves ----
@@ -927,6 +1002,35 @@ __global__ __launch_bounds__(256) void topk_refine_kernel(const float* __restric
     for (int i = tid; i < cap; i += 256) if (cv[i] == mx && ci[i] == bi) cv[i] = -INFINITY;
     __syncthreads();
   }
+}
+
+// gold_score[i] = alpha * Q_i . C_gold[i] for the rows whose gold column lies in this corpus block: one thread per query, one
+// fma chain with k ascending, as topk_refine_kernel re-evaluates its candidates.  ASSUMPTION (as there: "normally the same
+// bits", not proven for every input): the f32 MFMA accumulates in that order, so a corpus row EQUAL to the gold row scores an
+// exact tie in the counting pass and is ranked by index; should the matrix core round a pair of k differently, such a
+// duplicate is ranked by a 1-ulp difference instead - within the f32 score window the tests grant.  The gold column itself
+// never depends on it (it is excluded from the rank and counted through this score).  m * D * 8 bytes of row reads.
+__global__ __launch_bounds__(64) void gold_score_kernel(const float* __restrict__ Q, const float* __restrict__ Cm,
+                                                        const int64_t* __restrict__ gold, int64_t col_offset, int m, int n,
+                                                        int D, int vec_ok4, float alpha, float* __restrict__ out) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= m) return;
+  const int64_t gl = gold[i] - col_offset;
+  if (gl < 0 || gl >= n) return;          // another block holds this row's gold column
+  const float* q = Q + static_cast<int64_t>(i) * D;
+  const float* c = Cm + gl * D;
+  float acc = 0.f;
+  int k = 0;
+  if (vec_ok4) {
+#pragma unroll 4
+    for (; k + 4 <= D; k += 4) {
+      const float4 a = *reinterpret_cast<const float4*>(q + k);
+      const float4 b = *reinterpret_cast<const float4*>(c + k);
+      acc = fmaf(a.x, b.x, acc); acc = fmaf(a.y, b.y, acc); acc = fmaf(a.z, b.z, acc); acc = fmaf(a.w, b.w, acc);
+    }
+  }
+  for (; k < D; ++k) acc = fmaf(q[k], c[k], acc);
+  out[i] = __fmul_rn(alpha, acc);
 }
 
 // dA = alpha * sum_z slab[z] (fixed order), float4-wide; n4 = m*D/4 (D % 4 == 0 on this path)
@@ -1418,5 +1522,74 @@ extern "C" int dalm_sim_topk(const float* Q, const float* C, int64_t m, int64_t 
   hipLaunchKernelGGL(topk_refine_kernel, dim3(static_cast<unsigned>(m)), dim3(256), lds, s, At, static_cast<int>(f.ldm),
                      Bt, static_cast<int>(f.ldn), static_cast<int>(f.kpad), static_cast<int>(n), scale, q.gmax, q.ng, thr,
                      L.cap, static_cast<int>(k), out_val, out_idx, overflow);
+  return check_launch(__func__);
+}
+
+
+// ---- rank of one gold passage per query (eval metrics without selection) ---------------------------------------------
+// recall / precision / hit-rate at every k and MRR are functions of the gold passage's rank in the whole corpus, and the rank is a
+// count over the score stream: the MFMA pass of the search above with integer counters as its epilogue - no candidate
+// buffer, no limit on k, no overflow fallback.
+namespace {
+struct RankLayout { StreamPlan f; size_t at, bt, total; };
+inline RankLayout rank_layout(int64_t m, int64_t n, int64_t D) {
+  RankLayout L{};
+  L.f = stream_plan(m, n, D, true);
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 15) / 16 * 16; return at; };
+  L.at = take(static_cast<size_t>(L.f.kpad) * L.f.ldm * 4);
+  L.bt = take(static_cast<size_t>(L.f.kpad) * L.f.ldn * 4);
+  L.total = o;
+  return L;
+}
+}  // namespace
+
+extern "C" int dalm_sim_gold_score(const float* Q, const float* C, const int64_t* gold, int64_t m, int64_t n, int64_t D,
+                                   int64_t col_offset, float scale, float* gold_score, dalm_stream_t stream) {
+  DALM_REQUIRE(Q && C && gold && gold_score, DALM_E_NULL, "null pointer argument");
+  if (int e = check_gemm_dims(m, n, D, __func__)) return e;
+  DALM_REQUIRE(col_offset >= 0, DALM_E_SHAPE, "col_offset must not be negative");
+  const int v4 = vec_ok(Q, D) && vec_ok(C, D);
+  hipLaunchKernelGGL(gold_score_kernel, dim3(static_cast<unsigned>((m + 63) / 64)), dim3(64), 0, as_stream(stream), Q, C,
+                     gold, col_offset, static_cast<int>(m), static_cast<int>(n), static_cast<int>(D), v4, scale, gold_score);
+  return check_launch(__func__);
+}
+
+extern "C" size_t dalm_sim_gold_rank_workspace_bytes(int64_t m, int64_t n, int64_t D) {
+  if (m <= 0 || n <= 0 || D <= 0) return 0;
+  const RankLayout L = rank_layout(m, n, D);
+  return L.f.ok ? L.total : 0;
+}
+
+extern "C" int dalm_sim_gold_rank(const float* Q, const float* C, const int64_t* gold, const float* gold_score, int64_t m,
+                                  int64_t n, int64_t D, int64_t col_offset, float scale, float threshold, int64_t* rank,
+                                  int64_t* n_ge, void* ws, size_t ws_bytes, dalm_stream_t stream) {
+  DALM_REQUIRE(Q && C && gold && gold_score && rank && n_ge && ws, DALM_E_NULL, "null pointer argument");
+  if (int e = check_gemm_dims(m, n, D, __func__)) return e;
+  DALM_REQUIRE(col_offset >= 0, DALM_E_SHAPE, "col_offset must not be negative");
+  const RankLayout L = rank_layout(m, n, D);
+  DALM_REQUIRE(L.f.ok, DALM_E_SHAPE, "query or corpus block too large for 32-bit buffer offsets: (rows + 128) * padded D * 4 must stay below 2^31 for both");
+  DALM_REQUIRE(ws_bytes >= L.total, DALM_E_WORKSPACE, "workspace too small");
+  DALM_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 16 == 0 && reinterpret_cast<uintptr_t>(rank) % 8 == 0 &&
+                   reinterpret_cast<uintptr_t>(n_ge) % 8 == 0,
+               DALM_E_ALIGN, "workspace must be 16-byte aligned, the counters 8-byte aligned");
+  hipStream_t s = as_stream(stream);
+  char* base = static_cast<char*>(ws);
+  float* At = reinterpret_cast<float*>(base + L.at);
+  float* Bt = reinterpret_cast<float*>(base + L.bt);
+  const StreamPlan& f = L.f;
+  const int64_t ldmax = f.ldm > f.ldn ? f.ldm : f.ldn;
+  hipLaunchKernelGGL(transpose_pad_kernel, dim3(static_cast<unsigned>(ldmax / 32), static_cast<unsigned>((f.kpad + 31) / 32), 2),
+                     dim3(256), 0, s, Q, static_cast<int>(m), static_cast<int>(f.ldm), At, C, static_cast<int>(n),
+                     static_cast<int>(f.ldn), Bt, static_cast<int>(D), static_cast<int>(f.kpad));
+  StreamStatsParams q{};
+  q.At = At; q.Bt = Bt; q.m = static_cast<int>(m); q.n = static_cast<int>(n); q.Kpad = static_cast<int>(f.kpad);
+  q.ldm = static_cast<int>(f.ldm); q.ldn = static_cast<int>(f.ldn); q.alpha = scale;
+  q.row_blocks = f.row_blocks; q.nsplit = f.nsplit; q.blocks_per_split = f.blocks_per_split;
+  q.gold_score = gold_score; q.gold = gold; q.col_offset = col_offset; q.threshold = threshold;
+  q.rank = reinterpret_cast<unsigned long long*>(rank); q.n_ge = reinterpret_cast<unsigned long long*>(n_ge);
+  const dim3 grid(static_cast<unsigned>(f.row_blocks * f.nsplit));
+  if (f.rt == 2) hipLaunchKernelGGL((sim_rowstats_stream_kernel<2, MODE_RANK>), grid, dim3(256), 0, s, q);
+  else hipLaunchKernelGGL((sim_rowstats_stream_kernel<1, MODE_RANK>), grid, dim3(256), 0, s, q);
   return check_launch(__func__);
 }

@@ -70,6 +70,10 @@ SIGNATURES = {
     "dalm_sim_topk_supported": (_int, [_i64, _i64]),
     "dalm_sim_topk_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "dalm_sim_topk": (_int, [_vp, _vp, _i64, _i64, _i64, _f32, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dalm_pool_l2norm_packed_fwd": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "dalm_sim_gold_score": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp]),
+    "dalm_sim_gold_rank_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "dalm_sim_gold_rank": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _f32, _vp, _vp, _vp, _sz, _vp]),
     "dalm_lm_head_lse_workspace_bytes": (_sz, [_i64, _i64]),
     "dalm_lm_head_lse_fwd": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
     "dalm_comm_unique_id": (_int, [_vp]),

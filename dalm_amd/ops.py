@@ -58,6 +58,28 @@ class HipOps:
                  hip.ptr(emb), hip.ptr(norm), hip.ptr(inv_count), hip.ptr(ws), ws_bytes, hip.stream())
         return emb, norm, inv_count
 
+    def pool_packed_fwd(self, h: torch.Tensor, cu: torch.Tensor, nseq_out: Optional[int] = None,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """mean_pooling + F.normalize straight from packed rows (`dalm_pool_l2norm_packed_fwd`; evaluation, no backward):
+        h [n, D] f32 / bf16, cu int32 [nseq + 1] sequence starts; the first `nseq_out` sequences are written as f32 rows
+        into `out` [nseq_out, D] (a row slice of a larger f32 matrix is fine: its row stride is the leading dimension)."""
+        dev = hip.require_gpu(h, cu, out)
+        if h.dim() != 2 or cu.dim() != 1 or cu.numel() < 2:
+            raise ValueError(f"pool_packed: expected h [n,D] and cu [nseq+1], got {tuple(h.shape)} / {tuple(cu.shape)}")
+        h = h.contiguous()
+        cu = cu if (cu.dtype == torch.int32 and cu.is_contiguous()) else cu.to(torch.int32).contiguous()
+        n, D = h.shape
+        nseq = cu.numel() - 1
+        nseq_out = nseq if nseq_out is None else int(nseq_out)
+        if out is None:
+            out = torch.empty((nseq_out, D), device=dev, dtype=torch.float32)
+        if out.dtype != torch.float32 or out.dim() != 2 or out.shape != (nseq_out, D) or out.stride(1) != 1:
+            raise ValueError(f"pool_packed: out must be f32 [{nseq_out}, {D}] with unit column stride")
+        ld = out.stride(0) if nseq_out > 1 else max(out.stride(0), D)
+        hip.call("dalm_pool_l2norm_packed_fwd", hip.ptr(h), hip.dtype_code(h), hip.ptr(cu), n, nseq, nseq_out, D,
+                 hip.ptr(out), ld, None, None, hip.stream())
+        return out
+
     def pool_bwd(self, d_emb, emb, norm, inv_count, mask, normalize: bool, T: int, dtype: torch.dtype):
         dev = hip.require_gpu(d_emb, emb, norm, inv_count, mask)
         d_emb = hip.as_f32c(d_emb)
@@ -294,6 +316,41 @@ class HipOps:
         hip.call("dalm_sim_topk", hip.ptr(Q), hip.ptr(Cm), m, n, D, float(scale), int(k), hip.ptr(val), hip.ptr(idx),
                  hip.ptr(ovf), hip.ptr(ws), ws_bytes, hip.stream())
         return val, idx, ovf
+
+    def sim_gold_score(self, Q: torch.Tensor, Cm: torch.Tensor, gold: torch.Tensor, col_offset: int, out: torch.Tensor,
+                       scale: float = 1.0) -> torch.Tensor:
+        """out[i] = scale * Q_i . Cm[gold_i - col_offset] for the queries whose gold row lies in this corpus block
+        (`dalm_sim_gold_score`); the other entries of `out` are left as they are."""
+        hip.require_gpu(Q, Cm, gold, out)
+        Q, Cm, gold = hip.as_f32c(Q), hip.as_f32c(Cm), hip.as_i64(gold)
+        m, D = Q.shape
+        if Cm.shape[1] != D or gold.shape != (m,) or out.shape != (m,) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("sim_gold_score: Q [m,D], Cm [n,D], gold [m] int64, out [m] f32")
+        hip.call("dalm_sim_gold_score", hip.ptr(Q), hip.ptr(Cm), hip.ptr(gold), m, Cm.shape[0], D, int(col_offset),
+                 float(scale), hip.ptr(out), hip.stream())
+        return out
+
+    def sim_gold_rank(self, Q: torch.Tensor, Cm: torch.Tensor, gold: torch.Tensor, gold_score: torch.Tensor, col_offset: int,
+                      threshold: float, rank: torch.Tensor, n_ge: torch.Tensor, scale: float = 1.0):
+        """One corpus block of the rank sweep (`dalm_sim_gold_rank`): rank[i] += the block's columns that sort before query
+        i's gold passage (higher score, or equal score and lower corpus index), n_ge[i] += its columns scoring >=
+        `threshold`.  `rank` / `n_ge` are int64 [m] accumulators the caller zeroes before the first block."""
+        dev = hip.require_gpu(Q, Cm, gold, gold_score, rank, n_ge)
+        Q, Cm, gold, gold_score = hip.as_f32c(Q), hip.as_f32c(Cm), hip.as_i64(gold), hip.as_f32c(gold_score)
+        m, D = Q.shape
+        n = Cm.shape[0]
+        for t in (rank, n_ge):
+            if t.dtype != torch.int64 or t.shape != (m,) or not t.is_contiguous():
+                raise ValueError("sim_gold_rank: rank and n_ge must be contiguous int64 [m]")
+        if Cm.shape[1] != D or gold.shape != (m,) or gold_score.shape != (m,):
+            raise ValueError("sim_gold_rank: Q [m,D], Cm [n,D], gold [m], gold_score [m]")
+        ws_bytes = hip.load().dalm_sim_gold_rank_workspace_bytes(m, n, D)
+        if ws_bytes == 0:
+            raise ValueError("sim_gold_rank: query or corpus block too large for one call (m*D*4 and n*D*4 must stay below 2^31)")
+        ws = torch.empty((ws_bytes // 4,), device=dev, dtype=torch.float32)
+        hip.call("dalm_sim_gold_rank", hip.ptr(Q), hip.ptr(Cm), hip.ptr(gold), hip.ptr(gold_score), m, n, D, int(col_offset),
+                 float(scale), float(threshold), hip.ptr(rank), hip.ptr(n_ge), hip.ptr(ws), ws_bytes, hip.stream())
+        return rank, n_ge
 
     def lm_head_lse(self, hidden: torch.Tensor, weight: torch.Tensor, labels: torch.Tensor):
         """(row_lse [R], row_nll [R]) of logits = hidden @ weight^T without the logits: hidden [R,K] bf16, weight [V,K] bf16

@@ -9,7 +9,7 @@ passages the exact search is cheap on an MI355X: scores = Q . P_block^T on the m
 """
 from __future__ import annotations
 
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -113,3 +113,58 @@ def evaluate_retrieval(query_embs: torch.Tensor, corpus_embs: torch.Tensor, corr
         hits += int(int(correct[i]) in idx[i].tolist())
     n = max(len(precs), 1)
     return {"recall": sum(recs) / n, "precision": sum(precs) / n, "hit_rate": hits / n, "top_k": top_k, "queries": n}
+
+
+# ---------------------------------------------------------------------------
+# the same metrics without selection: rank of the gold passage
+# ---------------------------------------------------------------------------
+def gold_rank(query_embs: torch.Tensor, corpus_embs: torch.Tensor, gold_idx: torch.Tensor, threshold: float = 0.0,
+              block: int = 262144, ops=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(rank int64 [Nq], n_ge int64 [Nq], gold_score f32 [Nq]) of one gold passage per query over the whole corpus:
+    rank[i] = number of passages that sort before passage gold_idx[i] in query i's ranking (higher score, or equal score
+    and lower corpus index: the order `exact_topk` returns), n_ge[i] = number of passages scoring >= `threshold`.
+    One MFMA sweep per corpus block with integer counters (`dalm_sim_gold_rank`): no candidate buffer, no limit on k, no
+    per-query host work; `metrics_from_rank` turns the result into the whole recall curve."""
+    ops = ops or default_ops()
+    nq, nc = query_embs.shape[0], corpus_embs.shape[0]
+    D = corpus_embs.shape[1]
+    dev = query_embs.device
+    gold = gold_idx.to(device=dev, dtype=torch.int64).contiguous()
+    if gold.shape != (nq,):
+        raise ValueError(f"gold_idx must hold one corpus row per query ({nq}), got {tuple(gold.shape)}")
+    if nq and (int(gold_idx.min()) < 0 or int(gold_idx.max()) >= nc):      # eval path: one host sync is fine
+        raise ValueError(f"gold_idx outside the corpus [0, {nc})")
+    most = MAX_FUSED_BLOCK_BYTES // (4 * ((D + 15) // 16 * 16)) - 128         # rows of either operand per call
+    block = max(1, min(block, most))
+    score = torch.full((nq,), float("-inf"), device=dev, dtype=torch.float32)
+    rank = torch.zeros((nq,), device=dev, dtype=torch.int64)
+    n_ge = torch.zeros((nq,), device=dev, dtype=torch.int64)
+    for q0 in range(0, nq, max(1, most)):               # query blocks: only beyond ~2^19 queries
+        q1 = min(nq, q0 + max(1, most))
+        Q, g, sc = query_embs[q0:q1], gold[q0:q1], score[q0:q1]
+        for c0 in range(0, nc, block):                  # every query's gold score first: each block counts against it
+            ops.sim_gold_score(Q, corpus_embs[c0:c0 + block], g, c0, sc)
+        for c0 in range(0, nc, block):
+            ops.sim_gold_rank(Q, corpus_embs[c0:c0 + block], g, sc, c0, threshold, rank[q0:q1], n_ge[q0:q1])
+    return rank, n_ge, score
+
+
+def metrics_from_rank(rank: torch.Tensor, n_ge: torch.Tensor, top_k: Union[int, Sequence[int]]):
+    """recall / precision / hit-rate @ top_k and MRR from `gold_rank`'s counts (pure torch; CPU tensors are fine).
+
+    The reference (dalm/eval/utils.py:222-285) retrieves top_k passages, drops those scoring below threshold 0.0 and takes set
+    precision / recall against the query's single correct passage.  On a corpus of unique passages that is, per query,
+    c = min(top_k, n_ge) passages kept, hit = rank < c, recall = hit, precision = hit / c.  Where every retrieved score is
+    negative (c == 0) the reference divides by zero; here such a query scores 0 in all three.
+    Returns {"total_examples", "recall", "precision", "hit_rate", "mrr", "top_k"} with mrr = mean(1 / (rank + 1)); `top_k` may
+    be a list, which gives a list of such dicts from the same counts."""
+    if not isinstance(top_k, int):
+        return [metrics_from_rank(rank, n_ge, int(k)) for k in top_k]
+    rank, n_ge = rank.to(torch.int64), n_ge.to(torch.int64)
+    n = int(rank.numel())
+    c = torch.clamp(n_ge, max=int(top_k))
+    hit = rank < c
+    prec = torch.where(c > 0, hit.double() / c.clamp_min(1).double(), torch.zeros_like(c, dtype=torch.float64))
+    d = max(n, 1)
+    return {"total_examples": n, "recall": float(hit.double().sum()) / d, "precision": float(prec.sum()) / d,
+            "hit_rate": float(hit.double().sum()) / d, "mrr": float((1.0 / (rank.double() + 1.0)).sum()) / d, "top_k": int(top_k)}

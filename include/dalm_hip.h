@@ -71,6 +71,15 @@ int dalm_pool_l2norm_fwd_ws(const void* h, int dtype, const int64_t* mask,
                             int64_t B, int64_t T, int64_t D, int normalize,
                             float* emb, float* norm, float* inv_count,
                             void* ws, size_t ws_bytes, dalm_stream_t stream);
+/* Packed form for evaluation sweeps (forward only): h [n,D] contiguous (dtype) holds live token rows only, cu int32
+ * [nseq+1] are the sequence starts; sequence s owns rows cu[s] .. cu[s+1], each with weight 1.
+ *   u_s = sum h / max(count, 1e-9);  e_s = u_s / max(|u_s|, 1e-12)   (f32 accumulation; an empty sequence gives a zero row)
+ * The f32 row e_s is written at emb + s*ld_emb (ld_emb >= D, a multiple of 4) for the first nseq_out <= nseq sequences
+ * only (the slack sequences of a rounded pack cost nothing).  norm / inv_count [nseq_out] are optional (may be NULL).
+ * D must be a multiple of 16 bytes of dtype and at most 1024 (f32) / 2048 (bf16); h and emb 16-byte aligned. */
+int dalm_pool_l2norm_packed_fwd(const void* h, int dtype, const int32_t* cu, int64_t n, int64_t nseq,
+                                int64_t nseq_out, int64_t D, float* emb, int64_t ld_emb, float* norm,
+                                float* inv_count, dalm_stream_t stream);
 /* dh: [B,T,D] (dtype) is fully written (zeros where mask == 0). */
 int dalm_pool_l2norm_bwd(const float* d_emb, const float* emb, const float* norm,
                          const float* inv_count, const int64_t* mask,
@@ -341,6 +350,23 @@ size_t dalm_sim_topk_workspace_bytes(int64_t m, int64_t n, int64_t D, int64_t k)
 int dalm_sim_topk(const float* Q, const float* C, int64_t m, int64_t n, int64_t D,
                   float scale, int64_t k, float* out_val, int64_t* out_idx,
                   int* overflow, void* ws, size_t ws_bytes, dalm_stream_t stream);
+
+/* ---- rank of one gold passage per query (eval metrics without selection) ----
+ * With one gold passage per query, recall / precision / hit-rate at every k and MRR are functions of the gold passage's
+ * rank in the whole corpus; the rank is a count over the score stream of the search above (same f32 MFMA pass, integer
+ * counters instead of a candidate buffer: no limit on k, no overflow).  Q [m,D], C [n,D] one corpus block (f32, n*D*4 <
+ * 2^31 as for the search), gold [m] the GLOBAL corpus row of each query's gold passage, col_offset the global row of C[0].
+ *   gold_score[i]  = scale * Q_i . C_gold[i]          written by the call whose block holds that row, others leave it
+ *   rank[i]       += #{ j in block, j != gold_i : s_ij > g_i or (s_ij == g_i and j < gold_i) }   (the search's sort order)
+ *   n_ge[i]       += #{ j in block : s_ij >= threshold }, the gold column counted through gold_score[i]
+ * Walk the blocks twice: the score call for every block, then the rank call for every block with rank / n_ge zeroed
+ * before the first.  The counters are int64 and merged with integer atomics: the sums do not depend on the order. */
+int dalm_sim_gold_score(const float* Q, const float* C, const int64_t* gold, int64_t m, int64_t n, int64_t D,
+                        int64_t col_offset, float scale, float* gold_score, dalm_stream_t stream);
+size_t dalm_sim_gold_rank_workspace_bytes(int64_t m, int64_t n, int64_t D);
+int dalm_sim_gold_rank(const float* Q, const float* C, const int64_t* gold, const float* gold_score, int64_t m,
+                       int64_t n, int64_t D, int64_t col_offset, float scale, float threshold, int64_t* rank,
+                       int64_t* n_ge, void* ws, size_t ws_bytes, dalm_stream_t stream);
 
 /* lm_head + log-sum-exp + label gather without the logits (forward / evaluation): replaces
  *   logits = lm_head(hidden)                         dalm/models/rag_e2e_base_model.py:104-106
