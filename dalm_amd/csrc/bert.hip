@@ -77,6 +77,7 @@ struct AddNormArgs {
   int R, D;
   float eps, keep_scale;        // 1 / (1 - p)
   DropArgs drop;                // forward only (thr16 == 0: no dropout)
+  const unsigned char* live;    // [R] or NULL: a dead row is not read, everything written for it is zero (its keep bits are not written)
 };
 
 // s = f32(bf16(a keep / (1 - p))) + res for one chunk
@@ -95,6 +96,20 @@ __global__ __launch_bounds__(256) void bert_add_norm_fwd_kernel(const AddNormArg
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= p.R) return;
   const int64_t base = static_cast<int64_t>(row) * p.D;
+  if (p.live && !p.live[row]) {                                    // wave-uniform
+    float z[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) z[e] = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int d = (c * 64 + lane) * 8;
+      if (d >= p.D) continue;
+      st8f(p.y32 + base + d, z);
+      *reinterpret_cast<uint4*>(p.y16 + base + d) = make_uint4(0u, 0u, 0u, 0u);
+    }
+    if (lane == 0) { p.mean[row] = 0.f; p.rstd[row] = 0.f; }
+    return;
+  }
   const bool drop = p.drop.thr16 != 0u;
   DropKey key = {0u, 1u};
   if (drop) key = lora::drop_key(p.drop);
@@ -150,6 +165,19 @@ __global__ __launch_bounds__(256) void bert_add_norm_bwd_kernel(const AddNormArg
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= p.R) return;
   const int64_t base = static_cast<int64_t>(row) * p.D;
+  if (p.live && !p.live[row]) {                                    // wave-uniform
+    float z[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) z[e] = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int d = (c * 64 + lane) * 8;
+      if (d >= p.D) continue;
+      st8f(p.d_res + base + d, z);
+      *reinterpret_cast<uint4*>(p.d_a + base + d) = make_uint4(0u, 0u, 0u, 0u);
+    }
+    return;
+  }
   const bool drop = p.bits != nullptr;
   const float mean = p.mean[row], rstd = p.rstd[row];
   float xh[NCH][8], g[NCH][8];
@@ -230,9 +258,10 @@ using namespace dalm;
     }                                                                                                       \
   } while (0)
 
-extern "C" int dalm_bert_add_norm_fwd(const void* a, const float* res, const void* w, const void* b, int w_bf16, int64_t R, int64_t D,
-                                      float eps, float dropout_p, const void* seed, uint32_t salt, float* y32, void* y16,
-                                      uint8_t* keep_bits, float* mean, float* rstd, dalm_stream_t stream) {
+extern "C" int dalm_bert_add_norm_fwd_live(const void* a, const float* res, const void* w, const void* b, int w_bf16, int64_t R,
+                                           int64_t D, float eps, float dropout_p, const void* seed, uint32_t salt, float* y32,
+                                           void* y16, uint8_t* keep_bits, float* mean, float* rstd, const uint8_t* row_live,
+                                           dalm_stream_t stream) {
   DALM_REQUIRE(R >= 0, DALM_E_SHAPE, "R must be >= 0");
   if (R == 0) return 0;
   DALM_REQUIRE(a && res && w && b && y32 && y16 && mean && rstd, DALM_E_NULL, "null pointer argument");
@@ -249,13 +278,22 @@ extern "C" int dalm_bert_add_norm_fwd(const void* a, const float* res, const voi
   p.keep_scale = dropout_p > 0.f ? 1.0f / (1.0f - dropout_p) : 1.0f;
   p.drop = lora::drop_args(dropout_p, seed, salt);
   if (dropout_p == 0.f) p.drop.thr16 = 0u;
+  p.live = row_live;
   DALM_BERT_DISPATCH(bert_add_norm_fwd_kernel);
   return check_launch(__func__);
 }
 
-extern "C" int dalm_bert_add_norm_bwd(const float* g32, const void* g16, const void* a, const float* res, const void* w, int w_bf16,
-                                      const uint8_t* keep_bits, const float* mean, const float* rstd, int64_t R, int64_t D,
-                                      float dropout_p, float* d_res, void* d_a, dalm_stream_t stream) {
+extern "C" int dalm_bert_add_norm_fwd(const void* a, const float* res, const void* w, const void* b, int w_bf16, int64_t R, int64_t D,
+                                      float eps, float dropout_p, const void* seed, uint32_t salt, float* y32, void* y16,
+                                      uint8_t* keep_bits, float* mean, float* rstd, dalm_stream_t stream) {
+  return dalm_bert_add_norm_fwd_live(a, res, w, b, w_bf16, R, D, eps, dropout_p, seed, salt, y32, y16, keep_bits, mean, rstd, nullptr,
+                                     stream);
+}
+
+extern "C" int dalm_bert_add_norm_bwd_live(const float* g32, const void* g16, const void* a, const float* res, const void* w,
+                                           int w_bf16, const uint8_t* keep_bits, const float* mean, const float* rstd, int64_t R,
+                                           int64_t D, float dropout_p, float* d_res, void* d_a, const uint8_t* row_live,
+                                           dalm_stream_t stream) {
   DALM_REQUIRE(R >= 0, DALM_E_SHAPE, "R must be >= 0");
   if (R == 0) return 0;
   DALM_REQUIRE((g32 || g16) && a && res && w && mean && rstd && d_res && d_a, DALM_E_NULL, "null pointer argument");
@@ -272,7 +310,14 @@ extern "C" int dalm_bert_add_norm_bwd(const float* g32, const void* g16, const v
   p.d_res = d_res; p.d_a = static_cast<unsigned short*>(d_a);
   p.R = static_cast<int>(R); p.D = static_cast<int>(D);
   p.keep_scale = dropout_p > 0.f ? 1.0f / (1.0f - dropout_p) : 1.0f;
+  p.live = row_live;
   DALM_BERT_DISPATCH(bert_add_norm_bwd_kernel);
   return check_launch(__func__);
+}
+
+extern "C" int dalm_bert_add_norm_bwd(const float* g32, const void* g16, const void* a, const float* res, const void* w, int w_bf16,
+                                      const uint8_t* keep_bits, const float* mean, const float* rstd, int64_t R, int64_t D,
+                                      float dropout_p, float* d_res, void* d_a, dalm_stream_t stream) {
+  return dalm_bert_add_norm_bwd_live(g32, g16, a, res, w, w_bf16, keep_bits, mean, rstd, R, D, dropout_p, d_res, d_a, nullptr, stream);
 }
 #undef DALM_BERT_DISPATCH

@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void lora2_rowdot_kernel(
     const bf16_t* __restrict__ x0, const bf16_t* __restrict__ x1, const float* __restrict__ W0, const float* __restrict__ W1,
     float* __restrict__ out0, float* __restrict__ out1, unsigned char* __restrict__ bits0, unsigned char* __restrict__ bits1,
     const unsigned long long* __restrict__ seed, unsigned int salt0, unsigned int salt1, unsigned int thr16, int R, int K,
-    int rank, float scale) {
+    int rank, float scale, const unsigned char* __restrict__ live) {
   __shared__ float red[4][16][17];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -97,6 +97,10 @@ __global__ __launch_bounds__(256) void lora2_rowdot_kernel(
   const int li = MODE == 2 ? (i & 7) : i;                     // row within the tile / rank index
   const int row = static_cast<int>(blockIdx.x) * (MODE == 2 ? 8 : 16) + li;
   const int rowc = min(row, R - 1);
+  // row liveness: a dead row's x is not loaded (its A operand is zero), its mask bytes are not written and its z leaves as zero;
+  // a tile without a live row (the same rows in all four waves: workgroup-uniform) skips the K loop
+  const bool lv = !live || live[rowc];
+  const bool any_live = __builtin_amdgcn_ballot_w64(lv) != 0ull;
   const bf16_t* xr = ((MODE == 3 && prob) ? x1 : x0) + static_cast<int64_t>(rowc) * K + kg * 8;
   const bool wv = li < rank;                                  // this lane's B-operand column is a real rank index
   const float* wr = (lp ? W1 : W0) + static_cast<int64_t>(min(li, rank - 1)) * K + kg * 8;
@@ -117,7 +121,7 @@ __global__ __launch_bounds__(256) void lora2_rowdot_kernel(
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
       const int k = min(s0 + 4 * u, nsteps - 1) * 32;           // clamped: the extra steps are skipped in process()
-      xa[u] = *reinterpret_cast<const uint4*>(xr + k);
+      xa[u] = lv ? *reinterpret_cast<const uint4*>(xr + k) : make_uint4(0u, 0u, 0u, 0u);
       if (MODE == 2 || wv) {                                    // the other lanes' columns are never written out: any value does
         wa[u][0] = *reinterpret_cast<const float4*>(wr + k);
         wa[u][1] = *reinterpret_cast<const float4*>(wr + k + 4);
@@ -132,7 +136,7 @@ __global__ __launch_bounds__(256) void lora2_rowdot_kernel(
       uint4 v = xa[u];
       if constexpr (DROP) {
         const unsigned int byte = mask8(key, ebase + static_cast<unsigned int>(st) * 32u, thr_m1, v);
-        if (row < R) bp[st * 4] = static_cast<unsigned char>(byte);
+        if (row < R && lv) bp[st * 4] = static_cast<unsigned char>(byte);
       }
       unsigned int hi[4], lo[4];
       split_pair(wa[u][0].x, wa[u][0].y, hi[0], lo[0]);
@@ -147,8 +151,8 @@ __global__ __launch_bounds__(256) void lora2_rowdot_kernel(
 
   uint4 xa0[UN], xa1[UN];
   float4 wa0[UN][2], wa1[UN][2];
-  issue(xa0, wa0, wave);
-  for (int s0 = wave; s0 < nsteps; s0 += 8 * UN) {
+  if (any_live) issue(xa0, wa0, wave);
+  for (int s0 = wave; any_live && s0 < nsteps; s0 += 8 * UN) {
     const int s1 = s0 + 4 * UN, s2 = s0 + 8 * UN;
     if (s1 < nsteps) issue(xa1, wa1, s1);
     __builtin_amdgcn_sched_barrier(0);
@@ -169,10 +173,12 @@ __global__ __launch_bounds__(256) void lora2_rowdot_kernel(
     if constexpr (MODE == 2) {
       const int pm = m >> 3;
       const int orow = static_cast<int>(blockIdx.x) * 8 + (m & 7);
-      if (pm == (j >> 3) && orow < R) (pm ? out1 : out0)[static_cast<int64_t>(orow) * 8 + (j & 7)] = scale * s;
+      if (pm == (j >> 3) && orow < R)
+        (pm ? out1 : out0)[static_cast<int64_t>(orow) * 8 + (j & 7)] = (!live || live[orow]) ? scale * s : 0.f;
     } else {
       const int orow = static_cast<int>(blockIdx.x) * 16 + m;
-      if (j < rank && orow < R) (prob ? out1 : out0)[static_cast<int64_t>(orow) * rank + j] = scale * s;
+      if (j < rank && orow < R)
+        (prob ? out1 : out0)[static_cast<int64_t>(orow) * rank + j] = (!live || live[orow]) ? scale * s : 0.f;
     }
   }
 }
@@ -200,7 +206,7 @@ template <int RANK, int NT, bool BITS, bool TWO_Y, bool STAGE>
 __global__ __launch_bounds__(256) void lora2_rankupd_kernel(
     bf16_t* __restrict__ y0, bf16_t* __restrict__ y1, const float* __restrict__ z0, const float* __restrict__ z1,
     const float* __restrict__ W0, const float* __restrict__ W1, const unsigned char* __restrict__ bits0,
-    const unsigned char* __restrict__ bits1, int R, int C, int rows_per_wg, float scale) {
+    const unsigned char* __restrict__ bits1, int R, int C, int rows_per_wg, float scale, const unsigned char* __restrict__ live) {
   static_assert(!(TWO_Y && NT == 2), "two problems carry one term each");
   constexpr int UN = NT == 2 ? 3 : 4;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -229,22 +235,32 @@ __global__ __launch_bounds__(256) void lora2_rankupd_kernel(
       const int piece = idx & 3, rw = (idx >> 2) % rows_per_wg, t = (idx >> 2) / rows_per_wg;
       const int row = r_lo + rw, col_byte = static_cast<int>(blockIdx.x) * 64 + piece * 16;
       uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (row < r_hi && col_byte < bpr) v = *reinterpret_cast<const uint4*>(bt[t] + static_cast<int64_t>(row) * bpr + col_byte);
+      if (row < r_hi && col_byte < bpr && (!live || live[row]))
+        v = *reinterpret_cast<const uint4*>(bt[t] + static_cast<int64_t>(row) * bpr + col_byte);
       *reinterpret_cast<uint4*>(sbits + (t * rows_per_wg + rw) * 64 + piece * 16) = v;
     }
     __syncthreads();
   }
 
+  // row liveness: the wave's rows are r_lo + wave + 4 i, i < 64 (at most 256 rows per workgroup): bit i of `lw` = row i matters.
+  // A dead row is skipped: y is updated in place, nothing of the row is read or written
+  unsigned long long lw = ~0ull;
+  if (live) {
+    const int lrow = r_lo + wave + 4 * lane;
+    lw = __builtin_amdgcn_ballot_w64(lrow < r_hi && live[lrow] != 0);
+  }
+  auto row_live = [&](int row) __attribute__((always_inline)) { return ((lw >> ((row - r_lo) >> 2)) & 1ull) != 0ull; };   // row < r_hi
   auto issue = [&](uint4 (&raw)[UN], unsigned int (&by)[NT][UN], int b0) __attribute__((always_inline)) {
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
       const int row = min(b0 + 4 * u, R - 1);
-      raw[u] = valid ? *reinterpret_cast<const uint4*>(y + static_cast<int64_t>(row) * C + c0) : make_uint4(0u, 0u, 0u, 0u);
+      const bool ld = valid && b0 + 4 * u < r_hi && row_live(b0 + 4 * u);
+      raw[u] = ld ? *reinterpret_cast<const uint4*>(y + static_cast<int64_t>(row) * C + c0) : make_uint4(0u, 0u, 0u, 0u);
       if constexpr (BITS) {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
           if constexpr (STAGE) by[t][u] = sbits[(t * rows_per_wg + min(b0 + 4 * u, r_hi - 1) - r_lo) * 64 + lane];
-          else by[t][u] = valid ? bt[t][static_cast<int64_t>(row) * bpr + cb] : 0u;
+          else by[t][u] = ld ? bt[t][static_cast<int64_t>(row) * bpr + cb] : 0u;
         }
       }
     }
@@ -254,6 +270,7 @@ __global__ __launch_bounds__(256) void lora2_rankupd_kernel(
 #pragma unroll
     for (int u = 0; u < UN; ++u) {                                 // the batch's z rows first: scalar loads, one wait
       const int row = min(b0 + 4 * u, R - 1);
+      if (b0 + 4 * u >= r_hi || !row_live(b0 + 4 * u)) continue;   // wave-uniform
 #pragma unroll
       for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -262,7 +279,7 @@ __global__ __launch_bounds__(256) void lora2_rankupd_kernel(
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
       const int row = b0 + 4 * u;
-      if (row >= r_hi) continue;                                   // wave-uniform
+      if (row >= r_hi || !row_live(row)) continue;                 // wave-uniform
       float yv[8];
       Chunk8<bf16_t>::decode(raw[u], yv);
 #pragma unroll
@@ -335,7 +352,8 @@ __global__ __launch_bounds__(256, 2) void lora2_colacc_kernel(
     const unsigned char* __restrict__ bits0, const unsigned char* __restrict__ bits1, float* __restrict__ out0,
     float* __restrict__ out1, unsigned long long* __restrict__ part /* [2][S][C * RANK / 2] pairs of floats */,
     unsigned int* __restrict__ tickets /* [slabs * (TWO_X ? 2 : 1)], zero on entry, left zero */, int R, int C,
-    int rows_per_split, int S, float scale, int bits_off /* bytes: where the mask stage starts in LDS */) {
+    int rows_per_split, int S, float scale, int bits_off /* bytes: where the mask stage starts in LDS */,
+    const unsigned char* __restrict__ live, int live_off /* bytes: where the split's liveness bytes are staged in LDS */) {
   static_assert(!(TWO_X && NT == 2), "two problems carry one term each");
   constexpr int UN = (NT * RANK > 8) ? 2 : 4;                      // rows in flight per thread and buffer (the sums take NT*8*RANK registers)
   extern __shared__ __attribute__((aligned(16))) float smem[];   // z stage [NT][rows_per_split][RANK], later red[4][8][NT*8*RANK]
@@ -357,7 +375,7 @@ __global__ __launch_bounds__(256, 2) void lora2_colacc_kernel(
     float* zdst = smem + t * rows_per_split * RANK;
     for (int i4 = tid; i4 < rows_per_split * RANK / 4; i4 += 256) {
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (i4 * 4 < nrow * RANK) v = *reinterpret_cast<const float4*>(zsrc + i4 * 4);
+      if (i4 * 4 < nrow * RANK && (!live || live[r_lo + i4 * 4 / RANK])) v = *reinterpret_cast<const float4*>(zsrc + i4 * 4);
       *reinterpret_cast<float4*>(zdst + i4 * 4) = v;
     }
   }
@@ -368,10 +386,16 @@ __global__ __launch_bounds__(256, 2) void lora2_colacc_kernel(
     for (int idx = tid; idx < NT * rows_per_split; idx += 256) {
       const int t = idx / rows_per_split, rw = idx % rows_per_split, row = r_lo + rw;
       uint2 v = make_uint2(0u, 0u);
-      if (row < r_hi) v = *reinterpret_cast<const uint2*>(bt[t] + static_cast<int64_t>(row) * bpr + static_cast<int>(blockIdx.x) * 8);
+      if (row < r_hi && (!live || live[row]))
+        v = *reinterpret_cast<const uint2*>(bt[t] + static_cast<int64_t>(row) * bpr + static_cast<int>(blockIdx.x) * 8);
       *reinterpret_cast<uint2*>(sbits + static_cast<int64_t>(idx) * 8) = v;
     }
   }
+  // row liveness of the split, staged once: a dead row enters every sum as an exact zero (x not loaded, z and mask staged as zeros:
+  // the same partition and order of additions as without `live`); a batch of rows without a live one is not processed at all
+  unsigned char* slive = reinterpret_cast<unsigned char*>(smem) + live_off;      // [rows_per_split]
+  if (live)
+    for (int rw = tid; rw < rows_per_split; rw += 256) slive[rw] = (r_lo + rw < r_hi) ? live[r_lo + rw] : static_cast<unsigned char>(0);
   __syncthreads();
 
   float acc[NT][8][RANK];
@@ -383,10 +407,13 @@ __global__ __launch_bounds__(256, 2) void lora2_colacc_kernel(
       for (int j = 0; j < RANK; ++j) acc[t][e][j] = 0.f;
 
   auto issue = [&](uint4 (&raw)[UN], unsigned int (&by)[NT][UN], int b0) __attribute__((always_inline)) {
+    bool any = false;
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
       const int row = b0 + 32 * u;
-      const bool ok = valid && row < r_hi;
+      const bool rl_ok = row < r_hi && (!live || slive[row - r_lo]);
+      any = any || rl_ok;
+      const bool ok = valid && rl_ok;
       const int rr = min(row, R - 1);
       raw[u] = ok ? *reinterpret_cast<const uint4*>(x + static_cast<int64_t>(rr) * C + c0) : make_uint4(0u, 0u, 0u, 0u);
       if constexpr (BITS) {
@@ -397,6 +424,7 @@ __global__ __launch_bounds__(256, 2) void lora2_colacc_kernel(
         }
       }
     }
+    return __builtin_amdgcn_ballot_w64(any) != 0ull;                 // wave-uniform: the batch holds a row that matters
   };
   auto process = [&](uint4 (&raw)[UN], unsigned int (&by)[NT][UN], int b0) __attribute__((always_inline)) {
 #pragma unroll
@@ -428,15 +456,15 @@ __global__ __launch_bounds__(256, 2) void lora2_colacc_kernel(
     uint4 raw0[UN], raw1[UN];
     unsigned int by0[NT][UN], by1[NT][UN];
     const int first = r_lo + rl;
-    issue(raw0, by0, first);
+    bool any0 = issue(raw0, by0, first);
     for (int b0 = first; b0 < r_hi; b0 += 64 * UN) {
       const int b1 = b0 + 32 * UN, b2 = b0 + 64 * UN;
-      issue(raw1, by1, b1);                                          // rows past the split load nothing (ok == false)
+      const bool any1 = issue(raw1, by1, b1);                        // rows past the split load nothing (ok == false)
       __builtin_amdgcn_sched_barrier(0);
-      process(raw0, by0, b0);
-      issue(raw0, by0, b2);
+      if (any0) process(raw0, by0, b0);
+      any0 = issue(raw0, by0, b2);
       __builtin_amdgcn_sched_barrier(0);
-      if (b1 < r_hi) process(raw1, by1, b1);
+      if (any1) process(raw1, by1, b1);
     }
   }
 
@@ -507,7 +535,7 @@ __global__ __launch_bounds__(256, 2) void lora2_colacc_kernel(
 }
 
 // ---- launch geometry ----
-struct ColaccGeom { int rows_per_split, S, slabs; size_t lds; int bits_off; };
+struct ColaccGeom { int rows_per_split, S, slabs; size_t lds; int bits_off, live_off; };
 inline ColaccGeom colacc_geom(int64_t R, int64_t C, int rank, int nt, int nprob) {
   ColaccGeom g;
   g.slabs = static_cast<int>((C + 63) / 64);
@@ -526,6 +554,8 @@ inline ColaccGeom colacc_geom(int64_t R, int64_t C, int rank, int nt, int nprob)
   g.lds = stage > red ? stage : red;
   g.bits_off = static_cast<int>(g.lds);
   g.lds += static_cast<size_t>(nt) * rows * 8;                          // the mask stage (used when the call carries masks)
+  g.live_off = static_cast<int>(g.lds);
+  g.lds += static_cast<size_t>(rows);                                   // the rows' liveness bytes (used when the call carries them)
   return g;
 }
 
@@ -541,9 +571,10 @@ using namespace dalm;
   DALM_REQUIRE(mode >= 1 && mode <= 3, DALM_E_SHAPE, "mode must be 1 (one problem), 2 (two terms, shared activation) or 3 (two problems)"); \
   DALM_REQUIRE(mode != 2 || (rank) == 8, DALM_E_SHAPE, "stacked projections need rank 8")
 
-extern "C" int dalm_lora2_rowdot(const void* x0, const void* x1, const float* W0, const float* W1, float* out0, float* out1,
-                                 void* bits0, void* bits1, int64_t R, int64_t K, int rank, float scale, float p,
-                                 const void* seed, uint32_t salt0, uint32_t salt1, int mode, dalm_stream_t stream) {
+extern "C" int dalm_lora2_rowdot_live(const void* x0, const void* x1, const float* W0, const float* W1, float* out0, float* out1,
+                                      void* bits0, void* bits1, int64_t R, int64_t K, int rank, float scale, float p,
+                                      const void* seed, uint32_t salt0, uint32_t salt1, int mode, const uint8_t* row_live,
+                                      dalm_stream_t stream) {
   DALM_LORA2_SHAPE(R, K, rank);
   DALM_REQUIRE(K % 32 == 0, DALM_E_SHAPE, "the contraction length must be a multiple of 32");
   DALM_REQUIRE(p >= 0.f && p < 1.f, DALM_E_SHAPE, "dropout probability must be in [0, 1)");
@@ -565,7 +596,7 @@ extern "C" int dalm_lora2_rowdot(const void* x0, const void* x1, const float* W0
   hipStream_t s = as_stream(stream);
   const unsigned tiles16 = static_cast<unsigned>((R + 15) / 16), tiles8 = static_cast<unsigned>((R + 7) / 8);
 #define DALM_RD2(MODE, DR, GRID) hipLaunchKernelGGL((lora2_rowdot_kernel<MODE, DR>), GRID, dim3(256), 0, s, xa0, xa1, W0, Wa1, \
-    out0, oa1, ba0, ba1, sd, salt0, salt1, thr16, Ri, Ki, rank, scale)
+    out0, oa1, ba0, ba1, sd, salt0, salt1, thr16, Ri, Ki, rank, scale, row_live)
   if (mode == 1) { if (drop) DALM_RD2(1, true, dim3(tiles16)); else DALM_RD2(1, false, dim3(tiles16)); }
   else if (mode == 2) { if (drop) DALM_RD2(2, true, dim3(tiles8)); else DALM_RD2(2, false, dim3(tiles8)); }
   else { if (drop) DALM_RD2(3, true, dim3(tiles16, 2)); else DALM_RD2(3, false, dim3(tiles16, 2)); }
@@ -573,9 +604,15 @@ extern "C" int dalm_lora2_rowdot(const void* x0, const void* x1, const float* W0
   return check_launch(__func__);
 }
 
-extern "C" int dalm_lora2_rankupd(void* y0, void* y1, const float* z0, const float* z1, const float* W0, const float* W1,
-                                  const void* bits0, const void* bits1, int64_t R, int64_t C, int rank, float scale, int mode,
-                                  dalm_stream_t stream) {
+extern "C" int dalm_lora2_rowdot(const void* x0, const void* x1, const float* W0, const float* W1, float* out0, float* out1,
+                                 void* bits0, void* bits1, int64_t R, int64_t K, int rank, float scale, float p,
+                                 const void* seed, uint32_t salt0, uint32_t salt1, int mode, dalm_stream_t stream) {
+  return dalm_lora2_rowdot_live(x0, x1, W0, W1, out0, out1, bits0, bits1, R, K, rank, scale, p, seed, salt0, salt1, mode, nullptr, stream);
+}
+
+extern "C" int dalm_lora2_rankupd_live(void* y0, void* y1, const float* z0, const float* z1, const float* W0, const float* W1,
+                                       const void* bits0, const void* bits1, int64_t R, int64_t C, int rank, float scale, int mode,
+                                       const uint8_t* row_live, dalm_stream_t stream) {
   DALM_LORA2_SHAPE(R, C, rank);
   const bool two = mode != 1;
   DALM_REQUIRE(y0 && z0 && W0 && (!two || (z1 && W1)) && (mode != 3 || y1), DALM_E_NULL, "null pointer argument");
@@ -606,7 +643,7 @@ extern "C" int dalm_lora2_rankupd(void* y0, void* y1, const float* z0, const flo
   const bool stage = bits && C % 128 == 0;
   const size_t lds = stage ? static_cast<size_t>(mode == 2 ? 2 : 1) * rows_per_wg * 64 : 0;
 #define DALM_RU2(RK, NT, BT, TY, ST) hipLaunchKernelGGL((lora2_rankupd_kernel<RK, NT, BT, TY, ST>), grid, dim3(256), lds, s, ya0, ya1, \
-    z0, za1, W0, Wa1, ba0, ba1, Ri, Ci, rows_per_wg, scale)
+    z0, za1, W0, Wa1, ba0, ba1, Ri, Ci, rows_per_wg, scale, row_live)
 #define DALM_RU2_B(RK, NT, TY) do { if (stage) DALM_RU2(RK, NT, true, TY, true); else if (bits) DALM_RU2(RK, NT, true, TY, false); \
                                     else DALM_RU2(RK, NT, false, TY, false); } while (0)
   if (mode == 2) DALM_RU2_B(8, 2, false);
@@ -615,6 +652,12 @@ extern "C" int dalm_lora2_rankupd(void* y0, void* y1, const float* z0, const flo
 #undef DALM_RU2_B
 #undef DALM_RU2
   return check_launch(__func__);
+}
+
+extern "C" int dalm_lora2_rankupd(void* y0, void* y1, const float* z0, const float* z1, const float* W0, const float* W1,
+                                  const void* bits0, const void* bits1, int64_t R, int64_t C, int rank, float scale, int mode,
+                                  dalm_stream_t stream) {
+  return dalm_lora2_rankupd_live(y0, y1, z0, z1, W0, W1, bits0, bits1, R, C, rank, scale, mode, nullptr, stream);
 }
 
 extern "C" size_t dalm_lora2_colacc_workspace_bytes(int64_t R, int64_t C, int rank, int mode) {
@@ -627,9 +670,10 @@ extern "C" size_t dalm_lora2_colacc_ticket_words(int64_t C, int mode) {
   return static_cast<size_t>((C + 63) / 64) * (mode == 3 ? 2 : 1);
 }
 
-extern "C" int dalm_lora2_colacc(const void* x0, const void* x1, const float* z0, const float* z1, const void* bits0,
-                                 const void* bits1, float* out0, float* out1, int64_t R, int64_t C, int rank, float scale,
-                                 int mode, void* ws, size_t ws_bytes, uint32_t* tickets, dalm_stream_t stream) {
+extern "C" int dalm_lora2_colacc_live(const void* x0, const void* x1, const float* z0, const float* z1, const void* bits0,
+                                      const void* bits1, float* out0, float* out1, int64_t R, int64_t C, int rank, float scale,
+                                      int mode, void* ws, size_t ws_bytes, uint32_t* tickets, const uint8_t* row_live,
+                                      dalm_stream_t stream) {
   DALM_LORA2_SHAPE(R, C, rank);
   const bool two = mode != 1;
   DALM_REQUIRE(x0 && z0 && out0 && ws && tickets && (!two || (z1 && out1)) && (mode != 3 || x1), DALM_E_NULL, "null pointer argument");
@@ -652,7 +696,7 @@ extern "C" int dalm_lora2_colacc(const void* x0, const void* x1, const float* z0
   hipStream_t s = as_stream(stream);
   const bool stage = bits && C % 64 == 0;
 #define DALM_CA2(RK, NT, BT, TX, ST) hipLaunchKernelGGL((lora2_colacc_kernel<RK, NT, BT, TX, ST>), grid, dim3(256), g.lds, s, xa0, xa1, \
-    z0, za1, ba0, ba1, out0, oa1, part, tickets, Ri, Ci, g.rows_per_split, g.S, scale, g.bits_off)
+    z0, za1, ba0, ba1, out0, oa1, part, tickets, Ri, Ci, g.rows_per_split, g.S, scale, g.bits_off, row_live, g.live_off)
 #define DALM_CA2_B(RK, NT, TX) do { if (stage) DALM_CA2(RK, NT, true, TX, true); else if (bits) DALM_CA2(RK, NT, true, TX, false); \
                                     else DALM_CA2(RK, NT, false, TX, false); } while (0)
   if (mode == 2) DALM_CA2_B(8, 2, false);
@@ -661,4 +705,11 @@ extern "C" int dalm_lora2_colacc(const void* x0, const void* x1, const float* z0
 #undef DALM_CA2_B
 #undef DALM_CA2
   return check_launch(__func__);
+}
+
+extern "C" int dalm_lora2_colacc(const void* x0, const void* x1, const float* z0, const float* z1, const void* bits0,
+                                 const void* bits1, float* out0, float* out1, int64_t R, int64_t C, int rank, float scale,
+                                 int mode, void* ws, size_t ws_bytes, uint32_t* tickets, dalm_stream_t stream) {
+  return dalm_lora2_colacc_live(x0, x1, z0, z1, bits0, bits1, out0, out1, R, C, rank, scale, mode, ws, ws_bytes, tickets, nullptr,
+                                stream);
 }

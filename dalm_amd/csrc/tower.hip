@@ -69,6 +69,7 @@ struct RopeParams {
   RopeTensor q, k;
   const void* cos; const void* sin; int64_t cs[2];   // strides of (b, t)
   int B, T, Hq, Hk, hd, backward;
+  const unsigned char* live;                         // [B * T] or NULL: a dead (b, t) is not read, its outputs are zeros
 };
 
 template <typename T, bool VECTOR>
@@ -91,6 +92,14 @@ __global__ __launch_bounds__(256) void rope_qk_kernel(const RopeParams p) {
   const int head = is_k ? hh - p.Hq : hh;
   const T* x = static_cast<const T*>(R.x) + b * R.xs[0] + head * R.xs[1] + t * R.xs[2] + c;
   T* o = static_cast<T*>(R.o) + b * R.os[0] + head * R.os[1] + t * R.os[2] + c;
+  if (p.live && !p.live[bt]) {
+    float z[VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) z[e] = 0.f;
+    if constexpr (VECTOR) { EV<T>::store(o, z); EV<T>::store(o + h, z); }
+    else { EV<T>::store1(o, 0.f); EV<T>::store1(o + h, 0.f); }
+    return;
+  }
   const T* cs = static_cast<const T*>(p.cos) + b * p.cs[0] + t * p.cs[1] + c;
   const T* sn = static_cast<const T*>(p.sin) + b * p.cs[0] + t * p.cs[1] + c;
   float x1[VEC], x2[VEC], c1[VEC], c2[VEC], s1[VEC], s2[VEC], o1[VEC], o2[VEC];
@@ -152,18 +161,23 @@ __device__ __forceinline__ RowCol advance(RowCol rc, unsigned int step, unsigned
 
 template <typename T, int STEPS>
 __global__ __launch_bounds__(256) void swiglu_fwd_2d_kernel(const T* __restrict__ g, const T* __restrict__ u, T* __restrict__ a,
-                                                            int64_t n, SwigluLd ld) {
+                                                            int64_t n, SwigluLd ld, const unsigned char* __restrict__ live) {
   constexpr int VEC = EV<T>::VEC;
   const int64_t base = (static_cast<int64_t>(blockIdx.x) * STEPS * 256 + threadIdx.x) * VEC;
   float gv[STEPS][VEC], uv[STEPS][VEC];
   RowCol rc[STEPS];
+  bool lv[STEPS];                                                    // in range and (with `live`) a row that matters
   rc[0] = row_col(base < n ? base : 0, ld.C);
 #pragma unroll
   for (int k = 1; k < STEPS; ++k) rc[k] = advance(rc[k - 1], 256 * VEC, static_cast<unsigned int>(ld.C));
 #pragma unroll
   for (int k = 0; k < STEPS; ++k) {
     const int64_t e0 = base + static_cast<int64_t>(k) * 256 * VEC;
-    if (e0 < n) {
+    lv[k] = e0 < n && (!live || live[rc[k].row]);
+  }
+#pragma unroll
+  for (int k = 0; k < STEPS; ++k) {
+    if (lv[k]) {
       EV<T>::load(g + ld_at(rc[k], ld.g), gv[k]);
       EV<T>::load(u + ld_at(rc[k], ld.u), uv[k]);
     }
@@ -173,8 +187,13 @@ __global__ __launch_bounds__(256) void swiglu_fwd_2d_kernel(const T* __restrict_
     const int64_t e0 = base + static_cast<int64_t>(k) * 256 * VEC;
     if (e0 >= n) continue;
     float o[VEC];
+    if (lv[k]) {
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) o[e] = EV<T>::rb(__fmul_rn(EV<T>::rb(silu_f32(gv[k][e])), uv[k][e]));
+      for (int e = 0; e < VEC; ++e) o[e] = EV<T>::rb(__fmul_rn(EV<T>::rb(silu_f32(gv[k][e])), uv[k][e]));
+    } else {                                                         // a dead row: nothing was loaded, zeros leave
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) o[e] = 0.f;
+    }
     EV<T>::store(a + ld_at(rc[k], ld.a), o);
   }
 }
@@ -182,18 +201,23 @@ __global__ __launch_bounds__(256) void swiglu_fwd_2d_kernel(const T* __restrict_
 template <typename T, int STEPS>
 __global__ __launch_bounds__(256) void swiglu_bwd_2d_kernel(const T* __restrict__ da, const T* __restrict__ g,
                                                             const T* __restrict__ u, T* __restrict__ dg, T* __restrict__ du,
-                                                            int64_t n, SwigluLd ld) {
+                                                            int64_t n, SwigluLd ld, const unsigned char* __restrict__ live) {
   constexpr int VEC = EV<T>::VEC;
   const int64_t base = (static_cast<int64_t>(blockIdx.x) * STEPS * 256 + threadIdx.x) * VEC;
   float av[STEPS][VEC], gv[STEPS][VEC], uv[STEPS][VEC];
   RowCol rc[STEPS];
+  bool lv[STEPS];
   rc[0] = row_col(base < n ? base : 0, ld.C);
 #pragma unroll
   for (int k = 1; k < STEPS; ++k) rc[k] = advance(rc[k - 1], 256 * VEC, static_cast<unsigned int>(ld.C));
 #pragma unroll
   for (int k = 0; k < STEPS; ++k) {
     const int64_t e0 = base + static_cast<int64_t>(k) * 256 * VEC;
-    if (e0 < n) {
+    lv[k] = e0 < n && (!live || live[rc[k].row]);
+  }
+#pragma unroll
+  for (int k = 0; k < STEPS; ++k) {
+    if (lv[k]) {
       EV<T>::load(da + ld_at(rc[k], ld.a), av[k]);
       EV<T>::load(g + ld_at(rc[k], ld.g), gv[k]);
       EV<T>::load(u + ld_at(rc[k], ld.u), uv[k]);
@@ -204,14 +228,19 @@ __global__ __launch_bounds__(256) void swiglu_bwd_2d_kernel(const T* __restrict_
     const int64_t e0 = base + static_cast<int64_t>(k) * 256 * VEC;
     if (e0 >= n) continue;
     float og[VEC], ou[VEC];
+    if (lv[k]) {
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) {                                  // the contiguous kernel's arithmetic, statement for statement
-      const float x = gv[k][e];
-      const float s = EV<T>::rb(silu_f32(x));
-      const float ds = EV<T>::rb(__fmul_rn(av[k][e], uv[k][e]));
-      ou[e] = EV<T>::rb(__fmul_rn(av[k][e], s));
-      const float sig = 1.0f / (1.0f + expf(-x));
-      og[e] = EV<T>::rb(ds * sig * (1.0f + x * (1.0f - sig)));
+      for (int e = 0; e < VEC; ++e) {                                // the contiguous kernel's arithmetic, statement for statement
+        const float x = gv[k][e];
+        const float s = EV<T>::rb(silu_f32(x));
+        const float ds = EV<T>::rb(__fmul_rn(av[k][e], uv[k][e]));
+        ou[e] = EV<T>::rb(__fmul_rn(av[k][e], s));
+        const float sig = 1.0f / (1.0f + expf(-x));
+        og[e] = EV<T>::rb(ds * sig * (1.0f + x * (1.0f - sig)));
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) { og[e] = 0.f; ou[e] = 0.f; }
     }
     EV<T>::store(dg + ld_at(rc[k], ld.dg), og);
     EV<T>::store(du + ld_at(rc[k], ld.du), ou);
@@ -307,11 +336,27 @@ template <> struct RowVec<bf16_t> { static constexpr int N = 8; };
 template <typename T, int NCH, bool ADD>
 __global__ __launch_bounds__(256) void rms_norm_fwd_kernel(const T* __restrict__ x, const T* __restrict__ delta,
                                                            const T* __restrict__ w, T* __restrict__ h_out, T* __restrict__ y,
-                                                           float* __restrict__ rstd_out, int R, int D, float eps) {
+                                                           float* __restrict__ rstd_out, int R, int D, float eps,
+                                                           const unsigned char* __restrict__ live) {
   constexpr int N = RowVec<T>::N;
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= R) return;
   const int64_t base = static_cast<int64_t>(row) * D;
+  if (live && !live[row]) {                      // a dead row (wave-uniform): nothing is read, h, y and rstd leave as zeros
+    float z[N];
+#pragma unroll
+    for (int e = 0; e < N; ++e) z[e] = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int d = (c * 64 + lane) * N;
+      if (d < D) {
+        if constexpr (ADD) EV<T>::store(h_out + base + d, z);
+        EV<T>::store(y + base + d, z);
+      }
+    }
+    if (lane == 0) rstd_out[row] = 0.f;
+    return;
+  }
   float v[NCH][N];
   float ss = 0.f;
 #pragma unroll
@@ -349,11 +394,23 @@ __global__ __launch_bounds__(256) void rms_norm_fwd_kernel(const T* __restrict__
 template <typename T, int NCH, bool ADD>
 __global__ __launch_bounds__(256) void rms_norm_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ h,
                                                            const T* __restrict__ w, const float* __restrict__ rstd_in,
-                                                           const T* __restrict__ dres, T* __restrict__ dx, int R, int D) {
+                                                           const T* __restrict__ dres, T* __restrict__ dx, int R, int D,
+                                                           const unsigned char* __restrict__ live) {
   constexpr int N = RowVec<T>::N;
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= R) return;
   const int64_t base = static_cast<int64_t>(row) * D;
+  if (live && !live[row]) {                      // a dead row (wave-uniform): dx leaves as zeros
+    float z[N];
+#pragma unroll
+    for (int e = 0; e < N; ++e) z[e] = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int d = (c * 64 + lane) * N;
+      if (d < D) EV<T>::store(dx + base + d, z);
+    }
+    return;
+  }
   const float rstd = rstd_in[row];
   float g[NCH][N], xh[NCH][N];
   float dot = 0.f;
@@ -401,10 +458,19 @@ __global__ __launch_bounds__(256) void rms_norm_bwd_kernel(const T* __restrict__
 template <int NCH, bool ADD>
 __global__ __launch_bounds__(256) void rms_norm_bwd_v2_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ h,
                                                               const bf16_t* __restrict__ w, const float* __restrict__ rstd_in,
-                                                              const bf16_t* __restrict__ dres, bf16_t* __restrict__ dx, int R, int D) {
+                                                              const bf16_t* __restrict__ dres, bf16_t* __restrict__ dx, int R, int D,
+                                                              const unsigned char* __restrict__ live) {
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= R) return;
   const int64_t base = static_cast<int64_t>(row) * D;
+  if (live && !live[row]) {                      // a dead row (wave-uniform): dx leaves as zeros
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int d = (c * 64 + lane) * 8;
+      if (d < D) *reinterpret_cast<uint4*>(dx + base + d) = make_uint4(0u, 0u, 0u, 0u);
+    }
+    return;
+  }
   uint4 rg[NCH], rh[NCH], rr[NCH], rw[NCH];
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
@@ -456,10 +522,10 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 
 using namespace dalm;
 
-extern "C" int dalm_rope_qk(const void* q, const void* k, void* q_out, void* k_out, const void* cos, const void* sin, int dtype,
-                            int64_t B, int64_t T, int64_t Hq, int64_t Hk, int64_t hd, const int64_t* q_strides,
-                            const int64_t* k_strides, const int64_t* qo_strides, const int64_t* ko_strides,
-                            const int64_t* cs_strides, int backward, dalm_stream_t stream) {
+extern "C" int dalm_rope_qk_live(const void* q, const void* k, void* q_out, void* k_out, const void* cos, const void* sin, int dtype,
+                                 int64_t B, int64_t T, int64_t Hq, int64_t Hk, int64_t hd, const int64_t* q_strides,
+                                 const int64_t* k_strides, const int64_t* qo_strides, const int64_t* ko_strides,
+                                 const int64_t* cs_strides, int backward, const uint8_t* row_live, dalm_stream_t stream) {
   DALM_REQUIRE(q && k && q_out && k_out && cos && sin && q_strides && k_strides && qo_strides && ko_strides && cs_strides,
                DALM_E_NULL, "null pointer argument");
   DALM_REQUIRE(dtype == DALM_F32 || dtype == DALM_BF16, DALM_E_DTYPE, "dtype must be DALM_F32 or DALM_BF16");
@@ -479,6 +545,7 @@ extern "C" int dalm_rope_qk(const void* q, const void* k, void* q_out, void* k_o
   vector = vector && cs_strides[0] % vec == 0 && cs_strides[1] % vec == 0;
   p.B = static_cast<int>(B); p.T = static_cast<int>(T); p.Hq = static_cast<int>(Hq); p.Hk = static_cast<int>(Hk);
   p.hd = static_cast<int>(hd); p.backward = backward != 0;
+  p.live = row_live;
   const int64_t threads = rows * ((hd / 2) / (vector ? vec : 1));
   const int64_t blocks = (threads + 255) / 256;
   DALM_REQUIRE(blocks <= 0x7fffffffLL, DALM_E_SHAPE, "tensor too large for one launch");
@@ -492,6 +559,14 @@ extern "C" int dalm_rope_qk(const void* q, const void* k, void* q_out, void* k_o
     else hipLaunchKernelGGL((rope_qk_kernel<bf16_t, false>), grid, dim3(256), 0, s, p);
   }
   return check_launch(__func__);
+}
+
+extern "C" int dalm_rope_qk(const void* q, const void* k, void* q_out, void* k_out, const void* cos, const void* sin, int dtype,
+                            int64_t B, int64_t T, int64_t Hq, int64_t Hk, int64_t hd, const int64_t* q_strides,
+                            const int64_t* k_strides, const int64_t* qo_strides, const int64_t* ko_strides,
+                            const int64_t* cs_strides, int backward, dalm_stream_t stream) {
+  return dalm_rope_qk_live(q, k, q_out, k_out, cos, sin, dtype, B, T, Hq, Hk, hd, q_strides, k_strides, qo_strides, ko_strides,
+                           cs_strides, backward, nullptr, stream);
 }
 
 namespace {
@@ -544,8 +619,8 @@ extern "C" int dalm_swiglu_bwd(const void* d_act, const void* gate, const void* 
   return check_launch(__func__);
 }
 
-extern "C" int dalm_swiglu_fwd_2d(const void* gate, const void* up, void* act, int dtype, int64_t R, int64_t C, int64_t ld_gate,
-                                  int64_t ld_up, int64_t ld_act, dalm_stream_t stream) {
+extern "C" int dalm_swiglu_fwd_2d_live(const void* gate, const void* up, void* act, int dtype, int64_t R, int64_t C, int64_t ld_gate,
+                                       int64_t ld_up, int64_t ld_act, const uint8_t* row_live, dalm_stream_t stream) {
   DALM_REQUIRE(R >= 0 && C >= 0, DALM_E_SHAPE, "R, C must be >= 0");
   if (R == 0 || C == 0) return 0;
   DALM_REQUIRE(gate && up && act, DALM_E_NULL, "null pointer argument");
@@ -560,16 +635,21 @@ extern "C" int dalm_swiglu_fwd_2d(const void* gate, const void* up, void* act, i
   const SwigluLd ld = {C, ld_gate, ld_up, ld_act, 0, 0};
   if (dtype == DALM_F32)
     hipLaunchKernelGGL((swiglu_fwd_2d_kernel<float, kSwigluSteps>), grid, dim3(256), 0, as_stream(stream),
-                       static_cast<const float*>(gate), static_cast<const float*>(up), static_cast<float*>(act), n, ld);
+                       static_cast<const float*>(gate), static_cast<const float*>(up), static_cast<float*>(act), n, ld, row_live);
   else
     hipLaunchKernelGGL((swiglu_fwd_2d_kernel<bf16_t, kSwigluSteps>), grid, dim3(256), 0, as_stream(stream),
-                       static_cast<const bf16_t*>(gate), static_cast<const bf16_t*>(up), static_cast<bf16_t*>(act), n, ld);
+                       static_cast<const bf16_t*>(gate), static_cast<const bf16_t*>(up), static_cast<bf16_t*>(act), n, ld, row_live);
   return check_launch(__func__);
 }
 
-extern "C" int dalm_swiglu_bwd_2d(const void* d_act, const void* gate, const void* up, void* d_gate, void* d_up, int dtype, int64_t R,
-                                  int64_t C, int64_t ld_dact, int64_t ld_gate, int64_t ld_up, int64_t ld_dgate, int64_t ld_dup,
-                                  dalm_stream_t stream) {
+extern "C" int dalm_swiglu_fwd_2d(const void* gate, const void* up, void* act, int dtype, int64_t R, int64_t C, int64_t ld_gate,
+                                  int64_t ld_up, int64_t ld_act, dalm_stream_t stream) {
+  return dalm_swiglu_fwd_2d_live(gate, up, act, dtype, R, C, ld_gate, ld_up, ld_act, nullptr, stream);
+}
+
+extern "C" int dalm_swiglu_bwd_2d_live(const void* d_act, const void* gate, const void* up, void* d_gate, void* d_up, int dtype,
+                                       int64_t R, int64_t C, int64_t ld_dact, int64_t ld_gate, int64_t ld_up, int64_t ld_dgate,
+                                       int64_t ld_dup, const uint8_t* row_live, dalm_stream_t stream) {
   DALM_REQUIRE(R >= 0 && C >= 0, DALM_E_SHAPE, "R, C must be >= 0");
   if (R == 0 || C == 0) return 0;
   DALM_REQUIRE(d_act && gate && up && d_gate && d_up, DALM_E_NULL, "null pointer argument");
@@ -585,12 +665,34 @@ extern "C" int dalm_swiglu_bwd_2d(const void* d_act, const void* gate, const voi
   if (dtype == DALM_F32)
     hipLaunchKernelGGL((swiglu_bwd_2d_kernel<float, kSwigluSteps>), grid, dim3(256), 0, as_stream(stream),
                        static_cast<const float*>(d_act), static_cast<const float*>(gate), static_cast<const float*>(up),
-                       static_cast<float*>(d_gate), static_cast<float*>(d_up), n, ld);
+                       static_cast<float*>(d_gate), static_cast<float*>(d_up), n, ld, row_live);
   else
     hipLaunchKernelGGL((swiglu_bwd_2d_kernel<bf16_t, kSwigluSteps>), grid, dim3(256), 0, as_stream(stream),
                        static_cast<const bf16_t*>(d_act), static_cast<const bf16_t*>(gate), static_cast<const bf16_t*>(up),
-                       static_cast<bf16_t*>(d_gate), static_cast<bf16_t*>(d_up), n, ld);
+                       static_cast<bf16_t*>(d_gate), static_cast<bf16_t*>(d_up), n, ld, row_live);
   return check_launch(__func__);
+}
+
+extern "C" int dalm_swiglu_bwd_2d(const void* d_act, const void* gate, const void* up, void* d_gate, void* d_up, int dtype, int64_t R,
+                                  int64_t C, int64_t ld_dact, int64_t ld_gate, int64_t ld_up, int64_t ld_dgate, int64_t ld_dup,
+                                  dalm_stream_t stream) {
+  return dalm_swiglu_bwd_2d_live(d_act, gate, up, d_gate, d_up, dtype, R, C, ld_dact, ld_gate, ld_up, ld_dgate, ld_dup, nullptr, stream);
+}
+
+// the contiguous layout with a row structure ([R, C], row stride C).  Without `row_live` these are dalm_swiglu_{fwd,bwd} over R C
+// elements; with it the rows go through the strided kernels (the same arithmetic, statement for statement), which know a vector's row
+extern "C" int dalm_swiglu_fwd_live(const void* gate, const void* up, void* act, int dtype, int64_t R, int64_t C,
+                                    const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(R >= 0 && C >= 0, DALM_E_SHAPE, "R, C must be >= 0");
+  if (!row_live) return dalm_swiglu_fwd(gate, up, act, dtype, R * C, stream);
+  return dalm_swiglu_fwd_2d_live(gate, up, act, dtype, R, C, C, C, C, row_live, stream);
+}
+
+extern "C" int dalm_swiglu_bwd_live(const void* d_act, const void* gate, const void* up, void* d_gate, void* d_up, int dtype,
+                                    int64_t R, int64_t C, const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(R >= 0 && C >= 0, DALM_E_SHAPE, "R, C must be >= 0");
+  if (!row_live) return dalm_swiglu_bwd(d_act, gate, up, d_gate, d_up, dtype, R * C, stream);
+  return dalm_swiglu_bwd_2d_live(d_act, gate, up, d_gate, d_up, dtype, R, C, C, C, C, C, C, row_live, stream);
 }
 
 #define DALM_RMS_CHECKS                                                                                                  \
@@ -610,8 +712,8 @@ extern "C" int dalm_swiglu_bwd_2d(const void* d_act, const void* gate, const voi
     else hipLaunchKernelGGL((KERNEL<TT, 16, ADDV>), grid, dim3(256), 0, as_stream(stream), __VA_ARGS__);                 \
   } while (0)
 
-extern "C" int dalm_rms_norm_fwd(const void* x, const void* delta, const void* w, int dtype, int64_t R, int64_t D, float eps,
-                                 void* h_out, void* y, float* rstd, dalm_stream_t stream) {
+extern "C" int dalm_rms_norm_fwd_live(const void* x, const void* delta, const void* w, int dtype, int64_t R, int64_t D, float eps,
+                                      void* h_out, void* y, float* rstd, const uint8_t* row_live, dalm_stream_t stream) {
   DALM_REQUIRE(x && w && y && rstd, DALM_E_NULL, "null pointer argument");
   DALM_REQUIRE((delta == nullptr) == (h_out == nullptr), DALM_E_NULL, "delta and h_out go together");
   DALM_RMS_CHECKS;
@@ -619,44 +721,54 @@ extern "C" int dalm_rms_norm_fwd(const void* x, const void* delta, const void* w
   const int Ri = static_cast<int>(R), Di = static_cast<int>(D);
   if (dtype == DALM_F32) {
     if (delta) DALM_RMS_DISPATCH(rms_norm_fwd_kernel, float, true, static_cast<const float*>(x), static_cast<const float*>(delta),
-                                 static_cast<const float*>(w), static_cast<float*>(h_out), static_cast<float*>(y), rstd, Ri, Di, eps);
+                                 static_cast<const float*>(w), static_cast<float*>(h_out), static_cast<float*>(y), rstd, Ri, Di, eps, row_live);
     else DALM_RMS_DISPATCH(rms_norm_fwd_kernel, float, false, static_cast<const float*>(x), static_cast<const float*>(nullptr),
-                           static_cast<const float*>(w), static_cast<float*>(nullptr), static_cast<float*>(y), rstd, Ri, Di, eps);
+                           static_cast<const float*>(w), static_cast<float*>(nullptr), static_cast<float*>(y), rstd, Ri, Di, eps, row_live);
   } else {
     if (delta) DALM_RMS_DISPATCH(rms_norm_fwd_kernel, bf16_t, true, static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(delta),
-                                 static_cast<const bf16_t*>(w), static_cast<bf16_t*>(h_out), static_cast<bf16_t*>(y), rstd, Ri, Di, eps);
+                                 static_cast<const bf16_t*>(w), static_cast<bf16_t*>(h_out), static_cast<bf16_t*>(y), rstd, Ri, Di, eps, row_live);
     else DALM_RMS_DISPATCH(rms_norm_fwd_kernel, bf16_t, false, static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(nullptr),
-                           static_cast<const bf16_t*>(w), static_cast<bf16_t*>(nullptr), static_cast<bf16_t*>(y), rstd, Ri, Di, eps);
+                           static_cast<const bf16_t*>(w), static_cast<bf16_t*>(nullptr), static_cast<bf16_t*>(y), rstd, Ri, Di, eps, row_live);
   }
   return check_launch(__func__);
 }
 
-extern "C" int dalm_rms_norm_bwd(const void* dy, const void* h, const void* w, const float* rstd, const void* dres, int dtype,
-                                 int64_t R, int64_t D, void* dx, dalm_stream_t stream) {
+extern "C" int dalm_rms_norm_fwd(const void* x, const void* delta, const void* w, int dtype, int64_t R, int64_t D, float eps,
+                                 void* h_out, void* y, float* rstd, dalm_stream_t stream) {
+  return dalm_rms_norm_fwd_live(x, delta, w, dtype, R, D, eps, h_out, y, rstd, nullptr, stream);
+}
+
+extern "C" int dalm_rms_norm_bwd_live(const void* dy, const void* h, const void* w, const float* rstd, const void* dres, int dtype,
+                                      int64_t R, int64_t D, void* dx, const uint8_t* row_live, dalm_stream_t stream) {
   DALM_REQUIRE(dy && h && w && rstd && dx, DALM_E_NULL, "null pointer argument");
   DALM_RMS_CHECKS;
   DALM_REQUIRE(al16(dy) && al16(h) && al16(w) && al16(dx) && al16(dres), DALM_E_ALIGN, "tensors must be 16-byte aligned");
   const int Ri = static_cast<int>(R), Di = static_cast<int>(D);
   if (dtype == DALM_F32) {
     if (dres) DALM_RMS_DISPATCH(rms_norm_bwd_kernel, float, true, static_cast<const float*>(dy), static_cast<const float*>(h),
-                                static_cast<const float*>(w), rstd, static_cast<const float*>(dres), static_cast<float*>(dx), Ri, Di);
+                                static_cast<const float*>(w), rstd, static_cast<const float*>(dres), static_cast<float*>(dx), Ri, Di, row_live);
     else DALM_RMS_DISPATCH(rms_norm_bwd_kernel, float, false, static_cast<const float*>(dy), static_cast<const float*>(h),
-                           static_cast<const float*>(w), rstd, static_cast<const float*>(nullptr), static_cast<float*>(dx), Ri, Di);
+                           static_cast<const float*>(w), rstd, static_cast<const float*>(nullptr), static_cast<float*>(dx), Ri, Di, row_live);
   } else if (nch <= 8) {
 #define DALM_RMS_V2(ADDV, DRES)                                                                                           \
     do {                                                                                                                  \
-      if (nch <= 1) hipLaunchKernelGGL((rms_norm_bwd_v2_kernel<1, ADDV>), grid, dim3(256), 0, as_stream(stream), static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(h), static_cast<const bf16_t*>(w), rstd, DRES, static_cast<bf16_t*>(dx), Ri, Di); \
-      else if (nch <= 2) hipLaunchKernelGGL((rms_norm_bwd_v2_kernel<2, ADDV>), grid, dim3(256), 0, as_stream(stream), static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(h), static_cast<const bf16_t*>(w), rstd, DRES, static_cast<bf16_t*>(dx), Ri, Di); \
-      else if (nch <= 4) hipLaunchKernelGGL((rms_norm_bwd_v2_kernel<4, ADDV>), grid, dim3(256), 0, as_stream(stream), static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(h), static_cast<const bf16_t*>(w), rstd, DRES, static_cast<bf16_t*>(dx), Ri, Di); \
-      else hipLaunchKernelGGL((rms_norm_bwd_v2_kernel<8, ADDV>), grid, dim3(256), 0, as_stream(stream), static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(h), static_cast<const bf16_t*>(w), rstd, DRES, static_cast<bf16_t*>(dx), Ri, Di); \
+      if (nch <= 1) hipLaunchKernelGGL((rms_norm_bwd_v2_kernel<1, ADDV>), grid, dim3(256), 0, as_stream(stream), static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(h), static_cast<const bf16_t*>(w), rstd, DRES, static_cast<bf16_t*>(dx), Ri, Di, row_live); \
+      else if (nch <= 2) hipLaunchKernelGGL((rms_norm_bwd_v2_kernel<2, ADDV>), grid, dim3(256), 0, as_stream(stream), static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(h), static_cast<const bf16_t*>(w), rstd, DRES, static_cast<bf16_t*>(dx), Ri, Di, row_live); \
+      else if (nch <= 4) hipLaunchKernelGGL((rms_norm_bwd_v2_kernel<4, ADDV>), grid, dim3(256), 0, as_stream(stream), static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(h), static_cast<const bf16_t*>(w), rstd, DRES, static_cast<bf16_t*>(dx), Ri, Di, row_live); \
+      else hipLaunchKernelGGL((rms_norm_bwd_v2_kernel<8, ADDV>), grid, dim3(256), 0, as_stream(stream), static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(h), static_cast<const bf16_t*>(w), rstd, DRES, static_cast<bf16_t*>(dx), Ri, Di, row_live); \
     } while (0)
     if (dres) DALM_RMS_V2(true, static_cast<const bf16_t*>(dres)); else DALM_RMS_V2(false, static_cast<const bf16_t*>(nullptr));
 #undef DALM_RMS_V2
   } else {
     if (dres) DALM_RMS_DISPATCH(rms_norm_bwd_kernel, bf16_t, true, static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(h),
-                                static_cast<const bf16_t*>(w), rstd, static_cast<const bf16_t*>(dres), static_cast<bf16_t*>(dx), Ri, Di);
+                                static_cast<const bf16_t*>(w), rstd, static_cast<const bf16_t*>(dres), static_cast<bf16_t*>(dx), Ri, Di, row_live);
     else DALM_RMS_DISPATCH(rms_norm_bwd_kernel, bf16_t, false, static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(h),
-                           static_cast<const bf16_t*>(w), rstd, static_cast<const bf16_t*>(nullptr), static_cast<bf16_t*>(dx), Ri, Di);
+                           static_cast<const bf16_t*>(w), rstd, static_cast<const bf16_t*>(nullptr), static_cast<bf16_t*>(dx), Ri, Di, row_live);
   }
   return check_launch(__func__);
+}
+
+extern "C" int dalm_rms_norm_bwd(const void* dy, const void* h, const void* w, const float* rstd, const void* dres, int dtype,
+                                 int64_t R, int64_t D, void* dx, dalm_stream_t stream) {
+  return dalm_rms_norm_bwd_live(dy, h, w, rstd, dres, dtype, R, D, dx, nullptr, stream);
 }

@@ -131,6 +131,22 @@ SIGNATURES = {
     "dalm_transpose_bf16": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp]),
     "dalm_f32_to_bf16": (_int, [_vp, _vp, _i64, _vp]),
     "dalm_lora2_colacc": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _f32, _int, _vp, _sz, _vp, _vp]),
+    # the row-wise kernels with a row-liveness vector (one `row_live` pointer in front of the stream; NULL = the plain form)
+    "dalm_rope_qk_live": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _int, _vp,
+                                 _vp]),
+    "dalm_swiglu_fwd_live": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _vp, _vp]),
+    "dalm_swiglu_bwd_live": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _vp, _vp]),
+    "dalm_swiglu_fwd_2d_live": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "dalm_swiglu_bwd_2d_live": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "dalm_rms_norm_fwd_live": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "dalm_rms_norm_bwd_live": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _vp, _vp, _vp]),
+    "dalm_bert_add_norm_fwd_live": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _f32, _f32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _vp]),
+    "dalm_bert_add_norm_bwd_live": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
+    "dalm_lora2_rowdot_live": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _f32, _f32, _vp, C.c_uint32,
+                                      C.c_uint32, _int, _vp, _vp]),
+    "dalm_lora2_rankupd_live": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _f32, _int, _vp, _vp]),
+    "dalm_lora2_colacc_live": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _f32, _int, _vp, _sz, _vp, _vp, _vp]),
 }
 
 

@@ -192,7 +192,11 @@ class _RopeSdpaHip(torch.autograd.Function):
         from . import tower_ops
 
         B, H, T, hd = q.shape
-        q2, k2 = tower_ops._rope_launch(q, k, cos, sin, False)
+        from .. import live_rows
+
+        # dead (b, t) of a padded tower call leave the rotation as zeros (the attention kernels read finite values; the
+        # rotation's backward is inside dalm_attn_bwd, which is not row-aware)
+        q2, k2 = tower_ops._rope_launch(q, k, cos, sin, False, live_rows.current(B * T, q.device))
         pk = _pack(mask, B, H, T, causal, q.dtype, q.device)
         # multi-query (ONE key / value head, Falcon-7B): the kernels read it through stride-0 head views - nothing is broadcast
         # in memory; the backward kernels write per-head dk / dv, summed over the heads below

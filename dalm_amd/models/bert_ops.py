@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import torch
 
-from .. import hip
+from .. import hip, live_rows
 
 
 def twin(x: torch.Tensor) -> torch.Tensor:
@@ -32,13 +32,15 @@ def twin(x: torch.Tensor) -> torch.Tensor:
 
 class _BertAddNorm(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, a, res, w, b, eps, p, salt):
+    def forward(ctx, a, res, w, b, eps, p, salt, live=None):
         D = a.shape[-1]
         a2, r2 = a.reshape(-1, D), res.reshape(-1, D)
         a2 = a2 if a2.is_contiguous() else a2.contiguous()
         r2 = r2 if r2.is_contiguous() else r2.contiguous()
         R = a2.shape[0]
         dev = a.device
+        if live is None:
+            live = live_rows.current(R, dev)      # the padded tower call in progress: dead rows are not read, they leave as zeros
         y32 = torch.empty((R, D), dtype=torch.float32, device=dev)
         y16 = torch.empty((R, D), dtype=torch.bfloat16, device=dev)
         mean = torch.empty(R, dtype=torch.float32, device=dev)
@@ -49,11 +51,12 @@ class _BertAddNorm(torch.autograd.Function):
 
             bits = torch.empty((R, D // 8), dtype=torch.uint8, device=dev)
             seed = lora_ops.dropout_seed(dev)         # read in this launch only: the backward reads the stored bits
-        hip.call("dalm_bert_add_norm_fwd", hip.ptr(a2), hip.ptr(r2), hip.ptr(w), hip.ptr(b), int(w.dtype == torch.bfloat16), R, D,
+        hip.call("dalm_bert_add_norm_fwd_live", hip.ptr(a2), hip.ptr(r2), hip.ptr(w), hip.ptr(b), int(w.dtype == torch.bfloat16), R, D,
                  float(eps), float(p), hip.ptr(seed), int(salt) & 0xFFFFFFFF, hip.ptr(y32), hip.ptr(y16), hip.ptr(bits), hip.ptr(mean),
-                 hip.ptr(rstd), hip.stream())
-        ctx.save_for_backward(a2, r2, w, mean, rstd, *([bits] if bits is not None else []))
-        ctx.p, ctx.shape = float(p), a.shape
+                 hip.ptr(rstd), hip.ptr(live), hip.stream())
+        # (the liveness vector is kept: the backward runs after the tower call's context)
+        ctx.save_for_backward(a2, r2, w, mean, rstd, *([bits] if bits is not None else []), *([live] if live is not None else []))
+        ctx.p, ctx.shape, ctx.has_bits = float(p), a.shape, bits is not None
         ctx.set_materialize_grads(False)
         return y32.view(a.shape), y16.view(a.shape)
 
@@ -61,10 +64,12 @@ class _BertAddNorm(torch.autograd.Function):
     def backward(ctx, g32, g16):
         sv = ctx.saved_tensors
         a2, r2, w, mean, rstd = sv[:5]
-        bits = sv[5] if len(sv) > 5 else None
+        rest = list(sv[5:])
+        bits = rest.pop(0) if ctx.has_bits else None
+        live = rest.pop(0) if rest else None
         R, D = a2.shape
         if g32 is None and g16 is None:
-            return None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None
         if g32 is not None:
             g32 = g32.reshape(R, D)
             g32 = g32 if (g32.dtype == torch.float32 and g32.is_contiguous()) else g32.float().contiguous()
@@ -73,10 +78,10 @@ class _BertAddNorm(torch.autograd.Function):
             g16 = g16 if (g16.dtype == torch.bfloat16 and g16.is_contiguous()) else g16.to(torch.bfloat16).contiguous()
         d_res = torch.empty((R, D), dtype=torch.float32, device=a2.device)
         d_a = torch.empty((R, D), dtype=torch.bfloat16, device=a2.device)
-        hip.call("dalm_bert_add_norm_bwd", hip.ptr(g32), hip.ptr(g16), hip.ptr(a2), hip.ptr(r2), hip.ptr(w),
+        hip.call("dalm_bert_add_norm_bwd_live", hip.ptr(g32), hip.ptr(g16), hip.ptr(a2), hip.ptr(r2), hip.ptr(w),
                  int(w.dtype == torch.bfloat16), hip.ptr(bits), hip.ptr(mean), hip.ptr(rstd), R, D, ctx.p, hip.ptr(d_res), hip.ptr(d_a),
-                 hip.stream())
-        return d_a.view(ctx.shape), d_res.view(ctx.shape), None, None, None, None, None
+                 hip.ptr(live), hip.stream())
+        return d_a.view(ctx.shape), d_res.view(ctx.shape), None, None, None, None, None, None
 
 
 def supported(a: torch.Tensor, res: torch.Tensor, ln: torch.nn.Module) -> bool:
@@ -91,9 +96,10 @@ def supported(a: torch.Tensor, res: torch.Tensor, ln: torch.nn.Module) -> bool:
             and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16)
 
 
-def add_norm(a, res, ln: torch.nn.LayerNorm, p: float, salt: int) -> torch.Tensor:
-    """LayerNorm(dropout_p(a) + res) -> the f32 result carrying its bf16 twin."""
-    y32, y16 = _BertAddNorm.apply(a, res, ln.weight, ln.bias, float(ln.eps), float(p), int(salt))
+def add_norm(a, res, ln: torch.nn.LayerNorm, p: float, salt: int, live=None) -> torch.Tensor:
+    """LayerNorm(dropout_p(a) + res) -> the f32 result carrying its bf16 twin.  live: uint8 row liveness; None: that of the tower
+    call in progress (dalm_amd/live_rows.py), if any."""
+    y32, y16 = _BertAddNorm.apply(a, res, ln.weight, ln.bias, float(ln.eps), float(p), int(salt), live)
     y32._dalm_bf16 = y16
     y32._dalm_bf16_version, y32._dalm_bf16_tversion = y32._version, y16._version
     return y32

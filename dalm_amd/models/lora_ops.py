@@ -252,9 +252,10 @@ def _bt(b: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
-def rowdot2(xs, Ws, rank: int, scale: float, p: float, salts, mode: int):
+def rowdot2(xs, Ws, rank: int, scale: float, p: float, salts, mode: int, live=None):
     """mode 1: ([x], [W]) -> [z];  mode 2: ([x], [W0, W1]) -> [z0, z1] from ONE pass over x;  mode 3: ([x0, x1], [W0, W1]).
-    Returns (zs, bits): bits[t] is the [R, K/8] uint8 keep mask of slot t (None without dropout)."""
+    Returns (zs, bits): bits[t] is the [R, K/8] uint8 keep mask of slot t (None without dropout).
+    live (here and below): uint8 [R] row liveness or None (dalm_amd/live_rows.py): dead rows are not read, their z is zero."""
     x0 = xs[0]
     R, K = x0.shape
     n = 1 if mode == 1 else 2
@@ -263,26 +264,26 @@ def rowdot2(xs, Ws, rank: int, scale: float, p: float, salts, mode: int):
     bits = [torch.empty(R, K // 8, device=dev, dtype=torch.uint8) if p > 0 else None for _ in range(n)]
     seed = dropout_seed(dev) if p > 0 else None
     x1 = xs[1] if mode == 3 else None
-    hip.call("dalm_lora2_rowdot", hip.ptr(x0), hip.ptr(x1), hip.ptr(Ws[0]), hip.ptr(Ws[1]) if n == 2 else None,
+    hip.call("dalm_lora2_rowdot_live", hip.ptr(x0), hip.ptr(x1), hip.ptr(Ws[0]), hip.ptr(Ws[1]) if n == 2 else None,
              hip.ptr(zs[0]), hip.ptr(zs[1]) if n == 2 else None, hip.ptr(bits[0]), hip.ptr(bits[1]) if n == 2 else None,
              R, K, rank, float(scale), float(p), hip.ptr(seed), int(salts[0]) & 0xFFFFFFFF,
-             (int(salts[1]) & 0xFFFFFFFF) if n == 2 else 0, mode, hip.stream())
+             (int(salts[1]) & 0xFFFFFFFF) if n == 2 else 0, mode, hip.ptr(live), hip.stream())
     return zs, bits
 
 
-def rankupd2_(ys, zs, Ws, bits, rank: int, scale: float, mode: int):
+def rankupd2_(ys, zs, Ws, bits, rank: int, scale: float, mode: int, live=None):
     """mode 1: y += scale m (z W);  mode 2: ONE y += both terms;  mode 3: two independent (y, z, W)."""
     y0 = ys[0]
     R, C = y0.shape
     n = 1 if mode == 1 else 2
-    hip.call("dalm_lora2_rankupd", hip.ptr(y0), hip.ptr(ys[1]) if mode == 3 else None, hip.ptr(zs[0]),
+    hip.call("dalm_lora2_rankupd_live", hip.ptr(y0), hip.ptr(ys[1]) if mode == 3 else None, hip.ptr(zs[0]),
              hip.ptr(zs[1]) if n == 2 else None, hip.ptr(Ws[0]), hip.ptr(Ws[1]) if n == 2 else None,
              hip.ptr(bits[0]) if bits is not None else None, hip.ptr(bits[1]) if (bits is not None and n == 2) else None,
-             R, C, rank, float(scale), mode, hip.stream())
+             R, C, rank, float(scale), mode, hip.ptr(live), hip.stream())
     return ys
 
 
-def colacc2(xs, zs, bits, rank: int, scale: float, mode: int):
+def colacc2(xs, zs, bits, rank: int, scale: float, mode: int, live=None):
     """out_t [rank, C] = scale * sum_row m_t x_t[row, :] (x) z_t[row, :]; mode as in rowdot2 (mode 2: one pass over x)."""
     x0 = xs[0]
     R, C = x0.shape
@@ -293,10 +294,10 @@ def colacc2(xs, zs, bits, rank: int, scale: float, mode: int):
     nbytes = lib.dalm_lora2_colacc_workspace_bytes(R, C, rank, mode)
     ws = torch.empty(max(nbytes, 8), device=dev, dtype=torch.uint8)
     tickets = _colacc_tickets(dev, lib.dalm_lora2_colacc_ticket_words(C, mode))
-    hip.call("dalm_lora2_colacc", hip.ptr(x0), hip.ptr(xs[1]) if mode == 3 else None, hip.ptr(zs[0]),
+    hip.call("dalm_lora2_colacc_live", hip.ptr(x0), hip.ptr(xs[1]) if mode == 3 else None, hip.ptr(zs[0]),
              hip.ptr(zs[1]) if n == 2 else None, hip.ptr(bits[0]) if bits is not None else None,
              hip.ptr(bits[1]) if (bits is not None and n == 2) else None, hip.ptr(outs[0]), hip.ptr(outs[1]) if n == 2 else None,
-             R, C, rank, float(scale), mode, hip.ptr(ws), nbytes, hip.ptr(tickets), hip.stream())
+             R, C, rank, float(scale), mode, hip.ptr(ws), nbytes, hip.ptr(tickets), hip.ptr(live), hip.stream())
     return outs
 
 
@@ -329,6 +330,9 @@ class _LoRAGroupFn(torch.autograd.Function):
         lora = [i for i in range(n) if meta[i] is not None]
         rank = As[lora[0]].shape[0]
         zs, bits = [None] * n, [None] * n
+        from .. import live_rows
+
+        live = live_rows.current(x2.shape[0], x2.device)     # the padded tower call in progress: dead rows skip the branch
         # one pass over x per pair of adapters (one pass for q + v); members with different dropout rates cannot share a launch
         for grp in _pairs(lora):
             p = meta[grp[0]][1]
@@ -336,27 +340,29 @@ class _LoRAGroupFn(torch.autograd.Function):
                 # both adapters in one launch.  Mode 3 with the SAME x in both slots (16-row tiles, the second read of x comes
                 # from the caches) measured faster than mode 2's 8-row stacked tiles, which pull all of A_q and A_v through every
                 # workgroup: 37 vs 45 us at [4608, 4096] with dropout (profiles/r05_lora_bench_4608x4096.txt)
-                z, bt = rowdot2([x2, x2], [As[grp[0]], As[grp[1]]], rank, 1.0 / (1.0 - p), p, [meta[grp[0]][2], meta[grp[1]][2]], 3)
+                z, bt = rowdot2([x2, x2], [As[grp[0]], As[grp[1]]], rank, 1.0 / (1.0 - p), p, [meta[grp[0]][2], meta[grp[1]][2]], 3,
+                                live)
                 zs[grp[0]], zs[grp[1]], bits[grp[0]], bits[grp[1]] = z[0], z[1], bt[0], bt[1]
             else:
                 for i in grp:
                     pi = meta[i][1]
-                    z, bt = rowdot2([x2], [As[i]], rank, 1.0 / (1.0 - pi), pi, [meta[i][2]], 1)
+                    z, bt = rowdot2([x2], [As[i]], rank, 1.0 / (1.0 - pi), pi, [meta[i][2]], 1, live)
                     zs[i], bits[i] = z[0], bt[0]
         for grp in _pairs(lora):
             same = len(grp) == 2 and outs[grp[0]].shape == outs[grp[1]].shape and meta[grp[0]][0] == meta[grp[1]][0]
             if same:
                 rankupd2_([outs[grp[0]], outs[grp[1]]], [zs[grp[0]], zs[grp[1]]], [Bts[grp[0]], Bts[grp[1]]], None, rank,
-                          meta[grp[0]][0], 3)
+                          meta[grp[0]][0], 3, live)
             else:
                 for i in grp:
-                    rankupd2_([outs[i]], [zs[i]], [Bts[i]], None, rank, meta[i][0], 1)
+                    rankupd2_([outs[i]], [zs[i]], [Bts[i]], None, rank, meta[i][0], 1, live)
         ctx.meta, ctx.lora, ctx.n, ctx.rank = meta, lora, n, rank
         ctx.w_params = Ws
         ctx.xshape, ctx.xdtype = x.shape, x.dtype
         ctx.set_materialize_grads(False)          # an output nobody differentiated arrives as None, not as a zero tensor
         ctx.save_for_backward(x2, *wc, *[As[i] for i in lora], *[Bts[i] for i in lora], *[zs[i] for i in lora],
-                              *[b for b in (bits[i] for i in lora) if b is not None])
+                              *[b for b in (bits[i] for i in lora) if b is not None],
+                              *([live] if live is not None else []))     # the backward runs after the tower call's context
         ctx.has_bits = [bits[i] is not None for i in lora]
         return tuple(o.view(*x.shape[:-1], o.shape[-1]) for o in outs)
 
@@ -371,6 +377,7 @@ class _LoRAGroupFn(torch.autograd.Function):
         zs = dict(zip(lora, sv[1 + n + 2 * m:1 + n + 3 * m]))
         rest = list(sv[1 + n + 3 * m:])
         bits = {i: (rest.pop(0) if hb else None) for i, hb in zip(lora, ctx.has_bits)}
+        rows_live = rest.pop(0) if rest else None
         g2 = []
         for i in range(n):
             g = gs[i]
@@ -386,25 +393,26 @@ class _LoRAGroupFn(torch.autograd.Function):
         for grp in _pairs(live):
             same = len(grp) == 2 and g2[grp[0]].shape == g2[grp[1]].shape and meta[grp[0]][0] == meta[grp[1]][0]
             if same:                                       # dz = s g B and dB^T = s z^T g for both adapters, one launch each
-                z2, _ = rowdot2([g2[grp[0]], g2[grp[1]]], [Bts[grp[0]], Bts[grp[1]]], rank, meta[grp[0]][0], 0.0, [0, 0], 3)
-                d2 = colacc2([g2[grp[0]], g2[grp[1]]], [zs[grp[0]], zs[grp[1]]], None, rank, meta[grp[0]][0], 3)
+                z2, _ = rowdot2([g2[grp[0]], g2[grp[1]]], [Bts[grp[0]], Bts[grp[1]]], rank, meta[grp[0]][0], 0.0, [0, 0], 3,
+                                rows_live)
+                d2 = colacc2([g2[grp[0]], g2[grp[1]]], [zs[grp[0]], zs[grp[1]]], None, rank, meta[grp[0]][0], 3, rows_live)
                 for k, i in enumerate(grp):
                     dz[i], dBt[i] = z2[k], d2[k]
             else:
                 for i in grp:
-                    dz[i] = rowdot2([g2[i]], [Bts[i]], rank, meta[i][0], 0.0, [0], 1)[0][0]
-                    dBt[i] = colacc2([g2[i]], [zs[i]], None, rank, meta[i][0], 1)[0]
+                    dz[i] = rowdot2([g2[i]], [Bts[i]], rank, meta[i][0], 0.0, [0], 1, rows_live)[0][0]
+                    dBt[i] = colacc2([g2[i]], [zs[i]], None, rank, meta[i][0], 1, rows_live)[0]
         for grp in _pairs(live):                           # dA = dz^T (mask x) / (1-p): x streamed once per pair
             p = meta[grp[0]][1]
             both = len(grp) == 2 and rank == 8 and meta[grp[1]][1] == p and (bits[grp[0]] is None) == (bits[grp[1]] is None)
             if both:
                 bt = [bits[grp[0]], bits[grp[1]]] if bits[grp[0]] is not None else None
-                d2 = colacc2([x2], [dz[grp[0]], dz[grp[1]]], bt, rank, 1.0 / (1.0 - p), 2)
+                d2 = colacc2([x2], [dz[grp[0]], dz[grp[1]]], bt, rank, 1.0 / (1.0 - p), 2, rows_live)
                 dA[grp[0]], dA[grp[1]] = d2[0], d2[1]
             else:
                 for i in grp:
                     pi = meta[i][1]
-                    dA[i] = colacc2([x2], [dz[i]], [bits[i]] if bits[i] is not None else None, rank, 1.0 / (1.0 - pi), 1)[0]
+                    dA[i] = colacc2([x2], [dz[i]], [bits[i]] if bits[i] is not None else None, rank, 1.0 / (1.0 - pi), 1, rows_live)[0]
         dx = None
         if ctx.needs_input_grad[0]:
             from . import frozen_linear
@@ -428,11 +436,12 @@ class _LoRAGroupFn(torch.autograd.Function):
                 both = len(grp) == 2 and rank == 8 and meta[grp[1]][1] == p and (bits[grp[0]] is None) == (bits[grp[1]] is None)
                 if both:
                     bt = [bits[grp[0]], bits[grp[1]]] if bits[grp[0]] is not None else None
-                    rankupd2_([dx], [dz[grp[0]], dz[grp[1]]], [As[grp[0]], As[grp[1]]], bt, rank, 1.0 / (1.0 - p), 2)
+                    rankupd2_([dx], [dz[grp[0]], dz[grp[1]]], [As[grp[0]], As[grp[1]]], bt, rank, 1.0 / (1.0 - p), 2, rows_live)
                 else:
                     for i in grp:
                         pi = meta[i][1]
-                        rankupd2_([dx], [dz[i]], [As[i]], [bits[i]] if bits[i] is not None else None, rank, 1.0 / (1.0 - pi), 1)
+                        rankupd2_([dx], [dz[i]], [As[i]], [bits[i]] if bits[i] is not None else None, rank, 1.0 / (1.0 - pi), 1,
+                                  rows_live)
             dx = dx.view(ctx.xshape)
             if dx.dtype != ctx.xdtype:
                 dx = dx.to(ctx.xdtype)

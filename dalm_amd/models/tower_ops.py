@@ -14,15 +14,16 @@ import ctypes as C
 
 import torch
 
-from .. import hip
+from .. import hip, live_rows
 
 
 def _strides3(t: torch.Tensor):
     return (C.c_int64 * 3)(t.stride(0), t.stride(1), t.stride(2))
 
 
-def _rope_launch(q, k, cos, sin, backward: bool):
-    """q, k: [B, H, T, hd] (any b/h/t strides, contiguous last dim); cos, sin: [B or 1, T, hd]."""
+def _rope_launch(q, k, cos, sin, backward: bool, live=None):
+    """q, k: [B, H, T, hd] (any b/h/t strides, contiguous last dim); cos, sin: [B or 1, T, hd]; live: uint8 [B T] or None
+    (dalm_amd/live_rows.py: a dead (b, t) is not read and leaves as zeros for every head)."""
     hip.require_gpu(q, k, cos, sin)
     if q.stride(-1) != 1:
         q = q.contiguous()
@@ -35,22 +36,25 @@ def _rope_launch(q, k, cos, sin, backward: bool):
     B, Hq, T, hd = q.shape
     Hk = k.shape[1]
     cs = (C.c_int64 * 2)(cos.stride(0) if cos.shape[0] > 1 else 0, cos.stride(1))   # [1, T, hd]: one table for the batch
-    hip.call("dalm_rope_qk", hip.ptr(q), hip.ptr(k), hip.ptr(qo), hip.ptr(ko), hip.ptr(cos), hip.ptr(sin), hip.dtype_code(q),
-             B, T, Hq, Hk, hd, _strides3(q), _strides3(k), _strides3(qo), _strides3(ko), cs, int(backward), hip.stream())
+    hip.call("dalm_rope_qk_live", hip.ptr(q), hip.ptr(k), hip.ptr(qo), hip.ptr(ko), hip.ptr(cos), hip.ptr(sin), hip.dtype_code(q),
+             B, T, Hq, Hk, hd, _strides3(q), _strides3(k), _strides3(qo), _strides3(ko), cs, int(backward), hip.ptr(live),
+             hip.stream())
     return qo, ko
 
 
 class _RopeQK(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, cos, sin):
-        ctx.save_for_backward(cos, sin)
-        return _rope_launch(q, k, cos, sin, False)
+    def forward(ctx, q, k, cos, sin, live=None):
+        if live is None and q.dim() == 4:
+            live = live_rows.current(q.shape[0] * q.shape[2], q.device)
+        ctx.save_for_backward(cos, sin, *([live] if live is not None else []))   # the backward runs after the tower call's context
+        return _rope_launch(q, k, cos, sin, False, live)
 
     @staticmethod
     def backward(ctx, gq, gk):
-        cos, sin = ctx.saved_tensors
-        dq, dk = _rope_launch(gq, gk, cos, sin, True)
-        return dq, dk, None, None
+        cos, sin, *live = ctx.saved_tensors
+        dq, dk = _rope_launch(gq, gk, cos, sin, True, live[0] if live else None)
+        return dq, dk, None, None, None
 
 
 def rope_supported(q, k, cos, sin) -> bool:
@@ -63,9 +67,10 @@ def rope_supported(q, k, cos, sin) -> bool:
             and not cos.requires_grad and not sin.requires_grad)
 
 
-def rope_qk(q, k, cos, sin):
-    """(q*cos + rotate_half(q)*sin, k*cos + rotate_half(k)*sin) with cos / sin broadcast over the head dimension."""
-    return _RopeQK.apply(q, k, cos, sin)
+def rope_qk(q, k, cos, sin, live=None):
+    """(q*cos + rotate_half(q)*sin, k*cos + rotate_half(k)*sin) with cos / sin broadcast over the head dimension.
+    live: uint8 [B T] row liveness; None: that of the tower call in progress (dalm_amd/live_rows.py), if any."""
+    return _RopeQK.apply(q, k, cos, sin, live)
 
 
 def _halves_of_one(gate: torch.Tensor, up: torch.Tensor) -> bool:
@@ -85,26 +90,36 @@ def _halves_of_one(gate: torch.Tensor, up: torch.Tensor) -> bool:
 
 class _SwiGLU(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, gate, up):
+    def forward(ctx, gate, up, live=None):
         hip.require_gpu(gate, up)
         ctx.halves = _halves_of_one(gate, up)
+        C = gate.shape[-1] if gate.dim() else 0
+        R = gate.numel() // C if C else 0
+        if live is None and gate.dim() >= 2:
+            live = live_rows.current(R, gate.device)
+        if live is not None and (live.numel() != R or C % (16 // gate.element_size())):
+            live = None                    # the row-aware kernels walk 16-byte vectors that never cross a row
+        keep = [live] if live is not None else []          # the backward runs after the tower call's context
         if ctx.halves:                     # strided views of one [R, 2 C] GEMM output: read in place, no .contiguous() copies
-            C = gate.shape[-1]
-            R = gate.numel() // C
             act = torch.empty(gate.shape, dtype=gate.dtype, device=gate.device)
-            hip.call("dalm_swiglu_fwd_2d", hip.ptr(gate), hip.ptr(up), hip.ptr(act), hip.dtype_code(gate), R, C, 2 * C, 2 * C, C,
-                     hip.stream())
-            ctx.save_for_backward(gate, up)
+            hip.call("dalm_swiglu_fwd_2d_live", hip.ptr(gate), hip.ptr(up), hip.ptr(act), hip.dtype_code(gate), R, C, 2 * C, 2 * C, C,
+                     hip.ptr(live), hip.stream())
+            ctx.save_for_backward(gate, up, *keep)
             return act
         gate, up = gate.contiguous(), up.contiguous()
         act = torch.empty_like(gate)
-        hip.call("dalm_swiglu_fwd", hip.ptr(gate), hip.ptr(up), hip.ptr(act), hip.dtype_code(gate), gate.numel(), hip.stream())
-        ctx.save_for_backward(gate, up)
+        if live is not None:
+            hip.call("dalm_swiglu_fwd_live", hip.ptr(gate), hip.ptr(up), hip.ptr(act), hip.dtype_code(gate), R, C, hip.ptr(live),
+                     hip.stream())
+        else:
+            hip.call("dalm_swiglu_fwd", hip.ptr(gate), hip.ptr(up), hip.ptr(act), hip.dtype_code(gate), gate.numel(), hip.stream())
+        ctx.save_for_backward(gate, up, *keep)
         return act
 
     @staticmethod
     def backward(ctx, d_act):
-        gate, up = ctx.saved_tensors
+        gate, up, *keep = ctx.saved_tensors
+        live = keep[0] if keep else None
         d_act = d_act.contiguous()
         if ctx.halves:
             # gate / up read in place; d_gate and d_up leave as two CONTIGUOUS tensors: the two dgrad GEMMs then are the shapes
@@ -114,13 +129,18 @@ class _SwiGLU(torch.autograd.Function):
             R = gate.numel() // C
             dg = torch.empty(gate.shape, dtype=gate.dtype, device=gate.device)
             du = torch.empty(gate.shape, dtype=gate.dtype, device=gate.device)
-            hip.call("dalm_swiglu_bwd_2d", hip.ptr(d_act), hip.ptr(gate), hip.ptr(up), hip.ptr(dg), hip.ptr(du),
-                     hip.dtype_code(gate), R, C, C, 2 * C, 2 * C, C, C, hip.stream())
-            return dg, du
+            hip.call("dalm_swiglu_bwd_2d_live", hip.ptr(d_act), hip.ptr(gate), hip.ptr(up), hip.ptr(dg), hip.ptr(du),
+                     hip.dtype_code(gate), R, C, C, 2 * C, 2 * C, C, C, hip.ptr(live), hip.stream())
+            return dg, du, None
         dg, du = torch.empty_like(gate), torch.empty_like(up)
-        hip.call("dalm_swiglu_bwd", hip.ptr(d_act), hip.ptr(gate), hip.ptr(up), hip.ptr(dg), hip.ptr(du),
-                 hip.dtype_code(gate), gate.numel(), hip.stream())
-        return dg, du
+        if live is not None:
+            C = gate.shape[-1]
+            hip.call("dalm_swiglu_bwd_live", hip.ptr(d_act), hip.ptr(gate), hip.ptr(up), hip.ptr(dg), hip.ptr(du),
+                     hip.dtype_code(gate), gate.numel() // C, C, hip.ptr(live), hip.stream())
+        else:
+            hip.call("dalm_swiglu_bwd", hip.ptr(d_act), hip.ptr(gate), hip.ptr(up), hip.ptr(dg), hip.ptr(du),
+                     hip.dtype_code(gate), gate.numel(), hip.stream())
+        return dg, du, None
 
 
 def swiglu_supported(gate, up) -> bool:
@@ -128,9 +148,10 @@ def swiglu_supported(gate, up) -> bool:
             and up.shape == gate.shape)
 
 
-def swiglu(gate, up):
-    """silu(gate) * up."""
-    return _SwiGLU.apply(gate, up)
+def swiglu(gate, up, live=None):
+    """silu(gate) * up.  live: uint8 row liveness over the leading dimensions; None: that of the tower call in progress
+    (dalm_amd/live_rows.py), if any."""
+    return _SwiGLU.apply(gate, up, live)
 
 
 # ---------------------------------------------------------------------------
@@ -145,21 +166,21 @@ def rms_norm_supported(x: torch.Tensor, w: torch.Tensor) -> bool:
             and w.dtype == x.dtype and D % vec == 0 and D <= 64 * vec * 16)
 
 
-def _norm_fwd(x2, delta2, w, eps):
+def _norm_fwd(x2, delta2, w, eps, live=None):
     R, D = x2.shape
     y = torch.empty_like(x2)
     h = torch.empty_like(x2) if delta2 is not None else None
     rstd = torch.empty(R, device=x2.device, dtype=torch.float32)
-    hip.call("dalm_rms_norm_fwd", hip.ptr(x2), hip.ptr(delta2), hip.ptr(w), hip.dtype_code(x2), R, D, float(eps), hip.ptr(h),
-             hip.ptr(y), hip.ptr(rstd), hip.stream())
+    hip.call("dalm_rms_norm_fwd_live", hip.ptr(x2), hip.ptr(delta2), hip.ptr(w), hip.dtype_code(x2), R, D, float(eps), hip.ptr(h),
+             hip.ptr(y), hip.ptr(rstd), hip.ptr(live), hip.stream())
     return h, y, rstd
 
 
-def _norm_bwd(dy2, h2, w, rstd, dres2):
+def _norm_bwd(dy2, h2, w, rstd, dres2, live=None):
     R, D = h2.shape
     dx = torch.empty_like(h2)
-    hip.call("dalm_rms_norm_bwd", hip.ptr(dy2), hip.ptr(h2), hip.ptr(w), hip.ptr(rstd), hip.ptr(dres2), hip.dtype_code(h2), R, D,
-             hip.ptr(dx), hip.stream())
+    hip.call("dalm_rms_norm_bwd_live", hip.ptr(dy2), hip.ptr(h2), hip.ptr(w), hip.ptr(rstd), hip.ptr(dres2), hip.dtype_code(h2), R, D,
+             hip.ptr(dx), hip.ptr(live), hip.stream())
     return dx
 
 
@@ -181,32 +202,36 @@ class _AddRmsNorm(torch.autograd.Function):
     the gradient that reaches h through the residual path is added inside the norm's backward kernel."""
 
     @staticmethod
-    def forward(ctx, x, delta, w, eps):
+    def forward(ctx, x, delta, w, eps, live=None):
         D = x.shape[-1]
         w_c = w if w.dtype == x.dtype else w.to(x.dtype)
         x2 = _as_rows(x, D, x.dtype)
         d2 = _as_rows(delta, D, x.dtype) if delta is not None else None
-        h2, y2, rstd = _norm_fwd(x2, d2, w_c, eps)
-        ctx.save_for_backward(h2 if h2 is not None else x2, w_c, rstd)
+        if live is None:
+            live = live_rows.current(x2.shape[0], x2.device)
+        h2, y2, rstd = _norm_fwd(x2, d2, w_c, eps, live)
+        # (the liveness vector is kept: the backward runs after the tower call's context, on autograd's thread)
+        ctx.save_for_backward(h2 if h2 is not None else x2, w_c, rstd, *([live] if live is not None else []))
         ctx.shape, ctx.has_delta, ctx.w_dtype = x.shape, delta is not None, w.dtype
         h = h2.view(x.shape) if h2 is not None else x
         return h, y2.view(x.shape)
 
     @staticmethod
     def backward(ctx, dh, dy):
-        h2, w_c, rstd = ctx.saved_tensors
+        h2, w_c, rstd, *live = ctx.saved_tensors
         D = h2.shape[1]
         dy2 = _as_rows(dy, D, h2.dtype)
         dres2 = _as_rows(dh, D, h2.dtype) if dh is not None else None
-        d = _norm_bwd(dy2, h2, w_c, rstd, dres2).view(ctx.shape)
+        d = _norm_bwd(dy2, h2, w_c, rstd, dres2, live[0] if live else None).view(ctx.shape)
         dw = _weight_grad(dy2, h2, rstd).to(ctx.w_dtype) if ctx.needs_input_grad[2] else None
-        return d, (d if ctx.has_delta else None), dw, None
+        return d, (d if ctx.has_delta else None), dw, None, None
 
 
-def add_rms_norm(x, delta, w, eps):
+def add_rms_norm(x, delta, w, eps, live=None):
     """x + delta and its RMSNorm in one launch (one more in the backward, which also folds in the residual-path gradient).
-    delta = None: (x itself, rmsnorm(x) * w)."""
-    return _AddRmsNorm.apply(x, delta, w, eps)
+    delta = None: (x itself, rmsnorm(x) * w).  live: uint8 row liveness; None: that of the tower call in progress
+    (dalm_amd/live_rows.py), if any."""
+    return _AddRmsNorm.apply(x, delta, w, eps, live)
 
 
 # ---------------------------------------------------------------------------

@@ -270,21 +270,24 @@ class _RetrieverCall(torch.nn.Module):
     itself (AutoModelForSentenceEmbedding), its output is returned as is; otherwise its hidden states - of the PACKED rows when
     `rows` / `cu` are given (dalm_amd/packed.py) - go through the HIP pool / normalise."""
 
-    def __init__(self, tower, autocast_dtype, normalize: Optional[bool] = None):
+    def __init__(self, tower, autocast_dtype, normalize: Optional[bool] = None, skip_dead_rows: bool = True):
         super().__init__()
         self.tower = tower
         self.autocast_dtype = autocast_dtype
         self.normalize = normalize
+        self.skip_dead_rows = skip_dead_rows
 
     def forward(self, input_ids, attention_mask, rows=None, cu=None):
-        from .. import packed
+        from .. import live_rows, packed
         from ..fused import pool_l2norm
 
         with _autocast(self.autocast_dtype):
             if self.normalize is None:
-                return self.tower(input_ids, attention_mask)
-            if rows is None:
-                h = self.tower(input_ids, attention_mask)[0]
+                with live_rows.tower_call(attention_mask, False, self.skip_dead_rows):
+                    return self.tower(input_ids, attention_mask)
+            if rows is None:     # padded: the row-wise kernels skip the padding rows (dalm_amd/live_rows.py)
+                with live_rows.tower_call(attention_mask, False, self.skip_dead_rows):
+                    h = self.tower(input_ids, attention_mask)[0]
             else:
                 h = packed.retrieval_hidden(self.tower, input_ids, attention_mask, rows, cu)
         return pool_l2norm(h, attention_mask, self.normalize)
@@ -295,20 +298,23 @@ class _GeneratorCall(torch.nn.Module):
     consumes.  Given `rows` / `cu`: the final hidden states [n, H] of the packed rows, in the autocast dtype (what the reference's
     lm_head, an nn.Linear inside the autocast'ed forward, would read)."""
 
-    def __init__(self, generator, autocast_dtype, hidden_only: bool = False):
+    def __init__(self, generator, autocast_dtype, hidden_only: bool = False, skip_dead_rows: bool = True):
         super().__init__()
         self.generator = generator
         self.autocast_dtype = autocast_dtype
         self.hidden_only = hidden_only
+        self.skip_dead_rows = skip_dead_rows
 
     def forward(self, input_ids, attention_mask, rows=None, cu=None):
-        from .. import packed
+        from .. import live_rows, packed
 
         with _autocast(self.autocast_dtype):
-            if rows is None and self.hidden_only:
-                return self.generator.base_model(input_ids=input_ids, attention_mask=attention_mask, use_cache=False)[0]
-            if rows is None:     # no KV cache copies
-                return self.generator(input_ids=input_ids, attention_mask=attention_mask, use_cache=False).logits
+            if rows is None:     # padded: the row-wise kernels skip the rows nothing depends on (dalm_amd/live_rows.py)
+                with live_rows.tower_call(attention_mask, True, self.skip_dead_rows):
+                    if self.hidden_only:
+                        return self.generator.base_model(input_ids=input_ids, attention_mask=attention_mask, use_cache=False)[0]
+                    # no KV cache copies
+                    return self.generator(input_ids=input_ids, attention_mask=attention_mask, use_cache=False).logits
             h = packed.generator_hidden(self.generator, input_ids, attention_mask, rows, cu)
         dt = self.autocast_dtype
         return h if dt is None or h.dtype == dt else h.to(dt)
@@ -339,11 +345,11 @@ class GraphedEncoders:
     passage graphs run on the main stream); loss, optimizer and collectives stay eager.  Same reason as GraphedTowers at one rank:
     a whole-step graph captured across the two streams replays with a dependency bubble per node."""
 
-    def __init__(self, model, autocast_dtype, sample_batch: Dict[str, torch.Tensor]):
+    def __init__(self, model, autocast_dtype, sample_batch: Dict[str, torch.Tensor], skip_dead_rows: bool = True):
         if getattr(model, "is_autoregressive", False):
             raise NotImplementedError("graphed encoders: autoregressive retrievers run eagerly")
         warm_blas_handles()
-        calls = [_RetrieverCall(model, autocast_dtype) for _ in range(2)]
+        calls = [_RetrieverCall(model, autocast_dtype, skip_dead_rows=skip_dead_rows) for _ in range(2)]
         for c in calls:
             c.train(model.training)
         b = sample_batch
@@ -366,7 +372,8 @@ class GraphedTowers:
     loss with its stats exchange, the gradient all-reduce - and the optimizer stay eager.  That removes >99 %
     of the per-step launches from the host path while no collective is ever captured; it is what W > 1 uses."""
 
-    def __init__(self, rag_model, autocast_dtype, sample_batch: Dict[str, torch.Tensor], hidden_only: bool = False):
+    def __init__(self, rag_model, autocast_dtype, sample_batch: Dict[str, torch.Tensor], hidden_only: bool = False,
+                 skip_dead_rows: bool = True):
         if getattr(rag_model, "retriever_is_autoregressive", False):
             raise NotImplementedError("graphed towers: autoregressive retrievers run eagerly")
         warm_blas_handles()
@@ -374,8 +381,9 @@ class GraphedTowers:
         # around dalm_amd/packed.py's calls; the row counts are part of the key (one set of graphs per combination)
         self.packed = self.is_packed(sample_batch)
         retriever, normalize = rag_model.retriever_model, rag_model.normalize
-        calls = (_RetrieverCall(retriever, autocast_dtype, normalize), _RetrieverCall(retriever, autocast_dtype, normalize),
-                 _GeneratorCall(rag_model.generator_model, autocast_dtype, hidden_only))
+        calls = (_RetrieverCall(retriever, autocast_dtype, normalize, skip_dead_rows),
+                 _RetrieverCall(retriever, autocast_dtype, normalize, skip_dead_rows),
+                 _GeneratorCall(rag_model.generator_model, autocast_dtype, hidden_only, skip_dead_rows))
         for c in calls:
             c.train(rag_model.training)
         args = [tuple(t.clone() for t in self.args(sample_batch, tower)) for tower in ("passage", "query", "generator")]

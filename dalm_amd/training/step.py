@@ -18,6 +18,7 @@ import torch
 
 from .. import streams as _streams
 
+from .. import live_rows as _live_rows
 from .. import packed as _packed
 from ..fused import (GatherHandle, LocalComm, contrastive_loss, pool_l2norm, rag_e2e_loss, rag_e2e_loss_from_hidden,
                      rag_e2e_loss_packed)
@@ -37,8 +38,11 @@ def _advance_dropout(batch) -> None:
 
 class _StepBase:
     def __init__(self, model, optimizer, lr_scheduler, logit_scale, comm=None, autocast_dtype=None, ops=None,
-                 grad_overlap: bool = True, track_grad_norm: bool = False, grad_accum: int = 1):
+                 grad_overlap: bool = True, track_grad_norm: bool = False, grad_accum: int = 1, skip_dead_rows: bool = True):
         self.model, self.optimizer, self.lr_scheduler = model, optimizer, lr_scheduler
+        # padded tower calls tell the row-wise HIP kernels which rows nothing depends on (padding: dalm_amd/live_rows.py); those
+        # rows are then not read and leave as zeros - same loss, same gradients, less memory traffic.  False: every row is computed
+        self.skip_dead_rows = bool(skip_dead_rows)
         # global L2 norm of the (all-reduced) trainable gradients, left on the device in self.grad_norm right before
         # the optimizer consumes them - the quantity north_star's tolerance is stated on next to the loss
         self.track_grad_norm = track_grad_norm
@@ -199,7 +203,8 @@ class RagE2EStep(_StepBase):
                 and _packed.attention_is_packable(m.retriever_model)):
             key = None              # row lists for some towers only, or a model the packed call cannot serve: eager
         return self._tower_sets.get(
-            key, lambda: GraphedTowers(self.model, self.autocast_dtype, batch, hidden_only=self.fuse_lm_head))
+            key, lambda: GraphedTowers(self.model, self.autocast_dtype, batch, hidden_only=self.fuse_lm_head,
+                                       skip_dead_rows=self.skip_dead_rows))
 
     def _gather(self, emb):
         """Start the all-gather of an embedding matrix early on the side stream (overlaps the other tower)."""
@@ -216,7 +221,8 @@ class RagE2EStep(_StepBase):
         if rows is not None and not m.retriever_is_autoregressive and _packed.attention_is_packable(m.retriever_model):
             h = _packed.retrieval_hidden(m.retriever_model, ids, mask, rows, batch[f"retriever_{side}_pack_cu"])
             return pool_l2norm(h, mask, m.normalize)
-        return m("retrieval", ids, mask)
+        with _live_rows.tower_call(mask, False, self.skip_dead_rows):
+            return m("retrieval", ids, mask)
 
     def _towers(self, batch, towers: Optional[GraphedTowers]):
         pair = self._retrieve_pair(batch, "retriever_query", "retriever_passage") if towers is None else None
@@ -241,9 +247,10 @@ class RagE2EStep(_StepBase):
         gm = self.model.generator_model
         if packed:
             return _packed.generator_hidden(gm, ids, mask, batch["generator_pack_rows"], batch["generator_pack_cu"])
-        if self.fuse_lm_head:
-            return gm.base_model(input_ids=ids, attention_mask=mask, use_cache=False)[0]
-        return self.model("generation", ids, mask)
+        with _live_rows.tower_call(mask, True, self.skip_dead_rows):
+            if self.fuse_lm_head:
+                return gm.base_model(input_ids=ids, attention_mask=mask, use_cache=False)[0]
+            return self.model("generation", ids, mask)
 
     def _resolve_fuse(self, batch) -> None:
         """fuse_lm_head="auto": decided PER BATCH SHAPE (cached) - a later, longer batch that exceeds DALM_LOGITS_BUDGET_MB takes
@@ -327,7 +334,8 @@ class RetrieverStep(_StepBase):
         if rows is not None and not getattr(m, "is_autoregressive", False) and _packed.attention_is_packable(m.model):
             h = _packed.retrieval_hidden(m.model, ids, mask, rows, batch[f"{side}_pack_cu"])
             return pool_l2norm(h, mask, m.normalize)
-        return m(ids, mask)
+        with _live_rows.tower_call(mask, False, self.skip_dead_rows):
+            return m(ids, mask)
 
     def _embed_gather(self, batch, side: str):
         emb = self._embed(batch, side)
@@ -337,7 +345,8 @@ class RetrieverStep(_StepBase):
         self.towers = None
         if self.graph_towers:
             key = GraphedEncoders.key_of(batch) if "query_pack_rows" not in batch else None
-            self.towers = self._encoder_sets.get(key, lambda: GraphedEncoders(self.model, self.autocast_dtype, batch))
+            self.towers = self._encoder_sets.get(
+                key, lambda: GraphedEncoders(self.model, self.autocast_dtype, batch, skip_dead_rows=self.skip_dead_rows))
         _advance_dropout(batch)
         pair = None
         if self.towers is None:

@@ -472,6 +472,34 @@ int dalm_rms_norm_fwd(const void* x, const void* delta, const void* w, int dtype
                       void* y, float* rstd, dalm_stream_t stream);
 int dalm_rms_norm_bwd(const void* dy, const void* h, const void* w, const float* rstd, const void* dres, int dtype, int64_t R,
                       int64_t D, void* dx, dalm_stream_t stream);
+/* Row liveness.  The `_live` form of a row-wise kernel takes one more argument in front of the stream: `row_live`, R bytes in
+ * device memory, non-zero = the row matters (for the rotary kernel R = B T: one byte per (b, t), shared by all heads).  NULL =
+ * every row matters: the call then IS the function without the suffix (which is the `_live` form called with NULL).  With it:
+ *   - nothing of a dead row is loaded (activations, gradients, keep bits, per-row statistics) and nothing is computed for it;
+ *   - every freshly written output holds ZEROS in its dead rows (y, h_out, rstd, z, act, gradients: their readers - GEMMs,
+ *     attention - need finite values); a kernel that updates in place leaves dead rows untouched; keep bits of dead rows are
+ *     not written (only the same call's backward reads them, and it skips the same rows);
+ *   - live rows receive the same bits as without the vector; reductions over rows (colacc) keep their row partition and
+ *     summation order, a dead row enters as an exact zero.
+ * In a padded batch a row is dead when neither the loss nor any gradient depends on it (dalm_amd/packed.py).
+ * dalm_swiglu_{fwd,bwd}_live are the contiguous forms over [R, C] (row stride C; C a multiple of 16 bytes when row_live is given). */
+int dalm_rope_qk_live(const void* q, const void* k, void* q_out, void* k_out, const void* cos, const void* sin, int dtype,
+                      int64_t B, int64_t T, int64_t Hq, int64_t Hk, int64_t hd, const int64_t* q_strides,
+                      const int64_t* k_strides, const int64_t* qo_strides, const int64_t* ko_strides,
+                      const int64_t* cs_strides, int backward, const uint8_t* row_live, dalm_stream_t stream);
+int dalm_swiglu_fwd_live(const void* gate, const void* up, void* act, int dtype, int64_t R, int64_t C, const uint8_t* row_live,
+                         dalm_stream_t stream);
+int dalm_swiglu_bwd_live(const void* d_act, const void* gate, const void* up, void* d_gate, void* d_up, int dtype, int64_t R,
+                         int64_t C, const uint8_t* row_live, dalm_stream_t stream);
+int dalm_swiglu_fwd_2d_live(const void* gate, const void* up, void* act, int dtype, int64_t R, int64_t C, int64_t ld_gate,
+                            int64_t ld_up, int64_t ld_act, const uint8_t* row_live, dalm_stream_t stream);
+int dalm_swiglu_bwd_2d_live(const void* d_act, const void* gate, const void* up, void* d_gate, void* d_up, int dtype, int64_t R,
+                            int64_t C, int64_t ld_dact, int64_t ld_gate, int64_t ld_up, int64_t ld_dgate, int64_t ld_dup,
+                            const uint8_t* row_live, dalm_stream_t stream);
+int dalm_rms_norm_fwd_live(const void* x, const void* delta, const void* w, int dtype, int64_t R, int64_t D, float eps,
+                           void* h_out, void* y, float* rstd, const uint8_t* row_live, dalm_stream_t stream);
+int dalm_rms_norm_bwd_live(const void* dy, const void* h, const void* w, const float* rstd, const void* dres, int dtype, int64_t R,
+                           int64_t D, void* dx, const uint8_t* row_live, dalm_stream_t stream);
 
 /* Elementwise chains of a Falcon-7B decoder layer (transformers modeling_falcon.py FalconDecoderLayer.forward /
  * FalconMLP.forward / dropout_add, reached by the reference through self.generator_model(...),
@@ -507,6 +535,13 @@ int dalm_bert_add_norm_fwd(const void* a, const float* res, const void* w, const
 int dalm_bert_add_norm_bwd(const float* g32, const void* g16, const void* a, const float* res, const void* w, int w_bf16,
                            const uint8_t* keep_bits, const float* mean, const float* rstd, int64_t R, int64_t D, float dropout_p,
                            float* d_res, void* d_a, dalm_stream_t stream);
+/* The same with row liveness (see dalm_rope_qk_live): y32, y16, mean, rstd / d_res, d_a of a dead row are zeros. */
+int dalm_bert_add_norm_fwd_live(const void* a, const float* res, const void* w, const void* b, int w_bf16, int64_t R, int64_t D,
+                                float eps, float dropout_p, const void* seed, uint32_t salt, float* y32, void* y16,
+                                uint8_t* keep_bits, float* mean, float* rstd, const uint8_t* row_live, dalm_stream_t stream);
+int dalm_bert_add_norm_bwd_live(const float* g32, const void* g16, const void* a, const float* res, const void* w, int w_bf16,
+                                const uint8_t* keep_bits, const float* mean, const float* rstd, int64_t R, int64_t D,
+                                float dropout_p, float* d_res, void* d_a, const uint8_t* row_live, dalm_stream_t stream);
 
 /* Backward of scaled-dot-product attention, bf16, head width 128, boolean mask (dalm_amd/csrc/attn.hip).  Stands in for the
  * backward of torch.nn.functional.scaled_dot_product_attention as transformers' sdpa_attention_forward calls it inside
@@ -618,6 +653,17 @@ size_t dalm_lora2_colacc_ticket_words(int64_t C, int mode);
 int dalm_lora2_colacc(const void* x0, const void* x1, const float* z0, const float* z1, const void* bits0, const void* bits1,
                       float* out0, float* out1, int64_t R, int64_t C, int rank, float scale, int mode, void* ws,
                       size_t ws_bytes, uint32_t* tickets, dalm_stream_t stream);
+/* The same with row liveness (see dalm_rope_qk_live; one vector of R bytes for both slots): rowdot writes zero z rows and no keep
+ * bits for dead rows, rankupd leaves dead rows of y untouched, colacc adds dead rows as exact zeros without loading x, z or bits. */
+int dalm_lora2_rowdot_live(const void* x0, const void* x1, const float* W0, const float* W1, float* out0, float* out1, void* bits0,
+                           void* bits1, int64_t R, int64_t K, int rank, float scale, float p, const void* seed, uint32_t salt0,
+                           uint32_t salt1, int mode, const uint8_t* row_live, dalm_stream_t stream);
+int dalm_lora2_rankupd_live(void* y0, void* y1, const float* z0, const float* z1, const float* W0, const float* W1,
+                            const void* bits0, const void* bits1, int64_t R, int64_t C, int rank, float scale, int mode,
+                            const uint8_t* row_live, dalm_stream_t stream);
+int dalm_lora2_colacc_live(const void* x0, const void* x1, const float* z0, const float* z1, const void* bits0, const void* bits1,
+                           float* out0, float* out1, int64_t R, int64_t C, int rank, float scale, int mode, void* ws,
+                           size_t ws_bytes, uint32_t* tickets, const uint8_t* row_live, dalm_stream_t stream);
 
 /* ---- round 5: backward of the fused lm_head + marginalised CE ---------------------------------------
  * Replaces, for a FROZEN bias-free head,   logits = lm_head(hidden); loss(logits).backward()
