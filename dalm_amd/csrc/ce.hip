@@ -505,6 +505,9 @@ __global__ __launch_bounds__(BS) void marg_ce_stream_kernel(
     T* grow = dlogits + off;
     T* gbase = grow - w.lead;
     const float coef = mval / M;
+    // softmax = exp(x - max) / l, as the first pass took it: x - max is exact for rows at any offset, where exp(x - lse)
+    // carries the rounding of lse itself (5e-4 relative on a row shifted by 1e4)
+    const float inv = coef / l;
     // in-place safe only if every thread re-reads exactly the slots it writes: it does.
     for (int slot = tid; slot < w.nslots; slot += BS) {
       float v[VEC];
@@ -512,7 +515,7 @@ __global__ __launch_bounds__(BS) void marg_ce_stream_kernel(
 #pragma unroll
       for (int e = 0; e < VEC; ++e) {
         const int idx = slot * VEC + e - w.lead;
-        v[e] = coef * fast_exp(v[e] - lse) - ((idx == y) ? coef : 0.f);
+        v[e] = inv * fast_exp(v[e] - m) - ((idx == y) ? coef : 0.f);
       }
       if (!w.partial(slot)) {
         Elt<T>::store(gbase + static_cast<int64_t>(slot) * VEC, v);
