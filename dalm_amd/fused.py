@@ -22,7 +22,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass
-from typing import Any, Optional
+from typing import Any, NamedTuple, Optional
 
 import torch
 
@@ -138,7 +138,9 @@ class _ConState:
     S_cols: Optional[torch.Tensor] = None
 
 
-def _contrastive_forward(ops, comm, q, p, scale, q_all=None, p_all=None):
+def _contrastive_forward(ops, comm, q, p, scale, q_gather=None, p_gather=None):
+    q_all = q_gather.wait() if q_gather is not None else None
+    p_all = p_gather.wait() if p_gather is not None else None
     q = q.detach().float().contiguous()
     p = p.detach().float().contiguous()
     if q.shape != p.shape or q.dim() != 2:
@@ -185,15 +187,43 @@ def _contrastive_backward(ops, comm, st: _ConState, scale, a_local, b_local):
     return dq, dp
 
 
+def _rag_prologue(ops, comm, q, p, scale, q_gather, p_gather, mask, qlen):
+    """What both RAG-end2end nodes start with: (contrastive state, stats, N_b); stats[0] = M over the global batch."""
+    st = _contrastive_forward(ops, comm, q, p, scale, q_gather, p_gather)
+    stats, Nb, _Mb = ops.ce_prep(mask, qlen)
+    if not isinstance(comm, LocalComm):
+        comm.all_reduce_sum_(stats)  # stats[0] = M over the global batch (stats[1] becomes B_g)
+    return st, stats, Nb
+
+
+def _rag_finalize(ops, st, row_nll, Nb, stats, aux):
+    """The combined loss from the per-row NLL; fills `aux` when one is given."""
+    out3, doc_lp = ops.rag_loss_finalize(row_nll, Nb, st.lse_r, st.lse_c, st.diag, st.n_global, stats)
+    if aux is not None:
+        aux["contrastive"], aux["generator"] = out3[1], out3[2]
+        aux["doc_logprobs"], aux["num_target_tokens"] = doc_lp, stats[0]
+    return out3[0]
+
+
+def _embedding_grads(ctx, g, Nb=None, M=None):
+    """(dq, dp) of a node that kept st / scale / ops / comm / in_dtypes on ctx, g [1] f32.
+    dL/dS = (a_i softmax_row - ...) + (b_j softmax_col - ...),  b_j = g/(2B),  a_i = b_i (+ g N_i/M with the generator loss)."""
+    if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+        return None, None
+    st = ctx.st
+    b = (g / (2.0 * st.n_global)).expand(st.q.shape[0]).contiguous()
+    a = b if Nb is None else b + g * Nb / M
+    dq, dp = _contrastive_backward(ctx.ops, ctx.comm, st, ctx.scale, a, b)
+    return dq.to(ctx.in_dtypes[0]), dp.to(ctx.in_dtypes[1])
+
+
 # ---------------------------------------------------------------------------
 # retriever-only: symmetric in-batch-negatives loss
 # ---------------------------------------------------------------------------
 class _Contrastive(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, p, scale, ops, comm, q_gather, p_gather):
-        st = _contrastive_forward(ops, comm, q, p, scale,
-                                  q_gather.wait() if q_gather is not None else None,
-                                  p_gather.wait() if p_gather is not None else None)
+        st = _contrastive_forward(ops, comm, q, p, scale, q_gather, p_gather)
         loss, _ = ops.contrastive_finalize(st.lse_r, st.lse_c, st.diag, st.n_global)
         ctx.st, ctx.scale, ctx.ops, ctx.comm = st, scale, ops, comm
         ctx.in_dtypes = (q.dtype, p.dtype)
@@ -201,10 +231,7 @@ class _Contrastive(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        st = ctx.st
-        coef = (g.float() / (2.0 * st.n_global)).reshape(1).expand(st.q.shape[0]).contiguous()
-        dq, dp = _contrastive_backward(ctx.ops, ctx.comm, st, ctx.scale, coef, coef)
-        return dq.to(ctx.in_dtypes[0]), dp.to(ctx.in_dtypes[1]), None, None, None, None, None
+        return _embedding_grads(ctx, g.float().reshape(1)) + (None,) * 5
 
 
 def contrastive_loss(query_embs, passage_embs, logit_scale, *, comm=None, ops=None, q_gather=None, p_gather=None):
@@ -221,15 +248,9 @@ def contrastive_loss(query_embs, passage_embs, logit_scale, *, comm=None, ops=No
 class _RagE2E(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, p, logits, ids, mask, qlen, scale, ops, comm, fuse_grad, inplace_grad, q_gather, p_gather, aux):
-        st = _contrastive_forward(ops, comm, q, p, scale,
-                                  q_gather.wait() if q_gather is not None else None,
-                                  p_gather.wait() if p_gather is not None else None)
-        stats, Nb, _Mb = ops.ce_prep(mask, qlen)
-        if not isinstance(comm, LocalComm):
-            comm.all_reduce_sum_(stats)  # stats[0] = M over the global batch (stats[1] becomes B_g)
+        st, stats, Nb = _rag_prologue(ops, comm, q, p, scale, q_gather, p_gather, mask, qlen)
         need_grad = logits.requires_grad and fuse_grad
         row_lse, row_nll, dlogits = ops.ce_fwd(logits.detach(), ids, mask, stats, need_grad, inplace_grad)
-        out3, doc_lp = ops.rag_loss_finalize(row_nll, Nb, st.lse_r, st.lse_c, st.diag, st.n_global, stats)
         ctx.st, ctx.scale, ctx.ops, ctx.comm = st, scale, ops, comm
         ctx.in_dtypes = (q.dtype, p.dtype)
         ctx.fused = need_grad
@@ -237,16 +258,11 @@ class _RagE2E(torch.autograd.Function):
             ctx.save_for_backward(stats, Nb, dlogits)
         else:
             ctx.save_for_backward(stats, Nb, logits.detach(), ids, mask, row_lse)
-        if aux is not None:
-            aux["contrastive"] = out3[1]
-            aux["generator"] = out3[2]
-            aux["doc_logprobs"] = doc_lp
-            aux["num_target_tokens"] = stats[0]
-        return out3[0]
+        return _rag_finalize(ops, st, row_nll, Nb, stats, aux)
 
     @staticmethod
     def backward(ctx, g):
-        ops, st = ctx.ops, ctx.st
+        ops = ctx.ops
         g = g.float().reshape(1)
         if ctx.fused:
             stats, Nb, dlogits = ctx.saved_tensors
@@ -254,13 +270,7 @@ class _RagE2E(torch.autograd.Function):
         else:
             stats, Nb, logits, ids, mask, row_lse = ctx.saved_tensors
             dlogits = ops.ce_bwd(logits, ids, mask, stats, row_lse, g) if ctx.needs_input_grad[2] else None
-        dq = dp = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            # dL/dS = (a_i softmax_row - ...) + (b_j softmax_col - ...),  a_i = g (1/(2B) + N_i/M), b_j = g/(2B)
-            b = (g / (2.0 * st.n_global)).expand(st.q.shape[0]).contiguous()
-            a = b + g * Nb / stats[0]
-            dq, dp = _contrastive_backward(ops, ctx.comm, st, ctx.scale, a, b)
-            dq, dp = dq.to(ctx.in_dtypes[0]), dp.to(ctx.in_dtypes[1])
+        dq, dp = _embedding_grads(ctx, g, Nb, stats[0])
         return (dq, dp, dlogits) + (None,) * 11
 
 
@@ -398,101 +408,73 @@ def _row_chunks(rows: int, cap: int, unit: int):
     return [z for z in sizes if z > 0]
 
 
-def _use_two_contraction_kernels(ops, hc_all, w, dw, need_grad) -> bool:
-    """DALM_LM_HEAD_TRAIN_KERNEL=2: the row-chunk path below with BOTH contractions on the library's own bf16 MFMA kernels
-    (`dalm_lm_head_logits`, `dalm_lm_head_dhidden`) instead of hipBLASLt - the hand-written form of f1 WITHOUT the third
-    contraction (round 5 recomputed the logits for the backward): frozen bf16 head, V a multiple of 64, hidden width a multiple of 64."""
-    return (os.environ.get("DALM_LM_HEAD_TRAIN_KERNEL") == "2" and need_grad and dw is None and hc_all.is_cuda
-            and hc_all.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and w.shape[0] % 64 == 0 and w.shape[1] % 64 == 0
-            and hasattr(ops, "lm_head_logits"))
+# ---------------------------------------------------------------------------
+# The loss node behind `rag_e2e_loss_from_hidden` / `rag_e2e_loss_packed`: WHICH ROWS (`_lm_head_row_view`) x WHICH ENGINE
+# (`_lm_head_engine`).  K = DALM_LM_HEAD_KERNEL, T = DALM_LM_HEAD_TRAIN_KERNEL; "fits" = bf16 hidden states on the GPU,
+# H % 64 == 0 and the kernel in `ops` (for a gradient also: a frozen bf16 head).  T=1 where recompute does not fit raises.
+#
+#   rows               | no gradient wanted                       | gradient wanted
+#   -------------------+------------------------------------------+----------------------------------------------------
+#   all B*Tg           | lse if it fits and K=1, or K unset with  | recompute if it fits and T is not 0 / 2;
+#                      | a cache-sized head and no TunableOp; else sample_chunks (either column)
+#   live (host list)   | lse by the same rule; else mm_rows       | recompute if it fits and T is not 0 / 2; else
+#                      |                                          | logits_rows if T=2 fits (V % 64 == 0); else mm_rows
+#   packed             | mm_rows                                  | recompute if T=1; logits_rows if T=2 fits; else mm_rows
+#
+#   lse           `ops.lm_head_lse`, the forward-only MFMA kernel: no logits buffer
+#   recompute     `ops.lm_head_lse` + `ops.lm_head_backward`: logits recomputed per vocabulary chunk, nothing of size [rows, V]
+#   mm_rows       torch.mm x 2 around the fused CE kernel per row chunk
+#   logits_rows   the same chunks on `ops.lm_head_logits` / ONE `ops.lm_head_dhidden`
+#   sample_chunks `hc @ w.t()` per `chunk_samples` samples, the CE kernel on the real [b, Tg, V] layout
+# ---------------------------------------------------------------------------
+class _Rows(NamedTuple):
+    """The rows the head runs on, compact: row r predicts ids[r] (already shifted) with weight weights[r].  For `restore`:
+    shape = (B, Tg) of the padded layout (None: packed rows stay packed); inv (live rows) = flat row -> compact row, n if unlisted."""
+    h: torch.Tensor                         # [n, H]
+    ids: torch.Tensor                       # [n]
+    weights: torch.Tensor                   # [n]
+    shape: Optional[tuple] = None
+    inv: Optional[torch.Tensor] = None      # [B*Tg]
+
+    def labels(self):                       # ids, -1 on rows without weight: what the MFMA kernels take
+        return torch.where(self.weights != 0, self.ids, torch.full_like(self.ids, -1))
+
+    def restore(self, dh_c, nll_c):
+        """(d hidden, row_nll) in the caller's layout from an engine's compact results of n or n + 1 rows (row n: zero).
+        Packed rows: as they are.  All rows: a view.  Live rows: ONE gather each through the inverse map (dead rows -> the zero
+        row) instead of a zero fill plus a scatter (43 -> ~20 us at cfg3)."""
+        n, H = self.h.shape
+
+        def back(x):
+            if x is None or self.inv is None:
+                return x if x is None else x[:n]
+            if x.shape[0] == n:
+                x = torch.cat((x, x.new_zeros((1,) + x.shape[1:])), dim=0)
+            return x.index_select(0, self.inv)
+
+        dh, nll = back(dh_c), back(nll_c)
+        return (dh if dh is None or self.shape is None else dh.view(*self.shape, H)), nll
 
 
-def _lm_head_rows(ops, hc_all, w, ids_c, mask_c, stats, chunk_rows, dw, need_grad=True):
-    """lm_head + marginalised CE + d(hidden) of a COMPACT list of rows: hc_all [Rp, H] hidden states, ids_c / mask_c [Rp] the
-    label and the weight of each row (already shifted: row r predicts ids_c[r] with weight mask_c[r]).  The CE kernel sees each
-    row chunk as one virtual sample [1, n+1, V] whose shifted labels are the chunk's labels (row n is the kernel's always-dead
-    last position), so its code path and numerics are the uncompacted ones.  Returns (dh_c [Rp + 1, H] or None, nll_c [Rp + 1]):
-    the extra last row is zero (the target of dead rows when a caller maps back to a padded layout)."""
-    Rp, H = hc_all.shape
-    V = w.shape[0]
-    dh_c = torch.empty((Rp + 1, H), device=hc_all.device, dtype=hc_all.dtype) if need_grad else None
-    nll_c = torch.empty((Rp + 1,), device=hc_all.device, dtype=torch.float32)
-    if need_grad:
-        dh_c[Rp].zero_()
-    nll_c[Rp].zero_()
-    zero1 = ids_c.new_zeros((1,))
-    r1 = 0
-    kernels2 = _use_two_contraction_kernels(ops, hc_all, w, dw, need_grad)
-    wt = None
-    if kernels2:
-        from .models.frozen_linear import dgrad_weight
-
-        wt = dgrad_weight(w, torch.bfloat16)                     # the head's transposed copy [K, V] (frozen: made once)
-        if wt is None:
-            wt = w.t().contiguous()
-    if kernels2:
-        # both contractions on the library's own kernels.  The logits GEMM and the CE run per row chunk (the chunk is still in the
-        # Infinity Cache when the CE reads it); d(logits) of ALL chunks stays in one [Rp + 1, V] buffer and is contracted by
-        # ONE dalm_lm_head_dhidden launch: its 256 x 256 output tiles number (Rp / 256) x (K / 256) - a 2048-row chunk alone gives
-        # 128 tiles on a 256-CU part (measured 2.4 x the library path that way)
-        sizes = _row_chunks(Rp, chunk_rows, gemm_wave_rows(V))
-        big = torch.empty((Rp + 1, V), device=hc_all.device, dtype=hc_all.dtype)
-        for n in sizes:
-            # GEMM of chunk i, then its CE in place.  The CE kernel's virtual sample [1, n + 1, V] has ONE always-dead last row whose
-            # gradient it zeroes: that is the first row of chunk i + 1 (not computed yet - its own GEMM writes it next) or, for the
-            # last chunk, the extra row Rp
-            r0, r1 = r1, r1 + n
-            ops.lm_head_logits(hc_all[r0:r1], w, big[r0:r1])
-            ids_v = torch.cat((zero1, ids_c[r0:r1])).view(1, n + 1)
-            mask_v = torch.cat((zero1.to(mask_c.dtype), mask_c[r0:r1])).view(1, n + 1)
-            _lse, nll_v, _dl = ops.ce_fwd(big[r0:r1 + 1].view(1, n + 1, V), ids_v, mask_v, stats, True, True)
-            nll_c[r0:r1] = nll_v.reshape(-1)[:n]
-        dh_c[:Rp] = ops.lm_head_dhidden(big[:Rp], wt)
-        return dh_c, nll_c
-    for n in _row_chunks(Rp, chunk_rows, gemm_wave_rows(V)):
-        r0, r1 = r1, r1 + n
-        buf = torch.empty((n + 1, V), device=hc_all.device, dtype=hc_all.dtype)
-        if kernels2:
-            ops.lm_head_logits(hc_all[r0:r1], w, buf)
-        else:
-            torch.mm(hc_all[r0:r1], w.t(), out=buf[:n])
-        ids_v = torch.cat((zero1, ids_c[r0:r1])).view(1, n + 1)
-        mask_v = torch.cat((zero1.to(mask_c.dtype), mask_c[r0:r1])).view(1, n + 1)
-        _lse, nll_v, dl_v = ops.ce_fwd(buf.view(1, n + 1, V), ids_v, mask_v, stats, need_grad, need_grad)
-        nll_c[r0:r1] = nll_v.reshape(-1)[:n]
-        if not need_grad:
-            continue
-        dl2 = dl_v.view(n + 1, V)[:n]
-        if kernels2:
-            dh_c[r0:r1] = ops.lm_head_dhidden(dl2, wt)
-            continue
-        torch.mm(dl2, w, out=dh_c[r0:r1])
-        if dw is not None:
-            dw.addmm_(dl2.t().float(), hc_all[r0:r1].float())
-    return dh_c, nll_c
-
-
-def _lm_head_live_rows(ops, h, w, ids, mask, stats, live_rows, chunk_rows, dw, need_grad=True):
-    """lm_head + marginalised CE + d(hidden) over the live rows only.  Padding rows (38 % of bench.py's cfg3 batch, and
-    whatever padding='max_length' leaves in real data) carry no loss and a zero gradient, so both GEMMs and the CE pass
-    skip them (`_lm_head_rows` on the gathered rows)."""
+def _lm_head_row_view(h, ids, mask, live_rows, packed) -> _Rows:
+    """packed = (labels [n], weights [n]) of the PACKED generator rows h [n, H] (dalm_amd/packed.py), already shifted.  Else
+    h [B, Tg, H], ids / mask [B, Tg]: row (b, t) predicts ids[b, t + 1] with weight mask[b, t + 1] (0 at t = Tg - 1) - every
+    row, or the rows `live_rows` lists (its -1 entries: weight 0)."""
+    if packed is not None:
+        return _Rows(h, packed[0], packed[1])
     B, Tg, H = h.shape
-    R, Rp = B * Tg, live_rows.numel()
-    valid = live_rows >= 0
-    rows = live_rows.clamp_min(0)
-    dst = torch.where(valid, rows, torch.full_like(rows, R))       # padding entries land in a dump row
+    R = B * Tg
+    if live_rows is None:
+        nxt_ids = torch.cat((ids[:, 1:], ids[:, :1]), dim=1).reshape(-1)
+        nxt_mask = torch.cat((mask[:, 1:], torch.zeros_like(mask[:, :1])), dim=1).reshape(-1)
+        return _Rows(h.reshape(R, H), nxt_ids, nxt_mask, (B, Tg))
+    Rp, valid, rows = live_rows.numel(), live_rows >= 0, live_rows.clamp_min(0)
     nxt = rows + 1                                                  # live rows have t < Tg-1: same sample
-    ids_c = ids.reshape(-1).index_select(0, nxt)
-    mask_c = mask.reshape(-1).index_select(0, nxt) * valid.to(mask.dtype)
-    hc_all = h.reshape(R, H).index_select(0, rows)
-    # results land in [Rp+1]-row buffers whose last row stays zero; the full-size outputs are then ONE gather each through
-    # the inverse map (dead rows -> the zero row) instead of a zero fill plus a scatter (43 -> ~20 us at cfg3)
-    dh_c, nll_c = _lm_head_rows(ops, hc_all, w, ids_c, mask_c, stats, chunk_rows, dw, need_grad)
+    dst = torch.where(valid, rows, torch.full_like(rows, R))       # padding entries land in inv[R] (unused)
     inv = torch.full((R + 1,), Rp, device=h.device, dtype=torch.int64)
-    inv.scatter_(0, dst, torch.arange(Rp, device=h.device, dtype=torch.int64))   # padding entries land in inv[R] (unused)
-    dh = dh_c.index_select(0, inv[:R]).view(B, Tg, H) if need_grad else None
-    row_nll = nll_c.index_select(0, inv[:R])
-    return dh, row_nll
+    inv.scatter_(0, dst, torch.arange(Rp, device=h.device, dtype=torch.int64))
+    return _Rows(h.reshape(R, H).index_select(0, rows), ids.reshape(-1).index_select(0, nxt),
+                 mask.reshape(-1).index_select(0, nxt) * valid.to(mask.dtype), (B, Tg), inv[:R])
 
 
 # bytes of lm_head weight the fused kernel is preferred up to: 1.1 x the 256 MiB Infinity Cache.  Measured
@@ -503,175 +485,192 @@ def _lm_head_live_rows(ops, h, w, ids, mask, stats, live_rows, chunk_rows, dw, n
 _LM_HEAD_KERNEL_MAX_WEIGHT_BYTES = int(1.1 * (256 << 20))
 
 
-def _use_lm_head_kernel(ops, h, H, w=None) -> bool:
-    """Evaluation (no gradient wanted) through the library's own bf16 MFMA kernel (`dalm_lm_head_lse_fwd`: lm_head +
-    log-sum-exp + label gather in one kernel, no logits buffer at all).  Default since round 4 where it measured faster:
-    lm_head weights that fit the Infinity Cache (see above) while the library runs on its default heuristics (no tuned
-    solution table); DALM_LM_HEAD_KERNEL=1 / 0 forces it on / off."""
-    import os
-
-    if not (h.is_cuda and h.dtype == torch.bfloat16 and H % 64 == 0 and hasattr(ops, "lm_head_lse")):
-        return False
-    env = os.environ.get("DALM_LM_HEAD_KERNEL")
-    if env is not None:
-        return env == "1"
-    if w is None or w.dtype != torch.bfloat16 or w.numel() * 2 > _LM_HEAD_KERNEL_MAX_WEIGHT_BYTES:
-        return False
-    # With the pre-tuned GEMM solution table replayed (dalm_amd.tuning - the trainers and bench.py switch it on) the library
-    # path wins at the row counts the table holds (cfg3 live rows, chunks [2048, 1536]: 0.79 vs 0.84 ms,
-    # profiles/history/r04_lm_head_eval_paths.txt): the kernel is the default where the library runs on its default heuristics.
-    try:
-        import torch.cuda.tunable as tunable
-
-        if tunable.is_enabled():
-            return False
-    except Exception:
-        pass
-    return True
-
-
-def _lm_head_nll_kernel(ops, h, w, ids, mask, live_rows):
-    """row_nll [B*Tg] = mask-weighted NLL of the shifted labels, computed by the MFMA kernel over all rows or the live ones."""
-    B, Tg, H = h.shape
-    R = B * Tg
-    nxt_ids = torch.cat((ids[:, 1:], ids[:, :1]), dim=1).reshape(-1)
-    nxt_mask = torch.cat((mask[:, 1:], torch.zeros_like(mask[:, :1])), dim=1).reshape(-1)
-    labels = torch.where(nxt_mask != 0, nxt_ids, torch.full_like(nxt_ids, -1))
-    if live_rows is None:
-        _lse, nll = ops.lm_head_lse(h.reshape(R, H), w, labels)
-        return nll * nxt_mask.to(nll.dtype)
-    valid = live_rows >= 0
-    rows = live_rows.clamp_min(0)
-    lab_c = torch.where(valid, labels.index_select(0, rows), torch.full_like(rows, -1))
-    _lse, nll_c = ops.lm_head_lse(h.reshape(R, H).index_select(0, rows), w, lab_c)
-    nll_c = nll_c * nxt_mask.index_select(0, rows).to(nll_c.dtype) * valid.to(nll_c.dtype)
-    out = torch.zeros((R + 1,), device=h.device, dtype=torch.float32)
-    return out.index_copy_(0, torch.where(valid, rows, torch.full_like(rows, R)), nll_c)[:R]
-
-
-def _use_lm_head_train_kernel(ops, h, H, w, need_dw: bool) -> bool:
-    """TRAINING through the library's own bf16 MFMA kernels end to end (round 5): forward `dalm_lm_head_lse_fwd`,
-    backward `HipOps.lm_head_backward` (logits recomputed per vocabulary chunk; nothing of size [rows, V] is ever allocated -
-    the workspace is two chunk-sized staging buffers, <= 160 MB).  Taken when the head is frozen (LoRA: every BASELINE
-    configuration with a 7B generator) and bf16; a trainable head keeps the chunked library path below (it needs dW as well).
-    DALM_LM_HEAD_TRAIN_KERNEL=0 keeps the library path, =1 insists (raises when the shapes do not fit)."""
-    import os
-
-    env = os.environ.get("DALM_LM_HEAD_TRAIN_KERNEL")
-    ok = (h.is_cuda and h.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and H % 64 == 0 and not need_dw
-          and hasattr(ops, "lm_head_backward"))
-    if env == "1" and not ok:
+def _lm_head_engine(*, selection, need_grad, need_dw, cuda, h_dtype, w_dtype, H, V, weight_bytes, tunable, has,
+                    env_kernel, env_train_kernel) -> str:
+    """Name of the engine for one call (the table above) from plain facts: w_dtype / weight_bytes are the head's as it is
+    multiplied, `tunable` whether TunableOp replays a solution table, `has` the optional methods of `ops`, env_* the values of
+    DALM_LM_HEAD_KERNEL / DALM_LM_HEAD_TRAIN_KERNEL (None: unset).
+    lse is the no-gradient default since round 4 where it measured faster: heads that fit the Infinity Cache while the library
+    runs on its default heuristics (with the tuned table the library wins at the row counts it holds - cfg3 live rows, chunks
+    [2048, 1536]: 0.79 vs 0.84 ms, profiles/history/r04_lm_head_eval_paths.txt).  recompute (round 5) is for a
+    frozen head (LoRA: every BASELINE configuration with a 7B generator); a trainable one needs dW and keeps the library.
+    What the code has always done, kept as it is:
+    * packed rows take recompute only on =1, padded rows (all, live) take it by default;
+    * =2 is silently ignored on the all-rows padded route;
+    * packed evaluation never takes lse."""
+    mfma = cuda and h_dtype == torch.bfloat16 and H % 64 == 0
+    if not need_grad:
+        wanted = env_kernel == "1" if env_kernel is not None else (
+            w_dtype == torch.bfloat16 and weight_bytes <= _LM_HEAD_KERNEL_MAX_WEIGHT_BYTES and not tunable)
+        if wanted and selection != "packed" and mfma and "lm_head_lse" in has:
+            return "lse"
+        return "sample_chunks" if selection == "all" else "mm_rows"
+    frozen = mfma and w_dtype == torch.bfloat16 and not need_dw
+    fits = frozen and "lm_head_backward" in has
+    if env_train_kernel == "1" and not fits:
         raise RuntimeError("DALM_LM_HEAD_TRAIN_KERNEL=1 needs bf16 hidden states, a frozen bf16 head and a hidden width that is a "
                            "multiple of 64")
-    return ok and env not in ("0", "2")        # "2": the two-contraction form inside _lm_head_rows
+    if fits and (env_train_kernel == "1" if selection == "packed" else env_train_kernel not in ("0", "2")):
+        return "recompute"
+    if selection == "all":
+        return "sample_chunks"
+    if env_train_kernel == "2" and frozen and V % 64 == 0 and "lm_head_logits" in has:
+        return "logits_rows"
+    return "mm_rows"
 
 
-def _lm_head_train_kernel(ops, h, w, ids, mask, stats, live_rows):
-    """(d hidden [B, Tg, H], row_nll [B*Tg]) through the hand-written kernels; rows = the live ones when `live_rows` is given."""
+def _pick_lm_head_engine(ops, h, w, need_grad, need_dw, selection) -> str:
+    """`_lm_head_engine` on the facts of this call: the only place that reads the two variables, at every call."""
+    try:
+        import torch.cuda.tunable as tunable
+        tuned = bool(tunable.is_enabled())
+    except Exception:
+        tuned = False
+    return _lm_head_engine(
+        selection=selection, need_grad=need_grad, need_dw=need_dw, cuda=h.is_cuda, h_dtype=h.dtype, w_dtype=w.dtype,
+        H=h.shape[-1], V=w.shape[0], weight_bytes=w.numel() * w.element_size(), tunable=tuned,
+        has=frozenset(m for m in ("lm_head_lse", "lm_head_backward", "lm_head_logits") if hasattr(ops, m)),
+        env_kernel=os.environ.get("DALM_LM_HEAD_KERNEL"), env_train_kernel=os.environ.get("DALM_LM_HEAD_TRAIN_KERNEL"))
+
+
+# Engines: (ops, rows, w, stats, chunk_rows, dw, need_grad) -> (dh_c or None, nll_c) over the compact rows, n or n + 1 of them.
+def _lm_head_nll_kernel(ops, rows, w, stats, chunk_rows, dw, need_grad):
+    """lse: `dalm_lm_head_lse_fwd` - lm_head + log-sum-exp + label gather in one kernel, no logits buffer at all."""
+    _lse, nll_c = ops.lm_head_lse(rows.h, w, rows.labels())
+    return None, nll_c * rows.weights.to(nll_c.dtype)
+
+
+def _lm_head_train_kernel(ops, rows, w, stats, chunk_rows, dw, need_grad):
+    """recompute: the hand-written kernels end to end, forward `dalm_lm_head_lse_fwd`, backward `HipOps.lm_head_backward`."""
+    labels = rows.labels()
+    coef = rows.weights.to(torch.float32) / stats[0]                         # m_bt / M  (SURVEY 8a)
+    lse, nll_c = ops.lm_head_lse(rows.h, w, labels)
+    dh_c = ops.lm_head_backward(rows.h, w, labels, lse, coef)
+    return dh_c, nll_c * (coef != 0).to(nll_c.dtype)
+
+
+def _rows_out(rows, need_grad):
+    """(dh_c [n + 1, H] or None, nll_c [n + 1]) with the extra last row zero: the target of dead rows in `_Rows.restore`."""
+    n, H = rows.h.shape
+    dh_c = rows.h.new_empty((n + 1, H)) if need_grad else None
+    nll_c = rows.h.new_empty((n + 1,), dtype=torch.float32)
+    if need_grad:
+        dh_c[n].zero_()
+    nll_c[n].zero_()
+    return dh_c, nll_c
+
+
+def _ce_row_chunk(ops, buf, rows, r0, r1, stats, need_grad):
+    """The fused CE kernel on the logits buf [n + 1, V] of rows r0:r1, in place: it sees the chunk as one virtual sample
+    [1, n + 1, V] whose shifted labels are the chunk's labels (row n is the kernel's always-dead last position), so its code
+    path and numerics are the uncompacted ones.  Returns (nll [n], d(logits) [n, V] or None)."""
+    n = r1 - r0
+    zero1 = rows.ids.new_zeros((1,))
+    ids_v = torch.cat((zero1, rows.ids[r0:r1])).view(1, n + 1)
+    mask_v = torch.cat((zero1.to(rows.weights.dtype), rows.weights[r0:r1])).view(1, n + 1)
+    _lse, nll_v, dl_v = ops.ce_fwd(buf.view(1, n + 1, buf.shape[-1]), ids_v, mask_v, stats, need_grad, need_grad)
+    return nll_v.reshape(-1)[:n], (dl_v.view(n + 1, -1)[:n] if need_grad else None)
+
+
+def _lm_head_rows(ops, rows, w, stats, chunk_rows, dw, need_grad):
+    """mm_rows: logits_c = h_c W^T -> the fused CE kernel -> dh_c = dlogits_c W (and dW += dlogits_c^T h_c) per row chunk."""
+    n, V = rows.h.shape[0], w.shape[0]
+    dh_c, nll_c = _rows_out(rows, need_grad)
+    r1 = 0
+    for m in _row_chunks(n, chunk_rows, gemm_wave_rows(V)):
+        r0, r1 = r1, r1 + m
+        buf = torch.empty((m + 1, V), device=rows.h.device, dtype=rows.h.dtype)
+        torch.mm(rows.h[r0:r1], w.t(), out=buf[:m])
+        nll_c[r0:r1], dl2 = _ce_row_chunk(ops, buf, rows, r0, r1, stats, need_grad)
+        if not need_grad:
+            continue
+        torch.mm(dl2, w, out=dh_c[r0:r1])
+        if dw is not None:
+            dw.addmm_(dl2.t().float(), rows.h[r0:r1].float())
+    return dh_c, nll_c
+
+
+def _lm_head_logits_rows(ops, rows, w, stats, chunk_rows, dw, need_grad):
+    """logits_rows: the row chunks of `_lm_head_rows` with BOTH contractions on the library's own bf16 MFMA kernels
+    (`dalm_lm_head_logits`, `dalm_lm_head_dhidden`) instead of hipBLASLt - the hand-written form of f1 WITHOUT the third
+    contraction.  The logits GEMM and the CE run per row chunk (still in the Infinity Cache when the CE reads it); d(logits) of
+    ALL chunks stays in one [n + 1, V] buffer for ONE dalm_lm_head_dhidden launch: its 256 x 256 output tiles number (n / 256)
+    x (K / 256) - a 2048-row chunk alone gives 128 tiles on a 256-CU part (measured 2.4 x the library path that way)."""
+    from .models.frozen_linear import dgrad_weight
+
+    n, V = rows.h.shape[0], w.shape[0]
+    dh_c, nll_c = _rows_out(rows, True)
+    wt = dgrad_weight(w, torch.bfloat16)                     # the head's transposed copy [K, V] (frozen: made once)
+    if wt is None:
+        wt = w.t().contiguous()
+    big = torch.empty((n + 1, V), device=rows.h.device, dtype=rows.h.dtype)
+    r1 = 0
+    for m in _row_chunks(n, chunk_rows, gemm_wave_rows(V)):
+        # GEMM of chunk i, then its CE in place.  The always-dead last row of the CE kernel's virtual sample, whose gradient it
+        # zeroes, is the first row of chunk i + 1 (not computed yet - its own GEMM writes it next) or, for the last chunk, row n
+        r0, r1 = r1, r1 + m
+        ops.lm_head_logits(rows.h[r0:r1], w, big[r0:r1])
+        nll_c[r0:r1], _dl = _ce_row_chunk(ops, big[r0:r1 + 1], rows, r0, r1, stats, True)
+    dh_c[:n] = ops.lm_head_dhidden(big[:n], wt)
+    return dh_c, nll_c
+
+
+_LM_HEAD_ROW_ENGINES = {"lse": _lm_head_nll_kernel, "recompute": _lm_head_train_kernel, "mm_rows": _lm_head_rows,
+                        "logits_rows": _lm_head_logits_rows}
+
+
+def _lm_head_sample_chunks(ops, h, w, ids, mask, stats, chunk, dw, need_grad):
+    """sample_chunks: all rows in the padded layout, `chunk` samples at a time - the chunk shapes `chunk_samples` promises
+    and the GEMMs are tuned for; the CE kernel shifts the labels itself.  Returns (dh [B, Tg, H] or None, row_nll [B*Tg])."""
     B, Tg, H = h.shape
-    R = B * Tg
-    nxt_ids = torch.cat((ids[:, 1:], ids[:, :1]), dim=1).reshape(-1)
-    nxt_mask = torch.cat((mask[:, 1:], torch.zeros_like(mask[:, :1])), dim=1).reshape(-1)
-    coef_all = nxt_mask.to(torch.float32) / stats[0]                         # m_bt / M  (SURVEY 8a)
-    labels_all = torch.where(nxt_mask != 0, nxt_ids, torch.full_like(nxt_ids, -1))
-    if live_rows is None:
-        hc, labels, coef = h.reshape(R, H), labels_all, coef_all
-    else:
-        valid = live_rows >= 0
-        rows = live_rows.clamp_min(0)
-        hc = h.reshape(R, H).index_select(0, rows)
-        labels = torch.where(valid, labels_all.index_select(0, rows), torch.full_like(rows, -1))
-        coef = coef_all.index_select(0, rows) * valid.to(torch.float32)
-    _lse, nll_c = ops.lm_head_lse(hc, w, labels)
-    dh_c = ops.lm_head_backward(hc, w, labels, _lse, coef)
-    nll_c = nll_c * (coef != 0).to(nll_c.dtype)
-    if live_rows is None:
-        return dh_c.view(B, Tg, H), nll_c
-    Rp = live_rows.numel()
-    inv = torch.full((R + 1,), Rp, device=h.device, dtype=torch.int64)
-    dst = torch.where(valid, rows, torch.full_like(rows, R))
-    inv.scatter_(0, dst, torch.arange(Rp, device=h.device, dtype=torch.int64))
-    dh_pad = torch.cat((dh_c, dh_c.new_zeros((1, H))), dim=0)
-    nll_pad = torch.cat((nll_c, nll_c.new_zeros((1,))), dim=0)
-    return dh_pad.index_select(0, inv[:R]).view(B, Tg, H), nll_pad.index_select(0, inv[:R])
+    dh = torch.empty_like(h) if need_grad else None
+    row_nll = torch.empty((B * Tg,), device=h.device, dtype=torch.float32)
+    for b0 in range(0, B, chunk):
+        b1 = min(B, b0 + chunk)
+        hc = h[b0:b1].reshape(-1, H)
+        logits_c = (hc @ w.t()).view(b1 - b0, Tg, -1)
+        _lse, nll_c, dl_c = ops.ce_fwd(logits_c, ids[b0:b1], mask[b0:b1], stats, need_grad, need_grad)
+        row_nll[b0 * Tg:b1 * Tg] = nll_c
+        if not need_grad:
+            continue
+        dl2 = dl_c.view(-1, dl_c.shape[-1])
+        torch.mm(dl2, w, out=dh[b0:b1].view(-1, H))
+        if dw is not None:
+            dw.addmm_(dl2.t().float(), hc.float())
+    return dh, row_nll
 
 
 class _LMHeadRagE2E(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, p, hidden, weight, ids, mask, qlen, scale, ops, comm, chunk, q_gather, p_gather, aux, live_rows=None,
                 packed=None):
-        st = _contrastive_forward(ops, comm, q, p, scale,
-                                  q_gather.wait() if q_gather is not None else None,
-                                  p_gather.wait() if p_gather is not None else None)
-        stats, Nb, _Mb = ops.ce_prep(mask, qlen)
-        if not isinstance(comm, LocalComm):
-            comm.all_reduce_sum_(stats)
-        B, Tg = mask.shape
-        H = hidden.shape[-1]
+        st, stats, Nb = _rag_prologue(ops, comm, q, p, scale, q_gather, p_gather, mask, qlen)
         h = hidden.detach()
         w = weight.detach().to(h.dtype)
         need_dw = weight.requires_grad
         dw = torch.zeros(w.shape, device=w.device, dtype=torch.float32) if need_dw else None
         # evaluation (torch.no_grad(), or nothing upstream wants a gradient): forward-only CE, no d(hidden) GEMM
         need_grad = need_dw or any(ctx.needs_input_grad[:3])
-        if packed is not None:
-            # hidden is [n, H]: the PACKED generator rows (dalm_amd/packed.py), packed = (labels [n], weights [n]) already
-            # shifted.  Nothing maps back to a padded layout: the loss only sums row_nll, d(hidden) stays packed.
-            ids_c, mask_c = packed
-            if need_grad and _use_lm_head_train_kernel(ops, h, H, w, need_dw) and os.environ.get("DALM_LM_HEAD_TRAIN_KERNEL") == "1":
-                labels = torch.where(mask_c != 0, ids_c, torch.full_like(ids_c, -1))
-                coef = mask_c.to(torch.float32) / stats[0]
-                _lse, row_nll = ops.lm_head_lse(h, w, labels)
-                dh = ops.lm_head_backward(h, w, labels, _lse, coef)
-                row_nll = row_nll * (coef != 0).to(row_nll.dtype)
-            else:
-                dh_c, nll_c = _lm_head_rows(ops, h, w, ids_c, mask_c, stats, chunk * Tg, dw, need_grad)
-                dh = dh_c[:-1] if need_grad else None
-                row_nll = nll_c[:-1]
-        elif not need_grad and _use_lm_head_kernel(ops, h, H, w):
-            dh, row_nll = None, _lm_head_nll_kernel(ops, h, w, ids, mask, live_rows)
-        elif need_grad and _use_lm_head_train_kernel(ops, h, H, w, need_dw):
-            dh, row_nll = _lm_head_train_kernel(ops, h, w, ids, mask, stats, live_rows)
-        elif live_rows is None:
-            dh = torch.empty_like(h) if need_grad else None
-            row_nll = torch.empty((B * Tg,), device=h.device, dtype=torch.float32)
-            for b0 in range(0, B, chunk):
-                b1 = min(B, b0 + chunk)
-                hc = h[b0:b1].reshape(-1, H)
-                logits_c = (hc @ w.t()).view(b1 - b0, Tg, -1)
-                _lse, nll_c, dl_c = ops.ce_fwd(logits_c, ids[b0:b1], mask[b0:b1], stats, need_grad, need_grad)
-                row_nll[b0 * Tg:b1 * Tg] = nll_c
-                if not need_grad:
-                    continue
-                dl2 = dl_c.view(-1, dl_c.shape[-1])
-                torch.mm(dl2, w, out=dh[b0:b1].view(-1, H))
-                if need_dw:
-                    dw.addmm_(dl2.t().float(), hc.float())
+        selection = "packed" if packed is not None else "all" if live_rows is None else "live"
+        engine = _pick_lm_head_engine(ops, h, w, need_grad, need_dw, selection)
+        if engine == "sample_chunks":       # works on the [B, Tg] layout itself: no row view, nothing to restore
+            dh, row_nll = _lm_head_sample_chunks(ops, h, w, ids, mask, stats, chunk, dw, need_grad)
         else:
-            dh, row_nll = _lm_head_live_rows(ops, h, w, ids, mask, stats, live_rows, chunk * Tg, dw, need_grad)
-        out3, doc_lp = ops.rag_loss_finalize(row_nll, Nb, st.lse_r, st.lse_c, st.diag, st.n_global, stats)
+            rows = _lm_head_row_view(h, ids, mask, live_rows, packed)
+            dh, row_nll = rows.restore(*_LM_HEAD_ROW_ENGINES[engine](ops, rows, w, stats, chunk * mask.shape[1], dw, need_grad))
         ctx.st, ctx.scale, ctx.ops, ctx.comm = st, scale, ops, comm
         ctx.in_dtypes = (q.dtype, p.dtype, weight.dtype)
         ctx.save_for_backward(stats, Nb, dh, dw if need_dw else stats)
         ctx.need_dw = need_dw
-        if aux is not None:
-            aux["contrastive"], aux["generator"] = out3[1], out3[2]
-            aux["doc_logprobs"], aux["num_target_tokens"] = doc_lp, stats[0]
-        return out3[0]
+        return _rag_finalize(ops, st, row_nll, Nb, stats, aux)
 
     @staticmethod
     def backward(ctx, g):
-        ops, st = ctx.ops, ctx.st
         stats, Nb, dh, dw = ctx.saved_tensors
         g = g.float().reshape(1)
-        dh = ops.scale_inplace(dh, g) if dh.is_cuda else dh * g.to(dh.dtype)
+        dh = ctx.ops.scale_inplace(dh, g) if dh.is_cuda else dh * g.to(dh.dtype)
         dweight = (dw * g).to(ctx.in_dtypes[2]) if ctx.need_dw else None
-        dq = dp = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            b = (g / (2.0 * st.n_global)).expand(st.q.shape[0]).contiguous()
-            a = b + g * Nb / stats[0]
-            dq, dp = _contrastive_backward(ops, ctx.comm, st, ctx.scale, a, b)
-            dq, dp = dq.to(ctx.in_dtypes[0]), dp.to(ctx.in_dtypes[1])
+        dq, dp = _embedding_grads(ctx, g, Nb, stats[0])
         return (dq, dp, dh, dweight) + (None,) * 12
 
 

@@ -931,3 +931,171 @@ def test_resumed_optimizer_state_follows_the_transposed_lora_b_layout(tmp_path):
             if torch.is_tensor(v) and v.dim() > 1:
                 assert v.stride() == p.stride(), (k, v.stride(), p.stride())
                 assert torch.equal(v, opt.state[p][k])
+
+
+# ---------------------------------------------------------------------------
+# fused._lm_head_engine / fused._lm_head_row_view: the loss node behind rag_e2e_loss_from_hidden / rag_e2e_loss_packed
+# ---------------------------------------------------------------------------
+_LM_HEAD_METHODS = ("lm_head_lse", "lm_head_backward", "lm_head_logits")
+
+
+def _engine_rules_before_the_table(selection, need_grad, need_dw, cuda, h_dtype, w_dtype, H, V, weight_bytes, tunable, has,
+                                   env_kernel, env_train_kernel):
+    """The if / elif chain of `_LMHeadRagE2E.forward` and its three predicates as they stood before one function held them,
+    restated on plain facts (the table under test is never called here)."""
+    bf16 = torch.bfloat16
+
+    def use_lm_head_kernel():
+        if not (cuda and h_dtype == bf16 and H % 64 == 0 and "lm_head_lse" in has):
+            return False
+        if env_kernel is not None:
+            return env_kernel == "1"
+        if w_dtype != bf16 or weight_bytes > int(1.1 * (256 << 20)):
+            return False
+        return not tunable
+
+    def use_lm_head_train_kernel():
+        ok = cuda and h_dtype == bf16 and w_dtype == bf16 and H % 64 == 0 and not need_dw and "lm_head_backward" in has
+        if env_train_kernel == "1" and not ok:
+            raise RuntimeError("DALM_LM_HEAD_TRAIN_KERNEL=1")
+        return ok and env_train_kernel not in ("0", "2")
+
+    def rows():     # _lm_head_rows: the two-contraction kernels or torch.mm
+        two = (env_train_kernel == "2" and need_grad and not need_dw and cuda and h_dtype == bf16 and w_dtype == bf16
+               and V % 64 == 0 and H % 64 == 0 and "lm_head_logits" in has)
+        return "logits_rows" if two else "mm_rows"
+
+    if selection == "packed":
+        if need_grad and use_lm_head_train_kernel() and env_train_kernel == "1":
+            return "recompute"
+        return rows()
+    if not need_grad and use_lm_head_kernel():
+        return "lse"
+    if need_grad and use_lm_head_train_kernel():
+        return "recompute"
+    if selection == "all":
+        return "sample_chunks"
+    return rows()
+
+
+def test_lm_head_engine_table_is_the_if_chain_it_replaced():
+    import itertools
+
+    from dalm_amd.fused import _LM_HEAD_KERNEL_MAX_WEIGHT_BYTES, _lm_head_engine
+
+    assert _LM_HEAD_KERNEL_MAX_WEIGHT_BYTES == int(1.1 * (256 << 20))
+    tf, dt, env = (False, True), (torch.bfloat16, torch.float32), (None, "0", "1", "2")
+    subsets = [frozenset(c) for k in range(4) for c in itertools.combinations(_LM_HEAD_METHODS, k)]
+    names = ("selection", "need_grad", "need_dw", "cuda", "h_dtype", "w_dtype", "H", "V", "weight_bytes", "tunable", "has",
+             "env_kernel", "env_train_kernel")
+    seen, raised = set(), 0
+    for vals in itertools.product(("all", "live", "packed"), tf, tf, tf, dt, dt, (128, 100), (512, 1000),
+                                  (_LM_HEAD_KERNEL_MAX_WEIGHT_BYTES, _LM_HEAD_KERNEL_MAX_WEIGHT_BYTES + 1), tf, subsets, env, env):
+        facts = dict(zip(names, vals))
+        try:
+            want = _engine_rules_before_the_table(**facts)
+        except RuntimeError:
+            with pytest.raises(RuntimeError, match="DALM_LM_HEAD_TRAIN_KERNEL=1 needs bf16 hidden states, a frozen bf16 head"):
+                _lm_head_engine(**facts)
+            raised += 1
+            continue
+        assert _lm_head_engine(**facts) == want, facts
+        seen.add((facts["selection"], facts["need_grad"], want))
+    assert raised > 0
+    assert {e for _, _, e in seen} == {"lse", "recompute", "mm_rows", "logits_rows", "sample_chunks"}
+    assert seen == {("all", False, "lse"), ("all", False, "sample_chunks"), ("all", True, "recompute"), ("all", True, "sample_chunks"),
+                    ("live", False, "lse"), ("live", False, "mm_rows"), ("live", True, "recompute"), ("live", True, "logits_rows"),
+                    ("live", True, "mm_rows"), ("packed", False, "mm_rows"), ("packed", True, "recompute"),
+                    ("packed", True, "logits_rows"), ("packed", True, "mm_rows")}
+
+
+def test_lm_head_engine_table_keeps_its_asymmetries_and_its_error():
+    from dalm_amd.fused import _lm_head_engine
+
+    fit = dict(need_dw=False, cuda=True, h_dtype=torch.bfloat16, w_dtype=torch.bfloat16, H=4096, V=32000,
+               weight_bytes=32000 * 4096 * 2, tunable=False, has=frozenset(_LM_HEAD_METHODS), env_kernel=None,
+               env_train_kernel=None)
+
+    def pick(selection, need_grad, **over):
+        return _lm_head_engine(selection=selection, need_grad=need_grad, **{**fit, **over})
+
+    # packed rows take the recompute kernels only on =1, padded rows take them by default
+    assert pick("all", True) == pick("live", True) == "recompute" and pick("packed", True) == "mm_rows"
+    assert pick("packed", True, env_train_kernel="1") == "recompute"
+    # =2 is ignored on the all-rows padded route
+    assert pick("all", True, env_train_kernel="2") == "sample_chunks"
+    assert pick("live", True, env_train_kernel="2") == pick("packed", True, env_train_kernel="2") == "logits_rows"
+    # packed evaluation never takes the forward-only kernel
+    assert pick("all", False) == pick("live", False) == pick("live", False, env_kernel="1", tunable=True) == "lse"
+    assert pick("packed", False) == pick("packed", False, env_kernel="1") == "mm_rows"
+    assert pick("live", False, tunable=True) == "mm_rows" and pick("all", False, env_kernel="0") == "sample_chunks"
+    # =1 with shapes that do not fit raises on every selection, and only where a gradient is wanted
+    for unfit in (dict(H=4100), dict(h_dtype=torch.float32), dict(w_dtype=torch.float32), dict(need_dw=True), dict(cuda=False),
+                  dict(has=frozenset({"lm_head_lse", "lm_head_logits"}))):
+        for selection in ("all", "live", "packed"):
+            with pytest.raises(RuntimeError, match="DALM_LM_HEAD_TRAIN_KERNEL=1 needs"):
+                pick(selection, True, env_train_kernel="1", **unfit)
+            assert pick(selection, False, env_train_kernel="1", **unfit) in ("lse", "mm_rows", "sample_chunks")
+
+
+def test_lm_head_row_view_selects_shifts_and_restores():
+    from dalm_amd.fused import _lm_head_row_view, live_row_index
+
+    B, Tg, H = 4, 12, 3
+    mask = torch.zeros(B, Tg, dtype=torch.long)
+    mask[0, 5:] = 1          # left padding
+    mask[1, :7] = 1          # right padding
+    mask[2, :] = 1           # a full row
+    mask[3, -1] = 1          # one live token
+    g = torch.Generator().manual_seed(0)
+    ids = torch.randint(1, 50, (B, Tg), generator=g)
+    h = torch.randn(B, Tg, H, generator=g)
+    R = B * Tg
+    nxt_ids = torch.zeros(R, dtype=torch.long)
+    nxt_mask = torch.zeros(R, dtype=torch.long)
+    for b in range(B):
+        for t in range(Tg - 1):
+            nxt_ids[b * Tg + t], nxt_mask[b * Tg + t] = ids[b, t + 1], mask[b, t + 1]
+
+    def compact(n):          # distinct non-zero rows, the ones behind a -1 entry included
+        dh_c = (torch.arange(n, dtype=torch.float32) + 1).unsqueeze(1) * torch.tensor([1.0, 10.0, 100.0])
+        return dh_c, torch.arange(n, dtype=torch.float32) + 1
+
+    # all rows: the shift, and restore is a view
+    v = _lm_head_row_view(h, ids, mask, None, None)
+    assert torch.equal(v.h, h.reshape(R, H)) and torch.equal(v.weights, nxt_mask)
+    assert torch.equal(v.ids[nxt_mask != 0], nxt_ids[nxt_mask != 0])
+    assert torch.equal(v.labels(), torch.where(nxt_mask != 0, nxt_ids, torch.full_like(nxt_ids, -1)))
+    dh_c, nll_c = compact(R)
+    dh, nll = v.restore(dh_c, nll_c)
+    assert dh.shape == (B, Tg, H) and dh.data_ptr() == dh_c.data_ptr() and torch.equal(dh.reshape(R, H), dh_c)
+    assert torch.equal(nll, nll_c)
+    assert v.restore(None, nll_c)[0] is None
+
+    # live rows: 5 + 6 + 11 + 1 = 25 of 48, listed in 28 entries
+    live = live_row_index(mask, 4)
+    assert live.numel() == 28 and int((live < 0).sum()) == 3
+    v = _lm_head_row_view(h, ids, mask, live, None)
+    ok = live >= 0
+    assert torch.equal(v.h[ok], h.reshape(R, H)[live[ok]])
+    assert torch.equal(v.ids[ok], nxt_ids[live[ok]]) and torch.equal(v.weights[ok], nxt_mask[live[ok]])
+    assert bool((v.weights[ok] == 1).all()) and bool((v.weights[~ok] == 0).all()) and bool((v.labels()[~ok] == -1).all())
+    dh_c, nll_c = compact(28)
+    want_dh, want_nll = torch.zeros(R, H), torch.zeros(R)
+    want_dh[live[ok]], want_nll[live[ok]] = dh_c[ok], nll_c[ok]
+    dh, nll = v.restore(dh_c, nll_c)
+    assert dh.shape == (B, Tg, H) and torch.equal(dh.reshape(R, H), want_dh) and torch.equal(nll, want_nll)
+    # the engines that keep a zero row n themselves: same result, no copy needed
+    dh1, nll1 = v.restore(torch.cat((dh_c, torch.zeros(1, H))), torch.cat((nll_c, torch.zeros(1))))
+    assert torch.equal(dh1, dh) and torch.equal(nll1, nll)
+    assert v.restore(None, nll_c)[0] is None
+
+    # packed rows: taken as they are, handed back as they are
+    hp, yp, wp = torch.randn(7, H, generator=g), torch.arange(7), torch.tensor([1, 1, 0, 1, 0, 1, 0])
+    v = _lm_head_row_view(hp, None, mask, None, (yp, wp))
+    assert v.h is hp and v.ids is yp and v.weights is wp
+    dh_c, nll_c = compact(7)
+    dh, nll = v.restore(dh_c, nll_c)
+    assert torch.equal(dh, dh_c) and torch.equal(nll, nll_c) and dh.data_ptr() == dh_c.data_ptr()
+    dh1, nll1 = v.restore(torch.cat((dh_c, torch.zeros(1, H))), torch.cat((nll_c, torch.zeros(1))))
+    assert torch.equal(dh1, dh_c) and torch.equal(nll1, nll_c)

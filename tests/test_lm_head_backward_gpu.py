@@ -171,3 +171,134 @@ def test_two_contraction_kernels_match_the_library_path(dev, cfg, V, H):
     assert _rel(dq_k, dq_l) < 1e-4 and _rel(dp_k, dp_l) < 1e-4
     dead = (torch.cat((mask[:, 1:], torch.zeros_like(mask[:, :1])), 1) == 0)
     assert float(dh_k[dead].abs().max()) == 0.0
+
+
+# ---------------------------------------------------------------------------
+# every (selection, engine) pair `fused._lm_head_engine` can name for a frozen bf16 head: forced through the two variables, run,
+# and compared with `rag_e2e_loss` on the materialised logits of the same bf16 values
+# ---------------------------------------------------------------------------
+_PAIRS = {   # (selection, engine, gradient wanted) -> (DALM_LM_HEAD_KERNEL, DALM_LM_HEAD_TRAIN_KERNEL)
+    ("all", "recompute", True): (None, "1"), ("all", "sample_chunks", True): (None, "0"),
+    ("live", "recompute", True): (None, None), ("live", "logits_rows", True): (None, "2"), ("live", "mm_rows", True): (None, "0"),
+    ("packed", "recompute", True): (None, "1"), ("packed", "logits_rows", True): (None, "2"), ("packed", "mm_rows", True): (None, None),
+    ("all", "lse", False): ("1", None), ("all", "sample_chunks", False): ("0", None),
+    ("live", "lse", False): ("1", None), ("live", "mm_rows", False): ("0", None), ("packed", "mm_rows", False): ("1", None),
+}
+_PAIR_SHAPES = dict(B=4, Tg=64, H=64, V=512, D=32)
+_PAIR_CACHE = {}
+
+
+def _pair_batch(dev):
+    """Left padding; sample 0 is full, sample 1 has a single live token.  Built once, never written to."""
+    if "batch" not in _PAIR_CACHE:
+        from dalm_amd.fused import live_row_index, rag_e2e_loss
+        from dalm_amd.packed import packed_labels
+
+        B, Tg, H, V, D = (_PAIR_SHAPES[k] for k in ("B", "Tg", "H", "V", "D"))
+        g = torch.Generator().manual_seed(23)
+        glen = torch.tensor([Tg, 1, 23, 39]).unsqueeze(1)
+        mask = (torch.arange(Tg).unsqueeze(0) >= (Tg - glen)).long()
+        ids = torch.randint(0, V, (B, Tg), generator=g)
+        qlen = (glen.squeeze(1).float() * 0.7).long().clamp(min=1)
+        q = torch.nn.functional.normalize(torch.randn(B, D, generator=g), dim=1)
+        p = torch.nn.functional.normalize(torch.randn(B, D, generator=g), dim=1)
+        h = torch.randn(B, Tg, H, generator=g).bfloat16()
+        W = (torch.randn(V, H, generator=g) / H ** 0.5 * 2.0).bfloat16()
+        live = live_row_index(mask, 64)
+        assert live.numel() == 128 and int((live < 0).sum()) == 2
+        nxt = torch.cat((mask[:, 1:], torch.zeros_like(mask[:, :1])), 1)
+        tok = ((mask != 0) | (nxt != 0)).reshape(-1).nonzero().squeeze(1)   # the packed rows (dalm_amd/packed.py) + slack entries
+        pack = torch.cat((tok, torch.full((192 - tok.numel(),), -1)))
+        assert tok.numel() == 130
+        q, p, h, W, ids, mask, qlen, live, pack = [t.to(dev) for t in (q, p, h, W, ids, mask, qlen, live, pack)]
+        labels, weights = packed_labels(ids, mask, pack)
+        # reference: the logits of the same bf16 values, materialised in f64 and handed to the logits node in f32
+        logits = (h.double().reshape(B * Tg, H) @ W.double().t()).float().view(B, Tg, V).requires_grad_(True)
+        qq, pp = q.clone().requires_grad_(True), p.clone().requires_grad_(True)
+        loss = rag_e2e_loss(qq, pp, logits, ids, mask, qlen, 100.0)
+        loss.backward()
+        dh = (logits.grad.double().reshape(B * Tg, V) @ W.double()).view(B, Tg, H)
+        _PAIR_CACHE["batch"] = dict(q=q, p=p, h=h, W=W, ids=ids, mask=mask, qlen=qlen, live=live, pack=pack, labels=labels,
+                                    weights=weights, ref=(loss.detach(), qq.grad, pp.grad, dh),
+                                    x_max=float(logits.detach().abs().max()))
+    return _PAIR_CACHE["batch"]
+
+
+def _pair_run(dev, selection, engine, grad):
+    """(loss, dq, dp, dh [B, Tg, H]) of one pair, run once per module; the gradients are None for a forward-only pair."""
+    key = (selection, engine, grad)
+    if key in _PAIR_CACHE:
+        return _PAIR_CACHE[key]
+    from dalm_amd.fused import _pick_lm_head_engine, rag_e2e_loss_from_hidden, rag_e2e_loss_packed
+    from dalm_amd.ops import default_ops
+
+    b = _pair_batch(dev)
+    saved = {k: os.environ.pop(k, None) for k in ("DALM_LM_HEAD_KERNEL", "DALM_LM_HEAD_TRAIN_KERNEL")}
+    try:
+        for k, v in zip(saved, _PAIRS[key]):
+            if v is not None:
+                os.environ[k] = v
+        assert _pick_lm_head_engine(default_ops(), b["h"], b["W"], grad, False, selection) == engine
+        qq, pp, hh = [b[k].clone().requires_grad_(grad) for k in ("q", "p", "h")]
+        with torch.enable_grad() if grad else torch.no_grad():
+            if selection == "packed":
+                hr = hh.reshape(-1, hh.shape[-1]).index_select(0, b["pack"].clamp_min(0))
+                loss = rag_e2e_loss_packed(qq, pp, hr, b["W"], b["labels"], b["weights"], b["mask"], b["qlen"], 100.0)
+            else:
+                loss = rag_e2e_loss_from_hidden(qq, pp, hh, b["W"], b["ids"], b["mask"], b["qlen"], 100.0,
+                                                live_rows=b["live"] if selection == "live" else None)
+            if grad:
+                loss.backward()
+        torch.cuda.synchronize()
+    finally:
+        for k, v in saved.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+    _PAIR_CACHE[key] = (loss.detach(), qq.grad, pp.grad, hh.grad)
+    return _PAIR_CACHE[key]
+
+
+def test_the_pairs_are_all_the_table_names_at_these_shapes():
+    import itertools
+
+    from dalm_amd.fused import _lm_head_engine
+
+    V, H = _PAIR_SHAPES["V"], _PAIR_SHAPES["H"]
+    got = set()
+    for sel, grad, k, t in itertools.product(("all", "live", "packed"), (False, True), (None, "0", "1", "2"), (None, "0", "1", "2")):
+        got.add((sel, _lm_head_engine(selection=sel, need_grad=grad, need_dw=False, cuda=True, h_dtype=torch.bfloat16,
+                                      w_dtype=torch.bfloat16, H=H, V=V, weight_bytes=2 * V * H, tunable=False,
+                                      has=frozenset(("lm_head_lse", "lm_head_backward", "lm_head_logits")), env_kernel=k,
+                                      env_train_kernel=t), grad))
+    assert got == set(_PAIRS)
+
+
+@pytest.mark.parametrize("selection,engine,grad", sorted(_PAIRS), ids=lambda v: str(v))
+def test_every_selection_and_engine_vs_materialised_logits(dev, selection, engine, grad):
+    """Loss bounds as in test_training_through_the_kernels_vs_fp64_oracle_and_library_path: 2e-5 for the engines that keep the
+    logits in f32 (lse, recompute), 2e-3 for the ones that round them to bf16 (mm_rows, logits_rows, sample_chunks).  Gradients
+    of recompute: the same test's 6e-3 and 1.5 x the library engine's error + 1e-3.  d(hidden) of the bf16-logits engines, with
+    u = 2^-9 the unit roundoff of bf16: a logit x rounded to bf16 is off by at most u |x|, which moves a softmax probability by
+    at most a factor exp(2 u x_max) ~ 1 + 2 u x_max; d(logits) and d(hidden) are rounded to bf16 once each, u apiece - in all
+    (2 x_max + 2) u relative to the exact d(hidden), x_max the largest |logit| of the batch.  dq and dp do not depend on the head."""
+    b = _pair_batch(dev)
+    loss_ref, dq_ref, dp_ref, dh_ref = b["ref"]
+    loss, dq, dp, dh = _pair_run(dev, selection, engine, grad)
+    f32_logits = engine in ("lse", "recompute")
+    err = abs(float(loss) - float(loss_ref)) / abs(float(loss_ref))
+    print(f"{selection}/{engine}/grad={grad}: loss rel err {err:.3e}")
+    assert err <= (2e-5 if f32_logits else 2e-3)
+    if not grad:
+        return
+    e = {n: _rel(got, want) for n, got, want in (("dq", dq, dq_ref), ("dp", dp, dp_ref), ("dh", dh, dh_ref))}
+    print(f"{selection}/{engine}: {e}, x_max {b['x_max']:.2f}")
+    if f32_logits:
+        lib = _pair_run(dev, selection, "sample_chunks" if selection == "all" else "mm_rows", True)
+        for n, got_l, want in (("dq", lib[1], dq_ref), ("dp", lib[2], dp_ref), ("dh", lib[3], dh_ref)):
+            assert e[n] < 6e-3 and e[n] < 1.5 * _rel(got_l, want) + 1e-3, (n, e[n], _rel(got_l, want))
+    else:
+        assert e["dq"] < 6e-3 and e["dp"] < 6e-3, e
+        assert e["dh"] < (2.0 * b["x_max"] + 2.0) * 2.0 ** -9, (e, b["x_max"])
+    dead = (torch.cat((b["mask"][:, 1:], torch.zeros_like(b["mask"][:, :1])), 1) == 0)
+    assert float(dh[dead].abs().max()) == 0.0

@@ -1,6 +1,6 @@
 """How the two lm_head GEMMs (hipBLASLt, bf16) scale with the number of rows M on MI355X:
     GEMM1  logits[M, V]  = h[M, H] @ W[V, H]^T          GEMM2  dh[M, H] = dlogits[M, V] @ W[V, H]
-GPU-side time (hipGraph replay), so that chunk sizes for `dalm_amd.fused._lm_head_live_rows` are picked from measurements.
+GPU-side time (hipGraph replay), so that chunk sizes for `dalm_amd.fused._lm_head_rows` are picked from measurements.
     python tools/lm_head_gemm_sweep.py
 """
 import sys
