@@ -41,6 +41,7 @@
 // written = 8 B H T hd el (302 MB; the two launches together move 1.5 x that: each re-reads q, k, v, dO); algorithmic flops
 // 2 / 5 GEMMs x 2 T^2 hd per head over the live tiles (dq and dk/dv each recompute S and dP: 7 are executed).
 #include "common.hpp"
+#include "dispatch.hpp"
 
 namespace dalm {
 namespace {
@@ -1284,7 +1285,6 @@ __global__ __launch_bounds__(256) void attn_mask_bits_packed_kernel(const unsign
   if (wr) live[(static_cast<int64_t>(b) * W + (r >> 5)) * W + w] = 1;
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline void set_dropout(AttnBwdParams& p, float dropout_p, const void* seed, uint32_t salt) {
   const bool on = dropout_p > 0.f;
   p.seed = on ? static_cast<const unsigned long long*>(seed) : nullptr;
@@ -1334,14 +1334,14 @@ static int dalm_attn_bwd_any(const void* q, const void* k, const void* v, const 
   DALM_REQUIRE(B > 0 && H > 0 && T > 0 && T <= 2048 && B * H <= (1ll << 24), DALM_E_SHAPE, "need 0 < T <= 2048 and B H <= 2^24");
   const void* ptrs[8] = {q, k, v, o, d_o, dq, dk, dv};
   for (int i = 0; i < 8; ++i) {
-    DALM_REQUIRE(al16(ptrs[i]), DALM_E_ALIGN, "tensors must be 16-byte aligned");
+    DALM_REQUIRE(aligned16(ptrs[i]), DALM_E_ALIGN, "tensors must be 16-byte aligned");
     for (int a = 0; a < 3; ++a)
       DALM_REQUIRE(strides[3 * i + a] >= 0 && strides[3 * i + a] % 8 == 0, DALM_E_ALIGN, "strides must be non-negative multiples of 8 elements");
   }
   for (int i : {0, 1, 2, 4})      // the streamed tensors' rows are addressed with 32-bit byte offsets from the sequence's first row
     DALM_REQUIRE(T * strides[3 * i + 2] < (1ll << 30), DALM_E_SHAPE, "T x row stride must stay below 2^30 elements");
   DALM_REQUIRE((cos == nullptr) == (sin == nullptr), DALM_E_NULL, "cos and sin come together");
-  DALM_REQUIRE(!cos || (al16(cos) && al16(sin) && cs_stride_b >= 0 && cs_stride_b % 8 == 0 && cs_stride_t >= hd && cs_stride_t % 8 == 0),
+  DALM_REQUIRE(!cos || (aligned16(cos, sin) && cs_stride_b >= 0 && cs_stride_b % 8 == 0 && cs_stride_t >= hd && cs_stride_t % 8 == 0),
                DALM_E_ALIGN, "cos / sin: 16-byte aligned rows of hd elements");
   DALM_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f && (dropout_p == 0.f || (seed && T % 2 == 0)), DALM_E_SHAPE,
                "dropout needs 0 <= p < 1, a device seed word and an even T");
@@ -1419,7 +1419,7 @@ static int dalm_attn_fwd_any(const void* q, const void* k, const void* v, const 
   DALM_REQUIRE(B > 0 && H > 0 && T > 0 && T <= 2048 && B * H <= (1ll << 24), DALM_E_SHAPE, "need 0 < T <= 2048 and B H <= 2^24");
   const void* ptrs[4] = {q, k, v, o};
   for (int i = 0; i < 4; ++i) {
-    DALM_REQUIRE(al16(ptrs[i]), DALM_E_ALIGN, "tensors must be 16-byte aligned");
+    DALM_REQUIRE(aligned16(ptrs[i]), DALM_E_ALIGN, "tensors must be 16-byte aligned");
     for (int a = 0; a < 3; ++a)
       DALM_REQUIRE(strides[3 * i + a] >= 0 && strides[3 * i + a] % 8 == 0, DALM_E_ALIGN, "strides must be non-negative multiples of 8 elements");
   }

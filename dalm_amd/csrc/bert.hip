@@ -23,29 +23,13 @@ namespace {
 
 using lora::DropArgs;
 using lora::DropKey;
+using F8 = lora::Chunk8<float>;   // 8 f32 as two 16-byte accesses
 
-__device__ __forceinline__ void dec8(const uint4& v, float (&x)[8]) {
-  const unsigned int q[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { x[2 * i] = __uint_as_float(q[i] << 16); x[2 * i + 1] = __uint_as_float(q[i] & 0xffff0000u); }
-}
-__device__ __forceinline__ uint4 enc8(const float (&o)[8]) {
-  return make_uint4(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]), pack_bf16x2(o[6], o[7]));
-}
-__device__ __forceinline__ float rb(float x) { return bf16_to_f32(f32_to_bf16(x)); }
-__device__ __forceinline__ void ld8f(const float* p, float (&x)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-  x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
-}
-__device__ __forceinline__ void st8f(float* p, const float (&x)[8]) {
-  *reinterpret_cast<float4*>(p) = make_float4(x[0], x[1], x[2], x[3]);
-  *reinterpret_cast<float4*>(p + 4) = make_float4(x[4], x[5], x[6], x[7]);
-}
 // weight / bias vector element chunk, f32 or bf16 storage
 template <bool WBF16>
 __device__ __forceinline__ void ldw(const void* w, int d, float (&x)[8]) {
   if constexpr (WBF16) dec8(*reinterpret_cast<const uint4*>(static_cast<const unsigned short*>(w) + d), x);
-  else ld8f(static_cast<const float*>(w) + d, x);
+  else F8::load(static_cast<const float*>(w) + d, x);
 }
 
 // keep bits of the chunk of 8 elements with flat chunk index c (mask v2 of lora2.hip): bit e = element 8 c + e survives
@@ -86,7 +70,7 @@ __device__ __forceinline__ void sum_chunk(const uint4& ra, const float (&r)[8], 
   dec8(ra, av);
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
-    const float d = drop ? (((bits >> e) & 1u) ? rb(av[e] * ks) : 0.f) : av[e];
+    const float d = drop ? (((bits >> e) & 1u) ? Vec16<bf16_t>::rb(av[e] * ks) : 0.f) : av[e];
     s[e] = d + r[e];
   }
 }
@@ -104,7 +88,7 @@ __global__ __launch_bounds__(256) void bert_add_norm_fwd_kernel(const AddNormArg
     for (int c = 0; c < NCH; ++c) {
       const int d = (c * 64 + lane) * 8;
       if (d >= p.D) continue;
-      st8f(p.y32 + base + d, z);
+      F8::store(p.y32 + base + d, z);
       *reinterpret_cast<uint4*>(p.y16 + base + d) = make_uint4(0u, 0u, 0u, 0u);
     }
     if (lane == 0) { p.mean[row] = 0.f; p.rstd[row] = 0.f; }
@@ -125,7 +109,7 @@ __global__ __launch_bounds__(256) void bert_add_norm_fwd_kernel(const AddNormArg
     }
     const uint4 ra = *reinterpret_cast<const uint4*>(p.a + base + d);
     float r[8];
-    ld8f(p.res + base + d, r);
+    F8::load(p.res + base + d, r);
     unsigned int bits = 0xffu;
     if (drop) {
       bits = keep_bits8(static_cast<unsigned int>((base + d) >> 3), key, p.drop.thr16);
@@ -155,7 +139,7 @@ __global__ __launch_bounds__(256) void bert_add_norm_fwd_kernel(const AddNormArg
     ldw<WBF16>(p.b, d, bv);
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = fmaf((s[c][e] - mean) * rstd, wv[e], bv[e]);
-    st8f(p.y32 + base + d, o);
+    F8::store(p.y32 + base + d, o);
     *reinterpret_cast<uint4*>(p.y16 + base + d) = enc8(o);
   }
 }
@@ -173,7 +157,7 @@ __global__ __launch_bounds__(256) void bert_add_norm_bwd_kernel(const AddNormArg
     for (int c = 0; c < NCH; ++c) {
       const int d = (c * 64 + lane) * 8;
       if (d >= p.D) continue;
-      st8f(p.d_res + base + d, z);
+      F8::store(p.d_res + base + d, z);
       *reinterpret_cast<uint4*>(p.d_a + base + d) = make_uint4(0u, 0u, 0u, 0u);
     }
     return;
@@ -194,11 +178,11 @@ __global__ __launch_bounds__(256) void bert_add_norm_bwd_kernel(const AddNormArg
     }
     const uint4 ra = *reinterpret_cast<const uint4*>(p.a + base + d);
     float r[8], s[8], wv[8], dy[8];
-    ld8f(p.res + base + d, r);
+    F8::load(p.res + base + d, r);
     if (drop) kb[c] = p.bits[(base + d) >> 3];
     sum_chunk(ra, r, kb[c], p.keep_scale, drop, s);
     ldw<WBF16>(p.w, d, wv);
-    if (p.g32) ld8f(p.g32 + base + d, dy);
+    if (p.g32) F8::load(p.g32 + base + d, dy);
     else {
 #pragma unroll
       for (int e = 0; e < 8; ++e) dy[e] = 0.f;
@@ -227,36 +211,18 @@ __global__ __launch_bounds__(256) void bert_add_norm_bwd_kernel(const AddNormArg
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       ds[e] = rstd * (g[c][e] - sg - xh[c][e] * sgx);
-      const float h = rb(ds[e]);                                  // the gradient of the bf16 operand of the add, cast to bf16
+      const float h = Vec16<bf16_t>::rb(ds[e]);                   // the gradient of the bf16 operand of the add, cast to bf16
       da[e] = drop ? (((kb[c] >> e) & 1u) ? h * p.keep_scale : 0.f) : h;
     }
-    st8f(p.d_res + base + d, ds);
+    F8::store(p.d_res + base + d, ds);
     *reinterpret_cast<uint4*>(p.d_a + base + d) = enc8(da);
   }
 }
-
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 }  // namespace
 }  // namespace dalm
 
 using namespace dalm;
-
-#define DALM_BERT_DISPATCH(KERNEL)                                                                          \
-  do {                                                                                                      \
-    const dim3 grid(static_cast<unsigned>((R + 3) / 4));                                                    \
-    hipStream_t s = as_stream(stream);                                                                      \
-    if (D <= 512) {                                                                                         \
-      if (w_bf16) hipLaunchKernelGGL((KERNEL<1, true>), grid, dim3(256), 0, s, p);                          \
-      else hipLaunchKernelGGL((KERNEL<1, false>), grid, dim3(256), 0, s, p);                                \
-    } else if (D <= 1024) {                                                                                 \
-      if (w_bf16) hipLaunchKernelGGL((KERNEL<2, true>), grid, dim3(256), 0, s, p);                          \
-      else hipLaunchKernelGGL((KERNEL<2, false>), grid, dim3(256), 0, s, p);                                \
-    } else {                                                                                                \
-      if (w_bf16) hipLaunchKernelGGL((KERNEL<4, true>), grid, dim3(256), 0, s, p);                          \
-      else hipLaunchKernelGGL((KERNEL<4, false>), grid, dim3(256), 0, s, p);                                \
-    }                                                                                                       \
-  } while (0)
 
 extern "C" int dalm_bert_add_norm_fwd_live(const void* a, const float* res, const void* w, const void* b, int w_bf16, int64_t R,
                                            int64_t D, float eps, float dropout_p, const void* seed, uint32_t salt, float* y32,
@@ -266,7 +232,7 @@ extern "C" int dalm_bert_add_norm_fwd_live(const void* a, const float* res, cons
   if (R == 0) return 0;
   DALM_REQUIRE(a && res && w && b && y32 && y16 && mean && rstd, DALM_E_NULL, "null pointer argument");
   DALM_REQUIRE(D > 0 && D % 8 == 0 && D <= 2048 && R <= (1ll << 30), DALM_E_SHAPE, "D must be a multiple of 8, at most 2048");
-  DALM_REQUIRE(al16(a) && al16(res) && al16(w) && al16(b) && al16(y32) && al16(y16), DALM_E_ALIGN, "tensors must be 16-byte aligned");
+  DALM_REQUIRE(aligned16(a, res, w, b, y32, y16), DALM_E_ALIGN, "tensors must be 16-byte aligned");
   DALM_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f && (dropout_p == 0.f || (seed && keep_bits)), DALM_E_SHAPE,
                "dropout needs 0 <= p < 1, a device seed word and the keep-bit buffer");
   DALM_REQUIRE(R * D < (1ll << 35), DALM_E_SHAPE, "tensor too large (the mask's chunk index is 32 bits)");
@@ -279,7 +245,12 @@ extern "C" int dalm_bert_add_norm_fwd_live(const void* a, const float* res, cons
   p.drop = lora::drop_args(dropout_p, seed, salt);
   if (dropout_p == 0.f) p.drop.thr16 = 0u;
   p.live = row_live;
-  DALM_BERT_DISPATCH(bert_add_norm_fwd_kernel);
+  const dim3 grid(static_cast<unsigned>((R + 3) / 4));
+  by_ceil<1, 2, 4>(static_cast<int>((D + 511) / 512), [&](auto nch) {   // chunks of 64 lanes x 8 elements per row
+    by_bool(w_bf16 != 0, [&](auto wb) {
+      hipLaunchKernelGGL((bert_add_norm_fwd_kernel<nch, wb>), grid, dim3(256), 0, as_stream(stream), p);
+    });
+  });
   return check_launch(__func__);
 }
 
@@ -298,7 +269,7 @@ extern "C" int dalm_bert_add_norm_bwd_live(const float* g32, const void* g16, co
   if (R == 0) return 0;
   DALM_REQUIRE((g32 || g16) && a && res && w && mean && rstd && d_res && d_a, DALM_E_NULL, "null pointer argument");
   DALM_REQUIRE(D > 0 && D % 8 == 0 && D <= 2048 && R <= (1ll << 30), DALM_E_SHAPE, "D must be a multiple of 8, at most 2048");
-  DALM_REQUIRE(al16(g32) && al16(g16) && al16(a) && al16(res) && al16(w) && al16(d_res) && al16(d_a), DALM_E_ALIGN,
+  DALM_REQUIRE(aligned16(g32, g16, a, res, w, d_res, d_a), DALM_E_ALIGN,
                "tensors must be 16-byte aligned");
   DALM_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f && (dropout_p == 0.f || keep_bits), DALM_E_SHAPE,
                "dropout needs 0 <= p < 1 and the forward's keep bits");
@@ -311,7 +282,12 @@ extern "C" int dalm_bert_add_norm_bwd_live(const float* g32, const void* g16, co
   p.R = static_cast<int>(R); p.D = static_cast<int>(D);
   p.keep_scale = dropout_p > 0.f ? 1.0f / (1.0f - dropout_p) : 1.0f;
   p.live = row_live;
-  DALM_BERT_DISPATCH(bert_add_norm_bwd_kernel);
+  const dim3 grid(static_cast<unsigned>((R + 3) / 4));
+  by_ceil<1, 2, 4>(static_cast<int>((D + 511) / 512), [&](auto nch) {   // chunks of 64 lanes x 8 elements per row
+    by_bool(w_bf16 != 0, [&](auto wb) {
+      hipLaunchKernelGGL((bert_add_norm_bwd_kernel<nch, wb>), grid, dim3(256), 0, as_stream(stream), p);
+    });
+  });
   return check_launch(__func__);
 }
 
@@ -320,4 +296,3 @@ extern "C" int dalm_bert_add_norm_bwd(const float* g32, const void* g16, const v
                                       float dropout_p, float* d_res, void* d_a, dalm_stream_t stream) {
   return dalm_bert_add_norm_bwd_live(g32, g16, a, res, w, w_bf16, keep_bits, mean, rstd, R, D, dropout_p, d_res, d_a, nullptr, stream);
 }
-#undef DALM_BERT_DISPATCH

@@ -13,76 +13,10 @@
 // Row addressing uses 16-byte aligned windows: a row may start at any element
 // offset; the first/last 16-byte slot is masked on load and stored with scalar
 // writes, all interior slots are single dwordx4 accesses.
-#include "common.hpp"
+#include "vec16.hpp"
 
 namespace dalm {
 namespace {
-
-struct bf16_t { unsigned short v; };
-
-template <typename T> struct Elt;
-template <> struct Elt<float> {
-  static constexpr int VEC = 4;
-  __device__ static __forceinline__ void load(const float* p, float (&x)[4]) {
-    const float4 v = *reinterpret_cast<const float4*>(p);
-    x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-  }
-  __device__ static __forceinline__ void store(float* p, const float (&x)[4]) {
-    *reinterpret_cast<float4*>(p) = make_float4(x[0], x[1], x[2], x[3]);
-  }
-  __device__ static __forceinline__ float get(const float* p) { return *p; }
-  __device__ static __forceinline__ void put(float* p, float v) { *p = v; }
-  // streaming (non-temporal) forms: every logit is read once / every gradient written once
-  __device__ static __forceinline__ void load_nt(const float* p, float (&x)[4]) {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-    x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-  }
-  __device__ static __forceinline__ void store_nt(float* p, const float (&x)[4]) {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    f32x4 v;
-    v.x = x[0]; v.y = x[1]; v.z = x[2]; v.w = x[3];
-    __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
-  }
-};
-template <> struct Elt<bf16_t> {
-  static constexpr int VEC = 8;
-  __device__ static __forceinline__ void load(const bf16_t* p, float (&x)[8]) {
-    const uint4 v = *reinterpret_cast<const uint4*>(p);
-    const unsigned int w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      x[2 * i] = __uint_as_float(w[i] << 16);
-      x[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  }
-  __device__ static __forceinline__ void store(bf16_t* p, const float (&x)[8]) {
-    unsigned int w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      w[i] = pack_bf16x2(x[2 * i], x[2 * i + 1]);
-    *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-  __device__ static __forceinline__ float get(const bf16_t* p) { return bf16_to_f32(p->v); }
-  __device__ static __forceinline__ void put(bf16_t* p, float v) { p->v = f32_to_bf16(v); }
-  __device__ static __forceinline__ void load_nt(const bf16_t* p, float (&x)[8]) {
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-    const unsigned int w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      x[2 * i] = __uint_as_float(w[i] << 16);
-      x[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  }
-  __device__ static __forceinline__ void store_nt(bf16_t* p, const float (&x)[8]) {
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 v;
-    v.x = pack_bf16x2(x[0], x[1]); v.y = pack_bf16x2(x[2], x[3]);
-    v.z = pack_bf16x2(x[4], x[5]); v.w = pack_bf16x2(x[6], x[7]);
-    __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p));
-  }
-};
 
 // Geometry of one vocabulary row seen through 16-byte aligned slots.
 template <typename T>
@@ -92,14 +26,14 @@ struct RowWin {
   int nslots;      // slots covering [lead, lead+V)
   int V;
   __device__ __forceinline__ RowWin(const T* row, int V_) : V(V_) {
-    constexpr int VEC = Elt<T>::VEC;
+    constexpr int VEC = Vec16<T>::VEC;
     const uintptr_t a = reinterpret_cast<uintptr_t>(row);
     lead = static_cast<int>((a & 15u) / sizeof(T));
     abase = row - lead;
     nslots = (lead + V + VEC - 1) / VEC;
   }
   __device__ __forceinline__ bool partial(int slot) const {
-    constexpr int VEC = Elt<T>::VEC;
+    constexpr int VEC = Vec16<T>::VEC;
     return (slot == 0 && lead != 0) || (slot == nslots - 1 && ((lead + V) % VEC) != 0);
   }
 };
@@ -107,7 +41,7 @@ struct RowWin {
 // Write `fill` over one full row (used for masked rows and the t = Tg-1 slot).
 template <typename T, int BS>
 __device__ __forceinline__ void fill_row(T* row, int V, float fill) {
-  constexpr int VEC = Elt<T>::VEC;
+  constexpr int VEC = Vec16<T>::VEC;
   RowWin<T> w(row, V);
   T* abase = const_cast<T*>(w.abase);
   float z[VEC];
@@ -115,12 +49,12 @@ __device__ __forceinline__ void fill_row(T* row, int V, float fill) {
   for (int e = 0; e < VEC; ++e) z[e] = fill;
   for (int slot = threadIdx.x; slot < w.nslots; slot += BS) {
     if (!w.partial(slot)) {
-      Elt<T>::store(abase + static_cast<int64_t>(slot) * VEC, z);
+      Vec16<T>::store(abase + static_cast<int64_t>(slot) * VEC, z);
     } else {
 #pragma unroll
       for (int e = 0; e < VEC; ++e) {
         const int idx = slot * VEC + e - w.lead;
-        if (idx >= 0 && idx < V) Elt<T>::put(row + idx, fill);
+        if (idx >= 0 && idx < V) Vec16<T>::put(row + idx, fill);
       }
     }
   }
@@ -149,12 +83,12 @@ __device__ __forceinline__ int64_t map_row(unsigned blk, int Tg, int order) {
 // ---------------------------------------------------------------------------
 
 template <typename T, int BS, int SLOTS, bool WRITE_GRAD, bool ALIGNED>
-__global__ __launch_bounds__(BS, (SLOTS * Elt<T>::VEC > 64 ? 3 : 4)) void marg_ce_row_kernel(
+__global__ __launch_bounds__(BS, (SLOTS * Vec16<T>::VEC > 64 ? 3 : 4)) void marg_ce_row_kernel(
     const T* __restrict__ logits, int64_t stride_b, int64_t stride_t,
     const int64_t* __restrict__ ids, const int64_t* __restrict__ mask, int Tg, int V,
     const float* __restrict__ stats, float* __restrict__ row_lse, float* __restrict__ row_nll,
     T* dlogits, int order) {
-  constexpr int VEC = Elt<T>::VEC;
+  constexpr int VEC = Vec16<T>::VEC;
   __shared__ float red[BS / kWave];
   const int64_t row = map_row(blockIdx.x, Tg, order);
   const int b = static_cast<int>(row / Tg), t = static_cast<int>(row % Tg);
@@ -190,7 +124,7 @@ __global__ __launch_bounds__(BS, (SLOTS * Elt<T>::VEC > 64 ? 3 : 4)) void marg_c
   for (int k = 0; k < SLOTS; ++k) {
     const int slot = k * BS + tid;
     if (slot < nslots) {
-      Elt<T>::load_nt(reinterpret_cast<const T*>(abase + static_cast<unsigned>(slot) * 16u), x[k]);
+      Vec16<T>::load_nt(reinterpret_cast<const T*>(abase + static_cast<unsigned>(slot) * 16u), x[k]);
     } else {
 #pragma unroll
       for (int e = 0; e < VEC; ++e) x[k][e] = -INFINITY;
@@ -198,7 +132,7 @@ __global__ __launch_bounds__(BS, (SLOTS * Elt<T>::VEC > 64 ? 3 : 4)) void marg_c
   }
   // every lane reads the label logit (one broadcast request per wave): lane 0 needs it for the
   // NLL, the lane owning the label's slot for the gradient patch
-  const float xy = (y >= 0 && y < V) ? Elt<T>::get(xrow + y) : __builtin_nanf("");
+  const float xy = (y >= 0 && y < V) ? Vec16<T>::get(xrow + y) : __builtin_nanf("");
 
   float tmax = -INFINITY;
 #pragma unroll
@@ -254,12 +188,12 @@ __global__ __launch_bounds__(BS, (SLOTS * Elt<T>::VEC > 64 ? 3 : 4)) void marg_c
       bool part = false;
       if constexpr (!ALIGNED) part = (slot == 0 && lead != 0) || (slot == nslots - 1 && tail_partial);
       if (!part) {
-        Elt<T>::store_nt(reinterpret_cast<T*>(gbase + static_cast<unsigned>(slot) * 16u), x[k]);
+        Vec16<T>::store_nt(reinterpret_cast<T*>(gbase + static_cast<unsigned>(slot) * 16u), x[k]);
       } else {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
           const int idx = slot * VEC + e - lead;
-          if (idx >= 0 && idx < V) Elt<T>::put(grow + idx, x[k][e]);
+          if (idx >= 0 && idx < V) Vec16<T>::put(grow + idx, x[k][e]);
         }
       }
     }
@@ -268,7 +202,7 @@ __global__ __launch_bounds__(BS, (SLOTS * Elt<T>::VEC > 64 ? 3 : 4)) void marg_c
       if (tid == slot_y % BS) {  // the lane that owns (and has just stored) the label's slot
         const float py = __builtin_amdgcn_exp2f(fmaf(xy, kLog2e, mneg)) * inv;  // same ops as the row pass
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // its vector stores are acknowledged first
-        Elt<T>::put(grow + y, py - coef);
+        Vec16<T>::put(grow + y, py - coef);
       }
     }
   }
@@ -423,13 +357,13 @@ __global__ __launch_bounds__(BS, 8) void marg_ce_row_bf16_kernel(
           o.z = pack_bf16x2(g[4], g[5]); o.w = pack_bf16x2(g[6], g[7]);
           __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(gbase + static_cast<unsigned>(slot) * 16u));
         } else {
-          Elt<T>::store(reinterpret_cast<T*>(gbase + static_cast<unsigned>(slot) * 16u), g);
+          Vec16<T>::store(reinterpret_cast<T*>(gbase + static_cast<unsigned>(slot) * 16u), g);
         }
       } else {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
           const int idx = slot * VEC + e - lead;
-          if (idx >= 0 && idx < V) Elt<T>::put(grow + idx, g[e]);
+          if (idx >= 0 && idx < V) Vec16<T>::put(grow + idx, g[e]);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -448,7 +382,7 @@ __global__ __launch_bounds__(BS) void marg_ce_stream_kernel(
     const int64_t* __restrict__ ids, const int64_t* __restrict__ mask, int Tg, int V,
     const float* __restrict__ stats, float* __restrict__ row_lse, float* __restrict__ row_nll,
     T* dlogits, int order) {
-  constexpr int VEC = Elt<T>::VEC;
+  constexpr int VEC = Vec16<T>::VEC;
   __shared__ float red[BS / kWave];
   const int64_t row = map_row(blockIdx.x, Tg, order);
   const int b = static_cast<int>(row / Tg), t = static_cast<int>(row % Tg);
@@ -471,12 +405,12 @@ __global__ __launch_bounds__(BS) void marg_ce_stream_kernel(
   // label logit first: with dlogits aliasing logits (in-place mode) other waves may already be storing the
   // gradient of this row by the time thread 0 gets past the block reductions below
   float xy = 0.f;
-  if (tid == 0) xy = (y >= 0 && y < V) ? Elt<T>::get(xrow + y) : __builtin_nanf("");
+  if (tid == 0) xy = (y >= 0 && y < V) ? Vec16<T>::get(xrow + y) : __builtin_nanf("");
 
   float tm = -INFINITY, tl = 0.f;
   for (int slot = tid; slot < w.nslots; slot += BS) {
     float v[VEC];
-    Elt<T>::load(w.abase + static_cast<int64_t>(slot) * VEC, v);
+    Vec16<T>::load(w.abase + static_cast<int64_t>(slot) * VEC, v);
     if (w.partial(slot)) {
 #pragma unroll
       for (int e = 0; e < VEC; ++e) {
@@ -511,19 +445,19 @@ __global__ __launch_bounds__(BS) void marg_ce_stream_kernel(
     // in-place safe only if every thread re-reads exactly the slots it writes: it does.
     for (int slot = tid; slot < w.nslots; slot += BS) {
       float v[VEC];
-      Elt<T>::load(w.abase + static_cast<int64_t>(slot) * VEC, v);
+      Vec16<T>::load(w.abase + static_cast<int64_t>(slot) * VEC, v);
 #pragma unroll
       for (int e = 0; e < VEC; ++e) {
         const int idx = slot * VEC + e - w.lead;
         v[e] = inv * fast_exp(v[e] - m) - ((idx == y) ? coef : 0.f);
       }
       if (!w.partial(slot)) {
-        Elt<T>::store(gbase + static_cast<int64_t>(slot) * VEC, v);
+        Vec16<T>::store(gbase + static_cast<int64_t>(slot) * VEC, v);
       } else {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
           const int idx = slot * VEC + e - w.lead;
-          if (idx >= 0 && idx < V) Elt<T>::put(grow + idx, v[e]);
+          if (idx >= 0 && idx < V) Vec16<T>::put(grow + idx, v[e]);
         }
       }
     }
@@ -539,7 +473,7 @@ __global__ __launch_bounds__(BS) void marg_ce_bwd_kernel(
     const int64_t* __restrict__ ids, const int64_t* __restrict__ mask, int Tg, int V,
     const float* __restrict__ stats, const float* __restrict__ row_lse,
     const float* __restrict__ gscale, T* dlogits, const float* __restrict__ row_w) {
-  constexpr int VEC = Elt<T>::VEC;
+  constexpr int VEC = Vec16<T>::VEC;
   const int64_t row = blockIdx.x;
   const int b = static_cast<int>(row / Tg), t = static_cast<int>(row % Tg);
   const int tid = threadIdx.x;
@@ -563,19 +497,19 @@ __global__ __launch_bounds__(BS) void marg_ce_bwd_kernel(
   const float nlse = -row_lse[row] * kLog2e;
   for (int slot = tid; slot < w.nslots; slot += BS) {
     float v[VEC];
-    Elt<T>::load_nt(w.abase + static_cast<int64_t>(slot) * VEC, v);
+    Vec16<T>::load_nt(w.abase + static_cast<int64_t>(slot) * VEC, v);
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
       const int idx = slot * VEC + e - w.lead;
       v[e] = coef * __builtin_amdgcn_exp2f(fmaf(v[e], kLog2e, nlse)) - ((idx == y) ? coef : 0.f);
     }
     if (!w.partial(slot)) {
-      Elt<T>::store_nt(gbase + static_cast<int64_t>(slot) * VEC, v);
+      Vec16<T>::store_nt(gbase + static_cast<int64_t>(slot) * VEC, v);
     } else {
 #pragma unroll
       for (int e = 0; e < VEC; ++e) {
         const int idx = slot * VEC + e - w.lead;
-        if (idx >= 0 && idx < V) Elt<T>::put(grow + idx, v[e]);
+        if (idx >= 0 && idx < V) Vec16<T>::put(grow + idx, v[e]);
       }
     }
   }
@@ -682,19 +616,19 @@ __global__ __launch_bounds__(256) void ce_finalize_topk_kernel(const float* __re
 
 template <typename T>
 __global__ __launch_bounds__(256) void scale_inplace_kernel(T* x, int64_t n, const float* __restrict__ gscale) {
-  constexpr int VEC = Elt<T>::VEC;
+  constexpr int VEC = Vec16<T>::VEC;
   const float g = gscale[0];
   if (g == 1.f) return;  // uniform: the common loss.backward() case costs one tiny launch
   const int64_t nvec = n / VEC;
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < nvec; i += gridDim.x * 256ll) {
     float v[VEC];
-    Elt<T>::load(x + i * VEC, v);
+    Vec16<T>::load(x + i * VEC, v);
 #pragma unroll
     for (int e = 0; e < VEC; ++e) v[e] *= g;
-    Elt<T>::store(x + i * VEC, v);
+    Vec16<T>::store(x + i * VEC, v);
   }
   if (blockIdx.x == 0)
-    for (int64_t i = nvec * VEC + threadIdx.x; i < n; i += 256) Elt<T>::put(x + i, Elt<T>::get(x + i) * g);
+    for (int64_t i = nvec * VEC + threadIdx.x; i < n; i += 256) Vec16<T>::put(x + i, Vec16<T>::get(x + i) * g);
 }
 
 __global__ __launch_bounds__(256) void gather_nll_kernel(const float* __restrict__ lp,
@@ -727,7 +661,7 @@ template <typename T, bool GRAD, bool ALIGNED>
 void launch_fwd2(const T* logits, int64_t B, int64_t Tg, int64_t V, int64_t sb, int64_t st,
                  const int64_t* ids, const int64_t* mask, const float* stats, float* row_lse,
                  float* row_nll, T* dlogits, hipStream_t s) {
-  constexpr int VEC = Elt<T>::VEC;
+  constexpr int VEC = Vec16<T>::VEC;
   const int64_t need = ALIGNED ? V / VEC : (V + 2 * (VEC - 1)) / VEC;  // slots incl. worst-case lead
   const dim3 grid(static_cast<unsigned>(B * Tg));
   const int Tgi = static_cast<int>(Tg), Vi = static_cast<int>(V);
@@ -766,7 +700,7 @@ template <typename T, bool GRAD>
 int launch_fwd(const T* logits, int64_t B, int64_t Tg, int64_t V, int64_t sb, int64_t st,
                const int64_t* ids, const int64_t* mask, const float* stats, float* row_lse,
                float* row_nll, T* dlogits, hipStream_t s) {
-  constexpr int VEC = Elt<T>::VEC;
+  constexpr int VEC = Vec16<T>::VEC;
   const bool aligned = (reinterpret_cast<uintptr_t>(logits) % 16 == 0) && (V % VEC == 0) &&
                        (sb % VEC == 0) && (st % VEC == 0) &&
                        (!GRAD || reinterpret_cast<uintptr_t>(dlogits) % 16 == 0);

@@ -10,22 +10,11 @@
 //   add3       : out = bf16( c + bf16(a + b) )   (mlp_output += attention_output; residual + out)
 // One wave per row for the norm (the row stays in registers between the reductions and the scaling), flat 16-byte streams for
 // the other two.  Algorithmic bytes: norm fwd 2 R D el, bwd 3-4 R D el; gelu fwd 2 n el, bwd 3 n el; add3 4 n el.
-#include "common.hpp"
+#include "dispatch.hpp"
+#include "vec16.hpp"
 
 namespace dalm {
 namespace {
-
-struct bf16_t { unsigned short v; };
-
-__device__ __forceinline__ void dec8(const uint4& v, float (&x)[8]) {
-  const unsigned int q[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { x[2 * i] = __uint_as_float(q[i] << 16); x[2 * i + 1] = __uint_as_float(q[i] & 0xffff0000u); }
-}
-__device__ __forceinline__ uint4 enc8(const float (&o)[8]) {
-  return make_uint4(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]), pack_bf16x2(o[6], o[7]));
-}
-__device__ __forceinline__ float rb(float x) { return bf16_to_f32(f32_to_bf16(x)); }
 
 // ---- LayerNorm, bf16 rows of D elements (D % 8 == 0, D <= 8192), one wave per row, 4 rows per workgroup ----
 template <int NCH>
@@ -204,12 +193,10 @@ __global__ __launch_bounds__(256) void add3_kernel(const bf16_t* __restrict__ a,
     float x[8], y[8], z[8], o[8];
     dec8(ra[k], x); dec8(rbb[k], y); dec8(rc[k], z);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = z[e] + rb(x[e] + y[e]);
+    for (int e = 0; e < 8; ++e) o[e] = z[e] + Vec16<bf16_t>::rb(x[e] + y[e]);
     *reinterpret_cast<uint4*>(out + (c0 + k * 256) * 8) = enc8(o);
   }
 }
-
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 }  // namespace dalm
@@ -217,17 +204,14 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 using namespace dalm;
 
 // chunks of 64 lanes x 8 elements a wave holds per row: 9 is Falcon-7B's 4544 (8.875 chunks), 16 the 8192 limit
-#define DALM_LN_DISPATCH(M)                                                                                                       \
-  do {                                                                                                                            \
-    if (nch <= 1) { M(1); } else if (nch <= 2) { M(2); } else if (nch <= 4) { M(4); } else if (nch <= 6) { M(6); }                 \
-    else if (nch <= 8) { M(8); } else if (nch <= 9) { M(9); } else if (nch <= 12) { M(12); } else { M(16); }                       \
-  } while (0)
+template <typename F>
+inline void by_ln_chunks(int nch, F&& f) { by_ceil<1, 2, 4, 6, 8, 9, 12, 16>(nch, f); }
 
 extern "C" int dalm_layer_norm_fwd(const void* x, const void* w, const void* b, int64_t R, int64_t D, float eps, void* y,
                                    float* mean, float* rstd, dalm_stream_t stream) {
   DALM_REQUIRE(x && w && y && mean && rstd, DALM_E_NULL, "null pointer argument");
   DALM_REQUIRE(R > 0 && D > 0 && D % 8 == 0 && D <= 8192 && R <= 0x7ffffff0ll, DALM_E_SHAPE, "need R > 0 and D a multiple of 8, at most 8192");
-  DALM_REQUIRE(al16(x) && al16(w) && al16(y) && (!b || al16(b)), DALM_E_ALIGN, "tensors must be 16-byte aligned");
+  DALM_REQUIRE(aligned16(x, w, y, b), DALM_E_ALIGN, "tensors must be 16-byte aligned");
   const int nch = static_cast<int>((D + 511) / 512);
   const dim3 grid(static_cast<unsigned>((R + 3) / 4));
   hipStream_t s = as_stream(stream);
@@ -236,9 +220,9 @@ extern "C" int dalm_layer_norm_fwd(const void* x, const void* w, const void* b, 
   const bf16_t* bp = static_cast<const bf16_t*>(b);
   bf16_t* yp = static_cast<bf16_t*>(y);
   const int Ri = static_cast<int>(R), Di = static_cast<int>(D);
-#define DALM_LNF(N) hipLaunchKernelGGL((layer_norm_fwd_kernel<N>), grid, dim3(256), 0, s, xp, wp, bp, yp, mean, rstd, Ri, Di, eps)
-  DALM_LN_DISPATCH(DALM_LNF);
-#undef DALM_LNF
+  by_ln_chunks(nch, [&](auto n) {
+    hipLaunchKernelGGL((layer_norm_fwd_kernel<n>), grid, dim3(256), 0, s, xp, wp, bp, yp, mean, rstd, Ri, Di, eps);
+  });
   return check_launch(__func__);
 }
 
@@ -246,7 +230,7 @@ extern "C" int dalm_layer_norm_bwd(const void* dy, const void* x, const void* w,
                                    const void* dres, int64_t R, int64_t D, void* dx, dalm_stream_t stream) {
   DALM_REQUIRE(dy && x && w && mean && rstd && dx, DALM_E_NULL, "null pointer argument");
   DALM_REQUIRE(R > 0 && D > 0 && D % 8 == 0 && D <= 8192 && R <= 0x7ffffff0ll, DALM_E_SHAPE, "need R > 0 and D a multiple of 8, at most 8192");
-  DALM_REQUIRE(al16(dy) && al16(x) && al16(w) && al16(dx) && (!dres || al16(dres)), DALM_E_ALIGN, "tensors must be 16-byte aligned");
+  DALM_REQUIRE(aligned16(dy, x, w, dx, dres), DALM_E_ALIGN, "tensors must be 16-byte aligned");
   const int nch = static_cast<int>((D + 511) / 512);
   const dim3 grid(static_cast<unsigned>((R + 3) / 4));
   hipStream_t s = as_stream(stream);
@@ -256,12 +240,11 @@ extern "C" int dalm_layer_norm_bwd(const void* dy, const void* x, const void* w,
   const bf16_t* rp = static_cast<const bf16_t*>(dres);
   bf16_t* op = static_cast<bf16_t*>(dx);
   const int Ri = static_cast<int>(R), Di = static_cast<int>(D);
-#define DALM_LNB_T(N) hipLaunchKernelGGL((layer_norm_bwd_kernel<N, true>), grid, dim3(256), 0, s, gp, xp, wp, mean, rstd, rp, op, Ri, Di)
-#define DALM_LNB_F(N) hipLaunchKernelGGL((layer_norm_bwd_kernel<N, false>), grid, dim3(256), 0, s, gp, xp, wp, mean, rstd, rp, op, Ri, Di)
-  if (dres) DALM_LN_DISPATCH(DALM_LNB_T);
-  else DALM_LN_DISPATCH(DALM_LNB_F);
-#undef DALM_LNB_T
-#undef DALM_LNB_F
+  by_ln_chunks(nch, [&](auto n) {
+    by_bool(dres != nullptr, [&](auto add) {
+      hipLaunchKernelGGL((layer_norm_bwd_kernel<n, add>), grid, dim3(256), 0, s, gp, xp, wp, mean, rstd, rp, op, Ri, Di);
+    });
+  });
   return check_launch(__func__);
 }
 
@@ -275,7 +258,7 @@ extern "C" int dalm_layer_norm_bwd(const void* dy, const void* x, const void* w,
 extern "C" int dalm_gelu_fwd(const void* x, void* y, int64_t n, dalm_stream_t stream) {
   DALM_FLAT_CHECKS(n);
   DALM_REQUIRE(x && y, DALM_E_NULL, "null pointer argument");
-  DALM_REQUIRE(al16(x) && al16(y), DALM_E_ALIGN, "tensors must be 16-byte aligned");
+  DALM_REQUIRE(aligned16(x, y), DALM_E_ALIGN, "tensors must be 16-byte aligned");
   hipLaunchKernelGGL(gelu_fwd_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, as_stream(stream),
                      static_cast<const bf16_t*>(x), static_cast<bf16_t*>(y), n8);
   return check_launch(__func__);
@@ -284,7 +267,7 @@ extern "C" int dalm_gelu_fwd(const void* x, void* y, int64_t n, dalm_stream_t st
 extern "C" int dalm_gelu_bwd(const void* dy, const void* x, void* dx, int64_t n, dalm_stream_t stream) {
   DALM_FLAT_CHECKS(n);
   DALM_REQUIRE(dy && x && dx, DALM_E_NULL, "null pointer argument");
-  DALM_REQUIRE(al16(dy) && al16(x) && al16(dx), DALM_E_ALIGN, "tensors must be 16-byte aligned");
+  DALM_REQUIRE(aligned16(dy, x, dx), DALM_E_ALIGN, "tensors must be 16-byte aligned");
   hipLaunchKernelGGL(gelu_bwd_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, as_stream(stream),
                      static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(x), static_cast<bf16_t*>(dx), n8);
   return check_launch(__func__);
@@ -293,7 +276,7 @@ extern "C" int dalm_gelu_bwd(const void* dy, const void* x, void* dx, int64_t n,
 extern "C" int dalm_add3(const void* a, const void* b, const void* c, void* out, int64_t n, dalm_stream_t stream) {
   DALM_FLAT_CHECKS(n);
   DALM_REQUIRE(a && b && c && out, DALM_E_NULL, "null pointer argument");
-  DALM_REQUIRE(al16(a) && al16(b) && al16(c) && al16(out), DALM_E_ALIGN, "tensors must be 16-byte aligned");
+  DALM_REQUIRE(aligned16(a, b, c, out), DALM_E_ALIGN, "tensors must be 16-byte aligned");
   hipLaunchKernelGGL(add3_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, as_stream(stream),
                      static_cast<const bf16_t*>(a), static_cast<const bf16_t*>(b), static_cast<const bf16_t*>(c),
                      static_cast<bf16_t*>(out), n8);

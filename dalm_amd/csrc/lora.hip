@@ -449,35 +449,34 @@ extern "C" int dalm_lora_rowdot(const void* x, int dtype, const float* W, int w_
                                 float scale, float p, const void* seed, uint32_t salt, float* out, dalm_stream_t stream) {
   DALM_REQUIRE(x && W && out, DALM_E_NULL, "null pointer argument");
   DALM_LORA_COMMON_CHECKS(R, K);
-  DALM_REQUIRE(al16(x) && al16(W) && al16(out), DALM_E_ALIGN, "x / W / out must be 16-byte aligned");
+  DALM_REQUIRE(aligned16(x, W, out), DALM_E_ALIGN, "x / W / out must be 16-byte aligned");
   const DropArgs d = drop_args(p, seed, salt);
   hipStream_t s = as_stream(stream);
   if (dtype == DALM_BF16 && K % 32 == 0) {
     const dim3 mgrid(static_cast<unsigned>((R + 15) / 16));
-#define DALM_ROWDOT_M(RK, DR, KM) \
-    hipLaunchKernelGGL((lora_rowdot_mfma_kernel<RK, DR, KM>), mgrid, dim3(512), 0, s, static_cast<const bf16_t*>(x), W, out, \
-                       static_cast<int>(R), static_cast<int>(K), scale, d)
-#define DALM_ROWDOT_M_KM(RK, DR) do { if (w_kmajor) DALM_ROWDOT_M(RK, DR, true); else DALM_ROWDOT_M(RK, DR, false); } while (0)
-#define DALM_ROWDOT_M_DR(RK) do { if (p > 0.f) DALM_ROWDOT_M_KM(RK, true); else DALM_ROWDOT_M_KM(RK, false); } while (0)
-    if (rank == 8) DALM_ROWDOT_M_DR(8); else DALM_ROWDOT_M_DR(16);
-#undef DALM_ROWDOT_M_DR
-#undef DALM_ROWDOT_M_KM
-#undef DALM_ROWDOT_M
+    by_exact<8, 16>(rank, [&](auto rk) {
+      by_bool(p > 0.f, [&](auto dr) {
+        by_bool(w_kmajor != 0, [&](auto km) {
+          hipLaunchKernelGGL((lora_rowdot_mfma_kernel<rk, dr, km>), mgrid, dim3(512), 0, s, static_cast<const bf16_t*>(x), W, out,
+                             static_cast<int>(R), static_cast<int>(K), scale, d);
+        });
+      });
+    });
     return check_launch(__func__);
   }
   const int rows_per_wg = lora_rows_per_wg(R);
   const dim3 grid(static_cast<unsigned>((R + rows_per_wg - 1) / rows_per_wg));
-#define DALM_ROWDOT(TT, RK, DR, KM) \
-  hipLaunchKernelGGL((lora_rowdot_kernel<TT, RK, DR, KM>), grid, dim3(512), 0, s, static_cast<const TT*>(x), W, out, \
-                     static_cast<int>(R), static_cast<int>(K), rows_per_wg, scale, d)
-#define DALM_ROWDOT_KM(TT, RK, DR) do { if (w_kmajor) DALM_ROWDOT(TT, RK, DR, true); else DALM_ROWDOT(TT, RK, DR, false); } while (0)
-#define DALM_ROWDOT_DR(TT, RK) do { if (p > 0.f) DALM_ROWDOT_KM(TT, RK, true); else DALM_ROWDOT_KM(TT, RK, false); } while (0)
-#define DALM_ROWDOT_RK(TT) do { if (rank == 8) DALM_ROWDOT_DR(TT, 8); else DALM_ROWDOT_DR(TT, 16); } while (0)
-  if (dtype == DALM_F32) DALM_ROWDOT_RK(float); else DALM_ROWDOT_RK(bf16_t);
-#undef DALM_ROWDOT_RK
-#undef DALM_ROWDOT_DR
-#undef DALM_ROWDOT_KM
-#undef DALM_ROWDOT
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_exact<8, 16>(rank, [&](auto rk) {
+      by_bool(p > 0.f, [&](auto dr) {
+        by_bool(w_kmajor != 0, [&](auto km) {
+          hipLaunchKernelGGL((lora_rowdot_kernel<T, rk, dr, km>), grid, dim3(512), 0, s, static_cast<const T*>(x), W, out,
+                             static_cast<int>(R), static_cast<int>(K), rows_per_wg, scale, d);
+        });
+      });
+    });
+  });
   return check_launch(__func__);
 }
 
@@ -485,23 +484,23 @@ extern "C" int dalm_lora_rankupd(void* y, int dtype, const float* z, const float
                                  int rank, float scale, float p, const void* seed, uint32_t salt, dalm_stream_t stream) {
   DALM_REQUIRE(y && z && W, DALM_E_NULL, "null pointer argument");
   DALM_LORA_COMMON_CHECKS(R, C);
-  DALM_REQUIRE(al16(y) && al16(W) && al16(z), DALM_E_ALIGN, "y / z / W must be 16-byte aligned");
+  DALM_REQUIRE(aligned16(y, W, z), DALM_E_ALIGN, "y / z / W must be 16-byte aligned");
   const int64_t cpr = (C + 7) / 8 < 512 ? (C + 7) / 8 : 512;
   const int rows_per_wg = lora_rows_per_wg(R, 512 / cpr);
   const dim3 grid(static_cast<unsigned>((R + rows_per_wg - 1) / rows_per_wg));
   const DropArgs d = drop_args(p, seed, salt);
   hipStream_t s = as_stream(stream);
-#define DALM_RANKUPD(TT, RK, DR, CM) \
-  hipLaunchKernelGGL((lora_rankupd_kernel<TT, RK, DR, CM>), grid, dim3(512), 0, s, static_cast<TT*>(y), z, W, \
-                     static_cast<int>(R), static_cast<int>(C), rows_per_wg, scale, d)
-#define DALM_RANKUPD_CM(TT, RK, DR) do { if (w_cmajor) DALM_RANKUPD(TT, RK, DR, true); else DALM_RANKUPD(TT, RK, DR, false); } while (0)
-#define DALM_RANKUPD_DR(TT, RK) do { if (p > 0.f) DALM_RANKUPD_CM(TT, RK, true); else DALM_RANKUPD_CM(TT, RK, false); } while (0)
-#define DALM_RANKUPD_RK(TT) do { if (rank == 8) DALM_RANKUPD_DR(TT, 8); else DALM_RANKUPD_DR(TT, 16); } while (0)
-  if (dtype == DALM_F32) DALM_RANKUPD_RK(float); else DALM_RANKUPD_RK(bf16_t);
-#undef DALM_RANKUPD_RK
-#undef DALM_RANKUPD_DR
-#undef DALM_RANKUPD_CM
-#undef DALM_RANKUPD
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_exact<8, 16>(rank, [&](auto rk) {
+      by_bool(p > 0.f, [&](auto dr) {
+        by_bool(w_cmajor != 0, [&](auto cm) {
+          hipLaunchKernelGGL((lora_rankupd_kernel<T, rk, dr, cm>), grid, dim3(512), 0, s, static_cast<T*>(y), z, W,
+                             static_cast<int>(R), static_cast<int>(C), rows_per_wg, scale, d);
+        });
+      });
+    });
+  });
   return check_launch(__func__);
 }
 
@@ -517,7 +516,7 @@ extern "C" int dalm_lora_colacc(const void* x, int dtype, const float* z, int64_
                                 dalm_stream_t stream) {
   DALM_REQUIRE(x && z && out && ws, DALM_E_NULL, "null pointer argument");
   DALM_LORA_COMMON_CHECKS(R, C);
-  DALM_REQUIRE(al16(x) && al16(z), DALM_E_ALIGN, "x / z must be 16-byte aligned");
+  DALM_REQUIRE(aligned16(x, z), DALM_E_ALIGN, "x / z must be 16-byte aligned");
   DALM_REQUIRE(ws_bytes >= dalm_lora_colacc_workspace_bytes(R, C, rank), DALM_E_WORKSPACE, "workspace too small");
   const int rps = colacc_rows_per_split(R, C);
   const int64_t splits = (R + rps - 1) / rps;
@@ -526,21 +525,17 @@ extern "C" int dalm_lora_colacc(const void* x, int dtype, const float* z, int64_
   const DropArgs d = drop_args(p, seed, salt);
   hipStream_t s = as_stream(stream);
   float* part = static_cast<float*>(ws);
-#define DALM_COLACC(TT, RK, DR) \
-  hipLaunchKernelGGL((lora_colacc_kernel<TT, RK, DR>), grid, dim3(256), 0, s, static_cast<const TT*>(x), z, part, \
-                     static_cast<int>(R), static_cast<int>(C), rps, d)
-#define DALM_COLACC_DR(TT, RK) do { if (p > 0.f) DALM_COLACC(TT, RK, true); else DALM_COLACC(TT, RK, false); } while (0)
-#define DALM_COLACC_RK(TT) do { if (rank == 8) DALM_COLACC_DR(TT, 8); else DALM_COLACC_DR(TT, 16); } while (0)
-  if (dtype == DALM_F32) DALM_COLACC_RK(float); else DALM_COLACC_RK(bf16_t);
-#undef DALM_COLACC_RK
-#undef DALM_COLACC_DR
-#undef DALM_COLACC
   const unsigned rblocks = static_cast<unsigned>((C * rank + 255) / 256);
-  if (rank == 8)
-    hipLaunchKernelGGL(lora_colacc_reduce_kernel<8>, dim3(rblocks), dim3(256), 0, s, part, static_cast<int>(splits),
+  by_exact<8, 16>(rank, [&](auto rk) {
+    by_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      by_bool(p > 0.f, [&](auto dr) {
+        hipLaunchKernelGGL((lora_colacc_kernel<T, rk, dr>), grid, dim3(256), 0, s, static_cast<const T*>(x), z, part,
+                           static_cast<int>(R), static_cast<int>(C), rps, d);
+      });
+    });
+    hipLaunchKernelGGL(lora_colacc_reduce_kernel<rk>, dim3(rblocks), dim3(256), 0, s, part, static_cast<int>(splits),
                        static_cast<int>(C), scale, out_jmajor, out);
-  else
-    hipLaunchKernelGGL(lora_colacc_reduce_kernel<16>, dim3(rblocks), dim3(256), 0, s, part, static_cast<int>(splits),
-                       static_cast<int>(C), scale, out_jmajor, out);
+  });
   return check_launch(__func__);
 }

@@ -580,7 +580,7 @@ extern "C" int dalm_lora2_rowdot_live(const void* x0, const void* x1, const floa
   DALM_REQUIRE(p >= 0.f && p < 1.f, DALM_E_SHAPE, "dropout probability must be in [0, 1)");
   const bool two = mode != 1;
   DALM_REQUIRE(x0 && W0 && out0 && (!two || (W1 && out1)) && (mode != 3 || x1), DALM_E_NULL, "null pointer argument");
-  DALM_REQUIRE(al16(x0) && al16(W0) && (!two || al16(W1)) && (mode != 3 || al16(x1)), DALM_E_ALIGN, "x / W must be 16-byte aligned");
+  DALM_REQUIRE(aligned16(x0, W0) && (!two || aligned16(W1)) && (mode != 3 || aligned16(x1)), DALM_E_ALIGN, "x / W must be 16-byte aligned");
   const bool drop = p > 0.f;
   DALM_REQUIRE(!drop || (seed && bits0 && (!two || bits1)), DALM_E_NULL, "dropout needs the seed word and the mask buffers");
   const unsigned int thr16 = static_cast<unsigned int>(p * 65536.0f + 0.5f);
@@ -616,7 +616,7 @@ extern "C" int dalm_lora2_rankupd_live(void* y0, void* y1, const float* z0, cons
   DALM_LORA2_SHAPE(R, C, rank);
   const bool two = mode != 1;
   DALM_REQUIRE(y0 && z0 && W0 && (!two || (z1 && W1)) && (mode != 3 || y1), DALM_E_NULL, "null pointer argument");
-  DALM_REQUIRE(al16(y0) && al16(W0) && (!two || al16(W1)) && (mode != 3 || al16(y1)), DALM_E_ALIGN, "y / W must be 16-byte aligned");
+  DALM_REQUIRE(aligned16(y0, W0) && (!two || aligned16(W1)) && (mode != 3 || aligned16(y1)), DALM_E_ALIGN, "y / W must be 16-byte aligned");
   const bool bits = bits0 != nullptr;
   DALM_REQUIRE(!two || ((bits1 != nullptr) == bits), DALM_E_NULL, "either both terms carry a mask or neither");
   bf16_t* ya0 = static_cast<bf16_t*>(y0);
@@ -677,7 +677,7 @@ extern "C" int dalm_lora2_colacc_live(const void* x0, const void* x1, const floa
   DALM_LORA2_SHAPE(R, C, rank);
   const bool two = mode != 1;
   DALM_REQUIRE(x0 && z0 && out0 && ws && tickets && (!two || (z1 && out1)) && (mode != 3 || x1), DALM_E_NULL, "null pointer argument");
-  DALM_REQUIRE(al16(x0) && al16(z0) && (!two || al16(z1)) && (mode != 3 || al16(x1)) && (reinterpret_cast<uintptr_t>(ws) & 7) == 0,
+  DALM_REQUIRE(aligned16(x0, z0) && (!two || aligned16(z1)) && (mode != 3 || aligned16(x1)) && (reinterpret_cast<uintptr_t>(ws) & 7) == 0,
                DALM_E_ALIGN, "x / z must be 16-byte aligned, the workspace 8-byte aligned");
   DALM_REQUIRE(ws_bytes >= dalm_lora2_colacc_workspace_bytes(R, C, rank, mode), DALM_E_WORKSPACE, "workspace too small");
   const bool bits = bits0 != nullptr;

@@ -10,7 +10,7 @@
 //   (ties to the lower level - the decision tree compares with `>` against the midpoints);
 //   two 4-bit indices per byte, element 2j in the HIGH nibble;  w'_i = level[q_i] * a.
 // Both kernels are pure streaming work (HBM-bound): dequantise moves 0.5 B + 1/16 B in and 2 B (bf16) out per weight.
-#include "common.hpp"
+#include "vec16.hpp"
 
 namespace {
 using namespace dalm;
@@ -55,13 +55,7 @@ __global__ __launch_bounds__(256) void nf4_quantize_kernel(const T* __restrict__
       const float4 a = *reinterpret_cast<const float4*>(w + e0), b = *reinterpret_cast<const float4*>(w + e0 + 4);
       v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
     } else {
-      const uint4 a = *reinterpret_cast<const uint4*>(w + e0);
-      const unsigned int u[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        v[2 * j] = __uint_as_float(u[j] << 16);
-        v[2 * j + 1] = __uint_as_float(u[j] & 0xffff0000u);
-      }
+      dec8(*reinterpret_cast<const uint4*>(w + e0), v);
     }
   } else {
 #pragma unroll

@@ -8,72 +8,18 @@
 // lane accesses and padded tokens are never touched.  HBM-bound:
 //   forward : n_tok*D*eh bytes read (n_tok = unmasked tokens) + B*D*4 written
 //   backward: B*T*D*eh bytes written
-#include "common.hpp"
+#include "dispatch.hpp"
+#include "vec16.hpp"
 
 namespace dalm {
 namespace {
-
-struct bf16_t { unsigned short v; };
-
-template <typename T> struct HV;
-template <> struct HV<float> {
-  static constexpr int VEC = 4;
-  __device__ static __forceinline__ void load(const float* p, int nvalid, bool vec, float (&x)[4]) {
-    if (nvalid >= 4 && vec) {
-      // cached loads on purpose: the token states were just written by the encoder's last layer and sit in
-      // L2 / Infinity Cache (non-temporal loads measured 20 % slower here, unlike the CE kernels)
-      const float4 v = *reinterpret_cast<const float4*>(p);
-      x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) x[e] = (e < nvalid) ? p[e] : 0.f;
-    }
-  }
-  __device__ static __forceinline__ void store(float* p, int nvalid, bool vec, const float (&x)[4]) {
-    if (nvalid >= 4 && vec) {
-      *reinterpret_cast<float4*>(p) = make_float4(x[0], x[1], x[2], x[3]);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) if (e < nvalid) p[e] = x[e];
-    }
-  }
-};
-template <> struct HV<bf16_t> {
-  static constexpr int VEC = 8;
-  __device__ static __forceinline__ void load(const bf16_t* p, int nvalid, bool vec, float (&x)[8]) {
-    if (nvalid >= 8 && vec) {
-      const uint4 v = *reinterpret_cast<const uint4*>(p);
-      const unsigned int w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        x[2 * i] = __uint_as_float(w[i] << 16);
-        x[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) x[e] = (e < nvalid) ? bf16_to_f32(p[e].v) : 0.f;
-    }
-  }
-  __device__ static __forceinline__ void store(bf16_t* p, int nvalid, bool vec, const float (&x)[8]) {
-    if (nvalid >= 8 && vec) {
-      unsigned int w[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        w[i] = pack_bf16x2(x[2 * i], x[2 * i + 1]);
-      *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) if (e < nvalid) p[e].v = f32_to_bf16(x[e]);
-    }
-  }
-};
 
 // grid (DC, B); 4 waves share one 64*VEC-wide d-chunk and split the tokens.
 template <typename T>
 __global__ __launch_bounds__(256) void pool_sum_kernel(const T* __restrict__ h, const int64_t* __restrict__ mask,
                                                        int Tn, int D, int vec_ok, float* __restrict__ emb,
                                                        float* __restrict__ inv_count) {
-  constexpr int VEC = HV<T>::VEC;
+  constexpr int VEC = Vec16<T>::VEC;
   __shared__ float part[4][64 * VEC];
   __shared__ float cnt_part[4];
   const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -93,8 +39,8 @@ __global__ __launch_bounds__(256) void pool_sum_kernel(const T* __restrict__ h, 
     const int64_t m0 = mb[t];
     const int64_t m1 = (t2 < Tn) ? mb[t2] : 0;
     float x0[VEC], x1[VEC];
-    if (m0 != 0 && nvalid > 0) HV<T>::load(hb + static_cast<int64_t>(t) * D, nvalid, vec_ok, x0);
-    if (m1 != 0 && nvalid > 0) HV<T>::load(hb + static_cast<int64_t>(t2) * D, nvalid, vec_ok, x1);
+    if (m0 != 0 && nvalid > 0) Vec16<T>::load(hb + static_cast<int64_t>(t) * D, nvalid, vec_ok, x0);
+    if (m1 != 0 && nvalid > 0) Vec16<T>::load(hb + static_cast<int64_t>(t2) * D, nvalid, vec_ok, x1);
     const float f0 = static_cast<float>(m0), f1 = static_cast<float>(m1);
     cnt += f0 + f1;
     if (m0 != 0 && nvalid > 0) {
@@ -158,7 +104,7 @@ __global__ __launch_bounds__(NT) void pool_fused_kernel(const T* __restrict__ h,
                                                           float* __restrict__ emb, float* __restrict__ norm,
                                                           float* __restrict__ inv_count, float* __restrict__ part,
                                                           float* __restrict__ part_cnt) {
-  constexpr int VEC = HV<T>::VEC;
+  constexpr int VEC = Vec16<T>::VEC;
   constexpr int TIF = (NCH == 1) ? 8 : 4;   // token rows in flight per group on the fast path (128 B per thread)
   extern __shared__ float lds[];       // [G][Dp] partial sums, then reduction scratch
   __shared__ float red[16];
@@ -200,7 +146,7 @@ __global__ __launch_bounds__(NT) void pool_fused_kernel(const T* __restrict__ h,
 #pragma unroll
         for (int u = 0; u < TIF; ++u) {
           const int tt = (m[u] != 0) ? (t0 + u * G) : t_anchor;
-          HV<T>::load(hb + static_cast<int64_t>(tt) * D + dd, VEC, true, x[u]);
+          Vec16<T>::load(hb + static_cast<int64_t>(tt) * D + dd, VEC, true, x[u]);
         }
 #pragma unroll
         for (int u = 0; u < TIF; ++u) {
@@ -226,7 +172,7 @@ __global__ __launch_bounds__(NT) void pool_fused_kernel(const T* __restrict__ h,
         float x[4][VEC];
 #pragma unroll
         for (int u = 0; u < 4; ++u)
-          if (m[u] != 0 && nvalid > 0) HV<T>::load(hb + static_cast<int64_t>(t0 + u * G) * D + d, nvalid, false, x[u]);
+          if (m[u] != 0 && nvalid > 0) Vec16<T>::load(hb + static_cast<int64_t>(t0 + u * G) * D + d, nvalid, false, x[u]);
 #pragma unroll
         for (int u = 0; u < 4; ++u)
           if (m[u] != 0 && nvalid > 0) {
@@ -345,7 +291,7 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const float* __restrict__
                                                        const float* __restrict__ inv_count,
                                                        const int64_t* __restrict__ mask, int Tn, int D,
                                                        int normalize, int vec_ok, T* __restrict__ dh) {
-  constexpr int VEC = HV<T>::VEC;
+  constexpr int VEC = Vec16<T>::VEC;
   __shared__ float red[4];
   const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int d = (blockIdx.x * 64 + lane) * VEC;
@@ -382,7 +328,7 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const float* __restrict__
     float o[VEC];
 #pragma unroll
     for (int e = 0; e < VEC; ++e) o[e] = f * g[e];
-    HV<T>::store(hb + static_cast<int64_t>(t) * D, nvalid, vec_ok, o);
+    Vec16<T>::store(hb + static_cast<int64_t>(t) * D, nvalid, vec_ok, o);
   }
 }
 
@@ -397,7 +343,7 @@ __global__ __launch_bounds__(256) void pool_bwd_rows_kernel(const float* __restr
                                                             const float* __restrict__ inv_count,
                                                             const int64_t* __restrict__ mask, int Tn, int D,
                                                             int normalize, int tpr_log2, T* __restrict__ dh) {
-  constexpr int VEC = HV<T>::VEC;
+  constexpr int VEC = Vec16<T>::VEC;
   __shared__ float red[4];
   const int b = blockIdx.y, z = blockIdx.x, TZ = gridDim.x, tid = threadIdx.x;
   const int TPR = 1 << tpr_log2, G = 256 >> tpr_log2;
@@ -444,7 +390,7 @@ __global__ __launch_bounds__(256) void pool_bwd_rows_kernel(const float* __restr
             float o[VEC];
 #pragma unroll
             for (int e = 0; e < VEC; ++e) o[e] = f[u] * gv[q][e];
-            HV<T>::store(hb + static_cast<int64_t>(t) * D + d, VEC, true, o);
+            Vec16<T>::store(hb + static_cast<int64_t>(t) * D + d, VEC, true, o);
           }
         }
       }
@@ -465,7 +411,7 @@ __global__ __launch_bounds__(256) void pool_packed_kernel(const T* __restrict__ 
                                                           int nseq_out, int D, int wps, float* __restrict__ emb,
                                                           int64_t ld_emb, float* __restrict__ norm,
                                                           float* __restrict__ inv_count) {
-  constexpr int VEC = HV<T>::VEC;
+  constexpr int VEC = Vec16<T>::VEC;
   constexpr int TIF = (NCH <= 2) ? 4 : 2;       // token rows in flight per wave
   constexpr int DP = 64 * VEC * NCH;
   extern __shared__ float part[];               // [4][DP] when the waves of a sequence combine (wps > 1), nothing otherwise
@@ -496,7 +442,7 @@ __global__ __launch_bounds__(256) void pool_packed_kernel(const T* __restrict__ 
 #pragma unroll
       for (int u = 0; u < TIF; ++u) {
         const int r = r0 + u * wps;
-        HV<T>::load(h + static_cast<int64_t>(r < hi ? r : anchor) * D + dd, VEC, true, x[u]);
+        Vec16<T>::load(h + static_cast<int64_t>(r < hi ? r : anchor) * D + dd, VEC, true, x[u]);
       }
 #pragma unroll
       for (int u = 0; u < TIF; ++u) {
@@ -588,28 +534,15 @@ inline PoolPlan pool_plan(int64_t B, int64_t T, int64_t D, int vec) {
 template <typename T>
 void launch_pool_fused(const PoolPlan& pl, const T* h, const int64_t* mask, int B, int Tn, int D, int vok, int normalize,
                        float* emb, float* norm, float* inv_count, float* part, float* part_cnt, hipStream_t s) {
-  const int vec = HV<T>::VEC;
+  const int vec = Vec16<T>::VEC;
   const size_t lds = static_cast<size_t>(pl.nt) * vec * pl.nch * sizeof(float);
   const dim3 grid(static_cast<unsigned>(pl.tz), static_cast<unsigned>(B));
-#define DALM_POOL_LAUNCH(N, NT) \
-  hipLaunchKernelGGL((pool_fused_kernel<T, N, NT>), grid, dim3(NT), lds, s, h, mask, Tn, D, pl.tpr_log2, vok, normalize, \
-                     emb, norm, inv_count, part, part_cnt)
-  if (pl.nt == 256) {
-    switch (pl.nch) {
-      case 1: DALM_POOL_LAUNCH(1, 256); break;
-      case 2: DALM_POOL_LAUNCH(2, 256); break;
-      case 3: DALM_POOL_LAUNCH(3, 256); break;
-      default: DALM_POOL_LAUNCH(4, 256); break;
-    }
-  } else {
-    switch (pl.nch) {
-      case 1: DALM_POOL_LAUNCH(1, 1024); break;
-      case 2: DALM_POOL_LAUNCH(2, 1024); break;
-      case 3: DALM_POOL_LAUNCH(3, 1024); break;
-      default: DALM_POOL_LAUNCH(4, 1024); break;
-    }
-  }
-#undef DALM_POOL_LAUNCH
+  by_exact<256, 1024>(pl.nt, [&](auto nt) {
+    by_exact<1, 2, 3, 4>(pl.nch, [&](auto nch) {
+      hipLaunchKernelGGL((pool_fused_kernel<T, nch, nt>), grid, dim3(nt), lds, s, h, mask, Tn, D, pl.tpr_log2, vok, normalize,
+                         emb, norm, inv_count, part, part_cnt);
+    });
+  });
   if (pl.tz > 1)
     hipLaunchKernelGGL(pool_finish_kernel, dim3(static_cast<unsigned>(B)), dim3(256), 0, s, part, part_cnt, pl.tz, D,
                        normalize, emb, norm, inv_count);
@@ -633,28 +566,26 @@ extern "C" int dalm_pool_l2norm_fwd_ws(const void* h, int dtype, const int64_t* 
                "need 0<B<=65535, T>0, D>0");
   hipStream_t s = as_stream(stream);
   const int vec = (dtype == DALM_F32) ? 4 : 8;
-  const int vok = (reinterpret_cast<uintptr_t>(h) % 16 == 0) && (D % vec == 0);
+  const int vok = aligned16(h) && (D % vec == 0);
   PoolPlan pl = pool_plan(B, T, D, vec);
   const size_t need = dalm_pool_l2norm_fwd_workspace_bytes(B, T, D, dtype);
   if (pl.fused && pl.tz > 1 && (ws == nullptr || ws_bytes < need)) pl.tz = 1;   // no scratch: one slice per sample
   if (pl.fused) {
     float* part = static_cast<float*>(ws);
     float* part_cnt = part ? part + static_cast<size_t>(B) * pl.tz * D : nullptr;
-    if (dtype == DALM_F32)
-      launch_pool_fused<float>(pl, static_cast<const float*>(h), mask, static_cast<int>(B), static_cast<int>(T),
-                               static_cast<int>(D), vok, normalize, emb, norm, inv_count, part, part_cnt, s);
-    else
-      launch_pool_fused<bf16_t>(pl, static_cast<const bf16_t*>(h), mask, static_cast<int>(B), static_cast<int>(T),
-                                static_cast<int>(D), vok, normalize, emb, norm, inv_count, part, part_cnt, s);
+    by_dtype(dtype, [&](auto t) {
+      using Elt = typename decltype(t)::type;
+      launch_pool_fused<Elt>(pl, static_cast<const Elt*>(h), mask, static_cast<int>(B), static_cast<int>(T), static_cast<int>(D), vok,
+                           normalize, emb, norm, inv_count, part, part_cnt, s);
+    });
     return check_launch(__func__);
   }
   const dim3 grid(static_cast<unsigned>((D + 64 * vec - 1) / (64 * vec)), static_cast<unsigned>(B));
-  if (dtype == DALM_F32)
-    hipLaunchKernelGGL(pool_sum_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(h), mask,
-                       static_cast<int>(T), static_cast<int>(D), vok, emb, inv_count);
-  else
-    hipLaunchKernelGGL(pool_sum_kernel<bf16_t>, grid, dim3(256), 0, s, static_cast<const bf16_t*>(h), mask,
-                       static_cast<int>(T), static_cast<int>(D), vok, emb, inv_count);
+  by_dtype(dtype, [&](auto t) {
+    using Elt = typename decltype(t)::type;
+    hipLaunchKernelGGL(pool_sum_kernel<Elt>, grid, dim3(256), 0, s, static_cast<const Elt*>(h), mask, static_cast<int>(T),
+                       static_cast<int>(D), vok, emb, inv_count);
+  });
   hipLaunchKernelGGL(l2norm_rows_kernel, dim3(static_cast<unsigned>(B)), dim3(256), 0, s, emb,
                      static_cast<int>(D), normalize, norm);
   return check_launch(__func__);
@@ -675,7 +606,7 @@ extern "C" int dalm_pool_l2norm_bwd(const float* d_emb, const float* emb, const 
                "need 0<B<=65535, T>0, D>0");
   hipStream_t s = as_stream(stream);
   const int vec = (dtype == DALM_F32) ? 4 : 8;
-  const int vok = (reinterpret_cast<uintptr_t>(dh) % 16 == 0) && (D % vec == 0);
+  const int vok = aligned16(dh) && (D % vec == 0);
   const int64_t dc = (D + 64 * vec - 1) / (64 * vec);
   // token slices: every workgroup first rebuilds du (dot product over D, ~16 scalar loads per lane), so many thin slices
   // cost more than they spread - measured (tools/kernel_bench.py, hipGraph timing): cfg3 passage bf16 [18,128,1024]
@@ -705,25 +636,21 @@ extern "C" int dalm_pool_l2norm_bwd(const float* d_emb, const float* emb, const 
     if (rz > rz_max) rz = rz_max;
     if (rz < 1) rz = 1;
     const dim3 rgrid(static_cast<unsigned>(rz), static_cast<unsigned>(B));
-#define DALM_POOL_BWD_ROWS(TT, N) \
-    hipLaunchKernelGGL((pool_bwd_rows_kernel<TT, N>), rgrid, dim3(256), 0, s, d_emb, emb, norm, inv_count, mask, \
-                       static_cast<int>(T), static_cast<int>(D), normalize, pl.tpr_log2, static_cast<TT*>(dh))
-#define DALM_POOL_BWD_ROWS_N(TT) \
-    switch (pl.nch) { case 1: DALM_POOL_BWD_ROWS(TT, 1); break; case 2: DALM_POOL_BWD_ROWS(TT, 2); break; \
-                      case 3: DALM_POOL_BWD_ROWS(TT, 3); break; default: DALM_POOL_BWD_ROWS(TT, 4); break; }
-    if (dtype == DALM_F32) { DALM_POOL_BWD_ROWS_N(float) }
-    else { DALM_POOL_BWD_ROWS_N(bf16_t) }
-#undef DALM_POOL_BWD_ROWS_N
-#undef DALM_POOL_BWD_ROWS
+    by_dtype(dtype, [&](auto t) {
+      using Elt = typename decltype(t)::type;
+      by_exact<1, 2, 3, 4>(pl.nch, [&](auto nch) {
+        hipLaunchKernelGGL((pool_bwd_rows_kernel<Elt, nch>), rgrid, dim3(256), 0, s, d_emb, emb, norm, inv_count, mask,
+                           static_cast<int>(T), static_cast<int>(D), normalize, pl.tpr_log2, static_cast<Elt*>(dh));
+      });
+    });
     return check_launch(__func__);
   }
   const dim3 grid(static_cast<unsigned>(dc), static_cast<unsigned>(B), static_cast<unsigned>(tz));
-#define DALM_POOL_BWD(TT) \
-  hipLaunchKernelGGL((pool_bwd_kernel<TT>), grid, dim3(256), 0, s, d_emb, emb, norm, inv_count, mask, \
-                     static_cast<int>(T), static_cast<int>(D), normalize, vok, static_cast<TT*>(dh))
-  if (dtype == DALM_F32) DALM_POOL_BWD(float);
-  else DALM_POOL_BWD(bf16_t);
-#undef DALM_POOL_BWD
+  by_dtype(dtype, [&](auto t) {
+    using Elt = typename decltype(t)::type;
+    hipLaunchKernelGGL((pool_bwd_kernel<Elt>), grid, dim3(256), 0, s, d_emb, emb, norm, inv_count, mask, static_cast<int>(T),
+                       static_cast<int>(D), normalize, vok, static_cast<Elt*>(dh));
+  });
   return check_launch(__func__);
 }
 
@@ -736,7 +663,7 @@ extern "C" int dalm_pool_l2norm_packed_fwd(const void* h, int dtype, const int32
   DALM_REQUIRE(n > 0 && nseq > 0 && nseq_out >= 0 && nseq_out <= nseq && n <= 0x7fffffffll && nseq <= 0x7ffffff0ll &&
                    D > 0 && D % vec == 0 && D <= 64 * vec * 4 && ld_emb >= D,
                DALM_E_SHAPE, "need n>0, 0<=nseq_out<=nseq, D a multiple of 16 bytes and <= 256 lanes of them, ld_emb>=D");
-  DALM_REQUIRE(reinterpret_cast<uintptr_t>(h) % 16 == 0 && reinterpret_cast<uintptr_t>(emb) % 16 == 0 && ld_emb % 4 == 0,
+  DALM_REQUIRE(aligned16(h, emb) && ld_emb % 4 == 0,
                DALM_E_ALIGN, "h and emb rows must be 16-byte aligned");
   if (nseq_out == 0) return 0;
   const int64_t lanes = D / vec;
@@ -748,15 +675,13 @@ extern "C" int dalm_pool_l2norm_packed_fwd(const void* h, int dtype, const int32
   const int spw = 4 / wps;
   const dim3 grid(static_cast<unsigned>((nseq_out + spw - 1) / spw));
   hipStream_t s = as_stream(stream);
-#define DALM_POOL_PACKED(TT, N) \
-  hipLaunchKernelGGL((pool_packed_kernel<TT, N>), grid, dim3(256), wps > 1 ? 4 * 64 * vec * N * sizeof(float) : 0, s, static_cast<const TT*>(h), cu, static_cast<int>(n), \
-                     static_cast<int>(nseq_out), static_cast<int>(D), wps, emb, ld_emb, norm, inv_count)
-#define DALM_POOL_PACKED_N(TT) \
-  switch (nch) { case 1: DALM_POOL_PACKED(TT, 1); break; case 2: DALM_POOL_PACKED(TT, 2); break; \
-                 case 3: DALM_POOL_PACKED(TT, 3); break; default: DALM_POOL_PACKED(TT, 4); break; }
-  if (dtype == DALM_F32) { DALM_POOL_PACKED_N(float) }
-  else { DALM_POOL_PACKED_N(bf16_t) }
-#undef DALM_POOL_PACKED_N
-#undef DALM_POOL_PACKED
+  by_dtype(dtype, [&](auto t) {
+    using Elt = typename decltype(t)::type;
+    by_exact<1, 2, 3, 4>(nch, [&](auto nc) {
+      hipLaunchKernelGGL((pool_packed_kernel<Elt, nc>), grid, dim3(256), wps > 1 ? 4 * 64 * vec * nc * sizeof(float) : 0, s,
+                         static_cast<const Elt*>(h), cu, static_cast<int>(n), static_cast<int>(nseq_out), static_cast<int>(D), wps,
+                         emb, ld_emb, norm, inv_count);
+    });
+  });
   return check_launch(__func__);
 }

@@ -16,7 +16,8 @@
 // problems), operands staged k-major in LDS so that
 // every MFMA fragment read is one conflict-free ds_read_b32 per lane.
 // MFMA-bound: 2*m*n*D flop per launch against the 157 TF f32-matrix peak.
-#include "common.hpp"
+#include "dispatch.hpp"
+#include "vec16.hpp"
 #include <stdlib.h>
 
 namespace dalm {
@@ -46,16 +47,6 @@ struct GemmParams {
   const float* row_coef; const float* row_lse; const float* col_coef; const float* col_lse;
 };
 
-__device__ __forceinline__ float4 guarded_ld4(const float* p, int nvalid, bool vec_ok) {
-  if (nvalid >= 4 && vec_ok) return *reinterpret_cast<const float4*>(p);
-  float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (nvalid > 0) r.x = p[0];
-  if (nvalid > 1) r.y = p[1];
-  if (nvalid > 2) r.z = p[2];
-  if (nvalid > 3) r.w = p[3];
-  return r;
-}
-
 // Stages one operand tile (BR rows in the non-K dimension x BK) global -> regs -> LDS[k][r].
 // KC: source is X[r][k] (k contiguous) -> transposing ds_write_b32 (stride BR+1: conflict-free)
 // !KC: source is X[k][r] (r contiguous) -> ds_write_b128 rows (stride BR+4: 16-byte aligned)
@@ -75,13 +66,13 @@ struct Stage {
         const int r = r0 + rr, k = k0 + kq * 4;
         int nv = (r < R) ? (K - k) : 0;
         nv = nv < 0 ? 0 : nv;
-        v[p] = guarded_ld4(X + static_cast<int64_t>(r) * ld + k, nv, vec_ok);
+        v[p] = ld4_guard(X + static_cast<int64_t>(r) * ld + k, nv, vec_ok);
       } else {
         const int kk = idx / (BR / 4), rq = idx % (BR / 4);
         const int k = k0 + kk, r = r0 + rq * 4;
         int nv = (k < K) ? (R - r) : 0;
         nv = nv < 0 ? 0 : nv;
-        v[p] = guarded_ld4(X + static_cast<int64_t>(k) * ld + r, nv, vec_ok);
+        v[p] = ld4_guard(X + static_cast<int64_t>(k) * ld + r, nv, vec_ok);
       }
     }
   }
@@ -1113,10 +1104,6 @@ inline StreamPlan stream_plan(int64_t m, int64_t n, int64_t D, bool always = fal
   return f;
 }
 
-inline bool vec_ok(const float* p, int64_t ld) {
-  return (reinterpret_cast<uintptr_t>(p) % 16 == 0) && (ld % 4 == 0);
-}
-
 template <int BM, int BN, int BK, int EPI>
 void launch_gemm_tile(bool a_kc, bool b_kc, GemmParams p, hipStream_t s, int splitk = 1) {
   p.tiles_n = static_cast<unsigned>((p.N + BN - 1) / BN);
@@ -1136,8 +1123,6 @@ inline int64_t rowstats_parts(int64_t m, int64_t n) {
   const int64_t bn = use_big_tiles(m, n) ? 128 : 64;
   return 2 * ((n + bn - 1) / bn);
 }
-
-inline int64_t round_up4(int64_t x) { return (x + 3) / 4 * 4; }
 
 // Split-K for S = A.B^T problems that cannot fill 256 CUs with 64x64 tiles (the real batch sizes: 18 ... ~1200
 // rows): SK partial slabs + a one-block-per-row epilogue.  Returns 1 when the direct kernels are used.
@@ -1179,7 +1164,7 @@ extern "C" int dalm_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64
   GemmParams p{};
   p.A = A; p.lda = lda; p.B = Bm; p.ldb = ldb;
   p.M = static_cast<int>(M); p.N = static_cast<int>(N); p.K = static_cast<int>(K);
-  p.alpha = alpha; p.a_vec = vec_ok(A, lda); p.b_vec = vec_ok(Bm, ldb);
+  p.alpha = alpha; p.a_vec = rows_aligned16(A, lda); p.b_vec = rows_aligned16(Bm, ldb);
   p.C = C; p.ldc = ldc;
   // A k-contiguous <=> not transposed; B k-contiguous <=> transposed ([N,K])
   launch_gemm<EPI_STORE>(!transA, transB != 0, p, as_stream(stream));
@@ -1205,7 +1190,7 @@ static size_t rowstats_ws_f32(int64_t m, int64_t n, int64_t D) {
   if (const StreamPlan f = stream_plan(m, n, D); f.ok)   // k-major copies | (max, sum) granules [nsplit][m] (8 B each) | tickets
     return (static_cast<size_t>(f.kpad) * (f.ldm + f.ldn) + 2 * static_cast<size_t>(f.nsplit) * m + f.row_blocks + 2) * sizeof(float);
   const int sk = sim_splitk(m, n, D);
-  if (sk > 1) return static_cast<size_t>(sk) * static_cast<size_t>(m) * static_cast<size_t>(round_up4(n)) * sizeof(float);
+  if (sk > 1) return static_cast<size_t>(sk) * static_cast<size_t>(m) * static_cast<size_t>(round_up(n, 4)) * sizeof(float);
   return static_cast<size_t>(rowstats_parts(m, n)) * static_cast<size_t>(m) * 2 * sizeof(float);
 }
 
@@ -1263,9 +1248,9 @@ extern "C" int dalm_sim_rowstats_f32(const float* A, const float* Bm, int64_t m,
   GemmParams p{};
   p.A = A; p.lda = D; p.B = Bm; p.ldb = D;
   p.M = static_cast<int>(m); p.N = static_cast<int>(n); p.K = static_cast<int>(D);
-  p.alpha = scale; p.a_vec = vec_ok(A, D); p.b_vec = vec_ok(Bm, D);
+  p.alpha = scale; p.a_vec = rows_aligned16(A, D); p.b_vec = rows_aligned16(Bm, D);
   if (const int sk = sim_splitk(m, n, D); sk > 1) {
-    p.C = static_cast<float*>(ws); p.ldc = round_up4(n);
+    p.C = static_cast<float*>(ws); p.ldc = round_up(n, 4);
     launch_gemm_tile<64, 64, BK_SMALL, EPI_PARTIAL>(true, true, p, s, sk);
     hipLaunchKernelGGL(splitk_rowstats_kernel, dim3(static_cast<unsigned>(m)), dim3(256), 0, s, p.C, sk, p.M, p.N,
                        p.ldc, scale, diag_offset, row_lse, diag);
@@ -1292,7 +1277,7 @@ extern "C" size_t dalm_sim_grad_workspace_bytes(int64_t m, int64_t n, int64_t D)
     const FlashPlan f = flash_plan(m, n, D);   // k-major operand copies (+ per-split partial outputs)
     return (flash_copy_floats(f, D) + (f.nsplit > 1 ? static_cast<size_t>(f.nsplit) * m * D : 0)) * sizeof(float);
   }
-  const size_t panel = static_cast<size_t>(m) * static_cast<size_t>(round_up4(n)) * sizeof(float);
+  const size_t panel = static_cast<size_t>(m) * static_cast<size_t>(round_up(n, 4)) * sizeof(float);
   const int sk = sim_splitk(m, n, D);
   return panel * static_cast<size_t>(sk > 1 ? 1 + sk : 1);  // dS panel (+ split-K slabs)
 }
@@ -1350,13 +1335,13 @@ extern "C" int dalm_sim_grad(const float* A, const float* Bm, int64_t m, int64_t
     }
     return check_launch(__func__);
   }
-  const int64_t ldd = round_up4(n);
+  const int64_t ldd = round_up(n, 4);
   float* dS = static_cast<float*>(ws);
   {  // dS panel: recompute S tiles on the MFMA, transform in the epilogue
     GemmParams p{};
     p.A = A; p.lda = D; p.B = Bm; p.ldb = D;
     p.M = static_cast<int>(m); p.N = static_cast<int>(n); p.K = static_cast<int>(D);
-    p.alpha = scale; p.a_vec = vec_ok(A, D); p.b_vec = vec_ok(Bm, D);
+    p.alpha = scale; p.a_vec = rows_aligned16(A, D); p.b_vec = rows_aligned16(Bm, D);
     if (const int sk = sim_splitk(m, n, D); sk > 1) {
       float* part = dS + m * ldd;  // slabs live behind the dS panel
       p.C = part; p.ldc = ldd;
@@ -1373,7 +1358,7 @@ extern "C" int dalm_sim_grad(const float* A, const float* Bm, int64_t m, int64_t
     GemmParams p{};
     p.A = dS; p.lda = ldd; p.B = Bm; p.ldb = D;
     p.M = static_cast<int>(m); p.N = static_cast<int>(D); p.K = static_cast<int>(n);
-    p.alpha = scale; p.a_vec = vec_ok(dS, ldd); p.b_vec = vec_ok(Bm, D);
+    p.alpha = scale; p.a_vec = rows_aligned16(dS, ldd); p.b_vec = rows_aligned16(Bm, D);
     p.C = dA; p.ldc = D;
     launch_gemm<EPI_STORE>(true, false, p, s);
   }
@@ -1549,7 +1534,7 @@ extern "C" int dalm_sim_gold_score(const float* Q, const float* C, const int64_t
   DALM_REQUIRE(Q && C && gold && gold_score, DALM_E_NULL, "null pointer argument");
   if (int e = check_gemm_dims(m, n, D, __func__)) return e;
   DALM_REQUIRE(col_offset >= 0, DALM_E_SHAPE, "col_offset must not be negative");
-  const int v4 = vec_ok(Q, D) && vec_ok(C, D);
+  const int v4 = rows_aligned16(Q, D) && rows_aligned16(C, D);
   hipLaunchKernelGGL(gold_score_kernel, dim3(static_cast<unsigned>((m + 63) / 64)), dim3(64), 0, as_stream(stream), Q, C,
                      gold, col_offset, static_cast<int>(m), static_cast<int>(n), static_cast<int>(D), v4, scale, gold_score);
   return check_launch(__func__);

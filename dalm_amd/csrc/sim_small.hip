@@ -17,22 +17,13 @@
 // Exact f32 throughout (|S| <= 100, see sim.hip).  Deterministic: fixed summation orders, no float atomics.
 // Bound: launch/latency (46 MFLOP and 1.2 MB at 150^2 x 1024); the roofline-relevant similarity kernels are
 // the large-batch ones in sim.hip.
-#include "common.hpp"
+#include "dispatch.hpp"
+#include "vec16.hpp"
 
 namespace dalm {
 namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-__device__ __forceinline__ float4 ld4_guard(const float* p, int nvalid, bool vec_ok) {
-  if (nvalid >= 4 && vec_ok) return *reinterpret_cast<const float4*>(p);
-  float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (nvalid > 0) r.x = p[0];
-  if (nvalid > 1) r.y = p[1];
-  if (nvalid > 2) r.z = p[2];
-  if (nvalid > 3) r.w = p[3];
-  return r;
-}
 
 // C/D layout of v_mfma_f32_32x32x2_f32: acc[r] of lane l is (row = (r&3) + 8*(r>>2) + 4*(l>>5), col = l&31)
 __device__ __forceinline__ int mfma_row(int r, int lhi) { return (r & 3) + 8 * (r >> 2) + 4 * lhi; }
@@ -729,8 +720,6 @@ __global__ __launch_bounds__(1024) void rag_loss_finalize_kernel(const float* __
   }
 }
 
-inline int64_t round_up(int64_t x, int64_t q) { return (x + q - 1) / q * q; }
-
 struct SmallPlan { int sk, k_chunk; int64_t ldn, ldm; };
 inline SmallPlan small_plan(int64_t m, int64_t n, int64_t D) {
   const int64_t tiles = ((m + 31) / 32) * ((n + 31) / 32);
@@ -744,7 +733,6 @@ inline SmallPlan small_plan(int64_t m, int64_t n, int64_t D) {
   sk = (D + k_chunk - 1) / k_chunk;
   return {static_cast<int>(sk), static_cast<int>(k_chunk), round_up(n, 4), round_up(m, 4)};
 }
-inline bool vec16(const float* p, int64_t ld) { return (reinterpret_cast<uintptr_t>(p) % 16 == 0) && (ld % 4 == 0); }
 
 }  // namespace
 }  // namespace dalm
@@ -786,7 +774,7 @@ extern "C" int dalm_sim_small_fwd(const float* A, const float* Bm, int64_t m, in
   // slices: 512^2 ... 1024^2 on one GPU, the 150 x 1200 per-rank blocks), 4 rounds in flight (measured:
   // profiles/history/r04_small_pipe.txt, 512^2 -8 %, 150 x 1200 -4 %; depth 2-4 alike)
   const int rounds = (pl.k_chunk % 128 == 0 && static_cast<int64_t>(pl.k_chunk) * pl.sk == D) ? pl.k_chunk / 128 : 0;
-  const bool fast = vec16(A, D) && vec16(Bm, D) && D % 8 == 0;
+  const bool fast = rows_aligned16(A, D) && rows_aligned16(Bm, D) && D % 8 == 0;
   const FusedFwd none{};
 #define DALM_PIPE(R) hipLaunchKernelGGL((small_partial_pipe_kernel<R, 4>), pgrid, dim3(256), 0, s, A, Bm, static_cast<int>(m), \
     static_cast<int>(n), static_cast<int>(D), pl.k_chunk, tiles_n, slab, static_cast<int>(pl.ldn), slabT, static_cast<int>(pl.ldm), none)
@@ -799,8 +787,8 @@ extern "C" int dalm_sim_small_fwd(const float* A, const float* Bm, int64_t m, in
                        static_cast<int>(pl.ldn), slabT, static_cast<int>(pl.ldm), none);
   else
     hipLaunchKernelGGL(small_partial_kernel<false>, pgrid, dim3(256), 0, s, A, Bm, static_cast<int>(m),
-                       static_cast<int>(n), static_cast<int>(D), pl.k_chunk, tiles_n, static_cast<int>(vec16(A, D)),
-                       static_cast<int>(vec16(Bm, D)), slab, static_cast<int>(pl.ldn), slabT, static_cast<int>(pl.ldm), none);
+                       static_cast<int>(n), static_cast<int>(D), pl.k_chunk, tiles_n, static_cast<int>(rows_aligned16(A, D)),
+                       static_cast<int>(rows_aligned16(Bm, D)), slab, static_cast<int>(pl.ldn), slabT, static_cast<int>(pl.ldm), none);
   const int64_t rmax = want_cols ? (m > n ? m : n) : m;
   const int64_t cmax = want_cols ? (m > n ? m : n) : n;                  // longest row the statistics pass reduces
   if (cmax > 256)
@@ -876,7 +864,7 @@ extern "C" int dalm_sim_small_fwd1(const float* A, const float* Bm, int64_t m, i
   fz.tickets = tickets; fz.sk = pl.sk; fz.tiles_m = L.tiles_m; fz.tiles_n = L.tiles_n;
   const dim3 pgrid(static_cast<unsigned>(L.tiles_m * L.tiles_n), static_cast<unsigned>(pl.sk));
   const int rounds = (pl.k_chunk % 128 == 0 && static_cast<int64_t>(pl.k_chunk) * pl.sk == D) ? pl.k_chunk / 128 : 0;
-  const bool fast = vec16(A, D) && vec16(Bm, D) && D % 8 == 0;
+  const bool fast = rows_aligned16(A, D) && rows_aligned16(Bm, D) && D % 8 == 0;
   float* nof = nullptr;
 #define DALM_PIPE1(R) hipLaunchKernelGGL((small_partial_pipe_kernel<R, 4, true>), pgrid, dim3(256), 0, s, A, Bm, static_cast<int>(m), \
     static_cast<int>(n), static_cast<int>(D), pl.k_chunk, L.tiles_n, nof, 0, nof, 0, fz)
@@ -888,8 +876,8 @@ extern "C" int dalm_sim_small_fwd1(const float* A, const float* Bm, int64_t m, i
                        static_cast<int>(n), static_cast<int>(D), pl.k_chunk, L.tiles_n, 1, 1, nof, 0, nof, 0, fz);
   else
     hipLaunchKernelGGL((small_partial_kernel<false, true>), pgrid, dim3(256), 0, s, A, Bm, static_cast<int>(m),
-                       static_cast<int>(n), static_cast<int>(D), pl.k_chunk, L.tiles_n, static_cast<int>(vec16(A, D)),
-                       static_cast<int>(vec16(Bm, D)), nof, 0, nof, 0, fz);
+                       static_cast<int>(n), static_cast<int>(D), pl.k_chunk, L.tiles_n, static_cast<int>(rows_aligned16(A, D)),
+                       static_cast<int>(rows_aligned16(Bm, D)), nof, 0, nof, 0, fz);
   return check_launch(__func__);
 }
 

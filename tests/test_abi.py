@@ -139,3 +139,35 @@ def test_header_is_plain_c(tmp_path):
     r = subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", str(ROOT / "include"), "-c", str(src),
                         "-o", str(tmp_path / "abi_check.o")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
+
+
+def test_every_quoted_include_is_a_build_header():
+    """A header that a source includes but _build.HEADERS leaves out would not enter the object stamps: editing it would leave
+    stale objects linked."""
+    from dalm_amd import _build
+
+    known = {p.resolve() for p in _build.HEADERS}
+    files = [_build.CSRC / s for s in _build.SOURCES] + [p for p in _build.HEADERS if p.parent == _build.CSRC]
+    assert sorted(_build.CSRC.glob("*.hpp")) == sorted(p for p in _build.HEADERS if p.parent == _build.CSRC)
+    for f in files:
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read_text(), flags=re.M):
+            assert (f.parent / inc).resolve() in known, f"{f.name} includes {inc}, which _build.HEADERS does not list"
+
+
+def test_dispatch_header_selection_rules(tmp_path):
+    """csrc/dispatch.hpp is host-only C++17: tests/dispatch_check.cpp includes nothing else of the library, is built with the
+    host compiler under the address and undefined-behaviour sanitizers, and checks every selection rule at its edges."""
+    import shutil
+    import subprocess
+
+    cxx = shutil.which("g++")
+    if cxx is None:
+        pytest.skip("g++ not available")
+    exe = tmp_path / "dispatch_check"
+    r = subprocess.run([cxx, "-std=c++17", "-Wall", "-Wextra", "-Werror", "-O1", "-g", "-fsanitize=address,undefined",
+                        "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",   # runtimes inside the program
+                        "-I", str(ROOT / "dalm_amd" / "csrc"), str(ROOT / "tests" / "dispatch_check.cpp"), "-o", str(exe)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip() == "dispatch ok", (r.returncode, r.stdout, r.stderr)

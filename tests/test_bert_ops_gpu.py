@@ -43,7 +43,10 @@ def _eager(a, res, w, b, eps, keep=None, p=0.0):
 
 
 CASES = [(4608, 1024, torch.float32), (1672, 1024, torch.bfloat16), (19 * 50, 384, torch.float32), (7, 1024, torch.bfloat16),
-         (33, 512, torch.float32), (5, 2048, torch.bfloat16), (64, 8, torch.float32)]
+         (33, 512, torch.float32), (5, 2048, torch.bfloat16), (64, 8, torch.float32),
+         # the launcher's arms (1 | 2 | 4 chunks of 512 elements x f32 | bf16 weights) that the shapes above leave out, and the
+         # first width past each edge: one chunk with bf16 weights, three chunks with f32 weights, 512 + 8, 1024 + 8
+         (5, 384, torch.bfloat16), (5, 1536, torch.float32), (5, 520, torch.bfloat16), (5, 1032, torch.float32)]
 
 
 @pytest.mark.parametrize("R,D,wdt", CASES)

@@ -36,8 +36,14 @@ POOL_PROFILES = {
 }
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("D", [384, 768, 1024])       # 768 in f32 is the three-chunks-per-lane form
+# d-chunks per lane (64 lanes x 16 bytes each): f32 384 / 768 / 1024 are 2 / 3 / 4, 128 is 1; bf16 384 / 768 / 1024 are 1 / 2 / 2,
+# 1280 and 2048 are 3 and 4 (f32 rows end at 1024).  The ids read <D>-dtype<i>, as a D x dtype grid would name them.
+PACKED_WIDTHS = [pytest.param(D, dt, id=f"{D}-dtype{i}")
+                 for i, dt in enumerate((torch.float32, torch.bfloat16)) for D in (384, 768, 1024, 128, 1280, 2048)
+                 if not (dt == torch.float32 and D > 1024)]
+
+
+@pytest.mark.parametrize("D,dtype", PACKED_WIDTHS)
 @pytest.mark.parametrize("profile", sorted(POOL_PROFILES))
 def test_packed_pool_vs_fp64_mean_pooling(dev, profile, D, dtype):
     """mean_pooling + F.normalize of the reference (rag_e2e_base_model.py:95-97,108-111) restated in fp64 on the packed rows."""

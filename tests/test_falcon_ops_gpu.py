@@ -71,7 +71,11 @@ def test_gelu_matches_torch_bf16(dev, shape):
 
 
 @pytest.mark.parametrize("R,D,bias", [(5, 8, True), (130, 256, True), (4608, 4544, True), (333, 1024, False), (64, 8192, True),
-                                      (77, 4544 - 8, True)])
+                                      (77, 4544 - 8, True),
+                                      # the launcher's ladder of 1, 2, 4, 6, 8, 9, 12, 16 chunks of 512 elements: every arm the
+                                      # shapes above leave out, on both sides of every edge (3, 4, 5, 6, 7, 8, 10, 12, 13 chunks)
+                                      (5, 1032, True), (5, 2048, False), (5, 2056, True), (5, 3072, True), (5, 3080, False),
+                                      (5, 4096, True), (5, 4616, True), (5, 6144, False), (5, 6152, True)])
 def test_layer_norm_vs_fp64_and_the_autocast_chain(dev, R, D, bias):
     from dalm_amd.models import tower_ops
 

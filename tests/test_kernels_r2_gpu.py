@@ -219,7 +219,10 @@ POOL = [(18, 50, 1024), (18, 128, 1024), (150, 128, 1024), (19, 160, 384), (3, 1
         # round 4: batches >= 512 take the 256-thread form of the forward (TPR 128 / 64 / 256 threads per row, two d-chunks)
         (600, 37, 1024), (512, 9, 384), (515, 5, 2056), (700, 3, 3000),
         # ... and their backward slices the tokens (B * d-chunks > 1024 workgroups)
-        (1200, 60, 1024), (1100, 7, 96), (530, 21, 1504), (1030, 3, 4104), (2100, 2, 8200)]
+        (1200, 60, 1024), (1100, 7, 96), (530, 21, 1504), (1030, 3, 4104), (2100, 2, 8200),
+        # the chunk counts the launchers select on that the shapes above leave out: four d-chunks per thread in the fused forward
+        # (f32, 12296 = 3074 lanes of 4) and in the row-major backward (f32 3080 = 770 lanes, bf16 6152 = 769 lanes; 256 per chunk)
+        (3, 5, 12296), (4, 6, 3080), (4, 6, 6152)]
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

@@ -28,7 +28,8 @@ def _rel(a, b):
     return float((a - b).norm() / (b.norm() + 1e-30))
 
 
-SHAPES = [(4608, 4096, 4096, 8), (150 * 50, 1024, 1024, 8), (37, 64, 40, 8), (5, 4104, 8200, 8), (300, 96, 72, 16), (1, 8, 8, 16)]
+SHAPES = [(4608, 4096, 4096, 8), (150 * 50, 1024, 1024, 8), (37, 64, 40, 8), (5, 4104, 8200, 8), (300, 96, 72, 16), (1, 8, 8, 16),
+          (9, 96, 64, 16)]     # rank 16 on the matrix cores in both weight layouts (K and N multiples of 32)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -64,7 +65,8 @@ def test_kernels_vs_float64(dev, R, K, N, rank, dtype):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("R,K,rank", [(4608, 4096, 8), (333, 1024, 8), (64, 8200, 8), (200, 96, 16)])
+@pytest.mark.parametrize("R,K,rank", [(4608, 4096, 8), (333, 1024, 8), (64, 8200, 8), (200, 96, 16),
+                                      (9, 40, 16)])     # rank 16 off the matrix cores for bf16 rows too (K % 32 != 0)
 def test_dropout_mask_is_the_same_in_all_three_kernels(dev, R, K, rank, dtype):
     """bf16 rows take the matrix-core rowdot (K % 32 == 0) and the VALU rankupd / colacc: three different code paths that have
     to agree on every mask bit."""
@@ -86,6 +88,14 @@ def test_dropout_mask_is_the_same_in_all_three_kernels(dev, R, K, rank, dtype):
     assert lhs == float((x.double() * dx.double()).sum())
     assert lhs == float((A.double() * da.double()).sum())
     assert float(z.abs().sum()) > 0
+    # the other weight layout of each kernel (the transposed matrix: the same products in the same order) and rankupd on a tensor
+    # of the activation dtype (|dx| <= 2 * rank: exact in bf16) draw the same mask
+    At = A.t().contiguous()
+    assert torch.equal(L._rowdot(x, At, False, rank, 2.0, 0.5, seed, salt), z)
+    assert torch.equal(L._rankupd_(torch.zeros(R, K, device=dev), u, At, True, rank, 2.0, 0.5, seed, salt), dx)
+    for w, cmajor in ((A, False), (At, True)):
+        dxt = L._rankupd_(torch.zeros(R, K, device=dev, dtype=dtype), u, w, cmajor, rank, 2.0, 0.5, seed, salt)
+        assert torch.equal(dxt.float(), dx)
     p = 0.05
     # keep rate: with A = ones and x = ones, z (1 - p) counts the survivors of each row
     ones = torch.ones(R, K, device=dev, dtype=dtype)

@@ -95,6 +95,12 @@ def test_swiglu_kernel_vs_eager_chain(dev, shape, dtype):
 NORM_CASES = [(R, D, dt) for dt in (torch.bfloat16, torch.float32)
               for R, D in [(4608, 4096), (7, 4096), (33, 1024), (5, 8192), (9, 40), (3, 4544)]
               if not (dt == torch.float32 and D > 4096)]          # f32 rows are supported up to 4096 elements
+# the launcher's chunk ladder (1, 2, 4, 8, 16 chunks of 64 lanes x 16 bytes per row; bf16 rows of up to 8 chunks take the second
+# backward form): the arms the list above leaves out, and both sides of every edge.  Chunks: bf16 3 (the last one partly filled),
+# 4, 5; f32 2, 3, 5, 8 (the last one partly filled), 9
+NORM_CASES += [(5, 1536, torch.bfloat16), (5, 2048, torch.bfloat16), (5, 2056, torch.bfloat16),
+               (5, 384, torch.float32), (5, 520, torch.float32), (5, 1028, torch.float32), (5, 1800, torch.float32),
+               (5, 2052, torch.float32)]
 
 
 @pytest.mark.parametrize("R,D,dtype", NORM_CASES)
