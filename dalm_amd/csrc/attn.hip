@@ -40,6 +40,7 @@
 // Algorithmic bytes: forward q, k, v read + o written = 4 B H T hd el (151 MB at cfg3); backward q, k, v, o, dO read + dq, dk, dv
 // written = 8 B H T hd el (302 MB; the two launches together move 1.5 x that: each re-reads q, k, v, dO); algorithmic flops
 // 2 / 5 GEMMs x 2 T^2 hd per head over the live tiles (dq and dk/dv each recompute S and dP: 7 are executed).
+#include <cstdio>
 #include "common.hpp"
 #include "dispatch.hpp"
 
@@ -80,8 +81,13 @@ struct AttnBwdParams {
   const unsigned short *cos, *sin;       // backward only, may be NULL: q and k are ROTATED tensors (rotary embedding applied by
   int64_t cs_b, cs_t;                    // dalm_rope_qk); dq and dk leave as gradients of the UN-rotated ones.  [B or 1, T, hd]
   const int* cu;                         // PACKED (un-padded) layout, may be NULL: sequence b = token rows cu[b] .. cu[b + 1] - 1 of
-};                                       // [n_tokens, H, hd] tensors (batch strides unused), T = the longest sequence; lse / delta /
+                                         // [n_tokens, H, hd] tensors (batch strides unused), T = the longest sequence; lse / delta /
                                          // mask words keep the padded [B, H, T] / [B, 32 W, W] layout (they are small)
+  int S;                                 // grouped dk / dv SPLIT over S workgroups per (key block, KV head): G / S query heads each,
+  float* part;                           // f32 partials [S][dK, dV][part_rows token rows][Hkv][hd] in caller workspace, summed in
+  int64_t part_rows;                     // the order s = 0 .. S - 1 by attn_gqa_combine_kernel (S = 1: no workspace, no combine)
+  int Hkv, G;                            // GROUPED-QUERY heads: k, v, dk, dv have Hkv heads, query head h reads KV head h / G,
+};                                       // G = H / Hkv (repeat_kv's order: KV head j serves query heads j G .. j G + G - 1)
 
 // where sequence b starts (token rows) and how many rows it has
 struct Seq { int64_t r0; int T; };
@@ -233,6 +239,65 @@ __device__ __forceinline__ void store_rows_unrope(const unsigned char* out, unsi
   }
 }
 
+// The same two steps for a gradient that is an f32 SUM over the query heads of a group (attn_bwd_dkdv2_gqa_kernel): there is no
+// two-node form to stay bit-equal with, so the tile stays f32 ([rows][4 HD + 16] bytes) and the rotation's backward runs on it -
+// o1 = g1 c1 + g2 s2,  o2 = g2 c2 - g1 s1 - with ONE rounding at the store.
+template <int HD>
+constexpr int f32_row() { return 4 * HD + 16; }
+template <int HD, int ND>
+__device__ __forceinline__ void spill_transposed_f32(const f32x16 (&acc)[ND], int d0, float mul, unsigned char* out, int tile, int l31, int hi) {
+#pragma unroll
+  for (int dblk = 0; dblk < ND; ++dblk)
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      *reinterpret_cast<float4*>(out + (32 * tile + l31) * f32_row<HD>() + 4 * (32 * (d0 + dblk) + 8 * q + 4 * hi)) =
+          make_float4(acc[dblk][4 * q] * mul, acc[dblk][4 * q + 1] * mul, acc[dblk][4 * q + 2] * mul, acc[dblk][4 * q + 3] * mul);
+}
+template <int HD, int N>
+__device__ __forceinline__ void store_rows_unrope_f32(const unsigned char* out, unsigned short* dst, int64_t row_stride, int row0, int T,
+                                                      int t, const unsigned short* cosb, const unsigned short* sinb, int64_t cs_t) {
+  constexpr int CH = AT<HD>::CH;
+#pragma unroll
+  for (int n = 0; n < N; ++n) {
+    const int row = t / CH + (256 / CH) * n, c = t % CH, pc = c ^ (CH / 2);
+    if (row0 + row >= T) continue;
+    const float* own = reinterpret_cast<const float*>(out + row * f32_row<HD>() + 32 * c);
+    const float* oth = reinterpret_cast<const float*>(out + row * f32_row<HD>() + 32 * pc);
+    const uint4 cv = ld16(cosb + static_cast<int64_t>(row0 + row) * cs_t + 8 * c);
+    const uint4 sv = ld16(sinb + static_cast<int64_t>(row0 + row) * cs_t + 8 * pc);
+    const unsigned int cc[4] = {cv.x, cv.y, cv.z, cv.w}, ss[4] = {sv.x, sv.y, sv.z, sv.w};
+    const float sgn = c < CH / 2 ? 1.0f : -1.0f;
+    unsigned int r[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float v[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const float cx = u ? __uint_as_float(cc[e] & 0xffff0000u) : __uint_as_float(cc[e] << 16);
+        const float sx = u ? __uint_as_float(ss[e] & 0xffff0000u) : __uint_as_float(ss[e] << 16);
+        v[u] = fmaf(own[2 * e + u], cx, sgn * oth[2 * e + u] * sx);
+      }
+      r[e] = pack_bf16x2(v[0], v[1]);
+    }
+    *reinterpret_cast<uint4*>(dst + static_cast<int64_t>(row0 + row) * row_stride + 8 * c) = make_uint4(r[0], r[1], r[2], r[3]);
+  }
+}
+
+// the f32 tile's rows -> an f32 tensor (row stride in elements); rows past the sequence or past the tensor (`room` rows) stay out
+template <int HD, int N>
+__device__ __forceinline__ void store_rows_f32(const unsigned char* out, float* dst, int64_t row_stride, int row0, int T, int64_t room, int t) {
+  constexpr int CH = AT<HD>::CH;
+#pragma unroll
+  for (int n = 0; n < N; ++n) {
+    const int row = t / CH + (256 / CH) * n, c = t % CH;
+    if (row0 + row >= T || row >= room) continue;
+    const float4* src = reinterpret_cast<const float4*>(out + row * f32_row<HD>() + 32 * c);
+    float4* d = reinterpret_cast<float4*>(dst + row * row_stride + 8 * c);
+    d[0] = src[0];
+    d[1] = src[1];
+  }
+}
+
 // Attention dropout: P o M / (1 - p) in front of the P V product (torch applies it there), M regenerated by every kernel from
 // (device seed word, per-call salt, element index) - never stored.  One 32-bit hash serves the PAIR of elements (i, j), (i, j + 1),
 // j even (T even): 16-bit fields compared with round(p 65536).  oracle/attn_dropout.py restates it; tests pin every bit.
@@ -258,14 +323,19 @@ __device__ __forceinline__ unsigned int drop_pair(const AttnDrop& d, unsigned in
 // blocks of every (batch, head) are launched first, the light ones fill the tail (interleaved, the last workgroups to start were
 // heavy ones and ran alone for a third of the kernel's time).  Both row blocks of one (batch, head) keep the same launch index
 // mod 8 = the same XCD: the later one finds K / V (or Q / dO) in that L2 or in the Infinity Cache.
-__device__ __forceinline__ bool block_coords(const AttnBwdParams& p, int nblk, bool last_block_first, int& blk, int& h, int& b) {
-  const int pairs8 = (p.B * p.H + 7) & ~7;
+// `heads`: the head count the launch runs over (H; Hkv for the grouped dk / dv kernel, whose workgroups own a KV head).
+__device__ __forceinline__ bool block_coords_of(const AttnBwdParams& p, int heads, int nblk, bool last_block_first, int& blk, int& h,
+                                                int& b) {
+  const int pairs8 = (p.B * heads + 7) & ~7;
   const int n = blockIdx.x, a = n / pairs8, pair = n - a * pairs8;
   blk = last_block_first ? nblk - 1 - a : a;
-  if (pair >= p.B * p.H) return false;
-  h = pair % p.H;
-  b = pair / p.H;
+  if (pair >= p.B * heads) return false;
+  h = pair % heads;
+  b = pair / heads;
   return true;
+}
+__device__ __forceinline__ bool block_coords(const AttnBwdParams& p, int nblk, bool last_block_first, int& blk, int& h, int& b) {
+  return block_coords_of(p, p.H, nblk, last_block_first, blk, h, b);
 }
 
 // which 32-wide sub-blocks of the other axis have a live tile against this workgroup's NT 32-row tiles: bit jj (T <= 2048)
@@ -931,6 +1001,264 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv2_kernel(const AttnBwdPar
   store_rows<HD, A::N64>(dlds + A::RM, dv_base, p.s[7][2], j0, T, t);
 }
 
+// dk / dv for GROUPED-QUERY heads (k, v, dk, dv have Hkv heads; KV head hk serves query heads hk G .. hk G + G - 1): a workgroup
+// owns (64 key rows, KV head, batch), loads its K / V fragments once and streams the Q / dO blocks of ALL G query heads of its
+// group through attn_bwd_dkdv2_kernel's two-stage pipeline as ONE flattened (head in group, live query block) sequence - the
+// prefetch of the next block crosses head boundaries, lse / D rows follow the query head.  dV^T / dK^T stay in their f32
+// accumulators across the whole group and are scaled, un-rotated IN F32 (cos / sin given), rounded and stored ONCE: no per-head
+// dk / dv in memory, no host-side sum, no atomics, one rounding after an f32 sum.  The mask belongs to the batch row, not to the
+// head: every head of the group meets the same live blocks and the same mask words.  Per tile the arithmetic is
+// attn_bwd_dkdv2_kernel's.  No dropout.
+// SPLIT (a grid that under-fills the machine, e.g. B Hkv = 72 pairs of 4 key blocks): S workgroups share a (key block, KV head),
+// each runs G / S heads of the group and leaves its scaled f32 dK / dV tiles in the caller's workspace; attn_gqa_combine_kernel
+// adds them in a fixed order, un-rotates and rounds once.  Still no atomics, still one rounding after an f32 sum.
+template <int HD, bool SPLIT>
+__global__ __launch_bounds__(256, 2) void attn_bwd_dkdv2_gqa_kernel(const AttnBwdParams p) {
+  using A = AT<HD>;
+  constexpr int NDH = A::ND / 2;
+  constexpr int IMG = 64 * 2 * HD;                             // one block image
+  extern __shared__ __attribute__((aligned(16))) unsigned char dlds[];
+  // stage s: Q image at s 2 IMG, dO image at s 2 IMG + IMG; lse / D of the block's rows at 4 IMG + 512 s (+ 256)
+  const int t = threadIdx.x, w = t >> 6, l = t & 63, l31 = l & 31, hi = l >> 5, jt = w >> 1, dh = w & 1;
+  int blk, hk, b, part = 0;
+  if (!block_coords_of(p, SPLIT ? p.Hkv * p.S : p.Hkv, (p.T + 63) >> 6, false, blk, hk, b)) return;
+  if constexpr (SPLIT) { part = hk % p.S; hk /= p.S; }
+  const int j0 = blk * 64;
+  const int j = j0 + 32 * jt + l31;
+  const Seq sq = seq_of(p, b);
+  const int T = sq.T;
+  unsigned short* dk_base = p.dk + base_off(p, 6, b, hk, sq);
+  unsigned short* dv_base = p.dv + base_off(p, 7, b, hk, sq);
+  const unsigned long long need = need_mask<2>(p, b, j0 >> 5, false, l);
+  if (need == 0ull || T <= 0) {                                // no live tile for any head of the group
+    if constexpr (!SPLIT) {                                    // (split: the combine kernel writes the zeros)
+      store_rows<HD, A::N64>(nullptr, dk_base, p.s[6][2], j0, T, t);
+      store_rows<HD, A::N64>(nullptr, dv_base, p.s[7][2], j0, T, t);
+    }
+    return;
+  }
+  const int G = SPLIT ? p.G / p.S : p.G, h0 = hk * p.G + part * G;   // this workgroup's heads: h0 .. h0 + G - 1
+  const unsigned short* qbase0 = p.q + base_off(p, 0, b, h0, sq);
+  const unsigned short* gbase0 = p.d_o + base_off(p, 4, b, h0, sq);
+  const int64_t bh0 = static_cast<int64_t>(b) * p.H + h0;
+  const int Tp = 32 * p.W;
+  const int nI = (p.T + 63) >> 6;
+  unsigned int live = 0u;                                      // bit ib: query block ib has a live tile (T <= 2048: 32 blocks)
+  for (int ib = 0; ib < nI; ++ib) live |= (((need >> (2 * ib)) & 3ull) != 0ull ? 1u : 0u) << ib;
+
+  uint32_t nword[2];
+  const unsigned int lds0 = static_cast<unsigned int>(reinterpret_cast<uintptr_t>(dlds));   // LDS byte address of the carve-out
+  const int wu = __builtin_amdgcn_readfirstlane(w);
+  const unsigned int sq_row = static_cast<unsigned int>(p.s[0][2]), sg_row = static_cast<unsigned int>(p.s[4][2]);
+  auto issue = [&](int ib, int g, int stage) {                 // query block ib of head h0 + g
+    const unsigned int qi = lds0 + stage * (2 * IMG);
+    dma_block<HD>(qbase0 + g * p.s[0][1], sq_row, 64 * ib, T, qi, wu, l);
+    dma_block<HD>(gbase0 + g * p.s[4][1], sg_row, 64 * ib, T, qi + IMG, wu, l);
+    if (wu == 0) {
+      const unsigned int row = static_cast<unsigned int>(min(64 * ib + l, T - 1));
+      glds4(p.lse + (bh0 + g) * p.T, 4u * row, lds0 + 4 * IMG + 512 * stage);
+      glds4(p.delta + (bh0 + g) * p.T, 4u * row, lds0 + 4 * IMG + 512 * stage + 256);
+    }
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+      nword[c] = (j < Tp && 2 * ib + c < p.W) ? p.bits_cols[(static_cast<int64_t>(b) * Tp + j) * p.W + 2 * ib + c] : 0u;
+  };
+  // the flattened sequence: the live blocks of head h0, then of h0 + 1, ...; `rest` = what head h0 + g has left to issue
+  unsigned int rest = live;
+  int g = 0;
+  auto issue_next = [&](int stage) -> bool {
+    if (!rest) {
+      if (++g == G) return false;
+      rest = live;
+    }
+    const int ib = __builtin_ctz(rest);
+    rest &= rest - 1u;
+    issue(ib, g, stage);
+    return true;
+  };
+  issue_next(0);
+
+  bf16x8 Kb[A::KK], Vb[A::KK];
+  {
+    const bool ok = j < T;
+    const unsigned short* kr = p.k + base_off(p, 1, b, hk, sq) + static_cast<int64_t>(j) * p.s[1][2] + 8 * hi;
+    const unsigned short* vr = p.v + base_off(p, 2, b, hk, sq) + static_cast<int64_t>(j) * p.s[2][2] + 8 * hi;
+#pragma unroll
+    for (int kk = 0; kk < A::KK; ++kk) {
+      Kb[kk] = __builtin_bit_cast(bf16x8, ok ? ld16(kr + 16 * kk) : make_uint4(0u, 0u, 0u, 0u));
+      Vb[kk] = __builtin_bit_cast(bf16x8, ok ? ld16(vr + 16 * kk) : make_uint4(0u, 0u, 0u, 0u));
+    }
+  }
+  const float c1 = p.scale * kLog2e;
+  f32x16 dVt[NDH], dKt[NDH];
+#pragma unroll
+  for (int d = 0; d < NDH; ++d)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { dVt[d][r] = 0.f; dKt[d][r] = 0.f; }
+
+  int stage = 0;
+  while (true) {
+    stage_ready(nword);
+    const uint32_t word[2] = {nword[0], nword[1]};
+    const bool more = issue_next(stage ^ 1);
+    const unsigned char* Qi = dlds + stage * (2 * IMG);
+    const unsigned char* Gi = Qi + IMG;
+    const float* nl_s = reinterpret_cast<const float*>(dlds + 4 * IMG + 512 * stage);
+    const float* dl_s = nl_s + 64;
+#pragma unroll
+    for (int is = 0; is < 2; ++is) {
+      if (__builtin_amdgcn_ballot_w64(word[is] != 0u) == 0ull) continue;
+      f32x16 S, dP;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { S[r] = 0.f; dP[r] = 0.f; }
+#pragma unroll
+      for (int kk = 0; kk < A::KK; ++kk) {
+        S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_frag<HD>(Qi, is, l31, hi, kk), Kb[kk], S, 0, 0, 0);
+        dP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_frag<HD>(Gi, is, l31, hi, kk), Vb[kk], dP, 0, 0, 0);
+      }
+      unsigned int ppk[8], dpk[8];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float4 ls4 = *reinterpret_cast<const float4*>(nl_s + 32 * is + 8 * q + 4 * hi);
+        const float4 dl4 = *reinterpret_cast<const float4*>(dl_s + 32 * is + 8 * q + 4 * hi);
+        const float nl[4] = {-ls4.x * kLog2e, -ls4.y * kLog2e, -ls4.z * kLog2e, -ls4.w * kLog2e}, dl[4] = {dl4.x, dl4.y, dl4.z, dl4.w};
+        float pv[4], ds[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int il = 8 * q + 4 * hi + u;
+          pv[u] = ((word[is] >> il) & 1u) ? __builtin_amdgcn_exp2f(fmaf(S[4 * q + u], c1, nl[u])) : 0.f;
+          ds[u] = pv[u] * (dP[4 * q + u] - dl[u]);
+        }
+        ppk[2 * q] = pack_bf16x2(pv[0], pv[1]);
+        ppk[2 * q + 1] = pack_bf16x2(pv[2], pv[3]);
+        dpk[2 * q] = pack_bf16x2(ds[0], ds[1]);
+        dpk[2 * q + 1] = pack_bf16x2(ds[2], ds[3]);
+      }
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const bf16x8 pb = __builtin_bit_cast(bf16x8, make_uint4(ppk[4 * s], ppk[4 * s + 1], ppk[4 * s + 2], ppk[4 * s + 3]));
+        const bf16x8 db = __builtin_bit_cast(bf16x8, make_uint4(dpk[4 * s], dpk[4 * s + 1], dpk[4 * s + 2], dpk[4 * s + 3]));
+#pragma unroll
+        for (int d = 0; d < NDH; ++d) {
+          dVt[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_tr_frag<HD>(Gi, NDH * dh + d, 32 * is, s, l), pb, dVt[d], 0, 0, 0);
+          dKt[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_tr_frag<HD>(Qi, NDH * dh + d, 32 * is, s, l), db, dKt[d], 0, 0, 0);
+        }
+      }
+    }
+    if (!more) break;
+    stage ^= 1;
+  }
+  __syncthreads();
+  int le = l;
+  asm volatile("" : "+v"(le));                                 // the epilogue's LDS addresses are formed here, not carried through the loop
+  const int l31e = le & 31, hie = le >> 5;
+  if constexpr (SPLIT) {                                       // scaled f32 tiles -> this part's slice of the workspace, dK then dV
+    const int64_t grow0 = (p.cu ? sq.r0 : static_cast<int64_t>(b) * p.T) + j0;      // token row of the block's first row
+    float* pk = p.part + ((static_cast<int64_t>(part) * 2 * p.part_rows + grow0) * p.Hkv + hk) * HD;
+    const int64_t rs = static_cast<int64_t>(p.Hkv) * HD;
+    spill_transposed_f32<HD, NDH>(dKt, NDH * dh, p.scale, dlds, jt, l31e, hie);
+    __syncthreads();
+    store_rows_f32<HD, A::N64>(dlds, pk, rs, j0, T, p.part_rows - grow0, t);
+    __syncthreads();
+    spill_transposed_f32<HD, NDH>(dVt, NDH * dh, 1.0f, dlds, jt, l31e, hie);
+    __syncthreads();
+    store_rows_f32<HD, A::N64>(dlds, pk + p.part_rows * rs, rs, j0, T, p.part_rows - grow0, t);
+    return;
+  }
+  if (p.cos) {                                                 // un-rotate the f32 sums, round once (f32 dK tile, then the dV tile)
+    constexpr int DKF = 64 * f32_row<HD>();
+    static_assert(DKF + A::RM <= dkdv2_lds<HD>(), "epilogue tiles must fit the stages' LDS");
+    spill_transposed_f32<HD, NDH>(dKt, NDH * dh, p.scale, dlds, jt, l31e, hie);
+    spill_transposed<HD, NDH>(dVt, NDH * dh, 1.0f, dlds + DKF, jt, l31e, hie);
+    __syncthreads();
+    store_rows_unrope_f32<HD, A::N64>(dlds, dk_base, p.s[6][2], j0, T, t, p.cos + cs_off(p, b, sq), p.sin + cs_off(p, b, sq), p.cs_t);
+    store_rows<HD, A::N64>(dlds + DKF, dv_base, p.s[7][2], j0, T, t);
+    return;
+  }
+  spill_transposed<HD, NDH>(dKt, NDH * dh, p.scale, dlds, jt, l31e, hie);
+  spill_transposed<HD, NDH>(dVt, NDH * dh, 1.0f, dlds + A::RM, jt, l31e, hie);
+  __syncthreads();
+  store_rows<HD, A::N64>(dlds, dk_base, p.s[6][2], j0, T, t);
+  store_rows<HD, A::N64>(dlds + A::RM, dv_base, p.s[7][2], j0, T, t);
+}
+
+// The split form's second step: a workgroup owns (64 key rows, KV head, batch) as the unsplit kernel does, adds the S f32
+// partials of dK and dV in the order s = 0 .. S - 1 (fixed: the same bits on every run), applies the rotation's backward to the
+// f32 dK when cos / sin are given, rounds once and stores.  A key block without a live tile stores zeros (nothing was written
+// for it).  A thread holds one 16-byte output chunk of a row (and reads the partner chunk of dK for the rotation).
+template <int HD>
+__global__ __launch_bounds__(256) void attn_gqa_combine_kernel(const AttnBwdParams p) {
+  using A = AT<HD>;
+  constexpr int CH = A::CH;
+  const int t = threadIdx.x, l = t & 63;
+  int blk, hk, b;
+  if (!block_coords_of(p, p.Hkv, (p.T + 63) >> 6, false, blk, hk, b)) return;
+  const int j0 = blk * 64;
+  const Seq sq = seq_of(p, b);
+  const int T = sq.T;
+  unsigned short* dk_base = p.dk + base_off(p, 6, b, hk, sq);
+  unsigned short* dv_base = p.dv + base_off(p, 7, b, hk, sq);
+  const unsigned long long need = need_mask<2>(p, b, j0 >> 5, false, l);
+  if (need == 0ull || T <= 0) {
+    store_rows<HD, A::N64>(nullptr, dk_base, p.s[6][2], j0, T, t);
+    store_rows<HD, A::N64>(nullptr, dv_base, p.s[7][2], j0, T, t);
+    return;
+  }
+  const int64_t grow0 = (p.cu ? sq.r0 : static_cast<int64_t>(b) * p.T) + j0;
+  const int64_t rs = static_cast<int64_t>(p.Hkv) * HD, ps = 2 * p.part_rows * rs;     // row stride, part stride (elements)
+  const float* pk = p.part + (grow0 * p.Hkv + hk) * HD;
+  const unsigned short* cosb = p.cos ? p.cos + cs_off(p, b, sq) : nullptr;
+  const unsigned short* sinb = p.cos ? p.sin + cs_off(p, b, sq) : nullptr;
+#pragma unroll
+  for (int n = 0; n < A::N64; ++n) {
+    const int row = t / CH + (256 / CH) * n, c = t % CH, pc = c ^ (CH / 2);
+    if (j0 + row >= T || grow0 + row >= p.part_rows) continue;
+    float own[8], oth[8], dvv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { own[e] = 0.f; oth[e] = 0.f; dvv[e] = 0.f; }
+    for (int sidx = 0; sidx < p.S; ++sidx) {
+      const float* a = pk + sidx * ps + row * rs;
+      const float4 k0 = *reinterpret_cast<const float4*>(a + 8 * c), k1 = *reinterpret_cast<const float4*>(a + 8 * c + 4);
+      const float4 v0 = *reinterpret_cast<const float4*>(a + p.part_rows * rs + 8 * c);
+      const float4 v1 = *reinterpret_cast<const float4*>(a + p.part_rows * rs + 8 * c + 4);
+      const float kk[8] = {k0.x, k0.y, k0.z, k0.w, k1.x, k1.y, k1.z, k1.w}, vv[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { own[e] += kk[e]; dvv[e] += vv[e]; }
+      if (cosb) {
+        const float4 o0 = *reinterpret_cast<const float4*>(a + 8 * pc), o1 = *reinterpret_cast<const float4*>(a + 8 * pc + 4);
+        const float oo[8] = {o0.x, o0.y, o0.z, o0.w, o1.x, o1.y, o1.z, o1.w};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) oth[e] += oo[e];
+      }
+    }
+    unsigned int rk[4], rv[4];
+    if (cosb) {
+      const uint4 cv = ld16(cosb + static_cast<int64_t>(j0 + row) * p.cs_t + 8 * c);
+      const uint4 sv = ld16(sinb + static_cast<int64_t>(j0 + row) * p.cs_t + 8 * pc);
+      const unsigned int cc[4] = {cv.x, cv.y, cv.z, cv.w}, ss[4] = {sv.x, sv.y, sv.z, sv.w};
+      const float sgn = c < CH / 2 ? 1.0f : -1.0f;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float r2[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const float cx = u ? __uint_as_float(cc[e] & 0xffff0000u) : __uint_as_float(cc[e] << 16);
+          const float sx = u ? __uint_as_float(ss[e] & 0xffff0000u) : __uint_as_float(ss[e] << 16);
+          r2[u] = fmaf(own[2 * e + u], cx, sgn * oth[2 * e + u] * sx);
+        }
+        rk[e] = pack_bf16x2(r2[0], r2[1]);
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) rk[e] = pack_bf16x2(own[2 * e], own[2 * e + 1]);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) rv[e] = pack_bf16x2(dvv[2 * e], dvv[2 * e + 1]);
+    *reinterpret_cast<uint4*>(dk_base + static_cast<int64_t>(j0 + row) * p.s[6][2] + 8 * c) = make_uint4(rk[0], rk[1], rk[2], rk[3]);
+    *reinterpret_cast<uint4*>(dv_base + static_cast<int64_t>(j0 + row) * p.s[7][2] + 8 * c) = make_uint4(rv[0], rv[1], rv[2], rv[3]);
+  }
+}
+
 // the wave's 32 rows (lane <-> row) as B operands straight from HBM in fragment shape: k-step kk = the 16 bytes at d = 16 kk + 8 hi
 template <int HD>
 __device__ __forceinline__ void rows_frags_global(const unsigned short* base, int64_t row_stride, int row, int T, int hi, uint4 (&f)[AT<HD>::KK]) {
@@ -947,7 +1275,8 @@ constexpr int stream2_lds() { return 4 * 64 * 2 * HD; }      // two stages of (K
 // two stages of swizzled images, K^T operands by transpose reads of the K image, one barrier per block).  Q / dO fragments and
 // D = rowsum(dO o O) come from fragment-shaped loads (a lane pair l, l ^ 32 holds one row: even / odd 16-byte chunks); D is summed
 // in the first form's order (chunk dot products, then the butterfly over chunk pairs) so that both forms write the same bits.
-template <int HD, bool DROP>
+// GQA: k / v have Hkv heads and query head h streams KV head h / G - the only difference (same K / V values: same bits).
+template <int HD, bool DROP, bool GQA = false>
 __global__ __launch_bounds__(256, DROP ? 2 : AT<HD>::OCC) void attn_bwd_dq2_kernel(const AttnBwdParams p) {
   using A = AT<HD>;
   constexpr int IMG = 64 * 2 * HD;
@@ -966,8 +1295,9 @@ __global__ __launch_bounds__(256, DROP ? 2 : AT<HD>::OCC) void attn_bwd_dq2_kern
     store_rows<HD, A::N128>(nullptr, dq_base, p.s[5][2], i0, T, t);
     return;
   }
-  const unsigned short* kbase = p.k + base_off(p, 1, b, h, sq);
-  const unsigned short* vbase = p.v + base_off(p, 2, b, h, sq);
+  const int hk = GQA ? h / p.G : h;
+  const unsigned short* kbase = p.k + base_off(p, 1, b, hk, sq);
+  const unsigned short* vbase = p.v + base_off(p, 2, b, hk, sq);
   const int Tp = 32 * p.W;
   const int nJ = (p.T + 63) >> 6;
   unsigned int blocks = 0u;
@@ -1084,7 +1414,8 @@ __global__ __launch_bounds__(256, DROP ? 2 : AT<HD>::OCC) void attn_bwd_dq2_kern
 }
 
 // Forward, second form: attn_fwd_kernel's arithmetic on the same data path (K image read row-wise, V image by transpose reads).
-template <int HD, bool DROP>
+// GQA: as in attn_bwd_dq2_kernel.
+template <int HD, bool DROP, bool GQA = false>
 __global__ __launch_bounds__(256, (DROP && HD == 64) ? 2 : AT<HD>::OCC) void attn_fwd2_kernel(const AttnBwdParams p) {
   using A = AT<HD>;
   constexpr int IMG = 64 * 2 * HD;
@@ -1105,8 +1436,9 @@ __global__ __launch_bounds__(256, (DROP && HD == 64) ? 2 : AT<HD>::OCC) void att
     if (t < 128 && i0 + t < T) lse_out[bh * p.T + i0 + t] = 0.f;
     return;
   }
-  const unsigned short* kbase = p.k + base_off(p, 1, b, h, sq);
-  const unsigned short* vbase = p.v + base_off(p, 2, b, h, sq);
+  const int hk = GQA ? h / p.G : h;
+  const unsigned short* kbase = p.k + base_off(p, 1, b, hk, sq);
+  const unsigned short* vbase = p.v + base_off(p, 2, b, hk, sq);
   const int Tp = 32 * p.W;
   const int nJ = (p.T + 63) >> 6;
   unsigned int blocks = 0u;
@@ -1285,6 +1617,29 @@ __global__ __launch_bounds__(256) void attn_mask_bits_packed_kernel(const unsign
   if (wr) live[(static_cast<int64_t>(b) * W + (r >> 5)) * W + w] = 1;
 }
 
+// k, v (dk, dv) have Hkv heads: H for the plain entry points, a divisor of H for the grouped ones.  0 when the counts are usable.
+inline int check_heads(const char* fn, int64_t H, int64_t Hkv) {
+  if (Hkv >= 1 && H >= 1 && H % Hkv == 0) return 0;
+  char msg[160];
+  snprintf(msg, sizeof msg, "grouped-query heads: query heads H = %lld must be a positive multiple of key / value heads Hkv = %lld >= 1",
+           static_cast<long long>(H), static_cast<long long>(Hkv));
+  return fail(DALM_E_SHAPE, fn, msg);
+}
+
+// How many workgroups share a (key block, KV head) of the grouped dk / dv launch.  One workgroup per KV head fills the MI355X
+// (256 CUs x 2 resident workgroups of this kernel) from 512 workgroups on and measures faster than the per-head launch + sum
+// there (profiles/attn_gqa_bench.txt: 576 at the Llama-3-8B layer); a smaller grid is split by the smallest divisor of G that
+// gives the machine two rounds of workgroups, so that the light key blocks of the heavy-first order fill the tail.
+constexpr int64_t kGqaSlots = 512;
+inline int64_t gqa_splits(int64_t B, int64_t H, int64_t Hkv, int64_t T) {
+  const int64_t G = H / Hkv, wg = (B * Hkv + 7) / 8 * 8 * ((T + 63) / 64);
+  if (G <= 1 || wg >= kGqaSlots) return 1;
+  for (int64_t S = 2; S < G; ++S)
+    if (G % S == 0 && wg * S >= 2 * kGqaSlots) return S;
+  return G;
+}
+struct GqaSplit { int64_t S; void* ws; size_t ws_bytes; };     // S = 0: gqa_splits decides
+
 inline void set_dropout(AttnBwdParams& p, float dropout_p, const void* seed, uint32_t salt) {
   const bool on = dropout_p > 0.f;
   p.seed = on ? static_cast<const unsigned long long*>(seed) : nullptr;
@@ -1325,11 +1680,12 @@ extern "C" int dalm_attn_mask_bits_packed(const uint8_t* key_live, const int32_t
 
 static int dalm_attn_bwd_any(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
                          const uint32_t* bits_rows, const uint32_t* bits_cols, const uint8_t* live, const int32_t* cu, int64_t B, int64_t H,
-                         int64_t T, int64_t hd, float scale, const int64_t* strides, const void* cos, const void* sin,
+                         int64_t Hkv, int64_t T, int64_t hd, float scale, const int64_t* strides, const void* cos, const void* sin,
                          int64_t cs_stride_b, int64_t cs_stride_t, float dropout_p, const void* seed, uint32_t salt, void* dq,
-                         void* dk, void* dv, float* delta, dalm_stream_t stream) {
+                         void* dk, void* dv, float* delta, dalm_stream_t stream, GqaSplit split = {1, nullptr, 0}) {
   DALM_REQUIRE(q && k && v && o && d_o && lse && bits_rows && bits_cols && live && strides && dq && dk && dv && delta, DALM_E_NULL,
                "null pointer argument");
+  if (const int rc = check_heads(__func__, H, Hkv)) return rc;
   DALM_REQUIRE(hd == 128 || hd == 64, DALM_E_SHAPE, "head width must be 64 or 128");
   DALM_REQUIRE(B > 0 && H > 0 && T > 0 && T <= 2048 && B * H <= (1ll << 24), DALM_E_SHAPE, "need 0 < T <= 2048 and B H <= 2^24");
   const void* ptrs[8] = {q, k, v, o, d_o, dq, dk, dv};
@@ -1345,9 +1701,23 @@ static int dalm_attn_bwd_any(const void* q, const void* k, const void* v, const 
                DALM_E_ALIGN, "cos / sin: 16-byte aligned rows of hd elements");
   DALM_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f && (dropout_p == 0.f || (seed && T % 2 == 0)), DALM_E_SHAPE,
                "dropout needs 0 <= p < 1, a device seed word and an even T");
+  DALM_REQUIRE(Hkv == H || dropout_p == 0.f, DALM_E_SHAPE, "grouped-query heads run without attention dropout");
   AttnBwdParams p;
   set_dropout(p, dropout_p, seed, salt);
   p.cu = cu;
+  p.Hkv = static_cast<int>(Hkv); p.G = static_cast<int>(H / Hkv);
+  p.S = 1; p.part = nullptr; p.part_rows = 0;
+  if (Hkv != H) {
+    const int64_t S = split.S > 0 ? split.S : gqa_splits(B, H, Hkv, T);
+    DALM_REQUIRE(S >= 1 && (H / Hkv) % S == 0, DALM_E_SHAPE, "splits must divide the group size H / Hkv");
+    if (S > 1) {
+      DALM_REQUIRE(split.ws, DALM_E_NULL, "the split dk / dv form needs a workspace (dalm_attn_gqa_bwd_workspace_bytes)");
+      DALM_REQUIRE(aligned16(split.ws), DALM_E_ALIGN, "workspace must be 16-byte aligned");
+      const int64_t rows = static_cast<int64_t>(split.ws_bytes / (static_cast<size_t>(S) * 2 * Hkv * hd * sizeof(float)));
+      DALM_REQUIRE(rows >= (cu ? 1 : B * T), DALM_E_WORKSPACE, "workspace too small for the split dk / dv form");
+      p.S = static_cast<int>(S); p.part = static_cast<float*>(split.ws); p.part_rows = rows;
+    }
+  }
   p.cos = static_cast<const unsigned short*>(cos); p.sin = static_cast<const unsigned short*>(sin);
   p.cs_b = cs_stride_b; p.cs_t = cs_stride_t;
   p.q = static_cast<const unsigned short*>(q); p.k = static_cast<const unsigned short*>(k);
@@ -1368,7 +1738,9 @@ static int dalm_attn_bwd_any(const void* q, const void* k, const void* v, const 
       if (hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, dkdv_lds<128>()); e != hipSuccess)
         return fail(static_cast<int>(e), __func__, "could not raise the dynamic LDS limit of the dk / dv kernel");
     for (const void* fn : {reinterpret_cast<const void*>(attn_bwd_dkdv2_kernel<128, false>),
-                           reinterpret_cast<const void*>(attn_bwd_dkdv2_kernel<128, true>)})
+                           reinterpret_cast<const void*>(attn_bwd_dkdv2_kernel<128, true>),
+                           reinterpret_cast<const void*>(attn_bwd_dkdv2_gqa_kernel<128, false>),
+                           reinterpret_cast<const void*>(attn_bwd_dkdv2_gqa_kernel<128, true>)})
       if (hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, dkdv2_lds<128>()); e != hipSuccess)
         return fail(static_cast<int>(e), __func__, "could not raise the dynamic LDS limit of the dk / dv kernel");
     const char* env = getenv("DALM_ATTN_DKDV");
@@ -1378,6 +1750,23 @@ static int dalm_attn_bwd_any(const void* q, const void* k, const void* v, const 
   const int64_t pairs8 = (B * H + 7) / 8 * 8;
   const dim3 grid_dq(static_cast<unsigned>(pairs8 * ((T + 127) / 128))), grid_dkdv(static_cast<unsigned>(pairs8 * ((T + 63) / 64)));
   hipStream_t s = as_stream(stream);
+  if (Hkv != H) {      // grouped-query heads: dq per query head, dk / dv per KV head (a workgroup runs through its whole group)
+    const dim3 grid_kv(static_cast<unsigned>((B * Hkv + 7) / 8 * 8 * ((T + 63) / 64)));
+    const dim3 grid_split(static_cast<unsigned>((B * Hkv * p.S + 7) / 8 * 8 * ((T + 63) / 64)));
+#define DALM_ATTN_GQA_BWD(HD)                                                                                          \
+  do {                                                                                                                \
+    hipLaunchKernelGGL((attn_bwd_dq2_kernel<HD, false, true>), grid_dq, dim3(256), stream2_lds<HD>(), s, p);           \
+    if (p.S == 1) {                                                                                                   \
+      hipLaunchKernelGGL((attn_bwd_dkdv2_gqa_kernel<HD, false>), grid_kv, dim3(256), dkdv2_lds<HD>(), s, p);           \
+    } else {                                                                                                          \
+      hipLaunchKernelGGL((attn_bwd_dkdv2_gqa_kernel<HD, true>), grid_split, dim3(256), dkdv2_lds<HD>(), s, p);         \
+      hipLaunchKernelGGL((attn_gqa_combine_kernel<HD>), grid_kv, dim3(256), 0, s, p);                                  \
+    }                                                                                                                 \
+  } while (0)
+    if (hd == 128) DALM_ATTN_GQA_BWD(128); else DALM_ATTN_GQA_BWD(64);
+#undef DALM_ATTN_GQA_BWD
+    return check_launch(__func__);
+  }
 #define DALM_ATTN_BWD(HD, DROP)                                                                         \
   do {                                                                                                 \
     if (first_form) hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, DROP>), grid_dq, dim3(256), 0, s, p);  \
@@ -1396,7 +1785,7 @@ extern "C" int dalm_attn_bwd(const void* q, const void* k, const void* v, const 
                              int64_t T, int64_t hd, float scale, const int64_t* strides, const void* cos, const void* sin,
                              int64_t cs_stride_b, int64_t cs_stride_t, float dropout_p, const void* seed, uint32_t salt, void* dq,
                              void* dk, void* dv, float* delta, dalm_stream_t stream) {
-  return dalm_attn_bwd_any(q, k, v, o, d_o, lse, bits_rows, bits_cols, live, nullptr, B, H, T, hd, scale, strides, cos, sin,
+  return dalm_attn_bwd_any(q, k, v, o, d_o, lse, bits_rows, bits_cols, live, nullptr, B, H, H, T, hd, scale, strides, cos, sin,
                            cs_stride_b, cs_stride_t, dropout_p, seed, salt, dq, dk, dv, delta, stream);
 }
 
@@ -1407,14 +1796,38 @@ extern "C" int dalm_attn_bwd_packed(const void* q, const void* k, const void* v,
                                     const void* seed, uint32_t salt, void* dq, void* dk, void* dv, float* delta,
                                     dalm_stream_t stream) {
   DALM_REQUIRE(cu_seqlens, DALM_E_NULL, "null pointer argument");
-  return dalm_attn_bwd_any(q, k, v, o, d_o, lse, bits_rows, bits_cols, live, cu_seqlens, B, H, T, hd, scale, strides, cos, sin, 0,
+  return dalm_attn_bwd_any(q, k, v, o, d_o, lse, bits_rows, bits_cols, live, cu_seqlens, B, H, H, T, hd, scale, strides, cos, sin, 0,
                            cs_stride_t, dropout_p, seed, salt, dq, dk, dv, delta, stream);
 }
 
+extern "C" int dalm_attn_gqa_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
+                                 const uint32_t* bits_rows, const uint32_t* bits_cols, const uint8_t* live,
+                                 const int32_t* cu_seqlens, int64_t B, int64_t H, int64_t Hkv, int64_t T, int64_t hd, float scale,
+                                 const int64_t* strides, const void* cos, const void* sin, int64_t cs_stride_b,
+                                 int64_t cs_stride_t, int64_t splits, void* ws, size_t ws_bytes, void* dq, void* dk, void* dv,
+                                 float* delta, dalm_stream_t stream) {
+  DALM_REQUIRE(splits >= 0, DALM_E_SHAPE, "splits must be 0 (the library's choice) or a divisor of H / Hkv");
+  return dalm_attn_bwd_any(q, k, v, o, d_o, lse, bits_rows, bits_cols, live, cu_seqlens, B, H, Hkv, T, hd, scale, strides, cos, sin,
+                           cu_seqlens ? 0 : cs_stride_b, cs_stride_t, 0.f, nullptr, 0u, dq, dk, dv, delta, stream,
+                           GqaSplit{splits, ws, ws_bytes});
+}
+
+extern "C" int64_t dalm_attn_gqa_bwd_splits(int64_t B, int64_t H, int64_t Hkv, int64_t T) {
+  if (B <= 0 || T <= 0 || Hkv < 1 || H < 1 || H % Hkv != 0) return 1;
+  return gqa_splits(B, H, Hkv, T);
+}
+
+extern "C" size_t dalm_attn_gqa_bwd_workspace_bytes(int64_t rows, int64_t Hkv, int64_t hd, int64_t splits) {
+  if (rows <= 0 || Hkv <= 0 || hd <= 0 || splits <= 1) return 0;
+  return static_cast<size_t>(splits) * 2 * static_cast<size_t>(rows) * Hkv * hd * sizeof(float);
+}
+
 static int dalm_attn_fwd_any(const void* q, const void* k, const void* v, const uint32_t* bits_rows, const uint8_t* live,
-                            const int32_t* cu, int64_t B, int64_t H, int64_t T, int64_t hd, float scale, const int64_t* strides,
-                            float dropout_p, const void* seed, uint32_t salt, void* o, float* lse, dalm_stream_t stream) {
+                            const int32_t* cu, int64_t B, int64_t H, int64_t Hkv, int64_t T, int64_t hd, float scale,
+                            const int64_t* strides, float dropout_p, const void* seed, uint32_t salt, void* o, float* lse,
+                            dalm_stream_t stream) {
   DALM_REQUIRE(q && k && v && bits_rows && live && strides && o && lse, DALM_E_NULL, "null pointer argument");
+  if (const int rc = check_heads(__func__, H, Hkv)) return rc;
   DALM_REQUIRE(hd == 128 || hd == 64, DALM_E_SHAPE, "head width must be 64 or 128");
   DALM_REQUIRE(B > 0 && H > 0 && T > 0 && T <= 2048 && B * H <= (1ll << 24), DALM_E_SHAPE, "need 0 < T <= 2048 and B H <= 2^24");
   const void* ptrs[4] = {q, k, v, o};
@@ -1427,9 +1840,11 @@ static int dalm_attn_fwd_any(const void* q, const void* k, const void* v, const 
                "dropout needs 0 <= p < 1, a device seed word and an even T");
   for (int i : {1, 2})
     DALM_REQUIRE(T * strides[3 * i + 2] < (1ll << 30), DALM_E_SHAPE, "T x row stride must stay below 2^30 elements");
+  DALM_REQUIRE(Hkv == H || dropout_p == 0.f, DALM_E_SHAPE, "grouped-query heads run without attention dropout");
   AttnBwdParams p = {};
   set_dropout(p, dropout_p, seed, salt);
   p.cu = cu;
+  p.Hkv = static_cast<int>(Hkv); p.G = static_cast<int>(H / Hkv);
   p.q = static_cast<const unsigned short*>(q); p.k = static_cast<const unsigned short*>(k);
   p.v = static_cast<const unsigned short*>(v);
   p.bits_rows = bits_rows; p.live = live;
@@ -1443,6 +1858,11 @@ static int dalm_attn_fwd_any(const void* q, const void* k, const void* v, const 
   const int64_t pairs8 = (B * H + 7) / 8 * 8;
   const dim3 grid(static_cast<unsigned>(pairs8 * ((T + 127) / 128)));
   hipStream_t s = as_stream(stream);
+  if (Hkv != H) {                                              // grouped-query heads: query head h reads KV head h / G
+    if (hd == 128) hipLaunchKernelGGL((attn_fwd2_kernel<128, false, true>), grid, dim3(256), stream2_lds<128>(), s, p);
+    else hipLaunchKernelGGL((attn_fwd2_kernel<64, false, true>), grid, dim3(256), stream2_lds<64>(), s, p);
+    return check_launch(__func__);
+  }
   static const bool first_form = [] { const char* e = getenv("DALM_ATTN_FWD"); return e && e[0] == '1'; }();   // A/B runs
   if (first_form) {
     if (hd == 128) {
@@ -1465,7 +1885,7 @@ static int dalm_attn_fwd_any(const void* q, const void* k, const void* v, const 
 extern "C" int dalm_attn_fwd(const void* q, const void* k, const void* v, const uint32_t* bits_rows, const uint8_t* live, int64_t B,
                              int64_t H, int64_t T, int64_t hd, float scale, const int64_t* strides, float dropout_p, const void* seed,
                              uint32_t salt, void* o, float* lse, dalm_stream_t stream) {
-  return dalm_attn_fwd_any(q, k, v, bits_rows, live, nullptr, B, H, T, hd, scale, strides, dropout_p, seed, salt, o, lse, stream);
+  return dalm_attn_fwd_any(q, k, v, bits_rows, live, nullptr, B, H, H, T, hd, scale, strides, dropout_p, seed, salt, o, lse, stream);
 }
 
 extern "C" int dalm_attn_fwd_packed(const void* q, const void* k, const void* v, const uint32_t* bits_rows, const uint8_t* live,
@@ -1473,5 +1893,11 @@ extern "C" int dalm_attn_fwd_packed(const void* q, const void* k, const void* v,
                                     const int64_t* strides, float dropout_p, const void* seed, uint32_t salt, void* o, float* lse,
                                     dalm_stream_t stream) {
   DALM_REQUIRE(cu_seqlens, DALM_E_NULL, "null pointer argument");
-  return dalm_attn_fwd_any(q, k, v, bits_rows, live, cu_seqlens, B, H, T, hd, scale, strides, dropout_p, seed, salt, o, lse, stream);
+  return dalm_attn_fwd_any(q, k, v, bits_rows, live, cu_seqlens, B, H, H, T, hd, scale, strides, dropout_p, seed, salt, o, lse, stream);
+}
+
+extern "C" int dalm_attn_gqa_fwd(const void* q, const void* k, const void* v, const uint32_t* bits_rows, const uint8_t* live,
+                                 const int32_t* cu_seqlens, int64_t B, int64_t H, int64_t Hkv, int64_t T, int64_t hd, float scale,
+                                 const int64_t* strides, void* o, float* lse, dalm_stream_t stream) {
+  return dalm_attn_fwd_any(q, k, v, bits_rows, live, cu_seqlens, B, H, Hkv, T, hd, scale, strides, 0.f, nullptr, 0u, o, lse, stream);
 }

@@ -17,6 +17,9 @@ Attention dropout (BERT's attention_probs_dropout_prob in training mode) is appl
 from (a device seed word, a per-call salt, the element index) and never stored - this library's own generator
 (oracle/attn_dropout.py), not torch's philox stream.  Not supported under activation recompute (torch.utils.checkpoint): the
 salt is a host call counter, a re-run forward would draw another mask.
+Grouped-query heads (Llama-3 / Mistral / TinyLlama: k, v with Hkv < H heads) run un-expanded on `dalm_attn_gqa_fwd` /
+`dalm_attn_gqa_bwd` where `grouped_supported` holds: query head h reads KV head h // (H // Hkv), dk / dv come back with Hkv heads,
+summed over each group in f32 inside the kernel.  Elsewhere k / v are expanded by `repeat_kv` first.
 Everything the kernels do not take (CPU tensors, other head widths, odd T with dropout, float masks, a KV cache, no gradient wanted) goes
 to transformers' own `sdpa_attention_forward`, unchanged.  DALM_ATTN_KERNEL=0 keeps the model on "sdpa".
 """
@@ -100,8 +103,56 @@ def _dense_like(t: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _grouped(q, k) -> bool:
+    """k (and v) carry Hkv heads, 1 < Hkv < H: the grouped entry points.  (One KV head arrives as stride-0 views with H heads.)"""
+    return k.shape[1] != q.shape[1] and k.shape[1] > 1
+
+
+def _attn_forward_grouped(q, k, v, pk, scale):
+    B, H, T, hd = q.shape
+    sq = pk.packed
+    nseq, Tm = (B, T) if sq is None else (sq.nseq, sq.T)
+    out = torch.empty(B, T, H, hd, dtype=q.dtype, device=q.device).transpose(1, 2)
+    lse = torch.empty(nseq, H, Tm, dtype=torch.float32, device=q.device)
+    flat = []
+    for t in (q, k, v, out):
+        flat += _strides3(t)
+    hip.call("dalm_attn_gqa_fwd", hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(pk.rows), hip.ptr(pk.live),
+             None if sq is None else hip.ptr(sq.cu), nseq, H, k.shape[1], Tm, hd, float(scale), (C.c_int64 * 12)(*flat), hip.ptr(out),
+             hip.ptr(lse), hip.stream())
+    return out, lse
+
+
+_gqa_splits = [0]           # 0: the library's choice by grid size (dalm_attn_gqa_bwd_splits); tests set 1 or a divisor of H // Hkv
+
+
+def _attn_backward_grouped(q, k, v, out, lse, d_out, pk, scale, cos, sin):
+    B, H, T, hd = q.shape
+    sq = pk.packed
+    nseq, Tm = (B, T) if sq is None else (sq.nseq, sq.T)
+    dq, dk, dv = _dense_like(q), _dense_like(k), _dense_like(v)          # dk, dv: Hkv heads
+    delta = torch.empty(nseq, H, Tm, dtype=torch.float32, device=q.device)
+    flat = []
+    for t in (q, k, v, out, d_out, dq, dk, dv):
+        flat += _strides3(t)
+    cs_b = 0 if (cos is None or sq is not None or cos.shape[0] == 1) else cos.stride(0)
+    lib = hip.load()
+    splits = _gqa_splits[0] or int(lib.dalm_attn_gqa_bwd_splits(nseq, H, k.shape[1], Tm))
+    ws_bytes = int(lib.dalm_attn_gqa_bwd_workspace_bytes(B * T, k.shape[1], hd, splits))       # B T: the token rows of k / v
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=q.device) if ws_bytes else None
+    hip.call("dalm_attn_gqa_bwd", hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(out), hip.ptr(d_out), hip.ptr(lse), hip.ptr(pk.rows),
+             hip.ptr(pk.cols), hip.ptr(pk.live), None if sq is None else hip.ptr(sq.cu), nseq, H, k.shape[1], Tm, hd, float(scale),
+             (C.c_int64 * 24)(*flat), hip.ptr(cos), hip.ptr(sin), cs_b, 0 if cos is None else cos.stride(1), splits,
+             hip.ptr(ws), ws_bytes, hip.ptr(dq), hip.ptr(dk), hip.ptr(dv), hip.ptr(delta), hip.stream())
+    return dq, dk, dv
+
+
 def _attn_forward(q, k, v, pk, scale, causal, drop=(0.0, None, 0)):
     B, H, T, hd = q.shape
+    if _grouped(q, k):
+        if drop[0] != 0.0:
+            raise ValueError("dalm_amd: grouped-query attention kernels take no dropout (expand k / v with repeat_kv)")
+        return _attn_forward_grouped(q, k, v, pk, scale)
     if pk.packed is not None:                   # q, k, v: [1, H, n, hd] views of [n, H hd] projections; sequences from cu_seqlens
         sq = pk.packed
         out = torch.empty(1, T, H, hd, dtype=q.dtype, device=q.device).transpose(1, 2)
@@ -132,6 +183,8 @@ def _attn_backward(q, k, v, out, lse, d_out, pk, scale, cos=None, sin=None, drop
     B, H, T, hd = q.shape
     if d_out.stride(-1) != 1 or any(s % 8 for s in d_out.stride()[:3]):
         d_out = d_out.contiguous()
+    if _grouped(q, k):
+        return _attn_backward_grouped(q, k, v, out, lse, d_out, pk, scale, cos, sin)
     if pk.packed is not None:
         sq = pk.packed
         dq, dk, dv = _dense_like(q), _dense_like(k), _dense_like(v)
@@ -199,7 +252,8 @@ class _RopeSdpaHip(torch.autograd.Function):
         q2, k2 = tower_ops._rope_launch(q, k, cos, sin, False, live_rows.current(B * T, q.device))
         pk = _pack(mask, B, H, T, causal, q.dtype, q.device)
         # multi-query (ONE key / value head, Falcon-7B): the kernels read it through stride-0 head views - nothing is broadcast
-        # in memory; the backward kernels write per-head dk / dv, summed over the heads below
+        # in memory; the backward kernels write per-head dk / dv, summed over the heads below.  Grouped heads (1 < Hkv < H) go
+        # straight through: `_attn_forward` / `_attn_backward` take them to the grouped entry points, dk / dv return with Hkv heads
         ctx.mqa = k.shape[1] == 1 and H > 1
         kx = k2.expand(B, H, T, hd) if ctx.mqa else k2
         vx = v.expand(B, H, T, hd) if ctx.mqa else v
@@ -226,7 +280,7 @@ def rope_fusable(q, k, cos, sin) -> bool:
     return (tower_ops.rope_supported(q, k, cos, sin) and cos.dtype == torch.bfloat16 and cos.shape[-1] == q.shape[-1]
             and cos.stride(1) % 8 == 0 and (cos.shape[0] == 1 or cos.stride(0) % 8 == 0)
             and cos.data_ptr() % 16 == 0 and sin.data_ptr() % 16 == 0
-            and (k.shape == q.shape or (k.shape[1] == 1 and k.shape[0] == q.shape[0] and k.shape[2:] == q.shape[2:])))
+            and k.shape[0] == q.shape[0] and k.shape[2:] == q.shape[2:] and k.shape[1] >= 1 and q.shape[1] % k.shape[1] == 0)
 
 
 def rope_sdpa(query, key, value, cos, sin, mask, scale: float, causal: bool):
@@ -269,6 +323,32 @@ def packed_supported(query, key, value, dropout: float = 0.0) -> bool:
     return _views_ok(query, key, value) and not _off("DALM_ATTN_KERNEL")
 
 
+_MAX_GROUP = 16
+
+
+def group_ok(H: int, Hkv: int) -> bool:
+    """Head counts the grouped kernels are routed for: 1 < Hkv < H, whole groups of at most 16 query heads."""
+    return 1 < Hkv < H and H % Hkv == 0 and H // Hkv <= _MAX_GROUP
+
+
+def grouped_supported(query, key, value, mask=None, dropout: float = 0.0, causal: bool = False, kwargs=None, packed: bool = False) -> bool:
+    """What `dalm_attn_gqa_*` take un-expanded: key / value with Hkv heads, 1 < Hkv < H, H % Hkv == 0, H / Hkv <= 16, no dropout,
+    and everything `supported` (`packed_supported` for a packed call) asks of equal heads."""
+    if query.dim() != 4 or key.dim() != 4 or key.shape != value.shape or dropout != 0.0:
+        return False
+    if not group_ok(query.shape[1], key.shape[1]):
+        return False
+    if key.shape[0] != query.shape[0] or key.shape[2:] != query.shape[2:] or not _views_ok(key, value):
+        return False
+    if _off("DALM_ATTN_FWD_KERNEL"):                 # torch's forward knows equal heads only
+        return False
+    # the remaining conditions are those of equal heads: asked of head views with the query's shape
+    kx, vx = key[:, :1].expand(query.shape), value[:, :1].expand(query.shape)
+    if packed:
+        return packed_supported(query, kx, vx, dropout)
+    return supported(query, kx, vx, mask, dropout, causal, kwargs or {})
+
+
 def _packed_sdpa_torch(query, key, value, seqs, scale: float, dropout: float):
     """The packed attention without the kernels (CPU tensors, fp32, head widths they do not take): re-pad q / k / v to
     [nseq, H, T, hd] by index, torch's SDPA under the mask the sequence list describes, rows gathered back.  A row without a
@@ -298,10 +378,11 @@ def _packed_attention(module, query, key, value, attention_mask, seqs, dropout, 
     from transformers.integrations.sdpa_attention import repeat_kv
 
     groups = getattr(module, "num_key_value_groups", 1)
-    if groups > 1 and key.shape[1] != query.shape[1]:
+    native = groups > 1 and key.shape[1] != query.shape[1] and grouped_supported(query, key, value, dropout=dropout, packed=True)
+    if groups > 1 and key.shape[1] != query.shape[1] and not native:
         key, value = repeat_kv(key, groups), repeat_kv(value, groups)
     scale = float(scaling) if scaling is not None else float(query.shape[-1]) ** -0.5
-    if packed_supported(query, key, value, dropout):
+    if native or packed_supported(query, key, value, dropout):
         salt = 0
         if dropout > 0.0:
             module._dalm_attn_calls = getattr(module, "_dalm_attn_calls", 0) + 1
@@ -322,8 +403,11 @@ def dalm_sdpa_attention_forward(module, query, key, value, attention_mask, dropo
     groups = getattr(module, "num_key_value_groups", 1)
     causal = bool(query.shape[2] > 1 and attention_mask is None
                   and (is_causal if is_causal is not None else getattr(module, "is_causal", True)))
-    k2, v2 = (repeat_kv(key, groups), repeat_kv(value, groups)) if (groups > 1 and key.shape[1] != query.shape[1]) else (key, value)
-    if _off("DALM_ATTN_KERNEL") or not supported(query, k2, v2, attention_mask, dropout, causal, kwargs):
+    grouped = groups > 1 and key.shape[1] != query.shape[1]
+    native = (grouped and not _off("DALM_ATTN_KERNEL")                 # grouped heads the kernels read un-expanded
+              and grouped_supported(query, key, value, attention_mask, dropout, causal, kwargs))
+    k2, v2 = (repeat_kv(key, groups), repeat_kv(value, groups)) if (grouped and not native) else (key, value)
+    if _off("DALM_ATTN_KERNEL") or not (native or supported(query, k2, v2, attention_mask, dropout, causal, kwargs)):
         return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling,
                                       is_causal=is_causal, **kwargs)
     scale = float(scaling) if scaling is not None else float(query.shape[-1]) ** -0.5

@@ -598,16 +598,17 @@ def _llama_attention_forward(self, hidden_states, position_embeddings=None, atte
     causal = bool(query_states.shape[2] > 1 and attention_mask is None and getattr(self, "is_causal", True))
     if attention.packed_of(attention_mask) is not None:
         # packed (un-padded) call (dalm_amd/packed.py): [1, H, n, hd] views, sequences from the descriptor; same node
-        fused = (key_states.shape == query_states.shape and attention.packed_supported(query_states, key_states, value_states)
+        fused = ((attention.packed_supported(query_states, key_states, value_states)
+                  or attention.grouped_supported(query_states, key_states, value_states, packed=True))
                  and attention.rope_fusable(query_states, key_states, cos, sin))
-    else:
-        fused = (key_states.shape == query_states.shape
-                 and attention.supported(query_states, key_states, value_states, attention_mask, 0.0, causal, {})
+    else:                                            # equal heads, or grouped-query heads left un-expanded (same node)
+        fused = ((attention.supported(query_states, key_states, value_states, attention_mask, 0.0, causal, {})
+                  or attention.grouped_supported(query_states, key_states, value_states, attention_mask, 0.0, causal, {}))
                  and attention.rope_fusable(query_states, key_states, cos, sin))
     if fused:
         attn_output = attention.rope_sdpa(query_states, key_states, value_states, cos, sin, attention_mask, float(self.scaling), causal)
         attn_output = attn_output.transpose(1, 2)
-    else:                                            # grouped heads, CPU tensors, ...: transformers' own sequence from here on
+    else:                                            # CPU tensors, one KV head, ...: transformers' own sequence from here on
         import importlib
 
         from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS

@@ -598,6 +598,33 @@ int dalm_attn_bwd_packed(const void* q, const void* k, const void* v, const void
                          const void* sin, int64_t cs_stride_t, float dropout_p, const void* seed, uint32_t salt, void* dq, void* dk,
                          void* dv, float* delta, dalm_stream_t stream);
 
+/* GROUPED-QUERY forms (Llama-3 / Mistral / TinyLlama class generators: num_key_value_heads < num_attention_heads): q, o, d_o, dq
+ * have H heads, k, v, dk, dv have Hkv heads (their head strides are strides over KV heads), H a multiple of Hkv.  Query head h reads
+ * KV head h / (H / Hkv) - the order of transformers' repeat_kv: KV head j serves query heads j G .. j G + G - 1, G = H / Hkv.
+ * Nothing is expanded in memory: o, lse and dq carry the bits dalm_attn_fwd / dalm_attn_bwd write for K / V expanded by repeat_kv;
+ * dk / dv are summed over a group's query heads in f32 inside one workgroup and rounded once (no per-head gradients in memory, no
+ * atomics; with cos / sin the rotation's backward is applied to the f32 sum of dk in front of that one rounding).
+ * cu_seqlens NULL = the padded [B, heads, T, hd] layout, otherwise the packed one above (cs_stride_b is ignored).
+ * lse / delta stay [B, H, T]; no dropout.  Hkv == H computes what dalm_attn_fwd / dalm_attn_bwd (or their packed forms) compute.
+ * DALM_E_SHAPE unless Hkv >= 1 and H % Hkv == 0; every other limit as above.
+ * dk / dv launch: one workgroup per (64 key rows, KV head, batch) runs through its whole group.  Where that grid under-fills the
+ * machine (fewer than 512 workgroups) the group's heads are SPLIT over `splits` workgroups, each leaves scaled f32 partials in
+ * the caller's workspace and a combine kernel adds them in a fixed order, un-rotates and rounds once (no atomics).
+ *   dalm_attn_gqa_bwd_splits: the library's choice for a shape (1 = not split);
+ *   dalm_attn_gqa_bwd_workspace_bytes: rows = token rows of the k / v tensors (B T padded, n_tokens packed); 0 for splits <= 1;
+ *   dalm_attn_gqa_bwd: splits = 0 takes the library's choice, otherwise a divisor of H / Hkv; ws (16-byte aligned) may be NULL
+ *        when the form in use is not split, DALM_E_WORKSPACE when it is too small. */
+int dalm_attn_gqa_fwd(const void* q, const void* k, const void* v, const uint32_t* bits_rows, const uint8_t* live,
+                      const int32_t* cu_seqlens, int64_t B, int64_t H, int64_t Hkv, int64_t T, int64_t hd, float scale,
+                      const int64_t* strides, void* o, float* lse, dalm_stream_t stream);
+int dalm_attn_gqa_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
+                      const uint32_t* bits_rows, const uint32_t* bits_cols, const uint8_t* live, const int32_t* cu_seqlens,
+                      int64_t B, int64_t H, int64_t Hkv, int64_t T, int64_t hd, float scale, const int64_t* strides, const void* cos,
+                      const void* sin, int64_t cs_stride_b, int64_t cs_stride_t, int64_t splits, void* ws, size_t ws_bytes, void* dq,
+                      void* dk, void* dv, float* delta, dalm_stream_t stream);
+int64_t dalm_attn_gqa_bwd_splits(int64_t B, int64_t H, int64_t Hkv, int64_t T);
+size_t dalm_attn_gqa_bwd_workspace_bytes(int64_t rows, int64_t Hkv, int64_t hd, int64_t splits);
+
 /* ---- the low-rank branch of a LoRA-wrapped Linear ----------------------------------------------------------------
  * The reference wraps q_proj / v_proj (key / query / value for BERT retrievers) in peft LoRA adapters, r = 8, alpha = 16,
  * dropout 0.05 (dalm/models/rag_e2e_base_model.py:145-160, retriever_only_base_model.py:92-107); peft evaluates

@@ -1,5 +1,9 @@
 """Attention backward at the cfg3 layer shape (B 18, H 32, T 256, hd 128, HF causal + left-padding mask): `dalm_attn_bwd`
-against torch's memory-efficient backward, hipGraph replay timing.  -> stdout (profiles/r05_attn_bwd.txt)"""
+against torch's memory-efficient backward, hipGraph replay timing.  -> stdout (profiles/r05_attn_bwd.txt)
+
+--kv-heads N (grouped-query attention, N < H key / value heads): `dalm_attn_gqa_*` on the un-expanded k / v against the EXPANDED
+path - repeat_kv copies + the equal-heads kernels + autograd's sum of the per-head dk / dv - forward and backward, padded (causal +
+left padding) and packed layouts, alternated in one process.  -> stdout (profiles/attn_gqa_bench.txt)"""
 import argparse
 import sys
 from pathlib import Path
@@ -15,9 +19,12 @@ ap.add_argument("--H", type=int, default=32)
 ap.add_argument("--T", type=int, default=256)
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--lens", default="random", help="random (T/2..T) | full | <n> (every sequence n tokens, left-padded)")
+ap.add_argument("--hd", type=int, default=128, choices=(64, 128))
+ap.add_argument("--kv-heads", type=int, default=0, help="grouped-query heads: time dalm_attn_gqa_* against the expanded path")
+ap.add_argument("--rounds", type=int, default=3, help="--kv-heads: alternations of the two paths (median, min .. max reported)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
-B, H, T, hd = a.B, a.H, a.T, 128
+B, H, T, hd = a.B, a.H, a.T, a.hd
 g = torch.Generator().manual_seed(0)
 q, k, v, go = [torch.randn(B, T, H, hd, generator=g).bfloat16().to(dev).transpose(1, 2) for _ in range(4)]
 lens = torch.randint(T // 2, T + 1, (B,), generator=g)
@@ -33,34 +40,36 @@ scale = hd ** -0.5
 live_frac = float(mask.float().mean())
 
 
-def timed(fn, label, flops):
-    qq, kk, vv = [t.detach().clone().requires_grad_(True) for t in (q, k, v)]
+def timed(fn, label, flops, qkv=None, reps=5, quiet=False, d_out=None):
+    qq, kk, vv = [t.detach().clone().requires_grad_(True) for t in (qkv or (q, k, v))]
+    gg = go if d_out is None else d_out
     s = torch.cuda.Stream()
     torch.cuda.synchronize()
     with torch.cuda.stream(s):                       # forward on the capture stream: autograd replays the backward on it
         o = fn(qq, kk, vv)
         for _ in range(3):
-            torch.autograd.grad(o, (qq, kk, vv), go, retain_graph=True)
+            torch.autograd.grad(o, (qq, kk, vv), gg, retain_graph=True)
         torch.cuda.synchronize()
         gr = torch.cuda.CUDAGraph()
         with torch.cuda.graph(gr, stream=s):
             for _ in range(a.iters):
-                torch.autograd.grad(o, (qq, kk, vv), go, retain_graph=True)
+                torch.autograd.grad(o, (qq, kk, vv), gg, retain_graph=True)
     gr.replay()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    for _ in range(5):
+    for _ in range(reps):
         gr.replay()
     e1.record()
     torch.cuda.synchronize()
-    us = e0.elapsed_time(e1) * 1e3 / (5 * a.iters)
-    print(f"{label:48s} {us:8.1f} us   {flops / us / 1e6:7.1f} TFLOP/s on the live tiles' 5 products")
+    us = e0.elapsed_time(e1) * 1e3 / (reps * a.iters)
+    if not quiet:
+        print(f"{label:48s} {us:8.1f} us   {flops / us / 1e6:7.1f} TFLOP/s on the live tiles' 5 products")
     return us
 
 
-def timed_fwd(fn, label, flops):
-    qq, kk, vv = [t.detach().clone().requires_grad_(True) for t in (q, k, v)]
+def timed_fwd(fn, label, flops, qkv=None, reps=5, quiet=False, d_out=None):
+    qq, kk, vv = [t.detach().clone().requires_grad_(True) for t in (qkv or (q, k, v))]
     s = torch.cuda.Stream()
     torch.cuda.synchronize()
     with torch.cuda.stream(s):
@@ -75,13 +84,73 @@ def timed_fwd(fn, label, flops):
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    for _ in range(5):
+    for _ in range(reps):
         gr.replay()
     e1.record()
     torch.cuda.synchronize()
-    us = e0.elapsed_time(e1) * 1e3 / (5 * a.iters)
-    print(f"{label:48s} {us:8.1f} us   {flops / us / 1e6:7.1f} TFLOP/s on the live tiles' 2 products")
+    us = e0.elapsed_time(e1) * 1e3 / (reps * a.iters)
+    if not quiet:
+        print(f"{label:48s} {us:8.1f} us   {flops / us / 1e6:7.1f} TFLOP/s on the live tiles' 2 products")
     return us
+
+
+def grouped_bench(Hkv):
+    """Grouped against expanded, same inputs, alternated `--rounds` times; one line per (layout, pass): medians, spread, ratio."""
+    from transformers.integrations.sdpa_attention import repeat_kv
+
+    from dalm_amd import packed
+
+    G = H // Hkv
+    assert 1 < Hkv < H and H % Hkv == 0, "--kv-heads must divide --H, 1 < N < H"
+    el = 2
+    print(f"# grouped-query attention: B {B} H {H} Hkv {Hkv} (G {G}) T {T} hd {hd}; live fraction of the mask {live_frac:.3f}")
+    print(f"# algorithmic bytes: forward (2 + 2/G) B H T hd el = {(2 + 2 / G) * B * H * T * hd * el / 1e6:.0f} MB, "
+          f"backward (5 + 3/G) B H T hd el = {(5 + 3 / G) * B * H * T * hd * el / 1e6:.0f} MB (padded layout, padding included)")
+    reps = 20
+    print(f"# each figure: {a.iters} calls per hipGraph x {reps} replays, median of {a.rounds} alternations (min .. max) in us per call")
+    am = (col[None, :] >= st[:, None]).long()
+    rows, cu = packed.pack_plan(am, shifted=True, multiple=256)
+    _ids, _pos, desc, _valid = packed.packed_inputs(torch.zeros(B, T, dtype=torch.long, device=dev), am, rows.to(dev), cu.to(dev), True)
+    n = rows.numel()
+    layouts = {
+        "padded": ([torch.randn(B, T, h_, hd, generator=g).bfloat16().to(dev).transpose(1, 2) for h_ in (H, Hkv, Hkv)], mask),
+        "packed": ([torch.randn(1, n, h_, hd, generator=g).bfloat16().to(dev).transpose(1, 2) for h_ in (H, Hkv, Hkv)], desc),
+    }
+    from dalm_amd import hip
+
+    results = {}
+    for name, (qkv, m) in layouts.items():
+        nseq = B if name == "padded" else packed.packed_of(desc).nseq
+        chosen = int(hip.load().dalm_attn_gqa_bwd_splits(nseq, H, Hkv, T))
+        forms = sorted({chosen, 1} | ({2} if G % 2 == 0 and chosen > 1 else set()))      # dk / dv forms shown for the backward
+        d_out = torch.randn(qkv[0].shape[0], qkv[0].shape[2], H, hd, generator=g).bfloat16().to(dev).transpose(1, 2)
+        fns = {"grouped": lambda x, y, z, m=m: attention._SdpaHipBackward.apply(x, y, z, m, scale, False),
+               "expanded": lambda x, y, z, m=m: attention._SdpaHipBackward.apply(x, repeat_kv(y, G), repeat_kv(z, G), m, scale, False)}
+        assert attention.grouped_supported(qkv[0].detach().requires_grad_(True), qkv[1], qkv[2], m if name == "padded" else None,
+                                           packed=name == "packed")
+        for pas, timer in (("forward", timed_fwd), ("backward", timed)):
+            others = [S for S in forms if S != chosen] if pas == "backward" else []
+            t = {"grouped": [], "expanded": [], **{S: [] for S in others}}
+            for _ in range(a.rounds):
+                for which in ("grouped", "expanded", *others):
+                    attention._gqa_splits[0] = which if isinstance(which, int) else 0
+                    t[which].append(timer(fns["grouped" if isinstance(which, int) else which], "", 1.0, qkv=qkv, reps=reps, quiet=True,
+                                          d_out=d_out))
+            attention._gqa_splits[0] = 0
+            med = {w: sorted(x)[len(x) // 2] for w, x in t.items()}
+            results[(name, pas)] = med
+            print(f"{name:7s} {pas:8s} rows {qkv[0].shape[0] * qkv[0].shape[2]:6d}   grouped {med['grouped']:7.1f} ({min(t['grouped']):.1f} .. "
+                  f"{max(t['grouped']):.1f})   expanded {med['expanded']:7.1f} ({min(t['expanded']):.1f} .. {max(t['expanded']):.1f})   "
+                  f"expanded / grouped {med['expanded'] / med['grouped']:.2f}x")
+            if pas == "backward":
+                print(f"#   dk / dv form of the grouped figure: {chosen} workgroup(s) per (key block, KV head) - the library's choice for this grid"
+                      + "".join(f"; forced {S}: {med[S]:.1f} ({min(t[S]):.1f} .. {max(t[S]):.1f})" for S in others))
+    return results
+
+
+if a.kv_heads:
+    grouped_bench(a.kv_heads)
+    sys.exit(0)
 
 
 flops = 5 * 2.0 * B * H * T * T * hd * live_frac
