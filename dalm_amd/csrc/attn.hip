@@ -1,6 +1,6 @@
-// Scaled-dot-product attention of the towers - forward and backward, bf16, head width 128 (Llama-2-7b: BASELINE.json configs 3 / 4)
-// or 64 (Falcon-7b, config 5; bge-large / BERT, every config), arbitrary boolean mask (HF's causal + left-padding mask, BERT's
-// padding mask), optional attention dropout - hand-written for gfx950.
+// Scaled-dot-product attention of the towers - forward and backward, bf16, head width 128 (Llama-2-7b: BASELINE.json configs 3 / 4),
+// 64 (Falcon-7b, config 5; bge-large / BERT) or 32 (bge-small, config 1; e5-small, gte-small, all-MiniLM - "Head width 32" below),
+// arbitrary boolean mask (HF's causal + left-padding mask, BERT's padding mask), optional attention dropout - hand-written for gfx950.
 // transformers reaches torch.nn.functional.scaled_dot_product_attention through sdpa_attention_forward
 // (transformers/integrations/sdpa_attention.py) or FalconAttention.forward; the reference reaches it through
 // self.generator_model(...) / self.retriever_model(...) (dalm/models/rag_e2e_base_model.py:84-106) and differentiates it with
@@ -52,7 +52,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kTRow = 2 * 64 + 8;        // bytes of a [d][64 rows] transposed LDS row (8-byte reads stay aligned and spread)
 template <int HD>
-struct AT {                              // head width 128 (Llama-2-7b) or 64 (Falcon-7b)
+struct AT {                              // head width 128 (Llama-2-7b), 64 (Falcon-7b) or 32 (bge-small; see "Head width 32" below)
   static constexpr int LROW = 2 * HD + 16;   // bytes of a [row][HD] LDS row (16 bytes of padding: conflict-free 16-byte reads)
   static constexpr int KK = HD / 16;         // k-steps of a contraction over d
   static constexpr int ND = HD / 32;         // 32-column blocks of d
@@ -761,6 +761,158 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const AttnBwdPara
   if (p.cos) store_rows_unrope<HD, A::N64>(dlds, dk_base, p.s[6][2], j0, T, t, p.cos + cs_off(p, b, sq), p.sin + cs_off(p, b, sq), p.cs_t);
   else store_rows<HD, A::N64>(dlds, dk_base, p.s[6][2], j0, T, t);
   store_rows<HD, A::N64>(dlds + A::RM, dv_base, p.s[7][2], j0, T, t);
+}
+
+// ---- Head width 32 (bge-small / e5-small / gte-small / MiniLM class encoders: hidden 384, 12 heads) -------------------------------
+// The shapes are small: T is 50 (queries) or 128 (passages), the whole K and V of a (batch, head) pair are at most 8 KB each, a
+// contraction over d is two MFMA k-steps and O / dQ / dK / dV hold ONE f32x16 accumulator per 32 x 32 tile.  ONE form per kernel,
+// the register-staged one; DALM_ATTN_FWD / DALM_ATTN_DKDV select nothing at this width.  Reasons:
+//   - a workgroup streams one or two 64-row blocks in all, so the two-stage LDS-DMA pipeline of the second forms has nothing to
+//     overlap, and the block in flight in registers (fetch one ahead) already hides the one global round trip there is;
+//   - the images the LDS-DMA forms read cannot be padded, and their swizzle was derived for rows of 128 and 256 bytes.  A row of
+//     64 bytes is 16 banks: four consecutive rows fill the 64 banks once, so a 16-byte read of lanes <-> rows needs the chunk
+//     position to vary with r >> 2 while the transposed read (a 4-row x 64-byte patch per 16 lanes) needs it to vary with r & 3 -
+//     a fresh pattern to derive and to pin, for no step to hide.  The padded tiles here need none: a [row][32] row is LROW = 80
+//     bytes = 20 banks, a 16-byte read of row r starts at bank 20 r + 4 hi, and a ds_read_b128 is served 16 lanes at a time
+//     ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} of each half, one value of hi): 20 r mod 64 = 4 (5 r mod 16), and 5 r mod 16 is a
+//     bijection on any 16 rows that are distinct mod 16 - which both groups are - so every group touches each bank once.  The
+//     transposed copies keep kTRow = 136 bytes = 34 banks: the 8-byte reads of lanes <-> d rows start at bank 34 d + const,
+//     distinct for 32 consecutive d, two banks each: conflict-free as at the other widths.
+// Forward and dq are attn_fwd_kernel<32> / attn_bwd_dq_kernel<32> as they stand (AT<32>: KK 2, ND 1, one 16-byte chunk per wave
+// and staged row).  The dk / dv kernel cannot be: its waves split d in halves of HD / 2 >= 32 columns.  Here a workgroup owns 128
+// key rows and each wave ONE 32-row key tile and all of d (a single 32-column block), so dK / dV of a key row are summed by one
+// wave in the fixed order of the query blocks - no atomics, no partial sums - and a passage (T 128) is one workgroup per (batch,
+// head), which reads Q / dO once instead of twice.  160 VGPRs (180 with dropout), no scratch: three (two) workgroups a CU, as
+// attn_bwd_dq_kernel<32> (135 / 145); attn_fwd_kernel<32> takes 111 / 114, four a CU.  At cfg1 (B 19 x H 12 = 228 pairs against 256
+// CUs) a CU holds one workgroup anyway; bounds of four a CU made the dk / dv kernel spill (116 - 156 bytes a lane).
+template <bool DROP>
+__global__ __launch_bounds__(256, DROP ? 2 : 3) void attn_bwd_dkdv32_kernel(const AttnBwdParams p) {
+  constexpr int HD = 32;
+  using A = AT<HD>;
+  constexpr int STREAM = 2 * A::RM + 2 * A::TR + 2 * 64 * 4, OWN = 2 * 128 * A::LROW;
+  __shared__ __attribute__((aligned(16))) unsigned char lds[STREAM > OWN ? STREAM : OWN];
+  unsigned char* Qs = lds;
+  unsigned char* Gs = lds + A::RM;
+  unsigned char* QT = lds + 2 * A::RM;
+  unsigned char* GT = lds + 2 * A::RM + A::TR;
+  float* nl_s = reinterpret_cast<float*>(lds + 2 * A::RM + 2 * A::TR);
+  float* dl_s = nl_s + 64;
+  unsigned char* own2 = lds + 128 * A::LROW;                   // prologue: the workgroup's V rows; epilogue: its dV rows
+  const int t = threadIdx.x, w = t >> 6, l = t & 63, l31 = l & 31, hi = l >> 5;
+  int blk, h, b;
+  if (!block_coords(p, (p.T + 127) >> 7, false, blk, h, b)) return;
+  const int j0 = blk * 128;
+  const int j = j0 + 32 * w + l31;
+  const int64_t bh = static_cast<int64_t>(b) * p.H + h;
+  const Seq sq = seq_of(p, b);
+  const int T = sq.T;
+  unsigned short* dk_base = p.dk + base_off(p, 6, b, h, sq);
+  unsigned short* dv_base = p.dv + base_off(p, 7, b, h, sq);
+  const unsigned long long need = need_mask<2>(p, b, j0 >> 5, false, l) | need_mask<2>(p, b, (j0 >> 5) + 2, false, l);
+  if (need == 0ull) {                                          // keys nobody attends: zero gradient, nothing to read
+    store_rows<HD, A::N128>(nullptr, dk_base, p.s[6][2], j0, T, t);
+    store_rows<HD, A::N128>(nullptr, dv_base, p.s[7][2], j0, T, t);
+    return;
+  }
+  const unsigned short* qbase = p.q + base_off(p, 0, b, h, sq);
+  const unsigned short* gbase = p.d_o + base_off(p, 4, b, h, sq);
+  const int Tp = 32 * p.W;
+
+
+  bf16x8 Kb[A::KK], Vb[A::KK];
+  {
+    uint4 kv[A::N128], vv[A::N128];
+    rows_load<HD, A::N128>(p.k + base_off(p, 1, b, h, sq), p.s[1][2], j0, T, t, kv);
+    rows_load<HD, A::N128>(p.v + base_off(p, 2, b, h, sq), p.s[2][2], j0, T, t, vv);
+    rows_store<HD, A::N128>(kv, lds, t);
+    rows_store<HD, A::N128>(vv, own2, t);
+    __syncthreads();
+    rows_frags<HD>(lds, w, l31, hi, Kb);
+    rows_frags<HD>(own2, w, l31, hi, Vb);
+  }
+  const float c1 = p.scale * kLog2e;
+  f32x16 dVt[1], dKt[1];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { dVt[0][r] = 0.f; dKt[0][r] = 0.f; }
+
+  const AttnDrop drop = attn_drop(p);
+  (void)drop;
+  const int nI = (p.T + 63) >> 6;                              // (a block fetched ahead, as the dq kernel does, spills here as well)
+  for (int ib = 0; ib < nI; ++ib) {
+    if (((need >> (2 * ib)) & 3ull) == 0ull) continue;
+    uint32_t word[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+      word[c] = (j < Tp && 2 * ib + c < p.W) ? p.bits_cols[(static_cast<int64_t>(b) * Tp + j) * p.W + 2 * ib + c] : 0u;
+    uint4 qv[A::NCW], gv[A::NCW];
+    block_load<HD>(qbase, p.s[0][2], 64 * ib, T, w, l, qv);
+    block_load<HD>(gbase, p.s[4][2], 64 * ib, T, w, l, gv);
+    float nlv = 0.f, dlv = 0.f;
+    if (t < 64 && 64 * ib + t < T) {
+      nlv = -p.lse[bh * p.T + 64 * ib + t] * kLog2e;
+      dlv = p.delta[bh * p.T + 64 * ib + t];
+    }
+    __syncthreads();                                           // the previous block's (or K's and V's) fragments have been read
+    block_store<HD>(qv, Qs, QT, w, l);
+    block_store<HD>(gv, Gs, GT, w, l);
+    if (t < 64) { nl_s[t] = nlv; dl_s[t] = dlv; }
+    __syncthreads();
+#pragma unroll
+    for (int is = 0; is < 2; ++is) {
+      if (__builtin_amdgcn_ballot_w64(word[is] != 0u) == 0ull) continue;
+      f32x16 S, dP;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { S[r] = 0.f; dP[r] = 0.f; }
+      const unsigned char* qa = Qs + (32 * is + l31) * A::LROW + 16 * hi;
+      const unsigned char* ga = Gs + (32 * is + l31) * A::LROW + 16 * hi;
+#pragma unroll
+      for (int kk = 0; kk < A::KK; ++kk) {
+        S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(qa + 32 * kk), Kb[kk], S, 0, 0, 0);
+        dP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(ga + 32 * kk), Vb[kk], dP, 0, 0, 0);
+      }
+      unsigned int ppk[8], dpk[8];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float4 nl4 = *reinterpret_cast<const float4*>(nl_s + 32 * is + 8 * q + 4 * hi);
+        const float4 dl4 = *reinterpret_cast<const float4*>(dl_s + 32 * is + 8 * q + 4 * hi);
+        const float nl[4] = {nl4.x, nl4.y, nl4.z, nl4.w}, dl[4] = {dl4.x, dl4.y, dl4.z, dl4.w};
+        float pv[4], ds[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int il = 8 * q + 4 * hi + u;
+          pv[u] = ((word[is] >> il) & 1u) ? __builtin_amdgcn_exp2f(fmaf(S[4 * q + u], c1, nl[u])) : 0.f;
+          float dpe = dP[4 * q + u];
+          if constexpr (DROP) {                                  // the same element index, pair and field as at the other widths
+            const unsigned int c = (static_cast<unsigned int>(bh) * p.T + 64 * ib + 32 * is + il) * p.T + j;
+            const unsigned int hw = drop_pair(drop, c & ~1u);
+            const bool keep = ((c & 1u) ? hw >> 16 : hw & 0xffffu) >= drop.thresh;
+            dpe = keep ? dpe * drop.ks : 0.f;
+            ds[u] = pv[u] * (dpe - dl[u]);
+            pv[u] = keep ? pv[u] * drop.ks : 0.f;                // what multiplies dO in dV = (P o M / (1 - p))^T dO
+          } else {
+            ds[u] = pv[u] * (dpe - dl[u]);
+          }
+        }
+        ppk[2 * q] = pack_bf16x2(pv[0], pv[1]);
+        ppk[2 * q + 1] = pack_bf16x2(pv[2], pv[3]);
+        dpk[2 * q] = pack_bf16x2(ds[0], ds[1]);
+        dpk[2 * q + 1] = pack_bf16x2(ds[2], ds[3]);
+      }
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const bf16x8 pb = __builtin_bit_cast(bf16x8, make_uint4(ppk[4 * s], ppk[4 * s + 1], ppk[4 * s + 2], ppk[4 * s + 3]));
+        const bf16x8 db = __builtin_bit_cast(bf16x8, make_uint4(dpk[4 * s], dpk[4 * s + 1], dpk[4 * s + 2], dpk[4 * s + 3]));
+        dVt[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ld_tr_frag(GT, l31, 32 * is, s, hi), pb, dVt[0], 0, 0, 0);
+        dKt[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ld_tr_frag(QT, l31, 32 * is, s, hi), db, dKt[0], 0, 0, 0);
+      }
+    }
+  }
+  __syncthreads();
+  spill_transposed<HD, 1>(dKt, 0, p.scale, lds, w, l31, hi);
+  spill_transposed<HD, 1>(dVt, 0, 1.0f, own2, w, l31, hi);
+  __syncthreads();
+  store_rows<HD, A::N128>(lds, dk_base, p.s[6][2], j0, T, t);
+  store_rows<HD, A::N128>(own2, dv_base, p.s[7][2], j0, T, t);
 }
 
 // ---- LDS images filled by LDS-DMA (global_load_lds_dwordx4: the destination is a wave-uniform base + 16 bytes x lane, so an
@@ -1682,11 +1834,15 @@ static int dalm_attn_bwd_any(const void* q, const void* k, const void* v, const 
                          const uint32_t* bits_rows, const uint32_t* bits_cols, const uint8_t* live, const int32_t* cu, int64_t B, int64_t H,
                          int64_t Hkv, int64_t T, int64_t hd, float scale, const int64_t* strides, const void* cos, const void* sin,
                          int64_t cs_stride_b, int64_t cs_stride_t, float dropout_p, const void* seed, uint32_t salt, void* dq,
-                         void* dk, void* dv, float* delta, dalm_stream_t stream, GqaSplit split = {1, nullptr, 0}) {
+                         void* dk, void* dv, float* delta, dalm_stream_t stream, GqaSplit split = {1, nullptr, 0},
+                         bool gqa_entry = false) {
   DALM_REQUIRE(q && k && v && o && d_o && lse && bits_rows && bits_cols && live && strides && dq && dk && dv && delta, DALM_E_NULL,
                "null pointer argument");
   if (const int rc = check_heads(__func__, H, Hkv)) return rc;
-  DALM_REQUIRE(hd == 128 || hd == 64, DALM_E_SHAPE, "head width must be 64 or 128");
+  if (gqa_entry) DALM_REQUIRE(hd == 128 || hd == 64, DALM_E_SHAPE, "head width must be 64 or 128");
+  else DALM_REQUIRE(hd == 128 || hd == 64 || hd == 32, DALM_E_SHAPE, "head width must be 32, 64 or 128");
+  DALM_REQUIRE(hd != 32 || (cos == nullptr && sin == nullptr), DALM_E_SHAPE,
+               "head width 32 has no rotary epilogue: cos / sin must be NULL (rotate and un-rotate with dalm_rope_qk)");
   DALM_REQUIRE(B > 0 && H > 0 && T > 0 && T <= 2048 && B * H <= (1ll << 24), DALM_E_SHAPE, "need 0 < T <= 2048 and B H <= 2^24");
   const void* ptrs[8] = {q, k, v, o, d_o, dq, dk, dv};
   for (int i = 0; i < 8; ++i) {
@@ -1731,7 +1887,8 @@ static int dalm_attn_bwd_any(const void* q, const void* k, const void* v, const 
   for (int i = 0; i < 8; ++i)
     for (int a = 0; a < 3; ++a) p.s[i][a] = strides[3 * i + a];
   static bool lds_set = false;
-  static bool first_form = false;                              // DALM_ATTN_DKDV=1: the register-staged dk / dv kernel (A/B runs)
+  static bool first_form = false;                              // DALM_ATTN_DKDV=1: the register-staged dk / dv kernel (A/B runs;
+                                                               // head widths 64 / 128 - width 32 has one form, nothing to select)
   if (!lds_set) {
     for (const void* fn : {reinterpret_cast<const void*>(attn_bwd_dkdv_kernel<128, false>),
                            reinterpret_cast<const void*>(attn_bwd_dkdv_kernel<128, true>)})
@@ -1765,6 +1922,17 @@ static int dalm_attn_bwd_any(const void* q, const void* k, const void* v, const 
   } while (0)
     if (hd == 128) DALM_ATTN_GQA_BWD(128); else DALM_ATTN_GQA_BWD(64);
 #undef DALM_ATTN_GQA_BWD
+    return check_launch(__func__);
+  }
+  if (hd == 32) {      // one form per kernel (see "Head width 32"): a workgroup of the dk / dv kernel owns 128 key rows
+    const dim3 grid_dkdv32(static_cast<unsigned>(pairs8 * ((T + 127) / 128)));
+    if (p.seed) {
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<32, true>), grid_dq, dim3(256), 0, s, p);
+      hipLaunchKernelGGL((attn_bwd_dkdv32_kernel<true>), grid_dkdv32, dim3(256), 0, s, p);
+    } else {
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<32, false>), grid_dq, dim3(256), 0, s, p);
+      hipLaunchKernelGGL((attn_bwd_dkdv32_kernel<false>), grid_dkdv32, dim3(256), 0, s, p);
+    }
     return check_launch(__func__);
   }
 #define DALM_ATTN_BWD(HD, DROP)                                                                         \
@@ -1809,7 +1977,7 @@ extern "C" int dalm_attn_gqa_bwd(const void* q, const void* k, const void* v, co
   DALM_REQUIRE(splits >= 0, DALM_E_SHAPE, "splits must be 0 (the library's choice) or a divisor of H / Hkv");
   return dalm_attn_bwd_any(q, k, v, o, d_o, lse, bits_rows, bits_cols, live, cu_seqlens, B, H, Hkv, T, hd, scale, strides, cos, sin,
                            cu_seqlens ? 0 : cs_stride_b, cs_stride_t, 0.f, nullptr, 0u, dq, dk, dv, delta, stream,
-                           GqaSplit{splits, ws, ws_bytes});
+                           GqaSplit{splits, ws, ws_bytes}, true);
 }
 
 extern "C" int64_t dalm_attn_gqa_bwd_splits(int64_t B, int64_t H, int64_t Hkv, int64_t T) {
@@ -1825,10 +1993,11 @@ extern "C" size_t dalm_attn_gqa_bwd_workspace_bytes(int64_t rows, int64_t Hkv, i
 static int dalm_attn_fwd_any(const void* q, const void* k, const void* v, const uint32_t* bits_rows, const uint8_t* live,
                             const int32_t* cu, int64_t B, int64_t H, int64_t Hkv, int64_t T, int64_t hd, float scale,
                             const int64_t* strides, float dropout_p, const void* seed, uint32_t salt, void* o, float* lse,
-                            dalm_stream_t stream) {
+                            dalm_stream_t stream, bool gqa_entry = false) {
   DALM_REQUIRE(q && k && v && bits_rows && live && strides && o && lse, DALM_E_NULL, "null pointer argument");
   if (const int rc = check_heads(__func__, H, Hkv)) return rc;
-  DALM_REQUIRE(hd == 128 || hd == 64, DALM_E_SHAPE, "head width must be 64 or 128");
+  if (gqa_entry) DALM_REQUIRE(hd == 128 || hd == 64, DALM_E_SHAPE, "head width must be 64 or 128");
+  else DALM_REQUIRE(hd == 128 || hd == 64 || hd == 32, DALM_E_SHAPE, "head width must be 32, 64 or 128");
   DALM_REQUIRE(B > 0 && H > 0 && T > 0 && T <= 2048 && B * H <= (1ll << 24), DALM_E_SHAPE, "need 0 < T <= 2048 and B H <= 2^24");
   const void* ptrs[4] = {q, k, v, o};
   for (int i = 0; i < 4; ++i) {
@@ -1863,7 +2032,12 @@ static int dalm_attn_fwd_any(const void* q, const void* k, const void* v, const 
     else hipLaunchKernelGGL((attn_fwd2_kernel<64, false, true>), grid, dim3(256), stream2_lds<64>(), s, p);
     return check_launch(__func__);
   }
-  static const bool first_form = [] { const char* e = getenv("DALM_ATTN_FWD"); return e && e[0] == '1'; }();   // A/B runs
+  if (hd == 32) {                                              // one form (see "Head width 32"): DALM_ATTN_FWD selects nothing here
+    if (p.seed) hipLaunchKernelGGL((attn_fwd_kernel<32, true>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((attn_fwd_kernel<32, false>), grid, dim3(256), 0, s, p);
+    return check_launch(__func__);
+  }
+  static const bool first_form = [] { const char* e = getenv("DALM_ATTN_FWD"); return e && e[0] == '1'; }();   // A/B runs, widths 64 / 128
   if (first_form) {
     if (hd == 128) {
       if (p.seed) hipLaunchKernelGGL((attn_fwd_kernel<128, true>), grid, dim3(256), 0, s, p);
@@ -1899,5 +2073,5 @@ extern "C" int dalm_attn_fwd_packed(const void* q, const void* k, const void* v,
 extern "C" int dalm_attn_gqa_fwd(const void* q, const void* k, const void* v, const uint32_t* bits_rows, const uint8_t* live,
                                  const int32_t* cu_seqlens, int64_t B, int64_t H, int64_t Hkv, int64_t T, int64_t hd, float scale,
                                  const int64_t* strides, void* o, float* lse, dalm_stream_t stream) {
-  return dalm_attn_fwd_any(q, k, v, bits_rows, live, cu_seqlens, B, H, Hkv, T, hd, scale, strides, 0.f, nullptr, 0u, o, lse, stream);
+  return dalm_attn_fwd_any(q, k, v, bits_rows, live, cu_seqlens, B, H, Hkv, T, hd, scale, strides, 0.f, nullptr, 0u, o, lse, stream, true);
 }

@@ -4,7 +4,9 @@ dalm_amd/csrc/attn.hip), registered with transformers as the attention implement
 transformers evaluates a decoder layer's attention through `sdpa_attention_forward`
 (transformers/integrations/sdpa_attention.py) -> torch.nn.functional.scaled_dot_product_attention; the reference reaches it through
 `self.generator_model(...)` (dalm/models/rag_e2e_base_model.py:104-106) and differentiates it in `loss.backward()`
-(dalm/training/rag_e2e/train_rage2e.py:466).  Head widths 128 (Llama-2-7b) and 64 (Falcon-7b, through fastpath's FalconAttention patch).  With HF's boolean mask (causal + left padding) torch runs its memory-efficient
+(dalm/training/rag_e2e/train_rage2e.py:466).  Head widths 128 (Llama-2-7b), 64 (bge-large / BERT; Falcon-7b through fastpath's
+FalconAttention patch) and 32 (bge-small, e5-small, gte-small, all-MiniLM: hidden 384, 12 heads - equal heads, no fused rotary
+epilogue, no grouped heads: `rope_fusable` and `grouped_supported` decline that width).  With HF's boolean mask (causal + left padding) torch runs its memory-efficient
 kernels: 60 us forward, 440 us backward per layer at cfg3 (2.7 % of the MFMA peak).  Here
 
   forward   `dalm_attn_fwd` (one launch, online softmax, writes the rows' log-sum-exp);  DALM_ATTN_FWD_KERNEL=0: torch's own
@@ -36,7 +38,8 @@ from .fastpath import _off
 from .lora import dropout_uid
 
 NAME = "dalm_sdpa"
-_HEAD_DIMS = (64, 128)
+_HEAD_DIMS = (32, 64, 128)             # what dalm_attn_fwd / _bwd and their packed forms take
+_WIDE_HEAD_DIMS = (64, 128)            # what the rotary epilogues of dalm_attn_bwd and the grouped entry points (dalm_attn_gqa_*) take
 
 
 class _MaskPack:
@@ -277,7 +280,8 @@ def rope_fusable(q, k, cos, sin) -> bool:
     """cos / sin tables `dalm_attn_bwd` reads in its epilogues: what `tower_ops.rope_supported` takes, bf16, 16-byte rows."""
     from . import tower_ops
 
-    return (tower_ops.rope_supported(q, k, cos, sin) and cos.dtype == torch.bfloat16 and cos.shape[-1] == q.shape[-1]
+    return (q.shape[-1] in _WIDE_HEAD_DIMS                      # width 32: separate rotary kernels (tower_ops.rope_qk)
+            and tower_ops.rope_supported(q, k, cos, sin) and cos.dtype == torch.bfloat16 and cos.shape[-1] == q.shape[-1]
             and cos.stride(1) % 8 == 0 and (cos.shape[0] == 1 or cos.stride(0) % 8 == 0)
             and cos.data_ptr() % 16 == 0 and sin.data_ptr() % 16 == 0
             and k.shape[0] == q.shape[0] and k.shape[2:] == q.shape[2:] and k.shape[1] >= 1 and q.shape[1] % k.shape[1] == 0)
@@ -312,7 +316,7 @@ def supported(query, key, value, mask, dropout, causal, kwargs) -> bool:
 
 
 def packed_supported(query, key, value, dropout: float = 0.0) -> bool:
-    """What `dalm_attn_*_packed` take: [1, H, n, hd] bf16 views with 16-byte aligned rows, head width 64 / 128."""
+    """What `dalm_attn_*_packed` take: [1, H, n, hd] bf16 views with 16-byte aligned rows, head width 32 / 64 / 128."""
     if not (query.is_cuda and query.dtype == torch.bfloat16 and key.dtype == query.dtype and value.dtype == query.dtype):
         return False
     if query.dim() != 4 or query.shape[0] != 1 or query.shape[-1] not in _HEAD_DIMS or key.shape != query.shape \
@@ -333,8 +337,10 @@ def group_ok(H: int, Hkv: int) -> bool:
 
 def grouped_supported(query, key, value, mask=None, dropout: float = 0.0, causal: bool = False, kwargs=None, packed: bool = False) -> bool:
     """What `dalm_attn_gqa_*` take un-expanded: key / value with Hkv heads, 1 < Hkv < H, H % Hkv == 0, H / Hkv <= 16, no dropout,
-    and everything `supported` (`packed_supported` for a packed call) asks of equal heads."""
+    head width 64 / 128, and everything `supported` (`packed_supported` for a packed call) asks of equal heads."""
     if query.dim() != 4 or key.dim() != 4 or key.shape != value.shape or dropout != 0.0:
+        return False
+    if query.shape[-1] not in _WIDE_HEAD_DIMS:       # width 32: k / v are expanded by repeat_kv and run on the equal-heads kernels
         return False
     if not group_ok(query.shape[1], key.shape[1]):
         return False
@@ -454,7 +460,7 @@ def sdpa(query, key, value, mask, scale: float, causal: bool, dropout_p: float =
 
 
 def use_hip_attention_backward(model: torch.nn.Module) -> bool:
-    """Switch a Llama-family model (head width 64 or 128) from "sdpa" to "dalm_sdpa".  DALM_ATTN_KERNEL=0 disables."""
+    """Switch a Llama-family or BERT model (head width 32, 64 or 128) from "sdpa" to "dalm_sdpa".  DALM_ATTN_KERNEL=0 disables."""
     if _off("DALM_ATTN_KERNEL"):
         return False
     cfg = getattr(model, "config", None)

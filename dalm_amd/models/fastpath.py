@@ -608,7 +608,7 @@ def _llama_attention_forward(self, hidden_states, position_embeddings=None, atte
     if fused:
         attn_output = attention.rope_sdpa(query_states, key_states, value_states, cos, sin, attention_mask, float(self.scaling), causal)
         attn_output = attn_output.transpose(1, 2)
-    else:                                            # CPU tensors, one KV head, ...: transformers' own sequence from here on
+    else:                                            # CPU tensors, one KV head, head width 32, ...: transformers' own sequence from here on
         import importlib
 
         from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS

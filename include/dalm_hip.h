@@ -543,7 +543,7 @@ int dalm_bert_add_norm_bwd_live(const float* g32, const void* g16, const void* a
                                 const uint8_t* keep_bits, const float* mean, const float* rstd, int64_t R, int64_t D,
                                 float dropout_p, float* d_res, void* d_a, const uint8_t* row_live, dalm_stream_t stream);
 
-/* Backward of scaled-dot-product attention, bf16, head width 128, boolean mask (dalm_amd/csrc/attn.hip).  Stands in for the
+/* Backward of scaled-dot-product attention, bf16, head width hd = 32, 64 or 128, boolean mask (dalm_amd/csrc/attn.hip).  Stands in for the
  * backward of torch.nn.functional.scaled_dot_product_attention as transformers' sdpa_attention_forward calls it inside
  * self.generator_model(...) (dalm/models/rag_e2e_base_model.py:104-106; loss.backward(), train_rage2e.py:466).
  *   dalm_attn_mask_bits: mask [B, 1, T, T] bytes (non-zero = attend; element strides mask_stride_b / mask_stride_row, last
@@ -557,14 +557,18 @@ int dalm_bert_add_norm_bwd_live(const float* g32, const void* g16, const void* a
  *        must stay below 2^30 elements (the streamed blocks are addressed with 32-bit offsets from the sequence's first row).
  *        Two forms with the same arithmetic and bit-identical outputs (register-staged tiles / LDS-DMA stages + transpose reads,
  *        the default); DALM_ATTN_FWD=1 / DALM_ATTN_DKDV=1 select the first, read once per process (tools/attn_ab.py).
+ *        hd = 32 (bge-small class encoders) has ONE form per kernel, the switches select nothing there.
  *        cos / sin (NULL, or [B or 1, T, hd] bf16 with element strides cs_stride_b (0 for one table) / cs_stride_t): q and k
  *        are the outputs of dalm_rope_qk and dq / dk leave as the gradients of its INPUTS - that kernel's backward applied
- *        in the epilogue, same rounding points.
+ *        in the epilogue, same rounding points.  hd = 64 or 128 only: DALM_E_SHAPE for hd = 32 with cos / sin (no rotary
+ *        epilogue at that width; rotate and un-rotate with dalm_rope_qk).
  *   dropout_p > 0 (BERT's attention_probs_dropout_prob; T even): P o M / (1 - p) in front of P V, the keep mask M regenerated in
  *        every kernel from (the 64-bit word at `seed` in DEVICE memory, salt, element index ((b H + h) T + i) T + j) - never
  *        stored; pass the same three values to dalm_attn_fwd and dalm_attn_bwd.  oracle/attn_dropout.py restates the mask. */
 /*   dalm_attn_fwd: o = softmax(scale q k^T + mask) v and lse [B, H, T] f32 (natural log; 0 for rows without a live key, whose
- *        output is 0).  strides: 4 x (batch, head, row) element strides of q, k, v, o. */
+ *        output is 0).  strides: 4 x (batch, head, row) element strides of q, k, v, o.  hd = 32, 64 or 128.
+ *   Widths: dalm_attn_fwd and dalm_attn_bwd take hd = 32, 64 and 128 (dalm_attn_bwd with cos / sin: 64 and 128); every other
+ *        width is DALM_E_SHAPE. */
 int dalm_attn_fwd(const void* q, const void* k, const void* v, const uint32_t* bits_rows, const uint8_t* live, int64_t B, int64_t H,
                   int64_t T, int64_t hd, float scale, const int64_t* strides, float dropout_p, const void* seed, uint32_t salt,
                   void* o, float* lse, dalm_stream_t stream);
@@ -585,7 +589,9 @@ int dalm_attn_bwd(const void* q, const void* k, const void* v, const void* o, co
  * mask words [B][32 W][W] as above, built by
  *   dalm_attn_mask_bits_packed: key_live [n_tokens] bytes (NULL = all live; 0 = a token that only queries, e.g. the padding
  *        position in front of a left-padded sequence whose row predicts the first real token), causal flag: element (i, j) of
- *        sequence b is live when token j is a live key and (causal) j <= i - what the padded mask says about the same tokens. */
+ *        sequence b is live when token j is a live key and (causal) j <= i - what the padded mask says about the same tokens.
+ * Widths: dalm_attn_fwd_packed and dalm_attn_bwd_packed take hd = 32, 64 and 128 (dalm_attn_bwd_packed with cos / sin: 64 and
+ * 128), as the padded entry points. */
 int dalm_attn_mask_bits_packed(const uint8_t* key_live, const int32_t* cu_seqlens, int64_t B, int64_t T, int causal,
                                uint32_t* bits_rows, uint32_t* bits_cols, uint8_t* live, dalm_stream_t stream);
 int dalm_attn_fwd_packed(const void* q, const void* k, const void* v, const uint32_t* bits_rows, const uint8_t* live,
@@ -606,7 +612,8 @@ int dalm_attn_bwd_packed(const void* q, const void* k, const void* v, const void
  * atomics; with cos / sin the rotation's backward is applied to the f32 sum of dk in front of that one rounding).
  * cu_seqlens NULL = the padded [B, heads, T, hd] layout, otherwise the packed one above (cs_stride_b is ignored).
  * lse / delta stay [B, H, T]; no dropout.  Hkv == H computes what dalm_attn_fwd / dalm_attn_bwd (or their packed forms) compute.
- * DALM_E_SHAPE unless Hkv >= 1 and H % Hkv == 0; every other limit as above.
+ * DALM_E_SHAPE unless Hkv >= 1 and H % Hkv == 0; hd = 64 or 128 only (hd = 32 is DALM_E_SHAPE here, also with Hkv == H); every other
+ * limit as above.
  * dk / dv launch: one workgroup per (64 key rows, KV head, batch) runs through its whole group.  Where that grid under-fills the
  * machine (fewer than 512 workgroups) the group's heads are SPLIT over `splits` workgroups, each leaves scaled f32 partials in
  * the caller's workspace and a combine kernel adds them in a fixed order, un-rotates and rounds once (no atomics).

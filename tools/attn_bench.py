@@ -3,7 +3,13 @@ against torch's memory-efficient backward, hipGraph replay timing.  -> stdout (p
 
 --kv-heads N (grouped-query attention, N < H key / value heads): `dalm_attn_gqa_*` on the un-expanded k / v against the EXPANDED
 path - repeat_kv copies + the equal-heads kernels + autograd's sum of the per-head dk / dv - forward and backward, padded (causal +
-left padding) and packed layouts, alternated in one process.  -> stdout (profiles/attn_gqa_bench.txt)"""
+left padding) and packed layouts, alternated in one process.  -> stdout (profiles/attn_gqa_bench.txt)
+
+--encoder (a BERT-class retriever layer: bidirectional mask with RIGHT padding, sequence lengths uniform in --len-range, optional
+--dropout p): `dalm_attn_fwd` / `dalm_attn_bwd` against torch's SDPA on the same tensors and mask (what a model on "sdpa" runs),
+and the packed forms (`dalm_attn_*_packed` on the live rows) against `_packed_sdpa_torch` (re-pad, torch's SDPA, gather).  The two
+paths alternate --rounds times in one process; every figure is the median over rounds x 20 separately timed hipGraph replays
+(HIP events, --iters calls per graph, after warm-up replays).  -> stdout (profiles/attn_hd32_bench.txt, with --hd 32)"""
 import argparse
 import sys
 from pathlib import Path
@@ -19,9 +25,12 @@ ap.add_argument("--H", type=int, default=32)
 ap.add_argument("--T", type=int, default=256)
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--lens", default="random", help="random (T/2..T) | full | <n> (every sequence n tokens, left-padded)")
-ap.add_argument("--hd", type=int, default=128, choices=(64, 128))
+ap.add_argument("--hd", type=int, default=128, choices=(32, 64, 128))
 ap.add_argument("--kv-heads", type=int, default=0, help="grouped-query heads: time dalm_attn_gqa_* against the expanded path")
 ap.add_argument("--rounds", type=int, default=3, help="--kv-heads: alternations of the two paths (median, min .. max reported)")
+ap.add_argument("--encoder", action="store_true", help="encoder layer: bidirectional right-padding mask, padded and packed forms")
+ap.add_argument("--len-range", default="", help="--encoder: LO,HI - sequence lengths uniform in [LO, HI] (default T/2,T)")
+ap.add_argument("--dropout", type=float, default=0.0, help="--encoder: attention dropout probability (in-kernel / torch's own)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 B, H, T, hd = a.B, a.H, a.T, a.hd
@@ -148,8 +157,87 @@ def grouped_bench(Hkv):
     return results
 
 
+def replay_samples(fn, qkv, d_out, backward, reps=20):
+    """`--iters` calls of `fn` (its forward, or the backward of one forward) captured into one hipGraph; 3 warm-up replays, then
+    `reps` replays timed one by one with HIP events: us per call of each."""
+    qq, kk, vv = [t.detach().clone().requires_grad_(True) for t in qkv]
+    s = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        o = fn(qq, kk, vv)
+        for _ in range(3):
+            if backward:
+                torch.autograd.grad(o, (qq, kk, vv), d_out, retain_graph=True)
+            else:
+                fn(qq, kk, vv)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr, stream=s):
+            for _ in range(a.iters):
+                if backward:
+                    torch.autograd.grad(o, (qq, kk, vv), d_out, retain_graph=True)
+                else:
+                    fn(qq, kk, vv)
+    for _ in range(3):
+        gr.replay()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        gr.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1) * 1e3 / a.iters)
+    return out
+
+
+def encoder_bench():
+    from dalm_amd import packed
+
+    p = a.dropout
+    lo, hi = [int(x) for x in a.len_range.split(",")] if a.len_range else (T // 2, T)
+    ln = torch.randint(lo, hi + 1, (B,), generator=g)
+    am = (torch.arange(T)[None, :] < ln[:, None]).long()
+    m4 = am.bool().to(dev)[:, None, None, :].expand(B, 1, T, T)                      # HF's bidirectional padding mask
+    rows, cu = packed.pack_plan(am, shifted=False, multiple=packed.PACK_MULTIPLE)
+    _ids, _pos, desc, _valid = packed.packed_inputs(torch.zeros(B, T, dtype=torch.long, device=dev), am.to(dev), rows.to(dev), cu.to(dev), False)
+    seqs = packed.packed_of(desc)
+    n = rows.numel()
+    pad_qkv = (q, k, v)
+    pk_qkv = [torch.randn(1, n, H, hd, generator=g).bfloat16().to(dev).transpose(1, 2) for _ in range(3)]
+    pk_go = torch.randn(1, n, H, hd, generator=g).bfloat16().to(dev).transpose(1, 2)
+    assert attention.supported(q.detach().requires_grad_(True), k, v, m4, p, False, {}), "the padded kernels do not take this call"
+    assert attention.packed_supported(*pk_qkv, p), "the packed kernels do not take this call"
+    F = torch.nn.functional
+    paths = {
+        "padded": (pad_qkv, go, {"kernels": lambda x, y, z: attention.sdpa(x, y, z, m4, scale, False, p, 7),
+                                 "torch": lambda x, y, z: F.scaled_dot_product_attention(x, y, z, attn_mask=m4, dropout_p=p, scale=scale)}),
+        "packed": (pk_qkv, pk_go, {"kernels": lambda x, y, z: attention.sdpa(x, y, z, desc, scale, False, p, 7),
+                                   "torch": lambda x, y, z: attention._packed_sdpa_torch(x, y, z, seqs, scale, p).transpose(1, 2)}),
+    }
+    print(f"# encoder layer: B {B} H {H} T {T} hd {hd} dropout {p}; lengths U[{lo}, {hi}]: {int(ln.sum())} live tokens of {B * T}, "
+          f"{n} packed rows; median of {a.rounds} x 20 hipGraph replays ({a.iters} calls each) in us per call (min .. max)")
+    for layout, (qkv, d_out, fns) in paths.items():
+        t = {(w, pas): [] for w in fns for pas in ("fwd", "bwd")}
+        for _ in range(a.rounds):
+            for pas in ("fwd", "bwd"):
+                for w, fn in fns.items():                                            # the two paths alternate
+                    t[(w, pas)] += replay_samples(fn, qkv, d_out, pas == "bwd")
+        med = {key: sorted(x)[len(x) // 2] for key, x in t.items()}
+        tot = {w: med[(w, "fwd")] + med[(w, "bwd")] for w in fns}
+        print(f"hd {hd} B {B:3d} T {T:3d} p {p:.1f} {layout:6s}  "
+              + "  ".join(f"{pas} kernels {med[('kernels', pas)]:6.1f} ({min(t[('kernels', pas)]):.1f} .. {max(t[('kernels', pas)]):.1f}) "
+                          f"torch {med[('torch', pas)]:6.1f} ({min(t[('torch', pas)]):.1f} .. {max(t[('torch', pas)]):.1f})"
+                          for pas in ("fwd", "bwd"))
+              + f"  fwd+bwd kernels {tot['kernels']:6.1f} torch {tot['torch']:6.1f}  torch / kernels {tot['torch'] / tot['kernels']:.2f}x")
+
+
 if a.kv_heads:
     grouped_bench(a.kv_heads)
+    sys.exit(0)
+if a.encoder:
+    encoder_bench()
     sys.exit(0)
 
 
