@@ -20,6 +20,12 @@
 //   * colacc finishes in the launch (the last workgroup of a column slab to arrive adds the row splits in fixed order).
 // Algorithmic bytes ([R, C] bf16 activation): rowdot R*C*2 (+ R*C/8 per mask written), rankupd 2*R*C*2 (+ R*C/8 per mask read),
 // colacc R*C*2 (+ R*C/8 per mask read).
+// Row stride (the `_ld` entry points): `ld` is the distance, in elements, between two rows of the bf16 ACTIVATION operand (x0 / x1
+// of rowdot and colacc, y0 / y1 of rankupd; in mode 3 both share it), so that the operand may be a column slice [0, C) of a wider
+// row-major buffer (q | k | v as the output of one GEMM).  ld >= C, ld % 8 == 0, 16-byte-aligned bases.  Columns outside [0, C) of
+// a row are never read or written.  z, the weights, the mask bits, the workspace and the outputs stay dense, and the dropout
+// mask stays a function of the LOGICAL element index row * C + c: a slice draws the mask its contiguous copy would draw.  The
+// entry points without `_ld` pass ld = C.
 #include "lora_common.hpp"
 
 namespace dalm {
@@ -87,7 +93,7 @@ __global__ __launch_bounds__(256) void lora2_rowdot_kernel(
     const bf16_t* __restrict__ x0, const bf16_t* __restrict__ x1, const float* __restrict__ W0, const float* __restrict__ W1,
     float* __restrict__ out0, float* __restrict__ out1, unsigned char* __restrict__ bits0, unsigned char* __restrict__ bits1,
     const unsigned long long* __restrict__ seed, unsigned int salt0, unsigned int salt1, unsigned int thr16, int R, int K,
-    int rank, float scale, const unsigned char* __restrict__ live) {
+    int rank, float scale, const unsigned char* __restrict__ live, int ld /* row stride of x0 / x1, elements */) {
   __shared__ float red[4][16][17];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -101,7 +107,7 @@ __global__ __launch_bounds__(256) void lora2_rowdot_kernel(
   // a tile without a live row (the same rows in all four waves: workgroup-uniform) skips the K loop
   const bool lv = !live || live[rowc];
   const bool any_live = __builtin_amdgcn_ballot_w64(lv) != 0ull;
-  const bf16_t* xr = ((MODE == 3 && prob) ? x1 : x0) + static_cast<int64_t>(rowc) * K + kg * 8;
+  const bf16_t* xr = ((MODE == 3 && prob) ? x1 : x0) + static_cast<int64_t>(rowc) * ld + kg * 8;
   const bool wv = li < rank;                                  // this lane's B-operand column is a real rank index
   const float* wr = (lp ? W1 : W0) + static_cast<int64_t>(min(li, rank - 1)) * K + kg * 8;
   DropKey key{0u, 1u};
@@ -206,7 +212,8 @@ template <int RANK, int NT, bool BITS, bool TWO_Y, bool STAGE>
 __global__ __launch_bounds__(256) void lora2_rankupd_kernel(
     bf16_t* __restrict__ y0, bf16_t* __restrict__ y1, const float* __restrict__ z0, const float* __restrict__ z1,
     const float* __restrict__ W0, const float* __restrict__ W1, const unsigned char* __restrict__ bits0,
-    const unsigned char* __restrict__ bits1, int R, int C, int rows_per_wg, float scale, const unsigned char* __restrict__ live) {
+    const unsigned char* __restrict__ bits1, int R, int C, int rows_per_wg, float scale, const unsigned char* __restrict__ live,
+    int ld /* row stride of y0 / y1, elements; columns >= C of a row are a sibling's */) {
   static_assert(!(TWO_Y && NT == 2), "two problems carry one term each");
   constexpr int UN = NT == 2 ? 3 : 4;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -254,13 +261,13 @@ __global__ __launch_bounds__(256) void lora2_rankupd_kernel(
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
       const int row = min(b0 + 4 * u, R - 1);
-      const bool ld = valid && b0 + 4 * u < r_hi && row_live(b0 + 4 * u);
-      raw[u] = ld ? *reinterpret_cast<const uint4*>(y + static_cast<int64_t>(row) * C + c0) : make_uint4(0u, 0u, 0u, 0u);
+      const bool ok = valid && b0 + 4 * u < r_hi && row_live(b0 + 4 * u);
+      raw[u] = ok ? *reinterpret_cast<const uint4*>(y + static_cast<int64_t>(row) * ld + c0) : make_uint4(0u, 0u, 0u, 0u);
       if constexpr (BITS) {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
           if constexpr (STAGE) by[t][u] = sbits[(t * rows_per_wg + min(b0 + 4 * u, r_hi - 1) - r_lo) * 64 + lane];
-          else by[t][u] = ld ? bt[t][static_cast<int64_t>(row) * bpr + cb] : 0u;
+          else by[t][u] = ok ? bt[t][static_cast<int64_t>(row) * bpr + cb] : 0u;
         }
       }
     }
@@ -294,7 +301,7 @@ __global__ __launch_bounds__(256) void lora2_rankupd_kernel(
           else yv[e] = upd;
         }
       }
-      if (valid) Chunk8<bf16_t>::store(y + static_cast<int64_t>(row) * C + c0, yv);
+      if (valid) Chunk8<bf16_t>::store(y + static_cast<int64_t>(row) * ld + c0, yv);
     }
   };
 
@@ -353,7 +360,8 @@ __global__ __launch_bounds__(256, 2) void lora2_colacc_kernel(
     float* __restrict__ out1, unsigned long long* __restrict__ part /* [2][S][C * RANK / 2] pairs of floats */,
     unsigned int* __restrict__ tickets /* [slabs * (TWO_X ? 2 : 1)], zero on entry, left zero */, int R, int C,
     int rows_per_split, int S, float scale, int bits_off /* bytes: where the mask stage starts in LDS */,
-    const unsigned char* __restrict__ live, int live_off /* bytes: where the split's liveness bytes are staged in LDS */) {
+    const unsigned char* __restrict__ live, int live_off /* bytes: where the split's liveness bytes are staged in LDS */,
+    int ld /* row stride of x0 / x1, elements */) {
   static_assert(!(TWO_X && NT == 2), "two problems carry one term each");
   constexpr int UN = (NT * RANK > 8) ? 2 : 4;                      // rows in flight per thread and buffer (the sums take NT*8*RANK registers)
   extern __shared__ __attribute__((aligned(16))) float smem[];   // z stage [NT][rows_per_split][RANK], later red[4][8][NT*8*RANK]
@@ -415,7 +423,7 @@ __global__ __launch_bounds__(256, 2) void lora2_colacc_kernel(
       any = any || rl_ok;
       const bool ok = valid && rl_ok;
       const int rr = min(row, R - 1);
-      raw[u] = ok ? *reinterpret_cast<const uint4*>(x + static_cast<int64_t>(rr) * C + c0) : make_uint4(0u, 0u, 0u, 0u);
+      raw[u] = ok ? *reinterpret_cast<const uint4*>(x + static_cast<int64_t>(rr) * ld + c0) : make_uint4(0u, 0u, 0u, 0u);
       if constexpr (BITS) {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
@@ -571,11 +579,16 @@ using namespace dalm;
   DALM_REQUIRE(mode >= 1 && mode <= 3, DALM_E_SHAPE, "mode must be 1 (one problem), 2 (two terms, shared activation) or 3 (two problems)"); \
   DALM_REQUIRE(mode != 2 || (rank) == 8, DALM_E_SHAPE, "stacked projections need rank 8")
 
-extern "C" int dalm_lora2_rowdot_live(const void* x0, const void* x1, const float* W0, const float* W1, float* out0, float* out1,
+#define DALM_LORA2_LD(ld, C)                                                                                           \
+  DALM_REQUIRE((ld) >= (C) && (ld) % 8 == 0 && (ld) <= 0x7fffffffll, DALM_E_SHAPE,                                     \
+               "the activation's row stride must be a multiple of 8 elements, at least the column count")
+
+extern "C" int dalm_lora2_rowdot_ld(const void* x0, const void* x1, const float* W0, const float* W1, float* out0, float* out1,
                                       void* bits0, void* bits1, int64_t R, int64_t K, int rank, float scale, float p,
                                       const void* seed, uint32_t salt0, uint32_t salt1, int mode, const uint8_t* row_live,
-                                      dalm_stream_t stream) {
+                                      int64_t ld, dalm_stream_t stream) {
   DALM_LORA2_SHAPE(R, K, rank);
+  DALM_LORA2_LD(ld, K);
   DALM_REQUIRE(K % 32 == 0, DALM_E_SHAPE, "the contraction length must be a multiple of 32");
   DALM_REQUIRE(p >= 0.f && p < 1.f, DALM_E_SHAPE, "dropout probability must be in [0, 1)");
   const bool two = mode != 1;
@@ -596,12 +609,19 @@ extern "C" int dalm_lora2_rowdot_live(const void* x0, const void* x1, const floa
   hipStream_t s = as_stream(stream);
   const unsigned tiles16 = static_cast<unsigned>((R + 15) / 16), tiles8 = static_cast<unsigned>((R + 7) / 8);
 #define DALM_RD2(MODE, DR, GRID) hipLaunchKernelGGL((lora2_rowdot_kernel<MODE, DR>), GRID, dim3(256), 0, s, xa0, xa1, W0, Wa1, \
-    out0, oa1, ba0, ba1, sd, salt0, salt1, thr16, Ri, Ki, rank, scale, row_live)
+    out0, oa1, ba0, ba1, sd, salt0, salt1, thr16, Ri, Ki, rank, scale, row_live, static_cast<int>(ld))
   if (mode == 1) { if (drop) DALM_RD2(1, true, dim3(tiles16)); else DALM_RD2(1, false, dim3(tiles16)); }
   else if (mode == 2) { if (drop) DALM_RD2(2, true, dim3(tiles8)); else DALM_RD2(2, false, dim3(tiles8)); }
   else { if (drop) DALM_RD2(3, true, dim3(tiles16, 2)); else DALM_RD2(3, false, dim3(tiles16, 2)); }
 #undef DALM_RD2
   return check_launch(__func__);
+}
+
+extern "C" int dalm_lora2_rowdot_live(const void* x0, const void* x1, const float* W0, const float* W1, float* out0, float* out1,
+                                      void* bits0, void* bits1, int64_t R, int64_t K, int rank, float scale, float p,
+                                      const void* seed, uint32_t salt0, uint32_t salt1, int mode, const uint8_t* row_live,
+                                      dalm_stream_t stream) {
+  return dalm_lora2_rowdot_ld(x0, x1, W0, W1, out0, out1, bits0, bits1, R, K, rank, scale, p, seed, salt0, salt1, mode, row_live, K, stream);
 }
 
 extern "C" int dalm_lora2_rowdot(const void* x0, const void* x1, const float* W0, const float* W1, float* out0, float* out1,
@@ -610,10 +630,11 @@ extern "C" int dalm_lora2_rowdot(const void* x0, const void* x1, const float* W0
   return dalm_lora2_rowdot_live(x0, x1, W0, W1, out0, out1, bits0, bits1, R, K, rank, scale, p, seed, salt0, salt1, mode, nullptr, stream);
 }
 
-extern "C" int dalm_lora2_rankupd_live(void* y0, void* y1, const float* z0, const float* z1, const float* W0, const float* W1,
-                                       const void* bits0, const void* bits1, int64_t R, int64_t C, int rank, float scale, int mode,
-                                       const uint8_t* row_live, dalm_stream_t stream) {
+extern "C" int dalm_lora2_rankupd_ld(void* y0, void* y1, const float* z0, const float* z1, const float* W0, const float* W1,
+                                     const void* bits0, const void* bits1, int64_t R, int64_t C, int rank, float scale, int mode,
+                                     const uint8_t* row_live, int64_t ld, dalm_stream_t stream) {
   DALM_LORA2_SHAPE(R, C, rank);
+  DALM_LORA2_LD(ld, C);
   const bool two = mode != 1;
   DALM_REQUIRE(y0 && z0 && W0 && (!two || (z1 && W1)) && (mode != 3 || y1), DALM_E_NULL, "null pointer argument");
   DALM_REQUIRE(aligned16(y0, W0) && (!two || aligned16(W1)) && (mode != 3 || aligned16(y1)), DALM_E_ALIGN, "y / W must be 16-byte aligned");
@@ -643,7 +664,7 @@ extern "C" int dalm_lora2_rankupd_live(void* y0, void* y1, const float* z0, cons
   const bool stage = bits && C % 128 == 0;
   const size_t lds = stage ? static_cast<size_t>(mode == 2 ? 2 : 1) * rows_per_wg * 64 : 0;
 #define DALM_RU2(RK, NT, BT, TY, ST) hipLaunchKernelGGL((lora2_rankupd_kernel<RK, NT, BT, TY, ST>), grid, dim3(256), lds, s, ya0, ya1, \
-    z0, za1, W0, Wa1, ba0, ba1, Ri, Ci, rows_per_wg, scale, row_live)
+    z0, za1, W0, Wa1, ba0, ba1, Ri, Ci, rows_per_wg, scale, row_live, static_cast<int>(ld))
 #define DALM_RU2_B(RK, NT, TY) do { if (stage) DALM_RU2(RK, NT, true, TY, true); else if (bits) DALM_RU2(RK, NT, true, TY, false); \
                                     else DALM_RU2(RK, NT, false, TY, false); } while (0)
   if (mode == 2) DALM_RU2_B(8, 2, false);
@@ -652,6 +673,12 @@ extern "C" int dalm_lora2_rankupd_live(void* y0, void* y1, const float* z0, cons
 #undef DALM_RU2_B
 #undef DALM_RU2
   return check_launch(__func__);
+}
+
+extern "C" int dalm_lora2_rankupd_live(void* y0, void* y1, const float* z0, const float* z1, const float* W0, const float* W1,
+                                       const void* bits0, const void* bits1, int64_t R, int64_t C, int rank, float scale, int mode,
+                                       const uint8_t* row_live, dalm_stream_t stream) {
+  return dalm_lora2_rankupd_ld(y0, y1, z0, z1, W0, W1, bits0, bits1, R, C, rank, scale, mode, row_live, C, stream);
 }
 
 extern "C" int dalm_lora2_rankupd(void* y0, void* y1, const float* z0, const float* z1, const float* W0, const float* W1,
@@ -670,11 +697,12 @@ extern "C" size_t dalm_lora2_colacc_ticket_words(int64_t C, int mode) {
   return static_cast<size_t>((C + 63) / 64) * (mode == 3 ? 2 : 1);
 }
 
-extern "C" int dalm_lora2_colacc_live(const void* x0, const void* x1, const float* z0, const float* z1, const void* bits0,
-                                      const void* bits1, float* out0, float* out1, int64_t R, int64_t C, int rank, float scale,
-                                      int mode, void* ws, size_t ws_bytes, uint32_t* tickets, const uint8_t* row_live,
-                                      dalm_stream_t stream) {
+extern "C" int dalm_lora2_colacc_ld(const void* x0, const void* x1, const float* z0, const float* z1, const void* bits0,
+                                    const void* bits1, float* out0, float* out1, int64_t R, int64_t C, int rank, float scale,
+                                    int mode, void* ws, size_t ws_bytes, uint32_t* tickets, const uint8_t* row_live, int64_t ld,
+                                    dalm_stream_t stream) {
   DALM_LORA2_SHAPE(R, C, rank);
+  DALM_LORA2_LD(ld, C);
   const bool two = mode != 1;
   DALM_REQUIRE(x0 && z0 && out0 && ws && tickets && (!two || (z1 && out1)) && (mode != 3 || x1), DALM_E_NULL, "null pointer argument");
   DALM_REQUIRE(aligned16(x0, z0) && (!two || aligned16(z1)) && (mode != 3 || aligned16(x1)) && (reinterpret_cast<uintptr_t>(ws) & 7) == 0,
@@ -696,7 +724,7 @@ extern "C" int dalm_lora2_colacc_live(const void* x0, const void* x1, const floa
   hipStream_t s = as_stream(stream);
   const bool stage = bits && C % 64 == 0;
 #define DALM_CA2(RK, NT, BT, TX, ST) hipLaunchKernelGGL((lora2_colacc_kernel<RK, NT, BT, TX, ST>), grid, dim3(256), g.lds, s, xa0, xa1, \
-    z0, za1, ba0, ba1, out0, oa1, part, tickets, Ri, Ci, g.rows_per_split, g.S, scale, g.bits_off, row_live, g.live_off)
+    z0, za1, ba0, ba1, out0, oa1, part, tickets, Ri, Ci, g.rows_per_split, g.S, scale, g.bits_off, row_live, g.live_off, static_cast<int>(ld))
 #define DALM_CA2_B(RK, NT, TX) do { if (stage) DALM_CA2(RK, NT, true, TX, true); else if (bits) DALM_CA2(RK, NT, true, TX, false); \
                                     else DALM_CA2(RK, NT, false, TX, false); } while (0)
   if (mode == 2) DALM_CA2_B(8, 2, false);
@@ -705,6 +733,13 @@ extern "C" int dalm_lora2_colacc_live(const void* x0, const void* x1, const floa
 #undef DALM_CA2_B
 #undef DALM_CA2
   return check_launch(__func__);
+}
+
+extern "C" int dalm_lora2_colacc_live(const void* x0, const void* x1, const float* z0, const float* z1, const void* bits0,
+                                      const void* bits1, float* out0, float* out1, int64_t R, int64_t C, int rank, float scale,
+                                      int mode, void* ws, size_t ws_bytes, uint32_t* tickets, const uint8_t* row_live,
+                                      dalm_stream_t stream) {
+  return dalm_lora2_colacc_ld(x0, x1, z0, z1, bits0, bits1, out0, out1, R, C, rank, scale, mode, ws, ws_bytes, tickets, row_live, C, stream);
 }
 
 extern "C" int dalm_lora2_colacc(const void* x0, const void* x1, const float* z0, const float* z1, const void* bits0,

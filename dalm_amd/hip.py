@@ -152,6 +152,12 @@ SIGNATURES = {
                                       C.c_uint32, _int, _vp, _vp]),
     "dalm_lora2_rankupd_live": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _f32, _int, _vp, _vp]),
     "dalm_lora2_colacc_live": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _f32, _int, _vp, _sz, _vp, _vp, _vp]),
+    # the same with a row stride `ld` (elements) for the bf16 activation operand, in front of the stream
+    "dalm_lora2_rowdot_ld": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _f32, _f32, _vp, C.c_uint32,
+                                    C.c_uint32, _int, _vp, _i64, _vp]),
+    "dalm_lora2_rankupd_ld": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _f32, _int, _vp, _i64, _vp]),
+    "dalm_lora2_colacc_ld": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _f32, _int, _vp, _sz, _vp, _vp, _i64,
+                                    _vp]),
 }
 
 

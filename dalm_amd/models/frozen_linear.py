@@ -141,59 +141,110 @@ class _FrozenPairFn(torch.autograd.Function):
 _CAT = True            # tests clear it to build their two-GEMM reference
 
 
-def _cat_weights(m0: torch.nn.Linear, m1: torch.nn.Linear) -> Optional[torch.Tensor]:
-    """[W0; W1] as ONE contiguous [N0 + N1, K] tensor that the two modules' weights are VIEWS of (no second copy of the weights:
-    the parameters are re-pointed at the halves, state_dict keys and values unchanged).  Made on first use; re-made when a
-    parameter was replaced or moved (its storage is then no longer the cat's).  None when the pair cannot share (devices,
-    dtypes, trainable, not on a GPU).
+def _cat_weights(*mods: torch.nn.Linear) -> Optional[torch.Tensor]:
+    """[W0; W1; ...] as ONE contiguous [N0 + N1 + ..., K] tensor that the modules' weights are VIEWS of (no second copy of the
+    weights: the parameters are re-pointed at the row blocks, state_dict keys and values unchanged).  Two members for gate | up,
+    three for q | k | v; the N may differ (grouped-query k / v).  Made on first use; re-made when a parameter was replaced or moved
+    (its storage is then no longer the cat's).  None when the members cannot share (devices, dtypes, K, trainable, not on a GPU).
 
-    Why: hipBLASLt runs the [rows, K] x [K, N] projections on 256 x 256 tiles; one GEMM over 2 N columns fills the last wave of
-    tiles better than two over N (measured, tools/gemm_concat_probe.py: gate | up forward 672 -> 621 us at 4608 rows,
-    493 -> 425 us at 2944 packed rows; q | k | v 408 -> 355 us at 4608 rows)."""
-    w0, w1 = m0.weight, m1.weight
-    if not _CAT or w0.requires_grad or w1.requires_grad or not w0.is_cuda or w0.device != w1.device or w0.dtype != w1.dtype \
-            or w0.dim() != 2 or w1.dim() != 2 or w0.shape[1] != w1.shape[1]:
+    Why: hipBLASLt runs the [rows, K] x [K, N] projections on 256 x 256 tiles; one GEMM over the summed columns fills the last
+    wave of tiles better than one GEMM per member (measured, tools/gemm_concat_probe.py: gate | up forward 672 -> 621 us at 4608
+    rows, 493 -> 425 us at 2944 packed rows; q | k | v 408 -> 355 us at 4608 rows)."""
+    ws = [m.weight for m in mods]
+    w0 = ws[0]
+    if not _CAT or len(ws) < 2 or not w0.is_cuda or w0.dim() != 2:
         return None
-    cat = getattr(m0, "_dalm_cat", None)
-    n0, el = w0.shape[0], w0.element_size()
-    if cat is not None and cat.dtype == w0.dtype and cat.shape[0] == n0 + w1.shape[0] and w0.data_ptr() == cat.data_ptr() \
-            and w1.data_ptr() == cat.data_ptr() + n0 * w0.shape[1] * el and w0.is_contiguous() and w1.is_contiguous():
-        return cat
+    for w in ws:
+        if w.requires_grad or w.device != w0.device or w.dtype != w0.dtype or w.dim() != 2 or w.shape[1] != w0.shape[1]:
+            return None
+    cat = getattr(mods[0], "_dalm_cat", None)
+    el, K = w0.element_size(), w0.shape[1]
+    if cat is not None and cat.dtype == w0.dtype and cat.shape == (sum(w.shape[0] for w in ws), K):
+        off, ok = cat.data_ptr(), True
+        for w in ws:
+            ok = ok and w.data_ptr() == off and w.is_contiguous()
+            off += w.shape[0] * K * el
+        if ok:
+            return cat
     if torch.cuda.is_current_stream_capturing():
         return None                            # never re-point parameters inside a hipGraph capture
     with torch.no_grad():
-        cat = torch.cat((w0.detach(), w1.detach()), dim=0)
+        cat = torch.cat([w.detach() for w in ws], dim=0)
         torch.cuda.current_stream(w0.device).synchronize()      # other streams may run these modules next (see dgrad_weight)
-        w0.data = cat[:n0]
-        w1.data = cat[n0:]
-    for w in (w0, w1):                         # transposed dgrad copies made from the old storage are still VALUES-correct, but
+        n0 = 0
+        for w in ws:
+            w.data = cat[n0:n0 + w.shape[0]]
+            n0 += w.shape[0]
+    for w in ws:                               # transposed dgrad copies made from the old storage are still VALUES-correct, but
         drop_dgrad_copy(w)                     # keyed by pointer: drop them, they are rebuilt on the next backward
     try:
-        m0._dalm_cat = cat
+        mods[0]._dalm_cat = cat
+    except Exception:
+        return None
+    return cat
+
+
+def _cat_biases(*mods: torch.nn.Linear) -> Optional[torch.Tensor]:
+    """[b0; b1; ...] as ONE [N0 + N1 + ...] vector the modules' (frozen) biases are views of: the bias of the one GEMM over
+    `_cat_weights(*mods)`.  Same rules as there; None when a member has no bias or the biases cannot share."""
+    bs = [m.bias for m in mods]
+    if not _CAT or any(b is None for b in bs):
+        return None
+    b0 = bs[0]
+    for b in bs:
+        if b.requires_grad or not b.is_cuda or b.device != b0.device or b.dtype != b0.dtype or b.dim() != 1:
+            return None
+    cat = getattr(mods[0], "_dalm_cat_bias", None)
+    if cat is not None and cat.dtype == b0.dtype and cat.numel() == sum(b.numel() for b in bs):
+        off, ok = cat.data_ptr(), True
+        for b in bs:
+            ok = ok and b.data_ptr() == off and b.is_contiguous()
+            off += b.numel() * b.element_size()
+        if ok:
+            return cat
+    if torch.cuda.is_current_stream_capturing():
+        return None
+    with torch.no_grad():
+        cat = torch.cat([b.detach() for b in bs], dim=0)
+        torch.cuda.current_stream(b0.device).synchronize()
+        n0 = 0
+        for b in bs:
+            b.data = cat[n0:n0 + b.numel()]
+            n0 += b.numel()
+    try:
+        mods[0]._dalm_cat_bias = cat
     except Exception:
         return None
     return cat
 
 
 def uncat_weights(model: torch.nn.Module) -> int:
-    """Give every projection pair that shares ONE concatenated weight tensor (`_cat_weights`) its own storage again - for callers
-    that serialise whole modules tensor by tensor (`save_pretrained` of a frozen full model: safetensors refuses tensors that share
-    memory).  The next eligible forward concatenates again.  Returns how many pairs were separated."""
+    """Give every projection group that shares ONE concatenated weight tensor (`_cat_weights`, and `_cat_biases` with it) its own
+    storage again - for callers that serialise whole modules tensor by tensor (`save_pretrained` of a frozen full model:
+    safetensors refuses tensors that share memory).  The next eligible forward concatenates again.  Returns how many groups were
+    separated."""
     n = 0
     for m in model.modules():
         if getattr(m, "_dalm_cat", None) is None:
             continue
-        cat = m._dalm_cat
-        for other in model.modules():
-            w = getattr(other, "weight", None)
-            if isinstance(w, torch.Tensor) and w.dim() == 2 and w.untyped_storage().data_ptr() == cat.untyped_storage().data_ptr():
-                with torch.no_grad():
-                    w.data = w.detach().clone()
-                drop_dgrad_copy(w)
-        try:
-            del m._dalm_cat
-        except Exception:
-            m._dalm_cat = None
+        cats = [(m._dalm_cat, "weight", 2)]
+        if getattr(m, "_dalm_cat_bias", None) is not None:
+            cats.append((m._dalm_cat_bias, "bias", 1))
+        for cat, attr, dim in cats:
+            for other in model.modules():
+                w = getattr(other, attr, None)
+                if isinstance(w, torch.Tensor) and w.dim() == dim and w.untyped_storage().data_ptr() == cat.untyped_storage().data_ptr():
+                    with torch.no_grad():
+                        w.data = w.detach().clone()
+                    if dim == 2:
+                        drop_dgrad_copy(w)
+        drop_dgrad_copy(m._dalm_cat)
+        for a in ("_dalm_cat", "_dalm_cat_bias"):
+            if hasattr(m, a):
+                try:
+                    delattr(m, a)
+                except Exception:
+                    setattr(m, a, None)
         n += 1
     return n
 

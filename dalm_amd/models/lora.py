@@ -165,6 +165,22 @@ class LoRAGroup:
                     m.scaling, p, salt)
         return (m.weight, m.bias, None, None, 0.0, 0.0, 0)
 
+    def _cat(self):
+        """(W, bias or None): the members' frozen base weights (and biases) as views of ONE tensor, so that the group's base
+        projections run as one GEMM (frozen_linear._cat_weights); None when they cannot share."""
+        from . import frozen_linear
+
+        bases = [m.base_layer if isinstance(m, LoRALinear) else m for m in self.members]
+        if len(bases) < 2:
+            return None
+        w = frozen_linear._cat_weights(*bases)
+        if w is None:
+            return None
+        if all(b.bias is None for b in bases):
+            return (w, None)
+        bias = frozen_linear._cat_biases(*bases)
+        return (w, bias) if bias is not None else None
+
     def fetch(self, module, x):
         """The output of `module` for input x, or None (the caller computes it itself)."""
         if not self.enabled or not _GROUPS or not _FUSED:
@@ -199,7 +215,7 @@ class LoRAGroup:
         args = [self._member_args(m) for m in self.members]
         if not lora_ops.group_supported(x, args):
             return None
-        outs = lora_ops.lora_group_forward(x, args)
+        outs = lora_ops.lora_group_forward(x, args, self._cat())
         self._x = x
         self._outs = {id(m): o for m, o in zip(self.members, outs)}
         out = self._outs.pop(id(module))

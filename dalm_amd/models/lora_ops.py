@@ -15,6 +15,11 @@ base GEMMs of the backward accumulate into one dx (no autograd add kernels), and
 forward and kept as bits (the backward no longer reads the seed word).  lora_B is held in [r, N]-major memory (models/lora.py) so
 that every weight operand is K-major.  float32 activations keep the round-4 kernels below.
 
+One buffer for a group (frozen bf16 members whose weights `frozen_linear._cat_weights` made views of one [sum N, K] tensor): the
+base projections are ONE GEMM into [R, sum N]; the members' outputs are its column slices and the rank updates run in place on
+them through the kernels' row stride (`dalm_lora2_*_ld`).  The backward is unchanged - the accumulating dgrad GEMMs on dense
+gradients - and so is every result: the step computes bit for bit what it computed with one GEMM per member.
+
 Dropout (float32 path): the mask is never stored; the kernels regenerate it from (a 64-bit seed word in DEVICE memory, a per-call salt, the
 element index).  `advance_dropout_seed()` bumps the seed word with a device op, so it can be captured into the step's
 hipGraph: every replay draws new masks.  The per-call salt (module id and a host call counter) separates the modules and -
@@ -252,22 +257,34 @@ def _bt(b: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _row_stride(ts) -> int:
+    """The row stride (elements) the bf16 activation operands of one launch share: each a [R, C] tensor with unit column stride -
+    contiguous, or the column slice of a wider row-major buffer (q | k | v as the output of one GEMM)."""
+    ld = ts[0].stride(0) if ts[0].shape[0] > 1 else ts[0].shape[1]
+    for t in ts:
+        if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) != ld):
+            raise ValueError("dalm_lora2: the activation operands of one launch must be row-major with ONE row stride")
+    return ld
+
+
 def rowdot2(xs, Ws, rank: int, scale: float, p: float, salts, mode: int, live=None):
     """mode 1: ([x], [W]) -> [z];  mode 2: ([x], [W0, W1]) -> [z0, z1] from ONE pass over x;  mode 3: ([x0, x1], [W0, W1]).
     Returns (zs, bits): bits[t] is the [R, K/8] uint8 keep mask of slot t (None without dropout).
-    live (here and below): uint8 [R] row liveness or None (dalm_amd/live_rows.py): dead rows are not read, their z is zero."""
+    live (here and below): uint8 [R] row liveness or None (dalm_amd/live_rows.py): dead rows are not read, their z is zero.
+    The bf16 activations (here x, below y / x) may be column slices of a wider buffer: the kernels take their row stride."""
     x0 = xs[0]
     R, K = x0.shape
+    ld = _row_stride(xs)
     n = 1 if mode == 1 else 2
     dev = x0.device
     zs = [torch.empty(R, rank, device=dev, dtype=torch.float32) for _ in range(n)]
     bits = [torch.empty(R, K // 8, device=dev, dtype=torch.uint8) if p > 0 else None for _ in range(n)]
     seed = dropout_seed(dev) if p > 0 else None
     x1 = xs[1] if mode == 3 else None
-    hip.call("dalm_lora2_rowdot_live", hip.ptr(x0), hip.ptr(x1), hip.ptr(Ws[0]), hip.ptr(Ws[1]) if n == 2 else None,
+    hip.call("dalm_lora2_rowdot_ld", hip.ptr(x0), hip.ptr(x1), hip.ptr(Ws[0]), hip.ptr(Ws[1]) if n == 2 else None,
              hip.ptr(zs[0]), hip.ptr(zs[1]) if n == 2 else None, hip.ptr(bits[0]), hip.ptr(bits[1]) if n == 2 else None,
              R, K, rank, float(scale), float(p), hip.ptr(seed), int(salts[0]) & 0xFFFFFFFF,
-             (int(salts[1]) & 0xFFFFFFFF) if n == 2 else 0, mode, hip.ptr(live), hip.stream())
+             (int(salts[1]) & 0xFFFFFFFF) if n == 2 else 0, mode, hip.ptr(live), ld, hip.stream())
     return zs, bits
 
 
@@ -276,10 +293,11 @@ def rankupd2_(ys, zs, Ws, bits, rank: int, scale: float, mode: int, live=None):
     y0 = ys[0]
     R, C = y0.shape
     n = 1 if mode == 1 else 2
-    hip.call("dalm_lora2_rankupd_live", hip.ptr(y0), hip.ptr(ys[1]) if mode == 3 else None, hip.ptr(zs[0]),
+    ld = _row_stride(ys)
+    hip.call("dalm_lora2_rankupd_ld", hip.ptr(y0), hip.ptr(ys[1]) if mode == 3 else None, hip.ptr(zs[0]),
              hip.ptr(zs[1]) if n == 2 else None, hip.ptr(Ws[0]), hip.ptr(Ws[1]) if n == 2 else None,
              hip.ptr(bits[0]) if bits is not None else None, hip.ptr(bits[1]) if (bits is not None and n == 2) else None,
-             R, C, rank, float(scale), mode, hip.ptr(live), hip.stream())
+             R, C, rank, float(scale), mode, hip.ptr(live), ld, hip.stream())
     return ys
 
 
@@ -294,10 +312,11 @@ def colacc2(xs, zs, bits, rank: int, scale: float, mode: int, live=None):
     nbytes = lib.dalm_lora2_colacc_workspace_bytes(R, C, rank, mode)
     ws = torch.empty(max(nbytes, 8), device=dev, dtype=torch.uint8)
     tickets = _colacc_tickets(dev, lib.dalm_lora2_colacc_ticket_words(C, mode))
-    hip.call("dalm_lora2_colacc_live", hip.ptr(x0), hip.ptr(xs[1]) if mode == 3 else None, hip.ptr(zs[0]),
+    ld = _row_stride(xs)
+    hip.call("dalm_lora2_colacc_ld", hip.ptr(x0), hip.ptr(xs[1]) if mode == 3 else None, hip.ptr(zs[0]),
              hip.ptr(zs[1]) if n == 2 else None, hip.ptr(bits[0]) if bits is not None else None,
              hip.ptr(bits[1]) if (bits is not None and n == 2) else None, hip.ptr(outs[0]), hip.ptr(outs[1]) if n == 2 else None,
-             R, C, rank, float(scale), mode, hip.ptr(ws), nbytes, hip.ptr(tickets), hip.ptr(live), hip.stream())
+             R, C, rank, float(scale), mode, hip.ptr(ws), nbytes, hip.ptr(tickets), hip.ptr(live), ld, hip.stream())
     return outs
 
 
@@ -309,10 +328,13 @@ def _pairs(idx):
 class _LoRAGroupFn(torch.autograd.Function):
     """(out_0, ..., out_{n-1}) = (W_i x + b_i [+ s_i B_i A_i dropout_i(x)])_i for projections that read the same x.
     Tensor arguments after x, per member: weight, bias or None, lora_A or None, lora_B^T ([r, N] contiguous) or None.
-    meta: per member (scaling, p, salt) or None for a plain Linear."""
+    meta: per member (scaling, p, salt) or None for a plain Linear.
+    cat: None, or (W, bias or None) with W the ONE [sum N_i, K] tensor the members' weights are row blocks of
+    (frozen_linear._cat_weights): the base projections then run as one GEMM into a [R, sum N_i] buffer, the outputs are its
+    column slices, and the rank updates run in place on the slices, by row stride.  The backward is the same either way."""
 
     @staticmethod
-    def forward(ctx, x, meta, *flat):
+    def forward(ctx, x, meta, cat, *flat):
         n = len(meta)
         Ws, bs, As, Bts = flat[0::4], flat[1::4], flat[2::4], flat[3::4]
         K = Ws[0].shape[1]
@@ -324,9 +346,13 @@ class _LoRAGroupFn(torch.autograd.Function):
         wc = [w if w.dtype == x2.dtype else w.to(x2.dtype) for w in Ws]
         outs = []
         with torch.autocast("cuda", enabled=False):
-            for i in range(n):
-                bi = bs[i] if bs[i] is None or bs[i].dtype == x2.dtype else bs[i].to(x2.dtype)
-                outs.append(torch.nn.functional.linear(x2, wc[i], bi))
+            if cat is not None:
+                y = torch.nn.functional.linear(x2, cat[0], cat[1])                     # [R, sum N_i]: one GEMM
+                outs = list(y.split([w.shape[0] for w in Ws], dim=1))
+            else:
+                for i in range(n):
+                    bi = bs[i] if bs[i] is None or bs[i].dtype == x2.dtype else bs[i].to(x2.dtype)
+                    outs.append(torch.nn.functional.linear(x2, wc[i], bi))
         lora = [i for i in range(n) if meta[i] is not None]
         rank = As[lora[0]].shape[0]
         zs, bits = [None] * n, [None] * n
@@ -445,14 +471,15 @@ class _LoRAGroupFn(torch.autograd.Function):
             dx = dx.view(ctx.xshape)
             if dx.dtype != ctx.xdtype:
                 dx = dx.to(ctx.xdtype)
-        grads = [dx, None]
+        grads = [dx, None, None]
         for i in range(n):
             grads += [None, None, dA.get(i), dBt.get(i)]
         return tuple(grads)
 
 
-def lora_group_forward(x, members):
-    """members: list of (weight, bias, lora_A or None, lora_B or None, scaling, p, salt).  Returns the tuple of outputs."""
+def lora_group_forward(x, members, cat=None):
+    """members: list of (weight, bias, lora_A or None, lora_B or None, scaling, p, salt).  Returns the tuple of outputs.
+    cat: see _LoRAGroupFn (the caller made it with frozen_linear._cat_weights / _cat_biases from the members' modules)."""
     from .bert_ops import twin
 
     x = twin(x)               # an f32 LayerNorm output carrying its bf16 copy (bert_ops): no second cast, same autograd node
@@ -464,7 +491,12 @@ def lora_group_forward(x, members):
         else:
             meta.append((float(scaling), float(p), int(salt) & 0xFFFFFFFF))
             flat += [w, bias, a, _bt(b)]
-    return _LoRAGroupFn.apply(x, tuple(meta), *flat)
+    if cat is not None:
+        cdt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else x.dtype
+        if (cat[0].dtype != cdt or (cat[1] is not None and cat[1].dtype != cdt) or cat[0].shape[0] % 8 != 0
+                or any(w.shape[0] % 8 != 0 for (w, *_rest) in members)):
+            cat = None                # weights kept in another dtype are cast per call: nothing to share; slices must stay 16-byte aligned
+    return _LoRAGroupFn.apply(x, tuple(meta), cat, *flat)
 
 
 def group_supported(x, members) -> bool:

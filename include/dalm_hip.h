@@ -698,6 +698,20 @@ int dalm_lora2_rankupd_live(void* y0, void* y1, const float* z0, const float* z1
 int dalm_lora2_colacc_live(const void* x0, const void* x1, const float* z0, const float* z1, const void* bits0, const void* bits1,
                            float* out0, float* out1, int64_t R, int64_t C, int rank, float scale, int mode, void* ws,
                            size_t ws_bytes, uint32_t* tickets, const uint8_t* row_live, dalm_stream_t stream);
+/* The same with a row stride: `ld` is the distance in ELEMENTS between two rows of the bf16 activation operand (x0 / x1 of rowdot
+ * and colacc, y0 / y1 of rankupd; both slots of mode 3 share it), so the operand may be the columns [0, C) of a wider row-major
+ * buffer.  ld >= C and ld % 8 == 0 (DALM_E_SHAPE), bases 16-byte aligned (DALM_E_ALIGN).  Columns >= C of a row are neither read
+ * nor written.  z, W, bits, ws and the outputs stay dense; the dropout mask is that of the logical element index row * C + c,
+ * whatever ld.  The entry points above are these with ld = K (rowdot) / ld = C. */
+int dalm_lora2_rowdot_ld(const void* x0, const void* x1, const float* W0, const float* W1, float* out0, float* out1, void* bits0,
+                         void* bits1, int64_t R, int64_t K, int rank, float scale, float p, const void* seed, uint32_t salt0,
+                         uint32_t salt1, int mode, const uint8_t* row_live, int64_t ld, dalm_stream_t stream);
+int dalm_lora2_rankupd_ld(void* y0, void* y1, const float* z0, const float* z1, const float* W0, const float* W1,
+                          const void* bits0, const void* bits1, int64_t R, int64_t C, int rank, float scale, int mode,
+                          const uint8_t* row_live, int64_t ld, dalm_stream_t stream);
+int dalm_lora2_colacc_ld(const void* x0, const void* x1, const float* z0, const float* z1, const void* bits0, const void* bits1,
+                         float* out0, float* out1, int64_t R, int64_t C, int rank, float scale, int mode, void* ws,
+                         size_t ws_bytes, uint32_t* tickets, const uint8_t* row_live, int64_t ld, dalm_stream_t stream);
 
 /* ---- round 5: backward of the fused lm_head + marginalised CE ---------------------------------------
  * Replaces, for a FROZEN bias-free head,   logits = lm_head(hidden); loss(logits).backward()

@@ -71,7 +71,12 @@ def main():
             t = timed(lambda: F.linear(xx, W))
             print(f"rows {R:5d}  {name:8s} N={N:5d} K={Kk:5d}  forward {t:8.1f} us  {2.0 * R * N * Kk / t / 1e6:7.1f} TF/s", flush=True)
     if args.tune:
-        tunable.write_file()
+        # TunableOp writes its results file itself when the process exits; torch builds that also have an explicit
+        # tunable.write_file() get the file now
+        write = getattr(tunable, "write_file", None)
+        if write is not None:
+            write()
+        print("tuned solutions ->", tunable.get_filename(), flush=True)
 
 
 if __name__ == "__main__":
