@@ -497,6 +497,132 @@ __global__ __launch_bounds__(256) void pool_packed_kernel(const T* __restrict__ 
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Last-token pooling from packed rows (causal-LM retrievers: the reference pools the state of the last column, which a
+// `pack_plan(..., last_column=True)` keeps as the last row of every sequence).  Forward: one workgroup per sequence reads
+// ONE row, cu[s+1] - 1, into registers (up to 8192 elements: 32 f32 values per thread), forms |u| and writes the f32 row.
+// HBM: nseq_out*D*eh bytes read + nseq_out*D*4 written - a latency-sized kernel, the point is that nothing else is touched.
+// ---------------------------------------------------------------------------------------------------
+constexpr int POOL_LAST_MAX_D = 8192;
+
+template <typename T>
+__global__ __launch_bounds__(256) void pool_last_fwd_kernel(const T* __restrict__ h, const int* __restrict__ cu, int n, int D,
+                                                            int normalize, float* __restrict__ emb, int64_t ld_emb,
+                                                            float* __restrict__ norm) {
+  constexpr int VEC = Vec16<T>::VEC;
+  constexpr int NCH = POOL_LAST_MAX_D / VEC / 256;     // 16-byte chunks per thread at the widest row: 8 (f32) / 4 (bf16)
+  __shared__ float red[4];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const int hi = min(max(cu[s + 1], 0), n);            // clamped: a malformed cu cannot send a load out of h
+  const int lo = min(max(cu[s], 0), hi);
+  const bool some = hi > lo;
+  const T* row = h + static_cast<int64_t>(some ? hi - 1 : 0) * D;
+  float x[NCH][VEC];
+  float ss = 0.f;
+#pragma unroll
+  for (int q = 0; q < NCH; ++q) {
+    const int d = (q * 256 + tid) * VEC;
+    const bool ok = some && d < D;                     // D % VEC == 0: a chunk is inside the row or outside it
+    Vec16<T>::load(row + (d < D ? d : 0), x[q]);       // unconditional (n >= 1, D >= VEC): the value is dropped when !ok
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      x[q][e] = ok ? x[q][e] : 0.f;
+      ss = fmaf(x[q][e], x[q][e], ss);
+    }
+  }
+  ss = block_sum<256>(ss, red);
+  const float nrm = sqrtf(ss);
+  if (tid == 0 && norm) norm[s] = nrm;
+  const float denom = fmaxf(nrm, 1e-12f);
+  float* out = emb + static_cast<int64_t>(s) * ld_emb;
+#pragma unroll
+  for (int q = 0; q < NCH; ++q) {
+    const int d = (q * 256 + tid) * VEC;
+    if (d < D) {
+#pragma unroll
+      for (int e4 = 0; e4 < VEC; e4 += 4)
+        *reinterpret_cast<float4*>(out + d + e4) =
+            normalize ? make_float4(x[q][e4] / denom, x[q][e4 + 1] / denom, x[q][e4 + 2] / denom, x[q][e4 + 3] / denom)
+                      : make_float4(x[q][e4], x[q][e4 + 1], x[q][e4 + 2], x[q][e4 + 3]);
+    }
+  }
+}
+
+// Backward: dh [n, D] is written once, by one launch.  Workgroup w owns the rows [w R, (w + 1) R) - one contiguous byte range -
+// and walks it as zero segments between the rows that close a sequence < nseq_out: a binary search over cu finds the first
+// sequence end at or after its first row, the following ends are met in order.  The zero segments are flat 16-byte stores
+// (4 in flight per thread), a closing row gets du (the dot product e . d_e over the block first).  Everything that steers
+// the walk is the same in every lane; a malformed cu can only change WHICH of the workgroup's own rows count as closing.
+//   du = d_e                                       (normalize == 0)
+//   du = (d_e - e (e . d_e)) / |u|                 (|u| >= 1e-12)
+//   du = d_e / 1e-12                               (|u| <  1e-12: clamp_min branch, as pool_bwd_kernel)
+template <typename T>
+__global__ __launch_bounds__(256) void pool_last_bwd_kernel(const float* __restrict__ d_emb, int64_t ld_demb,
+                                                            const float* __restrict__ emb, int64_t ld_emb,
+                                                            const float* __restrict__ norm, const int* __restrict__ cu, int n,
+                                                            int nseq_out, int D, int rows_per_wg, int normalize,
+                                                            T* __restrict__ dh) {
+  constexpr int VEC = Vec16<T>::VEC;
+  __shared__ float red[4];
+  const int tid = threadIdx.x;
+  const int64_t r0 = static_cast<int64_t>(blockIdx.x) * rows_per_wg;
+  const int r1 = static_cast<int>(min(static_cast<int64_t>(n), r0 + rows_per_wg));
+  const int lanes = D / VEC;                           // 16-byte chunks of a row
+  float zero[VEC];
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) zero[e] = 0.f;
+  // first j in [1, nseq_out] with cu[j] >= r0 + 1 (nseq_out + 1: none)
+  int jl = 1, jh = nseq_out + 1;
+  while (jl < jh) {
+    const int jm = (jl + jh) >> 1;
+    if (cu[jm] < r0 + 1) jl = jm + 1; else jh = jm;
+  }
+  int j = jl;
+  int cur = static_cast<int>(r0);
+  while (cur < r1) {
+    while (j <= nseq_out && cu[j] < cur + 1) ++j;      // ends already behind: empty sequences repeat an end
+    const int close = (j <= nseq_out && cu[j] - 1 < r1) ? cu[j] - 1 : r1;
+    // zero rows [cur, close): one flat range of 16-byte chunks
+    T* base = dh + static_cast<int64_t>(cur) * D;
+    const int64_t chunks = static_cast<int64_t>(close - cur) * lanes;
+    for (int64_t i = tid; i < chunks; i += 4 * 256) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (i + u * 256 < chunks) Vec16<T>::store(base + (i + u * 256) * VEC, zero);
+    }
+    if (close >= r1) break;
+    const int s = j - 1;
+    const bool some = cu[s] <= close;                  // a non-empty sequence (always, for a monotone cu)
+    const float* de = d_emb + static_cast<int64_t>(s) * ld_demb;
+    const float* eb = emb + static_cast<int64_t>(s) * ld_emb;
+    float dot = 0.f, nrm = 1.f;
+    if (normalize && some) {
+      for (int i = tid; i < D; i += 256) dot = fmaf(eb[i], de[i], dot);
+      dot = block_sum<256>(dot, red);
+      nrm = norm[s];
+    }
+    T* row = dh + static_cast<int64_t>(close) * D;
+    for (int c = tid; c < lanes; c += 256) {
+      const int d = c * VEC;
+      float o[VEC];
+#pragma unroll
+      for (int e4 = 0; e4 < VEC; e4 += 4) {            // both rows are 16-byte aligned by contract
+        const float4 g4 = some ? *reinterpret_cast<const float4*>(de + d + e4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 q4 = (some && normalize) ? *reinterpret_cast<const float4*>(eb + d + e4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float g[4] = {g4.x, g4.y, g4.z, g4.w}, q[4] = {q4.x, q4.y, q4.z, q4.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float v = g[e];
+          if (normalize) v = (nrm >= 1e-12f) ? (g[e] - q[e] * dot) / nrm : g[e] / 1e-12f;
+          o[e4 + e] = some ? v : 0.f;
+        }
+      }
+      Vec16<T>::store(row + d, o);
+    }
+    cur = close + 1;
+  }
+}
+
 }  // namespace
 }  // namespace dalm
 
@@ -682,6 +808,61 @@ extern "C" int dalm_pool_l2norm_packed_fwd(const void* h, int dtype, const int32
                          static_cast<const Elt*>(h), cu, static_cast<int>(n), static_cast<int>(nseq_out), static_cast<int>(D), wps,
                          emb, ld_emb, norm, inv_count);
     });
+  });
+  return check_launch(__func__);
+}
+
+namespace dalm {
+namespace {
+// the argument checks the two last-token entry points share (before anything is enqueued)
+inline int pool_last_check(const char* fn, int dtype, int64_t n, int64_t nseq, int64_t nseq_out, int64_t D, int64_t ld_a, int64_t ld_b,
+                           bool aligned) {
+  if (dtype != DALM_F32 && dtype != DALM_BF16) return fail(DALM_E_DTYPE, fn, "dtype must be DALM_F32 or DALM_BF16");
+  const int vec = (dtype == DALM_F32) ? 4 : 8;
+  if (!(n > 0 && nseq > 0 && nseq_out >= 0 && nseq_out <= nseq && n <= 0x7fffffffll && nseq <= 0x7ffffff0ll && D > 0 &&
+        D % vec == 0 && D <= POOL_LAST_MAX_D && ld_a >= D && ld_b >= D))
+    return fail(DALM_E_SHAPE, fn, "need n>0, 0<=nseq_out<=nseq, D a multiple of 16 bytes and <= 8192, leading dimensions >= D");
+  if (!(aligned && ld_a % 4 == 0 && ld_b % 4 == 0))
+    return fail(DALM_E_ALIGN, fn, "rows must be 16-byte aligned: base pointers, and leading dimensions a multiple of 4");
+  return 0;
+}
+}  // namespace
+}  // namespace dalm
+
+extern "C" int dalm_pool_last_packed_fwd(const void* h, int dtype, const int32_t* cu, int64_t n, int64_t nseq, int64_t nseq_out,
+                                         int64_t D, int normalize, float* emb, int64_t ld_emb, float* norm, dalm_stream_t stream) {
+  DALM_REQUIRE(h && cu && (nseq_out == 0 || emb), DALM_E_NULL, "null pointer argument");
+  if (const int rc = pool_last_check(__func__, dtype, n, nseq, nseq_out, D, ld_emb, ld_emb, aligned16(h, emb))) return rc;
+  if (nseq_out == 0) return 0;
+  hipStream_t s = as_stream(stream);
+  by_dtype(dtype, [&](auto t) {
+    using Elt = typename decltype(t)::type;
+    hipLaunchKernelGGL((pool_last_fwd_kernel<Elt>), dim3(static_cast<unsigned>(nseq_out)), dim3(256), 0, s,
+                       static_cast<const Elt*>(h), cu, static_cast<int>(n), static_cast<int>(D), normalize, emb, ld_emb, norm);
+  });
+  return check_launch(__func__);
+}
+
+extern "C" int dalm_pool_last_packed_bwd(const float* d_emb, int64_t ld_demb, const float* emb, int64_t ld_emb, const float* norm,
+                                         const int32_t* cu, int64_t n, int64_t nseq, int64_t nseq_out, int64_t D, int normalize,
+                                         void* dh, int dtype, dalm_stream_t stream) {
+  // nseq_out == 0 pools nothing (dh is all zeros): the pooled side may then be empty tensors, i.e. NULL
+  DALM_REQUIRE(cu && dh && (nseq_out == 0 || (d_emb && emb && norm)), DALM_E_NULL, "null pointer argument");
+  if (const int rc = pool_last_check(__func__, dtype, n, nseq, nseq_out, D, ld_demb, ld_emb, aligned16(d_emb, emb, dh))) return rc;
+  // Rows per workgroup: at most 2048 workgroups (256 CUs x 8 resident 256-thread workgroups: the whole grid is resident at once
+  // and each workgroup streams one contiguous range), and at least 16 KB per workgroup (256 threads x 4 stores of 16 bytes in
+  // flight) so that a narrow row does not leave most of a workgroup idle.
+  const int64_t row_bytes = D * (dtype == DALM_F32 ? 4 : 2);
+  int64_t R = (n + 2047) / 2048;
+  const int64_t r_min = (16384 + row_bytes - 1) / row_bytes;
+  if (R < r_min) R = r_min;
+  const int64_t grid = (n + R - 1) / R;
+  hipStream_t s = as_stream(stream);
+  by_dtype(dtype, [&](auto t) {
+    using Elt = typename decltype(t)::type;
+    hipLaunchKernelGGL((pool_last_bwd_kernel<Elt>), dim3(static_cast<unsigned>(grid)), dim3(256), 0, s, d_emb, ld_demb, emb, ld_emb,
+                       norm, cu, static_cast<int>(n), static_cast<int>(nseq_out), static_cast<int>(D), static_cast<int>(R), normalize,
+                       static_cast<Elt*>(dh));
   });
   return check_launch(__func__);
 }

@@ -26,6 +26,7 @@ logger = logging.getLogger(__name__)
 
 RECALL_LADDER = (1, 5, 10, 20, 50, 100)
 PACKED_SWEEP_DEFAULT = False      # opt-in: the one measurement on record (profiles/eval_bench.txt) has it slower than the padded forward
+PACKED_POOL_LAST_MAX_WIDTH = 8192    # dalm_pool_last_packed_fwd (causal-LM retrievers)
 PACKED_POOL_MAX_WIDTH = 1024     # dalm_pool_l2norm_packed_fwd on f32 rows (the final LayerNorm under autocast returns f32)
 
 
@@ -85,9 +86,12 @@ def _autocast(device: str, torch_dtype: torch.dtype):
     return torch.autocast(device_type=kind, dtype=torch_dtype, enabled=torch_dtype in (torch.float16, torch.bfloat16))
 
 
-def _packable_encoder(forward_fn, torch_dtype: torch.dtype, device: str):
-    """The encoder module behind `forward_fn` (the bound `forward` / `retrieval_forward` of this package's two model classes)
-    when the packed sweep can run it, else None."""
+def _packable_encoder(forward_fn, torch_dtype: torch.dtype, device: str, T: Optional[int] = None):
+    """(encoder module, autoregressive) behind `forward_fn` (the bound `forward` / `retrieval_forward` of this package's two
+    model classes) when the packed sweep can run it, else None.  An autoregressive owner qualifies when the sweep can call its
+    decoder stack directly (models.rag_e2e_base_model.decoder_only; the model classes' own padded call stays the reference's):
+    the sweep then keeps the pooled column in its plans and pools with
+    `dalm_pool_last_packed_fwd`, whose width limit is 8192, not PACKED_POOL_MAX_WIDTH."""
     owner = getattr(forward_fn, "__self__", None)
     if owner is None or torch_dtype != torch.bfloat16 or torch.device(device).type != "cuda":
         return None
@@ -98,11 +102,16 @@ def _packable_encoder(forward_fn, torch_dtype: torch.dtype, device: str):
         enc, autoregressive = owner.retriever_model, owner.retriever_is_autoregressive
     else:
         return None
-    if autoregressive or not getattr(owner, "normalize", False) or not packed.attention_is_packable(enc):
+    if not getattr(owner, "normalize", False) or not packed.attention_is_packable(enc):
         return None
+    if autoregressive:
+        from ..models.rag_e2e_base_model import decoder_only
+
+        width = getattr(enc.config, "hidden_size", 1 << 30)
+        return (enc, True) if decoder_only(enc, T) and width <= PACKED_POOL_LAST_MAX_WIDTH and width % 8 == 0 else None
     if getattr(enc.config, "hidden_size", 1 << 30) > PACKED_POOL_MAX_WIDTH:       # wider rows: the padded pooling kernel
         return None
-    return enc
+    return enc, False
 
 
 def token_budget_batches(lengths: torch.Tensor, budget: int) -> Tuple[torch.Tensor, List[Tuple[int, int]]]:
@@ -136,14 +145,15 @@ def embed_dataset(dataset, prefix: str, forward_fn, device: str, torch_dtype: to
     N, T = ids.shape
     if N == 0:
         raise ValueError("nothing to embed: the dataset has no rows")
-    enc = None
+    enc, causal = None, False
     if packed_sweep or (packed_sweep is None and PACKED_SWEEP_DEFAULT):
-        enc = _packable_encoder(forward_fn, torch_dtype, device)
-        if enc is not None and not bool(((mask == 0) | (mask == 1)).all()):
-            enc = None
+        found = _packable_encoder(forward_fn, torch_dtype, device, T)
+        if found is not None and bool(((mask == 0) | (mask == 1)).all()):
+            enc, causal = found
         if enc is None and packed_sweep:
-            raise ValueError("packed_sweep=True needs bfloat16 on a GPU, 0/1 masks and an encoder retriever of this package "
-                             f"with packable attention and width <= {PACKED_POOL_MAX_WIDTH}")
+            raise ValueError("packed_sweep=True needs bfloat16 on a GPU, 0/1 masks and a retriever of this package with packable "
+                             f"attention: an encoder of width <= {PACKED_POOL_MAX_WIDTH}, or a causal LM whose decoder stack is "
+                             f"called directly, of width <= {PACKED_POOL_LAST_MAX_WIDTH}")
     out: Optional[torch.Tensor] = None
     if enc is None:
         for a in range(0, N, batch_size):
@@ -155,18 +165,28 @@ def embed_dataset(dataset, prefix: str, forward_fn, device: str, torch_dtype: to
         assert out is not None
         return out
     ops = default_ops()
-    order, cuts = token_budget_batches(mask.sum(dim=1), batch_size * T)
+    kept = mask != 0
+    if causal:                                    # the pooled column stays in every plan (packed.pack_plan, last_column)
+        kept = kept.clone()
+        kept[:, -1] = True
+    order, cuts = token_budget_batches(kept.sum(dim=1), batch_size * T)
     for a, b in cuts:
         idx = order[a:b]
         ids_b, mask_b = ids[idx], mask[idx]
-        rows, cu = packed.pack_plan(mask_b, shifted=False)
+        rows, cu = packed.pack_plan(mask_b, shifted=False, last_column=causal)
         ids_p, pos, desc, _valid = packed.packed_inputs(ids_b.to(device), mask_b.to(device), rows.to(device), cu.to(device),
-                                                        causal=False)
+                                                        causal=causal)
         with torch.no_grad(), _autocast(device, torch_dtype):
-            h = enc(input_ids=ids_p, attention_mask=desc, position_ids=pos)[0][0]                 # [n, D]
+            if causal:
+                h = enc.base_model(input_ids=ids_p, attention_mask=desc, position_ids=pos, use_cache=False)[0][0]
+            else:
+                h = enc(input_ids=ids_p, attention_mask=desc, position_ids=pos)[0][0]             # [n, D]
         if out is None:
             out = torch.empty((N, h.shape[1]), device=h.device, dtype=torch.float32)
-        ops.pool_packed_fwd(h, packed.packed_of(desc).cu, nseq_out=b - a, out=out[a:b])           # sorted order
+        if causal:
+            ops.pool_last_packed_fwd(h, packed.packed_of(desc).cu, nseq_out=b - a, normalize=True, out=out[a:b])
+        else:
+            ops.pool_packed_fwd(h, packed.packed_of(desc).cu, nseq_out=b - a, out=out[a:b])       # sorted order
     assert out is not None
     return torch.empty_like(out).index_copy_(0, order.to(out.device), out)                        # back to dataset order
 

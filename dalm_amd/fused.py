@@ -119,6 +119,30 @@ def pool_l2norm(token_embeddings: torch.Tensor, attention_mask: torch.Tensor, no
     return _PoolL2Norm.apply(token_embeddings, attention_mask, bool(normalize), ops or default_ops())
 
 
+class _PoolLastPacked(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, cu, nseq_out, normalize, ops):
+        cu = cu if (cu.dtype == torch.int32 and cu.is_contiguous()) else cu.to(torch.int32).contiguous()
+        emb, norm = ops.pool_last_packed_fwd(h, cu, nseq_out, normalize)
+        ctx.save_for_backward(emb, norm, cu)
+        ctx.normalize, ctx.ops, ctx.n, ctx.h_dtype = normalize, ops, h.shape[0], h.dtype
+        return emb
+
+    @staticmethod
+    def backward(ctx, d_emb):
+        emb, norm, cu = ctx.saved_tensors
+        dh = ctx.ops.pool_last_packed_bwd(d_emb, emb, norm, cu, ctx.n, ctx.normalize, ctx.h_dtype)
+        return dh, None, None, None, None
+
+
+def pool_last_packed(h: torch.Tensor, cu: torch.Tensor, nseq_out: Optional[int] = None, normalize: bool = True, ops=None):
+    """Last-token pooling (+ F.normalize) of a causal-LM retriever (retriever_only_base_model.py:43-63) from PACKED rows:
+    h [n, D], cu [nseq + 1] sequence starts; f32 [nseq_out, D] with row s = h[cu[s + 1] - 1] (normalised).  `nseq` and
+    `nseq_out` are shapes / Python ints: no host sync."""
+    nseq_out = int(cu.numel()) - 1 if nseq_out is None else int(nseq_out)
+    return _PoolLastPacked.apply(h, cu, nseq_out, bool(normalize), ops or default_ops())
+
+
 # ---------------------------------------------------------------------------
 # shared forward/backward pieces
 # ---------------------------------------------------------------------------

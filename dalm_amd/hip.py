@@ -71,6 +71,8 @@ SIGNATURES = {
     "dalm_sim_topk_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "dalm_sim_topk": (_int, [_vp, _vp, _i64, _i64, _i64, _f32, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dalm_pool_l2norm_packed_fwd": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "dalm_pool_last_packed_fwd": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _int, _vp, _i64, _vp, _vp]),
+    "dalm_pool_last_packed_bwd": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _int, _vp]),
     "dalm_sim_gold_score": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp]),
     "dalm_sim_gold_rank_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "dalm_sim_gold_rank": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _f32, _vp, _vp, _vp, _sz, _vp]),

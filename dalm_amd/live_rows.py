@@ -2,7 +2,7 @@
 
 The padded layout pushes every padding position through both towers, and padding contributes exactly zero to the loss and to
 every gradient (dalm_amd/packed.py states why and which rows matter: generator row (b, t) iff mask[b, t] or mask[b, t + 1],
-retriever row iff mask[b, t]).  The packed path removes those rows; the padded path keeps the layout - GEMM shapes, graph sets -
+retriever row iff mask[b, t] - or t = T - 1 for a causal-LM retriever, which pools that column).  The packed path removes those rows; the padded path keeps the layout - GEMM shapes, graph sets -
 and lets the hand-written row-wise kernels skip them instead: every `dalm_*_live` entry point takes the uint8 vector built
 here (include/dalm_hip.h: a dead row is not read, freshly written outputs hold zeros there, live rows get the same bits).
 
@@ -22,22 +22,27 @@ import torch
 _state = threading.local()
 
 
-def live_rows(attention_mask: torch.Tensor, shifted: bool) -> torch.Tensor:
+def live_rows(attention_mask: torch.Tensor, shifted: bool, last_column: bool = False) -> torch.Tensor:
     """attention_mask [B, T] -> uint8 [B T], non-zero = the row matters.  shifted=True (generator): a row also matters when the
-    NEXT column is live (it carries that token's label) - the `keep` of `packed.pack_plan`; shifted=False (retriever): live."""
+    NEXT column is live (it carries that token's label) - the `keep` of `packed.pack_plan`; shifted=False (retriever): live.
+    last_column=True (causal-LM retriever): column T - 1 matters whatever the mask says - it is the pooled one (`eos_mask`), on a
+    right-padded row too."""
     keep = attention_mask != 0
     if shifted:
         keep = keep.clone()
         keep[:, :-1] |= attention_mask[:, 1:] != 0
+    if last_column:
+        keep = keep.clone()
+        keep[:, -1] = True
     return keep.contiguous().view(torch.uint8).reshape(-1)
 
 
 @contextlib.contextmanager
-def tower_call(attention_mask: Optional[torch.Tensor], shifted: bool, enabled: bool = True):
+def tower_call(attention_mask: Optional[torch.Tensor], shifted: bool, enabled: bool = True, last_column: bool = False):
     """Hold the liveness vector of `attention_mask` while one padded tower call runs (forward only: the wrappers save it)."""
     vec = None
     if enabled and attention_mask is not None and attention_mask.dim() == 2 and attention_mask.is_cuda:
-        vec = live_rows(attention_mask, shifted)
+        vec = live_rows(attention_mask, shifted, last_column)
     prev = getattr(_state, "vec", None)
     _state.vec = vec
     try:

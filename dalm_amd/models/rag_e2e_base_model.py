@@ -63,6 +63,44 @@ def to_nf4(model: torch.nn.Module) -> torch.nn.Module:
     return model
 
 
+# causal-LM retrievers whose decoder stack the PACKED route calls directly (dalm_amd/packed.py): `lm.base_model` returns the
+# final (normed) states that `hidden_states[-1]` of the `*ForCausalLM` call holds, bit for bit.  Any other type is not packed.
+DECODER_ONLY_TYPES = ("llama", "mistral", "qwen2")
+
+
+def _sliding_window(cfg):
+    """The attention window of a config when any layer uses one (mistral: `sliding_window`; qwen2: only with
+    `use_sliding_window`), else None."""
+    if getattr(cfg, "use_sliding_window", True) is False:
+        return None
+    if "sliding_attention" not in (getattr(cfg, "layer_types", None) or ["sliding_attention"]):
+        return None
+    return getattr(cfg, "sliding_window", None)
+
+
+def decoder_only(lm, T: Optional[int] = None) -> bool:
+    """A causal LM the packed route can serve at sequence length T: one of DECODER_ONLY_TYPES, and full causal attention over
+    the T columns - the packed attention knows no sliding window, so a model whose window is shorter than T (T unknown: than
+    its positions) is turned down and goes the padded way."""
+    cfg = getattr(lm, "config", None)
+    if getattr(cfg, "model_type", None) not in DECODER_ONLY_TYPES:
+        return False
+    window = _sliding_window(cfg)
+    return window is None or window >= (getattr(cfg, "max_position_embeddings", 1 << 30) if T is None else T)
+
+
+def use_causal_retriever_fast_paths(lm) -> None:
+    """The generator's row-wise layer nodes on a causal-LM retriever (each has its own guards and leaves other models alone):
+    native RMSNorm, roll-rope, SwiGLU, fused residual + norm, "dalm_sdpa".  Roll-rope and fused residual + norm patch Llama's
+    modeling code only: on mistral / qwen2 they do nothing.  The rotary + attention node (`use_llama_attention_node`) is not
+    applied to retrievers, rotary and attention run as two nodes there: DESIGN.md section 5.3 says why."""
+    use_native_rms_norm(lm)
+    use_roll_rope(lm)
+    use_swiglu_kernel(lm)
+    use_fused_residual_norm(lm)
+    use_hip_attention_backward(lm)
+
+
 class AutoModelForRagE2E(torch.nn.Module):
     def __init__(
         self,
@@ -121,9 +159,10 @@ class AutoModelForRagE2E(torch.nn.Module):
         use_falcon_attention_kernels(self.generator_model)
         use_hip_attention_backward(self.generator_model)
         use_llama_attention_node(self.generator_model)
-        use_hip_attention_backward(self.retriever_model)          # BERT: head width 64, attention dropout inside the kernels
         if autoregressive:
-            use_native_rms_norm(self.retriever_model)
+            use_causal_retriever_fast_paths(self.retriever_model)
+        else:
+            use_hip_attention_backward(self.retriever_model)      # BERT: head width 64, attention dropout inside the kernels
         if get_peft is not None:
             get_peft = Mode(get_peft)
             if get_peft in (Mode.RETRIEVER, Mode.BOTH):

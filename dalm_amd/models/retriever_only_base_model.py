@@ -9,8 +9,7 @@ import torch
 from ..fused import pool_l2norm
 from ..utils import eos_mask
 from . import lora
-from .fastpath import use_native_rms_norm
-from .rag_e2e_base_model import nf4_enabled, to_nf4
+from .rag_e2e_base_model import nf4_enabled, to_nf4, use_causal_retriever_fast_paths
 
 
 class AutoModelForSentenceEmbedding(torch.nn.Module):
@@ -43,11 +42,12 @@ class AutoModelForSentenceEmbedding(torch.nn.Module):
         if use_bnb and nf4_enabled(use_bnb):          # the reference's 4-bit load (:23-27), before the adapters
             model = to_nf4(model)
         self.model = model
-        if is_autoregressive:
-            use_native_rms_norm(self.model)
         from .attention import use_hip_attention_backward
 
-        use_hip_attention_backward(self.model)        # BERT / Llama-family: dalm_attn_* (attention dropout inside the kernels)
+        if is_autoregressive:                         # a causal LM: the generator's layer nodes (Llama-family; each guards itself)
+            use_causal_retriever_fast_paths(self.model)
+        else:
+            use_hip_attention_backward(self.model)    # BERT: dalm_attn_* (attention dropout inside the kernels)
         if get_peft:
             lora.inject_lora(self.model, ["key", "query", "value"] if not is_autoregressive else ["q_proj", "v_proj"])
         # frozen projections: backward GEMM through a transposed weight copy; BERT layers: dropout + add + LayerNorm in one launch

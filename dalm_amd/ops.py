@@ -80,6 +80,40 @@ class HipOps:
                  hip.ptr(out), ld, None, None, hip.stream())
         return out
 
+    def pool_last_packed_fwd(self, h: torch.Tensor, cu: torch.Tensor, nseq_out: Optional[int] = None, normalize: bool = True,
+                             out: Optional[torch.Tensor] = None):
+        """Last-token pooling (+ F.normalize) straight from packed rows (`dalm_pool_last_packed_fwd`; causal-LM retrievers):
+        h [n, D] f32 / bf16, cu int32 [nseq + 1]; sequence s < `nseq_out` gives the f32 row of h[cu[s + 1] - 1] (zeros when the
+        sequence is empty) in `out` [nseq_out, D] - a row slice of a larger f32 matrix is fine.  Returns (out, norm [nseq_out])."""
+        dev = hip.require_gpu(h, cu, out)
+        if h.dim() != 2 or cu.dim() != 1 or cu.numel() < 2:
+            raise ValueError(f"pool_last_packed: expected h [n,D] and cu [nseq+1], got {tuple(h.shape)} / {tuple(cu.shape)}")
+        h = h.contiguous()
+        cu = cu if (cu.dtype == torch.int32 and cu.is_contiguous()) else cu.to(torch.int32).contiguous()
+        n, D = h.shape
+        nseq = cu.numel() - 1
+        nseq_out = nseq if nseq_out is None else int(nseq_out)
+        if out is None:
+            out = torch.empty((nseq_out, D), device=dev, dtype=torch.float32)
+        if out.dtype != torch.float32 or out.dim() != 2 or out.shape != (nseq_out, D) or out.stride(1) != 1:
+            raise ValueError(f"pool_last_packed: out must be f32 [{nseq_out}, {D}] with unit column stride")
+        ld = out.stride(0) if nseq_out > 1 else max(out.stride(0), D)
+        norm = torch.empty((nseq_out,), device=dev, dtype=torch.float32)
+        hip.call("dalm_pool_last_packed_fwd", hip.ptr(h), hip.dtype_code(h), hip.ptr(cu), n, nseq, nseq_out, D, int(normalize),
+                 hip.ptr(out), ld, hip.ptr(norm), hip.stream())
+        return out, norm
+
+    def pool_last_packed_bwd(self, d_emb, emb, norm, cu, n: int, normalize: bool, dtype: torch.dtype):
+        """dh [n, D] of `pool_last_packed_fwd`: one launch writes every row (zeros but for the pooled rows)."""
+        dev = hip.require_gpu(d_emb, emb, norm, cu)
+        d_emb, emb = hip.as_f32c(d_emb), hip.as_f32c(emb)
+        cu = cu if (cu.dtype == torch.int32 and cu.is_contiguous()) else cu.to(torch.int32).contiguous()
+        nseq_out, D = emb.shape
+        dh = torch.empty((n, D), device=dev, dtype=dtype)
+        hip.call("dalm_pool_last_packed_bwd", hip.ptr(d_emb), D, hip.ptr(emb), D, hip.ptr(norm), hip.ptr(cu), n, cu.numel() - 1,
+                 nseq_out, D, int(normalize), hip.ptr(dh), hip.dtype_code(dh), hip.stream())
+        return dh
+
     def pool_bwd(self, d_emb, emb, norm, inv_count, mask, normalize: bool, T: int, dtype: torch.dtype):
         dev = hip.require_gpu(d_emb, emb, norm, inv_count, mask)
         d_emb = hip.as_f32c(d_emb)

@@ -20,7 +20,11 @@ BASELINE.json's cfg3 batch 2.9 k instead of 4.6 k generator rows and ~20 % of th
     kernels and torch's memory-efficient kernels produce) and is marked key-dead.
 
 Token set of a sequence: generator {t : mask[t] != 0 or mask[t + 1] != 0}, retriever {t : mask[t] != 0}; arbitrary masks (holes)
-are fine - local order = column order, so causality is preserved.  The rows are listed on the HOST where the mask still is host
+are fine - local order = column order, so causality is preserved.  A causal-LM retriever pools the state of the LAST COLUMN
+whatever the mask says (`eos_mask`, dalm/models/retriever_only_base_model.py:43-63): its token set is {t : mask[t] != 0 or
+t == T - 1} (`pack_plan(..., last_column=True)`, the *_GROUPS_CAUSAL tables) - on a right-padded row column T - 1 is one more
+query-only token, which sees exactly the live tokens before it, so its state is the padded run's - and the embedding is read
+from the last row of every sequence (`dalm_pool_last_packed_*`), nothing is scattered back to [B, T, D].  The rows are listed on the HOST where the mask still is host
 memory (data loader / batch staging; the count sets tensor shapes and reading it from the device would cost a sync per step):
 `pack_plan` returns `rows` (flat index b T + t per packed row, -1 for the slack that rounds the count up to a multiple so that
 only a few distinct shapes = hipGraphs occur) and `cu` (sequence starts; the slack forms one more sequence without live keys:
@@ -40,9 +44,17 @@ PACK_MULTIPLE = 128
 ROW_MULTIPLES = {"generator": 256, "retriever_query": 256, "retriever_passage": 512, "query": 256, "passage": 512}
 
 
-def pack_plan(attention_mask: torch.Tensor, shifted: bool, multiple: int = PACK_MULTIPLE) -> Tuple[torch.Tensor, torch.Tensor]:
+# batch key suffix that marks the row lists of a `last_column` plan (a zero-length tensor: every batch value is a tensor)
+LAST_COLUMN_KEY = "pack_last_column"
+
+
+def pack_plan(attention_mask: torch.Tensor, shifted: bool, multiple: int = PACK_MULTIPLE,
+              last_column: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """HOST side.  attention_mask [B, T] (any integer / bool dtype) -> (rows int64 [n_pad], cu int32 [B + 1 + n_slack]).
     shifted=True (generator): a token also stays when the NEXT column is live (its row carries a label).
+    last_column=True (causal-LM retriever): column T - 1 stays whatever the mask says - the reference pools that column
+    (`eos_mask`), so the last row of each of the B sequences is the pooled one; on a right-padded row it is query-only
+    (`key_live` still comes from the mask).
     The slack rows (n_pad - n < multiple) form n_slack = ceil(multiple / T) extra sequences of at most T rows each (one when
     multiple <= T): a sequence must fit the T rows of the attention layout, and the number of cu entries must not depend on the
     batch (it is a tensor shape)."""
@@ -56,6 +68,8 @@ def pack_plan(attention_mask: torch.Tensor, shifted: bool, multiple: int = PACK_
     keep = live.clone()
     if shifted:
         keep[:, :-1] |= live[:, 1:]
+    if last_column and T > 0:
+        keep[:, -1] = True
     idx = keep.reshape(-1).nonzero().squeeze(1)
     n = int(idx.numel())
     n_pad = max(multiple, -(-n // multiple) * multiple)
@@ -216,11 +230,60 @@ def retrieval_hidden_pair(retriever_model, first, second):
     return outs[0], outs[1]
 
 
+def _decoder_stack(lm):
+    """The decoder stack of a `*ForCausalLM` (no lm_head); a bare decoder is its own stack."""
+    return getattr(lm, "base_model", lm)
+
+
+def causal_retrieval_hidden(retriever_model, input_ids, attention_mask, rows, cu):
+    """Final (normed) states [n, D] of a causal-LM retriever on the rows of a `pack_plan(..., last_column=True)`: causal attention per
+    sequence, original columns as positions, padding dead as keys.  The last row of sequence b < B is column T - 1."""
+    ids_p, pos, desc, _valid = packed_inputs(input_ids, attention_mask, rows, cu, causal=True)
+    return _decoder_stack(retriever_model)(input_ids=ids_p, attention_mask=desc, position_ids=pos, use_cache=False)[0][0]
+
+
+def causal_retrieval_embed(retriever_model, input_ids, attention_mask, rows, cu, normalize: bool):
+    """Embeddings [B, D] f32 of a causal-LM retriever from the packed rows: the decoder stack, then `dalm_pool_last_packed_*`
+    straight from [n, D] - nothing is scattered back to [B, T, D].  No host sync: B and the sequence count are shapes."""
+    from .fused import pool_last_packed
+
+    h = causal_retrieval_hidden(retriever_model, input_ids, attention_mask, rows, cu)
+    return pool_last_packed(h, cu, int(input_ids.shape[0]), normalize)
+
+
+def causal_retrieval_embed_pair(retriever_model, first, second, normalize: bool):
+    """BOTH retriever inputs of a step through the decoder stack in ONE packed call, as `retrieval_hidden_pair` does for encoders:
+    `first` / `second` are (input_ids, attention_mask, rows, cu) of `last_column` plans.  The slack sequences of `first` sit in
+    the middle of the joint cu, so every sequence is pooled (a slack row is finite and feeds nothing) and the two batches are
+    sliced out.  Returns the two [B, D] f32 embedding matrices."""
+    from .fused import pool_last_packed
+
+    parts = []
+    off = 0
+    for ids, mask, rows, cu in (first, second):
+        ids_p, pos, desc, _valid = packed_inputs(ids, mask, rows, cu, causal=True)
+        parts.append((ids_p, pos, packed_of(desc), int(ids.shape[0]), off))
+        off += int(rows.numel())
+    T = max(p[2].T for p in parts)
+    cu_all = torch.cat([parts[0][2].cu, parts[1][2].cu[1:] + parts[1][4]]).to(torch.int32)
+    seqs = PackedSeqs(cu=cu_all, nseq=int(cu_all.numel()) - 1, T=int(T), n=off,
+                      key_live=torch.cat([p[2].key_live for p in parts]), causal=True)
+    desc = attach(torch.ones((1, 1, 1, 1), dtype=torch.bool, device=cu_all.device), seqs)
+    h = _decoder_stack(retriever_model)(input_ids=torch.cat([p[0] for p in parts], dim=1), attention_mask=desc,
+                                        position_ids=torch.cat([p[1] for p in parts], dim=1), use_cache=False)[0][0]
+    emb = pool_last_packed(h, cu_all, None, normalize)
+    s1 = parts[0][2].nseq
+    return emb[:parts[0][3]], emb[s1:s1 + parts[1][3]]
+
+
 RAG_GROUPS = (("generator", "generator_input_input_ids", "generator_input_attention_mask", True),
               ("retriever_query", "retriever_query_input_ids", "retriever_query_attention_mask", False),
               ("retriever_passage", "retriever_passage_input_ids", "retriever_passage_attention_mask", False))
 RETRIEVER_GROUPS = (("query", "query_input_ids", "query_attention_mask", False),
                     ("passage", "passage_input_ids", "passage_attention_mask", False))
+# the same inputs with a causal-LM retriever: a fifth field, `last_column` (the pooled column stays in the plan)
+RAG_GROUPS_CAUSAL = (RAG_GROUPS[0],) + tuple(g + (True,) for g in RAG_GROUPS[1:])
+RETRIEVER_GROUPS_CAUSAL = tuple(g + (True,) for g in RETRIEVER_GROUPS)
 
 
 def add_pack_plans(batch: dict, groups=RAG_GROUPS, multiple=None, device=None) -> dict:
@@ -230,11 +293,14 @@ def add_pack_plans(batch: dict, groups=RAG_GROUPS, multiple=None, device=None) -
     out = dict(batch)
     if multiple is None:
         multiple = ROW_MULTIPLES
-    for prefix, _ids, mask_key, shifted in groups:
+    for prefix, _ids, mask_key, shifted, *last_column in groups:
         if mask_key not in batch:
             continue
-        rows, cu = pack_plan(batch[mask_key], shifted, multiple.get(prefix, PACK_MULTIPLE) if isinstance(multiple, dict) else int(multiple))
+        rows, cu = pack_plan(batch[mask_key], shifted, multiple.get(prefix, PACK_MULTIPLE) if isinstance(multiple, dict) else int(multiple),
+                             last_column=bool(last_column and last_column[0]))
         dev = device if device is not None else batch[mask_key].device
         out[f"{prefix}_pack_rows"] = rows.to(dev)
         out[f"{prefix}_pack_cu"] = cu.to(dev)
+        if last_column and last_column[0]:
+            out[f"{prefix}_{LAST_COLUMN_KEY}"] = torch.empty(0, dtype=torch.uint8, device=dev)
     return out

@@ -65,7 +65,7 @@ class ShardedBatches:
         shapes then vary from batch to batch; loss-preserving, see shards.py).
         live_rows: dict(mask=<generator attention-mask column>, multiple=<row granularity>) - every batch also carries
         `generator_live_rows` (fused.live_row_index of the host copy of that mask) for the fused lm_head path.
-        pack: dict(groups=<packed.RAG_GROUPS / RETRIEVER_GROUPS>, multiple={prefix: rows}) - every batch also carries the
+        pack: dict(groups=<packed.RAG_GROUPS / RETRIEVER_GROUPS, or their _CAUSAL forms for a causal-LM retriever>, multiple={prefix: rows}) - every batch also carries the
         packed row lists of its towers (`<prefix>_pack_rows` / `<prefix>_pack_cu`, dalm_amd/packed.py: the towers then run
         on the live tokens only; same loss and gradients)."""
         self.B, self.rank, self.world, self.seed = batch_size, rank, world, seed
@@ -170,16 +170,19 @@ class ShardedBatches:
         on the copy stream with the batch."""
         if not self.pack:
             return
-        from ..packed import PACK_MULTIPLE, pack_plan
+        from ..packed import LAST_COLUMN_KEY, PACK_MULTIPLE, pack_plan
 
         mult = self.pack.get("multiple", {})
-        for prefix, _ids, mask_key, shifted in self.pack["groups"]:
+        for prefix, _ids, mask_key, shifted, *last_column in self.pack["groups"]:     # a fifth field: packed.*_GROUPS_CAUSAL
             if mask_key not in host:
                 continue
-            rows, cu = pack_plan(host[mask_key], shifted, int(mult.get(prefix, PACK_MULTIPLE)))
+            rows, cu = pack_plan(host[mask_key], shifted, int(mult.get(prefix, PACK_MULTIPLE)),
+                                 last_column=bool(last_column and last_column[0]))
             if device.type == "cuda":
                 rows, cu = rows.pin_memory().to(device, non_blocking=True), cu.pin_memory().to(device, non_blocking=True)
             dev[f"{prefix}_pack_rows"], dev[f"{prefix}_pack_cu"] = rows, cu
+            if last_column and last_column[0]:          # marks the plan's mode for the steps
+                dev[f"{prefix}_{LAST_COLUMN_KEY}"] = torch.empty(0, dtype=torch.uint8, device=device)
 
     def epoch(self, epoch: int, device: torch.device, skip: int = 0) -> Iterable[Dict[str, torch.Tensor]]:
         g = torch.Generator().manual_seed(self.seed + epoch)

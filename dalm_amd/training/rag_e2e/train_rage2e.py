@@ -194,7 +194,9 @@ def train_e2e(
         # coarse row multiples: the packed row counts are part of a hipGraph's shape (one graph per combination seen)
         from ... import packed as packed_mod
 
-        pack = dict(groups=packed_mod.RAG_GROUPS, multiple=packed_mod.ROW_MULTIPLES)
+        # a causal-LM retriever pools column T - 1: its two plans keep that column (packed.pack_plan, last_column)
+        pack = dict(groups=packed_mod.RAG_GROUPS_CAUSAL if retriever_is_autoregressive else packed_mod.RAG_GROUPS,
+                    multiple=packed_mod.ROW_MULTIPLES)
         live_rows = None          # the packed generator path lists its own rows
     batches = common.ShardedBatches(processed, per_device_train_batch_size, comm.rank, comm.world_size,
                                     seed if seed is not None else 0, columns,

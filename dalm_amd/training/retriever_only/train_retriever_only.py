@@ -147,10 +147,12 @@ def train_retriever(
     trim = dict(groups=[("query_input_ids", "query_attention_mask"), ("passage_input_ids", "passage_attention_mask")]) \
         if trim_padding else None
     pack = None
-    if pack_tokens and not is_autoregressive:
+    if pack_tokens:
         from ... import packed as packed_mod
 
-        pack = dict(groups=packed_mod.RETRIEVER_GROUPS, multiple=packed_mod.ROW_MULTIPLES)
+        # a causal-LM retriever pools column T - 1: its plans keep that column (packed.pack_plan, last_column)
+        pack = dict(groups=packed_mod.RETRIEVER_GROUPS_CAUSAL if is_autoregressive else packed_mod.RETRIEVER_GROUPS,
+                    multiple=packed_mod.ROW_MULTIPLES)
     batches = common.ShardedBatches(processed, per_device_train_batch_size, comm.rank, comm.world_size,
                                     seed if seed is not None else 0, columns,
                                     bucket_by="passage_attention_mask" if length_bucketing else None, trim=trim,

@@ -94,13 +94,43 @@ class _StepBase:
         enc = getattr(m, "retriever_model", None) or getattr(m, "model", None)
         if (not isinstance(self.comm, LocalComm)
                 or f"{q_prefix}_pack_rows" not in batch or f"{p_prefix}_pack_rows" not in batch
-                or getattr(m, "retriever_is_autoregressive", getattr(m, "is_autoregressive", False))
-                or not _packed.attention_is_packable(enc)):
+                or not self._retriever_packable(enc, batch, q_prefix) or not self._retriever_packable(enc, batch, p_prefix)):
             return None
         q = (batch[f"{q_prefix}_input_ids"], batch[f"{q_prefix}_attention_mask"], batch[f"{q_prefix}_pack_rows"], batch[f"{q_prefix}_pack_cu"])
         p = (batch[f"{p_prefix}_input_ids"], batch[f"{p_prefix}_attention_mask"], batch[f"{p_prefix}_pack_rows"], batch[f"{p_prefix}_pack_cu"])
+        if self._causal_retriever():                  # row lists of a `last_column` plan: decoder stack + last-token pool
+            return _packed.causal_retrieval_embed_pair(enc, p, q, m.normalize)
         hp, hq = _packed.retrieval_hidden_pair(enc, p, q)
         return pool_l2norm(hp, p[1], m.normalize), pool_l2norm(hq, q[1], m.normalize)
+
+    def _causal_retriever(self) -> bool:
+        m = self.model
+        return bool(getattr(m, "retriever_is_autoregressive", getattr(m, "is_autoregressive", False)))
+
+    def _retriever_packable(self, enc, batch, prefix: str) -> bool:
+        """The retriever can run on the packed rows of input `prefix`: it reads the descriptor (`attention_is_packable`); a causal
+        LM must be one whose decoder stack is called directly, and its row lists must keep the pooled column (a `last_column`
+        plan, packed.*_GROUPS_CAUSAL, which leaves the marker key) - a plan of the live tokens alone goes the padded way."""
+        from ..models.rag_e2e_base_model import decoder_only
+
+        if not _packed.attention_is_packable(enc):
+            return False
+        return not self._causal_retriever() or (decoder_only(enc, int(batch[f"{prefix}_input_ids"].shape[1]))
+                                                and f"{prefix}_{_packed.LAST_COLUMN_KEY}" in batch)
+
+    def _embed_one(self, enc, batch, prefix: str, padded_call):
+        """One retriever input; packed when the batch carries its row list and the model allows it, else `padded_call(ids, mask)`
+        under its row liveness."""
+        m = self.model
+        causal = self._causal_retriever()
+        ids, mask = batch[f"{prefix}_input_ids"], batch[f"{prefix}_attention_mask"]
+        rows, cu = batch.get(f"{prefix}_pack_rows"), batch.get(f"{prefix}_pack_cu")
+        if rows is not None and self._retriever_packable(enc, batch, prefix):
+            if causal:
+                return _packed.causal_retrieval_embed(enc, ids, mask, rows, cu, m.normalize)
+            return pool_l2norm(_packed.retrieval_hidden(enc, ids, mask, rows, cu), mask, m.normalize)
+        with _live_rows.tower_call(mask, False, self.skip_dead_rows, last_column=causal):
+            return padded_call(ids, mask)
 
     def _beside(self, on_tower, on_main, main_first: bool = False):
         """Run `on_tower()` on the tower stream beside `on_main()` on the current stream (`main_first`: enqueue `on_main` first);
@@ -215,14 +245,7 @@ class RagE2EStep(_StepBase):
         `_pack_cu`, dalm_amd/packed.py) - same embeddings, the padding never enters the encoder."""
         if towers is not None:
             return getattr(towers, side)(*towers.args(batch, side))
-        m = self.model
-        ids, mask = batch[f"retriever_{side}_input_ids"], batch[f"retriever_{side}_attention_mask"]
-        rows = batch.get(f"retriever_{side}_pack_rows")
-        if rows is not None and not m.retriever_is_autoregressive and _packed.attention_is_packable(m.retriever_model):
-            h = _packed.retrieval_hidden(m.retriever_model, ids, mask, rows, batch[f"retriever_{side}_pack_cu"])
-            return pool_l2norm(h, mask, m.normalize)
-        with _live_rows.tower_call(mask, False, self.skip_dead_rows):
-            return m("retrieval", ids, mask)
+        return self._embed_one(self.model.retriever_model, batch, f"retriever_{side}", lambda ids, mask: self.model("retrieval", ids, mask))
 
     def _towers(self, batch, towers: Optional[GraphedTowers]):
         pair = self._retrieve_pair(batch, "retriever_query", "retriever_passage") if towers is None else None
@@ -328,14 +351,7 @@ class RetrieverStep(_StepBase):
         graphed encoders when the call has a set."""
         if self.towers is not None:
             return getattr(self.towers, side)(batch[f"{side}_input_ids"], batch[f"{side}_attention_mask"])
-        m = self.model
-        ids, mask = batch[f"{side}_input_ids"], batch[f"{side}_attention_mask"]
-        rows = batch.get(f"{side}_pack_rows")
-        if rows is not None and not getattr(m, "is_autoregressive", False) and _packed.attention_is_packable(m.model):
-            h = _packed.retrieval_hidden(m.model, ids, mask, rows, batch[f"{side}_pack_cu"])
-            return pool_l2norm(h, mask, m.normalize)
-        with _live_rows.tower_call(mask, False, self.skip_dead_rows):
-            return m(ids, mask)
+        return self._embed_one(self.model.model, batch, side, self.model)
 
     def _embed_gather(self, batch, side: str):
         emb = self._embed(batch, side)

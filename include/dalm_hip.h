@@ -80,6 +80,21 @@ int dalm_pool_l2norm_fwd_ws(const void* h, int dtype, const int64_t* mask,
 int dalm_pool_l2norm_packed_fwd(const void* h, int dtype, const int32_t* cu, int64_t n, int64_t nseq,
                                 int64_t nseq_out, int64_t D, float* emb, int64_t ld_emb, float* norm,
                                 float* inv_count, dalm_stream_t stream);
+/* Last-token pooling (+ L2 normalise) from packed rows - causal-LM retrievers, whose embedding is the state of the last column
+ * (dalm/models/retriever_only_base_model.py:43-63): h [n,D] contiguous (dtype) holds token rows, cu int32 [nseq+1] sequence starts.
+ *   u_s = h[cu[s+1]-1]   (an empty sequence: zero row, norm 0);   e_s = normalize ? u_s / max(|u_s|, 1e-12) : u_s
+ * written as f32 at emb + s*ld_emb for s < nseq_out <= nseq; norm [nseq_out] f32 (|u_s|) feeds the backward (may be NULL when no
+ * backward follows).  All arithmetic in f32.  D: a multiple of 16 bytes of dtype, at most 8192 (DALM_E_SHAPE, as nseq_out > nseq or a
+ * leading dimension < D); h / dh / emb / d_emb 16-byte aligned and the leading dimensions multiples of 4 (DALM_E_ALIGN).  The checks
+ * run before anything is enqueued. */
+int dalm_pool_last_packed_fwd(const void* h, int dtype, const int32_t* cu, int64_t n, int64_t nseq, int64_t nseq_out,
+                              int64_t D, int normalize, float* emb, int64_t ld_emb, float* norm, dalm_stream_t stream);
+/* dh [n,D] (dtype) is FULLY written by this one launch (no atomics, no memset, no workspace): zeros everywhere except row
+ * cu[s+1]-1 of every non-empty sequence s < nseq_out, which gets du_s = normalize ? (d_e - e (e . d_e)) / max(norm, 1e-12) : d_e
+ * (norm < 1e-12: d_e / 1e-12, as dalm_pool_l2norm_bwd).  nseq_out == 0: dh is all zeros; d_emb / emb / norm may be NULL. */
+int dalm_pool_last_packed_bwd(const float* d_emb, int64_t ld_demb, const float* emb, int64_t ld_emb, const float* norm,
+                              const int32_t* cu, int64_t n, int64_t nseq, int64_t nseq_out, int64_t D, int normalize,
+                              void* dh, int dtype, dalm_stream_t stream);
 /* dh: [B,T,D] (dtype) is fully written (zeros where mask == 0). */
 int dalm_pool_l2norm_bwd(const float* d_emb, const float* emb, const float* norm,
                          const float* inv_count, const int64_t* mask,

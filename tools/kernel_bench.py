@@ -268,6 +268,31 @@ def bench_tower(B, T, H, hd, inter, dtype):
     return out
 
 
+def bench_pool_last(B, T, D, dtype):
+    """Last-token pooling from packed rows next to the padded pool's backward on the same batch: B sequences of T rows
+    (n = B T), and the one-token mask of `eos_mask` for `dalm_pool_l2norm_bwd`.  Bytes the kernel has to move: forward reads
+    nseq x D elements and writes nseq x D f32, backward writes n x D elements."""
+    ops = default_ops()
+    dev = torch.device("cuda:0")
+    n, el = B * T, torch.empty((), dtype=dtype).element_size()
+    h = torch.randn(n, D, device=dev, dtype=dtype)
+    cu = torch.arange(0, n + 1, T, dtype=torch.int32, device=dev)
+    out = {}
+    med, _ = time_graph(lambda: ops.pool_last_packed_fwd(h, cu, B, True))
+    by = B * D * (el + 4)
+    out["last fwd"] = {"s": med, "GBps": by / med / 1e9, "frac": by / med / HBM_PEAK}
+    emb, norm = ops.pool_last_packed_fwd(h, cu, B, True)
+    de = torch.randn_like(emb)
+    med, _ = time_graph(lambda: ops.pool_last_packed_bwd(de, emb, norm, cu, n, True, dtype))
+    out["last bwd"] = {"s": med, "GBps": n * D * el / med / 1e9, "frac": n * D * el / med / HBM_PEAK}
+    mask = torch.zeros(B, T, dtype=torch.int64, device=dev)
+    mask[:, -1] = 1
+    e2, n2, ic = ops.pool_fwd(h.view(B, T, D), mask, True)
+    med, _ = time_graph(lambda: ops.pool_bwd(de, e2, n2, ic, mask, True, T, dtype))
+    out["l2norm bwd"] = {"s": med, "GBps": n * D * el / med / 1e9, "frac": n * D * el / med / HBM_PEAK}
+    return out
+
+
 def print_results(res) -> None:
     for k, v in res.items():
         print(k)
@@ -320,6 +345,12 @@ def main():
         res["pool cfg2 p B150 T128 D1024 f32"] = bench_pool(150, 128, 1024, torch.float32)
         res["pool cfg3 p B18 T128 D1024 f32"] = bench_pool(18, 128, 1024, torch.float32)
         res["pool B1200 T128 D1024 bf16"] = bench_pool(1200, 128, 1024, torch.bfloat16)
+    if args.only in ("", "pool", "pool_last"):
+        res["pool_last B150 T128 D1024 bf16"] = bench_pool_last(150, 128, 1024, torch.bfloat16)
+        res["pool_last B150 T128 D4096 bf16"] = bench_pool_last(150, 128, 4096, torch.bfloat16)
+        res["pool_last B150 T50 D4096 bf16"] = bench_pool_last(150, 50, 4096, torch.bfloat16)
+        res["pool_last B150 T128 D4096 f32"] = bench_pool_last(150, 128, 4096, torch.float32)
+        res["pool_last B18 T128 D4096 bf16"] = bench_pool_last(18, 128, 4096, torch.bfloat16)
     if args.only in ("", "nf4"):
         res["nf4 11008x4096 -> bf16"] = bench_nf4(11008, 4096, torch.bfloat16)
         res["nf4 4096x4096 -> bf16"] = bench_nf4(4096, 4096, torch.bfloat16)
