@@ -699,3 +699,212 @@ extern "C" int dalm_rms_norm_bwd(const void* dy, const void* h, const void* w, c
                                  int64_t R, int64_t D, void* dx, dalm_stream_t stream) {
   return dalm_rms_norm_bwd_live(dy, h, w, rstd, dres, dtype, R, D, dx, nullptr, stream);
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Qwen3: RMSNorm over the HEAD dimension of q and of k (q_norm / k_norm, one weight [hd] for all heads) followed by the rotary
+// embedding, one launch for q and k; and the backward of the norm alone (the rotation's backward is in dalm_attn_bwd's
+// epilogues).  transformers runs Qwen3RMSNorm x 2 and apply_rotary_pos_emb as ~12 eager launches forward (modeling_qwen3.py).
+// A head row of hd bf16 is hd / 8 sixteen-byte accesses: a GROUP of 16 (hd 128) or 8 (hd 64) adjacent lanes holds it, a wave
+// 4 or 8 head rows, rows walked head-fastest like rope_qk_kernel (q's rows first, then k's).  The mean is an xor-shuffle reduction inside the group; the
+// rotary partner of a lane's 8 elements (hd / 2 columns away) sits in lane ^ (group / 2).  Every lane of a wave runs the
+// shuffles - a group past the last row or of a dead (b, t) carries zeros, loads nothing and (in range) stores zeros.
+//   forward :  rstd = rsqrt(mean(x^2) + eps)   xh = rb(x rstd)   y = rb(w xh)   out = rope forward of y (rounding as above)
+//   backward:  gw = g w;  xh = x rstd (f32);  dx = rb(rstd (gw - xh mean(gw xh)))     - dalm_rms_norm_bwd's arithmetic
+// Algorithmic bytes: forward 2 (|q| + |k|) el + rstd, backward 3 (|q| + |k|) el + rstd (+ cos / sin / w, shared).
+// ---------------------------------------------------------------------------------------------------
+namespace {
+
+struct HeadNormTensor {
+  const void* x;                 // pre-norm projection output, [B, H, T, hd] view
+  const void* g;                 // backward: gradient of the normed, un-rotated value
+  void* o;                       // forward: normed + rotated; backward: gradient of x
+  const void* w;                 // [hd]
+  float* rstd;                   // [B, T, H] f32: written by the forward, read by the backward
+  int64_t xs[3], gs[3], os[3];   // element strides of (b, h, t)
+  float eps;
+};
+struct HeadNormParams {
+  HeadNormTensor q, k;
+  const void* cos; const void* sin; int64_t cs[2];   // strides of (b, t); forward only
+  int B, T, Hq, Hk;
+  unsigned q_blocks;                                 // workgroups that serve q; the rest serve k
+  const unsigned char* live;                         // [B * T] or NULL
+};
+
+template <int G>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+  for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// where lane `gid` works: head row -> (b, t, head of q or k); `in`: the row exists, `act`: and its (b, t) is live.  Workgroups
+// [0, q_blocks) walk the head rows of q, the rest those of k: which tensor a workgroup serves is uniform, so its pointers and
+// strides are chosen by scalar selects (a per-lane choice between the two sets cost the first form ~60 VALU operations a lane)
+struct HeadRow { bool in, act, is_k; int b, t, head, c; unsigned bt, row; };
+template <int G>
+__device__ __forceinline__ HeadRow head_row(const HeadNormParams& p) {
+  HeadRow r;
+  r.is_k = blockIdx.x >= p.q_blocks;
+  const unsigned H = static_cast<unsigned>(r.is_k ? p.Hk : p.Hq);
+  const unsigned gid = (r.is_k ? blockIdx.x - p.q_blocks : blockIdx.x) * 256u + threadIdx.x;   // the launcher keeps rows * G below 2^31
+  const unsigned row = gid / G;
+  r.c = static_cast<int>(gid % G) * 8;
+  r.in = row < static_cast<unsigned>(p.B) * p.T * H;
+  r.row = r.in ? row : 0u;                                  // also the index into rstd [B, T, H]
+  r.head = static_cast<int>(r.row % H);
+  r.bt = r.row / H;
+  r.t = static_cast<int>(r.bt % p.T); r.b = static_cast<int>(r.bt / p.T);
+  r.act = r.in && (!p.live || p.live[r.bt]);
+  return r;
+}
+__device__ __forceinline__ int64_t head_at(const HeadRow& r, const int64_t (&s)[3]) {
+  return r.b * s[0] + r.head * s[1] + r.t * s[2] + r.c;
+}
+
+template <int HD>
+__global__ __launch_bounds__(256) void head_norm_rope_fwd_kernel(const HeadNormParams p) {
+#pragma clang fp contract(off)   // the eager chain is separate mul and add kernels (see rope_qk_kernel)
+  using V = Vec16<bf16_t>;
+  constexpr int G = HD / 8;
+  const HeadRow r = head_row<G>(p);
+  const HeadNormTensor& R = r.is_k ? p.k : p.q;
+  float x[8], w[8], cs[8], sn[8], y[8], o[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) x[e] = w[e] = cs[e] = sn[e] = 0.f;
+  if (r.act) {                                   // every load of the row in flight before the reduction
+    const int64_t ca = r.b * p.cs[0] + r.t * p.cs[1] + r.c;
+    V::load(static_cast<const bf16_t*>(R.x) + head_at(r, R.xs), x);
+    V::load(static_cast<const bf16_t*>(R.w) + r.c, w);
+    V::load(static_cast<const bf16_t*>(p.cos) + ca, cs);
+    V::load(static_cast<const bf16_t*>(p.sin) + ca, sn);
+  }
+  float ss = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) ss = fmaf(x[e], x[e], ss);
+  ss = group_sum<G>(ss);
+  const float rstd = r.act ? rsqrtf(ss / static_cast<float>(HD) + R.eps) : 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) y[e] = V::rb(w[e] * V::rb(x[e] * rstd));
+  // the other half of the head row: y is exact in bf16, so it travels as four packed words
+  const uint4 mine = enc8(y);
+  float z[8];
+  dec8(make_uint4(__shfl_xor(mine.x, G / 2, 64), __shfl_xor(mine.y, G / 2, 64), __shfl_xor(mine.z, G / 2, 64),
+                  __shfl_xor(mine.w, G / 2, 64)), z);
+  const bool second = r.c >= HD / 2;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float a = V::rb(y[e] * cs[e]), b = V::rb(z[e] * sn[e]);
+    o[e] = V::rb(second ? a + b : a - b);
+  }
+  if (!r.in) return;
+  V::store(static_cast<bf16_t*>(R.o) + head_at(r, R.os), o);                     // a dead row: zeros
+  if (r.c == 0) R.rstd[r.row] = rstd;
+}
+
+template <int HD>
+__global__ __launch_bounds__(256) void head_norm_bwd_kernel(const HeadNormParams p) {
+  using V = Vec16<bf16_t>;
+  constexpr int G = HD / 8;
+  const HeadRow r = head_row<G>(p);
+  const HeadNormTensor& R = r.is_k ? p.k : p.q;
+  float g[8], xh[8], w[8], o[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) g[e] = xh[e] = w[e] = 0.f;
+  float rstd = 0.f;
+  if (r.act) {
+    V::load(static_cast<const bf16_t*>(R.g) + head_at(r, R.gs), g);
+    V::load(static_cast<const bf16_t*>(R.x) + head_at(r, R.xs), xh);
+    V::load(static_cast<const bf16_t*>(R.w) + r.c, w);
+    rstd = R.rstd[r.row];
+  }
+  float dot = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    g[e] *= w[e];
+    xh[e] *= rstd;
+    dot = fmaf(g[e], xh[e], dot);
+  }
+  dot = group_sum<G>(dot) / static_cast<float>(HD);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = rstd * (g[e] - xh[e] * dot);
+  if (!r.in) return;
+  V::store(static_cast<bf16_t*>(R.o) + head_at(r, R.os), o);                     // rounded once; a dead row: zeros
+}
+
+// the checks the two entry points share; fills B, T, Hq, Hk and the grid
+int head_norm_shape(const char* fn, int64_t B, int64_t T, int64_t Hq, int64_t Hk, int64_t hd, HeadNormParams& p, dim3& grid) {
+  if (!(hd == 64 || hd == 128)) return fail(DALM_E_SHAPE, fn, "head width must be 64 or 128");
+  if (!(B > 0 && T > 0 && Hq > 0 && Hk > 0 && Hq + Hk <= 65535)) return fail(DALM_E_SHAPE, fn, "need B, T, Hq, Hk > 0");
+  if (!(B <= 0x7fffffffLL && T <= 0x7fffffffLL && B * T <= 0x7fffffffLL && B * T * (Hq + Hk) * (hd / 8) <= 0x7fffffffLL))
+    return fail(DALM_E_SHAPE, fn, "tensor too large for one launch");
+  p.B = static_cast<int>(B); p.T = static_cast<int>(T); p.Hq = static_cast<int>(Hq); p.Hk = static_cast<int>(Hk);
+  const int64_t qb = (B * T * Hq * (hd / 8) + 255) / 256, kb = (B * T * Hk * (hd / 8) + 255) / 256;
+  p.q_blocks = static_cast<unsigned>(qb);
+  grid = dim3(static_cast<unsigned>(qb + kb));
+  return 0;
+}
+bool strides_mult8(const int64_t* s, int n) {
+  for (int i = 0; i < n; ++i)
+    if (s[i] % 8 != 0) return false;
+  return true;
+}
+
+}  // namespace
+
+extern "C" int dalm_head_norm_rope_fwd(const void* q, const void* k, const void* wq, const void* wk, float eps_q, float eps_k,
+                                       const void* cos, const void* sin, int64_t B, int64_t T, int64_t Hq, int64_t Hk, int64_t hd,
+                                       const int64_t* q_strides, const int64_t* k_strides, const int64_t* qo_strides,
+                                       const int64_t* ko_strides, const int64_t* cs_strides, void* q_out, void* k_out,
+                                       float* rstd_q, float* rstd_k, const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(q && k && wq && wk && cos && sin && q_strides && k_strides && qo_strides && ko_strides && cs_strides && q_out && k_out
+                   && rstd_q && rstd_k, DALM_E_NULL, "null pointer argument");
+  HeadNormParams p;
+  dim3 grid;
+  if (const int rc = head_norm_shape(__func__, B, T, Hq, Hk, hd, p, grid)) return rc;
+  DALM_REQUIRE(aligned16(q, k, wq, wk, cos, sin, q_out, k_out) && reinterpret_cast<uintptr_t>(rstd_q) % 4 == 0
+                   && reinterpret_cast<uintptr_t>(rstd_k) % 4 == 0 && strides_mult8(q_strides, 3) && strides_mult8(k_strides, 3)
+                   && strides_mult8(qo_strides, 3) && strides_mult8(ko_strides, 3) && strides_mult8(cs_strides, 2),
+               DALM_E_ALIGN, "tensors must be 16-byte aligned and every stride a multiple of 8 elements");
+  p.q.x = q; p.q.g = nullptr; p.q.o = q_out; p.q.w = wq; p.q.rstd = rstd_q; p.q.eps = eps_q;
+  p.k.x = k; p.k.g = nullptr; p.k.o = k_out; p.k.w = wk; p.k.rstd = rstd_k; p.k.eps = eps_k;
+  for (int i = 0; i < 3; ++i) {
+    p.q.xs[i] = q_strides[i]; p.q.os[i] = qo_strides[i]; p.q.gs[i] = 0;
+    p.k.xs[i] = k_strides[i]; p.k.os[i] = ko_strides[i]; p.k.gs[i] = 0;
+  }
+  p.cos = cos; p.sin = sin; p.cs[0] = cs_strides[0]; p.cs[1] = cs_strides[1];
+  p.live = row_live;
+  by_exact<64, 128>(static_cast<int>(hd), [&](auto width) {
+    hipLaunchKernelGGL((head_norm_rope_fwd_kernel<width>), grid, dim3(256), 0, as_stream(stream), p);
+  });
+  return check_launch(__func__);
+}
+
+extern "C" int dalm_head_norm_bwd(const void* gq, const void* gk, const void* q, const void* k, const void* wq, const void* wk,
+                                  const float* rstd_q, const float* rstd_k, int64_t B, int64_t T, int64_t Hq, int64_t Hk, int64_t hd,
+                                  const int64_t* gq_strides, const int64_t* gk_strides, const int64_t* q_strides,
+                                  const int64_t* k_strides, const int64_t* dq_strides, const int64_t* dk_strides, void* dq, void* dk,
+                                  const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(gq && gk && q && k && wq && wk && rstd_q && rstd_k && gq_strides && gk_strides && q_strides && k_strides && dq_strides
+                   && dk_strides && dq && dk, DALM_E_NULL, "null pointer argument");
+  HeadNormParams p;
+  dim3 grid;
+  if (const int rc = head_norm_shape(__func__, B, T, Hq, Hk, hd, p, grid)) return rc;
+  DALM_REQUIRE(aligned16(gq, gk, q, k, wq, wk, dq, dk) && reinterpret_cast<uintptr_t>(rstd_q) % 4 == 0
+                   && reinterpret_cast<uintptr_t>(rstd_k) % 4 == 0 && strides_mult8(gq_strides, 3) && strides_mult8(gk_strides, 3)
+                   && strides_mult8(q_strides, 3) && strides_mult8(k_strides, 3) && strides_mult8(dq_strides, 3)
+                   && strides_mult8(dk_strides, 3),
+               DALM_E_ALIGN, "tensors must be 16-byte aligned and every stride a multiple of 8 elements");
+  p.q.x = q; p.q.g = gq; p.q.o = dq; p.q.w = wq; p.q.rstd = const_cast<float*>(rstd_q); p.q.eps = 0.f;
+  p.k.x = k; p.k.g = gk; p.k.o = dk; p.k.w = wk; p.k.rstd = const_cast<float*>(rstd_k); p.k.eps = 0.f;
+  for (int i = 0; i < 3; ++i) {
+    p.q.xs[i] = q_strides[i]; p.q.gs[i] = gq_strides[i]; p.q.os[i] = dq_strides[i];
+    p.k.xs[i] = k_strides[i]; p.k.gs[i] = gk_strides[i]; p.k.os[i] = dk_strides[i];
+  }
+  p.cos = nullptr; p.sin = nullptr; p.cs[0] = p.cs[1] = 0;
+  p.live = row_live;
+  by_exact<64, 128>(static_cast<int>(hd), [&](auto width) {
+    hipLaunchKernelGGL((head_norm_bwd_kernel<width>), grid, dim3(256), 0, as_stream(stream), p);
+  });
+  return check_launch(__func__);
+}

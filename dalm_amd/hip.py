@@ -147,6 +147,11 @@ SIGNATURES = {
     "dalm_swiglu_bwd_2d_live": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
     "dalm_rms_norm_fwd_live": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp]),
     "dalm_rms_norm_bwd_live": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _vp, _vp, _vp]),
+    # Qwen3's q_norm / k_norm + rotary embedding (forward) and the norm's backward, q and k in one launch each
+    "dalm_head_norm_rope_fwd": (_int, [_vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dalm_head_norm_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _vp, _vp, _vp, _vp]),
     "dalm_bert_add_norm_fwd_live": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _f32, _f32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _vp]),
     "dalm_bert_add_norm_bwd_live": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),

@@ -22,6 +22,8 @@ salt is a host call counter, a re-run forward would draw another mask.
 Grouped-query heads (Llama-3 / Mistral / TinyLlama: k, v with Hkv < H heads) run un-expanded on `dalm_attn_gqa_fwd` /
 `dalm_attn_gqa_bwd` where `grouped_supported` holds: query head h reads KV head h // (H // Hkv), dk / dv come back with Hkv heads,
 summed over each group in f32 inside the kernel.  Elsewhere k / v are expanded by `repeat_kv` first.
+Qwen3 (q_norm / k_norm over the head dimension in front of the rotary embedding) runs norm + rotation + attention as one node,
+`norm_rope_sdpa`; a call that carries a `sliding_window` shorter than the sequence goes to transformers' own function.
 Everything the kernels do not take (CPU tensors, other head widths, odd T with dropout, float masks, a KV cache, no gradient wanted) goes
 to transformers' own `sdpa_attention_forward`, unchanged.  DALM_ATTN_KERNEL=0 keeps the model on "sdpa".
 """
@@ -276,6 +278,46 @@ class _RopeSdpaHip(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None, None
 
 
+class _NormRopeSdpaHip(torch.autograd.Function):
+    """Qwen3: RMSNorm over the head dimension of q and of k + rotary embedding (`dalm_head_norm_rope_fwd`, one launch) + the
+    attention.  Backward: `dalm_attn_bwd` / `dalm_attn_gqa_bwd` un-rotate dq / dk in their epilogues (as for `_RopeSdpaHip`),
+    then `dalm_head_norm_bwd` (one launch) takes them through the two norms.  Equal and grouped heads, padded and packed; one
+    key / value head is not routed here (`supported` / `grouped_supported` decline it).  No host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, wq, wk, eps_q, eps_k, cos, sin, mask, scale, causal):
+        from . import tower_ops
+
+        B, H, T, hd = q.shape
+        # dead (b, t) of a padded tower call leave norm + rotation as zeros (finite values for the attention kernels) and get
+        # zero gradients from the norm's backward
+        q2, k2, rq, rk, live = tower_ops.head_norm_rope(q, k, wq, wk, eps_q, eps_k, cos, sin)
+        pk = _pack(mask, B, H, T, causal, q.dtype, q.device)
+        out, lse = _attn_forward(q2, k2, v, pk, scale, causal)
+        ctx.save_for_backward(q, k, q2, k2, v, out, lse, cos, sin, wq, wk, rq, rk, *([live] if live is not None else []))
+        ctx.pack, ctx.scale = pk, scale
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        from . import tower_ops
+
+        q, k, q2, k2, v, out, lse, cos, sin, wq, wk, rq, rk, *live = ctx.saved_tensors
+        live = live[0] if live else None
+        gq, gk, dv = _attn_backward(q2, k2, v, out, lse, d_out, ctx.pack, ctx.scale, cos, sin)    # of the normed, un-rotated q / k
+        dq, dk = tower_ops.head_norm_bwd(gq, gk, q, k, wq, wk, rq, rk, live)
+        dwq = tower_ops.head_norm_weight_grad(gq, q, rq, live).to(wq.dtype) if ctx.needs_input_grad[3] else None
+        dwk = tower_ops.head_norm_weight_grad(gk, k, rk, live).to(wk.dtype) if ctx.needs_input_grad[4] else None
+        return dq, dk, dv, dwq, dwk, None, None, None, None, None, None, None
+
+
+def norm_rope_sdpa(query, key, value, wq, wk, eps_q: float, eps_k: float, cos, sin, mask, scale: float, causal: bool):
+    """sdpa(apply_rotary_pos_emb(rmsnorm(query) * wq, rmsnorm(key) * wk, cos, sin), value, ...) with the norms over the head
+    dimension (Qwen3's q_norm / k_norm), for what `tower_ops.head_norm_rope_supported`, `rope_fusable` and `supported` /
+    `packed_supported` / `grouped_supported` accept.  The norm weights may require grad."""
+    return _NormRopeSdpaHip.apply(query, key, value, wq, wk, eps_q, eps_k, cos, sin, mask, scale, causal)
+
+
 def rope_fusable(q, k, cos, sin) -> bool:
     """cos / sin tables `dalm_attn_bwd` reads in its epilogues: what `tower_ops.rope_supported` takes, bf16, 16-byte rows."""
     from . import tower_ops
@@ -406,6 +448,10 @@ def dalm_sdpa_attention_forward(module, query, key, value, attention_mask, dropo
     seqs = packed_of(attention_mask)
     if seqs is not None:                     # packed (un-padded) tower call: `attention_mask` is a descriptor, not a mask
         return _packed_attention(module, query, key, value, attention_mask, seqs, dropout, scaling)
+    window = kwargs.get("sliding_window")        # Qwen3 passes the keyword: None unless the layer is a `sliding_attention` one
+    if window is not None and window < key.shape[2]:     # the kernels know no window shorter than the sequence
+        return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling,
+                                      is_causal=is_causal, **kwargs)
     groups = getattr(module, "num_key_value_groups", 1)
     causal = bool(query.shape[2] > 1 and attention_mask is None
                   and (is_causal if is_causal is not None else getattr(module, "is_causal", True)))
@@ -466,7 +512,7 @@ def use_hip_attention_backward(model: torch.nn.Module) -> bool:
     cfg = getattr(model, "config", None)
     if cfg is None or getattr(cfg, "_attn_implementation", None) != "sdpa":
         return False
-    if getattr(cfg, "model_type", "") not in ("llama", "mistral", "qwen2", "bert"):
+    if getattr(cfg, "model_type", "") not in ("llama", "mistral", "qwen2", "qwen3", "bert"):
         return False
     hd = getattr(cfg, "head_dim", None) or (cfg.hidden_size // cfg.num_attention_heads)
     if hd not in _HEAD_DIMS or not register():

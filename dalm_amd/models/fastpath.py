@@ -190,7 +190,7 @@ def use_swiglu_kernel(model: torch.nn.Module) -> int:
         return 0
     n = 0
     for mod in model.modules():
-        if type(mod).__name__ not in ("LlamaMLP", "MistralMLP", "Qwen2MLP"):
+        if type(mod).__name__ not in ("LlamaMLP", "MistralMLP", "Qwen2MLP", "Qwen3MLP"):
             continue
         act = getattr(mod, "act_fn", None)
         if not all(hasattr(mod, a) for a in ("gate_proj", "up_proj", "down_proj")):
@@ -707,13 +707,15 @@ def use_fused_residual_norm(model: torch.nn.Module) -> int:
 
     n = 0
     for mod in model.modules():
-        if type(mod).__name__ != "LlamaDecoderLayer":
+        if type(mod).__name__ not in ("LlamaDecoderLayer", "Qwen3DecoderLayer"):
             continue
         try:
             params = [p if p != "kwargs" else "kwargs" for p in inspect.signature(type(mod).forward).parameters]
         except (TypeError, ValueError):
             continue
         if params != _LLAMA_LAYER_PARAMS:
+            continue
+        if type(mod).__name__ == "Qwen3DecoderLayer" and not _qwen3_layer_matches(type(mod)):
             continue
         ok = True
         for name in ("input_layernorm", "post_attention_layernorm"):
@@ -727,3 +729,135 @@ def use_fused_residual_norm(model: torch.nn.Module) -> int:
         mod.forward = types.MethodType(_llama_layer_forward, mod)
         n += 1
     return n
+
+
+def _qwen3_layer_matches(cls) -> bool:
+    """Qwen3DecoderLayer.forward must be, statement for statement, the LlamaDecoderLayer.forward `_llama_layer_forward` restates."""
+    key = ("qwen3-layer", cls)
+    if key not in _checked:
+        try:
+            import inspect
+
+            src = inspect.getsource(cls.forward)
+            body = [ln.strip() for ln in src.splitlines() if ln.strip() and not ln.strip().startswith("#")]
+            stmts = ["residual = hidden_states", "hidden_states = self.input_layernorm(hidden_states)",
+                     "hidden_states, _ = self.self_attn(", "hidden_states=hidden_states,", "attention_mask=attention_mask,",
+                     "position_ids=position_ids,", "past_key_values=past_key_values,", "use_cache=use_cache,",
+                     "position_embeddings=position_embeddings,", "**kwargs,", ")", "hidden_states = residual + hidden_states",
+                     "residual = hidden_states", "hidden_states = self.post_attention_layernorm(hidden_states)",
+                     "hidden_states = self.mlp(hidden_states)", "hidden_states = residual + hidden_states", "return hidden_states"]
+            _checked[key] = body[-len(stmts):] == stmts and body[-len(stmts) - 1].startswith(")")   # the whole body, behind the signature
+        except Exception:
+            _checked[key] = False
+        if not _checked[key]:
+            _warn_once("qwen3-layer", "Qwen3DecoderLayer.forward is not the code this patch restates: transformers' own code stays "
+                       "in place")
+    return _checked[key]
+
+
+# ---------------------------------------------------------------------------
+# Qwen3 attention: q_norm / k_norm over the head dimension + rotary embedding + attention as ONE autograd node
+# ---------------------------------------------------------------------------
+def _head_norm_ok(norm, hd: int) -> bool:
+    """A Qwen3RMSNorm over the head dimension: w * (x * rsqrt(mean(x^2) + eps)).to(dtype) with a plain weight [hd] - its own forward,
+    or `_native_forward` (`use_native_rms_norm`, the same formula behind its own run-time guard)."""
+    w = getattr(norm, "weight", None)
+    return (type(norm).__name__ == "Qwen3RMSNorm" and w is not None and w.dim() == 1 and w.shape[0] == hd
+            and (hasattr(norm, "variance_epsilon") or hasattr(norm, "_dalm_eps")))
+
+
+def _qwen3_attention_forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
+    """transformers' Qwen3Attention.forward for the training call ("dalm_sdpa", no KV cache, no dropout, no sliding window): the
+    same statements with q_norm + k_norm + apply_rotary_pos_emb + the attention call as `attention.norm_rope_sdpa`.  Every
+    other call goes to transformers' own forward."""
+    from . import attention, tower_ops
+
+    cfg = self.config
+    if (past_key_values is not None or position_embeddings is None or getattr(cfg, "_attn_implementation", None) != attention.NAME
+            or (self.training and float(getattr(self, "attention_dropout", 0.0)) != 0.0)
+            or getattr(self, "sliding_window", None) is not None
+            or _off("DALM_FAST_ROPE") or _off("DALM_ATTN_KERNEL") or kwargs.get("output_attentions")):
+        return self._dalm_orig_attn_forward(hidden_states, position_embeddings=position_embeddings, attention_mask=attention_mask,
+                                            past_key_values=past_key_values, **kwargs)
+    input_shape = hidden_states.shape[:-1]
+    hidden_shape = (*input_shape, -1, self.head_dim)
+    query_raw = self.q_proj(hidden_states).view(hidden_shape)
+    key_raw = self.k_proj(hidden_states).view(hidden_shape)
+    value_states = self.v_proj(hidden_states).view(hidden_shape).transpose(1, 2)
+    cos, sin = position_embeddings
+    q_t, k_t = query_raw.transpose(1, 2), key_raw.transpose(1, 2)          # pre-norm [B, H, T, hd] views
+    causal = bool(q_t.shape[2] > 1 and attention_mask is None and getattr(self, "is_causal", True))
+    qn, kn = self.q_norm, self.k_norm
+    fused = (_head_norm_ok(qn, self.head_dim) and _head_norm_ok(kn, self.head_dim)
+             and tower_ops.head_norm_rope_supported(q_t, k_t, qn.weight, kn.weight, cos, sin)
+             and attention.rope_fusable(q_t, k_t, cos, sin))
+    if fused and attention.packed_of(attention_mask) is not None:
+        fused = (attention.packed_supported(q_t, k_t, value_states)
+                 or attention.grouped_supported(q_t, k_t, value_states, packed=True))
+    elif fused:
+        fused = (attention.supported(q_t, k_t, value_states, attention_mask, 0.0, causal, {})
+                 or attention.grouped_supported(q_t, k_t, value_states, attention_mask, 0.0, causal, {}))
+    if fused:
+        attn_output = attention.norm_rope_sdpa(q_t, k_t, value_states, qn.weight, kn.weight, _norm_eps(qn), _norm_eps(kn), cos, sin,
+                                               attention_mask, float(self.scaling), causal)
+        attn_output = attn_output.transpose(1, 2)
+    else:                                            # CPU tensors, fp32, other head widths, ...: transformers' own sequence from here on
+        import importlib
+
+        from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
+
+        query_states = qn(query_raw).transpose(1, 2)
+        key_states = kn(key_raw).transpose(1, 2)
+        rope = importlib.import_module(type(self).__module__).apply_rotary_pos_emb
+        query_states, key_states = rope(query_states, key_states, cos, sin)
+        attn_output, _ = ALL_ATTENTION_FUNCTIONS[cfg._attn_implementation](
+            self, query_states, key_states, value_states, attention_mask, dropout=0.0, scaling=self.scaling,
+            sliding_window=self.sliding_window, **kwargs)
+    attn_output = attn_output.reshape(*input_shape, -1).contiguous()
+    return self.o_proj(attn_output), None
+
+
+def use_qwen3_attention_node(model: torch.nn.Module) -> int:
+    """Patch Qwen3Attention modules of a model that runs on "dalm_sdpa" (models/attention.py) and whose forward is the code
+    `_qwen3_attention_forward` restates.  Returns the count."""
+    from . import attention
+
+    if getattr(getattr(model, "config", None), "_attn_implementation", None) != attention.NAME:
+        return 0
+    n = 0
+    for mod in model.modules():
+        if type(mod).__name__ != "Qwen3Attention" or not all(hasattr(mod, a) for a in ("q_proj", "k_proj", "v_proj", "o_proj", "q_norm",
+                                                                                         "k_norm", "scaling", "sliding_window")):
+            continue
+        if not _qwen3_attention_matches(type(mod)):
+            continue
+        mod._dalm_orig_attn_forward = mod.forward
+        mod.forward = types.MethodType(_qwen3_attention_forward, mod)
+        n += 1
+    return n
+
+
+def _qwen3_attention_matches(cls) -> bool:
+    key = ("qwen3-attn", cls)
+    if key not in _checked:
+        try:
+            import inspect
+
+            params = list(inspect.signature(cls.forward).parameters)
+            src = inspect.getsource(cls.forward)
+            _checked[key] = (params == _LLAMA_ATTN_PARAMS
+                             and "query_states = self.q_norm(self.q_proj(hidden_states).view(hidden_shape)).transpose(1, 2)" in src
+                             and "key_states = self.k_norm(self.k_proj(hidden_states).view(hidden_shape)).transpose(1, 2)" in src
+                             and "value_states = self.v_proj(hidden_states).view(hidden_shape).transpose(1, 2)" in src
+                             and "query_states, key_states = apply_rotary_pos_emb(query_states, key_states, cos, sin)" in src
+                             and "dropout=0.0 if not self.training else self.attention_dropout" in src
+                             and "scaling=self.scaling" in src
+                             and "sliding_window=self.sliding_window" in src
+                             and "attn_output = attn_output.reshape(*input_shape, -1).contiguous()" in src
+                             and "attn_output = self.o_proj(attn_output)" in src)
+        except Exception:
+            _checked[key] = False
+        if not _checked[key]:
+            _warn_once("qwen3-attn:" + cls.__name__, f"{cls.__name__}.forward is not the code this patch restates: transformers' own "
+                       "code stays in place")
+    return _checked[key]

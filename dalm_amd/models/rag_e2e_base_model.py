@@ -16,7 +16,8 @@ from ..utils import eos_mask
 from . import lora
 from .attention import use_hip_attention_backward
 from .fastpath import (use_bert_layer_kernels, use_capturable_falcon_heads, use_falcon_attention_kernels, use_falcon_layer_kernels,
-                       use_fused_residual_norm, use_llama_attention_node, use_native_rms_norm, use_roll_rope, use_swiglu_kernel)
+                       use_fused_residual_norm, use_llama_attention_node, use_native_rms_norm, use_qwen3_attention_node, use_roll_rope,
+                       use_swiglu_kernel)
 
 
 class Mode(Enum):
@@ -65,12 +66,12 @@ def to_nf4(model: torch.nn.Module) -> torch.nn.Module:
 
 # causal-LM retrievers whose decoder stack the PACKED route calls directly (dalm_amd/packed.py): `lm.base_model` returns the
 # final (normed) states that `hidden_states[-1]` of the `*ForCausalLM` call holds, bit for bit.  Any other type is not packed.
-DECODER_ONLY_TYPES = ("llama", "mistral", "qwen2")
+DECODER_ONLY_TYPES = ("llama", "mistral", "qwen2", "qwen3")
 
 
 def _sliding_window(cfg):
     """The attention window of a config when any layer uses one (mistral: `sliding_window`; qwen2: only with
-    `use_sliding_window`), else None."""
+    `use_sliding_window`; qwen3: only with a `sliding_attention` entry in `layer_types`), else None."""
     if getattr(cfg, "use_sliding_window", True) is False:
         return None
     if "sliding_attention" not in (getattr(cfg, "layer_types", None) or ["sliding_attention"]):
@@ -91,9 +92,10 @@ def decoder_only(lm, T: Optional[int] = None) -> bool:
 
 def use_causal_retriever_fast_paths(lm) -> None:
     """The generator's row-wise layer nodes on a causal-LM retriever (each has its own guards and leaves other models alone):
-    native RMSNorm, roll-rope, SwiGLU, fused residual + norm, "dalm_sdpa".  Roll-rope and fused residual + norm patch Llama's
-    modeling code only: on mistral / qwen2 they do nothing.  The rotary + attention node (`use_llama_attention_node`) is not
-    applied to retrievers, rotary and attention run as two nodes there: DESIGN.md section 5.3 says why."""
+    native RMSNorm, roll-rope, SwiGLU, fused residual + norm, "dalm_sdpa".  Roll-rope patches Llama's modeling code only and
+    fused residual + norm Llama's and Qwen3's: on mistral / qwen2 they do nothing.  The rotary + attention nodes
+    (`use_llama_attention_node`, `use_qwen3_attention_node`) are not applied to retrievers: rotary and attention - and a Qwen3
+    layer's q_norm / k_norm - run as separate nodes there: DESIGN.md section 5.3 says why."""
     use_native_rms_norm(lm)
     use_roll_rope(lm)
     use_swiglu_kernel(lm)
@@ -159,6 +161,7 @@ class AutoModelForRagE2E(torch.nn.Module):
         use_falcon_attention_kernels(self.generator_model)
         use_hip_attention_backward(self.generator_model)
         use_llama_attention_node(self.generator_model)
+        use_qwen3_attention_node(self.generator_model)
         if autoregressive:
             use_causal_retriever_fast_paths(self.retriever_model)
         else:

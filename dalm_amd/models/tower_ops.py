@@ -235,6 +235,82 @@ def add_rms_norm(x, delta, w, eps, live=None):
 
 
 # ---------------------------------------------------------------------------
+# Qwen3: RMSNorm over the head dimension of q and k + rotary embedding (dalm_head_norm_rope_fwd / dalm_head_norm_bwd), bf16
+# ---------------------------------------------------------------------------
+_HEAD_NORM_DIMS = (64, 128)            # the widths the fused rotary attention takes
+
+
+def head_norm_rope_supported(q, k, wq, wk, cos, sin) -> bool:
+    """What `dalm_head_norm_rope_fwd` takes: q / k [B, H, T, hd] bf16 GPU views (contiguous last dimension, 16-byte rows), head
+    width 64 or 128, norm weights [hd] in the activation dtype (an f32 weight promotes the eager product to f32: another
+    output dtype and rounding, those modules keep transformers' code), and the cos / sin tables of `rope_supported`."""
+    if not (q.is_cuda and q.dtype == torch.bfloat16 and q.dim() == 4 and k.dim() == 4 and q.shape[-1] in _HEAD_NORM_DIMS):
+        return False
+    if not rope_supported(q, k, cos, sin):
+        return False
+    hd = q.shape[-1]
+    for w in (wq, wk):
+        if not (w.is_cuda and w.dtype == q.dtype and w.dim() == 1 and w.shape[0] == hd and w.is_contiguous()
+                and w.data_ptr() % 16 == 0):
+            return False
+    views = all(t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:3]) and t.data_ptr() % 16 == 0 for t in (q, k))
+    tables = all(t.data_ptr() % 16 == 0 and t.stride(1) % 8 == 0 and (t.shape[0] == 1 or t.stride(0) % 8 == 0) for t in (cos, sin))
+    return views and tables and q.shape[0] * q.shape[2] * (q.shape[1] + k.shape[1]) * (hd // 8) < 2 ** 31
+
+
+def _token_major(B, H, T, hd, like):
+    """[B, H, T, hd] view of fresh [B, T, H, hd] memory: the layout of the projections' views, dense as [B T, H hd]."""
+    return torch.empty(B, T, H, hd, dtype=like.dtype, device=like.device).transpose(1, 2)
+
+
+def head_norm_rope(q, k, wq, wk, eps_q, eps_k, cos, sin, live=None):
+    """(rope(rmsnorm_hd(q) * wq), rope(rmsnorm_hd(k) * wk), rstd_q [B, T, Hq], rstd_k [B, T, Hk]) in one launch; q / k are read
+    in place (column slices of a q|k|v GEMM output included).  live: uint8 [B T] row liveness; None: that of the tower call in
+    progress (dalm_amd/live_rows.py), if any.  Returns the vector it used as the fifth value: the backward needs the same one."""
+    hip.require_gpu(q, k, wq, wk, cos, sin)
+    B, Hq, T, hd = q.shape
+    Hk = k.shape[1]
+    if live is None:
+        live = live_rows.current(B * T, q.device)
+    qo, ko = _token_major(B, Hq, T, hd, q), _token_major(B, Hk, T, hd, k)
+    rq = torch.empty(B, T, Hq, dtype=torch.float32, device=q.device)
+    rk = torch.empty(B, T, Hk, dtype=torch.float32, device=q.device)
+    cs = (C.c_int64 * 2)(cos.stride(0) if cos.shape[0] > 1 else 0, cos.stride(1))
+    hip.call("dalm_head_norm_rope_fwd", hip.ptr(q), hip.ptr(k), hip.ptr(wq), hip.ptr(wk), float(eps_q), float(eps_k), hip.ptr(cos),
+             hip.ptr(sin), B, T, Hq, Hk, hd, _strides3(q), _strides3(k), _strides3(qo), _strides3(ko), cs, hip.ptr(qo), hip.ptr(ko),
+             hip.ptr(rq), hip.ptr(rk), hip.ptr(live), hip.stream())
+    return qo, ko, rq, rk, live
+
+
+def head_norm_bwd(gq, gk, q, k, wq, wk, rstd_q, rstd_k, live=None):
+    """Gradients of the pre-norm q / k from those of the normed, un-rotated ones (what `dalm_attn_bwd` leaves when it is given
+    cos / sin).  dq / dk come in [B, T, H, hd] memory order: their reshape to [B T, H hd] is dense and the dgrad GEMMs keep the
+    leading dimensions the tuned table holds.  live: the vector the forward used."""
+    B, Hq, T, hd = q.shape
+    Hk = k.shape[1]
+    if gq.stride(-1) != 1 or any(s % 8 for s in gq.stride()[:3]):
+        gq = gq.contiguous()
+    if gk.stride(-1) != 1 or any(s % 8 for s in gk.stride()[:3]):
+        gk = gk.contiguous()
+    dq, dk = _token_major(B, Hq, T, hd, q), _token_major(B, Hk, T, hd, k)
+    hip.call("dalm_head_norm_bwd", hip.ptr(gq), hip.ptr(gk), hip.ptr(q), hip.ptr(k), hip.ptr(wq), hip.ptr(wk), hip.ptr(rstd_q),
+             hip.ptr(rstd_k), B, T, Hq, Hk, hd, _strides3(gq), _strides3(gk), _strides3(q), _strides3(k), _strides3(dq), _strides3(dk),
+             hip.ptr(dq), hip.ptr(dk), hip.ptr(live), hip.stream())
+    return dq, dk
+
+
+def head_norm_weight_grad(g, x, rstd, live=None):
+    """Gradient of a head-norm weight [hd] (training without adapters; the kernels produce none): sum over (b, head, t) of
+    g * xh with xh rounded to the activation dtype first, as `_weight_grad`.  g, x: [B, H, T, hd]; rstd: [B, T, H]."""
+    xh = (x.float() * rstd.transpose(1, 2).unsqueeze(-1)).to(x.dtype)
+    prod = g.float() * xh.float()
+    if live is not None:                           # dead rows: g is whatever the attention backward left, x is not read
+        B, _, T, _ = x.shape
+        prod = prod.masked_fill((live == 0).view(B, 1, T, 1), 0.0)
+    return prod.sum((0, 1, 2))
+
+
+# ---------------------------------------------------------------------------
 # Falcon decoder layer: LayerNorm, erf-GELU and the three-way residual add (dalm_amd/csrc/falcon.hip), bf16 activations
 # ---------------------------------------------------------------------------
 def layer_norm_supported(x: torch.Tensor, w: torch.Tensor, b) -> bool:

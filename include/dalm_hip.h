@@ -515,6 +515,32 @@ int dalm_rms_norm_fwd_live(const void* x, const void* delta, const void* w, int 
                            void* h_out, void* y, float* rstd, const uint8_t* row_live, dalm_stream_t stream);
 int dalm_rms_norm_bwd_live(const void* dy, const void* h, const void* w, const float* rstd, const void* dres, int dtype, int64_t R,
                            int64_t D, void* dx, const uint8_t* row_live, dalm_stream_t stream);
+/* Qwen3: the RMSNorm over the HEAD dimension of q and of k (modeling_qwen3.py Qwen3Attention: q_norm / k_norm, one weight [hd]
+ * shared by all heads, between the projection and the rotary embedding) and apply_rotary_pos_emb, ONE launch for q and k.  bf16.
+ * Conventions of dalm_rope_qk_live: q / k / outputs / gradients are [B, H, T, hd] views with element strides {b, h, t} and a
+ * contiguous last dimension (q with Hq heads, k with Hk; column slices of one q|k|v GEMM output are read in place); cos / sin
+ * [B or 1, T, hd] with element strides {b, t} (b = 0 for one table); row_live [B T] bytes or NULL (Row liveness, above).
+ *   dalm_head_norm_rope_fwd: per live (b, t) and head
+ *        rstd = rsqrt(mean_d(x^2) + eps)  (f32);  xh = bf16(x rstd);  y = bf16(w xh);
+ *        out = bf16(bf16(y cos) + bf16(rotate_half(y) sin))
+ *        - the rounding points of Qwen3RMSNorm followed by apply_rotary_pos_emb on bf16 tensors with bf16 weights; only the f32
+ *        summation order of the mean is the kernel's own.  wq / wk [hd] bf16.  rstd_q [B, T, Hq], rstd_k [B, T, Hk] f32 are kept
+ *        for the backward.  A dead (b, t): nothing loaded, q_out / k_out / rstd zeros.
+ *   dalm_head_norm_bwd: gq / gk are the gradients of the normed, UN-rotated q / k - what dalm_attn_bwd / dalm_attn_gqa_bwd leave
+ *        when given cos / sin - and q / k the forward's inputs:  dx = bf16(rstd (g w - xh mean_d(g w xh))),  xh = x rstd in f32
+ *        (the arithmetic of dalm_rms_norm_bwd).  A dead (b, t): nothing loaded, dq / dk zeros.  No weight gradient is produced.
+ * hd = 64 or 128 and B T (Hq + Hk) hd / 8 < 2^31 (DALM_E_SHAPE); 16-byte aligned tensors, strides multiples of 8 (DALM_E_ALIGN).
+ * The checks run before anything is enqueued. */
+int dalm_head_norm_rope_fwd(const void* q, const void* k, const void* wq, const void* wk, float eps_q, float eps_k,
+                            const void* cos, const void* sin, int64_t B, int64_t T, int64_t Hq, int64_t Hk, int64_t hd,
+                            const int64_t* q_strides, const int64_t* k_strides, const int64_t* qo_strides,
+                            const int64_t* ko_strides, const int64_t* cs_strides, void* q_out, void* k_out, float* rstd_q,
+                            float* rstd_k, const uint8_t* row_live, dalm_stream_t stream);
+int dalm_head_norm_bwd(const void* gq, const void* gk, const void* q, const void* k, const void* wq, const void* wk,
+                       const float* rstd_q, const float* rstd_k, int64_t B, int64_t T, int64_t Hq, int64_t Hk, int64_t hd,
+                       const int64_t* gq_strides, const int64_t* gk_strides, const int64_t* q_strides, const int64_t* k_strides,
+                       const int64_t* dq_strides, const int64_t* dk_strides, void* dq, void* dk, const uint8_t* row_live,
+                       dalm_stream_t stream);
 
 /* Elementwise chains of a Falcon-7B decoder layer (transformers modeling_falcon.py FalconDecoderLayer.forward /
  * FalconMLP.forward / dropout_add, reached by the reference through self.generator_model(...),

@@ -293,6 +293,59 @@ def bench_pool_last(B, T, D, dtype):
     return out
 
 
+def bench_head_norm_rope(B, T, Hq, Hk, hd, rounds=3):
+    """Qwen3's q_norm / k_norm + rotary embedding: `dalm_head_norm_rope_fwd` / `dalm_head_norm_bwd` on the q | k column slices of
+    one [B T, (Hq + 2 Hk) hd] bf16 buffer, and beside them - alternating, in the same process - what runs without them for the
+    same math: F.rms_norm x 2 (what `use_native_rms_norm` leaves of Qwen3RMSNorm) + transformers' eager rotary chain, and
+    autograd's backward of that.  Algorithmic bytes: forward reads q, k and writes q, k and rstd; backward reads the gradients
+    and q, k, rstd and writes dq, dk.  Every figure: median over `rounds` alternations of a 20-call graph's per-call time,
+    with the lowest and highest round."""
+    import torch.nn.functional as F
+    from transformers.models.qwen3.modeling_qwen3 import apply_rotary_pos_emb
+
+    from dalm_amd.models import tower_ops
+
+    dev = torch.device("cuda:0")
+    R, W = B * T, (Hq + 2 * Hk) * hd
+    buf = torch.randn(R, W, device=dev, dtype=torch.bfloat16)
+    q = buf[:, :Hq * hd].view(B, T, Hq, hd).transpose(1, 2)
+    k = buf[:, Hq * hd:(Hq + Hk) * hd].view(B, T, Hk, hd).transpose(1, 2)
+    wq, wk = (1 + 0.1 * torch.randn(hd, device=dev)).bfloat16(), (1 + 0.1 * torch.randn(hd, device=dev)).bfloat16()
+    ang = torch.rand(1, T, hd // 2, device=dev) * 6.28
+    cos, sin = torch.cat((ang.cos(), ang.cos()), -1).bfloat16(), torch.cat((ang.sin(), ang.sin()), -1).bfloat16()
+    assert tower_ops.head_norm_rope_supported(q, k, wq, wk, cos, sin)
+    _, _, rq, rk, _ = tower_ops.head_norm_rope(q, k, wq, wk, 1e-6, 1e-6, cos, sin)
+    gq = torch.randn(B, T, Hq, hd, device=dev, dtype=torch.bfloat16).transpose(1, 2)
+    gk = torch.randn(B, T, Hk, hd, device=dev, dtype=torch.bfloat16).transpose(1, 2)
+    qg, kg = q.detach().clone().requires_grad_(True), k.detach().clone().requires_grad_(True)      # dense leaves for autograd
+
+    def eager_fwd(a, b):
+        return apply_rotary_pos_emb(F.rms_norm(a, (hd,), wq, 1e-6), F.rms_norm(b, (hd,), wk, 1e-6), cos, sin)
+
+    def eager_both():
+        oq, ok = eager_fwd(qg, kg)
+        return torch.autograd.grad((oq, ok), (qg, kg), (gq, gk))
+
+    fns = {"kernel fwd (1 launch)": lambda: tower_ops.head_norm_rope(q, k, wq, wk, 1e-6, 1e-6, cos, sin),
+           "kernel bwd (1 launch)": lambda: tower_ops.head_norm_bwd(gq, gk, q, k, wq, wk, rq, rk),
+           "eager fwd (rms_norm x2 + rotary chain)": lambda: eager_fwd(q, k),
+           "eager fwd + autograd bwd": eager_both}
+    el, n = 2, R * (Hq + Hk) * hd
+    nbytes = {"kernel fwd (1 launch)": 2 * n * el + R * (Hq + Hk) * 4, "kernel bwd (1 launch)": 3 * n * el + R * (Hq + Hk) * 4,
+              "eager fwd (rms_norm x2 + rotary chain)": 2 * n * el + R * (Hq + Hk) * 4,
+              "eager fwd + autograd bwd": 5 * n * el + 2 * R * (Hq + Hk) * 4}
+    seen = {name: [] for name in fns}
+    for _ in range(rounds):                      # alternate: every round visits all four
+        for name, fn in fns.items():
+            seen[name].append(time_graph(fn)[0])
+    out = {}
+    for name, ts in seen.items():
+        ts.sort()
+        med = ts[len(ts) // 2]
+        out[name] = {"s": med, "lo": ts[0], "hi": ts[-1], "GBps": nbytes[name] / med / 1e9, "frac": nbytes[name] / med / HBM_PEAK}
+    return out
+
+
 def print_results(res) -> None:
     for k, v in res.items():
         print(k)
@@ -357,6 +410,9 @@ def main():
         res["nf4 11008x4096 -> f32"] = bench_nf4(11008, 4096, torch.float32)
     if args.only in ("", "tower"):
         res["tower cfg3 layer: rope [18,32,256,128] + swiglu [4608,11008] bf16"] = bench_tower(18, 256, 32, 128, 11008, torch.bfloat16)
+    if args.only in ("", "head_norm_rope"):
+        res["head_norm_rope Qwen3-8B generator rows 18x256, 32+8 heads x 128"] = bench_head_norm_rope(18, 256, 32, 8, 128)
+        res["head_norm_rope Qwen3-8B packed rows 1x3008, 32+8 heads x 128"] = bench_head_norm_rope(1, 3008, 32, 8, 128)
     Path("gpurun_out").mkdir(exist_ok=True)
     Path("gpurun_out/kernel_bench.json").write_text(json.dumps(res, indent=1))
     print_results(res)
