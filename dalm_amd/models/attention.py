@@ -37,7 +37,7 @@ import torch
 from .. import hip
 from ..packed import packed_of
 from .fastpath import _off
-from .lora import dropout_uid
+from .lora import dropout_salt
 
 NAME = "dalm_sdpa"
 _HEAD_DIMS = (32, 64, 128)             # what dalm_attn_fwd / _bwd and their packed forms take
@@ -313,8 +313,8 @@ class _NormRopeSdpaHip(torch.autograd.Function):
 
 def norm_rope_sdpa(query, key, value, wq, wk, eps_q: float, eps_k: float, cos, sin, mask, scale: float, causal: bool):
     """sdpa(apply_rotary_pos_emb(rmsnorm(query) * wq, rmsnorm(key) * wk, cos, sin), value, ...) with the norms over the head
-    dimension (Qwen3's q_norm / k_norm), for what `tower_ops.head_norm_rope_supported`, `rope_fusable` and `supported` /
-    `packed_supported` / `grouped_supported` accept.  The norm weights may require grad."""
+    dimension (Qwen3's q_norm / k_norm), for what `tower_ops.head_norm_rope_supported`, `rope_fusable` and `node_supported`
+    accept.  The norm weights may require grad."""
     return _NormRopeSdpaHip.apply(query, key, value, wq, wk, eps_q, eps_k, cos, sin, mask, scale, causal)
 
 
@@ -330,7 +330,7 @@ def rope_fusable(q, k, cos, sin) -> bool:
 
 
 def rope_sdpa(query, key, value, cos, sin, mask, scale: float, causal: bool):
-    """sdpa(apply_rotary_pos_emb(query, key, cos, sin), value, ...) for what `supported` and `rope_fusable` accept."""
+    """sdpa(apply_rotary_pos_emb(query, key, cos, sin), value, ...) for what `node_supported` and `rope_fusable` accept."""
     return _RopeSdpaHip.apply(query, key, value, cos, sin, mask, scale, causal)
 
 
@@ -397,6 +397,15 @@ def grouped_supported(query, key, value, mask=None, dropout: float = 0.0, causal
     return supported(query, kx, vx, mask, dropout, causal, kwargs or {})
 
 
+def node_supported(query, key, value, mask, causal: bool) -> bool:
+    """Whether the attention of a rotary + attention node (`rope_sdpa`, `norm_rope_sdpa`; no dropout) can run on these tensors:
+    equal heads or grouped heads left un-expanded, padded or - `mask` a packed descriptor - packed.  The callers ask
+    `rope_fusable` as well."""
+    if packed_of(mask) is not None:
+        return packed_supported(query, key, value) or grouped_supported(query, key, value, packed=True)
+    return supported(query, key, value, mask, 0.0, causal, {}) or grouped_supported(query, key, value, mask, 0.0, causal, {})
+
+
 def _packed_sdpa_torch(query, key, value, seqs, scale: float, dropout: float):
     """The packed attention without the kernels (CPU tensors, fp32, head widths they do not take): re-pad q / k / v to
     [nseq, H, T, hd] by index, torch's SDPA under the mask the sequence list describes, rows gathered back.  A row without a
@@ -431,10 +440,7 @@ def _packed_attention(module, query, key, value, attention_mask, seqs, dropout, 
         key, value = repeat_kv(key, groups), repeat_kv(value, groups)
     scale = float(scaling) if scaling is not None else float(query.shape[-1]) ** -0.5
     if native or packed_supported(query, key, value, dropout):
-        salt = 0
-        if dropout > 0.0:
-            module._dalm_attn_calls = getattr(module, "_dalm_attn_calls", 0) + 1
-            salt = (dropout_uid(module) << 12) ^ (module._dalm_attn_calls & 0xFFF)
+        salt = dropout_salt(module, "_dalm_attn_calls") if dropout > 0.0 else 0
         out = _SdpaHipBackward.apply(query, key, value, attention_mask, scale, False, float(dropout), salt)
         return out.transpose(1, 2).contiguous(), None
     return _packed_sdpa_torch(query, key, value, seqs, scale, float(dropout)), None
@@ -463,10 +469,7 @@ def dalm_sdpa_attention_forward(module, query, key, value, attention_mask, dropo
         return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling,
                                       is_causal=is_causal, **kwargs)
     scale = float(scaling) if scaling is not None else float(query.shape[-1]) ** -0.5
-    salt = 0
-    if dropout > 0.0:      # this module's number in the upper bits, a host call counter below (graph replays re-use the captured
-        module._dalm_attn_calls = getattr(module, "_dalm_attn_calls", 0) + 1        # salt; there the device seed word changes the masks)
-        salt = (dropout_uid(module) << 12) ^ (module._dalm_attn_calls & 0xFFF)
+    salt = dropout_salt(module, "_dalm_attn_calls") if dropout > 0.0 else 0
     out = _SdpaHipBackward.apply(query, k2, v2, attention_mask, scale, causal, float(dropout), salt)
     return out.transpose(1, 2).contiguous(), None
 

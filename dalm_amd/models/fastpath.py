@@ -6,6 +6,9 @@ chains of a Llama-family layer the step spent the most launches on (rotary embed
 `torch.nn.functional.rms_norm` computes the same `w * x * rsqrt(mean(x^2) + eps)` (fp32 internally) in
 one fused kernel each way: 458 -> 124 us per norm (fwd+bwd, [4608, 4096] bf16 on MI355X), about 22 ms of
 a 230 ms cfg3 step.  Differences are bf16 rounding-order only (max 1 bf16 ulp).
+
+Every patch is a guard (`_guard`: a numeric probe, or for a forward that restates transformers' statements an entry of
+`_SOURCE_GUARDS` read by `_source_guard`), a forward, and a `use_*` function that is one call of `_install`.
 """
 from __future__ import annotations
 
@@ -43,45 +46,102 @@ def _close(a: torch.Tensor, b: torch.Tensor, ulps: float = 1.0) -> bool:
     return float((a.float() - b.float()).abs().max()) <= ulps * eps * scale
 
 
-def _native_forward(self, hidden_states: torch.Tensor) -> torch.Tensor:
-    return F.rms_norm(hidden_states, (hidden_states.shape[-1],), self.weight, self._dalm_eps)
+_checked: dict = {}
 
 
-def use_native_rms_norm(model: torch.nn.Module) -> int:
-    """Patch every `*RMSNorm` module with a plain weight vector; returns how many were patched."""
+def _guard(key: tuple, who: str, what: str, probe) -> bool:
+    """Run-time guard of one patch: `probe()` says whether transformers' `who` IS the code the replacement
+    stands for.  Asked once per `key` (a probe that raises counts as no); every refusal warns once per patch kind and `who`."""
+    if key not in _checked:
+        try:
+            _checked[key] = bool(probe())
+        except Exception:
+            _checked[key] = False
+    if not _checked[key]:
+        _warn_once(f"{key[0]}:{who}", f"{who} is not {what}: transformers' own code stays in place")
+    return _checked[key]
+
+
+def _source_guard(key: str, cls, check, what: str) -> bool:
+    """The guard of a patch that restates `cls.forward`: `check(params, src)` over the parameter names and the source text."""
+    import inspect
+
+    return _guard((key, cls), cls.__name__ + ".forward", what,
+                  lambda: check(list(inspect.signature(cls.forward).parameters), inspect.getsource(cls.forward)))
+
+
+_RESTATED = "the code this patch restates"
+_SOURCE_GUARDS: dict = {}      # patch kind -> (check(params, src), what the forward must be): filled in next to each restating forward
+
+
+def _matches(key: str, cls) -> bool:
+    return _source_guard(key, cls, *_SOURCE_GUARDS[key])
+
+
+def _qwen3_attention_matches(cls) -> bool:            # the names tests/test_qwen3_cpu.py asks the two Qwen3 guards by
+    return _matches("qwen3-attn", cls)
+
+
+def _qwen3_layer_matches(cls) -> bool:
+    return _matches("qwen3-layer", cls)
+
+
+def _body(src: str) -> list:
+    """The lines of a function's source, stripped, without blank and comment lines."""
+    return [ln.strip() for ln in src.splitlines() if ln.strip() and not ln.strip().startswith("#")]
+
+
+def _restates(params: list, *statements: str):
+    """A source check: exactly these parameters, and every one of these statements somewhere in the text."""
+    return lambda p, src: p == params and all(s in src for s in statements)
+
+
+def _install(model: torch.nn.Module, names: tuple, eligible, guard, forward, keep: str = "") -> int:
+    """Bind `forward` on every module whose class name matches one of `names` (fnmatch patterns), that `eligible(mod)` takes and
+    whose code passes its guard: a key of `_SOURCE_GUARDS`, or a function of the module.  `keep` names the attribute under
+    which the module's own forward stays reachable.  Returns how many modules were patched."""
+    from fnmatch import fnmatchcase
+
     n = 0
     for mod in model.modules():
-        if not type(mod).__name__.endswith("RMSNorm"):
+        if not any(fnmatchcase(type(mod).__name__, pat) for pat in names) or not eligible(mod):
             continue
-        w = getattr(mod, "weight", None)
-        eps = getattr(mod, "variance_epsilon", getattr(mod, "eps", None))
-        if w is None or w.dim() != 1 or eps is None:
+        if not (_matches(guard, type(mod)) if isinstance(guard, str) else guard(mod)):
             continue
-        if "Gemma" in type(mod).__name__:  # (1 + w) parameterisation: not the same formula
-            continue
-        mod._dalm_eps = float(eps)
-        if not _norm_matches(mod):
-            _warn_once("norm:" + type(mod).__name__, f"{type(mod).__name__}.forward is not w * x * rsqrt(mean(x^2) + eps) here: "
-                       "transformers' own code stays in place")
-            continue
-        mod.forward = types.MethodType(_native_forward, mod)
+        if keep:
+            setattr(mod, keep, mod.forward)
+        mod.forward = types.MethodType(forward, mod)
         n += 1
     return n
 
 
+def _native_forward(self, hidden_states: torch.Tensor) -> torch.Tensor:
+    return F.rms_norm(hidden_states, (hidden_states.shape[-1],), self.weight, self._dalm_eps)
+
+
+def _plain_rms_norm(mod) -> bool:
+    w = getattr(mod, "weight", None)
+    return (w is not None and w.dim() == 1 and getattr(mod, "variance_epsilon", getattr(mod, "eps", None)) is not None
+            and "Gemma" not in type(mod).__name__)             # Gemma: (1 + w) parameterisation, not the same formula
+
+
+def use_native_rms_norm(model: torch.nn.Module) -> int:
+    """Patch every `*RMSNorm` module with a plain weight vector; returns how many were patched."""
+    return _install(model, ("*RMSNorm",), _plain_rms_norm, _norm_matches, _native_forward)
+
+
 def _norm_matches(mod: torch.nn.Module) -> bool:
-    """Run-time guard: the module's OWN forward against the fused formula on a small random tensor, once per
-    class, dtype and device type."""
+    """The module's OWN forward against the fused formula on a small random tensor, once per class, dtype and device type."""
     w = mod.weight
-    key = ("norm", type(mod), w.dtype, w.device.type)
-    if key not in _checked:
+    mod._dalm_eps = float(getattr(mod, "variance_epsilon", getattr(mod, "eps", None)))       # what `_native_forward` reads
+
+    def probe():
         x = torch.randn(4, 3, w.shape[0], generator=torch.Generator().manual_seed(0)).to(device=w.device, dtype=w.dtype)
         with torch.no_grad():
-            _checked[key] = _close(_native_forward(mod, x), type(mod).forward(mod, x), 2.0)
-    return _checked[key]
+            return _close(_native_forward(mod, x), type(mod).forward(mod, x), 2.0)
 
-
-_checked: dict = {}
+    return _guard(("norm", type(mod), w.dtype, w.device.type), type(mod).__name__ + ".forward",
+                  "w * x * rsqrt(mean(x^2) + eps) here", probe)
 
 
 # ---------------------------------------------------------------------------
@@ -128,32 +188,24 @@ def use_roll_rope(model: torch.nn.Module) -> bool:
         return False
     if getattr(mod.apply_rotary_pos_emb, "__name__", "") != "_rope_hip":
         mod._dalm_orig_apply_rotary_pos_emb = mod.apply_rotary_pos_emb
-    # Run-time guard: the function being replaced must BE the formula the kernel implements.  The swap is
-    # PROCESS-WIDE (transformers resolves apply_rotary_pos_emb through the modeling file's globals; there is no per-model
-    # hook), so every model of this modeling file in the process takes the replacement.
+    # The function being replaced must BE the formula the kernel implements.  The swap is PROCESS-WIDE (transformers resolves
+    # apply_rotary_pos_emb through the modeling file's globals; there is no per-model hook), so every model of this modeling
+    # file in the process takes the replacement.
     dev = next((p.device for p in model.parameters()), torch.device("cpu"))
-    if not _rope_matches(mod._dalm_orig_apply_rotary_pos_emb, dev):
-        _warn_once("rope:" + mod_name, f"{mod_name}.apply_rotary_pos_emb is not x * cos + rotate_half(x) * sin here: "
-                   "transformers' own code stays in place")
-        mod.apply_rotary_pos_emb = mod._dalm_orig_apply_rotary_pos_emb
-        return False
-    mod.apply_rotary_pos_emb = _rope_hip
-    return True
+    ok = _rope_matches(mod._dalm_orig_apply_rotary_pos_emb, dev, mod_name)
+    mod.apply_rotary_pos_emb = _rope_hip if ok else mod._dalm_orig_apply_rotary_pos_emb
+    return ok
 
 
-def _rope_matches(orig, dev: torch.device) -> bool:
+def _rope_matches(orig, dev: torch.device, mod_name: str) -> bool:
     """orig(q, k, cos, sin) against `_rope_hip` on small random tensors: on the CPU against the roll form in float32 (the
     same formula, one fused multiply-add apart), on a GPU additionally against the HIP kernel in bfloat16 - there the values
     must be EQUAL (tests/test_tower_ops_gpu.py asserts the same)."""
-    key = ("rope", orig, dev.type)
-    if key in _checked:
-        return _checked[key]
-    g = torch.Generator().manual_seed(0)
-    q, k = torch.randn(2, 4, 5, 16, generator=g), torch.randn(2, 2, 5, 16, generator=g)
-    ang = torch.rand(2, 5, 8, generator=g) * 6.28
-    cos, sin = torch.cat((ang.cos(), ang.cos()), -1), torch.cat((ang.sin(), ang.sin()), -1)
-    ok = True
-    try:
+    def probe():
+        g = torch.Generator().manual_seed(0)
+        q, k = torch.randn(2, 4, 5, 16, generator=g), torch.randn(2, 2, 5, 16, generator=g)
+        ang = torch.rand(2, 5, 8, generator=g) * 6.28
+        cos, sin = torch.cat((ang.cos(), ang.cos()), -1), torch.cat((ang.sin(), ang.sin()), -1)
         with torch.no_grad():
             want = orig(q, k, cos, sin)
             got = _rope_roll(q, k, cos, sin)
@@ -161,10 +213,9 @@ def _rope_matches(orig, dev: torch.device) -> bool:
             if ok and dev.type == "cuda":
                 args = [t.to(dev, torch.bfloat16) for t in (q, k, cos, sin)]
                 ok = all(torch.equal(a, b) for a, b in zip(_rope_hip(*args), orig(*args)))
-    except Exception:
-        ok = False
-    _checked[key] = ok
-    return ok
+        return ok
+
+    return _guard(("rope", orig, dev.type), mod_name + ".apply_rotary_pos_emb", "x * cos + rotate_half(x) * sin here", probe)
 
 
 # ---------------------------------------------------------------------------
@@ -188,39 +239,27 @@ def use_swiglu_kernel(model: torch.nn.Module) -> int:
     Same rounding points as the eager chain.  DALM_SWIGLU_KERNEL=0 disables; returns how many modules were patched."""
     if _off("DALM_SWIGLU_KERNEL"):
         return 0
-    n = 0
-    for mod in model.modules():
-        if type(mod).__name__ not in ("LlamaMLP", "MistralMLP", "Qwen2MLP", "Qwen3MLP"):
-            continue
+
+    def gated_silu(mod) -> bool:
         act = getattr(mod, "act_fn", None)
-        if not all(hasattr(mod, a) for a in ("gate_proj", "up_proj", "down_proj")):
-            continue
-        if not (isinstance(act, torch.nn.SiLU) or type(act).__name__ in ("SiLUActivation", "SiLU")):
-            continue
-        if not _mlp_matches(mod):
-            _warn_once("mlp:" + type(mod).__name__, f"{type(mod).__name__}.forward is not down(silu(gate(x)) * up(x)) here: "
-                       "transformers' own code stays in place")
-            continue
-        mod.forward = types.MethodType(_swiglu_mlp_forward, mod)
-        n += 1
-    return n
+        return (all(hasattr(mod, a) for a in ("gate_proj", "up_proj", "down_proj"))
+                and (isinstance(act, torch.nn.SiLU) or type(act).__name__ in ("SiLUActivation", "SiLU")))
+
+    return _install(model, ("LlamaMLP", "MistralMLP", "Qwen2MLP", "Qwen3MLP"), gated_silu, _mlp_matches, _swiglu_mlp_forward)
 
 
 def _mlp_matches(mod: torch.nn.Module) -> bool:
-    """Run-time guard: the class's own forward against the patched one on a small random input, once per
-    class, dtype and device type (on a GPU the patched forward runs the HIP kernel: <= 1 ulp of the output dtype)."""
+    """The class's own forward against the patched one on a small random input, once per class, dtype and device type (on a
+    GPU the patched forward runs the HIP kernel: <= 1 ulp of the output dtype)."""
     w = getattr(mod.gate_proj, "weight", None)
-    if w is None:
-        return False
-    key = ("mlp", type(mod), w.dtype, w.device.type)
-    if key not in _checked:
+    where = (None, None) if w is None else (w.dtype, w.device.type)        # no resident weight: the probe fails, the guard says no
+
+    def probe():
         x = torch.randn(2, 3, mod.gate_proj.in_features, generator=torch.Generator().manual_seed(0)).to(device=w.device, dtype=w.dtype)
-        try:
-            with torch.no_grad():
-                _checked[key] = _close(_swiglu_mlp_forward(mod, x), type(mod).forward(mod, x), 2.0)
-        except Exception:
-            _checked[key] = False
-    return _checked[key]
+        with torch.no_grad():
+            return _close(_swiglu_mlp_forward(mod, x), type(mod).forward(mod, x), 2.0)
+
+    return _guard(("mlp", type(mod), *where), type(mod).__name__ + ".forward", "down(silu(gate(x)) * up(x)) here", probe)
 
 
 # ---------------------------------------------------------------------------
@@ -305,27 +344,19 @@ def use_falcon_layer_kernels(model: torch.nn.Module) -> int:
     (signature and source checked once per class).  DALM_FALCON_KERNELS=0 disables.  Returns how many layers were patched."""
     if _off("DALM_FALCON_KERNELS"):
         return 0
-    n = 0
-    for mod in model.modules():
-        if type(mod).__name__ != "FalconDecoderLayer":
-            continue
-        cfg = getattr(mod, "config", None)
-        if cfg is None or getattr(cfg, "new_decoder_architecture", True) or not getattr(cfg, "parallel_attn", False):
-            continue
-        if float(getattr(cfg, "hidden_dropout", 1.0)) != 0.0 or float(getattr(cfg, "attention_dropout", 1.0)) != 0.0:
-            continue            # dropout_add with p > 0 draws from torch's generator: transformers' code stays
-        ln = getattr(mod, "input_layernorm", None)
-        if not isinstance(ln, torch.nn.LayerNorm) or ln.weight is None or not hasattr(mod, "self_attention") \
-                or not hasattr(mod, "mlp"):
-            continue
-        if not _falcon_layer_matches(type(mod)):
-            continue
-        mod._dalm_orig_forward = mod.forward
-        mod.forward = types.MethodType(_falcon_layer_forward, mod)
-        mlp = mod.mlp
-        if type(mlp).__name__ == "FalconMLP" and _is_erf_gelu(getattr(mlp, "act", None)) and _falcon_mlp_matches(type(mlp)):
-            mlp.forward = types.MethodType(_falcon_mlp_forward, mlp)
-        n += 1
+
+    def plain_7b_layer(mod) -> bool:
+        cfg, ln = getattr(mod, "config", None), getattr(mod, "input_layernorm", None)
+        return (cfg is not None and not getattr(cfg, "new_decoder_architecture", True) and getattr(cfg, "parallel_attn", False)
+                # dropout_add with p > 0 draws from torch's generator: transformers' code stays
+                and float(getattr(cfg, "hidden_dropout", 1.0)) == 0.0 and float(getattr(cfg, "attention_dropout", 1.0)) == 0.0
+                and isinstance(ln, torch.nn.LayerNorm) and ln.weight is not None and hasattr(mod, "self_attention")
+                and hasattr(mod, "mlp"))
+
+    n = _install(model, ("FalconDecoderLayer",), plain_7b_layer, "falcon-layer", _falcon_layer_forward, keep="_dalm_orig_forward")
+    for layer in model.modules():                  # the MLP of a patched layer
+        if getattr(layer.forward, "__func__", None) is _falcon_layer_forward:
+            _install(layer.mlp, ("FalconMLP",), lambda mlp: _is_erf_gelu(getattr(mlp, "act", None)), "falcon-mlp", _falcon_mlp_forward)
     return n
 
 
@@ -336,45 +367,17 @@ def _is_erf_gelu(act) -> bool:
     return type(act).__name__ == "GELUActivation" and getattr(act, "act", None) is torch.nn.functional.gelu
 
 
-def _falcon_layer_matches(cls) -> bool:
-    """Run-time guard: the class's forward must have the signature and the statements `_falcon_layer_forward` restates."""
-    key = ("falcon-layer", cls)
-    if key not in _checked:
-        try:
-            import inspect
-
-            params = list(inspect.signature(cls.forward).parameters)
-            src = inspect.getsource(cls.forward)
-            _checked[key] = (params == _FALCON_LAYER_PARAMS
-                             and "attention_layernorm_out = self.input_layernorm(hidden_states)" in src
-                             and "mlp_layernorm_out = attention_layernorm_out" in src
-                             and "mlp_output = self.mlp(mlp_layernorm_out)" in src
-                             and "mlp_output += attention_output" in src
-                             and "output = dropout_add(mlp_output, residual, self.config.hidden_dropout, training=self.training)" in src
-                             and "return output, attn_weights" in src)
-        except Exception:
-            _checked[key] = False
-        if not _checked[key]:
-            _warn_once("falcon-layer", "FalconDecoderLayer.forward is not the code this patch restates: transformers' own "
-                       "code stays in place")
-    return _checked[key]
-
-
-def _falcon_mlp_matches(cls) -> bool:
-    key = ("falcon-mlp", cls)
-    if key not in _checked:
-        try:
-            import inspect
-
-            src = inspect.getsource(cls.forward)
-            _checked[key] = ("x = self.act(self.dense_h_to_4h(x))" in src and "x = self.dense_4h_to_h(x)" in src
-                             and src.count("self.") == 3)
-        except Exception:
-            _checked[key] = False
-        if not _checked[key]:
-            _warn_once("falcon-mlp", "FalconMLP.forward is not dense_4h_to_h(act(dense_h_to_4h(x))) here: transformers' own "
-                       "code stays in place")
-    return _checked[key]
+_SOURCE_GUARDS["falcon-layer"] = (_restates(
+    _FALCON_LAYER_PARAMS,
+    "attention_layernorm_out = self.input_layernorm(hidden_states)",
+    "mlp_layernorm_out = attention_layernorm_out",
+    "mlp_output = self.mlp(mlp_layernorm_out)",
+    "mlp_output += attention_output",
+    "output = dropout_add(mlp_output, residual, self.config.hidden_dropout, training=self.training)",
+    "return output, attn_weights"), _RESTATED)
+_SOURCE_GUARDS["falcon-mlp"] = (
+    lambda params, src: ("x = self.act(self.dense_h_to_4h(x))" in src and "x = self.dense_4h_to_h(x)" in src
+                         and src.count("self.") == 3), "dense_4h_to_h(act(dense_h_to_4h(x))) here")
 
 
 # ---------------------------------------------------------------------------
@@ -387,14 +390,12 @@ def _bert_output_forward(self, hidden_states: torch.Tensor, input_tensor: torch.
     with the last two on `dalm_bert_add_norm_{fwd,bwd}` where the tensors are what bf16 autocast over a frozen base produces
     (bf16 dense output, f32 residual); everything else runs the statements as they are."""
     from . import bert_ops
-    from .lora import dropout_uid
+    from .lora import dropout_salt
 
     hidden_states = self.dense(hidden_states)
     if bert_ops.supported(hidden_states, input_tensor, self.LayerNorm):
         p = float(self.dropout.p) if self.training else 0.0
-        self._dalm_calls = getattr(self, "_dalm_calls", 0) + 1
-        salt = (dropout_uid(self) << 12) ^ (self._dalm_calls & 0xFFF)   # module number above a host call counter (graph replays: the
-        return bert_ops.add_norm(hidden_states, input_tensor, self.LayerNorm, p, salt)   # device seed word changes the masks)
+        return bert_ops.add_norm(hidden_states, input_tensor, self.LayerNorm, p, dropout_salt(self, "_dalm_calls"))
     hidden_states = self.dropout(hidden_states)
     return self.LayerNorm(hidden_states + input_tensor)
 
@@ -402,38 +403,18 @@ def _bert_output_forward(self, hidden_states: torch.Tensor, input_tensor: torch.
 def use_bert_layer_kernels(model: torch.nn.Module) -> int:
     """Patch BertSelfOutput / BertOutput modules whose forward is the three statements above (source checked once per class) and
     whose LayerNorm is frozen.  Returns how many modules were patched."""
-    n = 0
-    for mod in model.modules():
-        if type(mod).__name__ not in ("BertSelfOutput", "BertOutput"):
-            continue
-        ln, drop = getattr(mod, "LayerNorm", None), getattr(mod, "dropout", None)
-        if not isinstance(ln, torch.nn.LayerNorm) or not isinstance(drop, torch.nn.Dropout) or not hasattr(mod, "dense"):
-            continue
-        if not _bert_output_matches(type(mod)):
-            continue
-        mod.forward = types.MethodType(_bert_output_forward, mod)
-        n += 1
-    return n
+    def dense_dropout_norm(mod) -> bool:
+        return (isinstance(getattr(mod, "LayerNorm", None), torch.nn.LayerNorm)
+                and isinstance(getattr(mod, "dropout", None), torch.nn.Dropout) and hasattr(mod, "dense"))
+
+    return _install(model, ("BertSelfOutput", "BertOutput"), dense_dropout_norm, "bert-output", _bert_output_forward)
 
 
-def _bert_output_matches(cls) -> bool:
-    key = ("bert-output", cls)
-    if key not in _checked:
-        try:
-            import inspect
-
-            params = list(inspect.signature(cls.forward).parameters)
-            src = inspect.getsource(cls.forward)
-            body = [ln.strip() for ln in src.splitlines()[1:] if ln.strip() and not ln.strip().startswith("#")]
-            _checked[key] = (params == ["self", "hidden_states", "input_tensor"]
-                             and body == ["hidden_states = self.dense(hidden_states)", "hidden_states = self.dropout(hidden_states)",
-                                          "hidden_states = self.LayerNorm(hidden_states + input_tensor)", "return hidden_states"])
-        except Exception:
-            _checked[key] = False
-        if not _checked[key]:
-            _warn_once("bert-output:" + cls.__name__, f"{cls.__name__}.forward is not dense -> dropout -> LayerNorm(h + input) here: "
-                       "transformers' own code stays in place")
-    return _checked[key]
+_SOURCE_GUARDS["bert-output"] = (
+    lambda params, src: (params == ["self", "hidden_states", "input_tensor"]
+                         and _body(src)[1:] == ["hidden_states = self.dense(hidden_states)", "hidden_states = self.dropout(hidden_states)",
+                                                "hidden_states = self.LayerNorm(hidden_states + input_tensor)", "return hidden_states"]),
+    "dense -> dropout -> LayerNorm(h + input) here")
 
 
 # ---------------------------------------------------------------------------
@@ -476,9 +457,9 @@ def _falcon_attention_forward(self, hidden_states, alibi, attention_mask, positi
         k1, v1 = key_layer.transpose(1, 2), value_layer.transpose(1, 2)                      # [b, 1, t, hd] views of fused_qkv
         kx, vx = k1.expand(batch_size, H, query_length, hd), v1.expand(batch_size, H, query_length, hd)
         seqs = attention.packed_of(attention_mask)
-        ok = (attention.packed_supported(q4, kx, vx) if seqs is not None
-              else attention.supported(q4, kx, vx, attention_mask, 0.0, is_causal, {}))
-        if ok and attention.rope_fusable(q4, k1, cos, sin):
+        # `node_supported` also asks for grouped heads; k / v reach it with H heads here (with H or one below), and a group needs
+        # 1 < Hkv < H: for Falcon it is `packed_supported` / `supported` alone
+        if attention.node_supported(q4, kx, vx, attention_mask, is_causal) and attention.rope_fusable(q4, k1, cos, sin):
             attn_output = attention.rope_sdpa(q4, k1, v1, cos, sin, attention_mask, float(hd) ** -0.5,
                                               False if seqs is not None else is_causal)
             attn_output = attn_output.permute(0, 2, 1, 3).reshape(batch_size, query_length, H * hd)
@@ -493,10 +474,11 @@ def _falcon_attention_forward(self, hidden_states, alibi, attention_mask, positi
     key_layer = key_layer.transpose(1, 2).reshape(batch_size, num_kv_heads, query_length, self.head_dim)
     value_layer = value_layer.transpose(1, 2).reshape(batch_size, num_kv_heads, query_length, self.head_dim)
     seqs = attention.packed_of(attention_mask)
+    fused = (rope_on and attention.node_supported(query_layer, key_layer, value_layer, attention_mask, is_causal)
+             and attention.rope_fusable(query_layer, key_layer, cos, sin))
     if seqs is not None:
         # packed (un-padded) call (dalm_amd/packed.py): [1, H, n, hd], sequences from the descriptor
-        if attention.packed_supported(query_layer, key_layer, value_layer) and attention.rope_fusable(query_layer, key_layer, cos, sin) \
-                and rope_on:
+        if fused:
             attn_output = attention.rope_sdpa(query_layer, key_layer, value_layer, cos, sin, attention_mask,
                                               float(self.head_dim) ** -0.5, False)
             attn_output = attn_output.permute(0, 2, 1, 3)
@@ -507,8 +489,7 @@ def _falcon_attention_forward(self, hidden_states, alibi, attention_mask, positi
                                                          float(self.head_dim) ** -0.5)            # [1, n, H, hd]
         attn_output = attn_output.reshape(batch_size, query_length, self.num_heads * self.head_dim)
         return self.dense(attn_output), None
-    if (attention.supported(query_layer, key_layer, value_layer, attention_mask, 0.0, is_causal, {})
-            and attention.rope_fusable(query_layer, key_layer, cos, sin) and rope_on):
+    if fused:
         attn_output = attention.rope_sdpa(query_layer, key_layer, value_layer, cos, sin, attention_mask,
                                           float(self.head_dim) ** -0.5, is_causal)     # the rotation's backward: in dalm_attn_bwd
         attn_output = attn_output.view(batch_size, self.num_heads, query_length, self.head_dim)
@@ -533,136 +514,148 @@ def use_falcon_attention_kernels(model: torch.nn.Module) -> int:
     restates (signature and statements checked once per class).  DALM_ATTN_KERNEL=0 disables.  Returns the count."""
     if _off("DALM_ATTN_KERNEL"):
         return 0
-    n = 0
-    for mod in model.modules():
-        if type(mod).__name__ != "FalconAttention" or getattr(mod, "head_dim", None) not in (64, 128):
-            continue
-        if getattr(getattr(mod, "config", None), "alibi", True) or float(getattr(mod.config, "attention_dropout", 1.0)) != 0.0:
-            continue
-        if not _falcon_attention_matches(type(mod)):
-            continue
-        mod._dalm_orig_attn_forward = mod.forward
-        mod.forward = types.MethodType(_falcon_attention_forward, mod)
-        n += 1
-    return n
+
+    def rotary_no_dropout(mod) -> bool:
+        cfg = getattr(mod, "config", None)
+        return (getattr(mod, "head_dim", None) in (64, 128) and not getattr(cfg, "alibi", True)
+                and float(getattr(cfg, "attention_dropout", 1.0)) == 0.0)
+
+    return _install(model, ("FalconAttention",), rotary_no_dropout, "falcon-attn", _falcon_attention_forward,
+                    keep="_dalm_orig_attn_forward")
 
 
-def _falcon_attention_matches(cls) -> bool:
-    key = ("falcon-attn", cls)
-    if key not in _checked:
-        try:
-            import inspect
-
-            params = list(inspect.signature(cls.forward).parameters)
-            src = inspect.getsource(cls.forward)
-            _checked[key] = (params == _FALCON_ATTN_PARAMS
-                             and "fused_qkv = self.query_key_value(hidden_states)" in src
-                             and "(query_layer, key_layer, value_layer) = self._split_heads(fused_qkv)" in src
-                             and "query_layer, key_layer = apply_rotary_pos_emb(query_layer, key_layer, cos, sin)" in src
-                             and "is_causal = self.is_causal and attention_mask is None and query_length > 1" in src
-                             and "attn_output = attn_output.view(batch_size, self.num_heads, query_length, self.head_dim)" in src
-                             and "attn_output = attn_output.permute(0, 2, 1, 3)" in src
-                             and "attn_output = self.dense(attn_output)" in src
-                             and "return attn_output, attention_scores" in src)
-        except Exception:
-            _checked[key] = False
-        if not _checked[key]:
-            _warn_once("falcon-attn", "FalconAttention.forward is not the code this patch restates: transformers' own code "
-                       "stays in place")
-    return _checked[key]
+_SOURCE_GUARDS["falcon-attn"] = (_restates(
+    _FALCON_ATTN_PARAMS,
+    "fused_qkv = self.query_key_value(hidden_states)",
+    "(query_layer, key_layer, value_layer) = self._split_heads(fused_qkv)",
+    "query_layer, key_layer = apply_rotary_pos_emb(query_layer, key_layer, cos, sin)",
+    "is_causal = self.is_causal and attention_mask is None and query_length > 1",
+    "attn_output = attn_output.view(batch_size, self.num_heads, query_length, self.head_dim)",
+    "attn_output = attn_output.permute(0, 2, 1, 3)",
+    "attn_output = self.dense(attn_output)",
+    "return attn_output, attention_scores"), _RESTATED)
 
 
 # ---------------------------------------------------------------------------
-# Llama attention: rotary embedding + attention as ONE autograd node (the rotation's backward rides in dalm_attn_bwd's epilogues)
+# Llama / Qwen3 attention: (q_norm / k_norm over the head dimension +) rotary embedding + attention as ONE autograd node (the
+# rotation's backward rides in dalm_attn_bwd's epilogues)
 # ---------------------------------------------------------------------------
 _LLAMA_ATTN_PARAMS = ["self", "hidden_states", "position_embeddings", "attention_mask", "past_key_values", "kwargs"]
+_LLAMA_ATTN_STATEMENTS = ("value_states = self.v_proj(hidden_states).view(hidden_shape).transpose(1, 2)",
+                          "query_states, key_states = apply_rotary_pos_emb(query_states, key_states, cos, sin)",
+                          "dropout=0.0 if not self.training else self.attention_dropout",
+                          "scaling=self.scaling",
+                          "attn_output = attn_output.reshape(*input_shape, -1).contiguous()",
+                          "attn_output = self.o_proj(attn_output)")
+_SOURCE_GUARDS["llama-attn"] = (_restates(
+    _LLAMA_ATTN_PARAMS,
+    "query_states = self.q_proj(hidden_states).view(hidden_shape).transpose(1, 2)",
+    "key_states = self.k_proj(hidden_states).view(hidden_shape).transpose(1, 2)",
+    *_LLAMA_ATTN_STATEMENTS), _RESTATED)
+_SOURCE_GUARDS["qwen3-attn"] = (_restates(
+    _LLAMA_ATTN_PARAMS,
+    "query_states = self.q_norm(self.q_proj(hidden_states).view(hidden_shape)).transpose(1, 2)",
+    "key_states = self.k_norm(self.k_proj(hidden_states).view(hidden_shape)).transpose(1, 2)",
+    "sliding_window=self.sliding_window",
+    *_LLAMA_ATTN_STATEMENTS), _RESTATED)
 
 
-def _llama_attention_forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
-    """transformers' LlamaAttention.forward for the training call ("dalm_sdpa", no KV cache, no dropout): the same statements with
-    apply_rotary_pos_emb + the attention call as `attention.rope_sdpa`.  Every other call goes to transformers' own forward."""
-    from . import attention
+def _norm_eps(norm) -> float:
+    return float(getattr(norm, "_dalm_eps", getattr(norm, "variance_epsilon", getattr(norm, "eps", 1e-6))))
+
+
+def _head_norm_ok(norm, hd: int) -> bool:
+    """A Qwen3RMSNorm over the head dimension: w * (x * rsqrt(mean(x^2) + eps)).to(dtype) with a plain weight [hd] - its own forward,
+    or `_native_forward` (`use_native_rms_norm`, the same formula behind its own run-time guard)."""
+    w = getattr(norm, "weight", None)
+    return (type(norm).__name__ == "Qwen3RMSNorm" and w is not None and w.dim() == 1 and w.shape[0] == hd
+            and (hasattr(norm, "variance_epsilon") or hasattr(norm, "_dalm_eps")))
+
+
+def _decoder_attention_forward(self, hidden_states, position_embeddings, attention_mask, past_key_values, kwargs, norms, window):
+    """transformers' LlamaAttention.forward / Qwen3Attention.forward for the training call ("dalm_sdpa", no KV cache, no dropout, no
+    sliding window): the same statements with (the head norms +) apply_rotary_pos_emb + the attention call as one node.  Every
+    other call goes to transformers' own forward.  The two classes differ in
+      norms   None, or Qwen3's (q_norm, k_norm) between the projections and the rotation;
+      window  the keyword Qwen3 adds to the attention call, `{"sliding_window": ...}`; `{}` for Llama."""
+    from . import attention, tower_ops
 
     cfg = self.config
     if (past_key_values is not None or position_embeddings is None or getattr(cfg, "_attn_implementation", None) != attention.NAME
             or (self.training and float(getattr(self, "attention_dropout", 0.0)) != 0.0)
+            or window.get("sliding_window") is not None
             or _off("DALM_FAST_ROPE") or _off("DALM_ATTN_KERNEL") or kwargs.get("output_attentions")):
         return self._dalm_orig_attn_forward(hidden_states, position_embeddings=position_embeddings, attention_mask=attention_mask,
                                             past_key_values=past_key_values, **kwargs)
     input_shape = hidden_states.shape[:-1]
     hidden_shape = (*input_shape, -1, self.head_dim)
-    query_states = self.q_proj(hidden_states).view(hidden_shape).transpose(1, 2)
-    key_states = self.k_proj(hidden_states).view(hidden_shape).transpose(1, 2)
+    query_raw = self.q_proj(hidden_states).view(hidden_shape)
+    key_raw = self.k_proj(hidden_states).view(hidden_shape)
     value_states = self.v_proj(hidden_states).view(hidden_shape).transpose(1, 2)
     cos, sin = position_embeddings
-    causal = bool(query_states.shape[2] > 1 and attention_mask is None and getattr(self, "is_causal", True))
-    if attention.packed_of(attention_mask) is not None:
-        # packed (un-padded) call (dalm_amd/packed.py): [1, H, n, hd] views, sequences from the descriptor; same node
-        fused = ((attention.packed_supported(query_states, key_states, value_states)
-                  or attention.grouped_supported(query_states, key_states, value_states, packed=True))
-                 and attention.rope_fusable(query_states, key_states, cos, sin))
-    else:                                            # equal heads, or grouped-query heads left un-expanded (same node)
-        fused = ((attention.supported(query_states, key_states, value_states, attention_mask, 0.0, causal, {})
-                  or attention.grouped_supported(query_states, key_states, value_states, attention_mask, 0.0, causal, {}))
-                 and attention.rope_fusable(query_states, key_states, cos, sin))
-    if fused:
-        attn_output = attention.rope_sdpa(query_states, key_states, value_states, cos, sin, attention_mask, float(self.scaling), causal)
-        attn_output = attn_output.transpose(1, 2)
-    else:                                            # CPU tensors, one KV head, head width 32, ...: transformers' own sequence from here on
+    q_t, k_t = query_raw.transpose(1, 2), key_raw.transpose(1, 2)          # [B, H, T, hd] views, in front of the norms
+    causal = bool(q_t.shape[2] > 1 and attention_mask is None and getattr(self, "is_causal", True))
+    # padded or packed (dalm_amd/packed.py: [1, H, n, hd] views, sequences from the descriptor), equal heads or grouped-query
+    # heads left un-expanded: the same node
+    fused = (attention.node_supported(q_t, k_t, value_states, attention_mask, causal)
+             and attention.rope_fusable(q_t, k_t, cos, sin))
+    qn, kn = norms or (None, None)
+    if fused and norms is not None:
+        fused = (_head_norm_ok(qn, self.head_dim) and _head_norm_ok(kn, self.head_dim)
+                 and tower_ops.head_norm_rope_supported(q_t, k_t, qn.weight, kn.weight, cos, sin))
+    if fused and norms is None:
+        attn_output = attention.rope_sdpa(q_t, k_t, value_states, cos, sin, attention_mask, float(self.scaling), causal)
+    elif fused:
+        attn_output = attention.norm_rope_sdpa(q_t, k_t, value_states, qn.weight, kn.weight, _norm_eps(qn), _norm_eps(kn), cos, sin,
+                                               attention_mask, float(self.scaling), causal)
+    else:                      # CPU tensors, fp32, one KV head, other head widths, ...: transformers' own sequence from here on
         import importlib
 
         from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
 
+        if norms is not None:
+            q_t, k_t = qn(query_raw).transpose(1, 2), kn(key_raw).transpose(1, 2)
         rope = importlib.import_module(type(self).__module__).apply_rotary_pos_emb
-        query_states, key_states = rope(query_states, key_states, cos, sin)
+        query_states, key_states = rope(q_t, k_t, cos, sin)
         attn_output, _ = ALL_ATTENTION_FUNCTIONS[cfg._attn_implementation](
-            self, query_states, key_states, value_states, attention_mask, dropout=0.0, scaling=self.scaling, **kwargs)
+            self, query_states, key_states, value_states, attention_mask, dropout=0.0, scaling=self.scaling, **window, **kwargs)
+    if fused:
+        attn_output = attn_output.transpose(1, 2)
     attn_output = attn_output.reshape(*input_shape, -1).contiguous()
     return self.o_proj(attn_output), None
+
+
+def _llama_attention_forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
+    """LlamaAttention.forward: rotary + attention as `attention.rope_sdpa`."""
+    return _decoder_attention_forward(self, hidden_states, position_embeddings, attention_mask, past_key_values, kwargs, None, {})
+
+
+def _qwen3_attention_forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
+    """Qwen3Attention.forward: q_norm + k_norm + rotary + attention as `attention.norm_rope_sdpa`."""
+    return _decoder_attention_forward(self, hidden_states, position_embeddings, attention_mask, past_key_values, kwargs,
+                                      (self.q_norm, self.k_norm), {"sliding_window": getattr(self, "sliding_window", None)})
+
+
+def _use_attention_node(model: torch.nn.Module, name: str, attrs: tuple, guard: str, forward) -> int:
+    from . import attention
+
+    if getattr(getattr(model, "config", None), "_attn_implementation", None) != attention.NAME:
+        return 0
+    return _install(model, (name,), lambda mod: all(hasattr(mod, a) for a in attrs), guard, forward, keep="_dalm_orig_attn_forward")
 
 
 def use_llama_attention_node(model: torch.nn.Module) -> int:
     """Patch LlamaAttention modules of a model that runs on "dalm_sdpa" (models/attention.py) and whose forward is the code
     `_llama_attention_forward` restates.  Returns the count."""
-    from . import attention
-
-    if getattr(getattr(model, "config", None), "_attn_implementation", None) != attention.NAME:
-        return 0
-    n = 0
-    for mod in model.modules():
-        if type(mod).__name__ != "LlamaAttention" or not all(hasattr(mod, a) for a in ("q_proj", "k_proj", "v_proj", "o_proj", "scaling")):
-            continue
-        if not _llama_attention_matches(type(mod)):
-            continue
-        mod._dalm_orig_attn_forward = mod.forward
-        mod.forward = types.MethodType(_llama_attention_forward, mod)
-        n += 1
-    return n
+    return _use_attention_node(model, "LlamaAttention", ("q_proj", "k_proj", "v_proj", "o_proj", "scaling"), "llama-attn",
+                               _llama_attention_forward)
 
 
-def _llama_attention_matches(cls) -> bool:
-    key = ("llama-attn", cls)
-    if key not in _checked:
-        try:
-            import inspect
-
-            params = list(inspect.signature(cls.forward).parameters)
-            src = inspect.getsource(cls.forward)
-            _checked[key] = (params == _LLAMA_ATTN_PARAMS
-                             and "query_states = self.q_proj(hidden_states).view(hidden_shape).transpose(1, 2)" in src
-                             and "key_states = self.k_proj(hidden_states).view(hidden_shape).transpose(1, 2)" in src
-                             and "value_states = self.v_proj(hidden_states).view(hidden_shape).transpose(1, 2)" in src
-                             and "query_states, key_states = apply_rotary_pos_emb(query_states, key_states, cos, sin)" in src
-                             and "dropout=0.0 if not self.training else self.attention_dropout" in src
-                             and "scaling=self.scaling" in src
-                             and "attn_output = attn_output.reshape(*input_shape, -1).contiguous()" in src
-                             and "attn_output = self.o_proj(attn_output)" in src)
-        except Exception:
-            _checked[key] = False
-        if not _checked[key]:
-            _warn_once("llama-attn", "LlamaAttention.forward is not the code this patch restates: transformers' own code stays "
-                       "in place")
-    return _checked[key]
+def use_qwen3_attention_node(model: torch.nn.Module) -> int:
+    """Patch Qwen3Attention modules of a model that runs on "dalm_sdpa" (models/attention.py) and whose forward is the code
+    `_qwen3_attention_forward` restates.  Returns the count."""
+    return _use_attention_node(model, "Qwen3Attention", ("q_proj", "k_proj", "v_proj", "o_proj", "q_norm", "k_norm", "scaling",
+                                                         "sliding_window"), "qwen3-attn", _qwen3_attention_forward)
 
 
 # ---------------------------------------------------------------------------
@@ -670,10 +663,6 @@ def _llama_attention_matches(cls) -> bool:
 # ---------------------------------------------------------------------------
 _LLAMA_LAYER_PARAMS = ["self", "hidden_states", "attention_mask", "position_ids", "past_key_values", "use_cache",
                        "position_embeddings", "kwargs"]
-
-
-def _norm_eps(norm) -> float:
-    return float(getattr(norm, "_dalm_eps", getattr(norm, "variance_epsilon", getattr(norm, "eps", 1e-6))))
 
 
 def _llama_layer_forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_values=None, use_cache=False,
@@ -698,166 +687,36 @@ def _llama_layer_forward(self, hidden_states, attention_mask=None, position_ids=
     return residual + self.mlp(normed)
 
 
+
+
 def use_fused_residual_norm(model: torch.nn.Module) -> int:
-    """Patch LlamaDecoderLayer modules whose forward has the signature this file was written against (transformers 5.x);
-    DALM_NORM_KERNEL=0 disables.  Returns how many layers were patched."""
+    """Patch LlamaDecoderLayer / Qwen3DecoderLayer modules whose forward has the signature this file was written against
+    (transformers 5.x; Qwen3's is also compared statement for statement); DALM_NORM_KERNEL=0 disables.  Returns how many layers
+    were patched."""
     if _off("DALM_NORM_KERNEL"):
         return 0
-    import inspect
 
-    n = 0
-    for mod in model.modules():
-        if type(mod).__name__ not in ("LlamaDecoderLayer", "Qwen3DecoderLayer"):
-            continue
-        try:
-            params = [p if p != "kwargs" else "kwargs" for p in inspect.signature(type(mod).forward).parameters]
-        except (TypeError, ValueError):
-            continue
-        if params != _LLAMA_LAYER_PARAMS:
-            continue
-        if type(mod).__name__ == "Qwen3DecoderLayer" and not _qwen3_layer_matches(type(mod)):
-            continue
-        ok = True
-        for name in ("input_layernorm", "post_attention_layernorm"):
-            nm = getattr(mod, name, None)
-            if nm is None or not type(nm).__name__.endswith("RMSNorm") or getattr(nm, "weight", None) is None \
-                    or nm.weight.dim() != 1 or "Gemma" in type(nm).__name__:
-                ok = False
-        if not ok or not all(hasattr(mod, a) for a in ("self_attn", "mlp")):
-            continue
-        mod._dalm_orig_forward = mod.forward
-        mod.forward = types.MethodType(_llama_layer_forward, mod)
-        n += 1
-    return n
+    def plain_rms_norm(nm) -> bool:
+        return (nm is not None and type(nm).__name__.endswith("RMSNorm") and getattr(nm, "weight", None) is not None
+                and nm.weight.dim() == 1 and "Gemma" not in type(nm).__name__)
+
+    def two_norms(mod) -> bool:
+        return (plain_rms_norm(getattr(mod, "input_layernorm", None)) and plain_rms_norm(getattr(mod, "post_attention_layernorm", None))
+                and all(hasattr(mod, a) for a in ("self_attn", "mlp")))
+
+    return sum(_install(model, (name,), two_norms, guard, _llama_layer_forward, keep="_dalm_orig_forward")
+               for name, guard in (("LlamaDecoderLayer", "llama-layer"), ("Qwen3DecoderLayer", "qwen3-layer")))
 
 
-def _qwen3_layer_matches(cls) -> bool:
-    """Qwen3DecoderLayer.forward must be, statement for statement, the LlamaDecoderLayer.forward `_llama_layer_forward` restates."""
-    key = ("qwen3-layer", cls)
-    if key not in _checked:
-        try:
-            import inspect
-
-            src = inspect.getsource(cls.forward)
-            body = [ln.strip() for ln in src.splitlines() if ln.strip() and not ln.strip().startswith("#")]
-            stmts = ["residual = hidden_states", "hidden_states = self.input_layernorm(hidden_states)",
+_SOURCE_GUARDS["llama-layer"] = (_restates(_LLAMA_LAYER_PARAMS), _RESTATED)
+# Qwen3DecoderLayer.forward must be, statement for statement, the LlamaDecoderLayer.forward `_llama_layer_forward` restates: the
+# whole body, behind the signature
+_QWEN3_LAYER_BODY = ["residual = hidden_states", "hidden_states = self.input_layernorm(hidden_states)",
                      "hidden_states, _ = self.self_attn(", "hidden_states=hidden_states,", "attention_mask=attention_mask,",
                      "position_ids=position_ids,", "past_key_values=past_key_values,", "use_cache=use_cache,",
                      "position_embeddings=position_embeddings,", "**kwargs,", ")", "hidden_states = residual + hidden_states",
                      "residual = hidden_states", "hidden_states = self.post_attention_layernorm(hidden_states)",
                      "hidden_states = self.mlp(hidden_states)", "hidden_states = residual + hidden_states", "return hidden_states"]
-            _checked[key] = body[-len(stmts):] == stmts and body[-len(stmts) - 1].startswith(")")   # the whole body, behind the signature
-        except Exception:
-            _checked[key] = False
-        if not _checked[key]:
-            _warn_once("qwen3-layer", "Qwen3DecoderLayer.forward is not the code this patch restates: transformers' own code stays "
-                       "in place")
-    return _checked[key]
-
-
-# ---------------------------------------------------------------------------
-# Qwen3 attention: q_norm / k_norm over the head dimension + rotary embedding + attention as ONE autograd node
-# ---------------------------------------------------------------------------
-def _head_norm_ok(norm, hd: int) -> bool:
-    """A Qwen3RMSNorm over the head dimension: w * (x * rsqrt(mean(x^2) + eps)).to(dtype) with a plain weight [hd] - its own forward,
-    or `_native_forward` (`use_native_rms_norm`, the same formula behind its own run-time guard)."""
-    w = getattr(norm, "weight", None)
-    return (type(norm).__name__ == "Qwen3RMSNorm" and w is not None and w.dim() == 1 and w.shape[0] == hd
-            and (hasattr(norm, "variance_epsilon") or hasattr(norm, "_dalm_eps")))
-
-
-def _qwen3_attention_forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
-    """transformers' Qwen3Attention.forward for the training call ("dalm_sdpa", no KV cache, no dropout, no sliding window): the
-    same statements with q_norm + k_norm + apply_rotary_pos_emb + the attention call as `attention.norm_rope_sdpa`.  Every
-    other call goes to transformers' own forward."""
-    from . import attention, tower_ops
-
-    cfg = self.config
-    if (past_key_values is not None or position_embeddings is None or getattr(cfg, "_attn_implementation", None) != attention.NAME
-            or (self.training and float(getattr(self, "attention_dropout", 0.0)) != 0.0)
-            or getattr(self, "sliding_window", None) is not None
-            or _off("DALM_FAST_ROPE") or _off("DALM_ATTN_KERNEL") or kwargs.get("output_attentions")):
-        return self._dalm_orig_attn_forward(hidden_states, position_embeddings=position_embeddings, attention_mask=attention_mask,
-                                            past_key_values=past_key_values, **kwargs)
-    input_shape = hidden_states.shape[:-1]
-    hidden_shape = (*input_shape, -1, self.head_dim)
-    query_raw = self.q_proj(hidden_states).view(hidden_shape)
-    key_raw = self.k_proj(hidden_states).view(hidden_shape)
-    value_states = self.v_proj(hidden_states).view(hidden_shape).transpose(1, 2)
-    cos, sin = position_embeddings
-    q_t, k_t = query_raw.transpose(1, 2), key_raw.transpose(1, 2)          # pre-norm [B, H, T, hd] views
-    causal = bool(q_t.shape[2] > 1 and attention_mask is None and getattr(self, "is_causal", True))
-    qn, kn = self.q_norm, self.k_norm
-    fused = (_head_norm_ok(qn, self.head_dim) and _head_norm_ok(kn, self.head_dim)
-             and tower_ops.head_norm_rope_supported(q_t, k_t, qn.weight, kn.weight, cos, sin)
-             and attention.rope_fusable(q_t, k_t, cos, sin))
-    if fused and attention.packed_of(attention_mask) is not None:
-        fused = (attention.packed_supported(q_t, k_t, value_states)
-                 or attention.grouped_supported(q_t, k_t, value_states, packed=True))
-    elif fused:
-        fused = (attention.supported(q_t, k_t, value_states, attention_mask, 0.0, causal, {})
-                 or attention.grouped_supported(q_t, k_t, value_states, attention_mask, 0.0, causal, {}))
-    if fused:
-        attn_output = attention.norm_rope_sdpa(q_t, k_t, value_states, qn.weight, kn.weight, _norm_eps(qn), _norm_eps(kn), cos, sin,
-                                               attention_mask, float(self.scaling), causal)
-        attn_output = attn_output.transpose(1, 2)
-    else:                                            # CPU tensors, fp32, other head widths, ...: transformers' own sequence from here on
-        import importlib
-
-        from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
-
-        query_states = qn(query_raw).transpose(1, 2)
-        key_states = kn(key_raw).transpose(1, 2)
-        rope = importlib.import_module(type(self).__module__).apply_rotary_pos_emb
-        query_states, key_states = rope(query_states, key_states, cos, sin)
-        attn_output, _ = ALL_ATTENTION_FUNCTIONS[cfg._attn_implementation](
-            self, query_states, key_states, value_states, attention_mask, dropout=0.0, scaling=self.scaling,
-            sliding_window=self.sliding_window, **kwargs)
-    attn_output = attn_output.reshape(*input_shape, -1).contiguous()
-    return self.o_proj(attn_output), None
-
-
-def use_qwen3_attention_node(model: torch.nn.Module) -> int:
-    """Patch Qwen3Attention modules of a model that runs on "dalm_sdpa" (models/attention.py) and whose forward is the code
-    `_qwen3_attention_forward` restates.  Returns the count."""
-    from . import attention
-
-    if getattr(getattr(model, "config", None), "_attn_implementation", None) != attention.NAME:
-        return 0
-    n = 0
-    for mod in model.modules():
-        if type(mod).__name__ != "Qwen3Attention" or not all(hasattr(mod, a) for a in ("q_proj", "k_proj", "v_proj", "o_proj", "q_norm",
-                                                                                         "k_norm", "scaling", "sliding_window")):
-            continue
-        if not _qwen3_attention_matches(type(mod)):
-            continue
-        mod._dalm_orig_attn_forward = mod.forward
-        mod.forward = types.MethodType(_qwen3_attention_forward, mod)
-        n += 1
-    return n
-
-
-def _qwen3_attention_matches(cls) -> bool:
-    key = ("qwen3-attn", cls)
-    if key not in _checked:
-        try:
-            import inspect
-
-            params = list(inspect.signature(cls.forward).parameters)
-            src = inspect.getsource(cls.forward)
-            _checked[key] = (params == _LLAMA_ATTN_PARAMS
-                             and "query_states = self.q_norm(self.q_proj(hidden_states).view(hidden_shape)).transpose(1, 2)" in src
-                             and "key_states = self.k_norm(self.k_proj(hidden_states).view(hidden_shape)).transpose(1, 2)" in src
-                             and "value_states = self.v_proj(hidden_states).view(hidden_shape).transpose(1, 2)" in src
-                             and "query_states, key_states = apply_rotary_pos_emb(query_states, key_states, cos, sin)" in src
-                             and "dropout=0.0 if not self.training else self.attention_dropout" in src
-                             and "scaling=self.scaling" in src
-                             and "sliding_window=self.sliding_window" in src
-                             and "attn_output = attn_output.reshape(*input_shape, -1).contiguous()" in src
-                             and "attn_output = self.o_proj(attn_output)" in src)
-        except Exception:
-            _checked[key] = False
-        if not _checked[key]:
-            _warn_once("qwen3-attn:" + cls.__name__, f"{cls.__name__}.forward is not the code this patch restates: transformers' own "
-                       "code stays in place")
-    return _checked[key]
+_SOURCE_GUARDS["qwen3-layer"] = (
+    lambda params, src: (params == _LLAMA_LAYER_PARAMS and _body(src)[-len(_QWEN3_LAYER_BODY):] == _QWEN3_LAYER_BODY
+                         and _body(src)[-len(_QWEN3_LAYER_BODY) - 1].startswith(")")), _RESTATED)

@@ -43,8 +43,7 @@ class LoRALinear(nn.Module):
         self.lora_B["default"].weight = nn.Parameter(torch.zeros(r, base.out_features, device=dev, dtype=torch.float32).t())
         self.merged = False
         self._group = None            # LoRAGroup of the projections that read the same input (build_groups)
-        LoRALinear._count += 1
-        self._uid = LoRALinear._count
+        dropout_uid(self)             # this module's number in its dropout salts, drawn at construction
 
     _count = 0
 
@@ -91,12 +90,10 @@ class LoRALinear(nn.Module):
         return self._eager_branch(self.base_layer(x), x)
 
     def next_mask_key(self):
-        """(p, salt) of this call.  salt: this module's id in the upper bits, a host call counter below it (graph replays re-use
-        the captured salt; there the device-side seed word, advanced once per step, changes the masks)."""
+        """(p, salt) of this call (`dropout_salt` over the call counter `_calls`)."""
         drop = self.lora_dropout["default"]
         p = float(getattr(drop, "p", 0.0)) if self.training else 0.0
-        self._calls = getattr(self, "_calls", 0) + 1
-        return p, (self._uid << 12) ^ (self._calls & 0xFFF)
+        return p, dropout_salt(self, "_calls")
 
     def _eager_branch(self, out: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
         a, b = self.lora_A["default"], self.lora_B["default"]
@@ -116,15 +113,24 @@ class LoRALinear(nn.Module):
 
 
 def dropout_uid(module: nn.Module) -> int:
-    """The number the attention and BERT add-norm dropout kernels put above their call counter in the salt: drawn on the module's
-    first masked call from the counter that numbers the LoRALinear modules (`_uid`), so no two dropout sites share one.  Fixed by
-    construction and call order, so the same program draws the same masks every run (an `id()` is an address and differs from
-    run to run)."""
+    """The number a dropout site (a LoRALinear, an attention module, a BERT add-norm module) puts above its call counter in the
+    salt: drawn from one counter - by a LoRALinear when it is built, by the others on their first masked call - so no two sites
+    share one.  Fixed by construction and call order, so the same program draws the same masks every run (an `id()` is an address
+    and differs from run to run)."""
     uid = getattr(module, "_dalm_uid", None)
     if uid is None:
         LoRALinear._count += 1
         uid = module._dalm_uid = LoRALinear._count
     return uid
+
+
+def dropout_salt(module: nn.Module, counter_attr: str) -> int:
+    """The salt of the module's next masked call: its number in the upper bits, the host call counter `counter_attr` (bumped here)
+    in the 12 below.  Graph replays re-use the captured salt; there the device-side seed word, advanced once per step, changes
+    the masks."""
+    calls = getattr(module, counter_attr, 0) + 1
+    setattr(module, counter_attr, calls)
+    return (dropout_uid(module) << 12) ^ (calls & 0xFFF)
 
 
 # ---- projections that read the same input ------------------------------------------------------------------------------

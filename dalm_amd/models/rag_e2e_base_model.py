@@ -90,17 +90,28 @@ def decoder_only(lm, T: Optional[int] = None) -> bool:
     return window is None or window >= (getattr(cfg, "max_position_embeddings", 1 << 30) if T is None else T)
 
 
-def use_causal_retriever_fast_paths(lm) -> None:
-    """The generator's row-wise layer nodes on a causal-LM retriever (each has its own guards and leaves other models alone):
-    native RMSNorm, roll-rope, SwiGLU, fused residual + norm, "dalm_sdpa".  Roll-rope patches Llama's modeling code only and
-    fused residual + norm Llama's and Qwen3's: on mistral / qwen2 they do nothing.  The rotary + attention nodes
-    (`use_llama_attention_node`, `use_qwen3_attention_node`) are not applied to retrievers: rotary and attention - and a Qwen3
-    layer's q_norm / k_norm - run as separate nodes there: DESIGN.md section 5.3 says why."""
-    use_native_rms_norm(lm)
-    use_roll_rope(lm)
-    use_swiglu_kernel(lm)
-    use_fused_residual_norm(lm)
-    use_hip_attention_backward(lm)
+# The installers a tower gets, in the order they run (each has its own guards and leaves other models alone).  The order matters:
+# `use_capturable_falcon_heads` reads "sdpa" before `use_hip_attention_backward` can change it, and the attention-node installers
+# need "dalm_sdpa" to be set already.
+_ROW_WISE_PATHS = (use_native_rms_norm, use_roll_rope, use_swiglu_kernel, use_fused_residual_norm)
+_RETRIEVER_PATHS = _ROW_WISE_PATHS + (use_hip_attention_backward,)
+_GENERATOR_PATHS = _ROW_WISE_PATHS + (use_capturable_falcon_heads, use_falcon_layer_kernels, use_falcon_attention_kernels,
+                                      use_hip_attention_backward, use_llama_attention_node, use_qwen3_attention_node)
+
+
+def use_causal_retriever_fast_paths(lm) -> dict:
+    """The generator's row-wise layer nodes on a causal-LM retriever: native RMSNorm, roll-rope, SwiGLU, fused residual + norm,
+    "dalm_sdpa".  Roll-rope patches Llama's modeling code only and fused residual + norm Llama's and Qwen3's: on mistral /
+    qwen2 they do nothing.  The rotary + attention nodes (`use_llama_attention_node`, `use_qwen3_attention_node`) are not
+    applied to retrievers: rotary and attention - and a Qwen3 layer's q_norm / k_norm - run as separate nodes there: DESIGN.md
+    section 5.3 says why.  Returns what each installer returned, by its name."""
+    return {use.__name__: use(lm) for use in _RETRIEVER_PATHS}
+
+
+def use_generator_fast_paths(lm) -> dict:
+    """Every tower patch of a generator: the retriever's list, the three Falcon installers and the two rotary + attention
+    nodes.  Returns what each installer returned, by its name."""
+    return {use.__name__: use(lm) for use in _GENERATOR_PATHS}
 
 
 class AutoModelForRagE2E(torch.nn.Module):
@@ -152,16 +163,7 @@ class AutoModelForRagE2E(torch.nn.Module):
             r_tok.pad_token = r_tok.eos_token
         self.normalize = normalize
         self.retriever_is_autoregressive = autoregressive
-        use_native_rms_norm(self.generator_model)
-        use_roll_rope(self.generator_model)
-        use_swiglu_kernel(self.generator_model)
-        use_fused_residual_norm(self.generator_model)
-        use_capturable_falcon_heads(self.generator_model)
-        use_falcon_layer_kernels(self.generator_model)
-        use_falcon_attention_kernels(self.generator_model)
-        use_hip_attention_backward(self.generator_model)
-        use_llama_attention_node(self.generator_model)
-        use_qwen3_attention_node(self.generator_model)
+        use_generator_fast_paths(self.generator_model)
         if autoregressive:
             use_causal_retriever_fast_paths(self.retriever_model)
         else:

@@ -456,3 +456,31 @@ def test_multi_query_shared_head_through_stride0_views(dev, packed_mode):
     assert torch.equal(o_mqa, o_ref)                                   # the same kernel on the same values
     assert _rel(g_mqa[..., :H, :], g_ref[..., :H, :]) < 1e-6           # dq: identical launches
     assert _rel(g_mqa[..., H:, :], g_ref[..., H:, :]) < 4e-3           # dk, dv: per-head bf16 gradients summed over the heads
+
+
+@pytest.mark.parametrize("Hkv,hd,dtype,takes", [(4, 64, torch.bfloat16, True), (2, 128, torch.bfloat16, True),
+                                                (4, 32, torch.bfloat16, True), (2, 32, torch.bfloat16, False),
+                                                (4, 64, torch.float32, False), (1, 64, torch.bfloat16, False)],
+                         ids=["equal-hd64", "grouped-hd128", "equal-hd32", "grouped-hd32", "fp32", "one-kv-head"])
+def test_node_supported_is_the_four_way_route_expression(dev, Hkv, hd, dtype, takes):
+    """`attention.node_supported` against the expression the patched forwards used to spell out, padded under a boolean mask,
+    padded and causal without one, and packed.  No kernel runs beyond the packed descriptor's."""
+    from dalm_amd import packed
+    from dalm_amd.models import attention
+
+    B, H, T = 2, 4, 64
+    g = torch.Generator().manual_seed(0)
+    q, k, v = [torch.randn(B, h, T, hd, generator=g).to(dev, dtype).requires_grad_(True) for h in (H, Hkv, Hkv)]
+    mask = _hf_mask(B, T, [0, 9], dev)
+    assert mask.dtype == torch.bool and tuple(mask.shape) == (B, 1, T, T)
+    for m, causal in ((mask, False), (None, True)):
+        want = (attention.supported(q, k, v, m, 0.0, causal, {}) or attention.grouped_supported(q, k, v, m, 0.0, causal, {}))
+        assert attention.node_supported(q, k, v, m, causal) is want and want is takes
+
+    m2 = torch.ones(B, T, dtype=torch.long)
+    rows, cu = packed.pack_plan(m2, shifted=True, multiple=64)
+    _i, _p, desc, _v = packed.packed_inputs(torch.zeros(B, T, dtype=torch.long, device=dev), m2.to(dev), rows.to(dev), cu.to(dev), True)
+    assert packed.packed_of(desc) is not None and rows.numel() == B * T
+    qp, kp, vp = [t.transpose(1, 2).reshape(1, B * T, t.shape[1], hd).transpose(1, 2) for t in (q, k, v)]     # [1, H, n, hd]
+    want = attention.packed_supported(qp, kp, vp) or attention.grouped_supported(qp, kp, vp, packed=True)
+    assert attention.node_supported(qp, kp, vp, desc, False) is want and want is takes

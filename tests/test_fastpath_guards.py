@@ -254,3 +254,56 @@ def test_falcon_attention_patch_is_refused_on_other_code():
     finally:
         cls.forward = orig
         fastpath._checked.clear()
+
+
+def test_source_guard_helper_on_a_toy_class():
+    """`_source_guard`: yes on the source it was written against; no, with exactly one warning and a memoised answer, on a
+    changed source; no, without raising, where the source cannot be read at all."""
+    from dalm_amd.models import fastpath
+
+    asked = []
+
+    def check(params, src):
+        asked.append(params)
+        return params == ["self", "x"] and "y = x + 1" in src and "return y" in src
+
+    class Toy:
+        def forward(self, x):
+            y = x + 1
+            return y
+
+    stock = Toy
+
+    class Toy:                                               # same name, another body
+        def forward(self, x):
+            y = x + 2
+            return y
+
+    changed = Toy
+    scope = {}
+    exec("forward = lambda self, x: x + 1", scope)           # no file behind it: inspect.getsource raises OSError
+    unreadable = [type("Toy", (), {"forward": scope["forward"]}), type("Toy", (), {"forward": len})]      # len: TypeError
+
+    def ask(cls):
+        with warnings.catch_warnings(record=True) as w:
+            warnings.simplefilter("always")
+            ok = fastpath._source_guard("toy", cls, check, "y = x + 1 here")
+        return ok, [str(m.message) for m in w]
+
+    try:
+        fastpath._warned.clear()
+        assert ask(stock) == (True, []) and len(asked) == 1
+        ok, msgs = ask(changed)
+        assert ok is False and len(msgs) == 1 and len(asked) == 2
+        assert "Toy.forward is not y = x + 1 here" in msgs[0] and "transformers' own code stays in place" in msgs[0]
+        assert ask(changed) == (False, []) and len(asked) == 2            # silent, and answered from the memo
+        assert ask(stock) == (True, []) and len(asked) == 2
+        for cls in unreadable:
+            fastpath._warned.clear()
+            ok, msgs = ask(cls)
+            assert ok is False and len(msgs) == 1 and len(asked) == 2     # the check itself is never reached
+            assert ask(cls) == (False, [])
+    finally:
+        for key in [k for k in fastpath._checked if k[0] == "toy"]:
+            del fastpath._checked[key]
+        fastpath._warned.clear()

@@ -29,8 +29,9 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 def build(dev):
     from transformers import Qwen3Config, Qwen3ForCausalLM
 
-    from dalm_amd.models import attention, fastpath, lora
+    from dalm_amd.models import fastpath, lora
     from dalm_amd.models.frozen_linear import use_transposed_dgrad
+    from dalm_amd.models.rag_e2e_base_model import use_generator_fast_paths
 
     torch.manual_seed(0)
     cfg = Qwen3Config(vocab_size=1024, hidden_size=4096, intermediate_size=12288, num_hidden_layers=1, num_attention_heads=32,
@@ -54,9 +55,9 @@ def build(dev):
     fastpath.use_native_rms_norm(before)
     before = finish(before)
     routed = base
-    fastpath.use_native_rms_norm(routed)
-    assert fastpath.use_swiglu_kernel(routed) == 1 and fastpath.use_fused_residual_norm(routed) == 1
-    assert attention.use_hip_attention_backward(routed) and fastpath.use_qwen3_attention_node(routed) == 1
+    went_in = use_generator_fast_paths(routed)
+    assert went_in["use_swiglu_kernel"] == 1 and went_in["use_fused_residual_norm"] == 1
+    assert went_in["use_hip_attention_backward"] and went_in["use_qwen3_attention_node"] == 1
     routed = finish(routed)
     return routed, before
 
