@@ -16,7 +16,7 @@
 // problems), operands staged k-major in LDS so that
 // every MFMA fragment read is one conflict-free ds_read_b32 per lane.
 // MFMA-bound: 2*m*n*D flop per launch against the 157 TF f32-matrix peak.
-#include "dispatch.hpp"
+#include "sim_plan.hpp"
 #include "vec16.hpp"
 #include <stdlib.h>
 
@@ -26,7 +26,6 @@ namespace {
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 constexpr int BK_BIG = 32;    // 128x128 tiles: 33 KB LDS, 3 blocks/CU
-constexpr int BK_SMALL = 128;  // 64x64 tiles of latency-bound small problems: 4x fewer barrier rounds
 
 enum { EPI_STORE = 0, EPI_ROWSTATS = 1, EPI_DS = 2, EPI_PARTIAL = 3 };
 
@@ -398,8 +397,6 @@ struct FlashParams {
   int row_blocks, nsplit, blocks_per_split;
   int debug_hot;         // 0 from the launcher; 1 (timing experiment only) re-reads the same cached rows every step
 };
-
-constexpr int FBM = 32, FBN = 128;
 
 // X [R][K] row-major -> Xt [K][ld] with Xt[k][r] = X[r][k] for r < R, 0 for R <= r < ld.  32x32 tiles through
 // LDS; grid (ld/32, ceil(K/32), 2): blockIdx.z selects (X0 -> Xt0) or (X1 -> Xt1) so both operands go in one launch.
@@ -1037,108 +1034,61 @@ __global__ __launch_bounds__(256) void flash_reduce_kernel(const float4* __restr
   }
 }
 
-struct FlashPlan { bool ok; int nt, row_blocks, nsplit, blocks_per_split; int64_t ldm, ldn; };
-inline FlashPlan flash_plan(int64_t m, int64_t n, int64_t D) {
-  FlashPlan f{false, 0, 0, 1, 0, 0, 0};
-  if (D > 1024 || D % 128 != 0) return f;        // accumulators hold 32 x D per workgroup, D = 128 * NT
-  if ((n + 128) * D * 4 >= (1ll << 31) || (m + 32) * D * 4 >= (1ll << 31)) return f;   // 32-bit buffer offsets
-  f.nt = static_cast<int>(D / 128);
-  f.row_blocks = static_cast<int>((m + FBM - 1) / FBM);
-  const int64_t col_blocks = (n + FBN - 1) / FBN;
-  // Column split: cost model fitted to MI355X timings (us).  One workgroup alone on a CU retires a 128-column
-  // block in ~38 us (+ ~5 us of fill/drain), two co-resident ones a pair of blocks in ~66 us (+ ~15 us): two per CU
-  // wins in steady state (4096^2: 4 splits), one per CU wins when a workgroup only has a block or two
-  // (1200^2: 5 splits -> 190 workgroups instead of 10 -> 380 on 256 CUs).  Partial-output traffic is charged at 4 TB/s.
-  double best = 1e30;
-  int64_t best_ns = 1;
-  for (int64_t ns = 1; ns <= col_blocks && ns <= 64; ++ns) {
-    const int64_t bps = (col_blocks + ns - 1) / ns;
-    const int64_t real_ns = (col_blocks + bps - 1) / bps;
-    if (real_ns != ns) continue;
-    const int64_t W = static_cast<int64_t>(f.row_blocks) * ns;
-    double t;
-    if (W <= 256) t = 5.0 + 38.0 * bps;
-    else t = 15.0 + 66.0 * bps * ((W + 511) / 512);
-    if (ns > 1) t += static_cast<double>(ns) * m * D * 8.0 / 4.0e6;
-    if (t < best) { best = t; best_ns = ns; }
-  }
-  f.blocks_per_split = static_cast<int>((col_blocks + best_ns - 1) / best_ns);
-  f.nsplit = static_cast<int>(best_ns);
-  f.ldm = static_cast<int64_t>(f.row_blocks) * FBM;
-  f.ldn = col_blocks * FBN;
-  f.ok = true;
-  return f;
-}
-inline size_t flash_copy_floats(const FlashPlan& f, int64_t D) { return static_cast<size_t>(D) * (f.ldm + f.ldn); }
-
-// Streaming row statistics: used once the problem is MFMA-sized (the small-batch path and the latency-bound
-// split-K form cover everything below); any D (the k-major copies are zero-padded to a multiple of 16).
-struct StreamPlan { bool ok; int rt, row_blocks, nsplit, blocks_per_split; int64_t ldm, ldn, kpad; int ks; };
-inline StreamPlan stream_plan(int64_t m, int64_t n, int64_t D, bool always = false) {
-  StreamPlan f{false, 1, 0, 1, 0, 0, 0, 0, 1};
-  if (!always && (m * n < 512 * 512 || D < 64)) return f;
-  f.rt = (m >= 4096) ? 2 : 1;   // measured: 2048^2 86 vs 77 TF, 4096^2 100 vs 107, 16384^2 118 vs 141
-  const int64_t bm = 32 * f.rt;
-  f.row_blocks = static_cast<int>((m + bm - 1) / bm);
-  // K slices per column tile, for the sizes whose 128-column blocks give the chip only one or two workgroups per CU
-  // (grid = row blocks x column blocks; measured, whole call, us: 768^2 (144) 36.0 / 37.7 / 37.5 for 1 / 2 / 4 slices,
-  // 1200^2 (380) 57.2 / 54.0 / 56.2, 1536^2 (576) 74.3 / 76.4 / 68.1, 2048^2 (1024) 90.8 / 103.6 / 108.2).  What did NOT
-  // move these sizes (profiles/history/r03_sim_midsize_experiments.txt): 16-byte operand loads from 4-k granule copies (slower),
-  // capping workgroups per CU through LDS padding (slower), XCD rectangles + an L2 warm-up pass (no change).
-  if (!always && f.rt == 1) {
-    const int64_t g128 = static_cast<int64_t>(f.row_blocks) * ((n + 127) / 128);
-    f.ks = (g128 >= 450 && g128 < 640) ? 4 : (g128 >= 300 && g128 < 450) ? 2 : 1;
-  }
-  f.kpad = (D + 16 * f.ks - 1) / (16 * f.ks) * (16 * f.ks);
-  if ((n + 128) * f.kpad * 4 >= (1ll << 31) || (m + 64) * f.kpad * 4 >= (1ll << 31)) return f;   // 32-bit buffer offsets
-  const int64_t col_blocks = (n + FBN / f.ks - 1) / (FBN / f.ks);
-  int64_t ns = ((f.rt == 2 ? 512 : 768) + f.row_blocks - 1) / f.row_blocks;      // 2-3 workgroups per CU (by registers)
-  if (ns > col_blocks) ns = col_blocks;
-  if (ns < 1) ns = 1;
-  if (ns > 64) ns = 64;
-  f.blocks_per_split = static_cast<int>((col_blocks + ns - 1) / ns);
-  f.nsplit = static_cast<int>((col_blocks + f.blocks_per_split - 1) / f.blocks_per_split);
-  f.ldm = static_cast<int64_t>(f.row_blocks) * bm;
-  f.ldn = (n + FBN - 1) / FBN * FBN;
-  f.ok = true;
-  return f;
-}
-
 template <int BM, int BN, int BK, int EPI>
 void launch_gemm_tile(bool a_kc, bool b_kc, GemmParams p, hipStream_t s, int splitk = 1) {
   p.tiles_n = static_cast<unsigned>((p.N + BN - 1) / BN);
   p.k_chunk = (splitk <= 1) ? p.K : ((p.K + splitk - 1) / splitk + BK - 1) / BK * BK;
   const dim3 grid(p.tiles_n * static_cast<unsigned>((p.M + BM - 1) / BM), static_cast<unsigned>(splitk <= 1 ? 1 : splitk));
-  if (a_kc && b_kc) hipLaunchKernelGGL((gemm_f32_mfma_kernel<BM, BN, BK, true, true, EPI>), grid, dim3(256), 0, s, p);
-  else if (a_kc && !b_kc) hipLaunchKernelGGL((gemm_f32_mfma_kernel<BM, BN, BK, true, false, EPI>), grid, dim3(256), 0, s, p);
-  else if (!a_kc && b_kc) hipLaunchKernelGGL((gemm_f32_mfma_kernel<BM, BN, BK, false, true, EPI>), grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((gemm_f32_mfma_kernel<BM, BN, BK, false, false, EPI>), grid, dim3(256), 0, s, p);
-}
-
-// 128x128 tiles once the grid fills the chip, 64x64 below that.
-inline bool use_big_tiles(int64_t M, int64_t N) {
-  return ((M + 127) / 128) * ((N + 127) / 128) >= 128;
-}
-inline int64_t rowstats_parts(int64_t m, int64_t n) {
-  const int64_t bn = use_big_tiles(m, n) ? 128 : 64;
-  return 2 * ((n + bn - 1) / bn);
-}
-
-// Split-K for S = A.B^T problems that cannot fill 256 CUs with 64x64 tiles (the real batch sizes: 18 ... ~1200
-// rows): SK partial slabs + a one-block-per-row epilogue.  Returns 1 when the direct kernels are used.
-inline int sim_splitk(int64_t m, int64_t n, int64_t D) {
-  if (use_big_tiles(m, n)) return 1;
-  const int64_t tiles = ((m + 63) / 64) * ((n + 63) / 64);
-  if (tiles > 512 || D < 256 || n > 8192) return 1;
-  int sk = 1;
-  while (sk < 8 && tiles * sk * 2 <= 1024 && D / (sk * 2) >= BK_SMALL) sk *= 2;
-  return sk;
+  by_bool(a_kc, [&](auto akc) {
+    by_bool(b_kc, [&](auto bkc) {
+      hipLaunchKernelGGL((gemm_f32_mfma_kernel<BM, BN, BK, akc, bkc, EPI>), grid, dim3(256), 0, s, p);
+    });
+  });
 }
 
 template <int EPI>
 void launch_gemm(bool a_kc, bool b_kc, const GemmParams& p, hipStream_t s) {
   if (use_big_tiles(p.M, p.N)) launch_gemm_tile<128, 128, BK_BIG, EPI>(a_kc, b_kc, p, s);
   else launch_gemm_tile<64, 64, BK_SMALL, EPI>(a_kc, b_kc, p, s);
+}
+
+// C = alpha * A.B with A [M][K] or [K][M] of stride lda, B likewise; the epilogue's own fields are the caller's
+GemmParams gemm_params(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t K, float alpha) {
+  GemmParams p{};
+  p.A = A; p.lda = lda; p.B = B; p.ldb = ldb;
+  p.M = static_cast<int>(M); p.N = static_cast<int>(N); p.K = static_cast<int>(K);
+  p.alpha = alpha; p.a_vec = rows_aligned16(A, lda); p.b_vec = rows_aligned16(B, ldb);
+  return p;
+}
+
+// The k-major, zero-padded copies At / Bt of both operands in one launch: `kpad` rows each (the padded width of a StreamPlan,
+// D itself for a FlashPlan), and the arrival tickets of the kernel that follows zeroed on the way.  Returns that kernel's
+// parameters (StreamStatsParams or FlashParams) with the geometry every consumer shares filled in.
+template <typename Params, typename Plan>
+Params launch_copies(const Plan& f, const float* A, const float* Bm, int64_t m, int64_t n, int64_t D, int64_t kpad, float* At,
+                     float* Bt, float alpha, hipStream_t s, unsigned* tickets = nullptr) {
+  const int64_t ldmax = f.ldm > f.ldn ? f.ldm : f.ldn;
+  hipLaunchKernelGGL(transpose_pad_kernel, dim3(static_cast<unsigned>(ldmax / 32), static_cast<unsigned>((kpad + 31) / 32), 2),
+                     dim3(256), 0, s, A, static_cast<int>(m), static_cast<int>(f.ldm), At, Bm, static_cast<int>(n),
+                     static_cast<int>(f.ldn), Bt, static_cast<int>(D), static_cast<int>(kpad), tickets, tickets ? f.row_blocks : 0);
+  Params p{};
+  p.At = At; p.Bt = Bt; p.m = static_cast<int>(m); p.n = static_cast<int>(n);
+  if constexpr (std::is_same_v<Params, FlashParams>) p.D = static_cast<int>(kpad); else p.Kpad = static_cast<int>(kpad);
+  p.ldm = static_cast<int>(f.ldm); p.ldn = static_cast<int>(f.ldn); p.alpha = alpha;
+  p.row_blocks = f.row_blocks; p.nsplit = f.nsplit; p.blocks_per_split = f.blocks_per_split;
+  return p;
+}
+
+// The streaming kernel of a plan: RT = 2 row tiles per wave, or RT = 1 with KS = 1 / 2 / 4 K slices (statistics mode only)
+template <int MODE>
+void launch_stream(const StreamPlan& f, const StreamStatsParams& q, hipStream_t s) {
+  const dim3 grid(static_cast<unsigned>(f.row_blocks * f.nsplit));
+  by_exact<2, 1>(f.rt, [&](auto rt) {
+    by_exact<4, 2, 1>(MODE == MODE_STATS && f.rt == 1 ? f.ks : 1, [&](auto ks) {
+      if constexpr (ks == 1 || (MODE == MODE_STATS && rt == 1))
+        hipLaunchKernelGGL((sim_rowstats_stream_kernel<rt, MODE, ks>), grid, dim3(256), 0, s, q);
+    });
+  });
 }
 
 int check_gemm_dims(int64_t M, int64_t N, int64_t K, const char* fn) {
@@ -1161,10 +1111,7 @@ extern "C" int dalm_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64
   if (int e = check_gemm_dims(M, N, K, __func__)) return e;
   DALM_REQUIRE(lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N, DALM_E_SHAPE,
                "leading dimension too small");
-  GemmParams p{};
-  p.A = A; p.lda = lda; p.B = Bm; p.ldb = ldb;
-  p.M = static_cast<int>(M); p.N = static_cast<int>(N); p.K = static_cast<int>(K);
-  p.alpha = alpha; p.a_vec = rows_aligned16(A, lda); p.b_vec = rows_aligned16(Bm, ldb);
+  GemmParams p = gemm_params(A, lda, Bm, ldb, M, N, K, alpha);
   p.C = C; p.ldc = ldc;
   // A k-contiguous <=> not transposed; B k-contiguous <=> transposed ([N,K])
   launch_gemm<EPI_STORE>(!transA, transB != 0, p, as_stream(stream));
@@ -1182,21 +1129,13 @@ static bool use_bf16x3(int64_t m, int64_t n, int64_t D, const float* A, const fl
   // measured crossover: 2048^2 64 vs 100 TF (f32 wins), 3072^2 142 vs 122 TF (profiles/history/r04_sim_midsize_merge_inlaunch.txt)
   constexpr int64_t min_rows = 3072;
   if (m < min_rows || n < min_rows) return false;
-  if (A && (reinterpret_cast<uintptr_t>(A) % 16 || reinterpret_cast<uintptr_t>(Bm) % 16)) return false;
+  if (!aligned16(A, Bm)) return false;   // the size query passes NULL, which counts as aligned
   return dalm_sim_rowstats_bf16x3_supported(m, n, D) != 0;
-}
-
-static size_t rowstats_ws_f32(int64_t m, int64_t n, int64_t D) {
-  if (const StreamPlan f = stream_plan(m, n, D); f.ok)   // k-major copies | (max, sum) granules [nsplit][m] (8 B each) | tickets
-    return (static_cast<size_t>(f.kpad) * (f.ldm + f.ldn) + 2 * static_cast<size_t>(f.nsplit) * m + f.row_blocks + 2) * sizeof(float);
-  const int sk = sim_splitk(m, n, D);
-  if (sk > 1) return static_cast<size_t>(sk) * static_cast<size_t>(m) * static_cast<size_t>(round_up(n, 4)) * sizeof(float);
-  return static_cast<size_t>(rowstats_parts(m, n)) * static_cast<size_t>(m) * 2 * sizeof(float);
 }
 
 extern "C" size_t dalm_sim_rowstats_workspace_bytes(int64_t m, int64_t n, int64_t D) {
   if (m <= 0 || n <= 0) return 0;
-  const size_t f32 = rowstats_ws_f32(m, n, D);
+  const size_t f32 = rowstats_layout(m, n, D).total;
   if (!use_bf16x3(m, n, D, nullptr, nullptr)) return f32;
   const size_t x3 = dalm_sim_rowstats_bf16x3_workspace_bytes(m, n, D);   // an unaligned operand still takes the f32 kernel
   return x3 > f32 ? x3 : f32;
@@ -1219,72 +1158,42 @@ extern "C" int dalm_sim_rowstats_f32(const float* A, const float* Bm, int64_t m,
   DALM_REQUIRE(A && Bm && row_lse && diag && ws, DALM_E_NULL, "null pointer argument");
   if (int e = check_gemm_dims(m, n, D, __func__)) return e;
   DALM_REQUIRE(diag_offset >= 0 && diag_offset + m <= n, DALM_E_SHAPE, "diag_offset + m must be <= n");
-  DALM_REQUIRE(ws_bytes >= rowstats_ws_f32(m, n, D), DALM_E_WORKSPACE, "workspace too small");
+  const RowstatsLayout L = rowstats_layout(m, n, D);
+  DALM_REQUIRE(ws_bytes >= L.total, DALM_E_WORKSPACE, "workspace too small");
   DALM_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 4 == 0, DALM_E_ALIGN, "workspace must be 4-byte aligned");
   hipStream_t s = as_stream(stream);
-  if (const StreamPlan f = stream_plan(m, n, D); f.ok) {
-    float* At = static_cast<float*>(ws);
-    float* Bt = At + static_cast<size_t>(f.kpad) * f.ldm;
-    float* pg = Bt + static_cast<size_t>(f.kpad) * f.ldn;
-    if (reinterpret_cast<uintptr_t>(pg) % 8) ++pg;                                   // 8-byte granules
-    unsigned* tickets = reinterpret_cast<unsigned*>(pg + 2 * static_cast<size_t>(f.nsplit) * m);
-    const int64_t ldmax = f.ldm > f.ldn ? f.ldm : f.ldn;
-    hipLaunchKernelGGL(transpose_pad_kernel, dim3(static_cast<unsigned>(ldmax / 32), static_cast<unsigned>(f.kpad / 32 + (f.kpad % 32 != 0)), 2),
-                       dim3(256), 0, s, A, static_cast<int>(m), static_cast<int>(f.ldm), At, Bm, static_cast<int>(n),
-                       static_cast<int>(f.ldn), Bt, static_cast<int>(D), static_cast<int>(f.kpad), tickets, f.row_blocks);
-    StreamStatsParams q{};
-    q.At = At; q.Bt = Bt; q.m = static_cast<int>(m); q.n = static_cast<int>(n); q.Kpad = static_cast<int>(f.kpad);
-    q.ldm = static_cast<int>(f.ldm); q.ldn = static_cast<int>(f.ldn); q.alpha = scale; q.diag_offset = diag_offset;
-    q.part = reinterpret_cast<unsigned long long*>(pg); q.tickets = tickets; q.row_lse = row_lse; q.diag = diag;
-    q.row_blocks = f.row_blocks; q.nsplit = f.nsplit; q.blocks_per_split = f.blocks_per_split;
-    const dim3 grid(static_cast<unsigned>(f.row_blocks * f.nsplit));
-    if (f.rt == 2) hipLaunchKernelGGL((sim_rowstats_stream_kernel<2, MODE_STATS>), grid, dim3(256), 0, s, q);
-    else if (f.ks == 4) hipLaunchKernelGGL((sim_rowstats_stream_kernel<1, MODE_STATS, 4>), grid, dim3(256), 0, s, q);
-    else if (f.ks == 2) hipLaunchKernelGGL((sim_rowstats_stream_kernel<1, MODE_STATS, 2>), grid, dim3(256), 0, s, q);
-    else hipLaunchKernelGGL((sim_rowstats_stream_kernel<1, MODE_STATS>), grid, dim3(256), 0, s, q);
-    return check_launch(__func__);      // (the merge of the column splits happens inside the kernel since round 4)
+  if (L.f.ok) {
+    char* base = align_up(ws, 8);                                                    // 8-byte granules
+    unsigned* tickets = region<unsigned>(base, L.tickets);
+    StreamStatsParams q = launch_copies<StreamStatsParams>(L.f, A, Bm, m, n, D, L.f.kpad, region(base, L.at), region(base, L.bt),
+                                                           scale, s, tickets);
+    q.diag_offset = diag_offset; q.part = region<unsigned long long>(base, L.part); q.tickets = tickets;
+    q.row_lse = row_lse; q.diag = diag;
+    launch_stream<MODE_STATS>(L.f, q, s);   // (the merge of the column splits happens inside the kernel since round 4)
+    return check_launch(__func__);
   }
-  const int64_t P = rowstats_parts(m, n);
-  GemmParams p{};
-  p.A = A; p.lda = D; p.B = Bm; p.ldb = D;
-  p.M = static_cast<int>(m); p.N = static_cast<int>(n); p.K = static_cast<int>(D);
-  p.alpha = scale; p.a_vec = rows_aligned16(A, D); p.b_vec = rows_aligned16(Bm, D);
-  if (const int sk = sim_splitk(m, n, D); sk > 1) {
-    p.C = static_cast<float*>(ws); p.ldc = round_up(n, 4);
-    launch_gemm_tile<64, 64, BK_SMALL, EPI_PARTIAL>(true, true, p, s, sk);
-    hipLaunchKernelGGL(splitk_rowstats_kernel, dim3(static_cast<unsigned>(m)), dim3(256), 0, s, p.C, sk, p.M, p.N,
+  GemmParams p = gemm_params(A, D, Bm, D, m, n, D, scale);
+  if (L.sk > 1) {
+    p.C = region(ws, L.slabs); p.ldc = L.ldc;
+    launch_gemm_tile<64, 64, BK_SMALL, EPI_PARTIAL>(true, true, p, s, L.sk);
+    hipLaunchKernelGGL(splitk_rowstats_kernel, dim3(static_cast<unsigned>(m)), dim3(256), 0, s, p.C, L.sk, p.M, p.N,
                        p.ldc, scale, diag_offset, row_lse, diag);
     return check_launch(__func__);
   }
-  p.part_m = static_cast<float*>(ws);
-  p.part_l = p.part_m + P * m;
+  p.part_m = region(ws, L.part_m);
+  p.part_l = region(ws, L.part_l);
   p.diag = diag; p.diag_offset = diag_offset;
   launch_gemm<EPI_ROWSTATS>(true, true, p, s);
   hipLaunchKernelGGL(rowstats_merge_kernel, dim3(static_cast<unsigned>((m + 255) / 256)), dim3(256), 0, s,
-                     p.part_m, p.part_l, static_cast<int>(P), p.M, row_lse);
+                     p.part_m, p.part_l, static_cast<int>(L.parts), p.M, row_lse);
   return check_launch(__func__);
 }
 
-
-// Which form dalm_sim_grad takes: 1 = flash (no dS panel), 0 = dS panel + NN GEMM (D > 1024 or odd D).
-static bool use_flash_grad(int64_t m, int64_t n, int64_t D) {
-  return flash_plan(m, n, D).ok;
-}
-
+// dalm_sim_grad takes the flash form (no dS panel) wherever flash_plan accepts the shape, else dS panel + NN GEMM (D > 1024 or
+// odd D): grad_layout carries the choice.
 extern "C" size_t dalm_sim_grad_workspace_bytes(int64_t m, int64_t n, int64_t D) {
   if (m <= 0 || n <= 0) return 0;
-  if (use_flash_grad(m, n, D)) {
-    const FlashPlan f = flash_plan(m, n, D);   // k-major operand copies (+ per-split partial outputs)
-    return (flash_copy_floats(f, D) + (f.nsplit > 1 ? static_cast<size_t>(f.nsplit) * m * D : 0)) * sizeof(float);
-  }
-  const size_t panel = static_cast<size_t>(m) * static_cast<size_t>(round_up(n, 4)) * sizeof(float);
-  const int sk = sim_splitk(m, n, D);
-  return panel * static_cast<size_t>(sk > 1 ? 1 + sk : 1);  // dS panel (+ split-K slabs)
-}
-
-template <int NT>
-static void launch_flash(const FlashParams& p, hipStream_t s) {
-  hipLaunchKernelGGL((sim_flash_grad_kernel<NT>), dim3(static_cast<unsigned>(p.row_blocks * p.nsplit)), dim3(256), 0, s, p);
+  return grad_layout(m, n, D).total;
 }
 
 extern "C" int dalm_sim_grad(const float* A, const float* Bm, int64_t m, int64_t n, int64_t D, float scale,
@@ -1295,37 +1204,21 @@ extern "C" int dalm_sim_grad(const float* A, const float* Bm, int64_t m, int64_t
                "null pointer argument");
   if (int e = check_gemm_dims(m, n, D, __func__)) return e;
   DALM_REQUIRE(diag_offset >= 0 && diag_offset + m <= n, DALM_E_SHAPE, "diag_offset + m must be <= n");
-  DALM_REQUIRE(ws_bytes >= dalm_sim_grad_workspace_bytes(m, n, D), DALM_E_WORKSPACE, "workspace too small");
-  DALM_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 16 == 0, DALM_E_ALIGN, "workspace must be 16-byte aligned");
+  const GradLayout L = grad_layout(m, n, D);
+  DALM_REQUIRE(ws_bytes >= L.total, DALM_E_WORKSPACE, "workspace too small");
+  DALM_REQUIRE(aligned16(ws), DALM_E_ALIGN, "workspace must be 16-byte aligned");
   hipStream_t s = as_stream(stream);
-  if (use_flash_grad(m, n, D)) {
-    DALM_REQUIRE(reinterpret_cast<uintptr_t>(dA) % 16 == 0, DALM_E_ALIGN, "dA must be 16-byte aligned");
-    const FlashPlan f = flash_plan(m, n, D);
-    float* At = static_cast<float*>(ws);
-    float* Bt = At + static_cast<size_t>(D) * f.ldm;
-    float* slabs = Bt + static_cast<size_t>(D) * f.ldn;
-    const int64_t ldmax = f.ldm > f.ldn ? f.ldm : f.ldn;
-    hipLaunchKernelGGL(transpose_pad_kernel, dim3(static_cast<unsigned>(ldmax / 32), static_cast<unsigned>((D + 31) / 32), 2),
-                       dim3(256), 0, s, A, static_cast<int>(m), static_cast<int>(f.ldm), At, Bm, static_cast<int>(n),
-                       static_cast<int>(f.ldn), Bt, static_cast<int>(D), static_cast<int>(D));
-    FlashParams p{};
-    p.At = At; p.Bt = Bt; p.B = Bm; p.m = static_cast<int>(m); p.n = static_cast<int>(n); p.D = static_cast<int>(D);
-    p.ldm = static_cast<int>(f.ldm); p.ldn = static_cast<int>(f.ldn);
-    p.alpha = scale; p.diag_offset = diag_offset;
+  if (L.f.ok) {
+    DALM_REQUIRE(aligned16(dA), DALM_E_ALIGN, "dA must be 16-byte aligned");
+    const FlashPlan& f = L.f;
+    float* slabs = region(ws, L.slabs);
+    FlashParams p = launch_copies<FlashParams>(f, A, Bm, m, n, D, D, region(ws, L.at), region(ws, L.bt), scale, s);
+    p.B = Bm; p.diag_offset = diag_offset;
     p.row_coef = row_coef; p.row_lse = row_lse; p.col_coef = col_coef; p.col_lse = col_lse;
     p.out = f.nsplit > 1 ? slabs : dA;
-    p.row_blocks = f.row_blocks; p.nsplit = f.nsplit; p.blocks_per_split = f.blocks_per_split;
-    p.debug_hot = 0;
-    switch (f.nt) {
-      case 1: launch_flash<1>(p, s); break;
-      case 2: launch_flash<2>(p, s); break;
-      case 3: launch_flash<3>(p, s); break;
-      case 4: launch_flash<4>(p, s); break;
-      case 5: launch_flash<5>(p, s); break;
-      case 6: launch_flash<6>(p, s); break;
-      case 7: launch_flash<7>(p, s); break;
-      default: launch_flash<8>(p, s); break;
-    }
+    by_exact<1, 2, 3, 4, 5, 6, 7, 8>(f.nt, [&](auto nt) {
+      hipLaunchKernelGGL((sim_flash_grad_kernel<nt>), dim3(static_cast<unsigned>(f.row_blocks * f.nsplit)), dim3(256), 0, s, p);
+    });
     if (f.nsplit > 1) {
       const int64_t n4 = m * D / 4;
       int64_t blocks = (n4 + 255) / 256;
@@ -1335,30 +1228,23 @@ extern "C" int dalm_sim_grad(const float* A, const float* Bm, int64_t m, int64_t
     }
     return check_launch(__func__);
   }
-  const int64_t ldd = round_up(n, 4);
-  float* dS = static_cast<float*>(ws);
+  float* dS = region(ws, L.ds);
   {  // dS panel: recompute S tiles on the MFMA, transform in the epilogue
-    GemmParams p{};
-    p.A = A; p.lda = D; p.B = Bm; p.ldb = D;
-    p.M = static_cast<int>(m); p.N = static_cast<int>(n); p.K = static_cast<int>(D);
-    p.alpha = scale; p.a_vec = rows_aligned16(A, D); p.b_vec = rows_aligned16(Bm, D);
-    if (const int sk = sim_splitk(m, n, D); sk > 1) {
-      float* part = dS + m * ldd;  // slabs live behind the dS panel
-      p.C = part; p.ldc = ldd;
-      launch_gemm_tile<64, 64, BK_SMALL, EPI_PARTIAL>(true, true, p, s, sk);
-      hipLaunchKernelGGL(splitk_ds_kernel, dim3(static_cast<unsigned>(m)), dim3(256), 0, s, part, sk, p.M, p.N, ldd,
-                         scale, diag_offset, row_coef, row_lse, col_coef, col_lse, dS, ldd);
+    GemmParams p = gemm_params(A, D, Bm, D, m, n, D, scale);
+    if (L.sk > 1) {
+      float* part = region(ws, L.part);  // slabs live behind the dS panel
+      p.C = part; p.ldc = L.ldd;
+      launch_gemm_tile<64, 64, BK_SMALL, EPI_PARTIAL>(true, true, p, s, L.sk);
+      hipLaunchKernelGGL(splitk_ds_kernel, dim3(static_cast<unsigned>(m)), dim3(256), 0, s, part, L.sk, p.M, p.N, L.ldd,
+                         scale, diag_offset, row_coef, row_lse, col_coef, col_lse, dS, L.ldd);
     } else {
-      p.C = dS; p.ldc = ldd; p.diag_offset = diag_offset;
+      p.C = dS; p.ldc = L.ldd; p.diag_offset = diag_offset;
       p.row_coef = row_coef; p.row_lse = row_lse; p.col_coef = col_coef; p.col_lse = col_lse;
       launch_gemm<EPI_DS>(true, true, p, s);
     }
   }
   {  // dA[m,D] = scale * dS[m,n] . B[n,D]
-    GemmParams p{};
-    p.A = dS; p.lda = ldd; p.B = Bm; p.ldb = D;
-    p.M = static_cast<int>(m); p.N = static_cast<int>(D); p.K = static_cast<int>(n);
-    p.alpha = scale; p.a_vec = rows_aligned16(dS, ldd); p.b_vec = rows_aligned16(Bm, D);
+    GemmParams p = gemm_params(dS, L.ldd, Bm, D, m, D, n, scale);
     p.C = dA; p.ldc = D;
     launch_gemm<EPI_STORE>(true, false, p, s);
   }
@@ -1432,22 +1318,9 @@ inline bool topk_use_x3(int64_t m, int64_t n, int64_t D) {
   if (const char* e = getenv("DALM_TOPK_BF16X3")) return e[0] == '1';
   return ((m + 255) / 256) * ((n + 255) / 256) >= 1024;
 }
-struct TopkLayout { StreamPlan f; int cap; size_t at, bt, gmax, thr, x3, x3_bytes, total; };
+// room for the bf16x3 operand images whenever that pass COULD be taken (the choice may be forced per call)
 inline TopkLayout topk_layout(int64_t m, int64_t n, int64_t D, int64_t k) {
-  TopkLayout L{};
-  L.f = stream_plan(m, n, D, true);
-  L.cap = static_cast<int>(8 * k + 64);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 15) / 16 * 16; return at; };
-  L.at = take(static_cast<size_t>(L.f.kpad) * L.f.ldm * 4);
-  L.bt = take(static_cast<size_t>(L.f.kpad) * L.f.ldn * 4);
-  L.gmax = take(static_cast<size_t>(m) * (L.f.ldn / 32) * 4);
-  L.thr = take(static_cast<size_t>(m) * 4);
-  // room for the bf16x3 operand images whenever that pass COULD be taken (the choice may be forced per call)
-  L.x3_bytes = dalm_sim_rowstats_bf16x3_supported(m, n, D) ? dalm_x3_group_max_workspace_bytes(m, n, D) : 0;
-  L.x3 = take(L.x3_bytes);
-  L.total = o;
-  return L;
+  return dalm::topk_layout(m, n, D, k, dalm_sim_rowstats_bf16x3_supported(m, n, D) ? dalm_x3_group_max_workspace_bytes(m, n, D) : 0);
 }
 }  // namespace
 
@@ -1472,41 +1345,30 @@ extern "C" int dalm_sim_topk(const float* Q, const float* C, int64_t m, int64_t 
   const TopkLayout L = topk_layout(m, n, D, k);
   DALM_REQUIRE(L.f.ok, DALM_E_SHAPE, "corpus block too large for 32-bit buffer offsets: search it in blocks of <= 2^19 rows");
   DALM_REQUIRE(ws_bytes >= L.total, DALM_E_WORKSPACE, "workspace too small");
-  DALM_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 16 == 0, DALM_E_ALIGN, "workspace must be 16-byte aligned");
+  DALM_REQUIRE(aligned16(ws), DALM_E_ALIGN, "workspace must be 16-byte aligned");
   // validated BEFORE anything is enqueued (dalm_sim_topk_supported is the same test for callers that want to fall back)
   DALM_REQUIRE(dalm_sim_topk_supported(D, k), DALM_E_SHAPE,
                "D and k too large for the refine kernel's LDS (padded D + 3*(8k+64) floats <= 15360)");
   hipStream_t s = as_stream(stream);
-  char* base = static_cast<char*>(ws);
-  float* At = reinterpret_cast<float*>(base + L.at);
-  float* Bt = reinterpret_cast<float*>(base + L.bt);
   const StreamPlan& f = L.f;
-  const int64_t ldmax = f.ldm > f.ldn ? f.ldm : f.ldn;
-  hipLaunchKernelGGL(transpose_pad_kernel, dim3(static_cast<unsigned>(ldmax / 32), static_cast<unsigned>((f.kpad + 31) / 32), 2),
-                     dim3(256), 0, s, Q, static_cast<int>(m), static_cast<int>(f.ldm), At, C, static_cast<int>(n),
-                     static_cast<int>(f.ldn), Bt, static_cast<int>(D), static_cast<int>(f.kpad));
-  StreamStatsParams q{};
-  q.At = At; q.Bt = Bt; q.m = static_cast<int>(m); q.n = static_cast<int>(n); q.Kpad = static_cast<int>(f.kpad);
-  q.ldm = static_cast<int>(f.ldm); q.ldn = static_cast<int>(f.ldn); q.alpha = scale;
-  q.row_blocks = f.row_blocks; q.nsplit = f.nsplit; q.blocks_per_split = f.blocks_per_split;
-  q.gmax = reinterpret_cast<float*>(base + L.gmax); q.ng = static_cast<int>(f.ldn / 32);
-  float* thr = reinterpret_cast<float*>(base + L.thr);
-  const dim3 grid(static_cast<unsigned>(f.row_blocks * f.nsplit));
+  StreamStatsParams q = launch_copies<StreamStatsParams>(f, Q, C, m, n, D, f.kpad, region(ws, L.at), region(ws, L.bt), scale, s);
+  q.gmax = region(ws, L.gmax); q.ng = static_cast<int>(f.ldn / 32);
+  float* thr = region(ws, L.thr);
   if (hipError_t e = hipMemsetAsync(overflow, 0, 4, s); e != hipSuccess) return static_cast<int>(e);
   float abs_slack = 2.4e-7f * sqrtf(static_cast<float>(f.kpad)) * fabsf(scale);
-  if (topk_use_x3(m, n, D) && reinterpret_cast<uintptr_t>(Q) % 16 == 0 && reinterpret_cast<uintptr_t>(C) % 16 == 0) {
+  if (topk_use_x3(m, n, D) && aligned16(Q, C)) {
     // the group maxima come from the bf16x3 kernel (every score within 2e-6 |scale| of the exact one): the threshold gives
     // way by twice that on top of the f32 slack, the refine pass below still recomputes the candidates in f32
-    if (int e = dalm_x3_group_max(Q, C, m, n, D, scale, q.gmax, q.ng, base + L.x3, L.x3_bytes, stream)) return e;
+    if (int e = dalm_x3_group_max(Q, C, m, n, D, scale, q.gmax, q.ng, region<char>(ws, L.x3), L.x3_bytes, stream)) return e;
     abs_slack += 5e-6f * fabsf(scale);
-  } else if (f.rt == 2) hipLaunchKernelGGL((sim_rowstats_stream_kernel<2, MODE_GMAX>), grid, dim3(256), 0, s, q);
-  else hipLaunchKernelGGL((sim_rowstats_stream_kernel<1, MODE_GMAX>), grid, dim3(256), 0, s, q);
+  } else {
+    launch_stream<MODE_GMAX>(f, q, s);
+  }
   hipLaunchKernelGGL(topk_threshold_kernel, dim3(static_cast<unsigned>(m)), dim3(256), 0, s, q.gmax, q.ng,
                      static_cast<int>(k), abs_slack, thr);
   const size_t lds = (static_cast<size_t>(f.kpad) + 3 * static_cast<size_t>(L.cap)) * 4;
-  hipLaunchKernelGGL(topk_refine_kernel, dim3(static_cast<unsigned>(m)), dim3(256), lds, s, At, static_cast<int>(f.ldm),
-                     Bt, static_cast<int>(f.ldn), static_cast<int>(f.kpad), static_cast<int>(n), scale, q.gmax, q.ng, thr,
-                     L.cap, static_cast<int>(k), out_val, out_idx, overflow);
+  hipLaunchKernelGGL(topk_refine_kernel, dim3(static_cast<unsigned>(m)), dim3(256), lds, s, q.At, q.ldm, q.Bt, q.ldn, q.Kpad,
+                     q.n, scale, q.gmax, q.ng, thr, L.cap, static_cast<int>(k), out_val, out_idx, overflow);
   return check_launch(__func__);
 }
 
@@ -1515,20 +1377,6 @@ extern "C" int dalm_sim_topk(const float* Q, const float* C, int64_t m, int64_t 
 // recall / precision / hit-rate at every k and MRR are functions of the gold passage's rank in the whole corpus, and the rank is a
 // count over the score stream: the MFMA pass of the search above with integer counters as its epilogue - no candidate
 // buffer, no limit on k, no overflow fallback.
-namespace {
-struct RankLayout { StreamPlan f; size_t at, bt, total; };
-inline RankLayout rank_layout(int64_t m, int64_t n, int64_t D) {
-  RankLayout L{};
-  L.f = stream_plan(m, n, D, true);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 15) / 16 * 16; return at; };
-  L.at = take(static_cast<size_t>(L.f.kpad) * L.f.ldm * 4);
-  L.bt = take(static_cast<size_t>(L.f.kpad) * L.f.ldn * 4);
-  L.total = o;
-  return L;
-}
-}  // namespace
-
 extern "C" int dalm_sim_gold_score(const float* Q, const float* C, const int64_t* gold, int64_t m, int64_t n, int64_t D,
                                    int64_t col_offset, float scale, float* gold_score, dalm_stream_t stream) {
   DALM_REQUIRE(Q && C && gold && gold_score, DALM_E_NULL, "null pointer argument");
@@ -1555,26 +1403,12 @@ extern "C" int dalm_sim_gold_rank(const float* Q, const float* C, const int64_t*
   const RankLayout L = rank_layout(m, n, D);
   DALM_REQUIRE(L.f.ok, DALM_E_SHAPE, "query or corpus block too large for 32-bit buffer offsets: (rows + 128) * padded D * 4 must stay below 2^31 for both");
   DALM_REQUIRE(ws_bytes >= L.total, DALM_E_WORKSPACE, "workspace too small");
-  DALM_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 16 == 0 && reinterpret_cast<uintptr_t>(rank) % 8 == 0 &&
-                   reinterpret_cast<uintptr_t>(n_ge) % 8 == 0,
+  DALM_REQUIRE(aligned16(ws) && reinterpret_cast<uintptr_t>(rank) % 8 == 0 && reinterpret_cast<uintptr_t>(n_ge) % 8 == 0,
                DALM_E_ALIGN, "workspace must be 16-byte aligned, the counters 8-byte aligned");
   hipStream_t s = as_stream(stream);
-  char* base = static_cast<char*>(ws);
-  float* At = reinterpret_cast<float*>(base + L.at);
-  float* Bt = reinterpret_cast<float*>(base + L.bt);
-  const StreamPlan& f = L.f;
-  const int64_t ldmax = f.ldm > f.ldn ? f.ldm : f.ldn;
-  hipLaunchKernelGGL(transpose_pad_kernel, dim3(static_cast<unsigned>(ldmax / 32), static_cast<unsigned>((f.kpad + 31) / 32), 2),
-                     dim3(256), 0, s, Q, static_cast<int>(m), static_cast<int>(f.ldm), At, C, static_cast<int>(n),
-                     static_cast<int>(f.ldn), Bt, static_cast<int>(D), static_cast<int>(f.kpad));
-  StreamStatsParams q{};
-  q.At = At; q.Bt = Bt; q.m = static_cast<int>(m); q.n = static_cast<int>(n); q.Kpad = static_cast<int>(f.kpad);
-  q.ldm = static_cast<int>(f.ldm); q.ldn = static_cast<int>(f.ldn); q.alpha = scale;
-  q.row_blocks = f.row_blocks; q.nsplit = f.nsplit; q.blocks_per_split = f.blocks_per_split;
+  StreamStatsParams q = launch_copies<StreamStatsParams>(L.f, Q, C, m, n, D, L.f.kpad, region(ws, L.at), region(ws, L.bt), scale, s);
   q.gold_score = gold_score; q.gold = gold; q.col_offset = col_offset; q.threshold = threshold;
   q.rank = reinterpret_cast<unsigned long long*>(rank); q.n_ge = reinterpret_cast<unsigned long long*>(n_ge);
-  const dim3 grid(static_cast<unsigned>(f.row_blocks * f.nsplit));
-  if (f.rt == 2) hipLaunchKernelGGL((sim_rowstats_stream_kernel<2, MODE_RANK>), grid, dim3(256), 0, s, q);
-  else hipLaunchKernelGGL((sim_rowstats_stream_kernel<1, MODE_RANK>), grid, dim3(256), 0, s, q);
+  launch_stream<MODE_RANK>(L.f, q, s);
   return check_launch(__func__);
 }

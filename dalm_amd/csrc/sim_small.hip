@@ -17,7 +17,7 @@
 // Exact f32 throughout (|S| <= 100, see sim.hip).  Deterministic: fixed summation orders, no float atomics.
 // Bound: launch/latency (46 MFLOP and 1.2 MB at 150^2 x 1024); the roofline-relevant similarity kernels are
 // the large-batch ones in sim.hip.
-#include "dispatch.hpp"
+#include "sim_plan.hpp"
 #include "vec16.hpp"
 
 namespace dalm {
@@ -29,7 +29,6 @@ using f32x16 = __attribute__((ext_vector_type(16))) float;
 __device__ __forceinline__ int mfma_row(int r, int lhi) { return (r & 3) + 8 * (r >> 2) + 4 * lhi; }
 
 constexpr int RED_STRIDE = 33;
-constexpr int SK_MAX = 16;       // most K slices a tile is split into
 
 // sums the 4 waves' 32x32 accumulators through LDS (fixed order w = 0..3); afterwards thread t owns tile
 // elements e = t + 256 q.  red: [4][32][33] floats.
@@ -502,7 +501,6 @@ __global__ __launch_bounds__(256) void small_slice_sum_kernel(const float* __res
 // conflict-free ds_read_b32 fragments), the 4 waves split the chunk and read the other operand's fragments
 // straight from global memory (lane (c,h) reads X[k+h][d0+c]: 128-byte rows, L2-resident), 8 steps in flight.
 // ---------------------------------------------------------------------------------------------------
-constexpr int GK = 256;
 
 // All loads below are UNCONDITIONAL with clamped indices (a predicated load compiles to a branch plus
 // s_waitcnt vmcnt(0), which serialises what should be one batch in flight); out-of-range entries are zeroed by
@@ -720,20 +718,6 @@ __global__ __launch_bounds__(1024) void rag_loss_finalize_kernel(const float* __
   }
 }
 
-struct SmallPlan { int sk, k_chunk; int64_t ldn, ldm; };
-inline SmallPlan small_plan(int64_t m, int64_t n, int64_t D) {
-  const int64_t tiles = ((m + 31) / 32) * ((n + 31) / 32);
-  constexpr int64_t target = 256;               // workgroups aimed at
-  int64_t sk = (target + tiles - 1) / tiles;
-  const int64_t sk_max = (D + 31) / 32;        // every workgroup gets at least 32 of K (8 per wave)
-  if (sk > SK_MAX) sk = SK_MAX;
-  if (sk > sk_max) sk = sk_max;
-  if (sk < 1) sk = 1;
-  const int64_t k_chunk = round_up((D + sk - 1) / sk, 32);
-  sk = (D + k_chunk - 1) / k_chunk;
-  return {static_cast<int>(sk), static_cast<int>(k_chunk), round_up(n, 4), round_up(m, 4)};
-}
-
 }  // namespace
 }  // namespace dalm
 
@@ -748,77 +732,68 @@ extern "C" int dalm_sim_small_supported(int64_t m, int64_t n, int64_t D) {
 
 extern "C" size_t dalm_sim_small_workspace_bytes(int64_t m, int64_t n, int64_t D, int want_cols) {
   if (!dalm_sim_small_supported(m, n, D)) return 0;
-  const SmallPlan pl = small_plan(m, n, D);
-  size_t b = static_cast<size_t>(pl.sk) * m * pl.ldn;
-  if (want_cols) b += static_cast<size_t>(pl.sk) * n * pl.ldm;
-  return b * sizeof(float);
+  return small_fwd_layout(m, n, D, want_cols).total;
 }
+
+namespace {
+// the argument rules dalm_sim_small_fwd and dalm_sim_small_fwd1 share; `ptrs`: every required pointer is there
+int check_small_fwd(const char* fn, bool ptrs, int64_t m, int64_t n, int64_t D, int64_t ldS, int64_t diag_offset) {
+  if (!ptrs) return fail(DALM_E_NULL, fn, "null pointer argument");
+  if (!dalm_sim_small_supported(m, n, D)) return fail(DALM_E_SHAPE, fn, "shape outside the small-batch path (see dalm_sim_small_supported)");
+  if (ldS < n) return fail(DALM_E_SHAPE, fn, "ldS must be >= n");
+  if (diag_offset < 0 || diag_offset + m > n) return fail(DALM_E_SHAPE, fn, "diag_offset + m must be <= n");
+  return 0;
+}
+
+// The partial-tile kernel of a plan.  Pipelined form: the split covers K exactly and a wave's share is 4 or 8 whole rounds of
+// 32 (D = 1024 with 1 or 2 slices: 512^2 ... 1024^2 on one GPU, the 150 x 1200 per-rank blocks), 4 rounds in flight (measured:
+// profiles/history/r04_small_pipe.txt, 512^2 -8 %, 150 x 1200 -4 %; depth 2-4 alike).  Else the plain form, with unconditional
+// loads (`fast`) or guarded ones.  FUSED: the one-launch forward, which finishes the statistics through `fz` and takes no slabs.
+template <bool FUSED>
+void launch_small_partial(const SmallPlan& pl, const float* A, const float* Bm, int64_t m, int64_t n, int64_t D, float* slab,
+                          float* slabT, const FusedFwd& fz, hipStream_t s) {
+  const int im = static_cast<int>(m), in = static_cast<int>(n), iD = static_cast<int>(D), tiles_n = static_cast<int>((n + 31) / 32);
+  const int ldn = FUSED ? 0 : static_cast<int>(pl.ldn), ldm = FUSED ? 0 : static_cast<int>(pl.ldm);
+  const dim3 grid(static_cast<unsigned>((m + 31) / 32) * tiles_n, static_cast<unsigned>(pl.sk));
+  const int rounds = (pl.k_chunk % 128 == 0 && static_cast<int64_t>(pl.k_chunk) * pl.sk == D) ? pl.k_chunk / 128 : 0;
+  const int a_vec = rows_aligned16(A, D), b_vec = rows_aligned16(Bm, D);
+  const bool fast = a_vec && b_vec && D % 8 == 0;
+  if (fast && (rounds == 4 || rounds == 8))
+    by_exact<4, 8>(rounds, [&](auto r) {
+      hipLaunchKernelGGL((small_partial_pipe_kernel<r, 4, FUSED>), grid, dim3(256), 0, s, A, Bm, im, in, iD, pl.k_chunk, tiles_n,
+                         slab, ldn, slabT, ldm, fz);
+    });
+  else
+    by_bool(fast, [&](auto f) {
+      hipLaunchKernelGGL((small_partial_kernel<f, FUSED>), grid, dim3(256), 0, s, A, Bm, im, in, iD, pl.k_chunk, tiles_n, a_vec,
+                         b_vec, slab, ldn, slabT, ldm, fz);
+    });
+}
+}  // namespace
 
 extern "C" int dalm_sim_small_fwd(const float* A, const float* Bm, int64_t m, int64_t n, int64_t D, float scale,
                                   int64_t diag_offset, float* S, int64_t ldS, float* row_lse, float* diag,
                                   float* col_lse, void* ws, size_t ws_bytes, dalm_stream_t stream) {
-  DALM_REQUIRE(A && Bm && S && row_lse && diag && ws, DALM_E_NULL, "null pointer argument");
-  DALM_REQUIRE(dalm_sim_small_supported(m, n, D), DALM_E_SHAPE, "shape outside the small-batch path (see dalm_sim_small_supported)");
-  DALM_REQUIRE(ldS >= n, DALM_E_SHAPE, "ldS must be >= n");
-  DALM_REQUIRE(diag_offset >= 0 && diag_offset + m <= n, DALM_E_SHAPE, "diag_offset + m must be <= n");
+  if (int e = check_small_fwd(__func__, A && Bm && S && row_lse && diag && ws, m, n, D, ldS, diag_offset)) return e;
   const int want_cols = col_lse != nullptr;
-  DALM_REQUIRE(ws_bytes >= dalm_sim_small_workspace_bytes(m, n, D, want_cols), DALM_E_WORKSPACE, "workspace too small");
+  const SmallFwdLayout L = small_fwd_layout(m, n, D, want_cols);
+  DALM_REQUIRE(ws_bytes >= L.total, DALM_E_WORKSPACE, "workspace too small");
   DALM_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 4 == 0, DALM_E_ALIGN, "workspace must be 4-byte aligned");
   hipStream_t s = as_stream(stream);
-  const SmallPlan pl = small_plan(m, n, D);
-  float* slab = static_cast<float*>(ws);
-  float* slabT = want_cols ? slab + static_cast<size_t>(pl.sk) * m * pl.ldn : nullptr;
-  const int tiles_m = static_cast<int>((m + 31) / 32), tiles_n = static_cast<int>((n + 31) / 32);
-  const dim3 pgrid(static_cast<unsigned>(tiles_m * tiles_n), static_cast<unsigned>(pl.sk));
-  // pipelined form: the split covers K exactly and a wave's share is 4 or 8 whole rounds of 32 (D = 1024 with 1 or 2
-  // slices: 512^2 ... 1024^2 on one GPU, the 150 x 1200 per-rank blocks), 4 rounds in flight (measured:
-  // profiles/history/r04_small_pipe.txt, 512^2 -8 %, 150 x 1200 -4 %; depth 2-4 alike)
-  const int rounds = (pl.k_chunk % 128 == 0 && static_cast<int64_t>(pl.k_chunk) * pl.sk == D) ? pl.k_chunk / 128 : 0;
-  const bool fast = rows_aligned16(A, D) && rows_aligned16(Bm, D) && D % 8 == 0;
-  const FusedFwd none{};
-#define DALM_PIPE(R) hipLaunchKernelGGL((small_partial_pipe_kernel<R, 4>), pgrid, dim3(256), 0, s, A, Bm, static_cast<int>(m), \
-    static_cast<int>(n), static_cast<int>(D), pl.k_chunk, tiles_n, slab, static_cast<int>(pl.ldn), slabT, static_cast<int>(pl.ldm), none)
-  if (fast && rounds == 4) DALM_PIPE(4);
-  else if (fast && rounds == 8) DALM_PIPE(8);
-  else if (fast)
-#undef DALM_PIPE
-    hipLaunchKernelGGL(small_partial_kernel<true>, pgrid, dim3(256), 0, s, A, Bm, static_cast<int>(m),
-                       static_cast<int>(n), static_cast<int>(D), pl.k_chunk, tiles_n, 1, 1, slab,
-                       static_cast<int>(pl.ldn), slabT, static_cast<int>(pl.ldm), none);
-  else
-    hipLaunchKernelGGL(small_partial_kernel<false>, pgrid, dim3(256), 0, s, A, Bm, static_cast<int>(m),
-                       static_cast<int>(n), static_cast<int>(D), pl.k_chunk, tiles_n, static_cast<int>(rows_aligned16(A, D)),
-                       static_cast<int>(rows_aligned16(Bm, D)), slab, static_cast<int>(pl.ldn), slabT, static_cast<int>(pl.ldm), none);
+  float* slab = region(ws, L.slab);
+  float* slabT = want_cols ? region(ws, L.slabT) : nullptr;
+  launch_small_partial<false>(L.pl, A, Bm, m, n, D, slab, slabT, FusedFwd{}, s);
   const int64_t rmax = want_cols ? (m > n ? m : n) : m;
   const int64_t cmax = want_cols ? (m > n ? m : n) : n;                  // longest row the statistics pass reduces
-  if (cmax > 256)
-    hipLaunchKernelGGL(small_stats_wide_kernel, dim3(static_cast<unsigned>(rmax), want_cols ? 2u : 1u), dim3(256), 0,
-                       s, slab, static_cast<int>(pl.ldn), slabT, static_cast<int>(pl.ldm), pl.sk, static_cast<int>(m),
-                       static_cast<int>(n), scale, diag_offset, S, ldS, row_lse, diag, col_lse);
-  else
-    hipLaunchKernelGGL(small_stats_kernel, dim3(static_cast<unsigned>((rmax + 3) / 4), want_cols ? 2u : 1u), dim3(256), 0,
-                       s, slab, static_cast<int>(pl.ldn), slabT, static_cast<int>(pl.ldm), pl.sk, static_cast<int>(m),
-                       static_cast<int>(n), scale, diag_offset, S, ldS, row_lse, diag, col_lse);
+  const bool wide = cmax > 256;                                          // one workgroup per row instead of one wave
+  hipLaunchKernelGGL(wide ? small_stats_wide_kernel : small_stats_kernel,
+                     dim3(static_cast<unsigned>(wide ? rmax : (rmax + 3) / 4), want_cols ? 2u : 1u), dim3(256), 0, s, slab,
+                     static_cast<int>(L.pl.ldn), slabT, static_cast<int>(L.pl.ldm), L.pl.sk, static_cast<int>(m), static_cast<int>(n),
+                     scale, diag_offset, S, ldS, row_lse, diag, col_lse);
   return check_launch(__func__);
 }
 
 // ---- one-launch forward --------------------------------------------------------------------------------------
-namespace {
-struct Fused1Layout { size_t tslab, rowpart, colpart, total; int tiles_m, tiles_n; };
-inline Fused1Layout fused1_layout(int64_t m, int64_t n, int64_t D, int want_cols) {
-  const SmallPlan pl = small_plan(m, n, D);
-  Fused1Layout L{};
-  L.tiles_m = static_cast<int>((m + 31) / 32); L.tiles_n = static_cast<int>((n + 31) / 32);
-  const size_t tiles = static_cast<size_t>(L.tiles_m) * L.tiles_n;
-  size_t o = 256;                                           // slack for aligning the caller's pointer up to 256 bytes
-  L.tslab = o; o += (pl.sk > 1 ? static_cast<size_t>(pl.sk) * tiles * 4096 : 0);
-  L.rowpart = o; o += static_cast<size_t>(L.tiles_n) * L.tiles_m * 32 * 8;
-  L.colpart = o; o += want_cols ? static_cast<size_t>(L.tiles_m) * L.tiles_n * 32 * 8 : 0;
-  L.total = o;
-  return L;
-}
-}  // namespace
-
 extern "C" size_t dalm_sim_small_fwd1_workspace_bytes(int64_t m, int64_t n, int64_t D, int want_cols) {
   if (!dalm_sim_small_supported(m, n, D)) return 0;
   return fused1_layout(m, n, D, want_cols).total;
@@ -844,61 +819,26 @@ extern "C" size_t dalm_sim_small_fwd1_ticket_words(int64_t m, int64_t n) {
 extern "C" int dalm_sim_small_fwd1(const float* A, const float* Bm, int64_t m, int64_t n, int64_t D, float scale,
                                    int64_t diag_offset, float* S, int64_t ldS, float* row_lse, float* diag,
                                    float* col_lse, void* ws, size_t ws_bytes, unsigned* tickets, dalm_stream_t stream) {
-  DALM_REQUIRE(A && Bm && S && row_lse && diag && ws && tickets, DALM_E_NULL, "null pointer argument");
-  DALM_REQUIRE(dalm_sim_small_supported(m, n, D), DALM_E_SHAPE, "shape outside the small-batch path (see dalm_sim_small_supported)");
-  DALM_REQUIRE(ldS >= n, DALM_E_SHAPE, "ldS must be >= n");
-  DALM_REQUIRE(diag_offset >= 0 && diag_offset + m <= n, DALM_E_SHAPE, "diag_offset + m must be <= n");
+  if (int e = check_small_fwd(__func__, A && Bm && S && row_lse && diag && ws && tickets, m, n, D, ldS, diag_offset)) return e;
   const int want_cols = col_lse != nullptr;
   const Fused1Layout L = fused1_layout(m, n, D, want_cols);
   DALM_REQUIRE(ws_bytes >= L.total, DALM_E_WORKSPACE, "workspace too small");
   DALM_REQUIRE(reinterpret_cast<uintptr_t>(tickets) % 4 == 0, DALM_E_ALIGN, "tickets must be 4-byte aligned");
-  hipStream_t s = as_stream(stream);
-  const SmallPlan pl = small_plan(m, n, D);
-  unsigned char* base = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(ws) + 255) / 256 * 256) - 256;
+  char* base = align_up(ws, 256);
   FusedFwd fz{};
   fz.S = S; fz.ldS = ldS; fz.row_lse = row_lse; fz.diag = diag; fz.col_lse = col_lse;
   fz.alpha = scale; fz.diag_offset = diag_offset;
-  fz.tslab = reinterpret_cast<float*>(base + L.tslab);
-  fz.rowpart = reinterpret_cast<unsigned long long*>(base + L.rowpart);
-  fz.colpart = want_cols ? reinterpret_cast<unsigned long long*>(base + L.colpart) : nullptr;
-  fz.tickets = tickets; fz.sk = pl.sk; fz.tiles_m = L.tiles_m; fz.tiles_n = L.tiles_n;
-  const dim3 pgrid(static_cast<unsigned>(L.tiles_m * L.tiles_n), static_cast<unsigned>(pl.sk));
-  const int rounds = (pl.k_chunk % 128 == 0 && static_cast<int64_t>(pl.k_chunk) * pl.sk == D) ? pl.k_chunk / 128 : 0;
-  const bool fast = rows_aligned16(A, D) && rows_aligned16(Bm, D) && D % 8 == 0;
-  float* nof = nullptr;
-#define DALM_PIPE1(R) hipLaunchKernelGGL((small_partial_pipe_kernel<R, 4, true>), pgrid, dim3(256), 0, s, A, Bm, static_cast<int>(m), \
-    static_cast<int>(n), static_cast<int>(D), pl.k_chunk, L.tiles_n, nof, 0, nof, 0, fz)
-  if (fast && rounds == 4) DALM_PIPE1(4);
-  else if (fast && rounds == 8) DALM_PIPE1(8);
-#undef DALM_PIPE1
-  else if (fast)
-    hipLaunchKernelGGL((small_partial_kernel<true, true>), pgrid, dim3(256), 0, s, A, Bm, static_cast<int>(m),
-                       static_cast<int>(n), static_cast<int>(D), pl.k_chunk, L.tiles_n, 1, 1, nof, 0, nof, 0, fz);
-  else
-    hipLaunchKernelGGL((small_partial_kernel<false, true>), pgrid, dim3(256), 0, s, A, Bm, static_cast<int>(m),
-                       static_cast<int>(n), static_cast<int>(D), pl.k_chunk, L.tiles_n, static_cast<int>(rows_aligned16(A, D)),
-                       static_cast<int>(rows_aligned16(Bm, D)), nof, 0, nof, 0, fz);
+  fz.tslab = region(base, L.tslab);
+  fz.rowpart = region<unsigned long long>(base, L.rowpart);
+  fz.colpart = want_cols ? region<unsigned long long>(base, L.colpart) : nullptr;
+  fz.tickets = tickets; fz.sk = L.pl.sk; fz.tiles_m = L.tiles_m; fz.tiles_n = L.tiles_n;
+  launch_small_partial<true>(L.pl, A, Bm, m, n, D, nullptr, nullptr, fz, as_stream(stream));
   return check_launch(__func__);
 }
 
-namespace {
-// contraction slices of the backward: as many as keep the grid at <= 1024 workgroups, at most one per 256-chunk; only
-// when ONE direction is asked for (the sharded form; with both directions the grid is already two problems wide)
-inline int small_bwd_slices(int64_t m, int64_t n, int64_t D, bool want_dA, bool want_dB) {
-  if (want_dA == want_dB) return 1;
-  const int64_t R = want_dA ? m : n, Kd = want_dA ? n : m;
-  const int64_t blocks = ((R + 31) / 32) * ((D + 31) / 32), chunks = (Kd + GK - 1) / GK;
-  int64_t nsl = blocks > 0 ? 1024 / blocks : 1;
-  if (nsl > chunks) nsl = chunks;
-  return static_cast<int>(nsl < 1 ? 1 : nsl);
-}
-}  // namespace
-
 extern "C" size_t dalm_sim_small_bwd_workspace_bytes(int64_t m, int64_t n, int64_t D, int want_dA, int want_dB) {
   if (!dalm_sim_small_supported(m, n, D)) return 0;
-  const int nsl = small_bwd_slices(m, n, D, want_dA != 0, want_dB != 0);
-  if (nsl <= 1) return 0;
-  return static_cast<size_t>(nsl) * static_cast<size_t>(want_dA ? m : n) * static_cast<size_t>(D) * sizeof(float);
+  return small_bwd_layout(m, n, D, want_dA != 0, want_dB != 0, false).total;
 }
 
 // One-launch form of the sliced backward (round 4): the slices of a contraction are summed by the last slice of every output
@@ -906,10 +846,7 @@ extern "C" size_t dalm_sim_small_bwd_workspace_bytes(int64_t m, int64_t n, int64
 // zero (the forward's ticket buffer can be shared: calls are stream-ordered).  Workspace: tile-major partial tiles.
 extern "C" size_t dalm_sim_small_bwd1_workspace_bytes(int64_t m, int64_t n, int64_t D, int want_dA, int want_dB) {
   if (!dalm_sim_small_supported(m, n, D)) return 0;
-  const int nsl = small_bwd_slices(m, n, D, want_dA != 0, want_dB != 0);
-  if (nsl <= 1) return 0;
-  const int64_t R = want_dA ? m : n;
-  return static_cast<size_t>(nsl) * static_cast<size_t>((R + 31) / 32) * static_cast<size_t>((D + 31) / 32) * 4096;
+  return small_bwd_layout(m, n, D, want_dA != 0, want_dB != 0, true).total;
 }
 
 extern "C" size_t dalm_sim_small_bwd1_ticket_words(int64_t m, int64_t n, int64_t D) {
@@ -921,7 +858,38 @@ extern "C" size_t dalm_sim_small_bwd1_ticket_words(int64_t m, int64_t n, int64_t
 static int small_bwd_impl(const float* S, int64_t ldS, const float* A, const float* Bm, int64_t m, int64_t n, int64_t D,
                           float scale, int64_t diag_offset, const float* row_coef, const float* row_lse, const float* col_coef,
                           const float* col_lse, float* dA, float* dB, void* ws, size_t ws_bytes, unsigned* tickets,
-                          dalm_stream_t stream, const char* fn);
+                          dalm_stream_t stream, const char* fn) {
+  if (!(S && A && Bm && row_coef && row_lse && col_coef && col_lse)) return fail(DALM_E_NULL, fn, "null pointer argument");
+  if (!(dA || dB)) return fail(DALM_E_NULL, fn, "at least one of dA / dB is required");
+  if (!dalm_sim_small_supported(m, n, D)) return fail(DALM_E_SHAPE, fn, "shape outside the small-batch path");
+  if (ldS < n) return fail(DALM_E_SHAPE, fn, "ldS must be >= n");
+  const int dir0 = dA ? 0 : 1, ndir = (dA && dB) ? 2 : 1;
+  const SmallBwdLayout L = small_bwd_layout(m, n, D, dA != nullptr, dB != nullptr, tickets != nullptr);
+  int nsl = L.nsl;
+  if (nsl > 1 && (!ws || ws_bytes < L.total || !aligned16(ws))) nsl = 1;   // no workspace: unsliced form
+  if (nsl <= 1) tickets = nullptr;
+  const int64_t rmax = (ndir == 2) ? (m > n ? m : n) : (dir0 ? n : m);
+  const dim3 grid(static_cast<unsigned>((rmax + 31) / 32), static_cast<unsigned>((D + 31) / 32),
+                  static_cast<unsigned>(ndir * nsl));
+  float* slab = region(ws, L.slab);
+  hipStream_t s = as_stream(stream);
+  // the shortest contraction among the launched directions decides the form (dir 0 contracts over n, dir 1 over m)
+  const int64_t kd_min = (ndir == 2) ? (m < n ? m : n) : (dir0 ? m : n);
+  by_bool(kd_min > 64, [&](auto lng) {
+    hipLaunchKernelGGL(small_grad_kernel<lng>, grid, dim3(256), 0, s, S, ldS, A, Bm, static_cast<int>(m),
+                       static_cast<int>(n), static_cast<int>(D), scale, diag_offset, row_coef, row_lse, col_coef, col_lse,
+                       dA, dB, dir0, nsl, dA ? slab : nullptr, dA ? nullptr : slab, tickets);
+  });
+  if (nsl > 1 && !tickets) {
+    const int64_t count = (dA ? m : n) * D;
+    int64_t blocks = (count / 4 + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(small_slice_sum_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, slab, nsl, count,
+                       dA ? dA : dB);
+  }
+  return check_launch(fn);
+}
 
 extern "C" int dalm_sim_small_bwd1(const float* S, int64_t ldS, const float* A, const float* Bm, int64_t m, int64_t n,
                                    int64_t D, float scale, int64_t diag_offset, const float* row_coef,
@@ -938,46 +906,6 @@ extern "C" int dalm_sim_small_bwd_ws(const float* S, int64_t ldS, const float* A
                                      float* dB, void* ws, size_t ws_bytes, dalm_stream_t stream) {
   return small_bwd_impl(S, ldS, A, Bm, m, n, D, scale, diag_offset, row_coef, row_lse, col_coef, col_lse, dA, dB, ws, ws_bytes,
                         nullptr, stream, __func__);
-}
-
-static int small_bwd_impl(const float* S, int64_t ldS, const float* A, const float* Bm, int64_t m, int64_t n, int64_t D,
-                          float scale, int64_t diag_offset, const float* row_coef, const float* row_lse, const float* col_coef,
-                          const float* col_lse, float* dA, float* dB, void* ws, size_t ws_bytes, unsigned* tickets,
-                          dalm_stream_t stream, const char* fn) {
-  if (!(S && A && Bm && row_coef && row_lse && col_coef && col_lse)) return fail(DALM_E_NULL, fn, "null pointer argument");
-  if (!(dA || dB)) return fail(DALM_E_NULL, fn, "at least one of dA / dB is required");
-  if (!dalm_sim_small_supported(m, n, D)) return fail(DALM_E_SHAPE, fn, "shape outside the small-batch path");
-  if (ldS < n) return fail(DALM_E_SHAPE, fn, "ldS must be >= n");
-  const int dir0 = dA ? 0 : 1, ndir = (dA && dB) ? 2 : 1;
-  int nsl = small_bwd_slices(m, n, D, dA != nullptr, dB != nullptr);
-  const size_t need = tickets ? dalm_sim_small_bwd1_workspace_bytes(m, n, D, dA != nullptr, dB != nullptr)
-                              : dalm_sim_small_bwd_workspace_bytes(m, n, D, dA != nullptr, dB != nullptr);
-  if (nsl > 1 && (!ws || ws_bytes < need || reinterpret_cast<uintptr_t>(ws) % 16 != 0)) nsl = 1;   // no workspace: unsliced form
-  if (nsl <= 1) tickets = nullptr;
-  const int64_t rmax = (ndir == 2) ? (m > n ? m : n) : (dir0 ? n : m);
-  const dim3 grid(static_cast<unsigned>((rmax + 31) / 32), static_cast<unsigned>((D + 31) / 32),
-                  static_cast<unsigned>(ndir * nsl));
-  float* slab = static_cast<float*>(ws);
-  hipStream_t s = as_stream(stream);
-  // the shortest contraction among the launched directions decides the form (dir 0 contracts over n, dir 1 over m)
-  const int64_t kd_min = (ndir == 2) ? (m < n ? m : n) : (dir0 ? m : n);
-  if (kd_min > 64)
-    hipLaunchKernelGGL(small_grad_kernel<true>, grid, dim3(256), 0, s, S, ldS, A, Bm, static_cast<int>(m),
-                       static_cast<int>(n), static_cast<int>(D), scale, diag_offset, row_coef, row_lse, col_coef, col_lse,
-                       dA, dB, dir0, nsl, dA ? slab : nullptr, dA ? nullptr : slab, tickets);
-  else
-    hipLaunchKernelGGL(small_grad_kernel<false>, grid, dim3(256), 0, s, S, ldS, A, Bm, static_cast<int>(m),
-                       static_cast<int>(n), static_cast<int>(D), scale, diag_offset, row_coef, row_lse, col_coef, col_lse,
-                       dA, dB, dir0, nsl, dA ? slab : nullptr, dA ? nullptr : slab, tickets);
-  if (nsl > 1 && !tickets) {
-    const int64_t count = (dA ? m : n) * D;
-    int64_t blocks = (count / 4 + 255) / 256;
-    if (blocks > 1024) blocks = 1024;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(small_slice_sum_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, slab, nsl, count,
-                       dA ? dA : dB);
-  }
-  return check_launch(fn);
 }
 
 extern "C" int dalm_sim_small_bwd(const float* S, int64_t ldS, const float* A, const float* Bm, int64_t m, int64_t n,

@@ -58,14 +58,13 @@ class HipOps:
                  hip.ptr(emb), hip.ptr(norm), hip.ptr(inv_count), hip.ptr(ws), ws_bytes, hip.stream())
         return emb, norm, inv_count
 
-    def pool_packed_fwd(self, h: torch.Tensor, cu: torch.Tensor, nseq_out: Optional[int] = None,
-                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """mean_pooling + F.normalize straight from packed rows (`dalm_pool_l2norm_packed_fwd`; evaluation, no backward):
-        h [n, D] f32 / bf16, cu int32 [nseq + 1] sequence starts; the first `nseq_out` sequences are written as f32 rows
-        into `out` [nseq_out, D] (a row slice of a larger f32 matrix is fine: its row stride is the leading dimension)."""
+    @staticmethod
+    def _packed_pool_args(name: str, h: torch.Tensor, cu: torch.Tensor, nseq_out: Optional[int], out: Optional[torch.Tensor]):
+        """What the packed pool entry points share: (dev, h, cu, n, nseq, nseq_out, D, out, ld) with h contiguous, cu int32, `out`
+        checked (or allocated) as f32 [nseq_out, D] and `ld` its leading dimension."""
         dev = hip.require_gpu(h, cu, out)
         if h.dim() != 2 or cu.dim() != 1 or cu.numel() < 2:
-            raise ValueError(f"pool_packed: expected h [n,D] and cu [nseq+1], got {tuple(h.shape)} / {tuple(cu.shape)}")
+            raise ValueError(f"{name}: expected h [n,D] and cu [nseq+1], got {tuple(h.shape)} / {tuple(cu.shape)}")
         h = h.contiguous()
         cu = cu if (cu.dtype == torch.int32 and cu.is_contiguous()) else cu.to(torch.int32).contiguous()
         n, D = h.shape
@@ -74,8 +73,16 @@ class HipOps:
         if out is None:
             out = torch.empty((nseq_out, D), device=dev, dtype=torch.float32)
         if out.dtype != torch.float32 or out.dim() != 2 or out.shape != (nseq_out, D) or out.stride(1) != 1:
-            raise ValueError(f"pool_packed: out must be f32 [{nseq_out}, {D}] with unit column stride")
+            raise ValueError(f"{name}: out must be f32 [{nseq_out}, {D}] with unit column stride")
         ld = out.stride(0) if nseq_out > 1 else max(out.stride(0), D)
+        return dev, h, cu, n, nseq, nseq_out, D, out, ld
+
+    def pool_packed_fwd(self, h: torch.Tensor, cu: torch.Tensor, nseq_out: Optional[int] = None,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """mean_pooling + F.normalize straight from packed rows (`dalm_pool_l2norm_packed_fwd`; evaluation, no backward):
+        h [n, D] f32 / bf16, cu int32 [nseq + 1] sequence starts; the first `nseq_out` sequences are written as f32 rows
+        into `out` [nseq_out, D] (a row slice of a larger f32 matrix is fine: its row stride is the leading dimension)."""
+        _, h, cu, n, nseq, nseq_out, D, out, ld = self._packed_pool_args("pool_packed", h, cu, nseq_out, out)
         hip.call("dalm_pool_l2norm_packed_fwd", hip.ptr(h), hip.dtype_code(h), hip.ptr(cu), n, nseq, nseq_out, D,
                  hip.ptr(out), ld, None, None, hip.stream())
         return out
@@ -85,19 +92,7 @@ class HipOps:
         """Last-token pooling (+ F.normalize) straight from packed rows (`dalm_pool_last_packed_fwd`; causal-LM retrievers):
         h [n, D] f32 / bf16, cu int32 [nseq + 1]; sequence s < `nseq_out` gives the f32 row of h[cu[s + 1] - 1] (zeros when the
         sequence is empty) in `out` [nseq_out, D] - a row slice of a larger f32 matrix is fine.  Returns (out, norm [nseq_out])."""
-        dev = hip.require_gpu(h, cu, out)
-        if h.dim() != 2 or cu.dim() != 1 or cu.numel() < 2:
-            raise ValueError(f"pool_last_packed: expected h [n,D] and cu [nseq+1], got {tuple(h.shape)} / {tuple(cu.shape)}")
-        h = h.contiguous()
-        cu = cu if (cu.dtype == torch.int32 and cu.is_contiguous()) else cu.to(torch.int32).contiguous()
-        n, D = h.shape
-        nseq = cu.numel() - 1
-        nseq_out = nseq if nseq_out is None else int(nseq_out)
-        if out is None:
-            out = torch.empty((nseq_out, D), device=dev, dtype=torch.float32)
-        if out.dtype != torch.float32 or out.dim() != 2 or out.shape != (nseq_out, D) or out.stride(1) != 1:
-            raise ValueError(f"pool_last_packed: out must be f32 [{nseq_out}, {D}] with unit column stride")
-        ld = out.stride(0) if nseq_out > 1 else max(out.stride(0), D)
+        dev, h, cu, n, nseq, nseq_out, D, out, ld = self._packed_pool_args("pool_last_packed", h, cu, nseq_out, out)
         norm = torch.empty((nseq_out,), device=dev, dtype=torch.float32)
         hip.call("dalm_pool_last_packed_fwd", hip.ptr(h), hip.dtype_code(h), hip.ptr(cu), n, nseq, nseq_out, D, int(normalize),
                  hip.ptr(out), ld, hip.ptr(norm), hip.stream())
@@ -151,94 +146,81 @@ class HipOps:
         return Cm
 
     # ---- K2-K4 fused ----------------------------------------------------------
-    def sim_rowstats(self, A: torch.Tensor, Bm: torch.Tensor, scale: float, diag_offset: int):
-        """row_lse[i] = logsumexp_j scale*A_i.B_j ; diag[i] = scale*A_i.B_{off+i}."""
-        dev = hip.require_gpu(A, Bm)
+    @staticmethod
+    def _sim_operands(A: torch.Tensor, Bm: torch.Tensor, *more):
+        """(dev, A, Bm, m, n, D) of the similarity problem A [m, D] . Bm [n, D]^T, operands f32 and contiguous."""
+        dev = hip.require_gpu(A, Bm, *more)
         A, Bm = hip.as_f32c(A), hip.as_f32c(Bm)
-        m, D = A.shape
-        n = Bm.shape[0]
+        return dev, A, Bm, A.shape[0], Bm.shape[0], A.shape[1]
+
+    @staticmethod
+    def _workspace(dev: torch.device, ws_bytes: int, as_bytes: bool = False) -> torch.Tensor:
+        """`ws_bytes` of scratch: f32 words (never empty, so it always has a pointer) or, `as_bytes`, exactly that many bytes."""
+        if as_bytes:
+            return torch.empty((ws_bytes,), device=dev, dtype=torch.uint8)
+        return torch.empty((max(ws_bytes, 4) // 4,), device=dev, dtype=torch.float32)
+
+    def _sim_rowstats(self, entry: str, size_fn: str, A, Bm, scale: float, diag_offset: int, x3_error: Optional[str] = None):
+        """(row_lse, diag) through `entry` with `size_fn` bytes of workspace; the bf16x3 entry point (`x3_error` set) refuses
+        unsupported shapes with that text and takes a byte workspace."""
+        dev, A, Bm, m, n, D = self._sim_operands(A, Bm)
         lib = hip.load()
-        ws_bytes = lib.dalm_sim_rowstats_workspace_bytes(m, n, D)
-        ws = torch.empty((max(ws_bytes, 4) // 4,), device=dev, dtype=torch.float32)
+        if x3_error and not getattr(lib, entry + "_supported")(m, n, D):
+            raise ValueError(x3_error.format(m=m, n=n, D=D))
+        ws_bytes = getattr(lib, size_fn)(m, n, D)
+        ws = self._workspace(dev, ws_bytes, as_bytes=bool(x3_error))
         row_lse = torch.empty((m,), device=dev, dtype=torch.float32)
         diag = torch.empty((m,), device=dev, dtype=torch.float32)
-        hip.call("dalm_sim_rowstats", hip.ptr(A), hip.ptr(Bm), m, n, D, float(scale), int(diag_offset),
+        hip.call(entry, hip.ptr(A), hip.ptr(Bm), m, n, D, float(scale), int(diag_offset),
                  hip.ptr(row_lse), hip.ptr(diag), hip.ptr(ws), ws_bytes, hip.stream())
         return row_lse, diag
 
+    def sim_rowstats(self, A: torch.Tensor, Bm: torch.Tensor, scale: float, diag_offset: int):
+        """row_lse[i] = logsumexp_j scale*A_i.B_j ; diag[i] = scale*A_i.B_{off+i}."""
+        return self._sim_rowstats("dalm_sim_rowstats", "dalm_sim_rowstats_workspace_bytes", A, Bm, scale, diag_offset)
+
     def sim_rowstats_f32(self, A: torch.Tensor, Bm: torch.Tensor, scale: float, diag_offset: int):
         """`sim_rowstats` pinned to the exact-f32 MFMA kernels (what every shape took before round 4) - for A/B checks."""
-        dev = hip.require_gpu(A, Bm)
-        A, Bm = hip.as_f32c(A), hip.as_f32c(Bm)
-        m, D = A.shape
-        n = Bm.shape[0]
-        lib = hip.load()
-        ws_bytes = lib.dalm_sim_rowstats_workspace_bytes(m, n, D)
-        ws = torch.empty((max(ws_bytes, 4) // 4,), device=dev, dtype=torch.float32)
-        row_lse = torch.empty((m,), device=dev, dtype=torch.float32)
-        diag = torch.empty((m,), device=dev, dtype=torch.float32)
-        hip.call("dalm_sim_rowstats_f32", hip.ptr(A), hip.ptr(Bm), m, n, D, float(scale), int(diag_offset),
-                 hip.ptr(row_lse), hip.ptr(diag), hip.ptr(ws), ws_bytes, hip.stream())
-        return row_lse, diag
+        return self._sim_rowstats("dalm_sim_rowstats_f32", "dalm_sim_rowstats_workspace_bytes", A, Bm, scale, diag_offset)
 
     def sim_rowstats_bf16x3(self, A: torch.Tensor, Bm: torch.Tensor, scale: float, diag_offset: int):
         """The same statistics on the bf16 matrix cores at f32 accuracy (three bf16 thirds per operand, six products along
         K; see include/dalm_hip.h).  `sim_rowstats` routes here by itself for m, n >= 3072."""
-        dev = hip.require_gpu(A, Bm)
-        A, Bm = hip.as_f32c(A), hip.as_f32c(Bm)
-        m, D = A.shape
-        n = Bm.shape[0]
-        lib = hip.load()
-        if not lib.dalm_sim_rowstats_bf16x3_supported(m, n, D):
-            raise ValueError(f"bf16x3 similarity does not support m={m}, n={n}, D={D} (D % 64 == 0, images below 4 GB)")
-        ws_bytes = lib.dalm_sim_rowstats_bf16x3_workspace_bytes(m, n, D)
-        ws = torch.empty((ws_bytes,), device=dev, dtype=torch.uint8)
-        row_lse = torch.empty((m,), device=dev, dtype=torch.float32)
-        diag = torch.empty((m,), device=dev, dtype=torch.float32)
-        hip.call("dalm_sim_rowstats_bf16x3", hip.ptr(A), hip.ptr(Bm), m, n, D, float(scale), int(diag_offset),
-                 hip.ptr(row_lse), hip.ptr(diag), hip.ptr(ws), ws_bytes, hip.stream())
-        return row_lse, diag
+        return self._sim_rowstats("dalm_sim_rowstats_bf16x3", "dalm_sim_rowstats_bf16x3_workspace_bytes", A, Bm, scale, diag_offset,
+                                  "bf16x3 similarity does not support m={m}, n={n}, D={D} (D % 64 == 0, images below 4 GB)")
 
-    def sim_grad(self, A, Bm, scale: float, diag_offset: int, row_coef, row_lse, col_coef, col_lse):
-        """dA = scale * dS . Bm with the closed-form dS of include/dalm_hip.h."""
-        dev = hip.require_gpu(A, Bm, row_coef, row_lse, col_coef, col_lse)
-        A, Bm = hip.as_f32c(A), hip.as_f32c(Bm)
+    def _sim_grad(self, entry: str, A, Bm, scale: float, diag_offset: int, row_coef, row_lse, col_coef, col_lse,
+                  x3_error: Optional[str] = None):
+        """dA through `entry` (its size function is `entry`_workspace_bytes); `x3_error` as in `_sim_rowstats`."""
+        dev, A, Bm, m, n, D = self._sim_operands(A, Bm, row_coef, row_lse, col_coef, col_lse)
         row_coef, row_lse = hip.as_f32c(row_coef), hip.as_f32c(row_lse)
         col_coef, col_lse = hip.as_f32c(col_coef), hip.as_f32c(col_lse)
-        m, D = A.shape
-        n = Bm.shape[0]
         lib = hip.load()
-        # large global batches: both contractions on the bf16 pipe at f32 accuracy (bf16x3).  From m, n >= 8192 it is the faster
-        # form (profiles/r05_sim_grad_x3.txt: 16384^2 9.2 -> 7.1 ms; at 4096^2 its launches of 64-128 tiles do not fill the chip
-        # and the f32-pipe flash kernel wins); DALM_SIM_GRAD_X3 = 0 keeps the flash kernel, = 1 forces x3
-        x3 = os.environ.get("DALM_SIM_GRAD_X3")
-        if x3 != "0" and lib.dalm_sim_grad_bf16x3_supported(m, n, D) and (x3 == "1" or (m >= 8192 and n >= 8192)):
-            return self.sim_grad_bf16x3(A, Bm, scale, diag_offset, row_coef, row_lse, col_coef, col_lse)
-        ws_bytes = lib.dalm_sim_grad_workspace_bytes(m, n, D)
-        ws = torch.empty((max(ws_bytes, 4) // 4,), device=dev, dtype=torch.float32)
+        if x3_error and not getattr(lib, entry + "_supported")(m, n, D):
+            raise ValueError(x3_error.format(m=m, n=n, D=D))
+        ws_bytes = getattr(lib, entry + "_workspace_bytes")(m, n, D)
+        ws = self._workspace(dev, ws_bytes, as_bytes=bool(x3_error))
         dA = torch.empty((m, D), device=dev, dtype=torch.float32)
-        hip.call("dalm_sim_grad", hip.ptr(A), hip.ptr(Bm), m, n, D, float(scale), int(diag_offset),
+        hip.call(entry, hip.ptr(A), hip.ptr(Bm), m, n, D, float(scale), int(diag_offset),
                  hip.ptr(row_coef), hip.ptr(row_lse), hip.ptr(col_coef), hip.ptr(col_lse), hip.ptr(dA),
                  hip.ptr(ws), ws_bytes, hip.stream())
         return dA
 
+    def sim_grad(self, A, Bm, scale: float, diag_offset: int, row_coef, row_lse, col_coef, col_lse):
+        """dA = scale * dS . Bm with the closed-form dS of include/dalm_hip.h."""
+        (m, D), n = A.shape, Bm.shape[0]
+        # large global batches: both contractions on the bf16 pipe at f32 accuracy (bf16x3).  From m, n >= 8192 it is the faster
+        # form (profiles/r05_sim_grad_x3.txt: 16384^2 9.2 -> 7.1 ms; at 4096^2 its launches of 64-128 tiles do not fill the chip
+        # and the f32-pipe flash kernel wins); DALM_SIM_GRAD_X3 = 0 keeps the flash kernel, = 1 forces x3
+        x3 = os.environ.get("DALM_SIM_GRAD_X3")
+        if x3 != "0" and hip.load().dalm_sim_grad_bf16x3_supported(m, n, D) and (x3 == "1" or (m >= 8192 and n >= 8192)):
+            return self.sim_grad_bf16x3(A, Bm, scale, diag_offset, row_coef, row_lse, col_coef, col_lse)
+        return self._sim_grad("dalm_sim_grad", A, Bm, scale, diag_offset, row_coef, row_lse, col_coef, col_lse)
+
     def sim_grad_bf16x3(self, A, Bm, scale: float, diag_offset: int, row_coef, row_lse, col_coef, col_lse):
         """`sim_grad` through `dalm_sim_grad_bf16x3` (S recomputed and dS . B contracted as bf16x3 on the lm_head core)."""
-        dev = hip.require_gpu(A, Bm, row_coef, row_lse, col_coef, col_lse)
-        A, Bm = hip.as_f32c(A), hip.as_f32c(Bm)
-        row_coef, row_lse = hip.as_f32c(row_coef), hip.as_f32c(row_lse)
-        col_coef, col_lse = hip.as_f32c(col_coef), hip.as_f32c(col_lse)
-        m, D = A.shape
-        n = Bm.shape[0]
-        lib = hip.load()
-        if not lib.dalm_sim_grad_bf16x3_supported(m, n, D):
-            raise ValueError(f"bf16x3 similarity backward does not support m={m}, n={n}, D={D}")
-        ws_bytes = lib.dalm_sim_grad_bf16x3_workspace_bytes(m, n, D)
-        ws = torch.empty((ws_bytes,), device=dev, dtype=torch.uint8)
-        dA = torch.empty((m, D), device=dev, dtype=torch.float32)
-        hip.call("dalm_sim_grad_bf16x3", hip.ptr(A), hip.ptr(Bm), m, n, D, float(scale), int(diag_offset), hip.ptr(row_coef),
-                 hip.ptr(row_lse), hip.ptr(col_coef), hip.ptr(col_lse), hip.ptr(dA), hip.ptr(ws), ws_bytes, hip.stream())
-        return dA
+        return self._sim_grad("dalm_sim_grad_bf16x3", A, Bm, scale, diag_offset, row_coef, row_lse, col_coef, col_lse,
+                              "bf16x3 similarity backward does not support m={m}, n={n}, D={D}")
 
     # ---- K2-K4, small-batch form: S once, 2 launches forward / 1 launch backward ----------------
     def sim_small_supported(self, m: int, n: int, D: int) -> bool:
@@ -264,10 +246,7 @@ class HipOps:
         """S = scale*A.B^T (saved), row_lse, diag and (want_cols) col_lse = logsumexp over rows.  One launch
         (dalm_sim_small_fwd1) or two (dalm_sim_small_fwd): by shape unless `one_launch` says, as measured
         (dalm_sim_small_fwd1_preferred, profiles/history/r04_small_one_launch.txt)."""
-        dev = hip.require_gpu(A, Bm)
-        A, Bm = hip.as_f32c(A), hip.as_f32c(Bm)
-        m, D = A.shape
-        n = Bm.shape[0]
+        dev, A, Bm, m, n, D = self._sim_operands(A, Bm)
         lib = hip.load()
         S = torch.empty((m, n), device=dev, dtype=torch.float32)
         row_lse = torch.empty((m,), device=dev, dtype=torch.float32)
@@ -277,13 +256,13 @@ class HipOps:
             one_launch = bool(lib.dalm_sim_small_fwd1_preferred(m, n, D))
         if one_launch:
             ws_bytes = lib.dalm_sim_small_fwd1_workspace_bytes(m, n, D, int(want_cols))
-            ws = torch.empty((ws_bytes,), device=dev, dtype=torch.uint8)
+            ws = self._workspace(dev, ws_bytes, as_bytes=True)
             tickets = self._small_tickets(dev, lib.dalm_sim_small_fwd1_ticket_words(m, n))
             hip.call("dalm_sim_small_fwd1", hip.ptr(A), hip.ptr(Bm), m, n, D, float(scale), int(diag_offset), hip.ptr(S), n,
                      hip.ptr(row_lse), hip.ptr(diag), hip.ptr(col_lse), hip.ptr(ws), ws_bytes, hip.ptr(tickets), hip.stream())
             return S, row_lse, diag, col_lse
         ws_bytes = lib.dalm_sim_small_workspace_bytes(m, n, D, int(want_cols))
-        ws = torch.empty((max(ws_bytes, 4) // 4,), device=dev, dtype=torch.float32)
+        ws = self._workspace(dev, ws_bytes)
         hip.call("dalm_sim_small_fwd", hip.ptr(A), hip.ptr(Bm), m, n, D, float(scale), int(diag_offset), hip.ptr(S), n,
                  hip.ptr(row_lse), hip.ptr(diag), hip.ptr(col_lse), hip.ptr(ws), ws_bytes, hip.stream())
         return S, row_lse, diag, col_lse
@@ -293,18 +272,15 @@ class HipOps:
     def sim_small_bwd(self, S, A, Bm, scale: float, diag_offset: int, row_coef, row_lse, col_coef, col_lse,
                       want_dA: bool = True, want_dB: bool = True, one_launch: bool = True):
         """(dA, dB) = (scale dS.B, scale dS^T.A) from the saved S; the closed-form dS of include/dalm_hip.h."""
-        dev = hip.require_gpu(S, A, Bm, row_coef, row_lse, col_coef, col_lse)
-        A, Bm, S = hip.as_f32c(A), hip.as_f32c(Bm), hip.as_f32c(S)
-        row_coef, row_lse = hip.as_f32c(row_coef), hip.as_f32c(row_lse)
+        dev, A, Bm, m, n, D = self._sim_operands(A, Bm, S, row_coef, row_lse, col_coef, col_lse)
+        S, row_coef, row_lse = hip.as_f32c(S), hip.as_f32c(row_coef), hip.as_f32c(row_lse)
         col_coef, col_lse = hip.as_f32c(col_coef), hip.as_f32c(col_lse)
-        m, D = A.shape
-        n = Bm.shape[0]
         dA = torch.empty((m, D), device=dev, dtype=torch.float32) if want_dA else None
         dB = torch.empty((n, D), device=dev, dtype=torch.float32) if want_dB else None
         lib = hip.load()
         ws_bytes = lib.dalm_sim_small_bwd1_workspace_bytes(m, n, D, int(want_dA), int(want_dB)) if one_launch else 0
         if one_launch and ws_bytes:        # sliced: the last slice of every output tile adds the slices (one launch)
-            ws = torch.empty((ws_bytes // 4,), device=dev, dtype=torch.float32)
+            ws = self._workspace(dev, ws_bytes)
             tickets = self._small_tickets(dev, lib.dalm_sim_small_bwd1_ticket_words(m, n, D))
             hip.call("dalm_sim_small_bwd1", hip.ptr(S), S.shape[1], hip.ptr(A), hip.ptr(Bm), m, n, D, float(scale),
                      int(diag_offset), hip.ptr(row_coef), hip.ptr(row_lse), hip.ptr(col_coef), hip.ptr(col_lse),
@@ -336,14 +312,11 @@ class HipOps:
         """(values [m,k] f32, indices [m,k] int64, overflow [1] int32) - exact top-k of scale*Q.Cm^T per row without the
         score matrix; `overflow` non-zero means a row had too many ties for the candidate buffer or ended with fewer than k
         candidates (fall back to the materialising search)."""
-        dev = hip.require_gpu(Q, Cm)
-        Q, Cm = hip.as_f32c(Q), hip.as_f32c(Cm)
-        m, D = Q.shape
-        n = Cm.shape[0]
+        dev, Q, Cm, m, n, D = self._sim_operands(Q, Cm)
         ws_bytes = hip.load().dalm_sim_topk_workspace_bytes(m, n, D, int(k))
         if ws_bytes == 0:
             raise ValueError("sim_topk: corpus block too large for one call (n*D*4 must stay below 2^31)")
-        ws = torch.empty((ws_bytes // 4,), device=dev, dtype=torch.float32)
+        ws = self._workspace(dev, ws_bytes)
         val = torch.empty((m, k), device=dev, dtype=torch.float32)
         idx = torch.empty((m, k), device=dev, dtype=torch.int64)
         ovf = torch.empty((1,), device=dev, dtype=torch.int32)
@@ -369,10 +342,8 @@ class HipOps:
         """One corpus block of the rank sweep (`dalm_sim_gold_rank`): rank[i] += the block's columns that sort before query
         i's gold passage (higher score, or equal score and lower corpus index), n_ge[i] += its columns scoring >=
         `threshold`.  `rank` / `n_ge` are int64 [m] accumulators the caller zeroes before the first block."""
-        dev = hip.require_gpu(Q, Cm, gold, gold_score, rank, n_ge)
-        Q, Cm, gold, gold_score = hip.as_f32c(Q), hip.as_f32c(Cm), hip.as_i64(gold), hip.as_f32c(gold_score)
-        m, D = Q.shape
-        n = Cm.shape[0]
+        dev, Q, Cm, m, n, D = self._sim_operands(Q, Cm, gold, gold_score, rank, n_ge)
+        gold, gold_score = hip.as_i64(gold), hip.as_f32c(gold_score)
         for t in (rank, n_ge):
             if t.dtype != torch.int64 or t.shape != (m,) or not t.is_contiguous():
                 raise ValueError("sim_gold_rank: rank and n_ge must be contiguous int64 [m]")
@@ -381,7 +352,7 @@ class HipOps:
         ws_bytes = hip.load().dalm_sim_gold_rank_workspace_bytes(m, n, D)
         if ws_bytes == 0:
             raise ValueError("sim_gold_rank: query or corpus block too large for one call (m*D*4 and n*D*4 must stay below 2^31)")
-        ws = torch.empty((ws_bytes // 4,), device=dev, dtype=torch.float32)
+        ws = self._workspace(dev, ws_bytes)
         hip.call("dalm_sim_gold_rank", hip.ptr(Q), hip.ptr(Cm), hip.ptr(gold), hip.ptr(gold_score), m, n, D, int(col_offset),
                  float(scale), float(threshold), hip.ptr(rank), hip.ptr(n_ge), hip.ptr(ws), ws_bytes, hip.stream())
         return rank, n_ge

@@ -154,20 +154,38 @@ def test_every_quoted_include_is_a_build_header():
             assert (f.parent / inc).resolve() in known, f"{f.name} includes {inc}, which _build.HEADERS does not list"
 
 
-def test_dispatch_header_selection_rules(tmp_path):
-    """csrc/dispatch.hpp is host-only C++17: tests/dispatch_check.cpp includes nothing else of the library, is built with the
-    host compiler under the address and undefined-behaviour sanitizers, and checks every selection rule at its edges."""
+def run_host_check(tmp_path, name, *args):
+    """Builds tests/<name>.cpp against csrc's headers with the host compiler under the address and undefined-behaviour
+    sanitizers (runtimes linked into the program), runs it and returns the finished process."""
     import shutil
     import subprocess
 
     cxx = shutil.which("g++")
     if cxx is None:
         pytest.skip("g++ not available")
-    exe = tmp_path / "dispatch_check"
+    exe = tmp_path / name
     r = subprocess.run([cxx, "-std=c++17", "-Wall", "-Wextra", "-Werror", "-O1", "-g", "-fsanitize=address,undefined",
                         "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",   # runtimes inside the program
-                        "-I", str(ROOT / "dalm_amd" / "csrc"), str(ROOT / "tests" / "dispatch_check.cpp"), "-o", str(exe)],
+                        "-I", str(ROOT / "dalm_amd" / "csrc"), str(ROOT / "tests" / f"{name}.cpp"), "-o", str(exe)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    return subprocess.run([str(exe), *map(str, args)], capture_output=True, text=True)
+
+
+def test_dispatch_header_selection_rules(tmp_path):
+    """csrc/dispatch.hpp is host-only C++17: tests/dispatch_check.cpp includes nothing else of the library, is built with the
+    host compiler under the address and undefined-behaviour sanitizers, and checks every selection rule at its edges."""
+    r = run_host_check(tmp_path, "dispatch_check")
     assert r.returncode == 0 and r.stdout.strip() == "dispatch ok", (r.returncode, r.stdout, r.stderr)
+
+
+def test_similarity_workspace_layouts(tmp_path):
+    """csrc/sim_plan.hpp is host-only C++17 too: tests/sim_plan_check.cpp checks, over the grid of tests/test_sim_sizes.py, that
+    every workspace layout's regions lie in order, disjoint, aligned and inside the total the size functions report, that the
+    column splits cover the matrix and that the 32-bit buffer offsets hold wherever a plan says ok."""
+    from test_sim_sizes import GRID
+
+    shapes = tmp_path / "shapes.txt"
+    shapes.write_text("".join(f"{m} {n} {D}\n" for m, n, D in GRID))
+    r = run_host_check(tmp_path, "sim_plan_check", shapes)
+    assert r.returncode == 0 and r.stdout.strip() == f"sim plans ok: {len(GRID)} shapes", (r.returncode, r.stdout, r.stderr)
