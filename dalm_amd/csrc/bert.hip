@@ -219,6 +219,118 @@ __global__ __launch_bounds__(256) void bert_add_norm_bwd_kernel(const AddNormArg
   }
 }
 
+// ---- RoBERTa-family embeddings front end: ids -> the first layer's input in one launch (forward only) ----
+// transformers' {Roberta,XLMRoberta,Camembert}Embeddings.forward evaluates, as ~20 eager launches,
+//     position_ids = create_position_ids_from_input_ids(input_ids, padding_idx)     (ne, int, cumsum, type_as, add, mul, long, add)
+//     embeddings = (word_embeddings(input_ids) + token_type_embeddings(token_type_ids)) + position_embeddings(position_ids)
+//     embeddings = dropout(LayerNorm(embeddings))                                   (f32 under bf16 autocast)
+// Here one wave per row (b, t): the position is padding_idx + |{j <= t : ids[b, j] != padding_idx}| for a non-pad id and padding_idx
+// for a pad id (ballot + popcount over ids[b, 0..t]), or read from `pos` where the caller has it (the packed route); the three
+// table rows are summed in eager's order in f32, normalised in f32, y32 = keep ? y / (1 - p) : 0, y16 = bf16(y32).
+// Every table index is CLAMPED into its table: eager device-asserts on an out-of-range id, this kernel reads row 0 / the last row
+// instead of memory outside the allocation.  Used only where the tables and the LayerNorm are frozen: nothing is saved.
+struct EmbedNormArgs {
+  const long long *ids, *tt, *pos;   // [B, T]; tt NULL: type 0; pos NULL: derived from ids
+  const float *word, *type, *ptab;   // [V, D], [NT, D], [NP, D]
+  const void *w, *b;                 // [D]
+  float* y32;
+  unsigned short* y16;
+  const unsigned char* live;         // [B T] or NULL
+  long long V, NT, NP, pad;
+  int R, T, D;
+  float eps, keep_scale;
+  DropArgs drop;                     // thr16 == 0: no dropout
+};
+
+__device__ __forceinline__ long long clamp_index(long long i, long long n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
+
+template <int NCH, bool WBF16>
+__global__ __launch_bounds__(256) void embed_norm_fwd_kernel(const EmbedNormArgs p) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= p.R) return;
+  const int64_t base = static_cast<int64_t>(row) * p.D;
+  if (p.live && !p.live[row]) {                                    // wave-uniform
+    float z[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) z[e] = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int d = (c * 64 + lane) * 8;
+      if (d >= p.D) continue;
+      F8::store(p.y32 + base + d, z);
+      *reinterpret_cast<uint4*>(p.y16 + base + d) = make_uint4(0u, 0u, 0u, 0u);
+    }
+    return;
+  }
+  const int bi = row / p.T, t = row - bi * p.T;
+  const long long* idrow = p.ids + static_cast<int64_t>(bi) * p.T;
+  const long long id = idrow[t];
+  long long pos;
+  if (p.pos) pos = p.pos[row];
+  else {
+    int cnt = 0;
+    for (int j0 = 0; j0 <= t; j0 += 64) {                          // wave-uniform trip count: every lane reaches the ballot
+      const int j = j0 + lane;
+      const bool tok = j <= t && idrow[j] != p.pad;
+      cnt += __popcll(__ballot(tok));
+    }
+    pos = id != p.pad ? p.pad + cnt : p.pad;
+  }
+  const float* wr = p.word + clamp_index(id, p.V) * p.D;
+  const float* tr = p.type + clamp_index(p.tt ? p.tt[row] : 0, p.NT) * p.D;
+  const float* pr = p.ptab + clamp_index(pos, p.NP) * p.D;
+  const bool drop = p.drop.thr16 != 0u;
+  DropKey key = {0u, 1u};
+  if (drop) key = lora::drop_key(p.drop);
+  float s[NCH][8];
+  float sum = 0.f;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * 8;
+    if (d >= p.D) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s[c][e] = 0.f;
+      continue;
+    }
+    float a[8], ty[8], po[8];
+    F8::load(wr + d, a);
+    F8::load(tr + d, ty);
+    F8::load(pr + d, po);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      s[c][e] = (a[e] + ty[e]) + po[e];
+      sum += s[c][e];
+    }
+  }
+  const float mean = wave_sum(sum) / static_cast<float>(p.D);
+  float ss = 0.f;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * 8;
+    if (d >= p.D) continue;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ss = fmaf(s[c][e] - mean, s[c][e] - mean, ss);
+  }
+  const float rstd = rsqrtf(wave_sum(ss) / static_cast<float>(p.D) + p.eps);
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * 8;
+    if (d >= p.D) continue;
+    float wv[8], bv[8], o[8];
+    ldw<WBF16>(p.w, d, wv);
+    ldw<WBF16>(p.b, d, bv);
+    unsigned int bits = 0xffu;
+    if (drop) bits = keep_bits8(static_cast<unsigned int>((base + d) >> 3), key, p.drop.thr16);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      o[e] = fmaf((s[c][e] - mean) * rstd, wv[e], bv[e]);
+      if (drop) o[e] = ((bits >> e) & 1u) ? o[e] * p.keep_scale : 0.f;
+    }
+    F8::store(p.y32 + base + d, o);
+    *reinterpret_cast<uint4*>(p.y16 + base + d) = enc8(o);
+  }
+}
+
 }  // namespace
 }  // namespace dalm
 
@@ -295,4 +407,40 @@ extern "C" int dalm_bert_add_norm_bwd(const float* g32, const void* g16, const v
                                       const uint8_t* keep_bits, const float* mean, const float* rstd, int64_t R, int64_t D,
                                       float dropout_p, float* d_res, void* d_a, dalm_stream_t stream) {
   return dalm_bert_add_norm_bwd_live(g32, g16, a, res, w, w_bf16, keep_bits, mean, rstd, R, D, dropout_p, d_res, d_a, nullptr, stream);
+}
+
+extern "C" int dalm_embed_norm_fwd(const int64_t* ids, const int64_t* token_type_ids, const int64_t* position_ids, const float* word,
+                                   const float* type, const float* pos, int64_t vocab, int64_t type_vocab, int64_t max_pos,
+                                   int64_t padding_idx, const void* w, const void* b, int w_bf16, int64_t B, int64_t T, int64_t D,
+                                   float eps, float dropout_p, const void* seed, uint32_t salt, float* y32, void* y16,
+                                   const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(B >= 0 && T >= 0, DALM_E_SHAPE, "B and T must be >= 0");
+  if (B == 0 || T == 0) return 0;
+  DALM_REQUIRE(ids && word && type && pos && w && b && y32 && y16, DALM_E_NULL, "null pointer argument");
+  DALM_REQUIRE(B <= (1ll << 30) && T <= (1ll << 30) && B * T <= (1ll << 30), DALM_E_SHAPE, "too many rows");
+  DALM_REQUIRE(D > 0 && D % 8 == 0 && D <= 2048, DALM_E_SHAPE, "D must be a multiple of 8, at most 2048");
+  DALM_REQUIRE(vocab > 0 && type_vocab > 0 && max_pos > 0, DALM_E_SHAPE, "every table needs at least one row");
+  DALM_REQUIRE(aligned16(word, type, pos, w, b, y32, y16), DALM_E_ALIGN, "tensors must be 16-byte aligned");
+  DALM_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f && (dropout_p == 0.f || seed), DALM_E_SHAPE,
+               "dropout needs 0 <= p < 1 and a device seed word");
+  const int64_t R = B * T;
+  DALM_REQUIRE(R * D < (1ll << 35), DALM_E_SHAPE, "tensor too large (the mask's chunk index is 32 bits)");
+  EmbedNormArgs p = {};
+  p.ids = reinterpret_cast<const long long*>(ids);
+  p.tt = reinterpret_cast<const long long*>(token_type_ids);
+  p.pos = reinterpret_cast<const long long*>(position_ids);
+  p.word = word; p.type = type; p.ptab = pos; p.w = w; p.b = b;
+  p.y32 = y32; p.y16 = static_cast<unsigned short*>(y16); p.live = row_live;
+  p.V = vocab; p.NT = type_vocab; p.NP = max_pos; p.pad = padding_idx;
+  p.R = static_cast<int>(R); p.T = static_cast<int>(T); p.D = static_cast<int>(D); p.eps = eps;
+  p.keep_scale = dropout_p > 0.f ? 1.0f / (1.0f - dropout_p) : 1.0f;
+  p.drop = lora::drop_args(dropout_p, seed, salt);
+  if (dropout_p == 0.f) p.drop.thr16 = 0u;
+  const dim3 grid(static_cast<unsigned>((R + 3) / 4));
+  by_ceil<1, 2, 4>(static_cast<int>((D + 511) / 512), [&](auto nch) {   // chunks of 64 lanes x 8 elements per row
+    by_bool(w_bf16 != 0, [&](auto wb) {
+      hipLaunchKernelGGL((embed_norm_fwd_kernel<nch, wb>), grid, dim3(256), 0, as_stream(stream), p);
+    });
+  });
+  return check_launch(__func__);
 }

@@ -175,7 +175,7 @@ def embed_dataset(dataset, prefix: str, forward_fn, device: str, torch_dtype: to
         ids_b, mask_b = ids[idx], mask[idx]
         rows, cu = packed.pack_plan(mask_b, shifted=False, last_column=causal)
         ids_p, pos, desc, _valid = packed.packed_inputs(ids_b.to(device), mask_b.to(device), rows.to(device), cu.to(device),
-                                                        causal=causal)
+                                                        causal=causal, model=enc)
         with torch.no_grad(), _autocast(device, torch_dtype):
             if causal:
                 h = enc.base_model(input_ids=ids_p, attention_mask=desc, position_ids=pos, use_cache=False)[0][0]

@@ -155,6 +155,9 @@ SIGNATURES = {
     "dalm_bert_add_norm_fwd_live": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _f32, _f32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _vp]),
     "dalm_bert_add_norm_bwd_live": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
+    # RoBERTa-family embeddings: positions from ids + three table rows + LayerNorm + dropout, forward only
+    "dalm_embed_norm_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _int, _i64, _i64, _i64, _f32, _f32,
+                                   _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
     "dalm_lora2_rowdot_live": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _f32, _f32, _vp, C.c_uint32,
                                       C.c_uint32, _int, _vp, _vp]),
     "dalm_lora2_rankupd_live": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _f32, _int, _vp, _vp]),

@@ -13,6 +13,11 @@ node, its gradient is added to y32's in the backward kernel.
 Dropout (BERT's hidden_dropout_prob, training mode) comes from this library's generator (seed word + salt + element index, mask
 kept as bits; oracle/lora_mask.py::keep_mask_v2) - torch's philox stream has no reference to match.  Needs its own RNG state to be
 re-run: not supported under activation recompute.
+
+The RoBERTa family (roberta, xlm-roberta, camembert) runs the same layer code, so the node above serves it unchanged; its
+embeddings front end - positions counted from the ids, three table gathers, two adds, an f32 LayerNorm, a dropout: ~20 eager
+launches per tower call - is `dalm_embed_norm_fwd` (`embed_norm`, forward only: used while the tables and the LayerNorm are
+frozen f32 tensors under bf16 autocast, so nothing needs a backward).  BertEmbeddings keeps transformers' code.
 """
 from __future__ import annotations
 
@@ -100,6 +105,74 @@ def add_norm(a, res, ln: torch.nn.LayerNorm, p: float, salt: int, live=None) -> 
     """LayerNorm(dropout_p(a) + res) -> the f32 result carrying its bf16 twin.  live: uint8 row liveness; None: that of the tower
     call in progress (dalm_amd/live_rows.py), if any."""
     y32, y16 = _BertAddNorm.apply(a, res, ln.weight, ln.bias, float(ln.eps), float(p), int(salt), live)
+    y32._dalm_bf16 = y16
+    y32._dalm_bf16_version, y32._dalm_bf16_tversion = y32._version, y16._version
+    return y32
+
+
+# ---- RoBERTa-family embeddings front end: `dalm_embed_norm_fwd` (forward only) -------------------------------------------------
+def embed_supported(emb: torch.nn.Module, input_ids, token_type_ids, position_ids, inputs_embeds, past_key_values_length) -> bool:
+    """A {Roberta,XLMRoberta,Camembert}Embeddings call the kernel stands for: ids [B, T] on a GPU under bf16 autocast, three frozen
+    f32 tables and a frozen affine LayerNorm (the LoRA configuration: the output carries no gradient, nothing is saved), no
+    `inputs_embeds`, no cache offset, and - where the positions are derived from the ids - room for them in the position table
+    (T + padding_idx + 1 <= max_position_embeddings: a longer row makes eager raise, and eager is what then runs)."""
+    if inputs_embeds is not None or input_ids is None or not isinstance(past_key_values_length, int) or past_key_values_length != 0:
+        return False
+    if not (input_ids.is_cuda and input_ids.dim() == 2 and input_ids.dtype == torch.int64):
+        return False
+    ln, pad = emb.LayerNorm, emb.padding_idx
+    tables = (emb.word_embeddings, emb.token_type_embeddings, emb.position_embeddings)
+    w, b = getattr(ln, "weight", None), getattr(ln, "bias", None)
+    if w is None or b is None or w.requires_grad or b.requires_grad or not isinstance(pad, int) or pad < 0:
+        return False
+    D = tables[0].weight.shape[1]
+    for t in tables:
+        tw = t.weight
+        if (tw.requires_grad or tw.dtype != torch.float32 or not tw.is_contiguous() or tw.device != input_ids.device
+                or tw.shape[1] != D or t.max_norm is not None):
+            return False
+    for ids in (token_type_ids, position_ids):
+        if ids is not None and not (ids.dtype == torch.int64 and ids.device == input_ids.device and ids.dim() == 2
+                                    and ids.shape[1] == input_ids.shape[1] and ids.shape[0] in (1, input_ids.shape[0])):
+            return False
+    if position_ids is None and input_ids.shape[1] + pad + 1 > tables[2].weight.shape[0]:
+        return False
+    return (tuple(ln.normalized_shape) == (D,) and D % 8 == 0 and D <= 2048 and w.dtype == b.dtype
+            and w.dtype in (torch.float32, torch.bfloat16) and w.is_contiguous() and b.is_contiguous() and w.device == input_ids.device
+            and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16)
+
+
+def _ids(t, like):
+    if t is None:
+        return None
+    t = t.expand_as(like) if t.shape != like.shape else t
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def embed_norm(emb: torch.nn.Module, input_ids, token_type_ids, position_ids, p: float, salt: int, live=None) -> torch.Tensor:
+    """dropout_p(LayerNorm((word[ids] + type[token_type_ids]) + pos[positions])) of a RoBERTa-family embeddings module for what
+    `embed_supported` accepts -> the f32 result [B, T, D] carrying its bf16 twin (as `add_norm`'s), no autograd node.
+    position_ids None: derived from the ids in the kernel.  live: uint8 row liveness; None: that of the tower call in progress."""
+    B, T = input_ids.shape
+    dev = input_ids.device
+    word, typ, pos = emb.word_embeddings.weight, emb.token_type_embeddings.weight, emb.position_embeddings.weight
+    ln = emb.LayerNorm
+    D = word.shape[1]
+    ids = input_ids if input_ids.is_contiguous() else input_ids.contiguous()
+    tt, ps = _ids(token_type_ids, ids), _ids(position_ids, ids)
+    if live is None:
+        live = live_rows.current(B * T, dev)
+    y32 = torch.empty((B, T, D), dtype=torch.float32, device=dev)
+    y16 = torch.empty((B, T, D), dtype=torch.bfloat16, device=dev)
+    seed = None
+    if p > 0.0:
+        from . import lora_ops
+
+        seed = lora_ops.dropout_seed(dev)
+    hip.call("dalm_embed_norm_fwd", hip.ptr(ids), hip.ptr(tt), hip.ptr(ps), hip.ptr(word), hip.ptr(typ), hip.ptr(pos), word.shape[0],
+             typ.shape[0], pos.shape[0], int(emb.padding_idx), hip.ptr(ln.weight), hip.ptr(ln.bias), int(ln.weight.dtype == torch.bfloat16),
+             B, T, D, float(ln.eps), float(p), hip.ptr(seed), int(salt) & 0xFFFFFFFF, hip.ptr(y32), hip.ptr(y16), hip.ptr(live),
+             hip.stream())
     y32._dalm_bf16 = y16
     y32._dalm_bf16_version, y32._dalm_bf16_tversion = y32._version, y16._version
     return y32

@@ -400,14 +400,20 @@ def _bert_output_forward(self, hidden_states: torch.Tensor, input_tensor: torch.
     return self.LayerNorm(hidden_states + input_tensor)
 
 
+# BertSelfOutput / BertOutput and the classes of the RoBERTa family whose forward is the same three statements (xlm-roberta-xl's
+# `XLMRobertaXL*` classes are other code - no LayerNorm in the self-output - and are not named)
+_BERT_OUTPUT_CLASSES = tuple(f"{family}{kind}" for family in ("Bert", "Roberta", "XLMRoberta", "Camembert")
+                             for kind in ("SelfOutput", "Output"))
+
+
 def use_bert_layer_kernels(model: torch.nn.Module) -> int:
-    """Patch BertSelfOutput / BertOutput modules whose forward is the three statements above (source checked once per class) and
-    whose LayerNorm is frozen.  Returns how many modules were patched."""
+    """Patch {Bert,Roberta,XLMRoberta,Camembert}{SelfOutput,Output} modules whose forward is the three statements above (source
+    checked once per class) and whose LayerNorm is frozen.  Returns how many modules were patched."""
     def dense_dropout_norm(mod) -> bool:
         return (isinstance(getattr(mod, "LayerNorm", None), torch.nn.LayerNorm)
                 and isinstance(getattr(mod, "dropout", None), torch.nn.Dropout) and hasattr(mod, "dense"))
 
-    return _install(model, ("BertSelfOutput", "BertOutput"), dense_dropout_norm, "bert-output", _bert_output_forward)
+    return _install(model, _BERT_OUTPUT_CLASSES, dense_dropout_norm, "bert-output", _bert_output_forward)
 
 
 _SOURCE_GUARDS["bert-output"] = (
@@ -415,6 +421,78 @@ _SOURCE_GUARDS["bert-output"] = (
                          and _body(src)[1:] == ["hidden_states = self.dense(hidden_states)", "hidden_states = self.dropout(hidden_states)",
                                                 "hidden_states = self.LayerNorm(hidden_states + input_tensor)", "return hidden_states"]),
     "dense -> dropout -> LayerNorm(h + input) here")
+
+
+# ---------------------------------------------------------------------------
+# RoBERTa-family embeddings: positions from the ids + three table rows + LayerNorm + dropout in one launch (forward only)
+# ---------------------------------------------------------------------------
+_ROBERTA_EMBEDDINGS_PARAMS = ["self", "input_ids", "token_type_ids", "position_ids", "inputs_embeds", "past_key_values_length"]
+
+
+def _roberta_embeddings_forward(self, input_ids=None, token_type_ids=None, position_ids=None, inputs_embeds=None,
+                                past_key_values_length=0):
+    """transformers' {Roberta,XLMRoberta,Camembert}Embeddings.forward:
+        position_ids = create_position_ids_from_input_ids(input_ids, self.padding_idx)     (when none are given)
+        token_type_ids = the all-zero buffer                                               (when none are given)
+        embeddings = (word_embeddings(input_ids) + token_type_embeddings(token_type_ids)) + position_embeddings(position_ids)
+        embeddings = self.dropout(self.LayerNorm(embeddings))
+    as `dalm_embed_norm_fwd` where the three tables and the LayerNorm are frozen f32 / bf16-autocast GPU tensors
+    (`bert_ops.embed_supported`); every other call runs the module's own statements.  BertEmbeddings is NOT patched: its dropout
+    would draw another mask than today's."""
+    from . import bert_ops
+    from .lora import dropout_salt
+
+    if bert_ops.embed_supported(self, input_ids, token_type_ids, position_ids, inputs_embeds, past_key_values_length):
+        p = float(self.dropout.p) if self.training else 0.0
+        return bert_ops.embed_norm(self, input_ids, token_type_ids, position_ids, p, dropout_salt(self, "_dalm_calls"))
+    return self._dalm_orig_forward(input_ids=input_ids, token_type_ids=token_type_ids, position_ids=position_ids,
+                                   inputs_embeds=inputs_embeds, past_key_values_length=past_key_values_length)
+
+
+def use_roberta_embeddings(model: torch.nn.Module) -> int:
+    """Patch {Roberta,XLMRoberta,Camembert}Embeddings modules whose forward is the code `_roberta_embeddings_forward` restates
+    (signature and statements checked once per class).  Returns the count."""
+    def three_tables(mod) -> bool:
+        return (all(isinstance(getattr(mod, a, None), torch.nn.Embedding)
+                    for a in ("word_embeddings", "token_type_embeddings", "position_embeddings"))
+                and isinstance(getattr(mod, "LayerNorm", None), torch.nn.LayerNorm)
+                and isinstance(getattr(mod, "dropout", None), torch.nn.Dropout) and isinstance(getattr(mod, "padding_idx", None), int))
+
+    def guard(mod) -> bool:
+        cls = type(mod)
+        return _matches("roberta-embeddings", cls) and _guard(
+            ("roberta-positions", cls), cls.__name__ + ".create_position_ids_from_input_ids",
+            "padding_idx + cumsum(ids != padding_idx) * (ids != padding_idx) here", lambda: _roberta_positions_match(cls))
+
+    return _install(model, ("RobertaEmbeddings", "XLMRobertaEmbeddings", "CamembertEmbeddings"), three_tables, guard,
+                    _roberta_embeddings_forward, keep="_dalm_orig_forward")
+
+
+def _roberta_positions_match(cls) -> bool:
+    """The class's create_position_ids_from_input_ids IS the rule the kernel and `packed.packed_positions` restate."""
+    import inspect
+
+    src = inspect.getsource(cls.create_position_ids_from_input_ids)
+    return all(s in src for s in ("mask = input_ids.ne(padding_idx).int()",
+                                  "incremental_indices = (torch.cumsum(mask, dim=1).type_as(mask) + past_key_values_length) * mask",
+                                  "return incremental_indices.long() + padding_idx"))
+
+
+_ROBERTA_EMBEDDINGS_BODY = [
+    "if token_type_ids is None:", 'if hasattr(self, "token_type_ids"):',
+    "buffered_token_type_ids = self.token_type_ids.to(position_ids.device).expand(position_ids.shape[0], -1)",
+    "buffered_token_type_ids = torch.gather(buffered_token_type_ids, dim=1, index=position_ids)",
+    "token_type_ids = buffered_token_type_ids.expand(batch_size, seq_length)", "else:",
+    "token_type_ids = torch.zeros(input_shape, dtype=torch.long, device=self.position_ids.device)",
+    "if inputs_embeds is None:", "inputs_embeds = self.word_embeddings(input_ids)",
+    "token_type_embeddings = self.token_type_embeddings(token_type_ids)", "embeddings = inputs_embeds + token_type_embeddings",
+    "position_embeddings = self.position_embeddings(position_ids)", "embeddings = embeddings + position_embeddings",
+    "embeddings = self.LayerNorm(embeddings)", "embeddings = self.dropout(embeddings)", "return embeddings"]
+_SOURCE_GUARDS["roberta-embeddings"] = (
+    lambda params, src: (params == _ROBERTA_EMBEDDINGS_PARAMS
+                         and _body(src)[-len(_ROBERTA_EMBEDDINGS_BODY):] == _ROBERTA_EMBEDDINGS_BODY
+                         and "position_ids = self.create_position_ids_from_input_ids(" in src
+                         and "input_ids, self.padding_idx, past_key_values_length" in src), _RESTATED)
 
 
 # ---------------------------------------------------------------------------

@@ -16,8 +16,8 @@ from ..utils import eos_mask
 from . import lora
 from .attention import use_hip_attention_backward
 from .fastpath import (use_bert_layer_kernels, use_capturable_falcon_heads, use_falcon_attention_kernels, use_falcon_layer_kernels,
-                       use_fused_residual_norm, use_llama_attention_node, use_native_rms_norm, use_qwen3_attention_node, use_roll_rope,
-                       use_swiglu_kernel)
+                       use_fused_residual_norm, use_llama_attention_node, use_native_rms_norm, use_qwen3_attention_node, use_roberta_embeddings,
+                       use_roll_rope, use_swiglu_kernel)
 
 
 class Mode(Enum):
@@ -167,7 +167,8 @@ class AutoModelForRagE2E(torch.nn.Module):
         if autoregressive:
             use_causal_retriever_fast_paths(self.retriever_model)
         else:
-            use_hip_attention_backward(self.retriever_model)      # BERT: head width 64, attention dropout inside the kernels
+            # BERT and the RoBERTa family (recognised from the config): attention dropout inside the kernels
+            use_hip_attention_backward(self.retriever_model)
         if get_peft is not None:
             get_peft = Mode(get_peft)
             if get_peft in (Mode.RETRIEVER, Mode.BOTH):
@@ -182,6 +183,7 @@ class AutoModelForRagE2E(torch.nn.Module):
         use_transposed_dgrad(self.generator_model)
         use_transposed_dgrad(self.retriever_model)
         use_bert_layer_kernels(self.retriever_model)              # dropout + add + LayerNorm of a BERT layer: one launch each way
+        use_roberta_embeddings(self.retriever_model)              # RoBERTa family: ids -> first layer input in one launch
 
     # ---- retrieval tower ---------------------------------------------------------------
     def retrieval_hidden(self, input_ids: torch.Tensor, attention_mask: torch.Tensor):

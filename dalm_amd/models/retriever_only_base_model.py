@@ -47,16 +47,17 @@ class AutoModelForSentenceEmbedding(torch.nn.Module):
         if is_autoregressive:                         # a causal LM: the generator's layer nodes (Llama-family; each guards itself)
             use_causal_retriever_fast_paths(self.model)
         else:
-            use_hip_attention_backward(self.model)    # BERT: dalm_attn_* (attention dropout inside the kernels)
+            use_hip_attention_backward(self.model)    # BERT, RoBERTa family: dalm_attn_* (attention dropout inside the kernels)
         if get_peft:
             lora.inject_lora(self.model, ["key", "query", "value"] if not is_autoregressive else ["q_proj", "v_proj"])
         # frozen projections: backward GEMM through a transposed weight copy; BERT layers: dropout + add + LayerNorm in one launch
         # each way (both no-ops for a model that is fine-tuned in full: they look at requires_grad)
-        from .fastpath import use_bert_layer_kernels
+        from .fastpath import use_bert_layer_kernels, use_roberta_embeddings
         from .frozen_linear import use_transposed_dgrad
 
         use_transposed_dgrad(self.model)
         use_bert_layer_kernels(self.model)
+        use_roberta_embeddings(self.model)            # RoBERTa family: positions + tables + LayerNorm + dropout in one launch
         self.normalize = normalize
         self.is_autoregressive = is_autoregressive
         self.tokenizer = tokenizer

@@ -12,8 +12,10 @@ through both towers; padding contributes exactly zero to its loss and to every g
 So the same loss and the same gradients come out of the towers run on a [n_live, H] matrix of the tokens that matter - at
 BASELINE.json's cfg3 batch 2.9 k instead of 4.6 k generator rows and ~20 % of the query tower's - provided that
 
-  * every token keeps its ORIGINAL column as its position (rotary tables / BERT position embeddings: transformers numbers
-    positions by column, padding included),
+  * every token keeps the position the PADDED call gives it: its original column for rotary tables and BERT's position
+    embeddings (transformers numbers those by column, padding included); for the RoBERTa family (roberta, xlm-roberta,
+    camembert) padding_idx + the number of non-pad IDS up to and including its column, computed on the padded ids before the
+    gather (`packed_positions`, the one place where the family decides),
   * attention runs per sequence (`dalm_attn_*_packed`: cu_seqlens, no cross-sequence tiles), and
   * a token that is needed only as a QUERY stays in: with left padding, row t0 - 1 (the last padding position) predicts the
     first real token with weight attention_mask[b, t0] = 1.  It attends nothing (its keys are all padding: output 0, as the padded
@@ -138,8 +140,39 @@ def packed_of(mask) -> Optional[PackedSeqs]:
     return getattr(mask, "_dalm_packed", None) if mask is not None else None
 
 
-def packed_inputs(input_ids: torch.Tensor, attention_mask: torch.Tensor, rows: torch.Tensor, cu: torch.Tensor, causal: bool):
-    """Device side, no host sync: (ids [1, n], position_ids [1, n], mask descriptor, valid [n] bool).
+# model types whose embeddings number positions from the DATA (transformers' create_position_ids_from_input_ids), not by column
+POSITIONS_FROM_IDS = ("roberta", "xlm-roberta", "camembert")
+
+
+def position_padding_idx(model) -> Optional[int]:
+    """The `padding_idx` of a model of the RoBERTa family (its config's pad_token_id), None for every other model: BERT and the
+    decoders number positions by column."""
+    cfg = getattr(model, "config", None)
+    if getattr(cfg, "model_type", None) not in POSITIONS_FROM_IDS:
+        return None
+    return int(cfg.pad_token_id)
+
+
+def packed_positions(input_ids: torch.Tensor, rows: torch.Tensor, padding_idx: Optional[int] = None) -> torch.Tensor:
+    """Device side, no host sync: the position id of every packed row, int64 [n] - THE place where the model family decides.
+    padding_idx None (BERT, the decoders): the original column, r % T; 0 on a slack row.
+    padding_idx given (`position_padding_idx`: RoBERTa, XLM-RoBERTa, CamemBERT): what transformers computes on the padded [B, T]
+    ids - padding_idx + the number of ids != padding_idx up to and including the column for such an id, padding_idx for a pad id
+    (the count runs over the IDS, not over the attention mask) - gathered at the kept rows; padding_idx on a slack row."""
+    B, T = input_ids.shape
+    valid = rows >= 0
+    r = rows.clamp_min(0)
+    if padding_idx is None:
+        return torch.where(valid, r % T, torch.zeros_like(r))
+    tok = input_ids.ne(padding_idx)
+    pos = torch.cumsum(tok, dim=1, dtype=torch.int64) * tok + padding_idx
+    return torch.where(valid, pos.reshape(-1).index_select(0, r), torch.full_like(r, padding_idx))
+
+
+def packed_inputs(input_ids: torch.Tensor, attention_mask: torch.Tensor, rows: torch.Tensor, cu: torch.Tensor, causal: bool,
+                  model=None):
+    """Device side, no host sync: (ids [1, n], position_ids [1, n], mask descriptor, valid [n] bool).  `model`: the tower the
+    inputs are for - its family picks the position rule (`packed_positions`); None: positions by column.
 
     The descriptor is a 4-D tensor: transformers' mask builders return 4-D masks untouched (masking_utils
     `_preprocess_mask_arguments`), so it reaches every layer's attention call, where `packed_of` finds the sequences."""
@@ -147,7 +180,7 @@ def packed_inputs(input_ids: torch.Tensor, attention_mask: torch.Tensor, rows: t
     valid = rows >= 0
     r = rows.clamp_min(0)
     ids_p = input_ids.reshape(-1).index_select(0, r)
-    pos = torch.where(valid, r % T, torch.zeros_like(r))
+    pos = packed_positions(input_ids, rows, position_padding_idx(model))
     key_live = ((attention_mask.reshape(-1).index_select(0, r) != 0) & valid).to(torch.uint8)
     seqs = PackedSeqs(cu=cu.to(torch.int32), nseq=int(cu.numel()) - 1, T=int(T), n=int(rows.numel()), key_live=key_live, causal=causal)
     desc = attach(torch.ones((1, 1, 1, 1), dtype=torch.bool, device=input_ids.device), seqs)
@@ -194,7 +227,7 @@ def retrieval_hidden(retriever_model, input_ids, attention_mask, rows, cu):
     """Token states of an encoder retriever on the packed rows, scattered back to the padded [B, T, D] layout (zeros at the
     padding, which the pooling kernel never reads: it multiplies with the mask)."""
     B, T = input_ids.shape
-    ids_p, pos, desc, valid = packed_inputs(input_ids, attention_mask, rows, cu, causal=False)
+    ids_p, pos, desc, valid = packed_inputs(input_ids, attention_mask, rows, cu, causal=False, model=retriever_model)
     h = retriever_model(input_ids=ids_p, attention_mask=desc, position_ids=pos)[0][0]              # [n, D]
     dst = torch.where(valid, rows, torch.full_like(rows, B * T))                                     # slack -> a dump row
     full = h.new_zeros((B * T + 1, h.shape[-1])).index_copy(0, dst, h)
@@ -210,7 +243,7 @@ def retrieval_hidden_pair(retriever_model, first, second):
     parts = []
     off = 0
     for ids, mask, rows, cu in (first, second):
-        ids_p, pos, desc, valid = packed_inputs(ids, mask, rows, cu, causal=False)
+        ids_p, pos, desc, valid = packed_inputs(ids, mask, rows, cu, causal=False, model=retriever_model)
         sq = packed_of(desc)
         parts.append((ids_p, pos, sq, valid, rows, ids.shape, off))
         off += int(rows.numel())

@@ -584,6 +584,23 @@ int dalm_bert_add_norm_bwd_live(const float* g32, const void* g16, const void* a
                                 const uint8_t* keep_bits, const float* mean, const float* rstd, int64_t R, int64_t D,
                                 float dropout_p, float* d_res, void* d_a, const uint8_t* row_live, dalm_stream_t stream);
 
+/* RoBERTa-family embeddings front end ({Roberta,XLMRoberta,Camembert}Embeddings.forward of transformers, reached through
+ * self.retriever_model(...)): ids to the first layer's input in one launch, forward only (dalm_amd/csrc/bert.hip).
+ *   s = (word[id] + type[tt]) + pos[p] in f32;  y = LayerNorm(s) (f32);  y32 = keep ? y / (1 - p) : 0;  y16 = bf16(y32).
+ *   ids [B, T] int64; token_type_ids [B, T] int64 or NULL (type 0); position_ids [B, T] int64 or NULL: the position of (b, t) is
+ *   then padding_idx + |{j <= t : ids[b, j] != padding_idx}| for ids[b, t] != padding_idx and padding_idx otherwise
+ *   (create_position_ids_from_input_ids).  word [vocab, D], type [type_vocab, D], pos [max_pos, D] f32 with row pitch D; w / b [D]
+ *   f32 (w_bf16 == 0) or bf16; D a multiple of 8, at most 2048.  The keep mask is that of dalm_bert_add_norm_fwd over the flat
+ *   index of y (seed: a 64-bit word in DEVICE memory; NULL allowed when dropout_p == 0); it is not stored - nothing here has a
+ *   backward, the caller uses this only while the tables and the LayerNorm are frozen.  row_live [B T] or NULL: a dead row is
+ *   not read and leaves as zeros.  Table indices are CLAMPED into their tables (eager device-asserts on an out-of-range id;
+ *   this entry point never reads outside an allocation). */
+int dalm_embed_norm_fwd(const int64_t* ids, const int64_t* token_type_ids, const int64_t* position_ids, const float* word,
+                        const float* type, const float* pos, int64_t vocab, int64_t type_vocab, int64_t max_pos,
+                        int64_t padding_idx, const void* w, const void* b, int w_bf16, int64_t B, int64_t T, int64_t D, float eps,
+                        float dropout_p, const void* seed, uint32_t salt, float* y32, void* y16, const uint8_t* row_live,
+                        dalm_stream_t stream);
+
 /* Backward of scaled-dot-product attention, bf16, head width hd = 32, 64 or 128, boolean mask (dalm_amd/csrc/attn.hip).  Stands in for the
  * backward of torch.nn.functional.scaled_dot_product_attention as transformers' sdpa_attention_forward calls it inside
  * self.generator_model(...) (dalm/models/rag_e2e_base_model.py:104-106; loss.backward(), train_rage2e.py:466).

@@ -346,6 +346,53 @@ def bench_head_norm_rope(B, T, Hq, Hk, hd, rounds=3):
     return out
 
 
+def bench_embed_norm(B, T, D, p, rounds=3):
+    """The RoBERTa-family embeddings front end (XLM-R-large tables: vocabulary 250002, 514 positions, one token type):
+    `dalm_embed_norm_fwd` beside the module's own eager chain (positions from the ids, three gathers, two adds, f32 LayerNorm,
+    dropout: ~20 launches) on the same right-padded ids, bf16 autocast, alternating in the same process.  Algorithmic bytes: the
+    ids, three f32 table rows per token read, y32 + y16 written.  Every figure: median over `rounds` alternations of a 20-call
+    graph's per-call time, with the lowest and highest round."""
+    from transformers import XLMRobertaConfig
+    from transformers.models.xlm_roberta.modeling_xlm_roberta import XLMRobertaEmbeddings
+
+    from dalm_amd.models import bert_ops
+
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    cfg = XLMRobertaConfig(hidden_size=D, vocab_size=250002, max_position_embeddings=514, type_vocab_size=1, pad_token_id=1,
+                           hidden_dropout_prob=p, layer_norm_eps=1e-5)
+    emb = XLMRobertaEmbeddings(cfg).to(dev).requires_grad_(False).train()
+    g = torch.Generator().manual_seed(1)
+    lens = torch.randint(max(T // 4, 1), T + 1, (B, 1), generator=g)
+    ids = torch.randint(3, 250002, (B, T), generator=g)
+    ids = torch.where(torch.arange(T).unsqueeze(0) < lens, ids, torch.ones_like(ids)).to(dev)
+
+    def kernel():
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            return bert_ops.embed_norm(emb, ids, None, None, p, 7)
+
+    def eager():
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            return emb(input_ids=ids)
+
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        assert bert_ops.embed_supported(emb, ids, None, None, None, 0)
+    if p == 0.0:
+        torch.testing.assert_close(kernel(), eager(), rtol=3e-6, atol=3e-6)
+    fns = {"kernel (1 launch)": kernel, "eager chain": eager}
+    nbytes = B * T * (8 + 3 * D * 4 + D * 4 + D * 2)
+    seen = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, fn in fns.items():
+            seen[name].append(time_graph(fn)[0])
+    out = {}
+    for name, ts in seen.items():
+        ts.sort()
+        med = ts[len(ts) // 2]
+        out[name] = {"s": med, "lo": ts[0], "hi": ts[-1], "GBps": nbytes / med / 1e9, "frac": nbytes / med / HBM_PEAK}
+    return out
+
+
 def print_results(res) -> None:
     for k, v in res.items():
         print(k)
@@ -413,6 +460,10 @@ def main():
     if args.only in ("", "head_norm_rope"):
         res["head_norm_rope Qwen3-8B generator rows 18x256, 32+8 heads x 128"] = bench_head_norm_rope(18, 256, 32, 8, 128)
         res["head_norm_rope Qwen3-8B packed rows 1x3008, 32+8 heads x 128"] = bench_head_norm_rope(1, 3008, 32, 8, 128)
+    if args.only in ("", "embed_norm"):
+        for B, T in ((150, 128), (150, 50)):
+            for p in (0.0, 0.1):
+                res[f"embed_norm XLM-R-large retriever-only rows {B}x{T} D1024 p={p}"] = bench_embed_norm(B, T, 1024, p)
     Path("gpurun_out").mkdir(exist_ok=True)
     Path("gpurun_out/kernel_bench.json").write_text(json.dumps(res, indent=1))
     print_results(res)
