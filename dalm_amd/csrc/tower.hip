@@ -16,6 +16,8 @@
 //   swiglu forward :  s = rb(g / (1 + exp(-g)));  a = rb(s u)
 //   swiglu backward:  ds = rb(da u);  du = rb(da s);  sig = 1 / (1 + exp(-g));  dg = rb(ds sig (1 + g (1 - sig)))
 // Algorithmic bytes: rope 2 * (|q| + |k|) * el (+ cos/sin, shared by all heads); swiglu forward 3 * n * el, backward 5 * n * el.
+// Further down: RMSNorm with the residual add (dalm_rms_norm_*), Qwen3's head norm + rotary (dalm_head_norm_*), and Gemma's two
+// formulas - GeGLU and the (1 + w) RMSNorm (dalm_geglu_*, dalm_gemma_norm_*) - each with its own comment block.
 #include "dispatch.hpp"
 #include "vec16.hpp"
 
@@ -905,6 +907,402 @@ extern "C" int dalm_head_norm_bwd(const void* gq, const void* gk, const void* q,
   p.live = row_live;
   by_exact<64, 128>(static_cast<int>(hd), [&](auto width) {
     hipLaunchKernelGGL((head_norm_bwd_kernel<width>), grid, dim3(256), 0, as_stream(stream), p);
+  });
+  return check_launch(__func__);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Gemma (modeling_gemma.py): the two row-wise formulas of its decoder layer that differ from Llama's.
+//   GemmaMLP      down(gelu_tanh(gate(x)) * up(x))                                        - dalm_geglu_{fwd,bwd}
+//   GemmaRMSNorm  (x.float() * rsqrt(mean(x.float()^2) + eps) * (1 + w.float())).type_as(x)   - dalm_gemma_norm_{fwd,bwd}
+// Rounding points are the eager chain's and its autograd's (rb = a round trip through the tensor dtype):
+//   geglu forward :  a = rb(gelu_tanh(g));  act = rb(a u)
+//   geglu backward:  du = rb(dact a);  da = rb(dact u);  dg = rb(torch's tanh-GELU backward of da at g)   - a is recomputed
+//   norm forward  :  h = rb(x + delta) [with delta];  rstd = rsqrt(mean(h^2) + eps);  y = rb(h rstd (1 + w))   - ONE rounding
+//   norm backward :  g = dy (1 + w);  xh = h rstd;  dx = rb(rstd (g - xh mean(g xh)) [+ dres])   - where rms_norm_bwd_kernel adds dres
+// Algorithmic bytes: geglu forward 3 R C el, backward 5 R C el; norm forward (2 or 4) R D el, backward (3 or 4) R D el.
+// ---------------------------------------------------------------------------------------------------
+namespace {
+
+// torch's tanh-GELU in f32, operation for operation (ATen's GeluCUDAKernelImpl / GeluBackwardCUDAKernelImpl, approximate = "tanh")
+constexpr float kGeluBeta = 0.7978845608028654f;   // sqrt(2) * (2 / sqrt(pi)) * 0.5
+constexpr float kGeluKappa = 0.044715f;
+__device__ __forceinline__ float gelu_tanh_f32(float x) {
+  const float x_cube = x * x * x;
+  const float inner = kGeluBeta * (x + kGeluKappa * x_cube);
+  return 0.5f * x * (1.0f + tanhf(inner));
+}
+__device__ __forceinline__ float gelu_tanh_bwd_f32(float dy, float x) {
+  const float x_sq = x * x;
+  const float x_cube = x_sq * x;
+  const float inner = kGeluBeta * (x + kGeluKappa * x_cube);
+  const float tanh_inner = tanhf(inner);
+  const float left = 0.5f * x;
+  const float right = 1.0f + tanh_inner;
+  const float left_derivative = 0.5f * right;
+  const float tanh_derivative = 1.0f - tanh_inner * tanh_inner;
+  const float inner_derivative = kGeluBeta * (1.0f + 3.0f * kGeluKappa * x_sq);
+  const float right_derivative = left * tanh_derivative * inner_derivative;
+  return dy * (left_derivative + right_derivative);
+}
+
+// [R, C] views with row strides, walked as tiles of 256 vectors by a capped grid: the tile one grid stride further on lies
+// step_row rows and step_col columns away (the launcher divides once; a thread divides once, for its first tile)
+struct GegluLd { int64_t g, u, a, dg, du; unsigned int C, step_row, step_col; };
+__device__ __forceinline__ RowCol next_tile(RowCol rc, const GegluLd& ld) {
+  rc.row += ld.step_row;
+  rc.col += ld.step_col;
+  if (rc.col >= ld.C) { rc.col -= ld.C; ++rc.row; }
+  return rc;
+}
+// tiles a thread has in flight per trip of its grid-stride loop; 1, 2 and 4 were measured by building with
+// -DDALM_GEGLU_TILES=<n>
+#ifndef DALM_GEGLU_TILES
+#define DALM_GEGLU_TILES 2
+#endif
+constexpr int kGegluTiles = DALM_GEGLU_TILES;
+constexpr int kStreamBlocks = 256 * 8;  // 256 CUs x 8 workgroups
+
+template <typename T>
+__global__ __launch_bounds__(256) void geglu_fwd_kernel(const T* __restrict__ g, const T* __restrict__ u, T* __restrict__ a,
+                                                        int64_t n, GegluLd ld, const unsigned char* __restrict__ live) {
+  constexpr int VEC = Vec16<T>::VEC, K = kGegluTiles;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * 256 * VEC;
+  int64_t e0 = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) * VEC;
+  if (e0 >= n) return;
+  RowCol at = row_col(e0, ld.C);
+  for (; e0 < n; e0 += K * stride) {
+    RowCol rc[K];
+    bool in[K], lv[K];
+    float gv[K][VEC], uv[K][VEC];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      rc[k] = at;
+      at = next_tile(at, ld);
+      in[k] = e0 + k * stride < n;
+      lv[k] = in[k] && (!live || live[rc[k].row]);
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (lv[k]) {
+        Vec16<T>::load(g + ld_at(rc[k], ld.g), gv[k]);
+        Vec16<T>::load(u + ld_at(rc[k], ld.u), uv[k]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (!in[k]) continue;
+      float o[VEC];
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) o[e] = lv[k] ? Vec16<T>::rb(__fmul_rn(Vec16<T>::rb(gelu_tanh_f32(gv[k][e])), uv[k][e])) : 0.f;
+      Vec16<T>::store(a + ld_at(rc[k], ld.a), o);                    // a dead row: nothing was loaded, zeros leave
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void geglu_bwd_kernel(const T* __restrict__ da, const T* __restrict__ g, const T* __restrict__ u,
+                                                        T* __restrict__ dg, T* __restrict__ du, int64_t n, GegluLd ld,
+                                                        const unsigned char* __restrict__ live) {
+  constexpr int VEC = Vec16<T>::VEC, K = kGegluTiles;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * 256 * VEC;
+  int64_t e0 = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) * VEC;
+  if (e0 >= n) return;
+  RowCol at = row_col(e0, ld.C);
+  for (; e0 < n; e0 += K * stride) {
+    RowCol rc[K];
+    bool in[K], lv[K];
+    float dav[K][VEC], gv[K][VEC], uv[K][VEC];                      // d_act, gate, up
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      rc[k] = at;
+      at = next_tile(at, ld);
+      in[k] = e0 + k * stride < n;
+      lv[k] = in[k] && (!live || live[rc[k].row]);
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (lv[k]) {
+        Vec16<T>::load(da + ld_at(rc[k], ld.a), dav[k]);
+        Vec16<T>::load(g + ld_at(rc[k], ld.g), gv[k]);
+        Vec16<T>::load(u + ld_at(rc[k], ld.u), uv[k]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (!in[k]) continue;
+      float og[VEC], ou[VEC];
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        if (lv[k]) {
+          const float x = gv[k][e];
+          const float a = Vec16<T>::rb(gelu_tanh_f32(x));                            // the activation the eager chain saved
+          const float d_a = Vec16<T>::rb(__fmul_rn(dav[k][e], uv[k][e]));
+          ou[e] = Vec16<T>::rb(__fmul_rn(dav[k][e], a));
+          og[e] = Vec16<T>::rb(gelu_tanh_bwd_f32(d_a, x));
+        } else {
+          og[e] = 0.f; ou[e] = 0.f;
+        }
+      }
+      Vec16<T>::store(dg + ld_at(rc[k], ld.dg), og);
+      Vec16<T>::store(du + ld_at(rc[k], ld.du), ou);
+    }
+  }
+}
+
+// N weights from column d on, f32 or bf16 whatever the activations are (the formula casts once, at the end)
+template <int N>
+__device__ __forceinline__ void load_weight(const void* w, bool w_f32, int d, float (&wv)[N]) {
+  if (w_f32) {
+    const float* p = static_cast<const float*>(w) + d;
+#pragma unroll
+    for (int i = 0; i < N; i += 4) {
+      const float4 v = *reinterpret_cast<const float4*>(p + i);
+      wv[i] = v.x; wv[i + 1] = v.y; wv[i + 2] = v.z; wv[i + 3] = v.w;
+    }
+  } else {
+    const bf16_t* p = static_cast<const bf16_t*>(w) + d;
+    if constexpr (N == 8) {
+      Vec16<bf16_t>::load(p, wv);
+    } else {
+      const uint2 v = *reinterpret_cast<const uint2*>(p);
+      wv[0] = __uint_as_float(v.x << 16); wv[1] = __uint_as_float(v.x & 0xffff0000u);
+      wv[2] = __uint_as_float(v.y << 16); wv[3] = __uint_as_float(v.y & 0xffff0000u);
+    }
+  }
+}
+
+// 16 raw bytes of a row as f32 (rows are kept raw between the reduction and the second pass: 4 registers a chunk, not 8)
+__device__ __forceinline__ void dec16(const uint4& v, float (&x)[8]) { dec8(v, x); }
+__device__ __forceinline__ void dec16(const uint4& v, float (&x)[4]) {
+  x[0] = __uint_as_float(v.x); x[1] = __uint_as_float(v.y); x[2] = __uint_as_float(v.z); x[3] = __uint_as_float(v.w);
+}
+
+template <typename T, int NCH, bool ADD>
+__global__ __launch_bounds__(256) void gemma_norm_fwd_kernel(const T* __restrict__ x, const T* __restrict__ delta,
+                                                             const void* __restrict__ w, bool w_f32, T* __restrict__ h_out,
+                                                             T* __restrict__ y, float* __restrict__ rstd_out, int R, int D, float eps,
+                                                             const unsigned char* __restrict__ live) {
+  constexpr int N = Vec16<T>::VEC;
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= R) return;
+  const int64_t base = static_cast<int64_t>(row) * D;
+  if (live && !live[row]) {                      // a dead row (wave-uniform): nothing is read, h, y and rstd leave as zeros
+    float z[N];
+#pragma unroll
+    for (int e = 0; e < N; ++e) z[e] = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int d = (c * 64 + lane) * N;
+      if (d < D) {
+        if constexpr (ADD) Vec16<T>::store(h_out + base + d, z);
+        Vec16<T>::store(y + base + d, z);
+      }
+    }
+    if (lane == 0) rstd_out[row] = 0.f;
+    return;
+  }
+  float v[NCH][N];
+  float ss = 0.f;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * N;
+    if (d < D) {
+      Vec16<T>::load(x + base + d, v[c]);
+      if constexpr (ADD) {
+        float dl[N];
+        Vec16<T>::load(delta + base + d, dl);
+#pragma unroll
+        for (int e = 0; e < N; ++e) v[c][e] = Vec16<T>::rb(v[c][e] + dl[e]);
+        Vec16<T>::store(h_out + base + d, v[c]);
+      }
+#pragma unroll
+      for (int e = 0; e < N; ++e) ss = fmaf(v[c][e], v[c][e], ss);
+    }
+  }
+  ss = wave_sum(ss);
+  const float rstd = rsqrtf(ss / static_cast<float>(D) + eps);
+  if (lane == 0) rstd_out[row] = rstd;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * N;
+    if (d < D) {
+      float wv[N], o[N];
+      load_weight<N>(w, w_f32, d, wv);
+#pragma unroll
+      for (int e = 0; e < N; ++e) o[e] = __fmul_rn(__fmul_rn(v[c][e], rstd), 1.0f + wv[e]);   // f32 throughout, rounded by the store
+      Vec16<T>::store(y + base + d, o);
+    }
+  }
+}
+
+template <typename T, int NCH, bool ADD>
+__global__ __launch_bounds__(256) void gemma_norm_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ h,
+                                                             const void* __restrict__ w, bool w_f32, const float* __restrict__ rstd_in,
+                                                             const T* __restrict__ dres, T* __restrict__ dx, int R, int D,
+                                                             const unsigned char* __restrict__ live) {
+  constexpr int N = Vec16<T>::VEC;
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= R) return;
+  const int64_t base = static_cast<int64_t>(row) * D;
+  const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+  if (live && !live[row]) {                      // a dead row (wave-uniform): dx leaves as zeros
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int d = (c * 64 + lane) * N;
+      if (d < D) *reinterpret_cast<uint4*>(dx + base + d) = zero;
+    }
+    return;
+  }
+  // the streams of a row are requested as raw 16-byte chunks before the wave reduction and decoded twice (rms_norm_bwd_v2_kernel)
+  uint4 rg[NCH], rh[NCH], rr[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * N;
+    const bool ok = d < D;
+    rg[c] = ok ? *reinterpret_cast<const uint4*>(dy + base + d) : zero;
+    rh[c] = ok ? *reinterpret_cast<const uint4*>(h + base + d) : zero;
+    if constexpr (ADD) rr[c] = ok ? *reinterpret_cast<const uint4*>(dres + base + d) : zero;
+  }
+  const float rstd = rstd_in[row];
+  float dot = 0.f;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * N;
+    if (d >= D) continue;
+    float g[N], xh[N], wv[N];
+    dec16(rg[c], g); dec16(rh[c], xh);
+    load_weight<N>(w, w_f32, d, wv);
+#pragma unroll
+    for (int e = 0; e < N; ++e) dot = fmaf(g[e] * (1.0f + wv[e]), xh[e] * rstd, dot);
+  }
+  dot = wave_sum(dot) / static_cast<float>(D);
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * N;
+    if (d >= D) continue;
+    float g[N], xh[N], wv[N], o[N];
+    dec16(rg[c], g); dec16(rh[c], xh);
+    load_weight<N>(w, w_f32, d, wv);
+#pragma unroll
+    for (int e = 0; e < N; ++e) o[e] = rstd * (g[e] * (1.0f + wv[e]) - (xh[e] * rstd) * dot);
+    if constexpr (ADD) {
+      float r[N];
+      dec16(rr[c], r);
+#pragma unroll
+      for (int e = 0; e < N; ++e) o[e] += r[e];
+    }
+    Vec16<T>::store(dx + base + d, o);                             // rounded once
+  }
+}
+
+// the checks the two GeGLU entry points share, after the NULL and dtype checks; fills the grid, the element count and the tile steps
+int geglu_plan(const char* fn, int dtype, int64_t R, int64_t C, std::initializer_list<int64_t> lds, dim3& grid, int64_t& n, GegluLd& ld) {
+  const int vec = dtype == DALM_F32 ? 4 : 8;
+  bool ok = C % vec == 0;
+  for (int64_t l : lds) ok = ok && l % vec == 0 && l >= C;
+  if (!ok) return fail(DALM_E_ALIGN, fn, "16-byte aligned pointers, C and the row strides multiples of 16 bytes, strides >= C");
+  if (R > ((1ll << 32) - 1) / C)                 // C > 0 here; bounded before the product is taken: R C cannot wrap
+    return fail(DALM_E_SHAPE, fn, "tensor too large for one launch (R C must stay below 2^32)");
+  n = R * C;
+  const int64_t tiles = (n + 256 * vec - 1) / (256 * vec), blocks = tiles < kStreamBlocks ? tiles : kStreamBlocks;
+  const int64_t stride = blocks * 256 * vec;
+  grid = dim3(static_cast<unsigned>(blocks));
+  ld.C = static_cast<unsigned int>(C);
+  ld.step_row = static_cast<unsigned int>(stride / C);
+  ld.step_col = static_cast<unsigned int>(stride % C);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int dalm_geglu_fwd(const void* gate, const void* up, void* act, int dtype, int64_t R, int64_t C, int64_t ld_gate,
+                              int64_t ld_up, int64_t ld_act, const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(R >= 0 && C >= 0, DALM_E_SHAPE, "R, C must be >= 0");
+  if (R == 0 || C == 0) return 0;
+  DALM_REQUIRE(gate && up && act, DALM_E_NULL, "null pointer argument");
+  DALM_REQUIRE(dtype == DALM_F32 || dtype == DALM_BF16, DALM_E_DTYPE, "dtype must be DALM_F32 or DALM_BF16");
+  DALM_REQUIRE(aligned16(gate, up, act), DALM_E_ALIGN, "gate / up / act must be 16-byte aligned");
+  dim3 grid;
+  int64_t n;
+  GegluLd ld = {ld_gate, ld_up, ld_act, 0, 0, 0u, 0u, 0u};
+  if (const int rc = geglu_plan(__func__, dtype, R, C, {ld_gate, ld_up, ld_act}, grid, n, ld)) return rc;
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((geglu_fwd_kernel<T>), grid, dim3(256), 0, as_stream(stream), static_cast<const T*>(gate),
+                       static_cast<const T*>(up), static_cast<T*>(act), n, ld, row_live);
+  });
+  return check_launch(__func__);
+}
+
+extern "C" int dalm_geglu_bwd(const void* d_act, const void* gate, const void* up, void* d_gate, void* d_up, int dtype, int64_t R,
+                              int64_t C, int64_t ld_dact, int64_t ld_gate, int64_t ld_up, int64_t ld_dgate, int64_t ld_dup,
+                              const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(R >= 0 && C >= 0, DALM_E_SHAPE, "R, C must be >= 0");
+  if (R == 0 || C == 0) return 0;
+  DALM_REQUIRE(d_act && gate && up && d_gate && d_up, DALM_E_NULL, "null pointer argument");
+  DALM_REQUIRE(dtype == DALM_F32 || dtype == DALM_BF16, DALM_E_DTYPE, "dtype must be DALM_F32 or DALM_BF16");
+  DALM_REQUIRE(aligned16(d_act, gate, up, d_gate, d_up), DALM_E_ALIGN, "all tensors must be 16-byte aligned");
+  dim3 grid;
+  int64_t n;
+  GegluLd ld = {ld_gate, ld_up, ld_dact, ld_dgate, ld_dup, 0u, 0u, 0u};
+  if (const int rc = geglu_plan(__func__, dtype, R, C, {ld_dact, ld_gate, ld_up, ld_dgate, ld_dup}, grid, n, ld)) return rc;
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((geglu_bwd_kernel<T>), grid, dim3(256), 0, as_stream(stream), static_cast<const T*>(d_act),
+                       static_cast<const T*>(gate), static_cast<const T*>(up), static_cast<T*>(d_gate), static_cast<T*>(d_up), n, ld,
+                       row_live);
+  });
+  return check_launch(__func__);
+}
+
+// dalm_rms_norm_*'s width rules; the weight has a dtype of its own and no rows is no work
+#define DALM_GEMMA_NORM_CHECKS                                                                                           \
+  DALM_REQUIRE(dtype == DALM_F32 || dtype == DALM_BF16, DALM_E_DTYPE, "dtype must be DALM_F32 or DALM_BF16");             \
+  DALM_REQUIRE(w_dtype == DALM_F32 || w_dtype == DALM_BF16, DALM_E_DTYPE, "w_dtype must be DALM_F32 or DALM_BF16");       \
+  const int vecn = dtype == DALM_F32 ? 4 : 8;                                                                            \
+  DALM_REQUIRE(R >= 0 && D > 0 && D % vecn == 0 && D <= 64ll * vecn * 16 && R <= 0x7ffffff0ll, DALM_E_SHAPE,              \
+               "need rows >= 0 and a width that is a multiple of 16 bytes, at most 8192 (bf16) / 4096 (f32) elements");   \
+  const int nch = static_cast<int>((D + 64 * vecn - 1) / (64 * vecn));                                                   \
+  const dim3 grid(static_cast<unsigned>((R + 3) / 4))
+
+extern "C" int dalm_gemma_norm_fwd(const void* x, const void* delta, const void* w, int dtype, int w_dtype, int64_t R, int64_t D,
+                                   float eps, void* h_out, void* y, float* rstd, const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(x && w && y && rstd, DALM_E_NULL, "null pointer argument");
+  DALM_REQUIRE((delta == nullptr) == (h_out == nullptr), DALM_E_NULL, "delta and h_out go together");
+  DALM_GEMMA_NORM_CHECKS;
+  DALM_REQUIRE(aligned16(x, w, y, delta, h_out), DALM_E_ALIGN, "tensors must be 16-byte aligned");
+  if (R == 0) return 0;
+  const int Ri = static_cast<int>(R), Di = static_cast<int>(D);
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_bool(delta != nullptr, [&](auto add) {
+      by_ceil<1, 2, 4, 8, 16>(nch, [&](auto n) {
+        hipLaunchKernelGGL((gemma_norm_fwd_kernel<T, n, add>), grid, dim3(256), 0, as_stream(stream), static_cast<const T*>(x),
+                           static_cast<const T*>(delta), w, w_dtype == DALM_F32, static_cast<T*>(h_out), static_cast<T*>(y), rstd,
+                           Ri, Di, eps, row_live);
+      });
+    });
+  });
+  return check_launch(__func__);
+}
+
+extern "C" int dalm_gemma_norm_bwd(const void* dy, const void* h, const void* w, const float* rstd, const void* dres, int dtype,
+                                   int w_dtype, int64_t R, int64_t D, void* dx, const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(dy && h && w && rstd && dx, DALM_E_NULL, "null pointer argument");
+  DALM_GEMMA_NORM_CHECKS;
+  DALM_REQUIRE(aligned16(dy, h, w, dx, dres), DALM_E_ALIGN, "tensors must be 16-byte aligned");
+  if (R == 0) return 0;
+  const int Ri = static_cast<int>(R), Di = static_cast<int>(D);
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_bool(dres != nullptr, [&](auto add) {
+      by_ceil<1, 2, 4, 8, 16>(nch, [&](auto n) {
+        hipLaunchKernelGGL((gemma_norm_bwd_kernel<T, n, add>), grid, dim3(256), 0, as_stream(stream), static_cast<const T*>(dy),
+                           static_cast<const T*>(h), w, w_dtype == DALM_F32, rstd, static_cast<const T*>(dres), static_cast<T*>(dx),
+                           Ri, Di, row_live);
+      });
+    });
   });
   return check_launch(__func__);
 }

@@ -152,6 +152,11 @@ SIGNATURES = {
                                        _vp, _vp, _vp, _vp, _vp, _vp]),
     "dalm_head_norm_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _vp, _vp, _vp, _vp]),
+    # Gemma: GeGLU and the (1 + w) RMSNorm, one entry point per direction (row liveness is an argument)
+    "dalm_geglu_fwd": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "dalm_geglu_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "dalm_gemma_norm_fwd": (_int, [_vp, _vp, _vp, _int, _int, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "dalm_gemma_norm_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _i64, _i64, _vp, _vp, _vp]),
     "dalm_bert_add_norm_fwd_live": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _f32, _f32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _vp]),
     "dalm_bert_add_norm_bwd_live": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),

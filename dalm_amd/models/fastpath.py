@@ -12,6 +12,7 @@ Every patch is a guard (`_guard`: a numeric probe, or for a forward that restate
 """
 from __future__ import annotations
 
+import copy
 import os
 import types
 
@@ -248,7 +249,7 @@ def use_swiglu_kernel(model: torch.nn.Module) -> int:
     return _install(model, ("LlamaMLP", "MistralMLP", "Qwen2MLP", "Qwen3MLP"), gated_silu, _mlp_matches, _swiglu_mlp_forward)
 
 
-def _mlp_matches(mod: torch.nn.Module) -> bool:
+def _mlp_matches(mod: torch.nn.Module, forward=_swiglu_mlp_forward, what: str = "down(silu(gate(x)) * up(x)) here") -> bool:
     """The class's own forward against the patched one on a small random input, once per class, dtype and device type (on a
     GPU the patched forward runs the HIP kernel: <= 1 ulp of the output dtype)."""
     w = getattr(mod.gate_proj, "weight", None)
@@ -257,9 +258,99 @@ def _mlp_matches(mod: torch.nn.Module) -> bool:
     def probe():
         x = torch.randn(2, 3, mod.gate_proj.in_features, generator=torch.Generator().manual_seed(0)).to(device=w.device, dtype=w.dtype)
         with torch.no_grad():
-            return _close(_swiglu_mlp_forward(mod, x), type(mod).forward(mod, x), 2.0)
+            return _close(forward(mod, x), type(mod).forward(mod, x), 2.0)
 
-    return _guard(("mlp", type(mod), *where), type(mod).__name__ + ".forward", "down(silu(gate(x)) * up(x)) here", probe)
+    return _guard(("mlp", type(mod), *where), type(mod).__name__ + ".forward", what, probe)
+
+
+# ---------------------------------------------------------------------------
+# Gemma: GeGLU MLP and the (1 + w) RMSNorm (the decoder layer itself is Llama's: `_llama_layer_forward` below)
+# ---------------------------------------------------------------------------
+def _geglu_mlp_forward(self, x):
+    from . import frozen_linear, tower_ops
+
+    gate, up = frozen_linear.pair_forward(x, self.gate_proj, self.up_proj)   # frozen: one node, the two dx GEMMs accumulate
+    if tower_ops.geglu_supported(gate, up):
+        return self.down_proj(tower_ops.geglu(gate, up))
+    return self.down_proj(self.act_fn(gate) * up)
+
+
+def _is_tanh_gelu(act) -> bool:
+    """torch's tanh-approximated GELU: nn.GELU(approximate="tanh"), or transformers' GELUTanh around
+    nn.functional.gelu(approximate="tanh") (ACT2FN["gelu_pytorch_tanh"]) - not its python spelling, which rounds elsewhere."""
+    if isinstance(act, torch.nn.GELU):
+        return getattr(act, "approximate", "none") == "tanh"
+    fn = getattr(act, "act", None)
+    return (type(act).__name__ in ("GELUTanh", "PytorchGELUTanh") and getattr(fn, "func", None) is torch.nn.functional.gelu
+            and getattr(fn, "keywords", None) == {"approximate": "tanh"})
+
+
+def use_geglu_kernel(model: torch.nn.Module) -> int:
+    """Patch the Gemma-family `*MLP` modules (GemmaMLP, Gemma2MLP, Gemma3MLP: the same forward text) that are
+    down(act(gate(x)) * up(x)) with act = tanh-GELU to evaluate gelu_tanh(gate) * up through `dalm_geglu_{fwd,bwd}`: 2 eager
+    launches forward and ~5 backward become 1 + 1 and the [tokens, intermediate] activation is recomputed instead of saved.
+    Same rounding points as the eager chain.  DALM_SWIGLU_KERNEL=0 disables; returns how many modules were patched."""
+    if _off("DALM_SWIGLU_KERNEL"):
+        return 0
+
+    def gated_tanh_gelu(mod) -> bool:
+        return all(hasattr(mod, a) for a in ("gate_proj", "up_proj", "down_proj")) and _is_tanh_gelu(getattr(mod, "act_fn", None))
+
+    return _install(model, ("GemmaMLP", "Gemma2MLP", "Gemma3MLP"), gated_tanh_gelu,
+                    lambda mod: _mlp_matches(mod, _geglu_mlp_forward, "down(gelu_tanh(gate(x)) * up(x)) here"), _geglu_mlp_forward)
+
+
+def _gemma_norm_formula(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
+    xf = x.float()
+    return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * (1.0 + w.float())).type_as(x)
+
+
+def _gemma_eps(mod) -> float:
+    return float(getattr(mod, "eps", getattr(mod, "variance_epsilon", None)))
+
+
+def _gemma_norm_forward(self, x: torch.Tensor) -> torch.Tensor:
+    from . import tower_ops
+
+    if tower_ops.gemma_rms_norm_supported(x, self.weight):
+        return tower_ops.gemma_add_rms_norm(x, None, self.weight, _gemma_eps(self))[1]
+    return _gemma_norm_formula(x, self.weight, _gemma_eps(self))
+
+
+def _gemma_norm_matches(mod: torch.nn.Module) -> bool:
+    """The module's OWN forward against the patched one (the formula above; on a GPU the HIP kernel) on a small random tensor, once
+    per class, dtype and device type: what tells GemmaRMSNorm from a `*RMSNorm` of the same name with another formula.  On a GPU
+    an f32 weight is probed under f32 AND bf16 activations: under autocast the kernel sees the latter.  Leaves `mod` as it is."""
+    w = mod.weight
+
+    def probe():
+        g = torch.Generator().manual_seed(0)
+        x = torch.randn(4, 3, w.shape[0], generator=g)
+        # at the zero initialisation (1 + w) is 1 and tells nothing: the probe runs on a twin of the module with a weight of its own
+        twin = copy.copy(mod)
+        twin._parameters = dict(mod._parameters)
+        twin.weight = torch.nn.Parameter((0.5 * torch.randn(w.shape, generator=g)).to(device=w.device, dtype=w.dtype), requires_grad=False)
+        x_dtypes = {w.dtype, torch.bfloat16} if w.is_cuda else {w.dtype}
+        with torch.no_grad():
+            return all(_close(_gemma_norm_forward(twin, xd), type(mod).forward(twin, xd), 2.0)
+                       for xd in (x.to(device=w.device, dtype=dt) for dt in sorted(x_dtypes, key=str)))
+
+    return _guard(("gemma-norm", type(mod), w.dtype, w.device.type), type(mod).__name__ + ".forward",
+                  "(x.float() * rsqrt(mean(x.float()^2) + eps) * (1 + w.float())).type_as(x) here", probe)
+
+
+def _gemma_rms_norm(mod) -> bool:
+    w = getattr(mod, "weight", None)
+    return w is not None and w.dim() == 1 and getattr(mod, "eps", getattr(mod, "variance_epsilon", None)) is not None
+
+
+def use_gemma_rms_norm(model: torch.nn.Module) -> int:
+    """Patch GemmaRMSNorm modules - and Gemma2RMSNorm / Gemma3RMSNorm where their own forward passes the same value probe - to run
+    on `dalm_gemma_norm_{fwd,bwd}`: one launch each way instead of transformers' f32 chain of ~8.  DALM_NORM_KERNEL=0 disables;
+    returns how many modules were patched."""
+    if _off("DALM_NORM_KERNEL"):
+        return 0
+    return _install(model, ("GemmaRMSNorm", "Gemma2RMSNorm", "Gemma3RMSNorm"), _gemma_rms_norm, _gemma_norm_matches, _gemma_norm_forward)
 
 
 # ---------------------------------------------------------------------------
@@ -752,25 +843,42 @@ def _llama_layer_forward(self, hidden_states, attention_mask=None, position_ids=
     LlamaRMSNorm up to the f32 summation order of mean(x^2)."""
     from . import tower_ops
 
+    return _two_norm_layer_forward(self, tower_ops.rms_norm_supported, tower_ops.add_rms_norm, hidden_states, attention_mask,
+                                   position_ids, past_key_values, use_cache, position_embeddings, kwargs)
+
+
+def _gemma_layer_forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_values=None, use_cache=False,
+                         position_embeddings=None, **kwargs):
+    """transformers' GemmaDecoderLayer.forward - LlamaDecoderLayer.forward, statement for statement (the "gemma-layer" guard) - with
+    its two (residual add, GemmaRMSNorm) pairs on `dalm_gemma_norm_{fwd,bwd}`, placed as `_llama_layer_forward` places Llama's."""
+    from . import tower_ops
+
+    return _two_norm_layer_forward(self, tower_ops.gemma_rms_norm_supported, tower_ops.gemma_add_rms_norm, hidden_states,
+                                   attention_mask, position_ids, past_key_values, use_cache, position_embeddings, kwargs)
+
+
+def _two_norm_layer_forward(self, supported, add_norm, hidden_states, attention_mask, position_ids, past_key_values, use_cache,
+                            position_embeddings, kwargs):
+    """The body the two forwards above share; `supported(x, w)` / `add_norm(x, delta, w, eps)` are the family's norm."""
     n1, n2 = self.input_layernorm, self.post_attention_layernorm
-    if not (tower_ops.rms_norm_supported(hidden_states, n1.weight) and tower_ops.rms_norm_supported(hidden_states, n2.weight)):
+    if not (supported(hidden_states, n1.weight) and supported(hidden_states, n2.weight)):
         return self._dalm_orig_forward(hidden_states, attention_mask=attention_mask, position_ids=position_ids,
                                        past_key_values=past_key_values, use_cache=use_cache,
                                        position_embeddings=position_embeddings, **kwargs)
-    residual, normed = tower_ops.add_rms_norm(hidden_states, None, n1.weight, _norm_eps(n1))
+    residual, normed = add_norm(hidden_states, None, n1.weight, _norm_eps(n1))
     attn_out, _ = self.self_attn(hidden_states=normed, attention_mask=attention_mask, position_ids=position_ids,
                                  past_key_values=past_key_values, use_cache=use_cache,
                                  position_embeddings=position_embeddings, **kwargs)
-    residual, normed = tower_ops.add_rms_norm(residual, attn_out, n2.weight, _norm_eps(n2))
+    residual, normed = add_norm(residual, attn_out, n2.weight, _norm_eps(n2))
     return residual + self.mlp(normed)
 
 
 
-
 def use_fused_residual_norm(model: torch.nn.Module) -> int:
-    """Patch LlamaDecoderLayer / Qwen3DecoderLayer modules whose forward has the signature this file was written against
-    (transformers 5.x; Qwen3's is also compared statement for statement); DALM_NORM_KERNEL=0 disables.  Returns how many layers
-    were patched."""
+    """Patch LlamaDecoderLayer / Qwen3DecoderLayer / GemmaDecoderLayer modules whose forward has the signature this file was
+    written against (transformers 5.x; Qwen3's and Gemma's are also compared statement for statement); DALM_NORM_KERNEL=0
+    disables.  A Gemma layer's two norms must be GemmaRMSNorm by name and by value (`_gemma_norm_matches`); Gemma2 / Gemma3 layers
+    (four norms) are other code and are not taken.  Returns how many layers were patched."""
     if _off("DALM_NORM_KERNEL"):
         return 0
 
@@ -778,12 +886,17 @@ def use_fused_residual_norm(model: torch.nn.Module) -> int:
         return (nm is not None and type(nm).__name__.endswith("RMSNorm") and getattr(nm, "weight", None) is not None
                 and nm.weight.dim() == 1 and "Gemma" not in type(nm).__name__)
 
-    def two_norms(mod) -> bool:
-        return (plain_rms_norm(getattr(mod, "input_layernorm", None)) and plain_rms_norm(getattr(mod, "post_attention_layernorm", None))
-                and all(hasattr(mod, a) for a in ("self_attn", "mlp")))
+    def gemma_rms_norm(nm) -> bool:
+        return nm is not None and type(nm).__name__ == "GemmaRMSNorm" and _gemma_rms_norm(nm) and _gemma_norm_matches(nm)
 
-    return sum(_install(model, (name,), two_norms, guard, _llama_layer_forward, keep="_dalm_orig_forward")
-               for name, guard in (("LlamaDecoderLayer", "llama-layer"), ("Qwen3DecoderLayer", "qwen3-layer")))
+    def two_norms(is_norm):
+        return lambda mod: (is_norm(getattr(mod, "input_layernorm", None)) and is_norm(getattr(mod, "post_attention_layernorm", None))
+                            and all(hasattr(mod, a) for a in ("self_attn", "mlp")))
+
+    return sum(_install(model, (name,), two_norms(is_norm), guard, forward, keep="_dalm_orig_forward")
+               for name, guard, is_norm, forward in (("LlamaDecoderLayer", "llama-layer", plain_rms_norm, _llama_layer_forward),
+                                                     ("Qwen3DecoderLayer", "qwen3-layer", plain_rms_norm, _llama_layer_forward),
+                                                     ("GemmaDecoderLayer", "gemma-layer", gemma_rms_norm, _gemma_layer_forward)))
 
 
 _SOURCE_GUARDS["llama-layer"] = (_restates(_LLAMA_LAYER_PARAMS), _RESTATED)
@@ -798,3 +911,4 @@ _QWEN3_LAYER_BODY = ["residual = hidden_states", "hidden_states = self.input_lay
 _SOURCE_GUARDS["qwen3-layer"] = (
     lambda params, src: (params == _LLAMA_LAYER_PARAMS and _body(src)[-len(_QWEN3_LAYER_BODY):] == _QWEN3_LAYER_BODY
                          and _body(src)[-len(_QWEN3_LAYER_BODY) - 1].startswith(")")), _RESTATED)
+_SOURCE_GUARDS["gemma-layer"] = _SOURCE_GUARDS["qwen3-layer"]       # GemmaDecoderLayer.forward: the same whole body, the same check

@@ -16,8 +16,8 @@ from ..utils import eos_mask
 from . import lora
 from .attention import use_hip_attention_backward
 from .fastpath import (use_bert_layer_kernels, use_capturable_falcon_heads, use_falcon_attention_kernels, use_falcon_layer_kernels,
-                       use_fused_residual_norm, use_llama_attention_node, use_native_rms_norm, use_qwen3_attention_node, use_roberta_embeddings,
-                       use_roll_rope, use_swiglu_kernel)
+                       use_fused_residual_norm, use_geglu_kernel, use_gemma_rms_norm, use_llama_attention_node, use_native_rms_norm,
+                       use_qwen3_attention_node, use_roberta_embeddings, use_roll_rope, use_swiglu_kernel)
 
 
 class Mode(Enum):
@@ -93,16 +93,16 @@ def decoder_only(lm, T: Optional[int] = None) -> bool:
 # The installers a tower gets, in the order they run (each has its own guards and leaves other models alone).  The order matters:
 # `use_capturable_falcon_heads` reads "sdpa" before `use_hip_attention_backward` can change it, and the attention-node installers
 # need "dalm_sdpa" to be set already.
-_ROW_WISE_PATHS = (use_native_rms_norm, use_roll_rope, use_swiglu_kernel, use_fused_residual_norm)
+_ROW_WISE_PATHS = (use_native_rms_norm, use_roll_rope, use_swiglu_kernel, use_geglu_kernel, use_gemma_rms_norm, use_fused_residual_norm)
 _RETRIEVER_PATHS = _ROW_WISE_PATHS + (use_hip_attention_backward,)
 _GENERATOR_PATHS = _ROW_WISE_PATHS + (use_capturable_falcon_heads, use_falcon_layer_kernels, use_falcon_attention_kernels,
                                       use_hip_attention_backward, use_llama_attention_node, use_qwen3_attention_node)
 
 
 def use_causal_retriever_fast_paths(lm) -> dict:
-    """The generator's row-wise layer nodes on a causal-LM retriever: native RMSNorm, roll-rope, SwiGLU, fused residual + norm,
-    "dalm_sdpa".  Roll-rope patches Llama's modeling code only and fused residual + norm Llama's and Qwen3's: on mistral /
-    qwen2 they do nothing.  The rotary + attention nodes (`use_llama_attention_node`, `use_qwen3_attention_node`) are not
+    """The generator's row-wise layer nodes on a causal-LM retriever: native RMSNorm, roll-rope, SwiGLU, Gemma's GeGLU and (1 + w)
+    RMSNorm, fused residual + norm, "dalm_sdpa".  Roll-rope patches Llama's modeling code only and fused residual + norm Llama's,
+    Qwen3's and Gemma's: on mistral / qwen2 they do nothing.  The rotary + attention nodes (`use_llama_attention_node`, `use_qwen3_attention_node`) are not
     applied to retrievers: rotary and attention - and a Qwen3 layer's q_norm / k_norm - run as separate nodes there: DESIGN.md
     section 5.3 says why.  Returns what each installer returned, by its name."""
     return {use.__name__: use(lm) for use in _RETRIEVER_PATHS}

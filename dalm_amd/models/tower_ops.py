@@ -6,6 +6,9 @@ transformers evaluates both as chains of eager elementwise ops (modeling_llama.p
 dalm/models/rag_e2e_base_model.py:104-106).  The kernels round where those chains round, so forward values and gradients
 are the eager chain's (tests/test_tower_ops_gpu.py asserts equality, not closeness).
 
+Also here: RMSNorm with the residual add, Qwen3's head norm + rotary, Gemma's GeGLU and (1 + w) RMSNorm (`dalm_geglu_*`,
+`dalm_gemma_norm_*`: modeling_gemma.py `GemmaMLP.forward`, `GemmaRMSNorm.forward`), and Falcon's layer ops.
+
 GPU tensors only: the callers in `fastpath.py` keep transformers' own code for CPU tensors.
 """
 from __future__ import annotations
@@ -232,6 +235,123 @@ def add_rms_norm(x, delta, w, eps, live=None):
     delta = None: (x itself, rmsnorm(x) * w).  live: uint8 row liveness; None: that of the tower call in progress
     (dalm_amd/live_rows.py), if any."""
     return _AddRmsNorm.apply(x, delta, w, eps, live)
+
+
+# ---------------------------------------------------------------------------
+# Gemma: GeGLU (dalm_geglu_{fwd,bwd}) and the (1 + w) RMSNorm with the residual add in front of it (dalm_gemma_norm_{fwd,bwd})
+# ---------------------------------------------------------------------------
+class _GeGLU(torch.autograd.Function):
+    """gelu_tanh(gate) * up, `_SwiGLU`'s shape: gate / up as the halves of one [R, 2 C] buffer are read in place, nothing but gate and
+    up is saved, d_gate and d_up leave as two contiguous tensors (the reason `_SwiGLU.backward` gives)."""
+
+    @staticmethod
+    def forward(ctx, gate, up, live=None):
+        hip.require_gpu(gate, up)
+        halves = _halves_of_one(gate, up)
+        if not halves:
+            gate, up = gate.contiguous(), up.contiguous()
+        C = gate.shape[-1]
+        R = gate.numel() // C if C else 0
+        if live is None and gate.dim() >= 2:
+            live = live_rows.current(R, gate.device)
+        if live is not None and live.numel() != R:
+            live = None
+        ctx.ld = 2 * C if halves else C
+        act = torch.empty(gate.shape, dtype=gate.dtype, device=gate.device)
+        hip.call("dalm_geglu_fwd", hip.ptr(gate), hip.ptr(up), hip.ptr(act), hip.dtype_code(gate), R, C, ctx.ld, ctx.ld, C, hip.ptr(live),
+                 hip.stream())
+        ctx.save_for_backward(gate, up, *([live] if live is not None else []))    # the backward runs after the tower call's context
+        return act
+
+    @staticmethod
+    def backward(ctx, d_act):
+        gate, up, *keep = ctx.saved_tensors
+        d_act = d_act.contiguous()
+        C = gate.shape[-1]
+        R = gate.numel() // C if C else 0
+        dg = torch.empty(gate.shape, dtype=gate.dtype, device=gate.device)
+        du = torch.empty(gate.shape, dtype=gate.dtype, device=gate.device)
+        hip.call("dalm_geglu_bwd", hip.ptr(d_act), hip.ptr(gate), hip.ptr(up), hip.ptr(dg), hip.ptr(du), hip.dtype_code(gate), R, C, C,
+                 ctx.ld, ctx.ld, C, C, hip.ptr(keep[0] if keep else None), hip.stream())
+        return dg, du, None
+
+
+def geglu_supported(gate, up) -> bool:
+    return (gate.is_cuda and gate.dtype in (torch.float32, torch.bfloat16) and up.dtype == gate.dtype and up.shape == gate.shape
+            and gate.dim() >= 1 and gate.shape[-1] % (16 // gate.element_size()) == 0 and gate.numel() < 2 ** 32
+            and gate.data_ptr() % 16 == 0 and up.data_ptr() % 16 == 0)     # a view at an odd storage offset: the eager chain
+
+
+def geglu(gate, up, live=None):
+    """gelu_tanh(gate) * up (GemmaMLP's activation).  live: uint8 row liveness over the leading dimensions; None: that of the tower
+    call in progress (dalm_amd/live_rows.py), if any."""
+    return _GeGLU.apply(gate, up, live)
+
+
+def gemma_rms_norm_supported(x: torch.Tensor, w: torch.Tensor) -> bool:
+    """What `dalm_gemma_norm_*` take: `rms_norm_supported`'s widths; the weight f32 or bf16 under either activation dtype (GemmaRMSNorm
+    computes in f32 and casts once, to the activation's dtype, whatever the weight's is)."""
+    D = x.shape[-1]
+    vec = 4 if x.dtype == torch.float32 else 8
+    return (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and w.is_cuda and w.dim() == 1 and w.shape[0] == D
+            and w.dtype in (torch.float32, torch.bfloat16) and w.is_contiguous() and w.data_ptr() % 16 == 0
+            and D % vec == 0 and D <= 64 * vec * 16)
+
+
+def _gemma_weight_grad(dy2, h2, rstd, live=None):
+    # sum over the rows of f32(dy) * xh; xh stays f32 (the eager chain multiplies with the weight before its one rounding)
+    prod = dy2.float() * (h2.float() * rstd.unsqueeze(1))
+    if live is not None:                           # dead rows: dy and h are whatever their producers left
+        prod = prod.masked_fill((live == 0).unsqueeze(1), 0.0)
+    return prod.sum(0)
+
+
+class _GemmaAddRmsNorm(torch.autograd.Function):
+    """`_AddRmsNorm` with GemmaRMSNorm's formula: (h, y) = (x + delta, (f32(h) * rstd * (1 + f32(w))).to(x.dtype)); with delta None h
+    IS x and only the backward is fused (the residual-path gradient is added inside the norm's backward kernel)."""
+
+    @staticmethod
+    def forward(ctx, x, delta, w, eps, live=None):
+        D = x.shape[-1]
+        x2 = _as_rows(x, D, x.dtype)
+        d2 = _as_rows(delta, D, x.dtype) if delta is not None else None
+        R = x2.shape[0]
+        if live is None:
+            live = live_rows.current(R, x2.device)
+        w = w.detach()
+        y2 = torch.empty_like(x2)
+        h2 = torch.empty_like(x2) if d2 is not None else None
+        rstd = torch.empty(R, device=x2.device, dtype=torch.float32)
+        hip.call("dalm_gemma_norm_fwd", hip.ptr(x2), hip.ptr(d2), hip.ptr(w), hip.dtype_code(x2), hip.dtype_code(w), R, D, float(eps),
+                 hip.ptr(h2), hip.ptr(y2), hip.ptr(rstd), hip.ptr(live), hip.stream())
+        # (the liveness vector is kept: the backward runs after the tower call's context, on autograd's thread)
+        ctx.save_for_backward(h2 if h2 is not None else x2, w, rstd, *([live] if live is not None else []))
+        ctx.shape, ctx.has_delta = x.shape, delta is not None
+        ctx.set_materialize_grads(False)           # no residual-path gradient: the backward kernel reads none, not a tensor of zeros
+        return (h2.view(x.shape) if h2 is not None else x), y2.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dh, dy):
+        if dy is None:
+            return dh, (dh if ctx.has_delta else None), None, None, None
+        h2, w, rstd, *keep = ctx.saved_tensors
+        live = keep[0] if keep else None
+        R, D = h2.shape
+        dy2 = _as_rows(dy, D, h2.dtype)
+        dres2 = _as_rows(dh, D, h2.dtype) if dh is not None else None
+        dx = torch.empty_like(h2)
+        hip.call("dalm_gemma_norm_bwd", hip.ptr(dy2), hip.ptr(h2), hip.ptr(w), hip.ptr(rstd), hip.ptr(dres2), hip.dtype_code(h2),
+                 hip.dtype_code(w), R, D, hip.ptr(dx), hip.ptr(live), hip.stream())
+        d = dx.view(ctx.shape)
+        dw = _gemma_weight_grad(dy2, h2, rstd, live).to(w.dtype) if ctx.needs_input_grad[2] else None
+        return d, (d if ctx.has_delta else None), dw, None, None
+
+
+def gemma_add_rms_norm(x, delta, w, eps, live=None):
+    """x + delta and its GemmaRMSNorm in one launch (one more in the backward, which also folds in the residual-path gradient).
+    delta = None: (x itself, the norm of x).  live: uint8 row liveness; None: that of the tower call in progress
+    (dalm_amd/live_rows.py), if any."""
+    return _GemmaAddRmsNorm.apply(x, delta, w, eps, live)
 
 
 # ---------------------------------------------------------------------------

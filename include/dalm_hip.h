@@ -541,6 +541,35 @@ int dalm_head_norm_bwd(const void* gq, const void* gk, const void* q, const void
                        const int64_t* gq_strides, const int64_t* gk_strides, const int64_t* q_strides, const int64_t* k_strides,
                        const int64_t* dq_strides, const int64_t* dk_strides, void* dq, void* dk, const uint8_t* row_live,
                        dalm_stream_t stream);
+/* Gemma (modeling_gemma.py; `model_type` "gemma"): the decoder layer is Llama's, two row-wise formulas are not.
+ *   GemmaMLP:      down(gelu_tanh(gate(x)) * up(x))                  (2 eager launches + ~5 backward, one saved activation)
+ *   GemmaRMSNorm:  (x.float() * rsqrt(mean(x.float()^2) + eps) * (1.0 + w.float())).type_as(x)      (~8 eager launches)
+ * One entry point per direction; row_live [R] bytes or NULL (Row liveness, above: nothing of a dead row is loaded, freshly written
+ * outputs hold zeros there, live rows receive the same bits as without the vector).
+ *   dalm_geglu_fwd / dalm_geglu_bwd: [R, C] views with row strides in elements (contiguous: ld = C); gate and up may be the two
+ *        halves of ONE [R, 2 C] GEMM output, read in place.  dtype DALM_F32 or DALM_BF16.  Rounding points of the eager chain and
+ *        its autograd:  a = round(gelu_tanh(gate)) (f32 arithmetic, torch's expression, tanhf);  act = round(a up);
+ *        d_up = round(d_act a);  d_a = round(d_act up);  d_gate = round(torch's tanh-GELU backward of d_a at gate).  The forward
+ *        saves nothing: the backward recomputes a.  C and the strides multiples of 16 bytes, strides >= C, 16-byte aligned
+ *        pointers (DALM_E_ALIGN); R C < 2^32 (DALM_E_SHAPE).  R == 0 or C == 0: nothing to do, 0.  Streaming kernels on a grid
+ *        of at most 256 x 8 workgroups: forward 3 R C elements of traffic, backward 5 R C.
+ *   dalm_gemma_norm_fwd / dalm_gemma_norm_bwd: one wave per row, [R, D] row-major, the D rules of dalm_rms_norm_* (a multiple of
+ *        16 bytes of `dtype`, at most 8192 (bf16) / 4096 (f32): DALM_E_SHAPE).  `w_dtype` is the weight's own dtype: f32 or bf16
+ *        under either activation dtype (the formula casts once, at the end).
+ *        fwd: delta != NULL: h_out = round(x + delta) and the norm is taken of h_out; delta == NULL (then h_out == NULL too): of
+ *             x.  rstd [R] f32 = rsqrt(mean(h^2) + eps);  y = round(f32(h) rstd (1 + f32(w))) - no rounding in between.
+ *        bwd: g = f32(dy) (1 + f32(w));  xh = f32(h) rstd;  dx = round(rstd (g - xh mean(g xh)) [+ dres, when dres != NULL]).
+ *        The weight gradient is not produced.  R == 0: nothing to do, 0.
+ * The checks run before anything is enqueued. */
+int dalm_geglu_fwd(const void* gate, const void* up, void* act, int dtype, int64_t R, int64_t C, int64_t ld_gate, int64_t ld_up,
+                   int64_t ld_act, const uint8_t* row_live, dalm_stream_t stream);
+int dalm_geglu_bwd(const void* d_act, const void* gate, const void* up, void* d_gate, void* d_up, int dtype, int64_t R, int64_t C,
+                   int64_t ld_dact, int64_t ld_gate, int64_t ld_up, int64_t ld_dgate, int64_t ld_dup, const uint8_t* row_live,
+                   dalm_stream_t stream);
+int dalm_gemma_norm_fwd(const void* x, const void* delta, const void* w, int dtype, int w_dtype, int64_t R, int64_t D, float eps,
+                        void* h_out, void* y, float* rstd, const uint8_t* row_live, dalm_stream_t stream);
+int dalm_gemma_norm_bwd(const void* dy, const void* h, const void* w, const float* rstd, const void* dres, int dtype, int w_dtype,
+                        int64_t R, int64_t D, void* dx, const uint8_t* row_live, dalm_stream_t stream);
 
 /* Elementwise chains of a Falcon-7B decoder layer (transformers modeling_falcon.py FalconDecoderLayer.forward /
  * FalconMLP.forward / dropout_add, reached by the reference through self.generator_model(...),

@@ -393,6 +393,115 @@ def bench_embed_norm(B, T, D, p, rounds=3):
     return out
 
 
+def _alternating(fns, nbytes, rounds):
+    """Median over `rounds` alternations (every round visits every function) of a 20-call graph's per-call time, with the lowest and
+    highest round; GB/s and the HBM fraction from the algorithmic bytes of each function."""
+    seen = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, fn in fns.items():
+            seen[name].append(time_graph(fn)[0])
+    out = {}
+    for name, ts in seen.items():
+        ts.sort()
+        med = ts[len(ts) // 2]
+        out[name] = {"s": med, "lo": ts[0], "hi": ts[-1], "GBps": nbytes[name] / med / 1e9, "frac": nbytes[name] / med / HBM_PEAK}
+    return out
+
+
+def bench_geglu(R, C, rounds=3):
+    """GemmaMLP's activation: `dalm_geglu_fwd` / `dalm_geglu_bwd` on the gate | up halves of one [R, 2 C] bf16 buffer (the routed
+    form: `frozen_linear.pair_forward`), and beside them - alternating, in the same process - the eager chain they replace on dense
+    tensors: gelu(approximate="tanh") and a multiply, and autograd's backward of the two.  Algorithmic bytes: forward 3 R C
+    elements, backward 5 R C (the eager chain moves more: it writes and re-reads the activation)."""
+    import torch.nn.functional as F
+
+    from dalm_amd import hip
+    from dalm_amd.models import tower_ops
+
+    dev = torch.device("cuda:0")
+    buf = torch.randn(R, 2 * C, device=dev, dtype=torch.bfloat16)
+    gate, up = buf[:, :C], buf[:, C:]
+    assert tower_ops.geglu_supported(gate, up) and tower_ops._halves_of_one(gate, up)
+    d_act = torch.randn(R, C, device=dev, dtype=torch.bfloat16)
+    dg, du = torch.empty_like(d_act), torch.empty_like(d_act)
+    gd, ud = gate.contiguous().requires_grad_(True), up.contiguous().requires_grad_(True)          # dense leaves for autograd
+
+    def kernel_bwd():
+        hip.call("dalm_geglu_bwd", hip.ptr(d_act), hip.ptr(gate), hip.ptr(up), hip.ptr(dg), hip.ptr(du), hip.dtype_code(gate), R, C, C,
+                 2 * C, 2 * C, C, C, None, hip.stream())
+
+    def eager_fwd(a, b):
+        return F.gelu(a, approximate="tanh") * b
+
+    def eager_both():
+        return torch.autograd.grad(eager_fwd(gd, ud), (gd, ud), d_act)
+
+    fns = {"kernel fwd (1 launch)": lambda: tower_ops.geglu(gate, up), "kernel bwd (1 launch)": kernel_bwd,
+           "eager fwd (gelu, mul)": lambda: eager_fwd(gd.detach(), ud.detach()), "eager fwd + autograd bwd": eager_both}
+    n = R * C * 2
+    out = _alternating(fns, {"kernel fwd (1 launch)": 3 * n, "kernel bwd (1 launch)": 5 * n, "eager fwd (gelu, mul)": 3 * n,
+                             "eager fwd + autograd bwd": 8 * n}, rounds)
+    k, e = out["kernel fwd (1 launch)"]["s"] + out["kernel bwd (1 launch)"]["s"], out["eager fwd + autograd bwd"]["s"]
+    out["kernel fwd + bwd against eager"] = {"kernel_s": k, "eager_s": e, "eager_over_kernel": e / k}
+    out["kernel fwd against eager fwd"] = {"eager_over_kernel": out["eager fwd (gelu, mul)"]["s"] / out["kernel fwd (1 launch)"]["s"]}
+    return out
+
+
+def bench_gemma_norm(R, D, rounds=3):
+    """GemmaRMSNorm with the residual add in front of it: `dalm_gemma_norm_fwd` (x + delta and the norm) / `dalm_gemma_norm_bwd`
+    (with the residual-path gradient) on [R, D] bf16 rows with a bf16 weight, and beside them - alternating, in the same process -
+    the eager add + transformers' GemmaRMSNorm.forward (an f32 chain of ~8 launches) and autograd's backward of it.  Algorithmic
+    bytes: forward 4 R D elements (+ rstd), backward 4 R D (+ rstd)."""
+    from transformers.models.gemma.modeling_gemma import GemmaRMSNorm
+
+    from dalm_amd import hip
+    from dalm_amd.models import tower_ops
+
+    dev = torch.device("cuda:0")
+    x = torch.randn(R, D, device=dev, dtype=torch.bfloat16)
+    delta = torch.randn(R, D, device=dev, dtype=torch.bfloat16)
+    gy, gres = torch.randn_like(x), torch.randn_like(x)
+    norm = GemmaRMSNorm(D, eps=1e-6).to(dev).to(torch.bfloat16).requires_grad_(False)
+    with torch.no_grad():
+        norm.weight.copy_(0.1 * torch.randn(D, device=dev))
+    w = norm.weight
+    assert tower_ops.gemma_rms_norm_supported(x, w)
+    with torch.no_grad():
+        h, _ = tower_ops.gemma_add_rms_norm(x, delta, w, 1e-6)
+    rstd = torch.rsqrt(h.float().pow(2).mean(-1) + 1e-6)
+    dx = torch.empty_like(x)
+    xd, dd = x.clone().requires_grad_(True), delta.clone().requires_grad_(True)
+
+    def kernel_fwd():
+        with torch.no_grad():
+            return tower_ops.gemma_add_rms_norm(x, delta, w, 1e-6)
+
+    def kernel_bwd():
+        hip.call("dalm_gemma_norm_bwd", hip.ptr(gy), hip.ptr(h), hip.ptr(w), hip.ptr(rstd), hip.ptr(gres), hip.dtype_code(h),
+                 hip.dtype_code(w), R, D, hip.ptr(dx), None, hip.stream())
+
+    def eager_fwd(a, b):
+        hh = a + b
+        return hh, norm(hh)
+
+    def eager_both():
+        return torch.autograd.grad(eager_fwd(xd, dd), (xd, dd), (gres, gy))
+
+    def eager_fwd_only():
+        with torch.no_grad():
+            return eager_fwd(x, delta)
+
+    fns = {"kernel fwd (1 launch)": kernel_fwd, "kernel bwd (1 launch)": kernel_bwd, "eager fwd (add + f32 chain)": eager_fwd_only,
+           "eager fwd + autograd bwd": eager_both}
+    n = R * D * 2
+    out = _alternating(fns, {"kernel fwd (1 launch)": 4 * n + 4 * R, "kernel bwd (1 launch)": 4 * n + 4 * R,
+                             "eager fwd (add + f32 chain)": 4 * n, "eager fwd + autograd bwd": 8 * n}, rounds)
+    k, e = out["kernel fwd (1 launch)"]["s"] + out["kernel bwd (1 launch)"]["s"], out["eager fwd + autograd bwd"]["s"]
+    out["kernel fwd + bwd against eager"] = {"kernel_s": k, "eager_s": e, "eager_over_kernel": e / k}
+    out["kernel fwd against eager fwd"] = {"eager_over_kernel": out["eager fwd (add + f32 chain)"]["s"] / out["kernel fwd (1 launch)"]["s"]}
+    return out
+
+
 def print_results(res) -> None:
     for k, v in res.items():
         print(k)
@@ -464,6 +573,13 @@ def main():
         for B, T in ((150, 128), (150, 50)):
             for p in (0.0, 0.1):
                 res[f"embed_norm XLM-R-large retriever-only rows {B}x{T} D1024 p={p}"] = bench_embed_norm(B, T, 1024, p)
+    # the headline batch's rows (18 x 256) at Gemma-7B's widths: intermediate 24576, hidden 3072
+    if args.only in ("", "geglu"):
+        res["geglu Gemma-7B rows 4608 x 24576 bf16 (halves of one [R, 2 C] buffer)"] = bench_geglu(4608, 24576)
+        res["geglu rows 4608 x 3072 bf16 (halves of one [R, 2 C] buffer)"] = bench_geglu(4608, 3072)
+    if args.only in ("", "gemma_norm"):
+        # (24576 is the MLP's width, not a norm's: the norm kernels take rows of at most 8192 elements)
+        res["gemma_norm Gemma-7B rows 4608 x 3072 bf16 (add + norm)"] = bench_gemma_norm(4608, 3072)
     Path("gpurun_out").mkdir(exist_ok=True)
     Path("gpurun_out/kernel_bench.json").write_text(json.dumps(res, indent=1))
     print_results(res)
