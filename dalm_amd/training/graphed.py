@@ -11,6 +11,7 @@ later round).
 from __future__ import annotations
 
 import contextlib
+import gc
 import warnings
 from typing import Callable, Dict, Hashable, Optional, Tuple
 
@@ -152,6 +153,26 @@ class GraphSets:
         return hit
 
 
+@contextlib.contextmanager
+def no_collection_while_capturing():
+    """Dead reference cycles are collected BEFORE a capture begins, and the cyclic collector stays off until it has ended.
+
+    torch.cuda.make_graphed_callables ties every graphed module into a cycle (module -> its replaced `forward` closure -> the
+    module), so the hipGraphs of a step that has been dropped are freed by the cyclic collector alone, whenever it next runs.
+    torch.cuda.graph used to collect on entry; by now it does so only under torch.compiler.config.force_cudagraph_gc.  A
+    collection that fires INSIDE a capture destroys those graphs and releases their memory pools on the capturing thread, which
+    the thread-local capture mode does not permit: the process aborts (seen in tests/test_live_rows_gpu.py, which builds a second
+    step with tower graphs right after dropping the first; whether it happens depends on the allocation count so far)."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
+
+
 class GraphedStep:
     def __init__(self, step, warmup: int = 3, eager_steps: int = 0, max_graphs: int = 8):
         """warmup: hidden extra steps run on a side stream right before the capture (benchmarks);
@@ -223,7 +244,7 @@ class GraphedStep:
             self._capture_stream = torch.cuda.Stream()
         cs = self._capture_stream
         cs.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(cs):
+        with no_collection_while_capturing(), torch.cuda.stream(cs):
             g.capture_begin(pool=self.pool, capture_error_mode="thread_local")   # other threads (a process group's watchdog) may query events
             try:
                 static_loss = self.step(static)
@@ -334,7 +355,8 @@ def thread_local_capture():
 
     torch.cuda.graph.__init__ = init
     try:
-        yield
+        with no_collection_while_capturing():
+            yield
     finally:
         torch.cuda.graph.__init__ = orig
 

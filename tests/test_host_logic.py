@@ -333,6 +333,49 @@ def test_graphed_step_is_freed_without_the_garbage_collector():
         gc.enable()
 
 
+def test_no_collection_while_capturing_collects_first_and_keeps_the_collector_off():
+    """torch.cuda.make_graphed_callables leaves every graphed module in a cycle (module -> replaced forward -> module): dropped
+    tower graphs are freed by the cyclic collector alone.  The capture window of dalm_amd/training/graphed.py frees them BEFORE the
+    capture begins and keeps the collector from running inside it; the collector's state is restored, also after an error."""
+    import gc
+    import weakref
+
+    from dalm_amd.training.graphed import no_collection_while_capturing, thread_local_capture
+
+    class Node:
+        pass
+
+    def cycle():
+        a = Node()
+        a.me = a
+        return weakref.ref(a)
+
+    assert gc.isenabled()
+    for window in (no_collection_while_capturing, thread_local_capture):
+        old = cycle()
+        with window():
+            assert old() is None                            # dead cycles from before the window are gone on entry
+            assert not gc.isenabled()
+            inner = cycle()
+            for _ in range(3):                              # allocation pressure does not start a collection
+                _ = [[] for _ in range(20000)]
+            assert inner() is not None
+        assert gc.isenabled()
+        gc.collect()
+        assert inner() is None
+    with pytest.raises(RuntimeError):
+        with no_collection_while_capturing():
+            raise RuntimeError("capture refused")
+    assert gc.isenabled()
+    gc.disable()                                            # a caller that runs with the collector off keeps it off
+    try:
+        with no_collection_while_capturing():
+            pass
+        assert not gc.isenabled()
+    finally:
+        gc.enable()
+
+
 def test_typer_cli_mirrors_trainer_signatures():
     """`dalm`-style CLI: same commands / positional order / option names as the reference's typer front-end
     (cli.py:41-277), generated from our trainer signatures so that defaults equal the golden reference defaults."""
