@@ -233,22 +233,25 @@ struct Lm8Params {
   const float* col_coef;     // [V]
   int64_t diag_offset;       // the positive of row i is global column diag_offset + i
   int64_t out_third;         // elements between the hi / mid / lo images inside a row of `out`
+  // EPI_LIVE (dalm_linear_live): the rows of H and `out` go through a stable partition of the row-liveness vector
+  const int* perm;           // [R] live rows first (ascending), then the dead ones
+  const int* n_live;         // device scalar: how many leading entries of perm are live (clamped to [0, R] by the kernel)
 };
 
 constexpr int L8_BUF = 65536;
-constexpr int EPI_LSE = 0, EPI_DLOGITS = 2, EPI_CSTORE = 3, EPI_DS3 = 4, EPI_LOGITS = 5;
+constexpr int EPI_LSE = 0, EPI_DLOGITS = 2, EPI_CSTORE = 3, EPI_DS3 = 4, EPI_LOGITS = 5, EPI_LIVE = 6;
 
 // Tile order.  The ordered tile list walks the output in bands of gh row tiles - within a band vocabulary tile by vocabulary
 // tile, the band's row tiles innermost - and every XCD (workgroup L runs on XCD L % 8, own 4 MB L2) works through ONE
 // contiguous run of that list.  The 32 tiles an XCD has in flight are then ~gh row panels x 32/gh vocabulary panels
 // (7 + 4.6 instead of 14 + 2.3 panels of 2 MB at 14 row tiles): every panel a CU pulls into the L2 is shared by 4-7 neighbours.
-__device__ __forceinline__ void lm_tile_of(const Lm8Params& p, unsigned block, unsigned nblocks, int& mt, int& nt) {
+__device__ __forceinline__ void lm_tile_order(int xcd_order, unsigned gh, unsigned NT, unsigned MT, unsigned block, unsigned nblocks,
+                                              int& mt, int& nt) {
   unsigned g = block;
-  if (p.xcd_order) {
+  if (xcd_order) {
     const unsigned q8 = nblocks >> 3, r8 = nblocks & 7u, xcd = block & 7u;
     g = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (block >> 3);
   }
-  const unsigned gh = static_cast<unsigned>(p.gh), NT = static_cast<unsigned>(p.NT), MT = static_cast<unsigned>(p.MT);
   const unsigned nfull = MT / gh, full = nfull * gh * NT;
   if (g < full) {
     const unsigned mg = g / (gh * NT), r = g % (gh * NT);
@@ -259,6 +262,10 @@ __device__ __forceinline__ void lm_tile_of(const Lm8Params& p, unsigned block, u
     nt = static_cast<int>(r / rem);
     mt = static_cast<int>(nfull * gh + r % rem);
   }
+}
+__device__ __forceinline__ void lm_tile_of(const Lm8Params& p, unsigned block, unsigned nblocks, int& mt, int& nt) {
+  lm_tile_order(p.xcd_order, static_cast<unsigned>(p.gh), static_cast<unsigned>(p.NT), static_cast<unsigned>(p.MT), block, nblocks,
+                mt, nt);
 }
 
 typedef __attribute__((address_space(3))) void lds_void_t;
@@ -586,46 +593,157 @@ __device__ __forceinline__ void lm_tile_epilogue_cstore(const Lm8Params& p, f32x
   }
 }
 
+// EPI_LIVE (dalm_linear_live): tile position i stands for row perm[i] of A and of C.  The (64 TI) x 256 tile leaves as bf16 into
+// out[perm[i]][c0 + column] - or is added in f32 to the bf16 value already there, one rounding - with the pair exchange of the
+// EPI_LOGITS epilogue (one dword per lane).  Positions n_live <= i < R of the boundary tile are dead rows: zeros when the output
+// is fresh, untouched when accumulating.  A perm entry outside [0, R) stores nothing.
+template <int TI>
+__device__ __forceinline__ void lm_tile_epilogue_live(const Lm8Params& p, f32x16 (&acc)[TI][4], unsigned char* lds, int r0, int c0,
+                                                      int nlive, int wr, int wc, int tid) {
+  const int lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
+  int* row_s = reinterpret_cast<int*>(lds);                   // [64 TI] row of C behind every tile position, -1: none
+  if (tid < 64 * TI) {
+    const int i = r0 + tid;
+    int row = -1;
+    if (i < p.R) {
+      row = p.perm[i];
+      if (static_cast<unsigned>(row) >= static_cast<unsigned>(p.R)) row = -1;
+    }
+    row_s[tid] = row;
+  }
+  __syncthreads();
+  const int colw = wc * 128 + l31;
+  const bool odd = (lane & 1) != 0;
+  const bool add = p.accumulate != 0;
+  unsigned short* outp = static_cast<unsigned short*>(p.out);
+#pragma unroll
+  for (int i = 0; i < TI; ++i) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int rl4 = wr * 32 * TI + i * 32 + 8 * g + 4 * lhi;   // positions rl4 .. rl4 + 3 = accumulator registers 4 g .. 4 g + 3
+      const int4 rw = *reinterpret_cast<const int4*>(row_s + rl4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int col = colw + 32 * j;
+        const int ce = c0 + (col & ~1);                          // even column of the lane pair
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const float mine_a = acc[i][j][4 * g + 2 * h], mine_b = acc[i][j][4 * g + 2 * h + 1];
+          const float send = odd ? mine_a : mine_b;
+          const float got = __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(send), 0xB1, 0xf, 0xf, false));
+          float x0 = odd ? got : mine_a, x1 = odd ? mine_b : got;   // columns (even, odd) of this lane's position
+          const int pos = r0 + rl4 + 2 * h + (odd ? 1 : 0);
+          const int row = h == 0 ? (odd ? rw.y : rw.x) : (odd ? rw.w : rw.z);
+          const bool live = pos < nlive;
+          if (row >= 0 && ce < p.out_cols && (live || !add)) {
+            unsigned int* dst = reinterpret_cast<unsigned int*>(outp + static_cast<int64_t>(row) * p.out_pitch + ce);
+            unsigned int word = 0u;
+            if (live) {
+              if (add) {
+                const unsigned int old = *dst;
+                x0 += __uint_as_float(old << 16);
+                x1 += __uint_as_float(old & 0xffff0000u);
+              }
+              word = pack_bf16x2(x0, x1);
+            }
+            *dst = word;
+          }
+        }
+      }
+    }
+  }
+}
+
+// EPI_LIVE, a tile whose every position is dead (block index past the live tiles): multiplies nothing.  A fresh output gets its
+// zeros here - tile positions r0 .. r0 + TROWS - 1 of perm, 256 columns from c0, 16 bytes per lane - an accumulating one nothing.
+__device__ __forceinline__ void lm_tile_zero_live(const Lm8Params& p, int r0, int trows, int c0, int tid) {
+  if (p.accumulate) return;
+  const int col = c0 + (tid & 31) * 8;
+  if (col >= p.out_cols) return;                                // out_cols % 8 == 0: a 16-byte piece is inside or outside
+  unsigned short* outp = static_cast<unsigned short*>(p.out);
+  for (int t = tid >> 5; t < trows; t += 8) {
+    const int i = r0 + t;
+    if (i >= p.R) break;
+    const int row = p.perm[i];
+    if (static_cast<unsigned>(row) >= static_cast<unsigned>(p.R)) continue;
+    *reinterpret_cast<uint4*>(outp + static_cast<int64_t>(row) * p.out_pitch + col) = make_uint4(0u, 0u, 0u, 0u);
+  }
+}
+
 // SPLIT3 (the bf16x3 similarity, see rowstats_bf16x3 below): the operands are [rows][3 D] bf16 images holding the (hi, mid,
 // lo) bf16 thirds of an f32 matrix side by side; the contraction walks SIX segments of D - the six significant products of
 // (hi + mid + lo) x (hi + mid + lo), smallest first - and K tile u reads third segA[u / tpd] of H against third segB[u / tpd]
 // of W: the same main loop, only the K offset of a tile is looked up instead of being u * 128.
-template <bool SPLIT3 = false, bool GMAX = false, int EPI = EPI_LSE>
+// TI = 32-row accumulator tiles per wave along the rows: the workgroup tile is (64 TI) x 256.  TI = 4 is the form described above;
+// TI = 2 (128 x 256, a wave owns 64 x 128: 8 MFMAs per 6 fragment reads instead of 16 per 8) exists for EPI_LIVE only, for shapes
+// whose row-tile count at 256 rows leaves a poor last round (dalm_linear_live's table).
+template <bool SPLIT3 = false, bool GMAX = false, int EPI = EPI_LSE, int TI = 4>
 __global__ __launch_bounds__(256, 1) void lm_head_lse4w_kernel(const Lm8Params p) {
-  // load pieces (16 per K tile and wave) issued in k-step 3 (right after the barrier) / 0 / 1 / 2: measured best of the placements
-  constexpr int N3 = 8, N0 = 8, N1 = 0, N2 = 0;
+  static_assert(TI == 4 || (TI == 2 && EPI == EPI_LIVE), "the 128-row form has the EPI_LIVE epilogue only");
+  constexpr int NA = 2 * TI, NP = NA + 8;        // load pieces of 32 rows per K tile: NA of the A tile, then 8 of the B tile
+  constexpr int NM = 4 * TI, NR = TI + 4;        // MFMAs and fragment reads per k-step
+  // load pieces (NP per K tile and wave) issued in k-step 3 (right after the barrier) / 0 / 1 / 2: measured best of the placements
+  constexpr int N3 = NP / 2, N0 = NP - NP / 2, N1 = 0, N2 = 0;
   __shared__ __attribute__((aligned(16))) unsigned char lds[2 * L8_BUF];
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 1, wc = wave & 1;
   int mt, nt;
-  lm_tile_of(p, blockIdx.x, gridDim.x, mt, nt);
-  const int r0 = mt * 256, c0 = nt * 256;
+  int nlive = 0;
+  if constexpr (EPI == EPI_LIVE) {
+    // the live row-tile count is a device value: the banded order runs over the live tiles, the skipping tiles come last
+    nlive = min(max(*p.n_live, 0), p.R);
+    const unsigned NT = static_cast<unsigned>(p.NT), mtl = static_cast<unsigned>((nlive + 64 * TI - 1) / (64 * TI));
+    const unsigned nlb = mtl * NT;
+    if (blockIdx.x >= nlb) {
+      const unsigned s = blockIdx.x - nlb;
+      lm_tile_zero_live(p, static_cast<int>(mtl + s / NT) * 64 * TI, 64 * TI, static_cast<int>(s % NT) * 256, tid);
+      return;
+    }
+    const unsigned bands = (mtl + 7) / 8;
+    lm_tile_order(p.xcd_order, (mtl + bands - 1) / bands, NT, mtl, blockIdx.x, nlb, mt, nt);
+  } else {
+    lm_tile_of(p, blockIdx.x, gridDim.x, mt, nt);
+  }
+  const int r0 = mt * 64 * TI, c0 = nt * 256;
   const __amdgpu_buffer_rsrc_t rsH = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.H), 0, static_cast<int>(p.bytesH), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.W), 0, static_cast<int>(p.bytesW), 0x00020000);
 
-  // load piece q (0..7: rows 32 q .. 32 q + 31 of the A tile, 8..15: of the B tile): thread -> row 32 q + tid / 8, chunk tid % 8
+  // load piece q (0..NA-1: rows 32 q .. 32 q + 31 of the A tile, NA..NP-1: of the B tile): thread -> row 32 q + tid / 8, chunk tid % 8
   const int srow = tid >> 3;
   const unsigned schunk = static_cast<unsigned>(((tid & 7) ^ ((srow >> 1) & 7)) * 16);
-  unsigned voff[16];
+  unsigned voff[NP];
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
-    voff[q] = static_cast<unsigned>(r0 + q * 32 + srow) * p.pitchH + schunk;
-    voff[8 + q] = static_cast<unsigned>(c0 + q * 32 + srow) * p.pitchW + schunk;
+    if constexpr (EPI == EPI_LIVE) {
+      // row gather: the A row of position i is perm[i]; a dead position gets row R = past the descriptor's range, reads zero
+      if (q < NA) {
+        const int i = r0 + q * 32 + srow;
+        int row = p.R;
+        if (i < nlive) {
+          row = p.perm[i];
+          if (static_cast<unsigned>(row) >= static_cast<unsigned>(p.R)) row = p.R;
+        }
+        voff[q] = static_cast<unsigned>(row) * p.pitchH + schunk;
+      }
+    } else {
+      voff[q] = static_cast<unsigned>(r0 + q * 32 + srow) * p.pitchH + schunk;
+    }
+    voff[NA + q] = static_cast<unsigned>(c0 + q * 32 + srow) * p.pitchW + schunk;
   }
   const int wave_lds = wave * 1024;
-#define L4_DMA(BUF, Q, KSA, KSB) lds_dma16((Q) < 8 ? rsH : rsW, lds + (BUF) * L8_BUF + (Q) * 4096 + wave_lds, voff[Q], (Q) < 8 ? (KSA) : (KSB));
+#define L4_DMA(BUF, Q, KSA, KSB) lds_dma16((Q) < NA ? rsH : rsW, lds + (BUF) * L8_BUF + (Q) * 4096 + wave_lds, voff[Q], (Q) < NA ? (KSA) : (KSB));
 
   const int f = (l31 >> 1) & 7;
   int koff[4];
 #pragma unroll
   for (int kk = 0; kk < 4; ++kk) koff[kk] = ((kk * 2 + lhi) ^ f) * 16;
-  const int abase = (wr * 128 + l31) * 128;
-  const int bbase = 32768 + (wc * 128 + l31) * 128;
+  const int abase = (wr * 32 * TI + l31) * 128;
+  const int bbase = NA * 4096 + (wc * 128 + l31) * 128;
 
-  f32x16 acc[4][4];
+  f32x16 acc[TI][4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < TI; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -646,25 +764,26 @@ __global__ __launch_bounds__(256, 1) void lm_head_lse4w_kernel(const Lm8Params p
       return static_cast<int>(third * p.seg_bytes) + w * 128;
     }
   };
-  bf16x8 fa0[4], fb0[4], fa1[4], fb1[4];
+  bf16x8 fa0[TI], fb0[4], fa1[TI], fb1[4];
 
+  // (TI = 4: the A and B reads of one i interleave, as the loop over both always did)
 #define L4_READ(BUF, KK, FA, FB)                                                                                      \
   _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                    \
-    FA[i] = *reinterpret_cast<const bf16x8*>(lds + (BUF) * L8_BUF + i * 4096 + abase + koff[KK]);                     \
+    if (i < TI) FA[i] = *reinterpret_cast<const bf16x8*>(lds + (BUF) * L8_BUF + i * 4096 + abase + koff[KK]);         \
     FB[i] = *reinterpret_cast<const bf16x8*>(lds + (BUF) * L8_BUF + i * 4096 + bbase + koff[KK]);                     \
   }
 #define L4_MFMA(FA, FB)                                                                                               \
-  _Pragma("unroll") for (int i = 0; i < 4; ++i) _Pragma("unroll") for (int j = 0; j < 4; ++j)                          \
+  _Pragma("unroll") for (int i = 0; i < TI; ++i) _Pragma("unroll") for (int j = 0; j < 4; ++j)                         \
       acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(FA[i], FB[j], acc[i][j], 0, 0, 0);
-  // 16 MFMAs, 8 fragment reads behind the first 8, ND load pieces behind the last ones
+  // NM MFMAs, NR fragment reads behind the first NR, ND load pieces behind the last ones (TI = 4: 16 and 8)
 #define L4_SCHED(ND)                                                                                                  \
-  _Pragma("unroll") for (int i = 0; i < 16; ++i) {                                                                    \
+  _Pragma("unroll") for (int i = 0; i < NM; ++i) {                                                                    \
     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                                \
-    if (i < 8) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                                     \
-    if ((ND) <= 8 ? (i >= 8 && i - 8 < (ND)) : (i >= 16 - (ND))) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);   \
+    if (i < NR) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                                    \
+    if ((ND) <= NM - NR ? (i >= NR && i - NR < (ND)) : (i >= NM - (ND))) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0); \
   }
 #define L4_PIECES(BUF, FIRST, COUNT, KSA, KSB)                                                                        \
-  _Pragma("unroll") for (int q = 0; q < 16; ++q) if (q >= (FIRST) && q < (FIRST) + (COUNT)) { L4_DMA(BUF, q, KSA, KSB) }
+  _Pragma("unroll") for (int q = 0; q < NP; ++q) if (q >= (FIRST) && q < (FIRST) + (COUNT)) { L4_DMA(BUF, q, KSA, KSB) }
 
   // one K tile in buffer BUF (OTH = the other buffer); fragments of its k-step 0 are already in fa0 / fb0
 #define L4_TILE(BUF, OTH, t)                                                                                          \
@@ -684,7 +803,7 @@ __global__ __launch_bounds__(256, 1) void lm_head_lse4w_kernel(const Lm8Params p
   }
 
   // ---- prologue: tile 0 complete, then the first pieces of tile 1 ----
-  _Pragma("unroll") for (int q = 0; q < 16; ++q) lds_dma16(q < 8 ? rsH : rsW, lds + q * 4096 + wave_lds, voff[q], ks(0, q < 8 ? 0 : 1));
+  _Pragma("unroll") for (int q = 0; q < NP; ++q) lds_dma16(q < NA ? rsH : rsW, lds + q * 4096 + wave_lds, voff[q], ks(0, q < NA ? 0 : 1));
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   L4_READ(0, 0, fa0, fb0)
@@ -706,7 +825,8 @@ __global__ __launch_bounds__(256, 1) void lm_head_lse4w_kernel(const Lm8Params p
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // tail re-reads still target the LDS about to be reused
   __builtin_amdgcn_s_barrier();
 
-  if constexpr (EPI == EPI_DS3) lm_tile_epilogue_ds3(p, acc, lds, r0, c0, wr, wc, tid);
+  if constexpr (EPI == EPI_LIVE) lm_tile_epilogue_live<TI>(p, acc, lds, r0, c0, nlive, wr, wc, tid);
+  else if constexpr (EPI == EPI_DS3) lm_tile_epilogue_ds3(p, acc, lds, r0, c0, wr, wc, tid);
   else if constexpr (EPI == EPI_DLOGITS) lm_tile_epilogue_dlogits<false>(p, acc, lds, r0, c0, wr, wc, tid);
   else if constexpr (EPI == EPI_LOGITS) lm_tile_epilogue_dlogits<true>(p, acc, lds, r0, c0, wr, wc, tid);
   else if constexpr (EPI == EPI_CSTORE) lm_tile_epilogue_cstore(p, acc, r0, c0, wr, wc, tid);
@@ -1262,5 +1382,97 @@ extern "C" int dalm_sim_grad_bf16x3(const float* A, const float* Bm, int64_t m, 
                          dim3(256), 0, s, q);
     }
   }
+  return check_launch(__func__);
+}
+
+
+// ---- padded step: frozen projections over the live rows only (DESIGN.md "Live-row GEMM") ---------------------------------------
+namespace {
+// Stable partition of a row-liveness vector in ONE workgroup: thread t owns the contiguous run of rows [t per, (t + 1) per),
+// counts its live rows, an inclusive scan over the 1024 counts gives every run its first live and first dead slot.  R is a
+// few thousand rows per tower call: one pass of a few microseconds on the caller's stream.
+__global__ __launch_bounds__(1024) void row_partition_kernel(const uint8_t* __restrict__ live, int R, int* __restrict__ perm,
+                                                             int* __restrict__ n_live) {
+  __shared__ int scan[1024];
+  const int t = threadIdx.x;
+  const int per = (R + 1023) / 1024;
+  const int lo = min(t * per, R), hi = min(lo + per, R);
+  int cnt = 0;
+  for (int r = lo; r < hi; ++r) cnt += live[r] != 0;
+  scan[t] = cnt;
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {
+    const int add = t >= off ? scan[t - off] : 0;
+    __syncthreads();
+    scan[t] += add;
+    __syncthreads();
+  }
+  const int total = scan[1023];
+  int li = scan[t] - cnt;               // live rows before this run
+  int di = total + (lo - li);           // dead rows before it, behind all the live ones
+  for (int r = lo; r < hi; ++r) {
+    if (live[r] != 0) perm[li++] = r;
+    else perm[di++] = r;
+  }
+  if (t == 0) *n_live = total;
+}
+
+// Tile form by shape: rows per workgroup tile, 256 or 128 (columns: 256 either way).  The choice is static - the live count is a
+// device value - and comes from tools/linear_live_bench.py at the padded step's shapes (profiles/linear_live_bench.txt).  Measured
+// there, the 128-row form (8 MFMAs per 6 fragment reads) is slower than or level with the 256-row form at every shape and mask,
+// also where 256-row tiles quantise worst (down dgrad, 2897 live rows: 516 tiles = 2.02 rounds, 288.4 us; 989 half tiles,
+// 288.6 us), so no shape selects it; callers can still name it (`form`).  A shape that wins with 128 rows gets its case here.
+inline int linear_live_form(int64_t R, int64_t N, int64_t K) {
+  (void)R; (void)N; (void)K;
+  return 256;
+}
+}  // namespace
+
+extern "C" int dalm_row_partition(const uint8_t* live, int64_t R, int32_t* perm, int32_t* n_live, dalm_stream_t stream) {
+  DALM_REQUIRE(live && perm && n_live, DALM_E_NULL, "null pointer argument");
+  DALM_REQUIRE(R > 0 && R <= 0x7fffff00ll, DALM_E_SHAPE, "need 0 < R < 2^31");
+  DALM_REQUIRE(reinterpret_cast<uintptr_t>(perm) % 4 == 0 && reinterpret_cast<uintptr_t>(n_live) % 4 == 0, DALM_E_ALIGN,
+               "perm / n_live must be 4-byte aligned");
+  hipLaunchKernelGGL(row_partition_kernel, dim3(1), dim3(1024), 0, as_stream(stream), live, static_cast<int>(R), perm, n_live);
+  return check_launch(__func__);
+}
+
+extern "C" int dalm_linear_live_form(int64_t R, int64_t N, int64_t K) { return linear_live_form(R, N, K); }
+
+extern "C" int dalm_linear_live(const void* A, int64_t lda, const void* W, void* C, int64_t ldc, int64_t R, int64_t N, int64_t K,
+                                const int32_t* perm, const int32_t* n_live, int accumulate, int form, dalm_stream_t stream) {
+  DALM_REQUIRE(A && W && C && perm && n_live, DALM_E_NULL, "null pointer argument");
+  DALM_REQUIRE(R > 0 && N > 0 && K > 0 && K % 64 == 0 && N % 8 == 0, DALM_E_SHAPE,
+               "need R, N, K > 0, K a multiple of 64 and N a multiple of 8");
+  DALM_REQUIRE(lda >= K && ldc >= N && lda % 8 == 0 && ldc % 8 == 0, DALM_E_SHAPE,
+               "row strides: lda >= K, ldc >= N, both multiples of 8 elements");
+  DALM_REQUIRE(R <= 0x7fffff00ll && N <= 0x7fffff00ll && lda <= 0x7fffffffll && ldc <= 0x7fffffffll, DALM_E_SHAPE,
+               "operands above 4 GB: use fewer rows per call");      // also keeps the products below inside 64 bits
+  DALM_REQUIRE(form == 0 || form == 128 || form == 256, DALM_E_SHAPE, "form: 0 (by shape), 128 or 256 rows per tile");
+  DALM_REQUIRE(accumulate == 0 || accumulate == 1, DALM_E_SHAPE, "accumulate: 0 or 1");
+  DALM_REQUIRE(reinterpret_cast<uintptr_t>(A) % 16 == 0 && reinterpret_cast<uintptr_t>(W) % 16 == 0 &&
+               reinterpret_cast<uintptr_t>(C) % 16 == 0, DALM_E_ALIGN, "A / W / C must be 16-byte aligned");
+  const uint64_t spanA = static_cast<uint64_t>(R + 256) * lda * 2, spanW = static_cast<uint64_t>(N + 256) * K * 2;
+  DALM_REQUIRE(spanA < 0xffffff00ull && spanW < 0xffffff00ull, DALM_E_SHAPE, "operands above 4 GB: use fewer rows per call");
+  const int rows = form ? form : linear_live_form(R, N, K);
+  Lm8Params q;
+  q.H = A; q.W = W; q.labels = nullptr; q.K = static_cast<int>(K);
+  q.R = static_cast<int>(R); q.V = static_cast<int>(N);
+  q.MT = static_cast<int>((R + rows - 1) / rows); q.NT = static_cast<int>((N + 255) / 256);
+  q.xcd_order = 1; q.gh = 1;                             // the kernel derives the banding from the live tile count
+  q.tpd = 0; q.tpd_inv = 0; q.seg_bytes = 0; q.gmax = nullptr; q.ng = 0;
+  q.pm = q.pl = q.z = nullptr;
+  q.bytesH = static_cast<unsigned>(static_cast<uint64_t>(R - 1) * lda * 2 + static_cast<uint64_t>(K) * 2);
+  q.bytesW = static_cast<unsigned>(static_cast<uint64_t>(N) * K * 2);
+  q.pitchH = static_cast<unsigned>(lda * 2); q.pitchW = static_cast<unsigned>(K * 2);
+  q.row_lse = nullptr; q.coef = nullptr; q.col_base = 0;
+  q.out = C; q.out_pitch = ldc; q.out_cols = static_cast<int>(N); q.accumulate = accumulate;
+  q.perm = perm; q.n_live = n_live;
+  DALM_REQUIRE(static_cast<int64_t>(q.MT) * q.NT <= 0x7fffffffll, DALM_E_SHAPE, "too many tiles for one launch");
+  const dim3 grid(static_cast<unsigned>(q.MT) * q.NT);
+  if (rows == 256)
+    hipLaunchKernelGGL((lm_head_lse4w_kernel<false, false, EPI_LIVE, 4>), grid, dim3(256), 0, as_stream(stream), q);
+  else
+    hipLaunchKernelGGL((lm_head_lse4w_kernel<false, false, EPI_LIVE, 2>), grid, dim3(256), 0, as_stream(stream), q);
   return check_launch(__func__);
 }

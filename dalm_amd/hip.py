@@ -173,6 +173,10 @@ SIGNATURES = {
     "dalm_lora2_rankupd_ld": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _f32, _int, _vp, _i64, _vp]),
     "dalm_lora2_colacc_ld": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _f32, _int, _vp, _sz, _vp, _vp, _i64,
                                     _vp]),
+    # padded step: stable partition of the row-liveness vector and the frozen-projection GEMM over the live rows
+    "dalm_row_partition": (_int, [_vp, _i64, _vp, _vp, _vp]),
+    "dalm_linear_live_form": (_int, [_i64, _i64, _i64]),
+    "dalm_linear_live": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _int, _int, _vp]),
 }
 
 

@@ -10,6 +10,12 @@ The vector is built ON THE DEVICE from the attention mask (no host sync, no chan
 recomputed from the graph's static mask input on every replay) and held for the duration of ONE tower call by `tower_call`;
 the op wrappers (tower_ops, lora_ops, bert_ops) read it in their forward with `current(rows)` and keep it for their backward.
 Nothing outside a training step enters the context: a module called directly gets None and the plain kernels.
+
+The frozen-projection GEMMs of the padded step (dalm_amd/linear_live.py) want the same information as a stable PARTITION of the
+rows - live rows first - plus the live count, both on the device: `current_partition(rows, device)` builds it from the vector with
+one launch of `dalm_row_partition`, on the first request inside a tower call (a tower whose projections never route never pays
+for it), and holds it beside the vector; inside a tower graph that launch is part of the graph, so the partition too is
+recomputed from the static mask on every replay.  The nodes keep it for their backward as they keep the vector.
 """
 from __future__ import annotations
 
@@ -43,12 +49,12 @@ def tower_call(attention_mask: Optional[torch.Tensor], shifted: bool, enabled: b
     vec = None
     if enabled and attention_mask is not None and attention_mask.dim() == 2 and attention_mask.is_cuda:
         vec = live_rows(attention_mask, shifted, last_column)
-    prev = getattr(_state, "vec", None)
-    _state.vec = vec
+    prev, prev_part = getattr(_state, "vec", None), getattr(_state, "part", None)
+    _state.vec, _state.part = vec, None
     try:
         yield vec
     finally:
-        _state.vec = prev
+        _state.vec, _state.part = prev, prev_part
 
 
 def current(rows: int, device=None) -> Optional[torch.Tensor]:
@@ -57,3 +63,17 @@ def current(rows: int, device=None) -> Optional[torch.Tensor]:
     if vec is None or vec.numel() != rows or (device is not None and vec.device != device):
         return None
     return vec
+
+
+def current_partition(rows: int, device=None):
+    """(perm int32 [rows], n_live int32 [1]) of the tower call in progress - `current(rows, device)` as a stable partition, live
+    rows first (dalm_amd/linear_live.py) - or None where `current` gives None."""
+    vec = current(rows, device)
+    if vec is None:
+        return None
+    part = getattr(_state, "part", None)
+    if part is None:
+        from . import linear_live
+
+        part = _state.part = linear_live.row_partition(vec)
+    return part

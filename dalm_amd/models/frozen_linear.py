@@ -77,12 +77,40 @@ def _compute_dtype(x: torch.Tensor) -> torch.dtype:
     return torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else x.dtype
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# padded tower call: the GEMM over the live rows only (dalm_amd/linear_live.py).  `_live_fwd` / `_live_dgrad` return None
+# when the call stays with the library - then nothing below differs from what it was.
+# ---------------------------------------------------------------------------------------------------------------------
+def _live_fwd(x: torch.Tensor, w: torch.Tensor, b):
+    """(y, partition) through dalm_linear_live, or None.  bf16 in and out without autocast's casts: x and w already are bf16."""
+    from .. import linear_live
+
+    if not linear_live.enabled() or b is not None or x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+        return None
+    x2 = x.reshape(-1, w.shape[1])
+    part = linear_live.route(x2, w, False)
+    if part is None:
+        return None
+    y = linear_live.linear_live(x2, w, part)
+    return y.view(*x.shape[:-1], w.shape[0]), part
+
+
+def _live_dgrad(g2: torch.Tensor, wt, part, dx=None):
+    """dx (+)= g2 . wt^T over the live rows (wt = the transposed copy [K, N]), or None when this shape stays with the library."""
+    from .. import linear_live
+
+    if part is None or wt is None or part[0].numel() != g2.shape[0] or not linear_live.accepts(g2, wt, False):
+        return None
+    return linear_live.linear_live(g2, wt, part, out=dx, accumulate=dx is not None)
+
+
 class _FrozenLinearFn(torch.autograd.Function):
     """y = x W^T + b with W, b frozen: the backward is dx = F.linear(g, W^T copy)."""
 
     @staticmethod
     def forward(ctx, x, w, b):
-        y = F.linear(x, w, b)                              # under autocast this casts exactly as nn.Linear.forward does
+        lv = _live_fwd(x, w, b)
+        y, ctx.part = lv if lv is not None else (F.linear(x, w, b), None)   # under autocast this casts exactly as nn.Linear.forward does
         ctx.w = w
         ctx.cdt = y.dtype
         ctx.xshape, ctx.xdtype = x.shape, x.dtype
@@ -95,7 +123,9 @@ class _FrozenLinearFn(torch.autograd.Function):
         g2 = g.reshape(-1, w.shape[0])
         if g2.dtype != ctx.cdt:
             g2 = g2.to(ctx.cdt)
-        dx = F.linear(g2, wt) if wt is not None else torch.mm(g2, w.to(ctx.cdt))
+        dx = _live_dgrad(g2, wt, ctx.part)
+        if dx is None:
+            dx = F.linear(g2, wt) if wt is not None else torch.mm(g2, w.to(ctx.cdt))
         dx = dx.view(ctx.xshape)
         return (dx if dx.dtype == ctx.xdtype else dx.to(ctx.xdtype)), None, None
 
@@ -106,7 +136,12 @@ class _FrozenPairFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w0, w1):
-        y0, y1 = F.linear(x, w0), F.linear(x, w1)
+        lv0 = _live_fwd(x, w0, None)
+        lv1 = _live_fwd(x, w1, None) if lv0 is not None else None
+        if lv1 is not None:
+            (y0, ctx.part), y1 = lv0, lv1[0]
+        else:
+            y0, y1, ctx.part = F.linear(x, w0), F.linear(x, w1), None
         ctx.w = (w0, w1)
         ctx.cdt = y0.dtype
         ctx.xshape, ctx.xdtype = x.shape, x.dtype
@@ -123,7 +158,10 @@ class _FrozenPairFn(torch.autograd.Function):
             if g2.dtype != ctx.cdt:
                 g2 = g2.to(ctx.cdt)
             wt = dgrad_weight(w, ctx.cdt)
-            if dx is None:
+            lv = _live_dgrad(g2, wt, ctx.part, dx)           # accumulating: adds into dx in f32, one rounding, as addmm_ does
+            if lv is not None:
+                dx = lv
+            elif dx is None:
                 dx = F.linear(g2, wt) if wt is not None else torch.mm(g2, w.to(ctx.cdt))
             elif wt is not None:
                 dx.addmm_(g2, wt.t())
@@ -256,7 +294,8 @@ class _FrozenCatPairFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, cat, w0, w1):
-        y = F.linear(x, cat)
+        lv = _live_fwd(x, cat, None)
+        y, ctx.part = lv if lv is not None else (F.linear(x, cat), None)
         n0 = w0.shape[0]
         ctx.w = (w0, w1)
         ctx.cdt = y.dtype

@@ -346,8 +346,12 @@ class _LoRAGroupFn(torch.autograd.Function):
         wc = [w if w.dtype == x2.dtype else w.to(x2.dtype) for w in Ws]
         outs = []
         with torch.autocast("cuda", enabled=False):
+            from . import frozen_linear
+
+            part = None
             if cat is not None:
-                y = torch.nn.functional.linear(x2, cat[0], cat[1])                     # [R, sum N_i]: one GEMM
+                lv = frozen_linear._live_fwd(x2, cat[0], cat[1])                       # padded tower call: the live rows only
+                y, part = lv if lv is not None else (torch.nn.functional.linear(x2, cat[0], cat[1]), None)   # [R, sum N_i]: one GEMM
                 outs = list(y.split([w.shape[0] for w in Ws], dim=1))
             else:
                 for i in range(n):
@@ -383,7 +387,7 @@ class _LoRAGroupFn(torch.autograd.Function):
                 for i in grp:
                     rankupd2_([outs[i]], [zs[i]], [Bts[i]], None, rank, meta[i][0], 1, live)
         ctx.meta, ctx.lora, ctx.n, ctx.rank = meta, lora, n, rank
-        ctx.w_params = Ws
+        ctx.w_params, ctx.part = Ws, part
         ctx.xshape, ctx.xdtype = x.shape, x.dtype
         ctx.set_materialize_grads(False)          # an output nobody differentiated arrives as None, not as a zero tensor
         ctx.save_for_backward(x2, *wc, *[As[i] for i in lora], *[Bts[i] for i in lora], *[zs[i] for i in lora],
@@ -449,7 +453,10 @@ class _LoRAGroupFn(torch.autograd.Function):
                 # frozen weights: through the transposed copy (the forward's GEMM layout: frozen_linear.py); ctx.w_params holds
                 # the PARAMETERS (the cache lives on them), wc the compute-dtype tensors the forward used
                 wt = frozen_linear.dgrad_weight(ctx.w_params[i], x2.dtype)
-                if dx is None:
+                lv = frozen_linear._live_dgrad(g2[i], wt, ctx.part, dx)
+                if lv is not None:
+                    dx = lv
+                elif dx is None:
                     dx = torch.nn.functional.linear(g2[i], wt) if wt is not None else torch.mm(g2[i], wc[i])
                 elif wt is not None:
                     dx.addmm_(g2[i], wt.t())

@@ -839,6 +839,23 @@ int dalm_sim_grad_bf16x3(const float* A, const float* Bm, int64_t m, int64_t n, 
                          const float* row_coef, const float* row_lse, const float* col_coef, const float* col_lse, float* dA,
                          void* ws, size_t ws_bytes, dalm_stream_t stream);
 
+/* ---- padded step: frozen projections over the live rows only -------------------------------------------------------------------
+ * dalm_row_partition: live [R] bytes (Row liveness, above) -> perm [R] int32, a STABLE partition - the live rows first, ascending,
+ *   then the dead rows, ascending - and the device scalar n_live = how many are live.  One launch of one workgroup.
+ * dalm_linear_live:   C[perm[i], :] (+)= A[perm[i], :] . W^T for i < n_live; A [R, K] (row stride lda), W [N, K] contiguous,
+ *   C [R, N] (row stride ldc), all bf16, f32 accumulation on the matrix cores (the lm_head main loop with a row gather on the A
+ *   operand: a tile of dead rows multiplies nothing).  Nothing of a dead row of A is read.  Dead rows of C: accumulate = 0 - zeros
+ *   (the `_live` contract); accumulate = 1 - left as they are, and a live row gets bf16(f32(C) + A . W^T), one rounding.  Columns
+ *   >= N of a strided C are not touched.  n_live is read on the device and clamped to [0, R]; perm entries outside [0, R) select
+ *   nothing.  The launch shape depends on (R, N, K, form) only: no host sync, replayable in a hipGraph with a changing mask.
+ *   form: rows per workgroup tile, 256 or 128; 0 = by shape (dalm_linear_live_form, a table measured at the padded step's shapes).
+ *   K % 64 == 0, N % 8 == 0, lda >= K, ldc >= N, both strides multiples of 8, (R + 256) lda and (N + 256) K below 2^31 elements
+ *   (DALM_E_SHAPE); A / W / C 16-byte aligned (DALM_E_ALIGN).  No bias, bf16 only.  Fixed summation order. */
+int dalm_row_partition(const uint8_t* live, int64_t R, int32_t* perm, int32_t* n_live, dalm_stream_t stream);
+int dalm_linear_live_form(int64_t R, int64_t N, int64_t K);
+int dalm_linear_live(const void* A, int64_t lda, const void* W, void* C, int64_t ldc, int64_t R, int64_t N, int64_t K,
+                     const int32_t* perm, const int32_t* n_live, int accumulate, int form, dalm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -502,6 +502,18 @@ def bench_gemma_norm(R, D, rounds=3):
     return out
 
 
+def bench_linear_live(members, halves):
+    """dalm_linear_live against the tuned library GEMM at 4608 padded rows under the first mask of the step bench
+    (tools/linear_live_bench.py holds the arms and the timing; its own run covers every mask)."""
+    import linear_live_bench as llb
+    from dalm_amd.tuning import enable_tuned_gemms
+
+    enable_tuned_gemms()
+    dev = torch.device("cuda")
+    _, res = llb.bench_gemm(members, halves, llb.masks(dev)[1:2], dev, lambda s: None)[0]
+    return {arm: {"s": t, "spread_s": sp} for arm, (t, sp) in res.items()}
+
+
 def print_results(res) -> None:
     for k, v in res.items():
         print(k)
@@ -573,6 +585,12 @@ def main():
         for B, T in ((150, 128), (150, 50)):
             for p in (0.0, 0.1):
                 res[f"embed_norm XLM-R-large retriever-only rows {B}x{T} D1024 p={p}"] = bench_embed_norm(B, T, 1024, p)
+    if args.only in ("", "linear_live"):
+        sys.path.insert(0, str(Path(__file__).resolve().parent))
+        import linear_live_bench as llb
+
+        for name, members, halves in llb.GEMMS:
+            res[f"linear_live {name} rows 4608 N{members[0][0]} K{members[0][1]} (batch 100 mask)"] = bench_linear_live(members, halves)
     # the headline batch's rows (18 x 256) at Gemma-7B's widths: intermediate 24576, hidden 3072
     if args.only in ("", "geglu"):
         res["geglu Gemma-7B rows 4608 x 24576 bf16 (halves of one [R, 2 C] buffer)"] = bench_geglu(4608, 24576)

@@ -1,0 +1,170 @@
+"""Kernel bench of `dalm_linear_live` against the tuned library GEMMs at the padded cfg3 step's generator shapes.
+
+    python tools/linear_live_bench.py [--out profiles/linear_live_bench.txt] [--quick]
+
+The seven GEMMs of one Llama-2-7b layer and the two of the materialised lm_head at R = 4608 padded rows (18 x 256), each with
+  * every row live, and the four masks of `bench.synthetic_batch(dev, 100 + i)` under the generator's shifted rule;
+  * three arms: the kernel in its 256-row and its 128-row tile form, and `F.linear` / `addmm_` through the tuned solution table.
+Every arm is timed inside a hipGraph of LAUNCHES (>= 20) launches, over a ring of weight copies larger than the Infinity Cache
+(in the step every layer brings its own weights from HBM); the median of 5 replays is taken and the spread (max - min) printed.
+FLOP are counted over LIVE rows (2 live N K), `frac` is against the bf16 MFMA peak - for the library arm too, so its frac at a
+padded mask shows what the padding costs.  `win` marks a kernel arm faster than the library arm by more than three times the
+larger of the two spreads: the routing table in dalm_amd/linear_live.py lists exactly those shapes.
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+from pathlib import Path
+
+import torch
+import torch.nn.functional as F
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+from dalm_amd import linear_live, live_rows  # noqa: E402
+
+BF16_PEAK = 2.5e15          # dense bf16 MFMA peak of the MI355X, FLOP/s
+R = 4608
+LAUNCHES = 20
+REPLAYS = 5
+RING_BYTES = 512 << 20
+
+# name, (N, K) of every accumulated member, A as column halves of one buffer
+GEMMS = [
+    ("o_proj fwd / o dgrad", [(4096, 4096)], False),
+    ("q|k|v fwd", [(12288, 4096)], False),
+    ("q|k|v dgrad (3 accumulated)", [(4096, 4096)] * 3, False),
+    ("gate|up fwd", [(22016, 4096)], False),
+    ("gate + up dgrad (2 accumulated)", [(4096, 11008)] * 2, True),
+    ("down fwd", [(4096, 11008)], False),
+    ("down dgrad", [(11008, 4096)], False),
+    ("lm_head fwd (materialised logits)", [(32000, 4096)], False),
+    ("lm_head dgrad", [(4096, 32000)], False),
+]
+
+
+def masks(dev):
+    import bench
+
+    out = [("all live", torch.ones(R, dtype=torch.uint8, device=dev))]
+    for i in range(4):
+        m = bench.synthetic_batch(dev, 100 + i)["generator_input_attention_mask"]
+        out.append((f"batch {100 + i}", live_rows.live_rows(m, shifted=True)))
+    return out
+
+
+def time_graph(fn):
+    """fn(i) = launch number i.  (median, spread) seconds per launch over REPLAYS replays of a graph of LAUNCHES launches."""
+    for i in range(2):
+        fn(i)
+    torch.cuda.synchronize()
+    g, s = torch.cuda.CUDAGraph(), torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        with torch.cuda.graph(g, stream=s):
+            for i in range(LAUNCHES):
+                fn(i)
+    torch.cuda.current_stream().wait_stream(s)
+    g.replay()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(REPLAYS):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        g.replay()
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b) * 1e-3 / LAUNCHES)
+    ts.sort()
+    return ts[len(ts) // 2], ts[-1] - ts[0]
+
+
+def bench_gemm(members, halves, mask_list, dev, emit):
+    n, k = members[0]
+    nm = len(members)
+    gen = torch.Generator(device=dev).manual_seed(7)
+    ring = max(2, min(LAUNCHES, RING_BYTES // (nm * n * k * 2) + 1))
+    ws = [[(torch.randn(n, k, device=dev, generator=gen) * 0.02).bfloat16() for _ in range(nm)] for _ in range(ring)]
+    if halves:
+        buf = torch.randn(R, nm * k, device=dev, generator=gen).bfloat16()
+        xs = [buf[:, j * k:(j + 1) * k] for j in range(nm)]
+    else:
+        xs = [torch.randn(R, k, device=dev, generator=gen).bfloat16() for _ in range(nm)]
+    out = torch.empty(R, n, dtype=torch.bfloat16, device=dev)
+    rows = []
+    for mname, vec in mask_list:
+        part = linear_live.row_partition(vec)
+        n_live = int(part[1].item())
+
+        def lib(i):
+            w = ws[i % ring]
+            y = F.linear(xs[0], w[0])
+            for j in range(1, nm):
+                y.addmm_(xs[j], w[j].t())
+
+        def kern(form):
+            def run(i):
+                w = ws[i % ring]
+                for j in range(nm):
+                    linear_live.linear_live(xs[j], w[j], part, out=out, accumulate=j > 0, form=form)
+            return run
+
+        fl = nm * linear_live.flops(n_live, n, k)
+        res = {"library": time_graph(lib), "kernel 256": time_graph(kern(256)), "kernel 128": time_graph(kern(128))}
+        lt, ls = res["library"]
+        for arm, (t, sp) in res.items():
+            win = ""
+            if arm != "library":
+                win = "win" if lt - t > 3 * max(sp, ls) else "-"
+            emit(f"  {mname:10s} live {n_live:5d}  {arm:11s} {t * 1e6:8.1f} us  spread {sp * 1e6:6.1f} us  "
+                 f"{fl / t / 1e12:7.1f} TF/s  frac {fl / t / BF16_PEAK:5.3f}  "
+                 f"tiles {linear_live.tiles(n_live, n, 128 if arm.endswith('128') else 256):5d}  {win}")
+        rows.append((mname, res))
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "linear_live_bench.txt"))
+    ap.add_argument("--quick", action="store_true", help="all-live and one batch mask only")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("linear_live_bench needs the GPU: there is no CPU timing of a HIP kernel")
+    dev = torch.device("cuda")
+    from dalm_amd.tuning import enable_tuned_gemms
+
+    lines = []
+
+    def emit(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    emit(f"linear_live_bench: R = {R}, graph of {LAUNCHES} launches, median of {REPLAYS} replays, "
+         f"weights rotate over a ring > {RING_BYTES >> 20} MB; tuned GEMM table loaded: {enable_tuned_gemms()}")
+    emit(f"device: {torch.cuda.get_device_name(0)}; bf16 peak taken as {BF16_PEAK / 1e12:.0f} TF/s; FLOP over live rows")
+    warm = torch.randn(4096, 4096, device=dev).bfloat16()
+    for _ in range(300):                                   # clocks up before the first timed arm
+        warm = F.linear(warm, warm) * 0.01
+    torch.cuda.synchronize()
+    ml = masks(dev)
+    if args.quick:
+        ml = ml[:2]
+    verdict = []
+    for name, members, halves in GEMMS:
+        n, k = members[0]
+        emit(f"{name}: N = {n}, K = {k}, members {len(members)}, routed form now: {linear_live.table_form(R, n, k)}")
+        rows = bench_gemm(members, halves, ml, dev, emit)
+        # a shape is routed when one form wins at EVERY batch mask (the all-live line is the no-padding reference)
+        for form in ("kernel 256", "kernel 128"):
+            ok = all(res["library"][0] - res[form][0] > 3 * max(res[form][1], res["library"][1]) for m, res in rows if m != "all live")
+            verdict.append(f"  {name:34s} {form}: {'clears the library at every batch mask' if ok else 'does not clear'}")
+    emit("verdict (faster than the library arm by > 3 x the larger spread, at all batch masks):")
+    for v in verdict:
+        emit(v)
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
