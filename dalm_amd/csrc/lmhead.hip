@@ -16,6 +16,9 @@
 // K-contiguous ("B^T input"), so A and B fragments use the same addressing; the loads of step i+1 are in flight while
 // step i is multiplied.
 #include "common.hpp"
+#include "swiglu_math.hpp"
+#include <atomic>
+#include <mutex>
 #include <type_traits>
 
 namespace dalm {
@@ -223,23 +226,31 @@ struct Lm8Params {
   // EPI_DLOGITS / EPI_CSTORE (round 5: the backward of the fused head)
   const float* row_lse;      // [R] log-sum-exp of every row over the WHOLE vocabulary
   const float* coef;         // [R] d loss / d log-prob of the row's label (0 for rows without loss)
-  int col_base;              // first vocabulary entry of this chunk (labels are global ids)
+  union {
+    int col_base;            // first vocabulary entry of this chunk (labels are global ids)
+    int y_half;              // EPI_LIVE_SWIGLU / EPI_LIVE_DSWIGLU: columns between the gate and up halves of a row of y (= C)
+  };
   void* out;                 // EPI_DLOGITS: bf16 [R][out_pitch];  EPI_CSTORE: f32 [R][out_pitch]
   int64_t out_pitch;         // elements
   int out_cols;              // columns that exist in `out` (EPI_DLOGITS: zero-filled from V up to here)
   int accumulate;            // EPI_CSTORE: add to what `out` holds
   // EPI_DS3 (round 5: the similarity backward on the bf16 pipe); row statistics ride in row_lse / coef above
-  const float* col_lse;      // [V] column log-sum-exp (global column = col_base + local)
-  const float* col_coef;     // [V]
-  int64_t diag_offset;       // the positive of row i is global column diag_offset + i
-  int64_t out_third;         // elements between the hi / mid / lo images inside a row of `out`
+  // The frozen MLP node's epilogues (EPI_LIVE_SWIGLU / EPI_LIVE_DSWIGLU) keep their operands in the same slots - the struct, and
+  // with it the kernel-argument layout every other instantiation was compiled against, does not grow: y = [gate | up]
+  // [R][y_pitch] bf16 (written through `out` by the forward, read by the backward); out2 = act (forward) / d_up (backward, where
+  // `out` is d_gate)
+  union { const float* col_lse; const void* y; };        // [V] column log-sum-exp (global column = col_base + local)
+  union { const float* col_coef; void* out2; };          // [V]
+  union { int64_t diag_offset; int64_t y_pitch; };       // the positive of row i is global column diag_offset + i
+  union { int64_t out_third; int64_t out2_pitch; };      // elements between the hi / mid / lo images inside a row of `out`
   // EPI_LIVE (dalm_linear_live): the rows of H and `out` go through a stable partition of the row-liveness vector
   const int* perm;           // [R] live rows first (ascending), then the dead ones
   const int* n_live;         // device scalar: how many leading entries of perm are live (clamped to [0, R] by the kernel)
 };
 
 constexpr int L8_BUF = 65536;
-constexpr int EPI_LSE = 0, EPI_DLOGITS = 2, EPI_CSTORE = 3, EPI_DS3 = 4, EPI_LOGITS = 5, EPI_LIVE = 6;
+constexpr int EPI_LSE = 0, EPI_DLOGITS = 2, EPI_CSTORE = 3, EPI_DS3 = 4, EPI_LOGITS = 5, EPI_LIVE = 6, EPI_LIVE_SWIGLU = 7,
+              EPI_LIVE_DSWIGLU = 8;
 
 // Tile order.  The ordered tile list walks the output in bands of gh row tiles - within a band vocabulary tile by vocabulary
 // tile, the band's row tiles innermost - and every XCD (workgroup L runs on XCD L % 8, own 4 MB L2) works through ONE
@@ -654,6 +665,205 @@ __device__ __forceinline__ void lm_tile_epilogue_live(const Lm8Params& p, f32x16
   }
 }
 
+// rb(silu(g)) for every bf16 g, indexed by g's 16 bits: 128 KB that stay in the caches.  The forward epilogue below is VALU-bound
+// with its one wave per SIMD - silu is an exp, an IEEE division and two transcendental-rate instructions per element, ~14 us per
+// tile against ~3 for the rest of the epilogue - and g has only 65536 values.  Filled once per device by silu_table_kernel with
+// swiglu_math.hpp's own function, so an entry holds the very bits the row-wise kernel computes (NaN payloads included).
+__device__ unsigned short g_silu_bf16_tab[65536];
+__global__ __launch_bounds__(256) void silu_table_kernel() {
+  const unsigned int i = blockIdx.x * 256 + threadIdx.x;
+  g_silu_bf16_tab[i] = f32_to_bf16(swiglu_silu_rb<Bf16Round>(bf16_to_f32(static_cast<unsigned short>(i))));
+}
+
+// The row behind every position of a 256-position live tile, for the two MLP epilogues below: -1 for a dead position (>= n_live)
+// and for a perm entry outside [0, R) - nothing is stored for either.
+__device__ __forceinline__ void lm_live_rows_to_lds(const Lm8Params& p, int* row_s, int r0, int nlive, int tid) {
+  const int i = r0 + tid;
+  int row = -1;
+  if (i < nlive) {
+    row = p.perm[i];
+    if (static_cast<unsigned>(row) >= static_cast<unsigned>(p.R)) row = -1;
+  }
+  row_s[tid] = row;
+  __syncthreads();
+}
+
+// EPI_LIVE_SWIGLU (dalm_linear_live_swiglu): the tile's 256 B rows are 128 gate rows and the 128 up rows of the SAME activation
+// columns c0 .. c0 + 127, so wave (wr, 0) holds gate and wave (wr, 1) up for the same (position, column) in the same accumulator
+// register of the same lane.  Both leave rounded to bf16 into y[perm[i]][c0 + col] / y[perm[i]][y_half + c0 + col] (the backward
+// reads them), and act = rb(s u), s = rb(silu(g)) from the table above, leaves into out2: each wave of a pair hands the packed
+// words of two of its four 32-row blocks to its partner through the LDS (free after the main loop; 16 KB per wave, lane-linear
+// dwords) and computes the other two.
+// Dead positions and corrupt perm entries store nothing, anywhere.
+// One 32-row block of a wave in two steps.  `hand over`: pack, store this wave's half of y, leave the words in the LDS for the
+// partner.  `finish`: pack, take the partner's words, gather s for all 32 words at once - the kernel runs one wave per SIMD, nothing
+// else hides a load's latency, so the 64 gathers go out together and ahead of the arithmetic - then act, then the stores, whose row
+// address is computed once per row.  A block is its own function so that the accumulator indices stay static.
+template <bool FINISH>
+__device__ __forceinline__ void lm_swiglu_block(const Lm8Params& p, const f32x16 (&a)[4], const int* row_s, unsigned int* xmine,
+                                                const unsigned int* xtheirs, int rl, int ce0, bool odd, int lhi, int wc) {
+  unsigned short* yp = static_cast<unsigned short*>(p.out) + (wc ? p.y_half : 0);
+  unsigned short* ap = static_cast<unsigned short*>(p.out2);
+  int row[4][2];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const int4 rw = *reinterpret_cast<const int4*>(row_s + rl + 8 * g + 4 * lhi);
+    row[g][0] = odd ? rw.y : rw.x;
+    row[g][1] = odd ? rw.w : rw.z;
+  }
+  unsigned int word[4][4][2], actw[4][4][2];
+#pragma unroll
+  for (int g = 0; g < 4; ++g)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const float mine_a = a[j][4 * g + 2 * h], mine_b = a[j][4 * g + 2 * h + 1];
+        const float send = odd ? mine_a : mine_b;
+        const float got = __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(send), 0xB1, 0xf, 0xf, false));
+        word[g][j][h] = odd ? pack_bf16x2(got, mine_b) : pack_bf16x2(mine_a, got);
+        if constexpr (!FINISH) xmine[((g * 4 + j) * 2 + h) * 64] = word[g][j][h];
+      }
+  if constexpr (FINISH) {
+    unsigned int other[4][4][2];
+    unsigned short s0[4][4][2], s1[4][4][2];
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) other[g][j][h] = xtheirs[((g * 4 + j) * 2 + h) * 64];
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const unsigned int gw = wc ? other[g][j][h] : word[g][j][h];
+          s0[g][j][h] = g_silu_bf16_tab[gw & 0xffffu];
+          s1[g][j][h] = g_silu_bf16_tab[gw >> 16];
+        }
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const unsigned int uw = wc ? word[g][j][h] : other[g][j][h];
+          const float a0 = swiglu_act_of<Bf16Round>(bf16_to_f32(s0[g][j][h]), __uint_as_float(uw << 16));
+          const float a1 = swiglu_act_of<Bf16Round>(bf16_to_f32(s1[g][j][h]), __uint_as_float(uw & 0xffff0000u));
+          actw[g][j][h] = pack_bf16x2(a0, a1);
+        }
+  }
+#pragma unroll
+  for (int g = 0; g < 4; ++g)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      if (row[g][h] < 0) continue;
+      unsigned short* yr = yp + static_cast<int64_t>(row[g][h]) * p.out_pitch + ce0;
+      unsigned short* ar = ap + static_cast<int64_t>(row[g][h]) * p.out2_pitch + ce0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        *reinterpret_cast<unsigned int*>(yr + 32 * j) = word[g][j][h];
+        if constexpr (FINISH) *reinterpret_cast<unsigned int*>(ar + 32 * j) = actw[g][j][h];
+      }
+    }
+}
+__device__ __forceinline__ void lm_tile_epilogue_live_swiglu(const Lm8Params& p, f32x16 (&acc)[4][4], unsigned char* lds, int r0,
+                                                             int c0, int nlive, int wr, int wc, int tid) {
+  const int lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
+  int* row_s = reinterpret_cast<int*>(lds);                    // [256]
+  unsigned int* xch = reinterpret_cast<unsigned int*>(lds + 4096);   // [4 waves][2 blocks][32 words][64 lanes]
+  lm_live_rows_to_lds(p, row_s, r0, nlive, tid);
+  const bool odd = (lane & 1) != 0;
+  const int ce0 = c0 + (l31 & ~1);                             // even column of the lane pair in accumulator tile j = 0 (C % 128 == 0: inside)
+  unsigned int* mine = xch + (wr * 2 + wc) * 4096 + lane;
+  const unsigned int* theirs = xch + (wr * 2 + (wc ^ 1)) * 4096 + lane;
+  const int rl = wr * 128;
+  // wave wc finishes blocks 2 wc and 2 wc + 1 and hands the other two over (wave-uniform branch, static accumulator indices)
+  if (wc == 0) {
+    lm_swiglu_block<false>(p, acc[2], row_s, mine, theirs, rl + 64, ce0, odd, lhi, wc);
+    lm_swiglu_block<false>(p, acc[3], row_s, mine + 2048, theirs, rl + 96, ce0, odd, lhi, wc);
+  } else {
+    lm_swiglu_block<false>(p, acc[0], row_s, mine, theirs, rl, ce0, odd, lhi, wc);
+    lm_swiglu_block<false>(p, acc[1], row_s, mine + 2048, theirs, rl + 32, ce0, odd, lhi, wc);
+  }
+  __syncthreads();
+  if (wc == 0) {
+    lm_swiglu_block<true>(p, acc[0], row_s, mine, theirs, rl, ce0, odd, lhi, wc);
+    lm_swiglu_block<true>(p, acc[1], row_s, mine, theirs + 2048, rl + 32, ce0, odd, lhi, wc);
+  } else {
+    lm_swiglu_block<true>(p, acc[2], row_s, mine, theirs, rl + 64, ce0, odd, lhi, wc);
+    lm_swiglu_block<true>(p, acc[3], row_s, mine, theirs + 2048, rl + 96, ce0, odd, lhi, wc);
+  }
+}
+
+// EPI_LIVE_DSWIGLU (dalm_linear_live_dswiglu): the tile is d_act of the down projection.  Per lane pair, as in the EPI_LIVE epilogue:
+// the pair rounded to bf16 is exactly what the unfused path stores as d_act; the gate and up words of y[perm[i]] at the same
+// columns are loaded, the SwiGLU backward applied, and d_gate / d_up leave into out / out2.  d_act itself is never written; dead
+// positions, corrupt perm entries and columns >= out_cols store nothing (their loads read word 0 of y instead: in bounds, unused).
+// One 32-row block of a wave at a time: its 64 loads are issued together, ahead of the arithmetic - the kernel runs one wave per
+// SIMD, nothing else hides a load's latency - and a block is its own function so that the accumulator indices stay static.
+__device__ __forceinline__ void lm_dswiglu_block(const Lm8Params& p, const f32x16 (&a)[4], const int* row_s, int rl, int cw, bool odd,
+                                                 int lhi) {
+  const unsigned short* yp = static_cast<const unsigned short*>(p.y);
+  unsigned short* dgp = static_cast<unsigned short*>(p.out);
+  unsigned short* dup = static_cast<unsigned short*>(p.out2);
+  int row[4][2];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const int4 rw = *reinterpret_cast<const int4*>(row_s + rl + 8 * g + 4 * lhi);
+    row[g][0] = odd ? rw.y : rw.x;
+    row[g][1] = odd ? rw.w : rw.z;
+  }
+  unsigned int gw[4][4][2], uw[4][4][2];
+#pragma unroll
+  for (int g = 0; g < 4; ++g)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int ce = cw + 32 * j;
+        const bool ok = row[g][h] >= 0 && ce < p.out_cols;
+        const unsigned short* yr = yp + (ok ? static_cast<int64_t>(row[g][h]) * p.y_pitch + ce : 0);
+        gw[g][j][h] = *reinterpret_cast<const unsigned int*>(yr);
+        uw[g][j][h] = *reinterpret_cast<const unsigned int*>(yr + p.y_half);
+      }
+#pragma unroll
+  for (int g = 0; g < 4; ++g)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int ce = cw + 32 * j;
+        const float mine_a = a[j][4 * g + 2 * h], mine_b = a[j][4 * g + 2 * h + 1];
+        const float send = odd ? mine_a : mine_b;
+        const float got = __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(send), 0xB1, 0xf, 0xf, false));
+        const unsigned int daw = odd ? pack_bf16x2(got, mine_b) : pack_bf16x2(mine_a, got);
+        const unsigned int g2 = gw[g][j][h], u2 = uw[g][j][h];
+        float dg0, dg1, du0, du1;
+        swiglu_bwd_elem<Bf16Round>(__uint_as_float(daw << 16), __uint_as_float(g2 << 16), __uint_as_float(u2 << 16), dg0, du0);
+        swiglu_bwd_elem<Bf16Round>(__uint_as_float(daw & 0xffff0000u), __uint_as_float(g2 & 0xffff0000u),
+                                   __uint_as_float(u2 & 0xffff0000u), dg1, du1);
+        if (row[g][h] >= 0 && ce < p.out_cols) {
+          *reinterpret_cast<unsigned int*>(dgp + static_cast<int64_t>(row[g][h]) * p.out_pitch + ce) = pack_bf16x2(dg0, dg1);
+          *reinterpret_cast<unsigned int*>(dup + static_cast<int64_t>(row[g][h]) * p.out2_pitch + ce) = pack_bf16x2(du0, du1);
+        }
+      }
+}
+__device__ __forceinline__ void lm_tile_epilogue_live_dswiglu(const Lm8Params& p, f32x16 (&acc)[4][4], unsigned char* lds, int r0,
+                                                              int c0, int nlive, int wr, int wc, int tid) {
+  const int lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
+  int* row_s = reinterpret_cast<int*>(lds);
+  lm_live_rows_to_lds(p, row_s, r0, nlive, tid);
+  const int cw = c0 + ((wc * 128 + l31) & ~1);                  // even column of the lane pair in accumulator tile j = 0
+  const bool odd = (lane & 1) != 0;
+  lm_dswiglu_block(p, acc[0], row_s, wr * 128, cw, odd, lhi);
+  lm_dswiglu_block(p, acc[1], row_s, wr * 128 + 32, cw, odd, lhi);
+  lm_dswiglu_block(p, acc[2], row_s, wr * 128 + 64, cw, odd, lhi);
+  lm_dswiglu_block(p, acc[3], row_s, wr * 128 + 96, cw, odd, lhi);
+}
+
 // EPI_LIVE, a tile whose every position is dead (block index past the live tiles): multiplies nothing.  A fresh output gets its
 // zeros here - tile positions r0 .. r0 + TROWS - 1 of perm, 256 columns from c0, 16 bytes per lane - an accumulating one nothing.
 __device__ __forceinline__ void lm_tile_zero_live(const Lm8Params& p, int r0, int trows, int c0, int tid) {
@@ -680,6 +890,9 @@ __device__ __forceinline__ void lm_tile_zero_live(const Lm8Params& p, int r0, in
 template <bool SPLIT3 = false, bool GMAX = false, int EPI = EPI_LSE, int TI = 4>
 __global__ __launch_bounds__(256, 1) void lm_head_lse4w_kernel(const Lm8Params p) {
   static_assert(TI == 4 || (TI == 2 && EPI == EPI_LIVE), "the 128-row form has the EPI_LIVE epilogue only");
+  // the three epilogues whose rows go through the partition; the two of the MLP node write node-private buffers whose dead rows
+  // nobody reads: their skipping blocks return at once
+  constexpr bool LIVE = EPI == EPI_LIVE || EPI == EPI_LIVE_SWIGLU || EPI == EPI_LIVE_DSWIGLU;
   constexpr int NA = 2 * TI, NP = NA + 8;        // load pieces of 32 rows per K tile: NA of the A tile, then 8 of the B tile
   constexpr int NM = 4 * TI, NR = TI + 4;        // MFMAs and fragment reads per k-step
   // load pieces (NP per K tile and wave) issued in k-step 3 (right after the barrier) / 0 / 1 / 2: measured best of the placements
@@ -690,14 +903,15 @@ __global__ __launch_bounds__(256, 1) void lm_head_lse4w_kernel(const Lm8Params p
   const int wr = wave >> 1, wc = wave & 1;
   int mt, nt;
   int nlive = 0;
-  if constexpr (EPI == EPI_LIVE) {
+  if constexpr (LIVE) {
     // the live row-tile count is a device value: the banded order runs over the live tiles, the skipping tiles come last
     nlive = min(max(*p.n_live, 0), p.R);
     const unsigned NT = static_cast<unsigned>(p.NT), mtl = static_cast<unsigned>((nlive + 64 * TI - 1) / (64 * TI));
     const unsigned nlb = mtl * NT;
     if (blockIdx.x >= nlb) {
       const unsigned s = blockIdx.x - nlb;
-      lm_tile_zero_live(p, static_cast<int>(mtl + s / NT) * 64 * TI, 64 * TI, static_cast<int>(s % NT) * 256, tid);
+      if constexpr (EPI == EPI_LIVE)
+        lm_tile_zero_live(p, static_cast<int>(mtl + s / NT) * 64 * TI, 64 * TI, static_cast<int>(s % NT) * 256, tid);
       return;
     }
     const unsigned bands = (mtl + 7) / 8;
@@ -705,7 +919,8 @@ __global__ __launch_bounds__(256, 1) void lm_head_lse4w_kernel(const Lm8Params p
   } else {
     lm_tile_of(p, blockIdx.x, gridDim.x, mt, nt);
   }
-  const int r0 = mt * 64 * TI, c0 = nt * 256;
+  // EPI_LIVE_SWIGLU: a column tile is 128 activation columns - 128 gate rows and 128 up rows of W = [Wgate; Wup]
+  const int r0 = mt * 64 * TI, c0 = nt * (EPI == EPI_LIVE_SWIGLU ? 128 : 256);
   const __amdgpu_buffer_rsrc_t rsH = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.H), 0, static_cast<int>(p.bytesH), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.W), 0, static_cast<int>(p.bytesW), 0x00020000);
 
@@ -715,7 +930,7 @@ __global__ __launch_bounds__(256, 1) void lm_head_lse4w_kernel(const Lm8Params p
   unsigned voff[NP];
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
-    if constexpr (EPI == EPI_LIVE) {
+    if constexpr (LIVE) {
       // row gather: the A row of position i is perm[i]; a dead position gets row R = past the descriptor's range, reads zero
       if (q < NA) {
         const int i = r0 + q * 32 + srow;
@@ -729,7 +944,10 @@ __global__ __launch_bounds__(256, 1) void lm_head_lse4w_kernel(const Lm8Params p
     } else {
       voff[q] = static_cast<unsigned>(r0 + q * 32 + srow) * p.pitchH + schunk;
     }
-    voff[NA + q] = static_cast<unsigned>(c0 + q * 32 + srow) * p.pitchW + schunk;
+    if constexpr (EPI == EPI_LIVE_SWIGLU)   // pieces 0..3: gate rows c0 .., 4..7: up rows y_half + c0 .. (wave column 0 / 1)
+      voff[NA + q] = static_cast<unsigned>((q < 4 ? c0 + q * 32 : p.y_half + c0 + (q - 4) * 32) + srow) * p.pitchW + schunk;
+    else
+      voff[NA + q] = static_cast<unsigned>(c0 + q * 32 + srow) * p.pitchW + schunk;
   }
   const int wave_lds = wave * 1024;
 #define L4_DMA(BUF, Q, KSA, KSB) lds_dma16((Q) < NA ? rsH : rsW, lds + (BUF) * L8_BUF + (Q) * 4096 + wave_lds, voff[Q], (Q) < NA ? (KSA) : (KSB));
@@ -826,6 +1044,8 @@ __global__ __launch_bounds__(256, 1) void lm_head_lse4w_kernel(const Lm8Params p
   __builtin_amdgcn_s_barrier();
 
   if constexpr (EPI == EPI_LIVE) lm_tile_epilogue_live<TI>(p, acc, lds, r0, c0, nlive, wr, wc, tid);
+  else if constexpr (EPI == EPI_LIVE_SWIGLU) lm_tile_epilogue_live_swiglu(p, acc, lds, r0, c0, nlive, wr, wc, tid);
+  else if constexpr (EPI == EPI_LIVE_DSWIGLU) lm_tile_epilogue_live_dswiglu(p, acc, lds, r0, c0, nlive, wr, wc, tid);
   else if constexpr (EPI == EPI_DS3) lm_tile_epilogue_ds3(p, acc, lds, r0, c0, wr, wc, tid);
   else if constexpr (EPI == EPI_DLOGITS) lm_tile_epilogue_dlogits<false>(p, acc, lds, r0, c0, wr, wc, tid);
   else if constexpr (EPI == EPI_LOGITS) lm_tile_epilogue_dlogits<true>(p, acc, lds, r0, c0, wr, wc, tid);
@@ -1474,5 +1694,105 @@ extern "C" int dalm_linear_live(const void* A, int64_t lda, const void* W, void*
     hipLaunchKernelGGL((lm_head_lse4w_kernel<false, false, EPI_LIVE, 4>), grid, dim3(256), 0, as_stream(stream), q);
   else
     hipLaunchKernelGGL((lm_head_lse4w_kernel<false, false, EPI_LIVE, 2>), grid, dim3(256), 0, as_stream(stream), q);
+  return check_launch(__func__);
+}
+
+// ---- the frozen SwiGLU MLP node of the padded step: SwiGLU inside the epilogues of its live-row GEMMs --------------------------
+namespace {
+// the operand checks and parameters the two entry points share with dalm_linear_live: A [R, K] (stride lda) against W [N, K]
+int linear_live_mlp_params(Lm8Params& q, const char* fn, const void* A, int64_t lda, const void* W, int64_t R, int64_t N, int64_t K,
+                           int64_t w_rows, int tile_cols, const int32_t* perm, const int32_t* n_live) {
+#define MLP_REQUIRE(cond, code, what) do { if (!(cond)) return ::dalm::fail((code), fn, (what)); } while (0)
+  MLP_REQUIRE(R > 0 && N > 0 && K > 0 && K % 64 == 0 && N % 8 == 0, DALM_E_SHAPE,
+               "need R, C, K > 0, K a multiple of 64 and C a multiple of 8");
+  MLP_REQUIRE(lda >= K && lda % 8 == 0, DALM_E_SHAPE, "row strides: lda >= K, a multiple of 8 elements");
+  MLP_REQUIRE(R <= 0x7fffff00ll && w_rows <= 0x7fffff00ll && lda <= 0x7fffffffll, DALM_E_SHAPE,
+               "operands above 4 GB: use fewer rows per call");
+  const uint64_t spanA = static_cast<uint64_t>(R + 256) * lda * 2, spanW = static_cast<uint64_t>(w_rows + 256) * K * 2;
+  MLP_REQUIRE(spanA < 0xffffff00ull && spanW < 0xffffff00ull, DALM_E_SHAPE, "operands above 4 GB: use fewer rows per call");
+  q.H = A; q.W = W; q.labels = nullptr; q.K = static_cast<int>(K);
+  q.R = static_cast<int>(R); q.V = static_cast<int>(N);
+  q.MT = static_cast<int>((R + 255) / 256); q.NT = static_cast<int>((N + tile_cols - 1) / tile_cols);
+  q.xcd_order = 1; q.gh = 1;
+  q.tpd = 0; q.tpd_inv = 0; q.seg_bytes = 0; q.gmax = nullptr; q.ng = 0;
+  q.pm = q.pl = q.z = nullptr;
+  q.bytesH = static_cast<unsigned>(static_cast<uint64_t>(R - 1) * lda * 2 + static_cast<uint64_t>(K) * 2);
+  q.bytesW = static_cast<unsigned>(static_cast<uint64_t>(w_rows) * K * 2);
+  q.pitchH = static_cast<unsigned>(lda * 2); q.pitchW = static_cast<unsigned>(K * 2);
+  q.row_lse = nullptr; q.coef = nullptr;
+  q.out_cols = static_cast<int>(N); q.accumulate = 0;
+  q.perm = perm; q.n_live = n_live;
+  MLP_REQUIRE(static_cast<int64_t>(q.MT) * q.NT <= 0x7fffffffll, DALM_E_SHAPE, "too many tiles for one launch");
+  return DALM_OK;
+#undef MLP_REQUIRE
+}
+}  // namespace
+
+namespace {
+// The silu table of the current device: filled on the first call, outside any stream capture, and complete (the stream is drained)
+// before the flag is set - a later call from any stream finds it whole.
+std::atomic<int> g_silu_tab_ready[64];
+std::mutex g_silu_tab_mutex;
+int ensure_silu_table(const char* fn, dalm_stream_t stream) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return ::dalm::fail(static_cast<int>(hipErrorInvalidDevice), fn, "no current device");
+  if (g_silu_tab_ready[dev].load(std::memory_order_acquire)) return DALM_OK;
+  std::lock_guard<std::mutex> lock(g_silu_tab_mutex);
+  if (g_silu_tab_ready[dev].load(std::memory_order_acquire)) return DALM_OK;
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(as_stream(stream), &st) != hipSuccess || st != hipStreamCaptureStatusNone)
+    return ::dalm::fail(static_cast<int>(hipErrorStreamCaptureUnsupported), fn,
+                        "the silu table of this device is not filled yet: call dalm_linear_live_swiglu_prepare outside a stream capture first");
+  hipLaunchKernelGGL(silu_table_kernel, dim3(256), dim3(256), 0, as_stream(stream));
+  const hipError_t e = hipStreamSynchronize(as_stream(stream));
+  if (e != hipSuccess) return ::dalm::fail(static_cast<int>(e), fn, hipGetErrorString(e));
+  g_silu_tab_ready[dev].store(1, std::memory_order_release);
+  return DALM_OK;
+}
+}  // namespace
+
+extern "C" int dalm_linear_live_swiglu_prepare(dalm_stream_t stream) { return ensure_silu_table(__func__, stream); }
+
+extern "C" int dalm_linear_live_swiglu(const void* A, int64_t lda, const void* Wcat, void* Y, int64_t ldy, void* Act, int64_t ldact,
+                                       int64_t R, int64_t C, int64_t K, const int32_t* perm, const int32_t* n_live,
+                                       dalm_stream_t stream) {
+  DALM_REQUIRE(A && Wcat && Y && Act && perm && n_live, DALM_E_NULL, "null pointer argument");
+  DALM_REQUIRE(C > 0 && C % 128 == 0, DALM_E_SHAPE, "need C a positive multiple of 128 (a column tile is 128 gate and 128 up rows)");
+  DALM_REQUIRE(ldy >= 2 * C && ldact >= C && ldy % 8 == 0 && ldact % 8 == 0 && ldy <= 0x7fffffffll && ldact <= 0x7fffffffll,
+               DALM_E_SHAPE, "row strides: ldy >= 2 C, ldact >= C, both multiples of 8 elements");
+  DALM_REQUIRE(reinterpret_cast<uintptr_t>(A) % 16 == 0 && reinterpret_cast<uintptr_t>(Wcat) % 16 == 0 &&
+               reinterpret_cast<uintptr_t>(Y) % 16 == 0 && reinterpret_cast<uintptr_t>(Act) % 16 == 0, DALM_E_ALIGN,
+               "A / Wcat / Y / Act must be 16-byte aligned");
+  Lm8Params q;
+  const int rc = linear_live_mlp_params(q, __func__, A, lda, Wcat, R, C, K, 2 * C, 128, perm, n_live);
+  if (rc != DALM_OK) return rc;
+  q.out = Y; q.out_pitch = ldy;
+  q.y = Y; q.y_pitch = ldy; q.y_half = static_cast<int>(C);
+  q.out2 = Act; q.out2_pitch = ldact;
+  const int tab = ensure_silu_table(__func__, stream);
+  if (tab != DALM_OK) return tab;
+  hipLaunchKernelGGL((lm_head_lse4w_kernel<false, false, EPI_LIVE_SWIGLU, 4>), dim3(static_cast<unsigned>(q.MT) * q.NT), dim3(256), 0,
+                     as_stream(stream), q);
+  return check_launch(__func__);
+}
+
+extern "C" int dalm_linear_live_dswiglu(const void* dOut, int64_t ldd, const void* WdT, const void* Y, int64_t ldy, void* dG,
+                                        int64_t lddg, void* dU, int64_t lddu, int64_t R, int64_t C, int64_t H, const int32_t* perm,
+                                        const int32_t* n_live, dalm_stream_t stream) {
+  DALM_REQUIRE(dOut && WdT && Y && dG && dU && perm && n_live, DALM_E_NULL, "null pointer argument");
+  DALM_REQUIRE(C > 0 && ldy >= 2 * C && lddg >= C && lddu >= C && ldy % 8 == 0 && lddg % 8 == 0 && lddu % 8 == 0 &&
+               ldy <= 0x7fffffffll && lddg <= 0x7fffffffll && lddu <= 0x7fffffffll, DALM_E_SHAPE,
+               "row strides: ldy >= 2 C, lddg >= C, lddu >= C, all multiples of 8 elements");
+  DALM_REQUIRE(reinterpret_cast<uintptr_t>(dOut) % 16 == 0 && reinterpret_cast<uintptr_t>(WdT) % 16 == 0 &&
+               reinterpret_cast<uintptr_t>(Y) % 16 == 0 && reinterpret_cast<uintptr_t>(dG) % 16 == 0 &&
+               reinterpret_cast<uintptr_t>(dU) % 16 == 0, DALM_E_ALIGN, "dOut / WdT / Y / dG / dU must be 16-byte aligned");
+  Lm8Params q;
+  const int rc = linear_live_mlp_params(q, __func__, dOut, ldd, WdT, R, C, H, C, 256, perm, n_live);
+  if (rc != DALM_OK) return rc;
+  q.out = dG; q.out_pitch = lddg;
+  q.y = Y; q.y_pitch = ldy; q.y_half = static_cast<int>(C);
+  q.out2 = dU; q.out2_pitch = lddu;
+  hipLaunchKernelGGL((lm_head_lse4w_kernel<false, false, EPI_LIVE_DSWIGLU, 4>), dim3(static_cast<unsigned>(q.MT) * q.NT), dim3(256),
+                     0, as_stream(stream), q);
   return check_launch(__func__);
 }

@@ -19,6 +19,7 @@
 // Further down: RMSNorm with the residual add (dalm_rms_norm_*), Qwen3's head norm + rotary (dalm_head_norm_*), and Gemma's two
 // formulas - GeGLU and the (1 + w) RMSNorm (dalm_geglu_*, dalm_gemma_norm_*) - each with its own comment block.
 #include "dispatch.hpp"
+#include "swiglu_math.hpp"
 #include "vec16.hpp"
 
 namespace dalm {
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(256) void rope_qk_kernel(const RopeParams p) {
 // SwiGLU over n contiguous elements.  A workgroup walks STEPS tiles of 256*VEC elements with every load issued before the
 // first store (single-tile workgroups are bound by workgroup dispatch at this size: profiles/history/r04_nf4_steps.txt).
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float silu_f32(float x) { return x / (1.0f + expf(-x)); }
+// (the element arithmetic - silu_f32, swiglu_fwd_elem, swiglu_bwd_elem - is swiglu_math.hpp's: the live-row GEMM epilogues share it)
 
 // [R, C] views with a row stride (gate and up as the two halves of ONE [R, 2C] GEMM output, models/frozen_linear.py): element
 // e of the logical [R, C] matrix lives at (e / C) * ld + e % C; C is a multiple of VEC, so a vector never crosses a row
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(256) void swiglu_fwd_2d_kernel(const T* __restrict_
     float o[VEC];
     if (lv[k]) {
 #pragma unroll
-      for (int e = 0; e < VEC; ++e) o[e] = Vec16<T>::rb(__fmul_rn(Vec16<T>::rb(silu_f32(gv[k][e])), uv[k][e]));
+      for (int e = 0; e < VEC; ++e) o[e] = swiglu_fwd_elem<Vec16<T>>(gv[k][e], uv[k][e]);
     } else {                                                         // a dead row: nothing was loaded, zeros leave
 #pragma unroll
       for (int e = 0; e < VEC; ++e) o[e] = 0.f;
@@ -195,14 +196,7 @@ __global__ __launch_bounds__(256) void swiglu_bwd_2d_kernel(const T* __restrict_
     float og[VEC], ou[VEC];
     if (lv[k]) {
 #pragma unroll
-      for (int e = 0; e < VEC; ++e) {                                // the contiguous kernel's arithmetic, statement for statement
-        const float x = gv[k][e];
-        const float s = Vec16<T>::rb(silu_f32(x));
-        const float ds = Vec16<T>::rb(__fmul_rn(av[k][e], uv[k][e]));
-        ou[e] = Vec16<T>::rb(__fmul_rn(av[k][e], s));
-        const float sig = 1.0f / (1.0f + expf(-x));
-        og[e] = Vec16<T>::rb(ds * sig * (1.0f + x * (1.0f - sig)));
-      }
+      for (int e = 0; e < VEC; ++e) swiglu_bwd_elem<Vec16<T>>(av[k][e], gv[k][e], uv[k][e], og[e], ou[e]);
     } else {
 #pragma unroll
       for (int e = 0; e < VEC; ++e) { og[e] = 0.f; ou[e] = 0.f; }
@@ -236,7 +230,7 @@ __global__ __launch_bounds__(256) void swiglu_fwd_kernel(const T* __restrict__ g
     if (e0 >= n) continue;
     float o[VEC];
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) o[e] = Vec16<T>::rb(__fmul_rn(Vec16<T>::rb(silu_f32(gv[k][e])), uv[k][e]));
+    for (int e = 0; e < VEC; ++e) o[e] = swiglu_fwd_elem<Vec16<T>>(gv[k][e], uv[k][e]);
     if (e0 + VEC <= n) Vec16<T>::store(a + e0, o);
     else
       for (int e = 0; e < VEC && e0 + e < n; ++e) Vec16<T>::put(a + e0 + e, o[e]);
@@ -270,14 +264,7 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const T* __restrict__ d
     if (e0 >= n) continue;
     float og[VEC], ou[VEC];
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      const float x = gv[k][e];
-      const float s = Vec16<T>::rb(silu_f32(x));                       // the activation the eager chain saved
-      const float ds = Vec16<T>::rb(__fmul_rn(av[k][e], uv[k][e]));
-      ou[e] = Vec16<T>::rb(__fmul_rn(av[k][e], s));
-      const float sig = 1.0f / (1.0f + expf(-x));
-      og[e] = Vec16<T>::rb(ds * sig * (1.0f + x * (1.0f - sig)));      // torch's silu_backward expression, contraction as compiled
-    }
+    for (int e = 0; e < VEC; ++e) swiglu_bwd_elem<Vec16<T>>(av[k][e], gv[k][e], uv[k][e], og[e], ou[e]);
     if (e0 + VEC <= n) { Vec16<T>::store(dg + e0, og); Vec16<T>::store(du + e0, ou); }
     else
       for (int e = 0; e < VEC && e0 + e < n; ++e) { Vec16<T>::put(dg + e0 + e, og[e]); Vec16<T>::put(du + e0 + e, ou[e]); }

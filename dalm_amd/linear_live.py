@@ -31,6 +31,11 @@ ROUTED_SHAPES = frozenset({
 # the kernel is faster there too, but not by three spreads of the library arm at every mask in every run of the bench.
 
 _enabled = True
+_mlp_fused = True
+# the backward piece (dalm_linear_live_dswiglu) did not clear its gate in tools/linear_live_bench.py --mlp-fused: two exps and two
+# IEEE divisions per element in an epilogue that runs one wave per SIMD cost more than the d_act round trip saves.
+# The node therefore runs the down dgrad and dalm_swiglu_bwd_2d_live as two launches unless this is set (tests, the bench).
+_mlp_fused_backward = False
 _table = ROUTED_SHAPES
 _calls = 0
 
@@ -43,6 +48,28 @@ def set_enabled(on: bool) -> None:
 
 def enabled() -> bool:
     return _enabled
+
+
+def set_mlp_fused(on: bool) -> None:
+    """Turn the fused frozen-MLP node on or off (A/B tools, tests); off = the three projections and the SwiGLU kernels run as
+    separate nodes, as before.  A function, not an environment variable: same bits either way, nothing a deployment selects."""
+    global _mlp_fused
+    _mlp_fused = bool(on)
+
+
+def mlp_fused() -> bool:
+    return _mlp_fused
+
+
+def set_mlp_fused_backward(on: bool) -> None:
+    """Let the fused node run its backward through `dalm_linear_live_dswiglu` too (off by default: measured slower than the pair of
+    launches it replaces; same bits either way)."""
+    global _mlp_fused_backward
+    _mlp_fused_backward = bool(on)
+
+
+def mlp_fused_backward() -> bool:
+    return _mlp_fused_backward
 
 
 def set_table(shapes: Optional[Iterable[Tuple[int, int, int]]]) -> None:
@@ -72,6 +99,32 @@ def routed(rows: int, n: int, k: int, dtype: torch.dtype, has_bias: bool, have_p
     """The routing predicate: bf16 compute, no bias, a partition that describes the rows, and a shape in the table."""
     return (_enabled and have_partition and not has_bias and dtype == torch.bfloat16 and shape_ok(rows, n, k)
             and (rows, n, k) in _table)
+
+
+_mlp_prepared: set = set()
+
+
+def mlp_prepare(device) -> bool:
+    """Fill the forward epilogue's silu table on `device` (once; synchronises the current stream).  False while a stream capture is
+    in progress and the table is not there yet: the caller keeps the unfused kernels for this call."""
+    device = torch.device(device)
+    if device in _mlp_prepared:
+        return True
+    if torch.cuda.is_current_stream_capturing():
+        return False
+    with torch.cuda.device(device):
+        hip.call("dalm_linear_live_swiglu_prepare", hip.stream())
+    _mlp_prepared.add(device)
+    return True
+
+
+def mlp_routed(rows: int, c: int, h: int, dtype: torch.dtype, has_bias: bool, have_partition: bool) -> bool:
+    """The frozen SwiGLU MLP (hidden h, intermediate c) as ONE node around `linear_live_swiglu` / `linear_live_dswiglu`: the switch,
+    128-column mixed tiles, and ALL four GEMM shapes of the node in the table - gate | up forward, down forward, down dgrad, gate
+    and up dgrad (the last two share one shape)."""
+    if not (_mlp_fused and c > 0 and c % 128 == 0):
+        return False
+    return all(routed(rows, n, k, dtype, has_bias, have_partition) for n, k in ((2 * c, h), (h, c), (c, h)))
 
 
 def _operand_ok(t: torch.Tensor) -> bool:
@@ -140,6 +193,57 @@ def linear_live(a: torch.Tensor, w: torch.Tensor, part, out: Optional[torch.Tens
                  hip.ptr(n_live), int(bool(accumulate)), int(form), hip.stream())
     _calls += 1
     return out
+
+
+def _check_part(part, rows: int):
+    perm, n_live = part
+    if perm.numel() != rows or perm.dtype != torch.int32 or n_live.dtype != torch.int32:
+        raise ValueError("linear_live: the partition does not describe these rows")
+    return perm, n_live
+
+
+def linear_live_swiglu(a: torch.Tensor, wcat: torch.Tensor, part):
+    """(y, act) for the live rows of `part`: y[r] = a[r] . wcat^T with wcat = [Wgate; Wup] [2C, K], act[r] = silu(y[r, :C]) * y[r, C:]
+    - the bits of `linear_live` followed by `dalm_swiglu_fwd_2d_live`.  Dead rows of BOTH outputs are NOT written (torch.empty):
+    the buffers are meant to stay inside one autograd node."""
+    global _calls
+    rows, k = a.shape
+    c = wcat.shape[0] // 2
+    perm, n_live = _check_part(part, rows)
+    hip.require_gpu(a, wcat, perm, n_live)
+    if not mlp_prepare(a.device):
+        raise RuntimeError("linear_live_swiglu: first use on this device inside a stream capture (call linear_live.mlp_prepare before)")
+    if not (_operand_ok(a) and wcat.dtype == torch.bfloat16 and wcat.is_contiguous()) or wcat.shape != (2 * c, k):
+        raise TypeError("linear_live_swiglu: bf16 a [R, K] with unit column stride and contiguous wcat [2C, K] expected")
+    y = torch.empty((rows, 2 * c), dtype=torch.bfloat16, device=a.device)
+    act = torch.empty((rows, c), dtype=torch.bfloat16, device=a.device)
+    with torch.cuda.device(a.device):
+        hip.call("dalm_linear_live_swiglu", hip.ptr(a), a.stride(0), hip.ptr(wcat), hip.ptr(y), 2 * c, hip.ptr(act), c, rows, c, k,
+                 hip.ptr(perm), hip.ptr(n_live), hip.stream())
+    _calls += 1
+    return y, act
+
+
+def linear_live_dswiglu(d_out: torch.Tensor, wdt: torch.Tensor, y: torch.Tensor, part):
+    """(d_gate, d_up) [R, C] each for the live rows of `part`: d_act = d_out . wdt^T (wdt [C, H] = the transposed down weight) goes
+    through the SwiGLU backward with y = [gate | up] inside the GEMM's epilogue - the bits of `linear_live` followed by
+    `dalm_swiglu_bwd_2d_live`; d_act is never stored.  Dead rows of the outputs are NOT written."""
+    global _calls
+    rows, h = d_out.shape
+    c = wdt.shape[0]
+    perm, n_live = _check_part(part, rows)
+    hip.require_gpu(d_out, wdt, y, perm, n_live)
+    if not (_operand_ok(d_out) and _operand_ok(y) and wdt.dtype == torch.bfloat16 and wdt.is_contiguous()):
+        raise TypeError("linear_live_dswiglu: bf16 operands with unit column stride expected (wdt contiguous)")
+    if wdt.shape != (c, h) or y.shape != (rows, 2 * c):
+        raise ValueError("linear_live_dswiglu: inconsistent shapes")
+    dg = torch.empty((rows, c), dtype=torch.bfloat16, device=d_out.device)
+    du = torch.empty((rows, c), dtype=torch.bfloat16, device=d_out.device)
+    with torch.cuda.device(d_out.device):
+        hip.call("dalm_linear_live_dswiglu", hip.ptr(d_out), d_out.stride(0), hip.ptr(wdt), hip.ptr(y), y.stride(0), hip.ptr(dg), c,
+                 hip.ptr(du), c, rows, c, h, hip.ptr(perm), hip.ptr(n_live), hip.stream())
+    _calls += 1
+    return dg, du
 
 
 # ---- tile accounting (pure Python: the estimate table of DESIGN.md, and the bench's FLOP column) -------------------------------

@@ -227,6 +227,9 @@ def _swiglu_mlp_forward(self, x):
 
     from . import frozen_linear
 
+    out = frozen_linear.swiglu_mlp_forward(x, self.gate_proj, self.up_proj, self.down_proj)   # padded step, all frozen: one node
+    if out is not None:
+        return out
     gate, up = frozen_linear.pair_forward(x, self.gate_proj, self.up_proj)   # frozen: one node, the two dx GEMMs accumulate
     if tower_ops.swiglu_supported(gate, up):
         return self.down_proj(tower_ops.swiglu(gate, up))

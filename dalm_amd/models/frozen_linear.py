@@ -308,6 +308,119 @@ class _FrozenCatPairFn(torch.autograd.Function):
         return _FrozenPairFn.backward(ctx, g0, g1) + (None,)
 
 
+class _FrozenSwigluMlpFn(torch.autograd.Function):
+    """down(silu(gate(x)) * up(x)) with all three projections frozen, inside a padded tower call, as ONE node: the SwiGLU forward
+    runs in the epilogue of the gate | up GEMM (dalm_amd/linear_live.py); its backward can run in the epilogue of the down dgrad
+    GEMM, but that piece measured slower than the two launches it replaces and is off by default.
+    y = [gate | up], act, d_gate and d_up never leave the node, so their dead rows are never written - nobody reads them: every
+    consumer is a live-row GEMM whose A gather skips them.  The output and dx leave the node and keep zeros in their dead rows.
+    Same bits as the separate nodes: same contraction order, same element arithmetic (csrc/swiglu_math.hpp)."""
+
+    @staticmethod
+    def forward(ctx, x, cat, w0, w1, wd, part):
+        from .. import linear_live, live_rows
+
+        x2 = x.reshape(-1, cat.shape[1])
+        y, act = linear_live.linear_live_swiglu(x2, cat, part)
+        out = linear_live.linear_live(act, wd, part)            # leaves the node: zeros for the dead rows
+        ctx.save_for_backward(y)                                # act is not needed again: every weight is frozen
+        ctx.part, ctx.w, ctx.wd = part, (w0, w1), wd
+        ctx.live = live_rows.current(x2.shape[0], x2.device)    # the vector behind `part`, for the row-wise backward kernel
+        ctx.xshape = x.shape
+        return out.view(*x.shape[:-1], wd.shape[0])
+
+    @staticmethod
+    def backward(ctx, g):
+        from .. import linear_live
+
+        (y,) = ctx.saved_tensors
+        w0, w1 = ctx.w
+        part = ctx.part
+        g2 = g.reshape(-1, ctx.wd.shape[0])
+        if g2.dtype != torch.bfloat16:
+            g2 = g2.to(torch.bfloat16)
+        if g2.stride(-1) != 1 or g2.stride(0) % 8 or g2.data_ptr() % 16:
+            g2 = g2.contiguous()
+        wdt, wt0, wt1 = (dgrad_weight(w, torch.bfloat16) for w in (ctx.wd, w0, w1))
+        if wdt is not None and wt0 is not None and wt1 is not None:
+            if linear_live.mlp_fused_backward():
+                dg, du = linear_live.linear_live_dswiglu(g2, wdt, y, part)
+            else:
+                # the backward epilogue did not clear its gate (linear_live._mlp_fused_backward): the two launches it would replace
+                from .. import hip
+
+                c = w0.shape[0]
+                d_act = linear_live.linear_live(g2, wdt, part)
+                dg, du = torch.empty_like(d_act), torch.empty_like(d_act)
+                hip.call("dalm_swiglu_bwd_2d_live", hip.ptr(d_act), hip.ptr(y), hip.ptr(y[:, c:]), hip.ptr(dg), hip.ptr(du),
+                         hip.dtype_code(y), y.shape[0], c, c, 2 * c, 2 * c, c, c, hip.ptr(ctx.live), hip.stream())
+            dx = linear_live.linear_live(dg, wt0, part)                      # as _FrozenPairFn.backward: fresh, zeros for dead rows,
+            dx = linear_live.linear_live(du, wt1, part, out=dx, accumulate=True)    # then accumulated in f32 with one rounding
+            return dx.view(ctx.xshape), None, None, None, None, None
+        raise RuntimeError("frozen SwiGLU MLP node: the transposed dgrad copies of its weights are missing (make them outside a "
+                           "graph capture: frozen_linear.dgrad_weight)")
+
+
+def swiglu_mlp_candidate(x: torch.Tensor, gate_proj, up_proj, down_proj):
+    """The part of the routing predicate that needs no device (meta tensors will do): (rows, C, H) when the switches are on, the
+    three projections are plain, bias-free, frozen and bf16 like x, the shapes are those of one gated MLP, C % 128 == 0 and all
+    four GEMM shapes of the node are in linear_live's table; else None."""
+    from .. import linear_live
+
+    if not (linear_live.enabled() and linear_live.mlp_fused()):
+        return None
+    plain = (torch.nn.Linear, FrozenLinearT)
+    mods = (gate_proj, up_proj, down_proj)
+    if any(type(m) not in plain or m.bias is not None or m.weight.requires_grad for m in mods):
+        return None
+    if x.dtype != torch.bfloat16 or any(m.weight.dtype != torch.bfloat16 or m.weight.dim() != 2 for m in mods):
+        return None
+    c, h = gate_proj.weight.shape
+    if up_proj.weight.shape != (c, h) or down_proj.weight.shape != (h, c) or x.dim() < 2 or x.shape[-1] != h:
+        return None
+    rows = x.numel() // h
+    if not linear_live.mlp_routed(rows, c, h, x.dtype, False, True):
+        return None
+    return rows, c, h
+
+
+def swiglu_mlp_route(x: torch.Tensor, gate_proj, up_proj, down_proj):
+    """The routing predicate of `swiglu_mlp_forward`: (cat, partition) when the call goes to the fused node, else None."""
+    from .. import linear_live
+
+    cand = swiglu_mlp_candidate(x, gate_proj, up_proj, down_proj)
+    if cand is None or not _eligible(x, gate_proj, up_proj, down_proj):
+        return None
+    cat = _cat_weights(gate_proj, up_proj)
+    if cat is None:
+        return None
+    x2 = x.reshape(-1, cand[2])
+    wd = down_proj.weight
+    if not (linear_live.accepts(x2, cat, False) and wd.is_contiguous() and wd.data_ptr() % 16 == 0 and wd.device == x.device):
+        return None
+    part = linear_live.route(x2, cat, False)             # None outside a padded tower call
+    if part is None:
+        return None
+    if not linear_live.mlp_prepare(x.device):            # the forward epilogue's silu table: not inside a capture the first time
+        return None
+    # the backward needs the three transposed copies; a first request from inside a graph capture cannot make them
+    if any(dgrad_weight(m.weight, torch.bfloat16) is None for m in (gate_proj, up_proj, down_proj)):
+        return None
+    return cat, part
+
+
+def swiglu_mlp_forward(x: torch.Tensor, gate_proj, up_proj, down_proj):
+    """down_proj(silu(gate_proj(x)) * up_proj(x)) through `_FrozenSwigluMlpFn`, or None when the call does not route (the caller then
+    runs the separate nodes): linear_live on with a padded tower call in progress and a partition of these rows, bf16, no biases,
+    three frozen plain projections whose gate | up weights share one tensor, C % 128 == 0, all four GEMM shapes in linear_live's
+    table, and `linear_live.set_mlp_fused` on."""
+    r = swiglu_mlp_route(x, gate_proj, up_proj, down_proj)
+    if r is None:
+        return None
+    cat, part = r
+    return _FrozenSwigluMlpFn.apply(x, cat, gate_proj.weight, up_proj.weight, down_proj.weight, part)
+
+
 def _eligible(x: torch.Tensor, *mods) -> bool:
     if not (x.is_cuda and torch.is_grad_enabled() and x.requires_grad):
         return False

@@ -1,6 +1,7 @@
 """Kernel bench of `dalm_linear_live` against the tuned library GEMMs at the padded cfg3 step's generator shapes.
 
     python tools/linear_live_bench.py [--out profiles/linear_live_bench.txt] [--quick]
+    python tools/linear_live_bench.py --mlp-fused [--out profiles/mlp_fused_bench.txt]
 
 The seven GEMMs of one Llama-2-7b layer and the two of the materialised lm_head at R = 4608 padded rows (18 x 256), each with
   * every row live, and the four masks of `bench.synthetic_batch(dev, 100 + i)` under the generator's shifted rule;
@@ -10,6 +11,11 @@ Every arm is timed inside a hipGraph of LAUNCHES (>= 20) launches, over a ring o
 FLOP are counted over LIVE rows (2 live N K), `frac` is against the bf16 MFMA peak - for the library arm too, so its frac at a
 padded mask shows what the padding costs.  `win` marks a kernel arm faster than the library arm by more than three times the
 larger of the two spreads: the routing table in dalm_amd/linear_live.py lists exactly those shapes.
+
+--mlp-fused: the two fused pieces of the frozen MLP node against the pairs of launches they replace, same protocol and same rule -
+  forward   {dalm_linear_live gate|up + dalm_swiglu_fwd_2d_live}   against dalm_linear_live_swiglu,
+  backward  {dalm_linear_live down dgrad + dalm_swiglu_bwd_2d_live} against dalm_linear_live_dswiglu,
+at the four batch masks.  A piece ships only if it beats its pair by more than three times the larger spread at EVERY mask.
 """
 from __future__ import annotations
 
@@ -124,11 +130,73 @@ def bench_gemm(members, halves, mask_list, dev, emit):
     return rows
 
 
+def bench_mlp_fused(mask_list, dev, emit, c=11008, h=4096):
+    """The two paired arms of the fused MLP node; returns {piece: ships?}."""
+    from dalm_amd import hip
+
+    gen = torch.Generator(device=dev).manual_seed(11)
+    ring_f = max(2, min(LAUNCHES, RING_BYTES // (2 * c * h * 2) + 1))
+    ring_b = max(2, min(LAUNCHES, RING_BYTES // (c * h * 2) + 1))
+    wcat = [(torch.randn(2 * c, h, device=dev, generator=gen) * 0.02).bfloat16() for _ in range(ring_f)]
+    wdt = [(torch.randn(c, h, device=dev, generator=gen) * 0.02).bfloat16() for _ in range(ring_b)]
+    x = torch.randn(R, h, device=dev, generator=gen).bfloat16()
+    d_out = torch.randn(R, h, device=dev, generator=gen).bfloat16()
+    y = torch.zeros(R, 2 * c, dtype=torch.bfloat16, device=dev)
+    act, d_act, dg, du = (torch.zeros(R, c, dtype=torch.bfloat16, device=dev) for _ in range(4))
+    dt = hip.dtype_code(y)
+    ships = {"forward": True, "backward": True}
+    for mname, vec in mask_list:
+        part = linear_live.row_partition(vec)
+        n_live = int(part[1].item())
+        perm, nl = hip.ptr(part[0]), hip.ptr(part[1])
+
+        def fwd_pair(i):
+            linear_live.linear_live(x, wcat[i % ring_f], part, out=y)
+            hip.call("dalm_swiglu_fwd_2d_live", hip.ptr(y), hip.ptr(y[:, c:]), hip.ptr(act), dt, R, c, 2 * c, 2 * c, c, hip.ptr(vec),
+                     hip.stream())
+
+        def fwd_fused(i):
+            hip.call("dalm_linear_live_swiglu", hip.ptr(x), h, hip.ptr(wcat[i % ring_f]), hip.ptr(y), 2 * c, hip.ptr(act), c, R, c, h,
+                     perm, nl, hip.stream())
+
+        def bwd_pair(i):
+            linear_live.linear_live(d_out, wdt[i % ring_b], part, out=d_act)
+            hip.call("dalm_swiglu_bwd_2d_live", hip.ptr(d_act), hip.ptr(y), hip.ptr(y[:, c:]), hip.ptr(dg), hip.ptr(du), dt, R, c, c,
+                     2 * c, 2 * c, c, c, hip.ptr(vec), hip.stream())
+
+        def bwd_fused(i):
+            hip.call("dalm_linear_live_dswiglu", hip.ptr(d_out), h, hip.ptr(wdt[i % ring_b]), hip.ptr(y), 2 * c, hip.ptr(dg), c,
+                     hip.ptr(du), c, R, c, h, perm, nl, hip.stream())
+
+        for piece, pair, fused, n in (("forward", fwd_pair, fwd_fused, 2 * c), ("backward", bwd_pair, bwd_fused, c)):
+            (tp, sp), (tf, sf) = time_graph(pair), time_graph(fused)
+            win = tp - tf > 3 * max(sp, sf)
+            ships[piece] = ships[piece] and (win or mname == "all live")
+            fl = linear_live.flops(n_live, n, h)
+            emit(f"  {mname:10s} live {n_live:5d}  {piece:8s} pair {tp * 1e6:8.1f} us (spread {sp * 1e6:5.1f})  fused {tf * 1e6:8.1f} us "
+                 f"(spread {sf * 1e6:5.1f})  saves {(tp - tf) * 1e6:7.1f} us  fused {fl / tf / 1e12:7.1f} TF/s  {'win' if win else '-'}")
+    return ships
+
+
+def main_mlp_fused(args, dev, emit, lines):
+    ml = masks(dev)
+    emit("mlp_fused: {dalm_linear_live + dalm_swiglu_*_2d_live} against the fused entry point, C = 11008, H = 4096")
+    ships = bench_mlp_fused(ml, dev, emit)
+    emit("verdict (fused faster than its pair by > 3 x the larger spread, at all four batch masks):")
+    for piece, ok in ships.items():
+        emit(f"  {piece:8s}: {'ships' if ok else 'does NOT clear the rule: the node keeps the unfused kernels for this direction'}")
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "linear_live_bench.txt"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--mlp-fused", action="store_true", help="the paired arms of the fused MLP node only")
     ap.add_argument("--quick", action="store_true", help="all-live and one batch mask only")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = str(ROOT / "profiles" / ("mlp_fused_bench.txt" if args.mlp_fused else "linear_live_bench.txt"))
     if not torch.cuda.is_available():
         raise SystemExit("linear_live_bench needs the GPU: there is no CPU timing of a HIP kernel")
     dev = torch.device("cuda")
@@ -147,6 +215,8 @@ def main():
     for _ in range(300):                                   # clocks up before the first timed arm
         warm = F.linear(warm, warm) * 0.01
     torch.cuda.synchronize()
+    if args.mlp_fused:
+        return main_mlp_fused(args, dev, emit, lines)
     ml = masks(dev)
     if args.quick:
         ml = ml[:2]
