@@ -22,7 +22,7 @@ from pathlib import Path
 
 CSRC = Path(__file__).resolve().parent / "csrc"
 LIB = CSRC / "libdalm_hip.so"
-SOURCES = ["lib.hip", "ce.hip", "sim.hip", "sim_small.hip", "pool.hip", "comm.hip", "lmhead.hip", "nf4.hip", "tower.hip", "falcon.hip", "attn.hip", "lora.hip", "lora2.hip", "bert.hip"]
+SOURCES = ["lib.hip", "ce.hip", "sim.hip", "sim_small.hip", "pool.hip", "comm.hip", "lmhead.hip", "sim_x3.hip", "linear_live.hip", "nf4.hip", "tower.hip", "falcon.hip", "attn.hip", "lora.hip", "lora2.hip", "bert.hip"]
 HEADERS = [*sorted(CSRC.glob("*.hpp")), CSRC.parent.parent / "include" / "dalm_hip.h"]   # every header: none can be forgotten
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC"]

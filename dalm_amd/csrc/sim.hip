@@ -1123,7 +1123,7 @@ extern "C" int dalm_sim_matmul(const float* A, const float* Bm, int64_t m, int64
   return dalm_gemm_f32(0, 1, m, n, D, scale, A, D, Bm, D, S, ldS, stream);
 }
 
-// Problems large enough for the bf16x3 form (csrc/lmhead.hip: 256 x 256 tiles, a few waves of them over the 256 CUs) go to
+// Problems large enough for the bf16x3 form (csrc/sim_x3.hip: 256 x 256 tiles, a few waves of them over the 256 CUs) go to
 // the bf16 matrix cores.
 static bool use_bf16x3(int64_t m, int64_t n, int64_t D, const float* A, const float* Bm) {
   // measured crossover: 2048^2 64 vs 100 TF (f32 wins), 3072^2 142 vs 122 TF (profiles/history/r04_sim_midsize_merge_inlaunch.txt)
@@ -1310,7 +1310,7 @@ extern "C" int dalm_contrastive_finalize(const float* row_lse, const float* col_
 
 // ---- exact top-k (eval retrieval): scores = scale * Q . C^T, k largest per query, no score matrix -------------
 namespace {
-// First pass (one maximum per row and 32 corpus columns) on the bf16 matrix cores at f32 accuracy (csrc/lmhead.hip, round 4)
+// First pass (one maximum per row and 32 corpus columns) on the bf16 matrix cores at f32 accuracy (csrc/sim_x3.hip, round 4)
 // once the score matrix has >= 1024 tiles of 256 x 256: 1.6x the f32 MFMA kernel's rate there.  DALM_TOPK_BF16X3 = 0 / 1
 // forces the f32 / bf16x3 pass (read per call: tests switch it).
 inline bool topk_use_x3(int64_t m, int64_t n, int64_t D) {

@@ -1,4 +1,4 @@
-// The SwiGLU element arithmetic, once: the row-wise kernels (tower.hip) and the live-row GEMM epilogues (lmhead.hip) round at the
+// The SwiGLU element arithmetic, once: the row-wise kernels (tower.hip) and the live-row GEMM epilogues (linear_live.hip) round at the
 // same points and produce the same bits.  RB names the tensor dtype's round trip (`RB::rb`, e.g. Vec16<T> or Bf16Round): every
 // place an eager elementwise op would round.
 //
@@ -20,7 +20,7 @@ struct Bf16Round {
 __device__ __forceinline__ float silu_f32(float x) { return x / (1.0f + expf(-x)); }
 
 // act = rb(s u) with s = rb(silu(g)).  The two halves are separate functions because s depends on g alone: a caller whose g is
-// bf16 may take s from a table of all 65536 values FILLED WITH swiglu_silu_rb (lmhead.hip does) - the same bits by construction.
+// bf16 may take s from a table of all 65536 values FILLED WITH swiglu_silu_rb (linear_live.hip does) - the same bits by construction.
 template <typename RB>
 __device__ __forceinline__ float swiglu_silu_rb(float g) { return RB::rb(silu_f32(g)); }
 template <typename RB>

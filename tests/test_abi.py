@@ -189,3 +189,16 @@ def test_similarity_workspace_layouts(tmp_path):
     shapes.write_text("".join(f"{m} {n} {D}\n" for m, n, D in GRID))
     r = run_host_check(tmp_path, "sim_plan_check", shapes)
     assert r.returncode == 0 and r.stdout.strip() == f"sim plans ok: {len(GRID)} shapes", (r.returncode, r.stdout, r.stderr)
+
+
+def test_gemm256_launch_plans(tmp_path):
+    """csrc/gemm256_plan.hpp, the launch geometry of the MFMA GEMM core, is host-only C++17 as well: tests/gemm256_plan_check.cpp
+    checks that the banded tile order (plain and live) is a bijection onto the tile grid for 1..40 row tiles, that the SPLIT3
+    reciprocal is exact over its whole domain, that the builder's fields and guards equal literally restated expectations (lm_head
+    and live-row shapes, and the grid of tests/test_sim_sizes.py), and the bf16x3 workspace layouts over that grid."""
+    from test_sim_sizes import GRID
+
+    shapes = tmp_path / "shapes.txt"
+    shapes.write_text("".join(f"{m} {n} {D}\n" for m, n, D in GRID))
+    r = run_host_check(tmp_path, "gemm256_plan_check", shapes)
+    assert r.returncode == 0 and r.stdout.strip() == f"gemm256 plans ok: {len(GRID)} shapes", (r.returncode, r.stdout, r.stderr)

@@ -1,4 +1,4 @@
-"""`dalm_row_partition` and `dalm_linear_live` (dalm_amd/csrc/lmhead.hip, wrappers in dalm_amd/linear_live.py) on the GPU.
+"""`dalm_row_partition` and `dalm_linear_live` (dalm_amd/csrc/linear_live.hip, wrappers in dalm_amd/linear_live.py) on the GPU.
 
 Reference: the fp64 product of the bf16 inputs on the host (plus the old C where accumulating).  Criterion, per element:
     |y - ref| <= ulp_bf16(ref) + C_TOL * sum_k |a_k w_k|

@@ -1,4 +1,4 @@
-"""`dalm_linear_live_swiglu` and `dalm_linear_live_dswiglu` (dalm_amd/csrc/lmhead.hip) on the GPU against the unfused pair of entry
+"""`dalm_linear_live_swiglu` and `dalm_linear_live_dswiglu` (dalm_amd/csrc/linear_live.hip) on the GPU against the unfused pair of entry
 points they replace, run in the same process: `dalm_linear_live` followed by `dalm_swiglu_fwd_2d_live` / `dalm_swiglu_bwd_2d_live`
 (those are checked against fp64 in test_linear_live_gpu.py and test_tower_ops_gpu.py).  Same contraction order, same element
 arithmetic (csrc/swiglu_math.hpp): the live rows must be EQUAL, bit for bit.
