@@ -70,12 +70,11 @@ struct Lm8Params {
   int out_cols;              // columns that exist in `out` (zero-filled from V up to here where the policy says so)
   int accumulate;            // add to what `out` holds
   // the similarity backward's dS policy; row statistics ride in row_lse / coef above
-  // The frozen MLP node's policies keep their operands in the same slots - the struct, and with it the kernel-argument layout
-  // every other instantiation was compiled against, does not grow: y = [gate | up] [R][y_pitch] bf16 (written through `out` by
-  // the forward, read by the backward); out2 = act (forward) / d_up (backward, where `out` is d_gate)
-  union { const float* col_lse; const void* y; };        // [V] column log-sum-exp (global column = col_base + local)
+  // The frozen MLP node's forward policy keeps its second output in the same slots - the struct, and with it the kernel-argument
+  // layout every other instantiation was compiled against, does not grow: y = [gate | up] leaves through `out`, act through out2
+  const float* col_lse;                                  // [V] column log-sum-exp (global column = col_base + local)
   union { const float* col_coef; void* out2; };          // [V]
-  union { int64_t diag_offset; int64_t y_pitch; };       // the positive of row i is global column diag_offset + i
+  int64_t diag_offset;                                   // the positive of row i is global column diag_offset + i
   union { int64_t out_third; int64_t out2_pitch; };      // elements between the hi / mid / lo images inside a row of `out`
   // live policies: the rows of H and `out` go through a stable partition of the row-liveness vector
   const int* perm;           // [R] live rows first (ascending), then the dead ones
@@ -142,7 +141,6 @@ __device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rs, unsigned ch
 
 // What the core asks of an epilogue policy `Epi`; a policy derives from this and overrides what differs.
 struct Gemm256Epi {
-  static constexpr int TI = 4;          // 32-row accumulator tiles per wave along the rows: the workgroup tile is (64 TI) x 256
   static constexpr bool LIVE = false;   // tile position i stands for row perm[i]; blocks past the live row tiles skip the multiply
   // output columns behind a column tile.  256: its B rows are rows c0 .. c0 + 255 of W.  128: two halves of 128 rows, c0 .. and
   // w_half(p) + c0 .., which wave columns 0 and 1 hold for the same output columns and the epilogue combines
@@ -151,25 +149,21 @@ struct Gemm256Epi {
   // LIVE: a block whose every position is dead; (r0, c0) is the tile it would have had
   static __device__ __forceinline__ void skipped(const Lm8Params&, int, int, int) {}
   // every policy defines
-  //   static __device__ void tile(const Lm8Params& p, f32x16 (&acc)[TI][4], unsigned char* lds,
+  //   static __device__ void tile(const Lm8Params& p, f32x16 (&acc)[4][4], unsigned char* lds,
   //                               int r0, int c0, int nt, int nlive, int wr, int wc, int tid)
-  // for the accumulators of wave (wr, wc)'s (32 TI) x 128 block of the tile at (r0, c0), the whole LDS free for its use
+  // for the accumulators of wave (wr, wc)'s 128 x 128 block of the tile at (r0, c0), the whole LDS free for its use
 };
 
 // SPLIT3 (the bf16x3 similarity, sim_x3.hip): the operands are [rows][3 D] bf16 images holding the (hi, mid,
 // lo) bf16 thirds of an f32 matrix side by side; the contraction walks SIX segments of D - the six significant products of
 // (hi + mid + lo) x (hi + mid + lo), smallest first - and K tile u reads third segA[u / tpd] of H against third segB[u / tpd]
 // of W: the same main loop, only the K offset of a tile is looked up instead of being u * 128.
-// TI = 32-row accumulator tiles per wave along the rows: the workgroup tile is (64 TI) x 256.  TI = 4 is the form described above;
-// TI = 2 (128 x 256, a wave owns 64 x 128: 8 MFMAs per 6 fragment reads instead of 16 per 8) is for shapes whose row-tile count at
-// 256 rows leaves a poor last round.
 template <class Epi, bool SPLIT3 = false>
 __global__ __launch_bounds__(256, 1) void gemm256_kernel(const Lm8Params p) {
-  constexpr int TI = Epi::TI;
   constexpr bool LIVE = Epi::LIVE;
-  static_assert((TI == 4 || TI == 2) && (Epi::COLS == 256 || Epi::COLS == 128), "tiles of 256 or 128 rows, 256 or 128 columns");
-  constexpr int NA = 2 * TI, NP = NA + 8;        // load pieces of 32 rows per K tile: NA of the A tile, then 8 of the B tile
-  constexpr int NM = 4 * TI, NR = TI + 4;        // MFMAs and fragment reads per k-step
+  static_assert(Epi::COLS == 256 || Epi::COLS == 128, "tiles of 256 or 128 columns");
+  constexpr int NA = 8, NP = 16;                 // load pieces of 32 rows per K tile: NA of the A tile, then 8 of the B tile
+  constexpr int NM = 16, NR = 8;                 // MFMAs and fragment reads per k-step
   // load pieces (NP per K tile and wave) issued in k-step 3 (right after the barrier) / 0 / 1 / 2: measured best of the placements
   constexpr int N3 = NP / 2, N0 = NP - NP / 2, N1 = 0, N2 = 0;
   __shared__ __attribute__((aligned(16))) unsigned char lds[2 * L8_BUF];
@@ -181,18 +175,18 @@ __global__ __launch_bounds__(256, 1) void gemm256_kernel(const Lm8Params p) {
   if constexpr (LIVE) {
     // the live row-tile count is a device value: the banded order runs over the live tiles, the skipping tiles come last
     nlive = min(max(*p.n_live, 0), p.R);
-    const unsigned NT = static_cast<unsigned>(p.NT), mtl = static_cast<unsigned>((nlive + 64 * TI - 1) / (64 * TI));
+    const unsigned NT = static_cast<unsigned>(p.NT), mtl = static_cast<unsigned>((nlive + 255) / 256);
     const unsigned nlb = mtl * NT;
     if (blockIdx.x >= nlb) {
       const unsigned s = blockIdx.x - nlb;
-      Epi::skipped(p, static_cast<int>(mtl + s / NT) * 64 * TI, static_cast<int>(s % NT) * Epi::COLS, tid);
+      Epi::skipped(p, static_cast<int>(mtl + s / NT) * 256, static_cast<int>(s % NT) * Epi::COLS, tid);
       return;
     }
     lm_tile_order(p.xcd_order, gemm256_band(mtl), NT, mtl, blockIdx.x, nlb, mt, nt);
   } else {
     lm_tile_of(p, blockIdx.x, gridDim.x, mt, nt);
   }
-  const int r0 = mt * 64 * TI, c0 = nt * Epi::COLS;
+  const int r0 = mt * 256, c0 = nt * Epi::COLS;
   const __amdgpu_buffer_rsrc_t rsH = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.H), 0, static_cast<int>(p.bytesH), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.W), 0, static_cast<int>(p.bytesW), 0x00020000);
 
@@ -204,15 +198,13 @@ __global__ __launch_bounds__(256, 1) void gemm256_kernel(const Lm8Params p) {
   for (int q = 0; q < 8; ++q) {
     if constexpr (LIVE) {
       // row gather: the A row of position i is perm[i]; a dead position gets row R = past the descriptor's range, reads zero
-      if (q < NA) {
-        const int i = r0 + q * 32 + srow;
-        int row = p.R;
-        if (i < nlive) {
-          row = p.perm[i];
-          if (static_cast<unsigned>(row) >= static_cast<unsigned>(p.R)) row = p.R;
-        }
-        voff[q] = static_cast<unsigned>(row) * p.pitchH + schunk;
+      const int i = r0 + q * 32 + srow;
+      int row = p.R;
+      if (i < nlive) {
+        row = p.perm[i];
+        if (static_cast<unsigned>(row) >= static_cast<unsigned>(p.R)) row = p.R;
       }
+      voff[q] = static_cast<unsigned>(row) * p.pitchH + schunk;
     } else {
       voff[q] = static_cast<unsigned>(r0 + q * 32 + srow) * p.pitchH + schunk;
     }
@@ -228,12 +220,12 @@ __global__ __launch_bounds__(256, 1) void gemm256_kernel(const Lm8Params p) {
   int koff[4];
 #pragma unroll
   for (int kk = 0; kk < 4; ++kk) koff[kk] = ((kk * 2 + lhi) ^ f) * 16;
-  const int abase = (wr * 32 * TI + l31) * 128;
+  const int abase = (wr * 128 + l31) * 128;
   const int bbase = NA * 4096 + (wc * 128 + l31) * 128;
 
-  f32x16 acc[TI][4];
+  f32x16 acc[4][4];
 #pragma unroll
-  for (int i = 0; i < TI; ++i)
+  for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -254,18 +246,18 @@ __global__ __launch_bounds__(256, 1) void gemm256_kernel(const Lm8Params p) {
       return static_cast<int>(third * p.seg_bytes) + w * 128;
     }
   };
-  bf16x8 fa0[TI], fb0[4], fa1[TI], fb1[4];
+  bf16x8 fa0[4], fb0[4], fa1[4], fb1[4];
 
-  // (TI = 4: the A and B reads of one i interleave, as the loop over both always did)
+  // (the A and B reads of one i interleave)
 #define L4_READ(BUF, KK, FA, FB)                                                                                      \
   _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                    \
-    if (i < TI) FA[i] = *reinterpret_cast<const bf16x8*>(lds + (BUF) * L8_BUF + i * 4096 + abase + koff[KK]);         \
+    FA[i] = *reinterpret_cast<const bf16x8*>(lds + (BUF) * L8_BUF + i * 4096 + abase + koff[KK]);                     \
     FB[i] = *reinterpret_cast<const bf16x8*>(lds + (BUF) * L8_BUF + i * 4096 + bbase + koff[KK]);                     \
   }
 #define L4_MFMA(FA, FB)                                                                                               \
-  _Pragma("unroll") for (int i = 0; i < TI; ++i) _Pragma("unroll") for (int j = 0; j < 4; ++j)                         \
+  _Pragma("unroll") for (int i = 0; i < 4; ++i) _Pragma("unroll") for (int j = 0; j < 4; ++j)                          \
       acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(FA[i], FB[j], acc[i][j], 0, 0, 0);
-  // NM MFMAs, NR fragment reads behind the first NR, ND load pieces behind the last ones (TI = 4: 16 and 8)
+  // NM MFMAs, NR fragment reads behind the first NR, ND load pieces behind the last ones
 #define L4_SCHED(ND)                                                                                                  \
   _Pragma("unroll") for (int i = 0; i < NM; ++i) {                                                                    \
     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                                \

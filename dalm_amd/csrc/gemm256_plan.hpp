@@ -63,13 +63,13 @@ struct Gemm256Shape {
   int64_t ldh, ldw;        // elements between rows of H / W
   int64_t w_rows;          // rows of W: V, or 2 V where a column tile gathers gate and up rows
   int64_t D;               // SPLIT3: width of one third (K = 6 D over rows of 3 D); 0 otherwise
-  int tile_rows, tile_cols;
+  int tile_cols;           // output columns per column tile: 256, or 128 for the gate | up tiles (a row tile is 256 rows)
   bool live;               // rows go through the partition: the kernel bands the LIVE row tiles itself
 };
-inline Gemm256Shape gemm256_dense(int64_t R, int64_t V, int64_t K) { return {R, V, K, K, K, V, 0, 256, 256, false}; }
-inline Gemm256Shape gemm256_split3(int64_t R, int64_t V, int64_t D) { return {R, V, 6 * D, 3 * D, 3 * D, V, D, 256, 256, false}; }
-inline Gemm256Shape gemm256_live(int64_t R, int64_t N, int64_t K, int64_t lda, int64_t w_rows, int tile_rows, int tile_cols) {
-  return {R, N, K, lda, K, w_rows, 0, tile_rows, tile_cols, true};
+inline Gemm256Shape gemm256_dense(int64_t R, int64_t V, int64_t K) { return {R, V, K, K, K, V, 0, 256, false}; }
+inline Gemm256Shape gemm256_split3(int64_t R, int64_t V, int64_t D) { return {R, V, 6 * D, 3 * D, 3 * D, V, D, 256, false}; }
+inline Gemm256Shape gemm256_live(int64_t R, int64_t N, int64_t K, int64_t lda, int64_t w_rows, int tile_cols) {
+  return {R, N, K, lda, K, w_rows, 0, tile_cols, true};
 }
 
 struct Gemm256Plan { int code; const char* what; Gemm256Geom g; };
@@ -89,7 +89,7 @@ inline Gemm256Plan gemm256_plan(const Gemm256Shape& s, const char* too_big) {
   if (spanH >= 0xffffff00ull || spanW >= 0xffffff00ull) return fail(DALM_E_SHAPE, too_big);
   Gemm256Geom& g = pl.g;
   g.R = static_cast<int>(s.R); g.V = static_cast<int>(s.V); g.K = static_cast<int>(s.K);
-  g.MT = static_cast<int>((s.R + s.tile_rows - 1) / s.tile_rows);
+  g.MT = static_cast<int>((s.R + 255) / 256);
   g.NT = static_cast<int>((s.V + s.tile_cols - 1) / s.tile_cols);
   g.xcd_order = 1;
   g.gh = s.live ? 1 : static_cast<int>(gemm256_band(static_cast<unsigned>(g.MT)));

@@ -1,5 +1,5 @@
 // The padded step's frozen projections over the live rows only (DESIGN.md "Live-row GEMM"): the row partition, dalm_linear_live and
-// the SwiGLU MLP node's two fused GEMMs - epilogue policies of the GEMM core of gemm256.hpp whose rows go through the partition.
+// the SwiGLU MLP node's fused gate | up GEMM - epilogue policies of the GEMM core of gemm256.hpp whose rows go through the partition.
 #include "gemm256.hpp"
 #include "swiglu_math.hpp"
 #include <atomic>
@@ -8,16 +8,15 @@
 namespace dalm {
 namespace {
 
-// EPI_LIVE (dalm_linear_live): tile position i stands for row perm[i] of A and of C.  The (64 TI) x 256 tile leaves as bf16 into
+// EPI_LIVE (dalm_linear_live): tile position i stands for row perm[i] of A and of C.  The 256 x 256 tile leaves as bf16 into
 // out[perm[i]][c0 + column] - or is added in f32 to the bf16 value already there, one rounding - with the pair exchange of the
 // EPI_LOGITS epilogue (one dword per lane).  Positions n_live <= i < R of the boundary tile are dead rows: zeros when the output
 // is fresh, untouched when accumulating.  A perm entry outside [0, R) stores nothing.
-template <int TI>
-__device__ __forceinline__ void lm_tile_epilogue_live(const Lm8Params& p, f32x16 (&acc)[TI][4], unsigned char* lds, int r0, int c0,
+__device__ __forceinline__ void lm_tile_epilogue_live(const Lm8Params& p, f32x16 (&acc)[4][4], unsigned char* lds, int r0, int c0,
                                                       int nlive, int wr, int wc, int tid) {
   const int lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
-  int* row_s = reinterpret_cast<int*>(lds);                   // [64 TI] row of C behind every tile position, -1: none
-  if (tid < 64 * TI) {
+  int* row_s = reinterpret_cast<int*>(lds);                   // [256] row of C behind every tile position, -1: none
+  if (tid < 256) {      // true for every thread; without it the kernel compiles to other instructions (profiles/live_gemm_forms_removed.md)
     const int i = r0 + tid;
     int row = -1;
     if (i < p.R) {
@@ -32,10 +31,10 @@ __device__ __forceinline__ void lm_tile_epilogue_live(const Lm8Params& p, f32x16
   const bool add = p.accumulate != 0;
   unsigned short* outp = static_cast<unsigned short*>(p.out);
 #pragma unroll
-  for (int i = 0; i < TI; ++i) {
+  for (int i = 0; i < 4; ++i) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const int rl4 = wr * 32 * TI + i * 32 + 8 * g + 4 * lhi;   // positions rl4 .. rl4 + 3 = accumulator registers 4 g .. 4 g + 3
+      const int rl4 = wr * 128 + i * 32 + 8 * g + 4 * lhi;   // positions rl4 .. rl4 + 3 = accumulator registers 4 g .. 4 g + 3
       const int4 rw = *reinterpret_cast<const int4*>(row_s + rl4);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -79,7 +78,7 @@ __global__ __launch_bounds__(256) void silu_table_kernel() {
   g_silu_bf16_tab[i] = f32_to_bf16(swiglu_silu_rb<Bf16Round>(bf16_to_f32(static_cast<unsigned short>(i))));
 }
 
-// The row behind every position of a 256-position live tile, for the two MLP epilogues below: -1 for a dead position (>= n_live)
+// The row behind every position of a 256-position live tile, for the MLP epilogue below: -1 for a dead position (>= n_live)
 // and for a perm entry outside [0, R) - nothing is stored for either.
 __device__ __forceinline__ void lm_live_rows_to_lds(const Lm8Params& p, int* row_s, int r0, int nlive, int tid) {
   const int i = r0 + tid;
@@ -202,80 +201,14 @@ __device__ __forceinline__ void lm_tile_epilogue_live_swiglu(const Lm8Params& p,
   }
 }
 
-// EPI_LIVE_DSWIGLU (dalm_linear_live_dswiglu): the tile is d_act of the down projection.  Per lane pair, as in the EPI_LIVE epilogue:
-// the pair rounded to bf16 is exactly what the unfused path stores as d_act; the gate and up words of y[perm[i]] at the same
-// columns are loaded, the SwiGLU backward applied, and d_gate / d_up leave into out / out2.  d_act itself is never written; dead
-// positions, corrupt perm entries and columns >= out_cols store nothing (their loads read word 0 of y instead: in bounds, unused).
-// One 32-row block of a wave at a time: its 64 loads are issued together, ahead of the arithmetic - the kernel runs one wave per
-// SIMD, nothing else hides a load's latency - and a block is its own function so that the accumulator indices stay static.
-__device__ __forceinline__ void lm_dswiglu_block(const Lm8Params& p, const f32x16 (&a)[4], const int* row_s, int rl, int cw, bool odd,
-                                                 int lhi) {
-  const unsigned short* yp = static_cast<const unsigned short*>(p.y);
-  unsigned short* dgp = static_cast<unsigned short*>(p.out);
-  unsigned short* dup = static_cast<unsigned short*>(p.out2);
-  int row[4][2];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const int4 rw = *reinterpret_cast<const int4*>(row_s + rl + 8 * g + 4 * lhi);
-    row[g][0] = odd ? rw.y : rw.x;
-    row[g][1] = odd ? rw.w : rw.z;
-  }
-  unsigned int gw[4][4][2], uw[4][4][2];
-#pragma unroll
-  for (int g = 0; g < 4; ++g)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int ce = cw + 32 * j;
-        const bool ok = row[g][h] >= 0 && ce < p.out_cols;
-        const unsigned short* yr = yp + (ok ? static_cast<int64_t>(row[g][h]) * p.y_pitch + ce : 0);
-        gw[g][j][h] = *reinterpret_cast<const unsigned int*>(yr);
-        uw[g][j][h] = *reinterpret_cast<const unsigned int*>(yr + p.y_half);
-      }
-#pragma unroll
-  for (int g = 0; g < 4; ++g)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int ce = cw + 32 * j;
-        const float mine_a = a[j][4 * g + 2 * h], mine_b = a[j][4 * g + 2 * h + 1];
-        const float send = odd ? mine_a : mine_b;
-        const float got = __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(send), 0xB1, 0xf, 0xf, false));
-        const unsigned int daw = odd ? pack_bf16x2(got, mine_b) : pack_bf16x2(mine_a, got);
-        const unsigned int g2 = gw[g][j][h], u2 = uw[g][j][h];
-        float dg0, dg1, du0, du1;
-        swiglu_bwd_elem<Bf16Round>(__uint_as_float(daw << 16), __uint_as_float(g2 << 16), __uint_as_float(u2 << 16), dg0, du0);
-        swiglu_bwd_elem<Bf16Round>(__uint_as_float(daw & 0xffff0000u), __uint_as_float(g2 & 0xffff0000u),
-                                   __uint_as_float(u2 & 0xffff0000u), dg1, du1);
-        if (row[g][h] >= 0 && ce < p.out_cols) {
-          *reinterpret_cast<unsigned int*>(dgp + static_cast<int64_t>(row[g][h]) * p.out_pitch + ce) = pack_bf16x2(dg0, dg1);
-          *reinterpret_cast<unsigned int*>(dup + static_cast<int64_t>(row[g][h]) * p.out2_pitch + ce) = pack_bf16x2(du0, du1);
-        }
-      }
-}
-__device__ __forceinline__ void lm_tile_epilogue_live_dswiglu(const Lm8Params& p, f32x16 (&acc)[4][4], unsigned char* lds, int r0,
-                                                              int c0, int nlive, int wr, int wc, int tid) {
-  const int lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
-  int* row_s = reinterpret_cast<int*>(lds);
-  lm_live_rows_to_lds(p, row_s, r0, nlive, tid);
-  const int cw = c0 + ((wc * 128 + l31) & ~1);                  // even column of the lane pair in accumulator tile j = 0
-  const bool odd = (lane & 1) != 0;
-  lm_dswiglu_block(p, acc[0], row_s, wr * 128, cw, odd, lhi);
-  lm_dswiglu_block(p, acc[1], row_s, wr * 128 + 32, cw, odd, lhi);
-  lm_dswiglu_block(p, acc[2], row_s, wr * 128 + 64, cw, odd, lhi);
-  lm_dswiglu_block(p, acc[3], row_s, wr * 128 + 96, cw, odd, lhi);
-}
-
 // EPI_LIVE, a tile whose every position is dead (block index past the live tiles): multiplies nothing.  A fresh output gets its
-// zeros here - tile positions r0 .. r0 + TROWS - 1 of perm, 256 columns from c0, 16 bytes per lane - an accumulating one nothing.
-__device__ __forceinline__ void lm_tile_zero_live(const Lm8Params& p, int r0, int trows, int c0, int tid) {
+// zeros here - tile positions r0 .. r0 + 255 of perm, 256 columns from c0, 16 bytes per lane - an accumulating one nothing.
+__device__ __forceinline__ void lm_tile_zero_live(const Lm8Params& p, int r0, int c0, int tid) {
   if (p.accumulate) return;
   const int col = c0 + (tid & 31) * 8;
   if (col >= p.out_cols) return;                                // out_cols % 8 == 0: a 16-byte piece is inside or outside
   unsigned short* outp = static_cast<unsigned short*>(p.out);
-  for (int t = tid >> 5; t < trows; t += 8) {
+  for (int t = tid >> 5; t < 256; t += 8) {
     const int i = r0 + t;
     if (i >= p.R) break;
     const int row = p.perm[i];
@@ -284,16 +217,14 @@ __device__ __forceinline__ void lm_tile_zero_live(const Lm8Params& p, int r0, in
   }
 }
 
-// ---- the policies: all three gather their rows through the partition.  dalm_linear_live writes the caller's output, so its
-// skipping blocks zero-fill; the two of the MLP node write node-private buffers whose dead rows nobody reads: theirs return at once
-template <int TI_>
+// ---- the policies: both gather their rows through the partition.  dalm_linear_live writes the caller's output, so its skipping
+// blocks zero-fill; the MLP node's forward writes node-private buffers whose dead rows nobody reads: its skipping blocks return at once
 struct EpiLive : Gemm256Epi {
-  static constexpr int TI = TI_;
   static constexpr bool LIVE = true;
-  static __device__ __forceinline__ void skipped(const Lm8Params& p, int r0, int c0, int tid) { lm_tile_zero_live(p, r0, 64 * TI, c0, tid); }
-  static __device__ __forceinline__ void tile(const Lm8Params& p, f32x16 (&acc)[TI][4], unsigned char* lds,
+  static __device__ __forceinline__ void skipped(const Lm8Params& p, int r0, int c0, int tid) { lm_tile_zero_live(p, r0, c0, tid); }
+  static __device__ __forceinline__ void tile(const Lm8Params& p, f32x16 (&acc)[4][4], unsigned char* lds,
                                             int r0, int c0, int nt, int nlive, int wr, int wc, int tid) {
-    lm_tile_epilogue_live<TI>(p, acc, lds, r0, c0, nlive, wr, wc, tid);
+    lm_tile_epilogue_live(p, acc, lds, r0, c0, nlive, wr, wc, tid);
   }
 };
 struct EpiLiveSwiglu : Gemm256Epi {
@@ -303,13 +234,6 @@ struct EpiLiveSwiglu : Gemm256Epi {
   static __device__ __forceinline__ void tile(const Lm8Params& p, f32x16 (&acc)[4][4], unsigned char* lds,
                                             int r0, int c0, int nt, int nlive, int wr, int wc, int tid) {
     lm_tile_epilogue_live_swiglu(p, acc, lds, r0, c0, nlive, wr, wc, tid);
-  }
-};
-struct EpiLiveDswiglu : Gemm256Epi {
-  static constexpr bool LIVE = true;
-  static __device__ __forceinline__ void tile(const Lm8Params& p, f32x16 (&acc)[4][4], unsigned char* lds,
-                                            int r0, int c0, int nt, int nlive, int wr, int wc, int tid) {
-    lm_tile_epilogue_live_dswiglu(p, acc, lds, r0, c0, nlive, wr, wc, tid);
   }
 };
 
@@ -342,16 +266,6 @@ __global__ __launch_bounds__(1024) void row_partition_kernel(const uint8_t* __re
   if (t == 0) *n_live = total;
 }
 
-// Tile form by shape: rows per workgroup tile, 256 or 128 (columns: 256 either way).  The choice is static - the live count is a
-// device value - and comes from tools/linear_live_bench.py at the padded step's shapes (profiles/linear_live_bench.txt).  Measured
-// there, the 128-row form (8 MFMAs per 6 fragment reads) is slower than or level with the 256-row form at every shape and mask,
-// also where 256-row tiles quantise worst (down dgrad, 2897 live rows: 516 tiles = 2.02 rounds, 288.4 us; 989 half tiles,
-// 288.6 us), so no shape selects it; callers can still name it (`form`).  A shape that wins with 128 rows gets its case here.
-inline int linear_live_form(int64_t R, int64_t N, int64_t K) {
-  (void)R; (void)N; (void)K;
-  return 256;
-}
-
 const char* const kTooBig = "operands above 4 GB: use fewer rows per call";
 }  // namespace
 }  // namespace dalm
@@ -367,10 +281,8 @@ extern "C" int dalm_row_partition(const uint8_t* live, int64_t R, int32_t* perm,
   return check_launch(__func__);
 }
 
-extern "C" int dalm_linear_live_form(int64_t R, int64_t N, int64_t K) { return linear_live_form(R, N, K); }
-
 extern "C" int dalm_linear_live(const void* A, int64_t lda, const void* W, void* C, int64_t ldc, int64_t R, int64_t N, int64_t K,
-                                const int32_t* perm, const int32_t* n_live, int accumulate, int form, dalm_stream_t stream) {
+                                const int32_t* perm, const int32_t* n_live, int accumulate, dalm_stream_t stream) {
   DALM_REQUIRE(A && W && C && perm && n_live, DALM_E_NULL, "null pointer argument");
   DALM_REQUIRE(R > 0 && N > 0 && K > 0 && K % 64 == 0 && N % 8 == 0, DALM_E_SHAPE,
                "need R, N, K > 0, K a multiple of 64 and N a multiple of 8");
@@ -378,37 +290,18 @@ extern "C" int dalm_linear_live(const void* A, int64_t lda, const void* W, void*
                "row strides: lda >= K, ldc >= N, both multiples of 8 elements");
   DALM_REQUIRE(R <= 0x7fffff00ll && N <= 0x7fffff00ll && lda <= 0x7fffffffll && ldc <= 0x7fffffffll, DALM_E_SHAPE,
                "operands above 4 GB: use fewer rows per call");      // also keeps the products below inside 64 bits
-  DALM_REQUIRE(form == 0 || form == 128 || form == 256, DALM_E_SHAPE, "form: 0 (by shape), 128 or 256 rows per tile");
   DALM_REQUIRE(accumulate == 0 || accumulate == 1, DALM_E_SHAPE, "accumulate: 0 or 1");
   DALM_REQUIRE(reinterpret_cast<uintptr_t>(A) % 16 == 0 && reinterpret_cast<uintptr_t>(W) % 16 == 0 &&
                reinterpret_cast<uintptr_t>(C) % 16 == 0, DALM_E_ALIGN, "A / W / C must be 16-byte aligned");
-  const int rows = form ? form : linear_live_form(R, N, K);
   Lm8Params q{};
-  const int rc = gemm256_params(q, __func__, A, W, gemm256_live(R, N, K, lda, N, rows, 256), kTooBig);
+  const int rc = gemm256_params(q, __func__, A, W, gemm256_live(R, N, K, lda, N, 256), kTooBig);
   if (rc != DALM_OK) return rc;
   q.out = C; q.out_pitch = ldc; q.out_cols = static_cast<int>(N); q.accumulate = accumulate;
   q.perm = perm; q.n_live = n_live;
-  if (rows == 256) return launch_gemm256<EpiLive<4>>(q, as_stream(stream), __func__);
-  return launch_gemm256<EpiLive<2>>(q, as_stream(stream), __func__);
+  return launch_gemm256<EpiLive>(q, as_stream(stream), __func__);
 }
 
-// ---- the frozen SwiGLU MLP node of the padded step: SwiGLU inside the epilogues of its live-row GEMMs --------------------------
-namespace {
-// the operand checks and parameters the two entry points share with dalm_linear_live: A [R, K] (stride lda) against W [N, K]
-int linear_live_mlp_params(Lm8Params& q, const char* fn, const void* A, int64_t lda, const void* W, int64_t R, int64_t N, int64_t K,
-                           int64_t w_rows, int tile_cols, const int32_t* perm, const int32_t* n_live) {
-  if (!(R > 0 && N > 0 && K > 0 && K % 64 == 0 && N % 8 == 0))
-    return fail(DALM_E_SHAPE, fn, "need R, C, K > 0, K a multiple of 64 and C a multiple of 8");
-  if (!(lda >= K && lda % 8 == 0)) return fail(DALM_E_SHAPE, fn, "row strides: lda >= K, a multiple of 8 elements");
-  if (!(R <= 0x7fffff00ll && w_rows <= 0x7fffff00ll && lda <= 0x7fffffffll)) return fail(DALM_E_SHAPE, fn, kTooBig);
-  const int rc = gemm256_params(q, fn, A, W, gemm256_live(R, N, K, lda, w_rows, 256, tile_cols), kTooBig);
-  if (rc != DALM_OK) return rc;
-  q.out_cols = static_cast<int>(N);
-  q.perm = perm; q.n_live = n_live;
-  return DALM_OK;
-}
-}  // namespace
-
+// ---- the frozen SwiGLU MLP node of the padded step: SwiGLU inside the epilogue of its gate | up live-row GEMM ------------------
 namespace {
 // The silu table of the current device: filled on the first call, outside any stream capture, and complete (the stream is drained)
 // before the flag is set - a later call from any stream finds it whole.
@@ -444,32 +337,19 @@ extern "C" int dalm_linear_live_swiglu(const void* A, int64_t lda, const void* W
   DALM_REQUIRE(reinterpret_cast<uintptr_t>(A) % 16 == 0 && reinterpret_cast<uintptr_t>(Wcat) % 16 == 0 &&
                reinterpret_cast<uintptr_t>(Y) % 16 == 0 && reinterpret_cast<uintptr_t>(Act) % 16 == 0, DALM_E_ALIGN,
                "A / Wcat / Y / Act must be 16-byte aligned");
+  // the operand checks dalm_linear_live makes: A [R, K] (stride lda) against Wcat [2 C, K]
+  DALM_REQUIRE(R > 0 && C > 0 && K > 0 && K % 64 == 0 && C % 8 == 0, DALM_E_SHAPE,
+               "need R, C, K > 0, K a multiple of 64 and C a multiple of 8");
+  DALM_REQUIRE(lda >= K && lda % 8 == 0, DALM_E_SHAPE, "row strides: lda >= K, a multiple of 8 elements");
+  DALM_REQUIRE(R <= 0x7fffff00ll && 2 * C <= 0x7fffff00ll && lda <= 0x7fffffffll, DALM_E_SHAPE, kTooBig);
   Lm8Params q{};
-  const int rc = linear_live_mlp_params(q, __func__, A, lda, Wcat, R, C, K, 2 * C, 128, perm, n_live);
+  const int rc = gemm256_params(q, __func__, A, Wcat, gemm256_live(R, C, K, lda, 2 * C, 128), kTooBig);
   if (rc != DALM_OK) return rc;
-  q.out = Y; q.out_pitch = ldy;
-  q.y = Y; q.y_pitch = ldy; q.y_half = static_cast<int>(C);
+  q.out_cols = static_cast<int>(C);
+  q.perm = perm; q.n_live = n_live;
+  q.out = Y; q.out_pitch = ldy; q.y_half = static_cast<int>(C);
   q.out2 = Act; q.out2_pitch = ldact;
   const int tab = ensure_silu_table(__func__, stream);
   if (tab != DALM_OK) return tab;
   return launch_gemm256<EpiLiveSwiglu>(q, as_stream(stream), __func__);
-}
-
-extern "C" int dalm_linear_live_dswiglu(const void* dOut, int64_t ldd, const void* WdT, const void* Y, int64_t ldy, void* dG,
-                                        int64_t lddg, void* dU, int64_t lddu, int64_t R, int64_t C, int64_t H, const int32_t* perm,
-                                        const int32_t* n_live, dalm_stream_t stream) {
-  DALM_REQUIRE(dOut && WdT && Y && dG && dU && perm && n_live, DALM_E_NULL, "null pointer argument");
-  DALM_REQUIRE(C > 0 && ldy >= 2 * C && lddg >= C && lddu >= C && ldy % 8 == 0 && lddg % 8 == 0 && lddu % 8 == 0 &&
-               ldy <= 0x7fffffffll && lddg <= 0x7fffffffll && lddu <= 0x7fffffffll, DALM_E_SHAPE,
-               "row strides: ldy >= 2 C, lddg >= C, lddu >= C, all multiples of 8 elements");
-  DALM_REQUIRE(reinterpret_cast<uintptr_t>(dOut) % 16 == 0 && reinterpret_cast<uintptr_t>(WdT) % 16 == 0 &&
-               reinterpret_cast<uintptr_t>(Y) % 16 == 0 && reinterpret_cast<uintptr_t>(dG) % 16 == 0 &&
-               reinterpret_cast<uintptr_t>(dU) % 16 == 0, DALM_E_ALIGN, "dOut / WdT / Y / dG / dU must be 16-byte aligned");
-  Lm8Params q{};
-  const int rc = linear_live_mlp_params(q, __func__, dOut, ldd, WdT, R, C, H, C, 256, perm, n_live);
-  if (rc != DALM_OK) return rc;
-  q.out = dG; q.out_pitch = lddg;
-  q.y = Y; q.y_pitch = ldy; q.y_half = static_cast<int>(C);
-  q.out2 = dU; q.out2_pitch = lddu;
-  return launch_gemm256<EpiLiveDswiglu>(q, as_stream(stream), __func__);
 }

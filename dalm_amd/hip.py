@@ -175,12 +175,10 @@ SIGNATURES = {
                                     _vp]),
     # padded step: stable partition of the row-liveness vector and the frozen-projection GEMM over the live rows
     "dalm_row_partition": (_int, [_vp, _i64, _vp, _vp, _vp]),
-    "dalm_linear_live_form": (_int, [_i64, _i64, _i64]),
-    "dalm_linear_live": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _int, _int, _vp]),
-    # the frozen SwiGLU MLP node: SwiGLU inside the epilogues of the gate | up forward and the down dgrad
+    "dalm_linear_live": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _int, _vp]),
+    # the frozen SwiGLU MLP node: SwiGLU inside the epilogue of the gate | up forward
     "dalm_linear_live_swiglu_prepare": (_int, [_vp]),
     "dalm_linear_live_swiglu": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
-    "dalm_linear_live_dswiglu": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
 }
 
 

@@ -32,10 +32,6 @@ ROUTED_SHAPES = frozenset({
 
 _enabled = True
 _mlp_fused = True
-# the backward piece (dalm_linear_live_dswiglu) did not clear its gate in tools/linear_live_bench.py --mlp-fused: two exps and two
-# IEEE divisions per element in an epilogue that runs one wave per SIMD cost more than the d_act round trip saves.
-# The node therefore runs the down dgrad and dalm_swiglu_bwd_2d_live as two launches unless this is set (tests, the bench).
-_mlp_fused_backward = False
 _table = ROUTED_SHAPES
 _calls = 0
 
@@ -61,17 +57,6 @@ def mlp_fused() -> bool:
     return _mlp_fused
 
 
-def set_mlp_fused_backward(on: bool) -> None:
-    """Let the fused node run its backward through `dalm_linear_live_dswiglu` too (off by default: measured slower than the pair of
-    launches it replaces; same bits either way)."""
-    global _mlp_fused_backward
-    _mlp_fused_backward = bool(on)
-
-
-def mlp_fused_backward() -> bool:
-    return _mlp_fused_backward
-
-
 def set_table(shapes: Optional[Iterable[Tuple[int, int, int]]]) -> None:
     """Replace the routing table ((rows, N, K) triples); None restores the measured one.  For tests at small shapes."""
     global _table
@@ -81,13 +66,6 @@ def set_table(shapes: Optional[Iterable[Tuple[int, int, int]]]) -> None:
 def calls() -> int:
     """How many times `linear_live` has launched the kernel in this process."""
     return _calls
-
-
-def table_form(rows: int, n: int, k: int) -> str:
-    """How the routing table treats a shape: "library", or the kernel's tile form for it."""
-    if (rows, n, k) not in _table:
-        return "library"
-    return "%d-row tiles" % hip.load().dalm_linear_live_form(rows, n, k)
 
 
 def shape_ok(rows: int, n: int, k: int) -> bool:
@@ -119,9 +97,9 @@ def mlp_prepare(device) -> bool:
 
 
 def mlp_routed(rows: int, c: int, h: int, dtype: torch.dtype, has_bias: bool, have_partition: bool) -> bool:
-    """The frozen SwiGLU MLP (hidden h, intermediate c) as ONE node around `linear_live_swiglu` / `linear_live_dswiglu`: the switch,
-    128-column mixed tiles, and ALL four GEMM shapes of the node in the table - gate | up forward, down forward, down dgrad, gate
-    and up dgrad (the last two share one shape)."""
+    """The frozen SwiGLU MLP (hidden h, intermediate c) as ONE node around `linear_live_swiglu`: the switch, 128-column mixed
+    tiles, and ALL four GEMM shapes of the node in the table - gate | up forward, down forward, down dgrad, gate and up dgrad (the
+    last two share one shape)."""
     if not (_mlp_fused and c > 0 and c % 128 == 0):
         return False
     return all(routed(rows, n, k, dtype, has_bias, have_partition) for n, k in ((2 * c, h), (h, c), (c, h)))
@@ -171,8 +149,8 @@ def partition_reference(live) -> Tuple[list, int]:
     return alive + [i for i, f in enumerate(flags) if not f], len(alive)
 
 
-def linear_live(a: torch.Tensor, w: torch.Tensor, part, out: Optional[torch.Tensor] = None, accumulate: bool = False,
-                form: int = 0) -> torch.Tensor:
+def linear_live(a: torch.Tensor, w: torch.Tensor, part, out: Optional[torch.Tensor] = None,
+                accumulate: bool = False) -> torch.Tensor:
     """out[perm[i]] (+)= a[perm[i]] . w^T for the live rows of `part` = (perm, n_live); a [R, K] and out [R, N] may be column
     views (row strides multiples of 8), w [N, K] contiguous, all bf16.  Fresh output: dead rows are zeros."""
     global _calls
@@ -190,7 +168,7 @@ def linear_live(a: torch.Tensor, w: torch.Tensor, part, out: Optional[torch.Tens
         raise ValueError("linear_live: inconsistent shapes")
     with torch.cuda.device(a.device):
         hip.call("dalm_linear_live", hip.ptr(a), a.stride(0), hip.ptr(w), hip.ptr(out), out.stride(0), rows, n, k, hip.ptr(perm),
-                 hip.ptr(n_live), int(bool(accumulate)), int(form), hip.stream())
+                 hip.ptr(n_live), int(bool(accumulate)), hip.stream())
     _calls += 1
     return out
 
@@ -222,28 +200,6 @@ def linear_live_swiglu(a: torch.Tensor, wcat: torch.Tensor, part):
                  hip.ptr(perm), hip.ptr(n_live), hip.stream())
     _calls += 1
     return y, act
-
-
-def linear_live_dswiglu(d_out: torch.Tensor, wdt: torch.Tensor, y: torch.Tensor, part):
-    """(d_gate, d_up) [R, C] each for the live rows of `part`: d_act = d_out . wdt^T (wdt [C, H] = the transposed down weight) goes
-    through the SwiGLU backward with y = [gate | up] inside the GEMM's epilogue - the bits of `linear_live` followed by
-    `dalm_swiglu_bwd_2d_live`; d_act is never stored.  Dead rows of the outputs are NOT written."""
-    global _calls
-    rows, h = d_out.shape
-    c = wdt.shape[0]
-    perm, n_live = _check_part(part, rows)
-    hip.require_gpu(d_out, wdt, y, perm, n_live)
-    if not (_operand_ok(d_out) and _operand_ok(y) and wdt.dtype == torch.bfloat16 and wdt.is_contiguous()):
-        raise TypeError("linear_live_dswiglu: bf16 operands with unit column stride expected (wdt contiguous)")
-    if wdt.shape != (c, h) or y.shape != (rows, 2 * c):
-        raise ValueError("linear_live_dswiglu: inconsistent shapes")
-    dg = torch.empty((rows, c), dtype=torch.bfloat16, device=d_out.device)
-    du = torch.empty((rows, c), dtype=torch.bfloat16, device=d_out.device)
-    with torch.cuda.device(d_out.device):
-        hip.call("dalm_linear_live_dswiglu", hip.ptr(d_out), d_out.stride(0), hip.ptr(wdt), hip.ptr(y), y.stride(0), hip.ptr(dg), c,
-                 hip.ptr(du), c, rows, c, h, hip.ptr(perm), hip.ptr(n_live), hip.stream())
-    _calls += 1
-    return dg, du
 
 
 # ---- tile accounting (pure Python: the estimate table of DESIGN.md, and the bench's FLOP column) -------------------------------

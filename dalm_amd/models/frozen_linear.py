@@ -310,8 +310,8 @@ class _FrozenCatPairFn(torch.autograd.Function):
 
 class _FrozenSwigluMlpFn(torch.autograd.Function):
     """down(silu(gate(x)) * up(x)) with all three projections frozen, inside a padded tower call, as ONE node: the SwiGLU forward
-    runs in the epilogue of the gate | up GEMM (dalm_amd/linear_live.py); its backward can run in the epilogue of the down dgrad
-    GEMM, but that piece measured slower than the two launches it replaces and is off by default.
+    runs in the epilogue of the gate | up GEMM (dalm_amd/linear_live.py); the backward runs the down dgrad GEMM and the row-wise
+    SwiGLU backward kernel as two launches (an epilogue form of the pair measured slower: DESIGN.md 5.7.1).
     y = [gate | up], act, d_gate and d_up never leave the node, so their dead rows are never written - nobody reads them: every
     consumer is a live-row GEMM whose A gather skips them.  The output and dx leave the node and keep zeros in their dead rows.
     Same bits as the separate nodes: same contraction order, same element arithmetic (csrc/swiglu_math.hpp)."""
@@ -331,7 +331,7 @@ class _FrozenSwigluMlpFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .. import linear_live
+        from .. import hip, linear_live
 
         (y,) = ctx.saved_tensors
         w0, w1 = ctx.w
@@ -343,18 +343,13 @@ class _FrozenSwigluMlpFn(torch.autograd.Function):
             g2 = g2.contiguous()
         wdt, wt0, wt1 = (dgrad_weight(w, torch.bfloat16) for w in (ctx.wd, w0, w1))
         if wdt is not None and wt0 is not None and wt1 is not None:
-            if linear_live.mlp_fused_backward():
-                dg, du = linear_live.linear_live_dswiglu(g2, wdt, y, part)
-            else:
-                # the backward epilogue did not clear its gate (linear_live._mlp_fused_backward): the two launches it would replace
-                from .. import hip
-
-                c = w0.shape[0]
-                d_act = linear_live.linear_live(g2, wdt, part)
-                dg, du = torch.empty_like(d_act), torch.empty_like(d_act)
-                hip.call("dalm_swiglu_bwd_2d_live", hip.ptr(d_act), hip.ptr(y), hip.ptr(y[:, c:]), hip.ptr(dg), hip.ptr(du),
-                         hip.dtype_code(y), y.shape[0], c, c, 2 * c, 2 * c, c, c, hip.ptr(ctx.live), hip.stream())
-            dx = linear_live.linear_live(dg, wt0, part)                      # as _FrozenPairFn.backward: fresh, zeros for dead rows,
+            # two launches: a SwiGLU backward inside the down dgrad's epilogue measured slower than this pair
+            c = w0.shape[0]
+            d_act = linear_live.linear_live(g2, wdt, part)
+            dg, du = torch.empty_like(d_act), torch.empty_like(d_act)
+            hip.call("dalm_swiglu_bwd_2d_live", hip.ptr(d_act), hip.ptr(y), hip.ptr(y[:, c:]), hip.ptr(dg), hip.ptr(du),
+                     hip.dtype_code(y), y.shape[0], c, c, 2 * c, 2 * c, c, c, hip.ptr(ctx.live), hip.stream())
+            dx = linear_live.linear_live(dg, wt0, part)                     # as _FrozenPairFn.backward: fresh, zeros for dead rows,
             dx = linear_live.linear_live(du, wt1, part, out=dx, accumulate=True)    # then accumulated in f32 with one rounding
             return dx.view(ctx.xshape), None, None, None, None, None
         raise RuntimeError("frozen SwiGLU MLP node: the transposed dgrad copies of its weights are missing (make them outside a "

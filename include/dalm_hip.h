@@ -847,28 +847,22 @@ int dalm_sim_grad_bf16x3(const float* A, const float* Bm, int64_t m, int64_t n, 
  *   operand: a tile of dead rows multiplies nothing).  Nothing of a dead row of A is read.  Dead rows of C: accumulate = 0 - zeros
  *   (the `_live` contract); accumulate = 1 - left as they are, and a live row gets bf16(f32(C) + A . W^T), one rounding.  Columns
  *   >= N of a strided C are not touched.  n_live is read on the device and clamped to [0, R]; perm entries outside [0, R) select
- *   nothing.  The launch shape depends on (R, N, K, form) only: no host sync, replayable in a hipGraph with a changing mask.
- *   form: rows per workgroup tile, 256 or 128; 0 = by shape (dalm_linear_live_form, a table measured at the padded step's shapes).
+ *   nothing.  The launch shape depends on (R, N, K) only: no host sync, replayable in a hipGraph with a changing mask.
  *   K % 64 == 0, N % 8 == 0, lda >= K, ldc >= N, both strides multiples of 8, (R + 256) lda and (N + 256) K below 2^31 elements
  *   (DALM_E_SHAPE); A / W / C 16-byte aligned (DALM_E_ALIGN).  No bias, bf16 only.  Fixed summation order. */
 int dalm_row_partition(const uint8_t* live, int64_t R, int32_t* perm, int32_t* n_live, dalm_stream_t stream);
-int dalm_linear_live_form(int64_t R, int64_t N, int64_t K);
 int dalm_linear_live(const void* A, int64_t lda, const void* W, void* C, int64_t ldc, int64_t R, int64_t N, int64_t K,
-                     const int32_t* perm, const int32_t* n_live, int accumulate, int form, dalm_stream_t stream);
-/* The frozen SwiGLU MLP of the padded step: SwiGLU inside the epilogues of the two live-row GEMMs around it.  Same main loop,
- * partition and limits as dalm_linear_live (256-row tiles); the element arithmetic is the one definition the dalm_swiglu_* kernels
- * use (csrc/swiglu_math.hpp), so live rows hold the same bits as dalm_linear_live followed by dalm_swiglu_{fwd,bwd}_2d_live.
- * Y, Act, dG and dU are meant as buffers private to one autograd node: dead rows are NOT WRITTEN (no zeros), and nothing of a
- * dead row of A / dOut / Y is read.  perm entries outside [0, R) select nothing.
+                     const int32_t* perm, const int32_t* n_live, int accumulate, dalm_stream_t stream);
+/* The frozen SwiGLU MLP of the padded step: SwiGLU inside the epilogue of its gate | up live-row GEMM.  Same main loop, partition
+ * and limits as dalm_linear_live; the element arithmetic is the one definition the dalm_swiglu_* kernels use
+ * (csrc/swiglu_math.hpp), so live rows hold the same bits as dalm_linear_live followed by dalm_swiglu_fwd_2d_live.
+ * Y and Act are meant as buffers private to one autograd node: dead rows are NOT WRITTEN (no zeros), and nothing of a dead row of
+ * A is read.  perm entries outside [0, R) select nothing.
  * dalm_linear_live_swiglu:  for i < n_live, r = perm[i]:  Y[r, :] = A[r, :] . Wcat^T with Wcat = [Wgate; Wup] [2C, K] contiguous
  *   (Y[r, :C] = gate, Y[r, C:2C] = up; Y [R, 2C], row stride ldy) and Act[r, :] = rb(rb(silu(gate)) up) (Act [R, C], row stride
  *   ldact).  A workgroup tile is 256 rows x (128 gate + 128 up columns of the same activation columns): C % 128 == 0, K % 64 == 0,
  *   lda >= K, ldy >= 2C, ldact >= C, strides multiples of 8 (DALM_E_SHAPE); pointers 16-byte aligned (DALM_E_ALIGN).
- *   (Argument errors come back before the table is looked at.)
- * dalm_linear_live_dswiglu: the down projection's dgrad with the SwiGLU backward behind it: d_act = dOut[r, :] . WdT^T (dOut [R, H],
- *   row stride ldd; WdT [C, H] contiguous = the transposed down weight) is rounded to bf16 in registers and never stored;
- *   dG[r, :], dU[r, :] = swiglu_bwd(d_act, Y[r, :C], Y[r, C:2C]) ([R, C], row strides lddg / lddu).  C % 8 == 0, H % 64 == 0,
- *   ldd >= H, ldy >= 2C, lddg / lddu >= C, strides multiples of 8 (DALM_E_SHAPE); pointers 16-byte aligned (DALM_E_ALIGN). */
+ *   (Argument errors come back before the table is looked at.) */
 /* dalm_linear_live_swiglu_prepare: the epilogue of the forward reads rb(silu(g)) from a table of all 65536 bf16 g (128 KB per device,
  *   filled by a kernel with the same arithmetic).  The first dalm_linear_live_swiglu on a device fills it too, synchronising `stream`
  *   once - which a stream capture forbids: inside a capture an unfilled table is an error (positive, hipErrorStreamCaptureUnsupported).
@@ -876,9 +870,6 @@ int dalm_linear_live(const void* A, int64_t lda, const void* W, void* C, int64_t
 int dalm_linear_live_swiglu_prepare(dalm_stream_t stream);
 int dalm_linear_live_swiglu(const void* A, int64_t lda, const void* Wcat, void* Y, int64_t ldy, void* Act, int64_t ldact, int64_t R,
                             int64_t C, int64_t K, const int32_t* perm, const int32_t* n_live, dalm_stream_t stream);
-int dalm_linear_live_dswiglu(const void* dOut, int64_t ldd, const void* WdT, const void* Y, int64_t ldy, void* dG, int64_t lddg,
-                             void* dU, int64_t lddu, int64_t R, int64_t C, int64_t H, const int32_t* perm, const int32_t* n_live,
-                             dalm_stream_t stream);
 
 #ifdef __cplusplus
 }

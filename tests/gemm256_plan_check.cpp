@@ -45,23 +45,22 @@ static void check_tile_order() {
         const unsigned bands = (MT + 7) / 8;                      // restated: bands of <= 8 row tiles, as even as possible
         CHECK(gemm256_band(MT) == (MT + bands - 1) / bands && gemm256_band(MT) <= 8);
         check_bijection(xcd_order, gemm256_band(MT), NT, MT, MT * NT);
-        // the live form, for both tile heights: the kernel bands the mtl live row tiles and walks them with the first mtl * NT
-        // blocks; block nlb + s skips tile (mtl + s / NT, s % NT)
-        for (const int rows : {256, 128})
-          for (unsigned want = 0; want <= MT; ++want)
-            for (const int nlive : {static_cast<int>(want) * rows, static_cast<int>(want) * rows - (rows - 1)}) {
-              if (nlive < 0) continue;
-              c3 = nlive;
-              const unsigned mtl = static_cast<unsigned>((nlive + rows - 1) / rows), nlb = mtl * NT;
-              CHECK(mtl == want);
-              if (mtl) check_bijection(xcd_order, gemm256_band(mtl), NT, mtl, nlb);
-              std::vector<char> dead(static_cast<size_t>(MT - mtl) * NT, 0);
-              for (unsigned b = nlb; b < MT * NT; ++b) {
-                const unsigned s = b - nlb, mt = mtl + s / NT, nt = s % NT;
-                CHECK(mt >= mtl && mt < MT && !dead[static_cast<size_t>(mt - mtl) * NT + nt]);
-                if (mt < MT) dead[static_cast<size_t>(mt - mtl) * NT + nt] = 1;
-              }
+        // the live form: the kernel bands the mtl live row tiles (256 rows each) and walks them with the first mtl * NT blocks;
+        // block nlb + s skips tile (mtl + s / NT, s % NT)
+        for (unsigned want = 0; want <= MT; ++want)
+          for (const int nlive : {static_cast<int>(want) * 256, static_cast<int>(want) * 256 - 255}) {
+            if (nlive < 0) continue;
+            c3 = nlive;
+            const unsigned mtl = static_cast<unsigned>((nlive + 255) / 256), nlb = mtl * NT;
+            CHECK(mtl == want);
+            if (mtl) check_bijection(xcd_order, gemm256_band(mtl), NT, mtl, nlb);
+            std::vector<char> dead(static_cast<size_t>(MT - mtl) * NT, 0);
+            for (unsigned b = nlb; b < MT * NT; ++b) {
+              const unsigned s = b - nlb, mt = mtl + s / NT, nt = s % NT;
+              CHECK(mt >= mtl && mt < MT && !dead[static_cast<size_t>(mt - mtl) * NT + nt]);
+              if (mt < MT) dead[static_cast<size_t>(mt - mtl) * NT + nt] = 1;
             }
+          }
       }
 }
 
@@ -97,12 +96,12 @@ static void check_dense(int64_t R, int64_t V, int64_t K) {
   CHECK(g.pitchH == K * 2 && g.pitchW == K * 2 && g.tpd == 0 && g.tpd_inv == 0 && g.seg_bytes == 0);
 }
 
-static void check_live(int64_t R, int64_t N, int64_t K, int64_t lda, int64_t w_rows, int rows, int cols) {
+static void check_live(int64_t R, int64_t N, int64_t K, int64_t lda, int64_t w_rows, int cols) {
   c0 = R; c1 = N; c2 = K; c3 = lda;
-  const Gemm256Plan pl = gemm256_plan(gemm256_live(R, N, K, lda, w_rows, rows, cols), "too big");
+  const Gemm256Plan pl = gemm256_plan(gemm256_live(R, N, K, lda, w_rows, cols), "too big");
   expect_ok(pl);
   const Gemm256Geom& g = pl.g;
-  CHECK(g.R == R && g.V == N && g.K == K && g.MT == ceil_div(R, rows) && g.NT == ceil_div(N, cols) && g.xcd_order == 1 && g.gh == 1);
+  CHECK(g.R == R && g.V == N && g.K == K && g.MT == ceil_div(R, 256) && g.NT == ceil_div(N, cols) && g.xcd_order == 1 && g.gh == 1);
   CHECK(g.bytesH == static_cast<uint64_t>(R - 1) * lda * 2 + static_cast<uint64_t>(K) * 2);
   CHECK(g.bytesW == static_cast<uint64_t>(w_rows) * K * 2 && g.pitchH == lda * 2 && g.pitchW == K * 2);
   CHECK(g.tpd == 0 && g.tpd_inv == 0 && g.seg_bytes == 0);
@@ -186,15 +185,15 @@ static void check_guards() {
   expect_ok(gemm256_plan(gemm256_dense(1, last, 64), "too big"));
   expect_fail(gemm256_plan(gemm256_dense(1, last + 1, 64), "too big"), "too big");
   // the live entries: the span of A counts lda, the span of W its w_rows (2 C for the gate | up weight)
-  expect_ok(gemm256_plan(gemm256_live(33554430 / 2 - 1 - 256, 8, 64, 128, 8, 256, 256), "too big"));
-  expect_fail(gemm256_plan(gemm256_live(33554430 / 2 - 256, 8, 64, 128, 8, 256, 256), "too big"), "too big");
-  expect_ok(gemm256_plan(gemm256_live(1, (last - 1) / 2, 64, 64, last - 1, 256, 128), "too big"));
-  expect_fail(gemm256_plan(gemm256_live(1, (last + 1) / 2, 64, 64, last + 1, 256, 128), "too big"), "too big");
+  expect_ok(gemm256_plan(gemm256_live(33554430 / 2 - 1 - 256, 8, 64, 128, 8, 256), "too big"));
+  expect_fail(gemm256_plan(gemm256_live(33554430 / 2 - 256, 8, 64, 128, 8, 256), "too big"), "too big");
+  expect_ok(gemm256_plan(gemm256_live(1, (last - 1) / 2, 64, 64, last - 1, 128), "too big"));
+  expect_fail(gemm256_plan(gemm256_live(1, (last + 1) / 2, 64, 64, last + 1, 128), "too big"), "too big");
   // tiles: 46340 * 46341 = 2147441940 <= 0x7fffffff < 2147488281 = 46341 * 46341 (the spans stay far below 4 GB)
   expect_ok(gemm256_plan(gemm256_dense(46340 * 256, 46341 * 256, 64), "too big"));
   expect_fail(gemm256_plan(gemm256_dense(46341 * 256, 46341 * 256, 64), "too big"), "too many tiles for one launch");
-  expect_ok(gemm256_plan(gemm256_live(46340 * 128, 46341 * 128, 64, 64, 2 * 46341 * 128, 128, 128), "too big"));
-  expect_fail(gemm256_plan(gemm256_live(46340 * 128 + 1, 46341 * 128, 64, 64, 2 * 46341 * 128, 128, 128), "too big"),
+  expect_ok(gemm256_plan(gemm256_live(46340 * 256, 46341 * 128, 64, 64, 2 * 46341 * 128, 128), "too big"));
+  expect_fail(gemm256_plan(gemm256_live(46340 * 256 + 1, 46341 * 128, 64, 64, 2 * 46341 * 128, 128), "too big"),
               "too many tiles for one launch");
   // the contraction width
   expect_fail(gemm256_plan(gemm256_dense(8, 8, 96), "too big"), "the contraction width must be a positive multiple of 64");
@@ -211,9 +210,9 @@ int main(int argc, char** argv) {
   // lm_head and live-row shapes: one row, the 256 / 257 tile edge, strided rows, the narrowest output, the padded step's own
   check_dense(1, 1, 64); check_dense(256, 32000, 4096); check_dense(257, 50257, 768); check_dense(3584, 32000, 4096);
   check_dense(3584, 4096, 32000);
-  check_live(1, 8, 64, 64, 8, 256, 256); check_live(256, 264, 64, 72, 264, 128, 256); check_live(257, 8, 128, 136, 8, 128, 256);
-  check_live(257, 264, 64, 64, 264, 256, 256); check_live(2897, 5504, 2048, 2048, 11008, 256, 128);
-  check_live(300, 2048, 5504, 5512, 2048, 256, 256);
+  check_live(1, 8, 64, 64, 8, 256); check_live(256, 264, 64, 72, 264, 256); check_live(257, 8, 128, 136, 8, 256);
+  check_live(257, 264, 64, 64, 264, 256); check_live(2897, 5504, 2048, 2048, 11008, 128);
+  check_live(300, 2048, 5504, 5512, 2048, 256);
   long long m, n, D;
   int shapes = 0;
   while (fscanf(in, "%lld %lld %lld", &m, &n, &D) == 3) { check_shape(m, n, D); ++shapes; }

@@ -1,4 +1,4 @@
-"""`dalm_row_partition` / `dalm_linear_live` / `dalm_linear_live_form` without a GPU: declared in the header, exported by the
+"""`dalm_row_partition` / `dalm_linear_live` without a GPU: declared in the header, exported by the
 library and listed in the ctypes table with matching arity; every argument error comes back with its DALM_E_* code before
 anything is enqueued (the pointers below are host memory: a launch would fail differently)."""
 import ctypes as C
@@ -9,7 +9,7 @@ import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
 HEADER = ROOT / "include" / "dalm_hip.h"
-NAMES = ("dalm_row_partition", "dalm_linear_live_form", "dalm_linear_live")
+NAMES = ("dalm_row_partition", "dalm_linear_live")
 E_NULL, E_SHAPE, E_ALIGN = -1, -2, -4
 
 
@@ -30,8 +30,7 @@ def test_entry_points_in_header_library_and_table(lib):
         assert m, f"{name} is not declared in include/dalm_hip.h"
         assert hasattr(lib, name), f"{name} is not exported by the library"
         assert name in hip.SIGNATURES and len(hip.SIGNATURES[name][1]) == m.group(1).count(",") + 1
-        if name != "dalm_linear_live_form":
-            assert m.group(1).rstrip().endswith("dalm_stream_t stream")
+        assert m.group(1).rstrip().endswith("dalm_stream_t stream")
 
 
 def _buffers():
@@ -40,11 +39,11 @@ def _buffers():
     return raw, [base + 1024 * i for i in range(6)]
 
 
-def _linear(lib, p, R=4, N=8, K=64, lda=None, ldc=None, accumulate=0, form=0, null=None, **over):
+def _linear(lib, p, R=4, N=8, K=64, lda=None, ldc=None, accumulate=0, null=None, **over):
     a = dict(A=p[0], W=p[1], C=p[2], perm=p[3], n_live=p[4])
     a.update(over)
     args = [a["A"], K if lda is None else lda, a["W"], a["C"], N if ldc is None else ldc, R, N, K, a["perm"], a["n_live"],
-            accumulate, form, None]
+            accumulate, None]
     if null is not None:
         args[null] = None
     return lib.dalm_linear_live(*args)
@@ -70,7 +69,7 @@ def test_shapes(lib):
     for bad in (dict(lda=56), dict(lda=68), dict(ldc=4), dict(N=16, ldc=20), dict(N=16, ldc=8)):
         assert _linear(lib, p, **bad) == E_SHAPE, bad
     assert b"row strides" in lib.dalm_last_error_string()
-    for bad in (dict(form=1), dict(form=64), dict(form=512), dict(form=-128), dict(accumulate=2), dict(accumulate=-1)):
+    for bad in (dict(accumulate=2), dict(accumulate=-1)):
         assert _linear(lib, p, **bad) == E_SHAPE, bad
     # operands above 4 GB: the A span (R + 256) lda 2 bytes, the W span (N + 256) K 2 bytes
     assert _linear(lib, p, R=1 << 20, K=4096) == E_SHAPE and b"4 GB" in lib.dalm_last_error_string()
@@ -92,7 +91,3 @@ def test_alignment(lib):
     assert lib.dalm_row_partition(p[0], 4, p[3], p[4] + 1, None) == E_ALIGN
     del raw
 
-
-def test_form_table(lib):
-    assert lib.dalm_linear_live_form(4608, 4096, 4096) in (128, 256)
-    assert lib.dalm_linear_live_form(7, 8, 64) == 256                  # unlisted shapes: the 256-row form

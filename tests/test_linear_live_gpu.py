@@ -24,7 +24,6 @@ C_TOL = 2.0 ** -24
 KS = (64, 128, 192)                 # no loop iteration / even / odd tail of the two-buffer K loop
 NS = (8, 256, 264)                  # one partial column tile / exactly one / one and a partial
 RS = (1, 255, 256, 257, 513)
-FORMS = (256, 128)
 
 
 @pytest.fixture(scope="module")
@@ -75,7 +74,7 @@ def _vec(R, count, seed, dev):
     return v.to(dev)
 
 
-def _run(dev, a, w, old, vec, accumulate, form, strided):
+def _run(dev, a, w, old, vec, accumulate, strided):
     """One launch on poisoned inputs -> (C view, whole C buffer).  Strided: A and C are column views at offset 8 of buffers 16
     columns wider (lda > K, ldc > N)."""
     from dalm_amd import linear_live
@@ -92,14 +91,14 @@ def _run(dev, a, w, old, vec, accumulate, form, strided):
     if accumulate:
         cv.copy_(old)
     part = linear_live.row_partition(vec)
-    out = linear_live.linear_live(av, w, part, out=cv, accumulate=accumulate, form=form)
+    out = linear_live.linear_live(av, w, part, out=cv, accumulate=accumulate)
     assert out.data_ptr() == cv.data_ptr()
     return cv, cbuf
 
 
-def _verify(dev, R, N, K, vec, accumulate, form, strided, tag):
+def _verify(dev, R, N, K, vec, accumulate, strided, tag):
     a, w, old, ref, sabs = _case(R, N, K, dev)
-    cv, cbuf = _run(dev, a, w, old, vec, accumulate, form, strided)
+    cv, cbuf = _run(dev, a, w, old, vec, accumulate, strided)
     keep = vec != 0
     want = ref + old.double() if accumulate else ref
     ex = _excess(cv[keep], want[keep], sabs[keep])
@@ -122,8 +121,7 @@ def test_shapes_live_counts_modes_and_forms(dev, K, N, strided):
         for count in _live_counts(R):
             vec = _vec(R, count, 31 * R + count, dev)
             for accumulate in (False, True):
-                for form in FORMS:
-                    _verify(dev, R, N, K, vec, accumulate, form, strided, f"R={R} N={N} K={K} live={count} acc={accumulate} form={form}")
+                _verify(dev, R, N, K, vec, accumulate, strided, f"R={R} N={N} K={K} live={count} acc={accumulate}")
 
 
 def _prefix_mask(dev):
@@ -143,24 +141,8 @@ def test_live_patterns(dev, pattern):
         vec = torch.zeros(R, dtype=torch.uint8, device=dev)
         vec[(1 if pattern.endswith("odd") else 0)::2] = 1
     for accumulate in (False, True):
-        for form in FORMS:
-            for strided in (False, True):
-                _verify(dev, R, N, K, vec, accumulate, form, strided, f"{pattern} acc={accumulate} form={form} strided={strided}")
-
-
-def test_form_by_shape_is_one_of_the_two(dev):
-    """form = 0 takes the launcher's table: same result as naming that form."""
-    from dalm_amd import hip
-
-    R, N, K = 257, 264, 128
-    vec = _vec(R, 200, 5, dev)
-    a, w, old, ref, sabs = _case(R, N, K, dev)
-    form = hip.load().dalm_linear_live_form(R, N, K)
-    assert form in FORMS
-    by_table, _ = _run(dev, a, w, old, vec, False, 0, False)
-    named, _ = _run(dev, a, w, old, vec, False, form, False)
-    assert torch.equal(by_table.view(torch.int16), named.view(torch.int16))
-    assert hip.load().dalm_linear_live_form(4608, 11008, 4096) in FORMS
+        for strided in (False, True):
+            _verify(dev, R, N, K, vec, accumulate, strided, f"{pattern} acc={accumulate} strided={strided}")
 
 
 def test_library_gemm_sets_the_constant(dev):

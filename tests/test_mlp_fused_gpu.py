@@ -1,10 +1,10 @@
-"""`dalm_linear_live_swiglu` and `dalm_linear_live_dswiglu` (dalm_amd/csrc/linear_live.hip) on the GPU against the unfused pair of entry
-points they replace, run in the same process: `dalm_linear_live` followed by `dalm_swiglu_fwd_2d_live` / `dalm_swiglu_bwd_2d_live`
-(those are checked against fp64 in test_linear_live_gpu.py and test_tower_ops_gpu.py).  Same contraction order, same element
-arithmetic (csrc/swiglu_math.hpp): the live rows must be EQUAL, bit for bit.
+"""`dalm_linear_live_swiglu` (dalm_amd/csrc/linear_live.hip) on the GPU against the unfused pair of entry points it replaces, run in
+the same process: `dalm_linear_live` followed by `dalm_swiglu_fwd_2d_live` (those are checked against fp64 in
+test_linear_live_gpu.py and test_tower_ops_gpu.py).  Same contraction order, same element arithmetic (csrc/swiglu_math.hpp): the
+live rows must be EQUAL, bit for bit.
 
 Dead rows of every input hold NaN: they must not be read.  Every output arrives filled with a sentinel, with guard rows in front of
-and behind it: dead rows and guard rows must still hold the sentinel afterwards - the fused entry points write nothing there.
+and behind it: dead rows and guard rows must still hold the sentinel afterwards - the fused entry point writes nothing there.
 """
 import math
 
@@ -55,14 +55,12 @@ _INPUTS = {}
 
 
 def _inputs(C, K, dev):
-    """a [R, K], wcat [2C, K], d_out [R, K], wdt [C, K] (bf16 on the device), shared by every case of one shape."""
+    """a [R, K], wcat [2C, K] (bf16 on the device), shared by every case of one shape."""
     if (C, K) not in _INPUTS:
         g = torch.Generator().manual_seed(100 * C + K)
         a = torch.randn(R, K, generator=g).bfloat16()
         wcat = (2.0 * torch.randn(2 * C, K, generator=g) / math.sqrt(K)).bfloat16()
-        d_out = torch.randn(R, K, generator=g).bfloat16()
-        wdt = (torch.randn(C, K, generator=g) / math.sqrt(K)).bfloat16()
-        _INPUTS[(C, K)] = tuple(t.to(dev) for t in (a, wcat, d_out, wdt))
+        _INPUTS[(C, K)] = tuple(t.to(dev) for t in (a, wcat))
     return _INPUTS[(C, K)]
 
 
@@ -96,7 +94,7 @@ def _fused_fwd(a, wcat, C, K, part, dev):
 def test_forward_equals_the_unfused_pair(dev, C, K):
     from dalm_amd import linear_live
 
-    a0, wcat, _, _ = _inputs(C, K, dev)
+    a0, wcat = _inputs(C, K, dev)
     for count in LIVE_COUNTS:
         for name, vec in _masks(count, dev):
             tag = f"C={C} K={K} live={count} {name}"
@@ -114,58 +112,12 @@ def test_forward_equals_the_unfused_pair(dev, C, K):
             _assert_untouched(abuf, act, keep, tag + " (act)")
 
 
-def _y_for_backward(C, H, vec, part, dev):
-    """[gate | up] of the unfused forward (C = 392 has no fused one), with the saturation ends of exp(-g) planted in the gate half:
-    +-30 and 0 in three columns of every row; dead rows NaN."""
-    from dalm_amd import linear_live
-
-    a0, _, _, _ = _inputs(C, H, dev)
-    g = torch.Generator().manual_seed(5 * C + H)
-    wcat = (2.0 * torch.randn(2 * C, H, generator=g) / math.sqrt(H)).bfloat16().to(dev)
-    y = linear_live.linear_live(a0, wcat, part)
-    y[:, 1] = 30.0
-    y[:, C - 2] = -30.0
-    y[:, 5] = 0.0
-    return _poisoned(y, vec)
-
-
-@pytest.mark.parametrize("H", [64, 192])
-@pytest.mark.parametrize("C", [128, 384, 392])       # 392: the column edge of an ordinary 256-column tile
-def test_backward_equals_the_unfused_pair(dev, C, H):
-    from dalm_amd import hip, linear_live
-
-    _, _, d0, _ = _inputs(C, H, dev)
-    wdt = _inputs(C, H, dev)[3]
-    for count in LIVE_COUNTS:
-        for name, vec in _masks(count, dev):
-            tag = f"C={C} H={H} live={count} {name}"
-            keep = vec != 0
-            part = linear_live.row_partition(vec)
-            y = _y_for_backward(C, H, vec, part, dev)
-            d_out = _poisoned(d0, vec)
-            d_act = linear_live.linear_live(d_out, wdt, part)
-            dg_ref = torch.full((R, C), SENT, dtype=torch.bfloat16, device=dev)
-            du_ref = torch.full((R, C), SENT, dtype=torch.bfloat16, device=dev)
-            hip.call("dalm_swiglu_bwd_2d_live", hip.ptr(d_act), hip.ptr(y[:, :C]), hip.ptr(y[:, C:]), hip.ptr(dg_ref), hip.ptr(du_ref),
-                     hip.dtype_code(y), R, C, C, 2 * C, 2 * C, C, C, hip.ptr(vec), hip.stream())
-            gbuf, dg = _guarded(C, dev)
-            ubuf, du = _guarded(C, dev)
-            hip.call("dalm_linear_live_dswiglu", hip.ptr(d_out), H, hip.ptr(wdt), hip.ptr(y), 2 * C, hip.ptr(dg), C, hip.ptr(du), C,
-                     R, C, H, hip.ptr(part[0]), hip.ptr(part[1]), hip.stream())
-            torch.cuda.synchronize()
-            assert torch.equal(_bits(dg[keep]), _bits(dg_ref[keep])), f"{tag}: d_gate differs from dalm_swiglu_bwd_2d_live"
-            assert torch.equal(_bits(du[keep]), _bits(du_ref[keep])), f"{tag}: d_up differs from dalm_swiglu_bwd_2d_live"
-            assert torch.isfinite(dg[keep].float()).all() and torch.isfinite(du[keep].float()).all(), f"{tag}: NaN leaked in"
-            _assert_untouched(gbuf, dg, keep, tag + " (d_gate)")
-            _assert_untouched(ubuf, du, keep, tag + " (d_up)")
-
-
 def test_wrappers_return_the_same_bits(dev):
-    """linear_live.linear_live_swiglu / linear_live_dswiglu (fresh torch.empty outputs) against the raw calls above."""
+    """linear_live.linear_live_swiglu (fresh torch.empty outputs) against the raw calls above."""
     from dalm_amd import linear_live
 
     C, K = 384, 192
-    a0, wcat, d0, wdt = _inputs(C, K, dev)
+    a0, wcat = _inputs(C, K, dev)
     vec = _masks(257, dev)[0][1]
     keep = vec != 0
     part = linear_live.row_partition(vec)
@@ -173,17 +125,12 @@ def test_wrappers_return_the_same_bits(dev):
     y_ref = linear_live.linear_live(a0, wcat, part)
     assert torch.equal(_bits(y[keep]), _bits(y_ref[keep]))
     assert torch.equal(_bits(act[keep]), _bits(_swiglu_fwd_ref(y_ref, C, vec)[keep]))
-    dg, du = linear_live.linear_live_dswiglu(_poisoned(d0, vec), wdt, y, part)
-    assert dg.shape == (R, C) and du.shape == (R, C)
-    assert torch.isfinite(dg[keep].float()).all() and torch.isfinite(du[keep].float()).all()
 
 
 def test_a_corrupt_partition_stores_nothing_out_of_bounds(dev):
     """perm entries outside [0, R) select nothing: only the rows a valid entry names may change; guard rows keep their sentinel."""
-    from dalm_amd import hip
-
     C, K = 384, 192
-    a, wcat, d_out, wdt = _inputs(C, K, dev)
+    a, wcat = _inputs(C, K, dev)
     g = torch.Generator().manual_seed(11)
     perm = torch.randperm(R, generator=g).to(torch.int32)
     bad = torch.tensor([-1, R, R + 1, R + GUARD, 2 ** 31 - 1, -2 ** 31, -R, 1 << 20], dtype=torch.int32)
@@ -199,12 +146,3 @@ def test_a_corrupt_partition_stores_nothing_out_of_bounds(dev):
     _assert_untouched(ybuf, y, named, "forward y")
     _assert_untouched(abuf, act, named, "forward act")
     assert torch.isfinite(y[named].float()).all() and not bool((act[named] == SENT).all())
-    yin = torch.randn(R, 2 * C, generator=g).bfloat16().to(dev)
-    gbuf, dg = _guarded(C, dev)
-    ubuf, du = _guarded(C, dev)
-    hip.call("dalm_linear_live_dswiglu", hip.ptr(d_out), K, hip.ptr(wdt), hip.ptr(yin), 2 * C, hip.ptr(dg), C, hip.ptr(du), C,
-             R, C, K, hip.ptr(part[0]), hip.ptr(part[1]), hip.stream())
-    torch.cuda.synchronize()
-    _assert_untouched(gbuf, dg, named, "backward d_gate")
-    _assert_untouched(ubuf, du, named, "backward d_up")
-    assert torch.isfinite(dg[named].float()).all() and torch.isfinite(du[named].float()).all()

@@ -5,7 +5,7 @@ three mixed tiles, LoRA on q / v) over 2 x 96 left-padded rows through `RagE2ESt
 shapes for the test (the measured table holds the 4608-row shapes only), as tests/test_linear_live_step_gpu.py does.
 
 Second test: the MLP forward and backward captured in a hipGraph inside a padded tower call and replayed with a second mask - the
-`perm` / `n_live` that `dalm_row_partition` writes INSIDE the graph are what the two new epilogues must read on every replay.
+`perm` / `n_live` that `dalm_row_partition` writes INSIDE the graph are what the node's kernels must read on every replay.
 """
 import copy
 
@@ -76,27 +76,22 @@ class _Recording(torch.optim.SGD):
 
 
 class _Counted:
-    """Count the launches of the two fused entry points through their wrappers."""
+    """Count the launches of the fused entry point through its wrapper."""
 
     def __init__(self, monkeypatch):
         from dalm_amd import linear_live
 
-        self.n = {"fwd": 0, "bwd": 0}
-        fwd, bwd = linear_live.linear_live_swiglu, linear_live.linear_live_dswiglu
+        self.n = {"fwd": 0}
+        fwd = linear_live.linear_live_swiglu
 
         def cf(*a, **k):
             self.n["fwd"] += 1
             return fwd(*a, **k)
 
-        def cb(*a, **k):
-            self.n["bwd"] += 1
-            return bwd(*a, **k)
-
         monkeypatch.setattr(linear_live, "linear_live_swiglu", cf)
-        monkeypatch.setattr(linear_live, "linear_live_dswiglu", cb)
 
 
-def _run(dev, fused, fused_backward=False):
+def _run(dev, fused):
     from dalm_amd import linear_live
     from dalm_amd.models import AutoModelForRagE2E
     from dalm_amd.models.lora import LoRALinear
@@ -115,14 +110,12 @@ def _run(dev, fused, fused_backward=False):
     linear_live.set_table(SHAPES)
     linear_live.set_enabled(True)
     linear_live.set_mlp_fused(fused)
-    linear_live.set_mlp_fused_backward(fused_backward)
     try:
         loss = step(_batch(dev)).detach().clone()
         torch.cuda.synchronize()
     finally:
         linear_live.set_table(None)
         linear_live.set_mlp_fused(True)
-        linear_live.set_mlp_fused_backward(False)
     return loss, {n: gr for (n, _), gr in zip(named, opt.seen)}
 
 
@@ -133,19 +126,16 @@ def test_step_with_the_fused_node_equals_the_step_without(monkeypatch):
     dev = torch.device("cuda:0")
     counted = _Counted(monkeypatch)
     loss_off, g_off = _run(dev, fused=False)
-    assert counted.n == {"fwd": 0, "bwd": 0}, counted.n
+    assert counted.n == {"fwd": 0}, counted.n
     gen = [n for n in g_off if "generator" in n]
     assert gen and all(float(g_off[n].float().norm()) > 0 for n in gen), "a generator LoRA gradient is zero: nothing compared"
-    # the node as it ships (forward epilogue fused, backward as two launches), then with the backward epilogue too
-    for fused_backward in (False, True):
-        before = dict(counted.n)
-        loss_on, g_on = _run(dev, fused=True, fused_backward=fused_backward)
-        ran = {k: counted.n[k] - before[k] for k in before}
-        print(f"fused launches (backward epilogue {fused_backward}): {ran}; loss off {float(loss_off):.8f} on {float(loss_on):.8f}")
-        assert ran["fwd"] >= 1 and (ran["bwd"] >= 1) == fused_backward, f"the fused node did not run as asked: {ran}"
-        assert torch.equal(loss_on, loss_off), (float(loss_on), float(loss_off))
-        differing = [n for n in sorted(g_off) if not torch.equal(g_on[n], g_off[n])]
-        assert not differing, (fused_backward, differing)
+    # the node: forward epilogue fused, backward as two launches
+    loss_on, g_on = _run(dev, fused=True)
+    print(f"fused launches: {counted.n}; loss off {float(loss_off):.8f} on {float(loss_on):.8f}")
+    assert counted.n["fwd"] >= 1, f"the fused node did not run: {counted.n}"
+    assert torch.equal(loss_on, loss_off), (float(loss_on), float(loss_off))
+    differing = [n for n in sorted(g_off) if not torch.equal(g_on[n], g_off[n])]
+    assert not differing, differing
 
 
 def _mlp(dev):
@@ -169,7 +159,7 @@ def _masks(dev):
     return first.to(dev), second.to(dev)
 
 
-def _captured(dev, fused, x0, g0, masks, fused_backward=False):
+def _captured(dev, fused, x0, g0, masks):
     """MLP forward + backward inside a padded tower call, captured once with the first mask, replayed with both -> [(out, dx)]."""
     from dalm_amd import linear_live, live_rows
 
@@ -185,7 +175,6 @@ def _captured(dev, fused, x0, g0, masks, fused_backward=False):
 
     linear_live.set_table(SHAPES)
     linear_live.set_mlp_fused(fused)
-    linear_live.set_mlp_fused_backward(fused_backward)
     try:
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -206,7 +195,6 @@ def _captured(dev, fused, x0, g0, masks, fused_backward=False):
     finally:
         linear_live.set_table(None)
         linear_live.set_mlp_fused(True)
-        linear_live.set_mlp_fused_backward(False)
     return results
 
 
@@ -221,14 +209,9 @@ def test_graph_replay_follows_a_changed_mask(monkeypatch):
     masks = _masks(dev)
     counted = _Counted(monkeypatch)
     off = _captured(dev, False, x0, g0, masks)
-    assert counted.n == {"fwd": 0, "bwd": 0}
-    shipped = _captured(dev, True, x0, g0, masks)
-    assert counted.n["fwd"] >= 1 and counted.n["bwd"] == 0, f"the fused node did not run as it ships: {counted.n}"
-    both = _captured(dev, True, x0, g0, masks, fused_backward=True)
-    assert counted.n["bwd"] >= 1, f"the backward epilogue never ran: {counted.n}"
-    for a, b in zip(shipped, both):
-        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
-    on = both
+    assert counted.n == {"fwd": 0}
+    on = _captured(dev, True, x0, g0, masks)
+    assert counted.n["fwd"] >= 1, f"the fused node did not run: {counted.n}"
     for m, (o_on, d_on), (o_off, d_off) in zip(masks, on, off):
         keep = live_rows.live_rows(m, True).view(B, T) != 0
         assert torch.equal(o_on, o_off) and torch.equal(d_on, d_off)

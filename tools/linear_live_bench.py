@@ -5,17 +5,16 @@
 
 The seven GEMMs of one Llama-2-7b layer and the two of the materialised lm_head at R = 4608 padded rows (18 x 256), each with
   * every row live, and the four masks of `bench.synthetic_batch(dev, 100 + i)` under the generator's shifted rule;
-  * three arms: the kernel in its 256-row and its 128-row tile form, and `F.linear` / `addmm_` through the tuned solution table.
+  * two arms: the kernel, and `F.linear` / `addmm_` through the tuned solution table.
 Every arm is timed inside a hipGraph of LAUNCHES (>= 20) launches, over a ring of weight copies larger than the Infinity Cache
 (in the step every layer brings its own weights from HBM); the median of 5 replays is taken and the spread (max - min) printed.
 FLOP are counted over LIVE rows (2 live N K), `frac` is against the bf16 MFMA peak - for the library arm too, so its frac at a
 padded mask shows what the padding costs.  `win` marks a kernel arm faster than the library arm by more than three times the
 larger of the two spreads: the routing table in dalm_amd/linear_live.py lists exactly those shapes.
 
---mlp-fused: the two fused pieces of the frozen MLP node against the pairs of launches they replace, same protocol and same rule -
-  forward   {dalm_linear_live gate|up + dalm_swiglu_fwd_2d_live}   against dalm_linear_live_swiglu,
-  backward  {dalm_linear_live down dgrad + dalm_swiglu_bwd_2d_live} against dalm_linear_live_dswiglu,
-at the four batch masks.  A piece ships only if it beats its pair by more than three times the larger spread at EVERY mask.
+--mlp-fused: the fused forward of the frozen MLP node against the pair of launches it replaces, same protocol and same rule -
+  forward   {dalm_linear_live gate|up + dalm_swiglu_fwd_2d_live}   against dalm_linear_live_swiglu
+at the four batch masks.  It ships only if it beats its pair by more than three times the larger spread at EVERY mask.
 """
 from __future__ import annotations
 
@@ -109,15 +108,13 @@ def bench_gemm(members, halves, mask_list, dev, emit):
             for j in range(1, nm):
                 y.addmm_(xs[j], w[j].t())
 
-        def kern(form):
-            def run(i):
-                w = ws[i % ring]
-                for j in range(nm):
-                    linear_live.linear_live(xs[j], w[j], part, out=out, accumulate=j > 0, form=form)
-            return run
+        def kern(i):
+            w = ws[i % ring]
+            for j in range(nm):
+                linear_live.linear_live(xs[j], w[j], part, out=out, accumulate=j > 0)
 
         fl = nm * linear_live.flops(n_live, n, k)
-        res = {"library": time_graph(lib), "kernel 256": time_graph(kern(256)), "kernel 128": time_graph(kern(128))}
+        res = {"library": time_graph(lib), "kernel": time_graph(kern)}
         lt, ls = res["library"]
         for arm, (t, sp) in res.items():
             win = ""
@@ -125,26 +122,23 @@ def bench_gemm(members, halves, mask_list, dev, emit):
                 win = "win" if lt - t > 3 * max(sp, ls) else "-"
             emit(f"  {mname:10s} live {n_live:5d}  {arm:11s} {t * 1e6:8.1f} us  spread {sp * 1e6:6.1f} us  "
                  f"{fl / t / 1e12:7.1f} TF/s  frac {fl / t / BF16_PEAK:5.3f}  "
-                 f"tiles {linear_live.tiles(n_live, n, 128 if arm.endswith('128') else 256):5d}  {win}")
+                 f"tiles {linear_live.tiles(n_live, n):5d}  {win}")
         rows.append((mname, res))
     return rows
 
 
 def bench_mlp_fused(mask_list, dev, emit, c=11008, h=4096):
-    """The two paired arms of the fused MLP node; returns {piece: ships?}."""
+    """The paired arms of the fused MLP node's forward; returns {piece: ships?}."""
     from dalm_amd import hip
 
     gen = torch.Generator(device=dev).manual_seed(11)
     ring_f = max(2, min(LAUNCHES, RING_BYTES // (2 * c * h * 2) + 1))
-    ring_b = max(2, min(LAUNCHES, RING_BYTES // (c * h * 2) + 1))
     wcat = [(torch.randn(2 * c, h, device=dev, generator=gen) * 0.02).bfloat16() for _ in range(ring_f)]
-    wdt = [(torch.randn(c, h, device=dev, generator=gen) * 0.02).bfloat16() for _ in range(ring_b)]
     x = torch.randn(R, h, device=dev, generator=gen).bfloat16()
-    d_out = torch.randn(R, h, device=dev, generator=gen).bfloat16()
     y = torch.zeros(R, 2 * c, dtype=torch.bfloat16, device=dev)
-    act, d_act, dg, du = (torch.zeros(R, c, dtype=torch.bfloat16, device=dev) for _ in range(4))
+    act = torch.zeros(R, c, dtype=torch.bfloat16, device=dev)
     dt = hip.dtype_code(y)
-    ships = {"forward": True, "backward": True}
+    ships = {"forward": True}
     for mname, vec in mask_list:
         part = linear_live.row_partition(vec)
         n_live = int(part[1].item())
@@ -159,16 +153,7 @@ def bench_mlp_fused(mask_list, dev, emit, c=11008, h=4096):
             hip.call("dalm_linear_live_swiglu", hip.ptr(x), h, hip.ptr(wcat[i % ring_f]), hip.ptr(y), 2 * c, hip.ptr(act), c, R, c, h,
                      perm, nl, hip.stream())
 
-        def bwd_pair(i):
-            linear_live.linear_live(d_out, wdt[i % ring_b], part, out=d_act)
-            hip.call("dalm_swiglu_bwd_2d_live", hip.ptr(d_act), hip.ptr(y), hip.ptr(y[:, c:]), hip.ptr(dg), hip.ptr(du), dt, R, c, c,
-                     2 * c, 2 * c, c, c, hip.ptr(vec), hip.stream())
-
-        def bwd_fused(i):
-            hip.call("dalm_linear_live_dswiglu", hip.ptr(d_out), h, hip.ptr(wdt[i % ring_b]), hip.ptr(y), 2 * c, hip.ptr(dg), c,
-                     hip.ptr(du), c, R, c, h, perm, nl, hip.stream())
-
-        for piece, pair, fused, n in (("forward", fwd_pair, fwd_fused, 2 * c), ("backward", bwd_pair, bwd_fused, c)):
+        for piece, pair, fused, n in (("forward", fwd_pair, fwd_fused, 2 * c),):
             (tp, sp), (tf, sf) = time_graph(pair), time_graph(fused)
             win = tp - tf > 3 * max(sp, sf)
             ships[piece] = ships[piece] and (win or mname == "all live")
@@ -223,12 +208,12 @@ def main():
     verdict = []
     for name, members, halves in GEMMS:
         n, k = members[0]
-        emit(f"{name}: N = {n}, K = {k}, members {len(members)}, routed form now: {linear_live.table_form(R, n, k)}")
+        emit(f"{name}: N = {n}, K = {k}, members {len(members)}, routed now: "
+             f"{'kernel' if (R, n, k) in linear_live.ROUTED_SHAPES else 'library'}")
         rows = bench_gemm(members, halves, ml, dev, emit)
-        # a shape is routed when one form wins at EVERY batch mask (the all-live line is the no-padding reference)
-        for form in ("kernel 256", "kernel 128"):
-            ok = all(res["library"][0] - res[form][0] > 3 * max(res[form][1], res["library"][1]) for m, res in rows if m != "all live")
-            verdict.append(f"  {name:34s} {form}: {'clears the library at every batch mask' if ok else 'does not clear'}")
+        # a shape is routed when the kernel wins at EVERY batch mask (the all-live line is the no-padding reference)
+        ok = all(res["library"][0] - res["kernel"][0] > 3 * max(res["kernel"][1], res["library"][1]) for m, res in rows if m != "all live")
+        verdict.append(f"  {name:34s} kernel: {'clears the library at every batch mask' if ok else 'does not clear'}")
     emit("verdict (faster than the library arm by > 3 x the larger spread, at all batch masks):")
     for v in verdict:
         emit(v)
