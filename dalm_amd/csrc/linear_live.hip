@@ -1,6 +1,8 @@
 // The padded step's frozen projections over the live rows only (DESIGN.md "Live-row GEMM"): the row partition, dalm_linear_live and
-// the SwiGLU MLP node's fused gate | up GEMM - epilogue policies of the GEMM core of gemm256.hpp whose rows go through the partition.
+// the SwiGLU MLP node's fused gate | up GEMM, the ReLU^2 MLP node's fused up GEMM - epilogue policies of the GEMM core of gemm256.hpp
+// whose rows go through the partition.
 #include "gemm256.hpp"
+#include "relu2_math.hpp"
 #include "swiglu_math.hpp"
 #include <atomic>
 #include <mutex>
@@ -201,6 +203,50 @@ __device__ __forceinline__ void lm_tile_epilogue_live_swiglu(const Lm8Params& p,
   }
 }
 
+// EPI_LIVE_RELU2 (dalm_linear_live_relu2): EPI_LIVE's 256 x 256 tile and pair exchange with two outputs and no accumulating form.
+// y = bf16(A . Wup^T) leaves into out[perm[i]][c0 + column], act = relu(y)^2 OF THE ROUNDED y (relu2_math.hpp: the row-wise
+// kernel's function on the row-wise kernel's input) into out2 at the same place.  No partner, no table: every lane holds what its
+// two columns need.  Dead positions and corrupt perm entries store nothing, anywhere; columns from out_cols on (a partial tile:
+// out_cols % 8 == 0, so a column pair is inside or outside) store nothing either.
+__device__ __forceinline__ void lm_tile_epilogue_live_relu2(const Lm8Params& p, f32x16 (&acc)[4][4], unsigned char* lds, int r0,
+                                                            int c0, int nlive, int wr, int wc, int tid) {
+  const int lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
+  int* row_s = reinterpret_cast<int*>(lds);                    // [256]
+  lm_live_rows_to_lds(p, row_s, r0, nlive, tid);
+  const int colw = wc * 128 + l31;
+  const bool odd = (lane & 1) != 0;
+  unsigned short* yp = static_cast<unsigned short*>(p.out);
+  unsigned short* ap = static_cast<unsigned short*>(p.out2);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int rl4 = wr * 128 + i * 32 + 8 * g + 4 * lhi;   // positions rl4 .. rl4 + 3 = accumulator registers 4 g .. 4 g + 3
+      const int4 rw = *reinterpret_cast<const int4*>(row_s + rl4);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int row = h == 0 ? (odd ? rw.y : rw.x) : (odd ? rw.w : rw.z);
+        unsigned short* yr = yp + static_cast<int64_t>(row) * p.out_pitch;
+        unsigned short* ar = ap + static_cast<int64_t>(row) * p.out2_pitch;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int ce = c0 + ((colw + 32 * j) & ~1);            // even column of the lane pair
+          const float mine_a = acc[i][j][4 * g + 2 * h], mine_b = acc[i][j][4 * g + 2 * h + 1];
+          const float send = odd ? mine_a : mine_b;
+          const float got = __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(send), 0xB1, 0xf, 0xf, false));
+          const unsigned int word = odd ? pack_bf16x2(got, mine_b) : pack_bf16x2(mine_a, got);   // columns (even, odd) of this lane's position
+          if (row >= 0 && ce < p.out_cols) {
+            const float a0 = relu2_fwd_elem<Bf16Round>(__uint_as_float(word << 16));
+            const float a1 = relu2_fwd_elem<Bf16Round>(__uint_as_float(word & 0xffff0000u));
+            *reinterpret_cast<unsigned int*>(yr + ce) = word;
+            *reinterpret_cast<unsigned int*>(ar + ce) = pack_bf16x2(a0, a1);
+          }
+        }
+      }
+    }
+  }
+}
+
 // EPI_LIVE, a tile whose every position is dead (block index past the live tiles): multiplies nothing.  A fresh output gets its
 // zeros here - tile positions r0 .. r0 + 255 of perm, 256 columns from c0, 16 bytes per lane - an accumulating one nothing.
 __device__ __forceinline__ void lm_tile_zero_live(const Lm8Params& p, int r0, int c0, int tid) {
@@ -218,7 +264,7 @@ __device__ __forceinline__ void lm_tile_zero_live(const Lm8Params& p, int r0, in
 }
 
 // ---- the policies: both gather their rows through the partition.  dalm_linear_live writes the caller's output, so its skipping
-// blocks zero-fill; the MLP node's forward writes node-private buffers whose dead rows nobody reads: its skipping blocks return at once
+// blocks zero-fill; the MLP nodes' forwards write node-private buffers whose dead rows nobody reads: their skipping blocks return at once
 struct EpiLive : Gemm256Epi {
   static constexpr bool LIVE = true;
   static __device__ __forceinline__ void skipped(const Lm8Params& p, int r0, int c0, int tid) { lm_tile_zero_live(p, r0, c0, tid); }
@@ -234,6 +280,14 @@ struct EpiLiveSwiglu : Gemm256Epi {
   static __device__ __forceinline__ void tile(const Lm8Params& p, f32x16 (&acc)[4][4], unsigned char* lds,
                                             int r0, int c0, int nt, int nlive, int wr, int wc, int tid) {
     lm_tile_epilogue_live_swiglu(p, acc, lds, r0, c0, nlive, wr, wc, tid);
+  }
+};
+
+struct EpiLiveRelu2 : Gemm256Epi {      // full 256-column tiles of Wup; node-private outputs: skipping blocks return at once
+  static constexpr bool LIVE = true;
+  static __device__ __forceinline__ void tile(const Lm8Params& p, f32x16 (&acc)[4][4], unsigned char* lds,
+                                            int r0, int c0, int nt, int nlive, int wr, int wc, int tid) {
+    lm_tile_epilogue_live_relu2(p, acc, lds, r0, c0, nlive, wr, wc, tid);
   }
 };
 
@@ -352,4 +406,30 @@ extern "C" int dalm_linear_live_swiglu(const void* A, int64_t lda, const void* W
   const int tab = ensure_silu_table(__func__, stream);
   if (tab != DALM_OK) return tab;
   return launch_gemm256<EpiLiveSwiglu>(q, as_stream(stream), __func__);
+}
+
+// ---- the frozen ReLU^2 MLP node of the padded step (Arcee): relu(y)^2 inside the epilogue of its up GEMM ------------------------
+extern "C" int dalm_linear_live_relu2(const void* A, int64_t lda, const void* Wup, void* Y, int64_t ldy, void* Act, int64_t ldact,
+                                      int64_t R, int64_t C, int64_t K, const int32_t* perm, const int32_t* n_live,
+                                      dalm_stream_t stream) {
+  DALM_REQUIRE(R >= 0 && C >= 0, DALM_E_SHAPE, "R, C must be >= 0");
+  if (R == 0 || C == 0) return 0;
+  DALM_REQUIRE(A && Wup && Y && Act && perm && n_live, DALM_E_NULL, "null pointer argument");
+  // the operand checks dalm_linear_live makes: A [R, K] (stride lda) against Wup [C, K]
+  DALM_REQUIRE(K > 0 && K % 64 == 0 && C % 8 == 0, DALM_E_SHAPE, "need K > 0, K a multiple of 64 and C a multiple of 8");
+  DALM_REQUIRE(lda >= K && ldy >= C && ldact >= C && lda % 8 == 0 && ldy % 8 == 0 && ldact % 8 == 0, DALM_E_SHAPE,
+               "row strides: lda >= K, ldy >= C, ldact >= C, all multiples of 8 elements");
+  DALM_REQUIRE(R <= 0x7fffff00ll && C <= 0x7fffff00ll && lda <= 0x7fffffffll && ldy <= 0x7fffffffll && ldact <= 0x7fffffffll,
+               DALM_E_SHAPE, kTooBig);
+  DALM_REQUIRE(reinterpret_cast<uintptr_t>(A) % 16 == 0 && reinterpret_cast<uintptr_t>(Wup) % 16 == 0 &&
+               reinterpret_cast<uintptr_t>(Y) % 16 == 0 && reinterpret_cast<uintptr_t>(Act) % 16 == 0, DALM_E_ALIGN,
+               "A / Wup / Y / Act must be 16-byte aligned");
+  Lm8Params q{};
+  const int rc = gemm256_params(q, __func__, A, Wup, gemm256_live(R, C, K, lda, C, 256), kTooBig);
+  if (rc != DALM_OK) return rc;
+  q.out_cols = static_cast<int>(C);
+  q.perm = perm; q.n_live = n_live;
+  q.out = Y; q.out_pitch = ldy;
+  q.out2 = Act; q.out2_pitch = ldact;
+  return launch_gemm256<EpiLiveRelu2>(q, as_stream(stream), __func__);
 }

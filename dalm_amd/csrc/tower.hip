@@ -17,8 +17,10 @@
 //   swiglu backward:  ds = rb(da u);  du = rb(da s);  sig = 1 / (1 + exp(-g));  dg = rb(ds sig (1 + g (1 - sig)))
 // Algorithmic bytes: rope 2 * (|q| + |k|) * el (+ cos/sin, shared by all heads); swiglu forward 3 * n * el, backward 5 * n * el.
 // Further down: RMSNorm with the residual add (dalm_rms_norm_*), Qwen3's head norm + rotary (dalm_head_norm_*), and Gemma's two
-// formulas - GeGLU and the (1 + w) RMSNorm (dalm_geglu_*, dalm_gemma_norm_*) - each with its own comment block.
+// formulas - GeGLU and the (1 + w) RMSNorm (dalm_geglu_*, dalm_gemma_norm_*) - and Arcee's ReLU^2 (dalm_relu2_*), each with its own
+// comment block.
 #include "dispatch.hpp"
+#include "relu2_math.hpp"
 #include "swiglu_math.hpp"
 #include "vec16.hpp"
 
@@ -936,7 +938,8 @@ __device__ __forceinline__ float gelu_tanh_bwd_f32(float dy, float x) {
 // [R, C] views with row strides, walked as tiles of 256 vectors by a capped grid: the tile one grid stride further on lies
 // step_row rows and step_col columns away (the launcher divides once; a thread divides once, for its first tile)
 struct GegluLd { int64_t g, u, a, dg, du; unsigned int C, step_row, step_col; };
-__device__ __forceinline__ RowCol next_tile(RowCol rc, const GegluLd& ld) {
+template <class Ld>                               // GegluLd, or Relu2Ld further down: the same three tile fields
+__device__ __forceinline__ RowCol next_tile(RowCol rc, const Ld& ld) {
   rc.row += ld.step_row;
   rc.col += ld.step_col;
   if (rc.col >= ld.C) { rc.col -= ld.C; ++rc.row; }
@@ -1184,7 +1187,8 @@ __global__ __launch_bounds__(256) void gemma_norm_bwd_kernel(const T* __restrict
 }
 
 // the checks the two GeGLU entry points share, after the NULL and dtype checks; fills the grid, the element count and the tile steps
-int geglu_plan(const char* fn, int dtype, int64_t R, int64_t C, std::initializer_list<int64_t> lds, dim3& grid, int64_t& n, GegluLd& ld) {
+template <class Ld>
+int geglu_plan(const char* fn, int dtype, int64_t R, int64_t C, std::initializer_list<int64_t> lds, dim3& grid, int64_t& n, Ld& ld) {
   const int vec = dtype == DALM_F32 ? 4 : 8;
   bool ok = C % vec == 0;
   for (int64_t l : lds) ok = ok && l % vec == 0 && l >= C;
@@ -1290,6 +1294,130 @@ extern "C" int dalm_gemma_norm_bwd(const void* dy, const void* h, const void* w,
                            Ri, Di, row_live);
       });
     });
+  });
+  return check_launch(__func__);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Arcee (modeling_arcee.py; AFM): the decoder layer, attention and norm are Llama's, the MLP is not - no gate:
+//   ArceeMLP  down(relu(up(x))^2)     act_fn = ReLUSquaredActivation = torch.square(F.relu(x))            - dalm_relu2_{fwd,bwd}
+// Rounding points are the eager chain's and its autograd's (relu2_math.hpp: the live-row up-GEMM's epilogue shares the arithmetic):
+//   forward :  act = rb(relu(y)^2)
+//   backward:  d_y = rb(d_act rb(2 relu(y))) where relu(y) > 0 or y is NaN, zero elsewhere   - nothing but y was saved
+// The GeGLU kernels' walk: [R, C] views with row strides, tiles of 256 vectors, a capped grid, kGegluTiles tiles in flight.
+// Algorithmic bytes: forward 2 R C el, backward 3 R C el.
+// ---------------------------------------------------------------------------------------------------
+namespace {
+
+struct Relu2Ld { int64_t y, a, dy; unsigned int C, step_row, step_col; };
+
+template <typename T>
+__global__ __launch_bounds__(256) void relu2_fwd_kernel(const T* __restrict__ y, T* __restrict__ a, int64_t n, Relu2Ld ld,
+                                                        const unsigned char* __restrict__ live) {
+  constexpr int VEC = Vec16<T>::VEC, K = kGegluTiles;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * 256 * VEC;
+  int64_t e0 = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) * VEC;
+  if (e0 >= n) return;
+  RowCol at = row_col(e0, ld.C);
+  for (; e0 < n; e0 += K * stride) {
+    RowCol rc[K];
+    bool in[K], lv[K];
+    float yv[K][VEC];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      rc[k] = at;
+      at = next_tile(at, ld);
+      in[k] = e0 + k * stride < n;
+      lv[k] = in[k] && (!live || live[rc[k].row]);
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (lv[k]) Vec16<T>::load(y + ld_at(rc[k], ld.y), yv[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (!in[k]) continue;
+      float o[VEC];
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) o[e] = lv[k] ? relu2_fwd_elem<Vec16<T>>(yv[k][e]) : 0.f;
+      Vec16<T>::store(a + ld_at(rc[k], ld.a), o);                    // a dead row: nothing was loaded, zeros leave
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void relu2_bwd_kernel(const T* __restrict__ da, const T* __restrict__ y, T* __restrict__ dy,
+                                                        int64_t n, Relu2Ld ld, const unsigned char* __restrict__ live) {
+  constexpr int VEC = Vec16<T>::VEC, K = kGegluTiles;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * 256 * VEC;
+  int64_t e0 = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) * VEC;
+  if (e0 >= n) return;
+  RowCol at = row_col(e0, ld.C);
+  for (; e0 < n; e0 += K * stride) {
+    RowCol rc[K];
+    bool in[K], lv[K];
+    float dav[K][VEC], yv[K][VEC];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      rc[k] = at;
+      at = next_tile(at, ld);
+      in[k] = e0 + k * stride < n;
+      lv[k] = in[k] && (!live || live[rc[k].row]);
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (lv[k]) {
+        Vec16<T>::load(da + ld_at(rc[k], ld.a), dav[k]);
+        Vec16<T>::load(y + ld_at(rc[k], ld.y), yv[k]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (!in[k]) continue;
+      float o[VEC];
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) o[e] = lv[k] ? relu2_bwd_elem<Vec16<T>>(dav[k][e], yv[k][e]) : 0.f;
+      Vec16<T>::store(dy + ld_at(rc[k], ld.dy), o);
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int dalm_relu2_fwd(const void* y, void* act, int dtype, int64_t R, int64_t C, int64_t ld_y, int64_t ld_act,
+                              const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(R >= 0 && C >= 0, DALM_E_SHAPE, "R, C must be >= 0");
+  if (R == 0 || C == 0) return 0;
+  DALM_REQUIRE(y && act, DALM_E_NULL, "null pointer argument");
+  DALM_REQUIRE(dtype == DALM_F32 || dtype == DALM_BF16, DALM_E_DTYPE, "dtype must be DALM_F32 or DALM_BF16");
+  DALM_REQUIRE(aligned16(y, act), DALM_E_ALIGN, "y / act must be 16-byte aligned");
+  dim3 grid;
+  int64_t n;
+  Relu2Ld ld = {ld_y, ld_act, 0, 0u, 0u, 0u};
+  if (const int rc = geglu_plan(__func__, dtype, R, C, {ld_y, ld_act}, grid, n, ld)) return rc;
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((relu2_fwd_kernel<T>), grid, dim3(256), 0, as_stream(stream), static_cast<const T*>(y), static_cast<T*>(act), n,
+                       ld, row_live);
+  });
+  return check_launch(__func__);
+}
+
+extern "C" int dalm_relu2_bwd(const void* d_act, const void* y, void* d_y, int dtype, int64_t R, int64_t C, int64_t ld_dact,
+                              int64_t ld_y, int64_t ld_dy, const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(R >= 0 && C >= 0, DALM_E_SHAPE, "R, C must be >= 0");
+  if (R == 0 || C == 0) return 0;
+  DALM_REQUIRE(d_act && y && d_y, DALM_E_NULL, "null pointer argument");
+  DALM_REQUIRE(dtype == DALM_F32 || dtype == DALM_BF16, DALM_E_DTYPE, "dtype must be DALM_F32 or DALM_BF16");
+  DALM_REQUIRE(aligned16(d_act, y, d_y), DALM_E_ALIGN, "all tensors must be 16-byte aligned");
+  dim3 grid;
+  int64_t n;
+  Relu2Ld ld = {ld_y, ld_dact, ld_dy, 0u, 0u, 0u};
+  if (const int rc = geglu_plan(__func__, dtype, R, C, {ld_dact, ld_y, ld_dy}, grid, n, ld)) return rc;
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((relu2_bwd_kernel<T>), grid, dim3(256), 0, as_stream(stream), static_cast<const T*>(d_act),
+                       static_cast<const T*>(y), static_cast<T*>(d_y), n, ld, row_live);
   });
   return check_launch(__func__);
 }

@@ -157,6 +157,9 @@ SIGNATURES = {
     "dalm_geglu_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
     "dalm_gemma_norm_fwd": (_int, [_vp, _vp, _vp, _int, _int, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp]),
     "dalm_gemma_norm_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _i64, _i64, _vp, _vp, _vp]),
+    # Arcee: ReLU^2 (ArceeMLP's activation), one entry point per direction (row liveness is an argument)
+    "dalm_relu2_fwd": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "dalm_relu2_bwd": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
     "dalm_bert_add_norm_fwd_live": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _f32, _f32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _vp]),
     "dalm_bert_add_norm_bwd_live": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
@@ -179,6 +182,8 @@ SIGNATURES = {
     # the frozen SwiGLU MLP node: SwiGLU inside the epilogue of the gate | up forward
     "dalm_linear_live_swiglu_prepare": (_int, [_vp]),
     "dalm_linear_live_swiglu": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    # the frozen ReLU^2 MLP node: relu(y)^2 inside the epilogue of the up forward
+    "dalm_linear_live_relu2": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
 }
 
 

@@ -1,5 +1,5 @@
-"""Frozen projections of a PADDED tower call over the live rows only: the wrappers of `dalm_row_partition` / `dalm_linear_live`
-(include/dalm_hip.h), the routing predicate the frozen-linear nodes ask, and the tile accounting behind the routing table.
+"""Frozen projections of a PADDED tower call over the live rows only: the wrappers of `dalm_row_partition` / `dalm_linear_live` and
+of the two MLP-node forwards `dalm_linear_live_swiglu` / `dalm_linear_live_relu2` (include/dalm_hip.h), the routing predicate the frozen-linear nodes ask, and the tile accounting behind the routing table.
 
 The padded layout keeps every padding row in the GEMM shapes (dalm_amd/live_rows.py); the row-wise kernels skip the rows nothing
 depends on, the library GEMMs cannot.  `dalm_linear_live` is the lm_head MFMA main loop with a row gather on its A operand: it
@@ -29,6 +29,9 @@ ROUTED_SHAPES = frozenset({
 })
 # Not listed: (4608, 4096, 4096) (o_proj both ways, the members of the q | k | v dgrad) and (4608, 12288, 4096) (q | k | v forward) -
 # the kernel is faster there too, but not by three spreads of the library arm at every mask in every run of the bench.
+# Not listed either: AFM-4.5B's MLP shapes (tools/linear_live_bench.py --candidates, profiles/arcee_bench.txt).  (4608, 2560, 18432) -
+# 180 tiles on 256 CUs - loses to the library at every mask; (4608, 18432, 2560) wins, but over a library arm that was never tuned at
+# that shape.  The ReLU^2 MLP node needs both, so it routes under `set_table` only.
 
 _enabled = True
 _mlp_fused = True
@@ -47,8 +50,8 @@ def enabled() -> bool:
 
 
 def set_mlp_fused(on: bool) -> None:
-    """Turn the fused frozen-MLP node on or off (A/B tools, tests); off = the three projections and the SwiGLU kernels run as
-    separate nodes, as before.  A function, not an environment variable: same bits either way, nothing a deployment selects."""
+    """Turn the fused frozen-MLP nodes (SwiGLU, ReLU^2) on or off (A/B tools, tests); off = the projections and the activation
+    kernels run as separate nodes, as before.  A function, not an environment variable: same bits either way, nothing a deployment selects."""
     global _mlp_fused
     _mlp_fused = bool(on)
 
@@ -103,6 +106,15 @@ def mlp_routed(rows: int, c: int, h: int, dtype: torch.dtype, has_bias: bool, ha
     if not (_mlp_fused and c > 0 and c % 128 == 0):
         return False
     return all(routed(rows, n, k, dtype, has_bias, have_partition) for n, k in ((2 * c, h), (h, c), (c, h)))
+
+
+def relu2_mlp_routed(rows: int, c: int, h: int, dtype: torch.dtype, has_bias: bool, have_partition: bool) -> bool:
+    """The frozen ReLU^2 MLP (Arcee: hidden h, intermediate c, no gate) as ONE node around `linear_live_relu2`: `mlp_routed`'s
+    switches and BOTH GEMM shapes of the node in the table - (rows, c, h): up forward and down dgrad, (rows, h, c): down forward and
+    up dgrad."""
+    if not (_mlp_fused and c > 0):
+        return False
+    return all(routed(rows, n, k, dtype, has_bias, have_partition) for n, k in ((c, h), (h, c)))
 
 
 def _operand_ok(t: torch.Tensor) -> bool:
@@ -197,6 +209,26 @@ def linear_live_swiglu(a: torch.Tensor, wcat: torch.Tensor, part):
     act = torch.empty((rows, c), dtype=torch.bfloat16, device=a.device)
     with torch.cuda.device(a.device):
         hip.call("dalm_linear_live_swiglu", hip.ptr(a), a.stride(0), hip.ptr(wcat), hip.ptr(y), 2 * c, hip.ptr(act), c, rows, c, k,
+                 hip.ptr(perm), hip.ptr(n_live), hip.stream())
+    _calls += 1
+    return y, act
+
+
+def linear_live_relu2(a: torch.Tensor, w_up: torch.Tensor, part):
+    """(y, act) for the live rows of `part`: y[r] = a[r] . w_up^T (w_up [C, K] contiguous), act[r] = relu(y[r])^2 - the bits of
+    `linear_live` followed by `dalm_relu2_fwd`.  Dead rows of BOTH outputs are NOT written (torch.empty): the buffers are meant to
+    stay inside one autograd node."""
+    global _calls
+    rows, k = a.shape
+    perm, n_live = _check_part(part, rows)
+    hip.require_gpu(a, w_up, perm, n_live)
+    if not (_operand_ok(a) and w_up.dim() == 2 and w_up.dtype == torch.bfloat16 and w_up.is_contiguous()) or w_up.shape[1] != k:
+        raise TypeError("linear_live_relu2: bf16 a [R, K] with unit column stride and contiguous w_up [C, K] expected")
+    c = w_up.shape[0]
+    y = torch.empty((rows, c), dtype=torch.bfloat16, device=a.device)
+    act = torch.empty((rows, c), dtype=torch.bfloat16, device=a.device)
+    with torch.cuda.device(a.device):
+        hip.call("dalm_linear_live_relu2", hip.ptr(a), a.stride(0), hip.ptr(w_up), hip.ptr(y), c, hip.ptr(act), c, rows, c, k,
                  hip.ptr(perm), hip.ptr(n_live), hip.stream())
     _calls += 1
     return y, act

@@ -175,14 +175,15 @@ def _rope_hip(q, k, cos, sin, position_ids=None, unsqueeze_dim=1):
 
 
 def use_roll_rope(model: torch.nn.Module) -> bool:
-    """Swap the module-level apply_rotary_pos_emb of the model's own modeling file (Llama and Falcon)."""
+    """Swap the module-level apply_rotary_pos_emb of the model's own modeling file (Llama, Falcon and Arcee)."""
     if _off("DALM_FAST_ROPE"):
         return False
     import importlib
 
     mod_name = type(getattr(model, "base_model", model)).__module__
-    # modeling files whose apply_rotary_pos_emb is the formula above, word for word (Falcon calls it only without alibi)
-    if not mod_name.endswith(("modeling_llama", "modeling_falcon")):
+    # modeling files whose apply_rotary_pos_emb is the formula above, word for word (Falcon calls it only without alibi; Arcee's
+    # is Llama's text)
+    if not mod_name.endswith(("modeling_llama", "modeling_falcon", "modeling_arcee")):
         return False
     mod = importlib.import_module(mod_name)
     if not hasattr(mod, "apply_rotary_pos_emb"):
@@ -252,14 +253,16 @@ def use_swiglu_kernel(model: torch.nn.Module) -> int:
     return _install(model, ("LlamaMLP", "MistralMLP", "Qwen2MLP", "Qwen3MLP"), gated_silu, _mlp_matches, _swiglu_mlp_forward)
 
 
-def _mlp_matches(mod: torch.nn.Module, forward=_swiglu_mlp_forward, what: str = "down(silu(gate(x)) * up(x)) here") -> bool:
+def _mlp_matches(mod: torch.nn.Module, forward=_swiglu_mlp_forward, what: str = "down(silu(gate(x)) * up(x)) here",
+                 first: str = "gate_proj") -> bool:
     """The class's own forward against the patched one on a small random input, once per class, dtype and device type (on a
-    GPU the patched forward runs the HIP kernel: <= 1 ulp of the output dtype)."""
-    w = getattr(mod.gate_proj, "weight", None)
+    GPU the patched forward runs the HIP kernel: <= 1 ulp of the output dtype).  `first`: a projection that takes x."""
+    first = getattr(mod, first)
+    w = getattr(first, "weight", None)
     where = (None, None) if w is None else (w.dtype, w.device.type)        # no resident weight: the probe fails, the guard says no
 
     def probe():
-        x = torch.randn(2, 3, mod.gate_proj.in_features, generator=torch.Generator().manual_seed(0)).to(device=w.device, dtype=w.dtype)
+        x = torch.randn(2, 3, first.in_features, generator=torch.Generator().manual_seed(0)).to(device=w.device, dtype=w.dtype)
         with torch.no_grad():
             return _close(forward(mod, x), type(mod).forward(mod, x), 2.0)
 
@@ -301,6 +304,38 @@ def use_geglu_kernel(model: torch.nn.Module) -> int:
 
     return _install(model, ("GemmaMLP", "Gemma2MLP", "Gemma3MLP"), gated_tanh_gelu,
                     lambda mod: _mlp_matches(mod, _geglu_mlp_forward, "down(gelu_tanh(gate(x)) * up(x)) here"), _geglu_mlp_forward)
+
+
+# ---------------------------------------------------------------------------
+# Arcee (AFM): the ungated ReLU^2 MLP; attention, norm and decoder layer are Llama's (`_llama_attention_forward`, `_llama_layer_forward`)
+# ---------------------------------------------------------------------------
+def _relu2_mlp_forward(self, x):
+    from . import frozen_linear, tower_ops
+
+    out = frozen_linear.relu2_mlp_forward(x, self.up_proj, self.down_proj)   # padded step, both frozen: one node
+    if out is not None:
+        return out
+    y = self.up_proj(x)
+    if tower_ops.relu2_supported(y):
+        return self.down_proj(tower_ops.relu2(y))
+    return self.down_proj(self.act_fn(y))
+
+
+def use_relu2_kernel(model: torch.nn.Module) -> int:
+    """Patch the bias-free `ArceeMLP` modules that are down(act(up(x))) with act = transformers' ReLUSquaredActivation
+    (square(relu(x))) and no gate to evaluate relu(up)^2 through `dalm_relu2_{fwd,bwd}`: 2 eager launches forward and ~4 backward become 1 + 1, and nothing
+    but the up projection's output is saved.  Same rounding points as the eager chain.  DALM_SWIGLU_KERNEL=0 disables; returns how
+    many modules were patched."""
+    if _off("DALM_SWIGLU_KERNEL"):
+        return 0
+
+    def ungated_relu2(mod) -> bool:
+        return (all(hasattr(mod, a) for a in ("up_proj", "down_proj")) and not hasattr(mod, "gate_proj")
+                and mod.up_proj.bias is None and mod.down_proj.bias is None          # AFM is bias-free: `mlp_bias` stays transformers'
+                and type(getattr(mod, "act_fn", None)).__name__ == "ReLUSquaredActivation")
+
+    return _install(model, ("ArceeMLP",), ungated_relu2,
+                    lambda mod: _mlp_matches(mod, _relu2_mlp_forward, "down(relu(up(x))^2) here", first="up_proj"), _relu2_mlp_forward)
 
 
 def _gemma_norm_formula(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
@@ -817,10 +852,10 @@ def _use_attention_node(model: torch.nn.Module, name: str, attrs: tuple, guard: 
 
 
 def use_llama_attention_node(model: torch.nn.Module) -> int:
-    """Patch LlamaAttention modules of a model that runs on "dalm_sdpa" (models/attention.py) and whose forward is the code
-    `_llama_attention_forward` restates.  Returns the count."""
-    return _use_attention_node(model, "LlamaAttention", ("q_proj", "k_proj", "v_proj", "o_proj", "scaling"), "llama-attn",
-                               _llama_attention_forward)
+    """Patch LlamaAttention modules - and ArceeAttention ones, Llama's forward under the same source guard - of a model that runs on
+    "dalm_sdpa" (models/attention.py) and whose forward is the code `_llama_attention_forward` restates.  Returns the count."""
+    return sum(_use_attention_node(model, name, ("q_proj", "k_proj", "v_proj", "o_proj", "scaling"), "llama-attn",
+                                   _llama_attention_forward) for name in ("LlamaAttention", "ArceeAttention"))
 
 
 def use_qwen3_attention_node(model: torch.nn.Module) -> int:
@@ -878,8 +913,8 @@ def _two_norm_layer_forward(self, supported, add_norm, hidden_states, attention_
 
 
 def use_fused_residual_norm(model: torch.nn.Module) -> int:
-    """Patch LlamaDecoderLayer / Qwen3DecoderLayer / GemmaDecoderLayer modules whose forward has the signature this file was
-    written against (transformers 5.x; Qwen3's and Gemma's are also compared statement for statement); DALM_NORM_KERNEL=0
+    """Patch LlamaDecoderLayer / Qwen3DecoderLayer / ArceeDecoderLayer / GemmaDecoderLayer modules whose forward has the signature this
+    file was written against (transformers 5.x; Qwen3's, Arcee's and Gemma's are also compared statement for statement); DALM_NORM_KERNEL=0
     disables.  A Gemma layer's two norms must be GemmaRMSNorm by name and by value (`_gemma_norm_matches`); Gemma2 / Gemma3 layers
     (four norms) are other code and are not taken.  Returns how many layers were patched."""
     if _off("DALM_NORM_KERNEL"):
@@ -899,6 +934,7 @@ def use_fused_residual_norm(model: torch.nn.Module) -> int:
     return sum(_install(model, (name,), two_norms(is_norm), guard, forward, keep="_dalm_orig_forward")
                for name, guard, is_norm, forward in (("LlamaDecoderLayer", "llama-layer", plain_rms_norm, _llama_layer_forward),
                                                      ("Qwen3DecoderLayer", "qwen3-layer", plain_rms_norm, _llama_layer_forward),
+                                                     ("ArceeDecoderLayer", "arcee-layer", plain_rms_norm, _llama_layer_forward),
                                                      ("GemmaDecoderLayer", "gemma-layer", gemma_rms_norm, _gemma_layer_forward)))
 
 
@@ -915,3 +951,4 @@ _SOURCE_GUARDS["qwen3-layer"] = (
     lambda params, src: (params == _LLAMA_LAYER_PARAMS and _body(src)[-len(_QWEN3_LAYER_BODY):] == _QWEN3_LAYER_BODY
                          and _body(src)[-len(_QWEN3_LAYER_BODY) - 1].startswith(")")), _RESTATED)
 _SOURCE_GUARDS["gemma-layer"] = _SOURCE_GUARDS["qwen3-layer"]       # GemmaDecoderLayer.forward: the same whole body, the same check
+_SOURCE_GUARDS["arcee-layer"] = _SOURCE_GUARDS["qwen3-layer"]       # ArceeDecoderLayer.forward likewise

@@ -416,6 +416,104 @@ def swiglu_mlp_forward(x: torch.Tensor, gate_proj, up_proj, down_proj):
     return _FrozenSwigluMlpFn.apply(x, cat, gate_proj.weight, up_proj.weight, down_proj.weight, part)
 
 
+class _FrozenRelu2MlpFn(torch.autograd.Function):
+    """down(relu(up(x))^2) (ArceeMLP) with both projections frozen, inside a padded tower call, as ONE node: relu(y)^2 runs in the
+    epilogue of the up GEMM (dalm_amd/linear_live.py); the backward is the down dgrad GEMM, the row-wise ReLU^2 backward kernel and
+    the up dgrad GEMM.  y, act and d_y never leave the node, so their dead rows are never written - every consumer is a live-row GEMM
+    whose A gather skips them, or the row-wise kernel under the node's liveness vector.  The output and dx leave the node and keep
+    zeros in their dead rows.  Same bits as the separate nodes: same contraction order, same element arithmetic
+    (csrc/relu2_math.hpp)."""
+
+    @staticmethod
+    def forward(ctx, x, wu, wd, part):
+        from .. import linear_live, live_rows
+
+        x2 = x.reshape(-1, wu.shape[1])
+        y, act = linear_live.linear_live_relu2(x2, wu, part)
+        out = linear_live.linear_live(act, wd, part)            # leaves the node: zeros for the dead rows
+        ctx.save_for_backward(y)                                # act is not needed again: every weight is frozen
+        ctx.part, ctx.wu, ctx.wd = part, wu, wd
+        ctx.live = live_rows.current(x2.shape[0], x2.device)    # the vector behind `part`, for the row-wise backward kernel
+        ctx.xshape = x.shape
+        return out.view(*x.shape[:-1], wd.shape[0])
+
+    @staticmethod
+    def backward(ctx, g):
+        from .. import hip, linear_live
+
+        (y,) = ctx.saved_tensors
+        part = ctx.part
+        g2 = g.reshape(-1, ctx.wd.shape[0])
+        if g2.dtype != torch.bfloat16:
+            g2 = g2.to(torch.bfloat16)
+        if g2.stride(-1) != 1 or g2.stride(0) % 8 or g2.data_ptr() % 16:
+            g2 = g2.contiguous()
+        wdt, wut = (dgrad_weight(w, torch.bfloat16) for w in (ctx.wd, ctx.wu))
+        if wdt is None or wut is None:
+            raise RuntimeError("frozen ReLU^2 MLP node: the transposed dgrad copies of its weights are missing (make them outside a "
+                               "graph capture: frozen_linear.dgrad_weight)")
+        rows, c = y.shape
+        d_act = linear_live.linear_live(g2, wdt, part)
+        dy = torch.empty_like(d_act)
+        hip.call("dalm_relu2_bwd", hip.ptr(d_act), hip.ptr(y), hip.ptr(dy), hip.dtype_code(y), rows, c, c, c, c, hip.ptr(ctx.live),
+                 hip.stream())
+        dx = linear_live.linear_live(dy, wut, part)             # fresh: zeros for the dead rows
+        return dx.view(ctx.xshape), None, None, None
+
+
+def relu2_mlp_candidate(x: torch.Tensor, up_proj, down_proj):
+    """The part of the routing predicate that needs no device (meta tensors will do): (rows, C, H) when the switches are on, the two
+    projections are plain, bias-free, frozen and bf16 like x, the shapes are those of one ungated MLP and both GEMM shapes of the
+    node are in linear_live's table; else None."""
+    from .. import linear_live
+
+    if not (linear_live.enabled() and linear_live.mlp_fused()):
+        return None
+    plain = (torch.nn.Linear, FrozenLinearT)
+    mods = (up_proj, down_proj)
+    if any(type(m) not in plain or m.bias is not None or m.weight.requires_grad for m in mods):
+        return None
+    if x.dtype != torch.bfloat16 or any(m.weight.dtype != torch.bfloat16 or m.weight.dim() != 2 for m in mods):
+        return None
+    c, h = up_proj.weight.shape
+    if down_proj.weight.shape != (h, c) or x.dim() < 2 or x.shape[-1] != h:
+        return None
+    rows = x.numel() // h
+    if not linear_live.relu2_mlp_routed(rows, c, h, x.dtype, False, True):
+        return None
+    return rows, c, h
+
+
+def relu2_mlp_route(x: torch.Tensor, up_proj, down_proj):
+    """The routing predicate of `relu2_mlp_forward`: the partition when the call goes to the fused node, else None."""
+    from .. import linear_live
+
+    cand = relu2_mlp_candidate(x, up_proj, down_proj)
+    if cand is None or not _eligible(x, up_proj, down_proj):
+        return None
+    x2 = x.reshape(-1, cand[2])
+    wu, wd = up_proj.weight, down_proj.weight
+    if not (linear_live.accepts(x2, wu, False) and wd.is_contiguous() and wd.data_ptr() % 16 == 0 and wd.device == x.device):
+        return None
+    part = linear_live.route(x2, wu, False)              # None outside a padded tower call
+    if part is None:
+        return None
+    # the backward needs the two transposed copies; a first request from inside a graph capture cannot make them
+    if any(dgrad_weight(m.weight, torch.bfloat16) is None for m in (up_proj, down_proj)):
+        return None
+    return part
+
+
+def relu2_mlp_forward(x: torch.Tensor, up_proj, down_proj):
+    """down_proj(relu(up_proj(x))^2) through `_FrozenRelu2MlpFn`, or None when the call does not route (the caller then runs the
+    separate nodes): linear_live on with a padded tower call in progress and a partition of these rows, bf16, no biases, two frozen
+    plain projections, both GEMM shapes in linear_live's table, and `linear_live.set_mlp_fused` on."""
+    part = relu2_mlp_route(x, up_proj, down_proj)
+    if part is None:
+        return None
+    return _FrozenRelu2MlpFn.apply(x, up_proj.weight, down_proj.weight, part)
+
+
 def _eligible(x: torch.Tensor, *mods) -> bool:
     if not (x.is_cuda and torch.is_grad_enabled() and x.requires_grad):
         return False

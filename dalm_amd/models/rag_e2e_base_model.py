@@ -17,7 +17,7 @@ from . import lora
 from .attention import use_hip_attention_backward
 from .fastpath import (use_bert_layer_kernels, use_capturable_falcon_heads, use_falcon_attention_kernels, use_falcon_layer_kernels,
                        use_fused_residual_norm, use_geglu_kernel, use_gemma_rms_norm, use_llama_attention_node, use_native_rms_norm,
-                       use_qwen3_attention_node, use_roberta_embeddings, use_roll_rope, use_swiglu_kernel)
+                       use_qwen3_attention_node, use_relu2_kernel, use_roberta_embeddings, use_roll_rope, use_swiglu_kernel)
 
 
 class Mode(Enum):
@@ -93,7 +93,8 @@ def decoder_only(lm, T: Optional[int] = None) -> bool:
 # The installers a tower gets, in the order they run (each has its own guards and leaves other models alone).  The order matters:
 # `use_capturable_falcon_heads` reads "sdpa" before `use_hip_attention_backward` can change it, and the attention-node installers
 # need "dalm_sdpa" to be set already.
-_ROW_WISE_PATHS = (use_native_rms_norm, use_roll_rope, use_swiglu_kernel, use_geglu_kernel, use_gemma_rms_norm, use_fused_residual_norm)
+_ROW_WISE_PATHS = (use_native_rms_norm, use_roll_rope, use_swiglu_kernel, use_geglu_kernel, use_relu2_kernel, use_gemma_rms_norm,
+                   use_fused_residual_norm)
 _RETRIEVER_PATHS = _ROW_WISE_PATHS + (use_hip_attention_backward,)
 _GENERATOR_PATHS = _ROW_WISE_PATHS + (use_capturable_falcon_heads, use_falcon_layer_kernels, use_falcon_attention_kernels,
                                       use_hip_attention_backward, use_llama_attention_node, use_qwen3_attention_node)

@@ -7,7 +7,8 @@ dalm/models/rag_e2e_base_model.py:104-106).  The kernels round where those chain
 are the eager chain's (tests/test_tower_ops_gpu.py asserts equality, not closeness).
 
 Also here: RMSNorm with the residual add, Qwen3's head norm + rotary, Gemma's GeGLU and (1 + w) RMSNorm (`dalm_geglu_*`,
-`dalm_gemma_norm_*`: modeling_gemma.py `GemmaMLP.forward`, `GemmaRMSNorm.forward`), and Falcon's layer ops.
+`dalm_gemma_norm_*`: modeling_gemma.py `GemmaMLP.forward`, `GemmaRMSNorm.forward`), Arcee's ReLU^2 (`dalm_relu2_*`: modeling_arcee.py
+`ArceeMLP.forward`), and Falcon's layer ops.
 
 GPU tensors only: the callers in `fastpath.py` keep transformers' own code for CPU tensors.
 """
@@ -286,6 +287,55 @@ def geglu(gate, up, live=None):
     """gelu_tanh(gate) * up (GemmaMLP's activation).  live: uint8 row liveness over the leading dimensions; None: that of the tower
     call in progress (dalm_amd/live_rows.py), if any."""
     return _GeGLU.apply(gate, up, live)
+
+
+# ---------------------------------------------------------------------------
+# Arcee: ReLU^2 (dalm_relu2_{fwd,bwd}; modeling_arcee.py `ArceeMLP.forward`: down(act_fn(up(x))), act_fn = square(relu(x)))
+# ---------------------------------------------------------------------------
+class _ReLU2(torch.autograd.Function):
+    """relu(y)^2, `_GeGLU`'s shape with one input: y (a row-strided 2-D view is read in place) is all that is saved, the backward
+    recomputes relu(y) and leaves d_y contiguous."""
+
+    @staticmethod
+    def forward(ctx, y, live=None):
+        hip.require_gpu(y)
+        C = y.shape[-1]
+        rows_in_place = y.dim() == 2 and y.stride(1) == 1 and y.stride(0) >= C and y.stride(0) % (16 // y.element_size()) == 0
+        if not rows_in_place:
+            y = y.contiguous()
+        R = y.numel() // C if C else 0
+        if live is None and y.dim() >= 2:
+            live = live_rows.current(R, y.device)
+        if live is not None and live.numel() != R:
+            live = None
+        ctx.ld = y.stride(0) if rows_in_place else C
+        act = torch.empty(y.shape, dtype=y.dtype, device=y.device)
+        hip.call("dalm_relu2_fwd", hip.ptr(y), hip.ptr(act), hip.dtype_code(y), R, C, ctx.ld, C, hip.ptr(live), hip.stream())
+        ctx.save_for_backward(y, *([live] if live is not None else []))    # the backward runs after the tower call's context
+        return act
+
+    @staticmethod
+    def backward(ctx, d_act):
+        y, *keep = ctx.saved_tensors
+        d_act = d_act.contiguous()
+        C = y.shape[-1]
+        R = y.numel() // C if C else 0
+        dy = torch.empty(y.shape, dtype=y.dtype, device=y.device)
+        hip.call("dalm_relu2_bwd", hip.ptr(d_act), hip.ptr(y), hip.ptr(dy), hip.dtype_code(y), R, C, C, ctx.ld, C,
+                 hip.ptr(keep[0] if keep else None), hip.stream())
+        return dy, None
+
+
+def relu2_supported(y) -> bool:
+    return (y.is_cuda and y.dtype in (torch.float32, torch.bfloat16) and y.dim() >= 1
+            and y.shape[-1] % (16 // y.element_size()) == 0 and y.numel() < 2 ** 32
+            and y.data_ptr() % 16 == 0)                                    # a view at an odd storage offset: the eager chain
+
+
+def relu2(y, live=None):
+    """relu(y)^2 (ArceeMLP's activation).  live: uint8 row liveness over the leading dimensions; None: that of the tower call in
+    progress (dalm_amd/live_rows.py), if any."""
+    return _ReLU2.apply(y, live)
 
 
 def gemma_rms_norm_supported(x: torch.Tensor, w: torch.Tensor) -> bool:

@@ -571,6 +571,21 @@ int dalm_gemma_norm_fwd(const void* x, const void* delta, const void* w, int dty
 int dalm_gemma_norm_bwd(const void* dy, const void* h, const void* w, const float* rstd, const void* dres, int dtype, int w_dtype,
                         int64_t R, int64_t D, void* dx, const uint8_t* row_live, dalm_stream_t stream);
 
+/* Arcee (modeling_arcee.py; `model_type` "arcee", AFM): attention, norm and decoder layer are Llama's, the MLP has no gate:
+ *   ArceeMLP:  down(act_fn(up(x)))  with act_fn = ReLUSquaredActivation = torch.square(F.relu(x))
+ * dalm_relu2_fwd / dalm_relu2_bwd: one entry point per direction, the shape of dalm_geglu_*: [R, C] views with row strides in
+ *   elements (contiguous: ld = C), dtype DALM_F32 or DALM_BF16, row_live [R] bytes or NULL (Row liveness, above: nothing of a dead
+ *   row is loaded, freshly written outputs hold zeros there, live rows receive the same bits as without the vector).  Rounding
+ *   points of the eager chain and its autograd:  act = round(relu(y)^2);  d_y = round(d_act round(2 relu(y))) where relu(y) > 0 (and
+ *   NaN where y is NaN), zero elsewhere - whatever d_act holds there.  2 relu(y) is exact short of overflow, so one rounding each
+ *   way.  The forward saves nothing but y.  C and the strides multiples of 16 bytes, strides >= C, 16-byte aligned pointers
+ *   (DALM_E_ALIGN); R C < 2^32 (DALM_E_SHAPE).  R == 0 or C == 0: nothing to do, 0.  Streaming kernels on a grid of at most
+ *   256 x 8 workgroups: forward 2 R C elements of traffic, backward 3 R C.  The checks run before anything is enqueued. */
+int dalm_relu2_fwd(const void* y, void* act, int dtype, int64_t R, int64_t C, int64_t ld_y, int64_t ld_act, const uint8_t* row_live,
+                   dalm_stream_t stream);
+int dalm_relu2_bwd(const void* d_act, const void* y, void* d_y, int dtype, int64_t R, int64_t C, int64_t ld_dact, int64_t ld_y,
+                   int64_t ld_dy, const uint8_t* row_live, dalm_stream_t stream);
+
 /* Elementwise chains of a Falcon-7B decoder layer (transformers modeling_falcon.py FalconDecoderLayer.forward /
  * FalconMLP.forward / dropout_add, reached by the reference through self.generator_model(...),
  * dalm/models/rag_e2e_base_model.py:104-106; BASELINE.json config 5).  bf16 tensors, 16-byte aligned.
@@ -870,6 +885,16 @@ int dalm_linear_live(const void* A, int64_t lda, const void* W, void* C, int64_t
 int dalm_linear_live_swiglu_prepare(dalm_stream_t stream);
 int dalm_linear_live_swiglu(const void* A, int64_t lda, const void* Wcat, void* Y, int64_t ldy, void* Act, int64_t ldact, int64_t R,
                             int64_t C, int64_t K, const int32_t* perm, const int32_t* n_live, dalm_stream_t stream);
+/* The frozen ReLU^2 MLP of the padded step (Arcee): relu(y)^2 inside the epilogue of its up live-row GEMM.  Main loop, partition
+ * and limits of dalm_linear_live on full 256-column tiles; the element arithmetic is the one definition dalm_relu2_fwd uses
+ * (csrc/relu2_math.hpp), applied to the ROUNDED y, so live rows hold the same bits as dalm_linear_live followed by dalm_relu2_fwd.
+ * dalm_linear_live_relu2:  for i < n_live, r = perm[i]:  Y[r, :] = bf16(A[r, :] . Wup^T) (Wup [C, K] contiguous; Y [R, C], row
+ *   stride ldy) and Act[r, :] = round(relu(Y[r, :])^2) (Act [R, C], row stride ldact).  Y and Act are meant as buffers private to one
+ *   autograd node: dead rows are NOT WRITTEN, nothing of a dead row of A is read, perm entries outside [0, R) select nothing, columns
+ *   >= C of a strided output are not touched.  K % 64 == 0, C % 8 == 0, lda >= K, ldy >= C, ldact >= C, strides multiples of 8
+ *   (DALM_E_SHAPE); pointers 16-byte aligned (DALM_E_ALIGN).  R == 0 or C == 0: nothing to do, 0.  No table, no prepare call. */
+int dalm_linear_live_relu2(const void* A, int64_t lda, const void* Wup, void* Y, int64_t ldy, void* Act, int64_t ldact, int64_t R,
+                           int64_t C, int64_t K, const int32_t* perm, const int32_t* n_live, dalm_stream_t stream);
 
 #ifdef __cplusplus
 }

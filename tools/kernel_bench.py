@@ -447,6 +447,42 @@ def bench_geglu(R, C, rounds=3):
     return out
 
 
+def bench_relu2(R, C, rounds=3):
+    """ArceeMLP's activation: `dalm_relu2_fwd` / `dalm_relu2_bwd` on a dense [R, C] bf16 tensor, and beside them - alternating, in the
+    same process - the eager chain they replace: relu and square, and autograd's backward of the two.  Algorithmic bytes: forward
+    2 R C elements, backward 3 R C (the eager chain moves more: it writes and re-reads relu(y))."""
+    import torch.nn.functional as F
+
+    from dalm_amd import hip
+    from dalm_amd.models import tower_ops
+
+    dev = torch.device("cuda:0")
+    y = torch.randn(R, C, device=dev, dtype=torch.bfloat16)
+    assert tower_ops.relu2_supported(y)
+    d_act = torch.randn(R, C, device=dev, dtype=torch.bfloat16)
+    dy = torch.empty_like(d_act)
+    yd = y.clone().requires_grad_(True)
+
+    def kernel_bwd():
+        hip.call("dalm_relu2_bwd", hip.ptr(d_act), hip.ptr(y), hip.ptr(dy), hip.dtype_code(y), R, C, C, C, C, None, hip.stream())
+
+    def eager_fwd(a):
+        return torch.square(F.relu(a))
+
+    def eager_both():
+        return torch.autograd.grad(eager_fwd(yd), (yd,), d_act)
+
+    fns = {"kernel fwd (1 launch)": lambda: tower_ops.relu2(y), "kernel bwd (1 launch)": kernel_bwd,
+           "eager fwd (relu, square)": lambda: eager_fwd(y), "eager fwd + autograd bwd": eager_both}
+    n = R * C * 2
+    out = _alternating(fns, {"kernel fwd (1 launch)": 2 * n, "kernel bwd (1 launch)": 3 * n, "eager fwd (relu, square)": 2 * n,
+                             "eager fwd + autograd bwd": 5 * n}, rounds)
+    k, e = out["kernel fwd (1 launch)"]["s"] + out["kernel bwd (1 launch)"]["s"], out["eager fwd + autograd bwd"]["s"]
+    out["kernel fwd + bwd against eager"] = {"kernel_s": k, "eager_s": e, "eager_over_kernel": e / k}
+    out["kernel fwd against eager fwd"] = {"eager_over_kernel": out["eager fwd (relu, square)"]["s"] / out["kernel fwd (1 launch)"]["s"]}
+    return out
+
+
 def bench_gemma_norm(R, D, rounds=3):
     """GemmaRMSNorm with the residual add in front of it: `dalm_gemma_norm_fwd` (x + delta and the norm) / `dalm_gemma_norm_bwd`
     (with the residual-path gradient) on [R, D] bf16 rows with a bf16 weight, and beside them - alternating, in the same process -
@@ -598,6 +634,10 @@ def main():
     if args.only in ("", "gemma_norm"):
         # (24576 is the MLP's width, not a norm's: the norm kernels take rows of at most 8192 elements)
         res["gemma_norm Gemma-7B rows 4608 x 3072 bf16 (add + norm)"] = bench_gemma_norm(4608, 3072)
+    # the headline batch's rows (18 x 256) at AFM-4.5B's widths: intermediate 18432, hidden 2560
+    if args.only in ("", "relu2"):
+        res["relu2 AFM-4.5B rows 4608 x 18432 bf16"] = bench_relu2(4608, 18432)
+        res["relu2 rows 4608 x 2560 bf16"] = bench_relu2(4608, 2560)
     Path("gpurun_out").mkdir(exist_ok=True)
     Path("gpurun_out/kernel_bench.json").write_text(json.dumps(res, indent=1))
     print_results(res)

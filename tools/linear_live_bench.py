@@ -2,6 +2,7 @@
 
     python tools/linear_live_bench.py [--out profiles/linear_live_bench.txt] [--quick]
     python tools/linear_live_bench.py --mlp-fused [--out profiles/mlp_fused_bench.txt]
+    python tools/linear_live_bench.py --candidates --out FILE
 
 The seven GEMMs of one Llama-2-7b layer and the two of the materialised lm_head at R = 4608 padded rows (18 x 256), each with
   * every row live, and the four masks of `bench.synthetic_batch(dev, 100 + i)` under the generator's shifted rule;
@@ -15,6 +16,11 @@ larger of the two spreads: the routing table in dalm_amd/linear_live.py lists ex
 --mlp-fused: the fused forward of the frozen MLP node against the pair of launches it replaces, same protocol and same rule -
   forward   {dalm_linear_live gate|up + dalm_swiglu_fwd_2d_live}   against dalm_linear_live_swiglu
 at the four batch masks.  It ships only if it beats its pair by more than three times the larger spread at EVERY mask.
+
+--candidates: the two GEMM shapes of an AFM-4.5B layer's ungated MLP (hidden 2560, intermediate 18432) under the same protocol and
+the same rule - they enter ROUTED_SHAPES only if the kernel clears the library arm at every batch mask, in every run - and the fused
+up forward of the ReLU^2 node, {dalm_linear_live up + dalm_relu2_fwd} against dalm_linear_live_relu2.  The solution table was tuned
+at Llama-2-7b's shapes: at these the library arm runs the library's own choice.
 """
 from __future__ import annotations
 
@@ -46,6 +52,12 @@ GEMMS = [
     ("down dgrad", [(11008, 4096)], False),
     ("lm_head fwd (materialised logits)", [(32000, 4096)], False),
     ("lm_head dgrad", [(4096, 32000)], False),
+]
+
+# shapes measured for the table but not (yet) in it: AFM-4.5B's MLP, hidden 2560, intermediate 18432, no gate
+CANDIDATES = [
+    ("AFM up fwd / down dgrad", [(18432, 2560)], False),
+    ("AFM down fwd / up dgrad", [(2560, 18432)], False),
 ]
 
 
@@ -163,6 +175,40 @@ def bench_mlp_fused(mask_list, dev, emit, c=11008, h=4096):
     return ships
 
 
+def bench_relu2_fused(mask_list, dev, emit, c=18432, h=2560):
+    """The paired arms of the ReLU^2 node's forward; returns whether the fused one clears its pair at every batch mask."""
+    from dalm_amd import hip
+
+    gen = torch.Generator(device=dev).manual_seed(13)
+    ring = max(2, min(LAUNCHES, RING_BYTES // (c * h * 2) + 1))
+    wup = [(torch.randn(c, h, device=dev, generator=gen) * 0.02).bfloat16() for _ in range(ring)]
+    x = torch.randn(R, h, device=dev, generator=gen).bfloat16()
+    y = torch.zeros(R, c, dtype=torch.bfloat16, device=dev)
+    act = torch.zeros(R, c, dtype=torch.bfloat16, device=dev)
+    dt = hip.dtype_code(y)
+    ships = True
+    for mname, vec in mask_list:
+        part = linear_live.row_partition(vec)
+        n_live = int(part[1].item())
+        perm, nl = hip.ptr(part[0]), hip.ptr(part[1])
+
+        def pair(i):
+            linear_live.linear_live(x, wup[i % ring], part, out=y)
+            hip.call("dalm_relu2_fwd", hip.ptr(y), hip.ptr(act), dt, R, c, c, c, hip.ptr(vec), hip.stream())
+
+        def fused(i):
+            hip.call("dalm_linear_live_relu2", hip.ptr(x), h, hip.ptr(wup[i % ring]), hip.ptr(y), c, hip.ptr(act), c, R, c, h, perm, nl,
+                     hip.stream())
+
+        (tp, sp), (tf, sf) = time_graph(pair), time_graph(fused)
+        win = tp - tf > 3 * max(sp, sf)
+        ships = ships and (win or mname == "all live")
+        fl = linear_live.flops(n_live, c, h)
+        emit(f"  {mname:10s} live {n_live:5d}  forward  pair {tp * 1e6:8.1f} us (spread {sp * 1e6:5.1f})  fused {tf * 1e6:8.1f} us "
+             f"(spread {sf * 1e6:5.1f})  saves {(tp - tf) * 1e6:7.1f} us  fused {fl / tf / 1e12:7.1f} TF/s  {'win' if win else '-'}")
+    return ships
+
+
 def main_mlp_fused(args, dev, emit, lines):
     ml = masks(dev)
     emit("mlp_fused: {dalm_linear_live + dalm_swiglu_*_2d_live} against the fused entry point, C = 11008, H = 4096")
@@ -178,8 +224,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--mlp-fused", action="store_true", help="the paired arms of the fused MLP node only")
+    ap.add_argument("--candidates", action="store_true", help="the AFM-4.5B MLP shapes (not in the table) and the ReLU^2 node's forward")
     ap.add_argument("--quick", action="store_true", help="all-live and one batch mask only")
     args = ap.parse_args()
+    if args.candidates and args.out is None:
+        ap.error("--candidates needs --out: it does not replace a committed profile")
     if args.out is None:
         args.out = str(ROOT / "profiles" / ("mlp_fused_bench.txt" if args.mlp_fused else "linear_live_bench.txt"))
     if not torch.cuda.is_available():
@@ -206,7 +255,7 @@ def main():
     if args.quick:
         ml = ml[:2]
     verdict = []
-    for name, members, halves in GEMMS:
+    for name, members, halves in (CANDIDATES if args.candidates else GEMMS):
         n, k = members[0]
         emit(f"{name}: N = {n}, K = {k}, members {len(members)}, routed now: "
              f"{'kernel' if (R, n, k) in linear_live.ROUTED_SHAPES else 'library'}")
@@ -217,6 +266,10 @@ def main():
     emit("verdict (faster than the library arm by > 3 x the larger spread, at all batch masks):")
     for v in verdict:
         emit(v)
+    if args.candidates:
+        emit("relu2 node forward: {dalm_linear_live up + dalm_relu2_fwd} against dalm_linear_live_relu2, C = 18432, H = 2560")
+        ok = bench_relu2_fused(ml, dev, emit)
+        emit(f"  fused forward: {'clears its pair at every batch mask' if ok else 'does not clear its pair at every batch mask'}")
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     Path(args.out).write_text("\n".join(lines) + "\n")
 
