@@ -40,6 +40,8 @@
 // Algorithmic bytes: forward q, k, v read + o written = 4 B H T hd el (151 MB at cfg3); backward q, k, v, o, dO read + dq, dk, dv
 // written = 8 B H T hd el (302 MB; the two launches together move 1.5 x that: each re-reads q, k, v, dO); algorithmic flops
 // 2 / 5 GEMMs x 2 T^2 hd per head over the live tiles (dq and dk/dv each recompute S and dP: 7 are executed).
+// MPNet retrievers (a per-head relative-position bias that depends on the column difference only): the BIAS forms of the second-form
+// kernels at head width 64 and the dalm_attn_rel_* entry points - see "Relative-position bias" below.
 #include <cstdio>
 #include "common.hpp"
 #include "dispatch.hpp"
@@ -87,7 +89,12 @@ struct AttnBwdParams {
   float* part;                           // f32 partials [S][dK, dV][part_rows token rows][Hkv][hd] in caller workspace, summed in
   int64_t part_rows;                     // the order s = 0 .. S - 1 by attn_gqa_combine_kernel (S = 1: no workspace, no combine)
   int Hkv, G;                            // GROUPED-QUERY heads: k, v, dk, dv have Hkv heads, query head h reads KV head h / G,
-};                                       // G = H / Hkv (repeat_kv's order: KV head j serves query heads j G .. j G + G - 1)
+                                         // G = H / Hkv (repeat_kv's order: KV head j serves query heads j G .. j G + G - 1)
+  const float* rel;                      // BIAS kernels only (see "Relative-position bias"): head h's vector at rel + h rel_sh,
+  const int* cols;                       // 2 rel_T - 1 entries, entry rel_T - 1 = column difference 0; cols [n_tokens]: a packed
+  int64_t rel_sh;                        // token's original column (NULL, and always in the padded layout: the row index)
+  int rel_T;
+};
 
 // where sequence b starts (token rows) and how many rows it has
 struct Seq { int64_t r0; int T; };
@@ -990,6 +997,59 @@ __device__ __forceinline__ void stage_ready(const uint32_t (&nword)[2]) {
   asm volatile("" :: "v"(nword[0]), "v"(nword[1]) : "memory");
 }
 
+
+// Relative-position bias (MPNet: relative_attention_bias(bucket(j - i))[h] with positions arange(T) - a function of the head and
+// the COLUMN DIFFERENCE only, a Toeplitz matrix per head): the BIAS forms of the three second-form kernels add
+//   rel[h][col(j) - col(i) + rel_T - 1]
+// to scale q.k in f32, as the addend of the fma that forms the log2-domain score.  The head's vector (2 rel_T - 1 floats) is
+// copied to LDS once per workgroup, multiplied by log2(e) on the way (the ONE place where it is scaled), behind the streamed
+// images; a score element costs one ds_read_b32 whose address is (streamed row's column) + (own row's centre - column): lanes
+// are own rows, so a wave reads consecutive words.  Columns: the streamed block's 64 go to LDS once per block (LDS-DMA from
+// `cols`, or the row indices written by wave 0), the own row's one is a register.  Columns are clamped to the sequence's last
+// row, where the streamed images are: with rel_T >= T (host check) and cols < rel_T every index stays inside the vector.
+// The bias changes no tile's liveness: mask words, live bytes and the block order are the bias-free kernels'.
+// LDS bytes behind the images: 2 x 256 (columns of the two stages) + 4 (2 rel_T - 1) rounded up to 16.
+__host__ __device__ constexpr int bias_lds(int rel_T) { return 512 + ((4 * (2 * rel_T - 1) + 15) & ~15); }
+// the stage's 64 columns (wave 0 calls this inside `issue`)
+__device__ __forceinline__ void bias_stage_cols(const AttnBwdParams& p, const Seq& sq, int row0, int T, int l, unsigned char* lds,
+                                                unsigned int lds_addr) {
+  const int row = min(row0 + l, T - 1);
+  if (p.cols) glds4(p.cols + sq.r0, 4u * static_cast<unsigned int>(row), lds_addr);
+  else reinterpret_cast<int*>(lds)[l] = row;
+}
+// head h's vector -> LDS, in log2 units
+__device__ __forceinline__ void bias_stage_vector(const AttnBwdParams& p, int h, int t, unsigned char* lds) {
+  const float* rv = p.rel + h * p.rel_sh;
+  float* dst = reinterpret_cast<float*>(lds);
+  for (int x = t; x < 2 * p.rel_T - 1; x += 256) dst[x] = rv[x] * kLog2e;
+}
+// the own row's column (clamped as the streamed ones)
+__device__ __forceinline__ int bias_own_col(const AttnBwdParams& p, const Seq& sq, int row, int T) {
+  const int r = min(row, T - 1);
+  return p.cols ? p.cols[sq.r0 + r] : r;
+}
+// stage_ready of a BIAS kernel: LDS stores (the vector, wave 0's columns) are waited for as well - lgkmcnt(0) costs nothing here,
+// every LDS read of the previous block has been consumed by its MFMAs
+__device__ __forceinline__ void stage_ready_bias(const uint32_t (&nword)[2]) {
+  __builtin_amdgcn_s_waitcnt(0x0070);                          // vmcnt(0), lgkmcnt(0)
+  asm volatile("s_barrier" ::: "memory");
+  asm volatile("" :: "v"(nword[0]), "v"(nword[1]) : "memory");
+}
+// the 16 bias terms of a 32 x 32 tile (register r <-> streamed row (r & 3) + 8 (r >> 2) + 4 hi of sub-block `sub`), log2 units
+// OWN_IS_KEY false (forward, dq: own rows are queries): entry streamed column + own_off, own_off = rel_T - 1 - own column;
+// true (dk / dv: own rows are keys): entry own_off - streamed column, own_off = rel_T - 1 + own column
+template <bool OWN_IS_KEY>
+__device__ __forceinline__ void bias_tile(const unsigned char* cols_s, const unsigned char* vec, int sub, int hi, int own_off, float (&bs)[16]) {
+  const float* rv = reinterpret_cast<const float*>(vec);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int4 c4 = *reinterpret_cast<const int4*>(cols_s + 4 * (32 * sub + 8 * q + 4 * hi));
+    const int c[4] = {c4.x, c4.y, c4.z, c4.w};
+#pragma unroll
+    for (int u = 0; u < 4; ++u) bs[4 * q + u] = rv[OWN_IS_KEY ? own_off - c[u] : c[u] + own_off];
+  }
+}
+
 template <int HD>
 constexpr int dkdv2_lds() { return 4 * 64 * 2 * HD + 1024; }
 
@@ -1001,11 +1061,13 @@ constexpr int dkdv2_lds() { return 4 * 64 * 2 * HD + 1024; }
 // this kernel's LDS time) are gone: dO^T / Q^T operands are transpose reads of the row-major images.  The log-sum-exp and D of the
 // block's rows travel the same way (4-byte pieces).  K / V fragments of the workgroup's own rows come straight from HBM in
 // fragment shape (once per workgroup).
-template <int HD, bool DROP>
+// BIAS ("Relative-position bias" above): the query block's columns at dkdv2_lds() + 256 stage, the head's vector behind them.
+template <int HD, bool DROP, bool BIAS = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv2_kernel(const AttnBwdParams p) {
   using A = AT<HD>;
   constexpr int NDH = A::ND / 2;
   constexpr int IMG = 64 * 2 * HD;                             // one block image
+  constexpr int BOFF = dkdv2_lds<HD>();                        // BIAS: columns of the two stages, then the vector
   extern __shared__ __attribute__((aligned(16))) unsigned char dlds[];
   // stage s: Q image at s 2 IMG, dO image at s 2 IMG + IMG; lse / D of the block's rows at 4 IMG + 512 s (+ 256)
   const int t = threadIdx.x, w = t >> 6, l = t & 63, l31 = l & 31, hi = l >> 5, jt = w >> 1, dh = w & 1;
@@ -1045,6 +1107,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv2_kernel(const AttnBwdPar
       const unsigned int row = static_cast<unsigned int>(min(64 * ib + l, T - 1));
       glds4(lse_row, 4u * row, lds0 + 4 * IMG + 512 * stage);
       glds4(delta_row, 4u * row, lds0 + 4 * IMG + 512 * stage + 256);
+      if constexpr (BIAS) bias_stage_cols(p, sq, 64 * ib, T, l, dlds + BOFF + 256 * stage, lds0 + BOFF + 256 * stage);
     }
 #pragma unroll
     for (int c = 0; c < 2; ++c)
@@ -1053,6 +1116,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv2_kernel(const AttnBwdPar
   int cur = __builtin_ctz(blocks);
   blocks &= blocks - 1u;
   issue(cur, 0);
+  int own_off = 0;
+  if constexpr (BIAS) {
+    bias_stage_vector(p, h, t, dlds + BOFF + 512);
+    own_off = p.rel_T - 1 + bias_own_col(p, sq, j, T);
+  }
+  (void)own_off;
 
   bf16x8 Kb[A::KK], Vb[A::KK];
   {
@@ -1076,7 +1145,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv2_kernel(const AttnBwdPar
   (void)drop;
   int stage = 0;
   while (true) {
-    stage_ready(nword);
+    if constexpr (BIAS) stage_ready_bias(nword); else stage_ready(nword);
     const uint32_t word[2] = {nword[0], nword[1]};
     const int ib = cur;
     (void)ib;
@@ -1101,6 +1170,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv2_kernel(const AttnBwdPar
         S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_frag<HD>(Qi, is, l31, hi, kk), Kb[kk], S, 0, 0, 0);
         dP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_frag<HD>(Gi, is, l31, hi, kk), Vb[kk], dP, 0, 0, 0);
       }
+      float bs[16];
+      if constexpr (BIAS) bias_tile<true>(dlds + BOFF + 256 * stage, dlds + BOFF + 512, is, hi, own_off, bs);
       unsigned int ppk[8], dpk[8];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -1111,7 +1182,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv2_kernel(const AttnBwdPar
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const int il = 8 * q + 4 * hi + u;
-          pv[u] = ((word[is] >> il) & 1u) ? __builtin_amdgcn_exp2f(fmaf(S[4 * q + u], c1, nl[u])) : 0.f;
+          const float off = BIAS ? nl[u] + bs[4 * q + u] : nl[u];
+          pv[u] = ((word[is] >> il) & 1u) ? __builtin_amdgcn_exp2f(fmaf(S[4 * q + u], c1, off)) : 0.f;
           float dpe = dP[4 * q + u];
           if constexpr (DROP) {
             const unsigned int c = (static_cast<unsigned int>(bh) * p.T + 64 * ib + 32 * is + il) * p.T + j;
@@ -1428,10 +1500,11 @@ constexpr int stream2_lds() { return 4 * 64 * 2 * HD; }      // two stages of (K
 // D = rowsum(dO o O) come from fragment-shaped loads (a lane pair l, l ^ 32 holds one row: even / odd 16-byte chunks); D is summed
 // in the first form's order (chunk dot products, then the butterfly over chunk pairs) so that both forms write the same bits.
 // GQA: k / v have Hkv heads and query head h streams KV head h / G - the only difference (same K / V values: same bits).
-template <int HD, bool DROP, bool GQA = false>
-__global__ __launch_bounds__(256, DROP ? 2 : AT<HD>::OCC) void attn_bwd_dq2_kernel(const AttnBwdParams p) {
+template <int HD, bool DROP, bool GQA = false, bool BIAS = false>
+__global__ __launch_bounds__(256, BIAS ? 2 : (DROP ? 2 : AT<HD>::OCC)) void attn_bwd_dq2_kernel(const AttnBwdParams p) {
   using A = AT<HD>;
   constexpr int IMG = 64 * 2 * HD;
+  constexpr int BOFF = stream2_lds<HD>();                      // BIAS: the key block's columns (two stages), then the vector
   extern __shared__ __attribute__((aligned(16))) unsigned char dlds[];
   const int t = threadIdx.x, w = t >> 6, l = t & 63, l31 = l & 31, hi = l >> 5;
   int blk, h, b;
@@ -1463,6 +1536,7 @@ __global__ __launch_bounds__(256, DROP ? 2 : AT<HD>::OCC) void attn_bwd_dq2_kern
     const unsigned int ki = lds0 + stage * (2 * IMG);
     dma_block<HD>(kbase, sk_row, 64 * jb, T, ki, wu, l);
     dma_block<HD>(vbase, sv_row, 64 * jb, T, ki + IMG, wu, l);
+    if constexpr (BIAS) if (wu == 0) bias_stage_cols(p, sq, 64 * jb, T, l, dlds + BOFF + 256 * stage, lds0 + BOFF + 256 * stage);
 #pragma unroll
     for (int c = 0; c < 2; ++c)
       nword[c] = (i < Tp && 2 * jb + c < p.W) ? p.bits_rows[(static_cast<int64_t>(b) * Tp + i) * p.W + 2 * jb + c] : 0u;
@@ -1470,6 +1544,12 @@ __global__ __launch_bounds__(256, DROP ? 2 : AT<HD>::OCC) void attn_bwd_dq2_kern
   int cur = __builtin_ctz(blocks);
   blocks &= blocks - 1u;
   issue(cur, 0);
+  int own_off = 0;
+  if constexpr (BIAS) {
+    bias_stage_vector(p, h, t, dlds + BOFF + 512);
+    own_off = p.rel_T - 1 - bias_own_col(p, sq, i, T);
+  }
+  (void)own_off;
 
   bf16x8 Qb[A::KK], Gb[A::KK];
   float Dl;
@@ -1506,7 +1586,7 @@ __global__ __launch_bounds__(256, DROP ? 2 : AT<HD>::OCC) void attn_bwd_dq2_kern
   (void)drop; (void)cbase;
   int stage = 0;
   while (true) {
-    stage_ready(nword);
+    if constexpr (BIAS) stage_ready_bias(nword); else stage_ready(nword);
     const uint32_t word[2] = {nword[0], nword[1]};
     const int jb = cur;
     (void)jb;
@@ -1529,6 +1609,8 @@ __global__ __launch_bounds__(256, DROP ? 2 : AT<HD>::OCC) void attn_bwd_dq2_kern
         St = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_frag<HD>(Ki, js, l31, hi, kk), Qb[kk], St, 0, 0, 0);
         Pt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_frag<HD>(Vi, js, l31, hi, kk), Gb[kk], Pt, 0, 0, 0);
       }
+      float bs[16];
+      if constexpr (BIAS) bias_tile<false>(dlds + BOFF + 256 * stage, dlds + BOFF + 512, js, hi, own_off, bs);
       unsigned int pk[8];
 #pragma unroll
       for (int r = 0; r < 16; r += 2) {
@@ -1539,7 +1621,8 @@ __global__ __launch_bounds__(256, DROP ? 2 : AT<HD>::OCC) void attn_bwd_dq2_kern
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           const int jl = jl0 + u;
-          const float pv = ((word[js] >> jl) & 1u) ? __builtin_amdgcn_exp2f(fmaf(St[r + u], c1, nl)) : 0.f;
+          const float off = BIAS ? nl + bs[r + u] : nl;
+          const float pv = ((word[js] >> jl) & 1u) ? __builtin_amdgcn_exp2f(fmaf(St[r + u], c1, off)) : 0.f;
           float dpe = Pt[r + u];
           if constexpr (DROP) dpe = ((u ? hw >> 16 : hw & 0xffffu) >= drop.thresh) ? dpe * drop.ks : 0.f;
           ds[u] = pv * (dpe - Dl);
@@ -1567,10 +1650,11 @@ __global__ __launch_bounds__(256, DROP ? 2 : AT<HD>::OCC) void attn_bwd_dq2_kern
 
 // Forward, second form: attn_fwd_kernel's arithmetic on the same data path (K image read row-wise, V image by transpose reads).
 // GQA: as in attn_bwd_dq2_kernel.
-template <int HD, bool DROP, bool GQA = false>
-__global__ __launch_bounds__(256, (DROP && HD == 64) ? 2 : AT<HD>::OCC) void attn_fwd2_kernel(const AttnBwdParams p) {
+template <int HD, bool DROP, bool GQA = false, bool BIAS = false>
+__global__ __launch_bounds__(256, BIAS ? (DROP ? 2 : 3) : ((DROP && HD == 64) ? 2 : AT<HD>::OCC)) void attn_fwd2_kernel(const AttnBwdParams p) {
   using A = AT<HD>;
   constexpr int IMG = 64 * 2 * HD;
+  constexpr int BOFF = stream2_lds<HD>();                      // BIAS: the key block's columns (two stages), then the vector
   extern __shared__ __attribute__((aligned(16))) unsigned char dlds[];
   const int t = threadIdx.x, w = t >> 6, l = t & 63, l31 = l & 31, hi = l >> 5;
   int blk, h, b;
@@ -1604,6 +1688,7 @@ __global__ __launch_bounds__(256, (DROP && HD == 64) ? 2 : AT<HD>::OCC) void att
     const unsigned int ki = lds0 + stage * (2 * IMG);
     dma_block<HD>(kbase, sk_row, 64 * jb, T, ki, wu, l);
     dma_block<HD>(vbase, sv_row, 64 * jb, T, ki + IMG, wu, l);
+    if constexpr (BIAS) if (wu == 0) bias_stage_cols(p, sq, 64 * jb, T, l, dlds + BOFF + 256 * stage, lds0 + BOFF + 256 * stage);
 #pragma unroll
     for (int c = 0; c < 2; ++c)
       nword[c] = (i < Tp && 2 * jb + c < p.W) ? p.bits_rows[(static_cast<int64_t>(b) * Tp + i) * p.W + 2 * jb + c] : 0u;
@@ -1611,6 +1696,12 @@ __global__ __launch_bounds__(256, (DROP && HD == 64) ? 2 : AT<HD>::OCC) void att
   int cur = __builtin_ctz(blocks);
   blocks &= blocks - 1u;
   issue(cur, 0);
+  int own_off = 0;
+  if constexpr (BIAS) {
+    bias_stage_vector(p, h, t, dlds + BOFF + 512);
+    own_off = p.rel_T - 1 - bias_own_col(p, sq, i, T);
+  }
+  (void)own_off;
 
   bf16x8 Qb[A::KK];
   {
@@ -1632,7 +1723,7 @@ __global__ __launch_bounds__(256, (DROP && HD == 64) ? 2 : AT<HD>::OCC) void att
   (void)drop; (void)cbase;
   int stage = 0;
   while (true) {
-    stage_ready(nword);
+    if constexpr (BIAS) stage_ready_bias(nword); else stage_ready(nword);
     const uint32_t word[2] = {nword[0], nword[1]};
     const int jb = cur;
     (void)jb;
@@ -1653,11 +1744,14 @@ __global__ __launch_bounds__(256, (DROP && HD == 64) ? 2 : AT<HD>::OCC) void att
 #pragma unroll
       for (int kk = 0; kk < A::KK; ++kk)
         St = __builtin_amdgcn_mfma_f32_32x32x16_bf16(img_frag<HD>(Ki, js, l31, hi, kk), Qb[kk], St, 0, 0, 0);
+      float bs[16];
+      if constexpr (BIAS) bias_tile<false>(dlds + BOFF + 256 * stage, dlds + BOFF + 512, js, hi, own_off, bs);
       float mx = -INFINITY;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int jl = (r & 3) + 8 * (r >> 2) + 4 * hi;
-        St[r] = ((word[js] >> jl) & 1u) ? St[r] * c1 : -INFINITY;
+        if constexpr (BIAS) St[r] = ((word[js] >> jl) & 1u) ? fmaf(St[r], c1, bs[r]) : -INFINITY;
+        else St[r] = ((word[js] >> jl) & 1u) ? St[r] * c1 : -INFINITY;
         mx = fmaxf(mx, St[r]);
       }
       mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
@@ -1792,6 +1886,22 @@ inline int64_t gqa_splits(int64_t B, int64_t H, int64_t Hkv, int64_t T) {
 }
 struct GqaSplit { int64_t S; void* ws; size_t ws_bytes; };     // S = 0: gqa_splits decides
 
+// The relative-position bias of the dalm_attn_rel_* entry points (NULL: the bias-free kernels): checks and parameter fill shared by
+// the forward and the backward launcher.
+struct RelBias { const float* rel; int64_t stride_h, rel_T; const int32_t* cols; };
+inline int set_rel_bias(const char* fn, AttnBwdParams& p, const RelBias* rb, int64_t H, int64_t Hkv, int64_t T, int64_t hd) {
+  p.rel = nullptr; p.cols = nullptr; p.rel_sh = 0; p.rel_T = 0;
+  if (!rb) return 0;
+  if (!rb->rel) return fail(DALM_E_NULL, fn, "null pointer argument (rel)");
+  if (hd != 64 || Hkv != H) return fail(DALM_E_SHAPE, fn, "head width must be 64 (equal heads) with a relative-position bias");
+  if (rb->rel_T < T || rb->rel_T > 2048) return fail(DALM_E_SHAPE, fn, "need T <= rel_T <= 2048: the bias vector is centred at rel_T - 1");
+  if (rb->stride_h < 2 * rb->rel_T - 1) return fail(DALM_E_SHAPE, fn, "rel_stride_h must be at least 2 rel_T - 1");
+  if (reinterpret_cast<uintptr_t>(rb->rel) % 4 != 0 || reinterpret_cast<uintptr_t>(rb->cols) % 4 != 0)
+    return fail(DALM_E_ALIGN, fn, "rel and cols must be 4-byte aligned");
+  p.rel = rb->rel; p.cols = rb->cols; p.rel_sh = rb->stride_h; p.rel_T = static_cast<int>(rb->rel_T);
+  return 0;
+}
+
 inline void set_dropout(AttnBwdParams& p, float dropout_p, const void* seed, uint32_t salt) {
   const bool on = dropout_p > 0.f;
   p.seed = on ? static_cast<const unsigned long long*>(seed) : nullptr;
@@ -1835,10 +1945,12 @@ static int dalm_attn_bwd_any(const void* q, const void* k, const void* v, const 
                          int64_t Hkv, int64_t T, int64_t hd, float scale, const int64_t* strides, const void* cos, const void* sin,
                          int64_t cs_stride_b, int64_t cs_stride_t, float dropout_p, const void* seed, uint32_t salt, void* dq,
                          void* dk, void* dv, float* delta, dalm_stream_t stream, GqaSplit split = {1, nullptr, 0},
-                         bool gqa_entry = false) {
+                         bool gqa_entry = false, const RelBias* rb = nullptr) {
   DALM_REQUIRE(q && k && v && o && d_o && lse && bits_rows && bits_cols && live && strides && dq && dk && dv && delta, DALM_E_NULL,
                "null pointer argument");
   if (const int rc = check_heads(__func__, H, Hkv)) return rc;
+  AttnBwdParams p;
+  if (const int rc = set_rel_bias(__func__, p, rb, H, Hkv, T, hd)) return rc;
   if (gqa_entry) DALM_REQUIRE(hd == 128 || hd == 64, DALM_E_SHAPE, "head width must be 64 or 128");
   else DALM_REQUIRE(hd == 128 || hd == 64 || hd == 32, DALM_E_SHAPE, "head width must be 32, 64 or 128");
   DALM_REQUIRE(hd != 32 || (cos == nullptr && sin == nullptr), DALM_E_SHAPE,
@@ -1858,7 +1970,6 @@ static int dalm_attn_bwd_any(const void* q, const void* k, const void* v, const 
   DALM_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f && (dropout_p == 0.f || (seed && T % 2 == 0)), DALM_E_SHAPE,
                "dropout needs 0 <= p < 1, a device seed word and an even T");
   DALM_REQUIRE(Hkv == H || dropout_p == 0.f, DALM_E_SHAPE, "grouped-query heads run without attention dropout");
-  AttnBwdParams p;
   set_dropout(p, dropout_p, seed, salt);
   p.cu = cu;
   p.Hkv = static_cast<int>(Hkv); p.G = static_cast<int>(H / Hkv);
@@ -1907,6 +2018,17 @@ static int dalm_attn_bwd_any(const void* q, const void* k, const void* v, const 
   const int64_t pairs8 = (B * H + 7) / 8 * 8;
   const dim3 grid_dq(static_cast<unsigned>(pairs8 * ((T + 127) / 128))), grid_dkdv(static_cast<unsigned>(pairs8 * ((T + 63) / 64)));
   hipStream_t s = as_stream(stream);
+  if (p.rel) {         // relative-position bias: the second forms only, the environment switches select nothing
+    const size_t extra = bias_lds(p.rel_T);
+    if (p.seed) {
+      hipLaunchKernelGGL((attn_bwd_dq2_kernel<64, true, false, true>), grid_dq, dim3(256), stream2_lds<64>() + extra, s, p);
+      hipLaunchKernelGGL((attn_bwd_dkdv2_kernel<64, true, true>), grid_dkdv, dim3(256), dkdv2_lds<64>() + extra, s, p);
+    } else {
+      hipLaunchKernelGGL((attn_bwd_dq2_kernel<64, false, false, true>), grid_dq, dim3(256), stream2_lds<64>() + extra, s, p);
+      hipLaunchKernelGGL((attn_bwd_dkdv2_kernel<64, false, true>), grid_dkdv, dim3(256), dkdv2_lds<64>() + extra, s, p);
+    }
+    return check_launch(__func__);
+  }
   if (Hkv != H) {      // grouped-query heads: dq per query head, dk / dv per KV head (a workgroup runs through its whole group)
     const dim3 grid_kv(static_cast<unsigned>((B * Hkv + 7) / 8 * 8 * ((T + 63) / 64)));
     const dim3 grid_split(static_cast<unsigned>((B * Hkv * p.S + 7) / 8 * 8 * ((T + 63) / 64)));
@@ -1993,9 +2115,11 @@ extern "C" size_t dalm_attn_gqa_bwd_workspace_bytes(int64_t rows, int64_t Hkv, i
 static int dalm_attn_fwd_any(const void* q, const void* k, const void* v, const uint32_t* bits_rows, const uint8_t* live,
                             const int32_t* cu, int64_t B, int64_t H, int64_t Hkv, int64_t T, int64_t hd, float scale,
                             const int64_t* strides, float dropout_p, const void* seed, uint32_t salt, void* o, float* lse,
-                            dalm_stream_t stream, bool gqa_entry = false) {
+                            dalm_stream_t stream, bool gqa_entry = false, const RelBias* rb = nullptr) {
   DALM_REQUIRE(q && k && v && bits_rows && live && strides && o && lse, DALM_E_NULL, "null pointer argument");
   if (const int rc = check_heads(__func__, H, Hkv)) return rc;
+  AttnBwdParams p = {};
+  if (const int rc = set_rel_bias(__func__, p, rb, H, Hkv, T, hd)) return rc;
   if (gqa_entry) DALM_REQUIRE(hd == 128 || hd == 64, DALM_E_SHAPE, "head width must be 64 or 128");
   else DALM_REQUIRE(hd == 128 || hd == 64 || hd == 32, DALM_E_SHAPE, "head width must be 32, 64 or 128");
   DALM_REQUIRE(B > 0 && H > 0 && T > 0 && T <= 2048 && B * H <= (1ll << 24), DALM_E_SHAPE, "need 0 < T <= 2048 and B H <= 2^24");
@@ -2010,7 +2134,6 @@ static int dalm_attn_fwd_any(const void* q, const void* k, const void* v, const 
   for (int i : {1, 2})
     DALM_REQUIRE(T * strides[3 * i + 2] < (1ll << 30), DALM_E_SHAPE, "T x row stride must stay below 2^30 elements");
   DALM_REQUIRE(Hkv == H || dropout_p == 0.f, DALM_E_SHAPE, "grouped-query heads run without attention dropout");
-  AttnBwdParams p = {};
   set_dropout(p, dropout_p, seed, salt);
   p.cu = cu;
   p.Hkv = static_cast<int>(Hkv); p.G = static_cast<int>(H / Hkv);
@@ -2027,6 +2150,12 @@ static int dalm_attn_fwd_any(const void* q, const void* k, const void* v, const 
   const int64_t pairs8 = (B * H + 7) / 8 * 8;
   const dim3 grid(static_cast<unsigned>(pairs8 * ((T + 127) / 128)));
   hipStream_t s = as_stream(stream);
+  if (p.rel) {                                                 // relative-position bias: the second form only
+    const size_t lds = stream2_lds<64>() + bias_lds(p.rel_T);
+    if (p.seed) hipLaunchKernelGGL((attn_fwd2_kernel<64, true, false, true>), grid, dim3(256), lds, s, p);
+    else hipLaunchKernelGGL((attn_fwd2_kernel<64, false, false, true>), grid, dim3(256), lds, s, p);
+    return check_launch(__func__);
+  }
   if (Hkv != H) {                                              // grouped-query heads: query head h reads KV head h / G
     if (hd == 128) hipLaunchKernelGGL((attn_fwd2_kernel<128, false, true>), grid, dim3(256), stream2_lds<128>(), s, p);
     else hipLaunchKernelGGL((attn_fwd2_kernel<64, false, true>), grid, dim3(256), stream2_lds<64>(), s, p);
@@ -2074,4 +2203,50 @@ extern "C" int dalm_attn_gqa_fwd(const void* q, const void* k, const void* v, co
                                  const int32_t* cu_seqlens, int64_t B, int64_t H, int64_t Hkv, int64_t T, int64_t hd, float scale,
                                  const int64_t* strides, void* o, float* lse, dalm_stream_t stream) {
   return dalm_attn_fwd_any(q, k, v, bits_rows, live, cu_seqlens, B, H, Hkv, T, hd, scale, strides, 0.f, nullptr, 0u, o, lse, stream, true);
+}
+
+// The same four calls with a per-head relative-position bias (MPNet): score = scale q.k + rel[h][col(j) - col(i) + rel_T - 1], rel
+// f32 [H][rel_stride_h] with 2 rel_T - 1 entries per head (entry rel_T - 1: column difference 0), rel_T >= T; col = the row index
+// within the sequence, or - packed forms, cols given - cols[token] in [0, rel_T).  Head width 64, equal heads, second-form kernels
+// (the DALM_ATTN_* switches select nothing).  No gradient for rel.
+extern "C" int dalm_attn_rel_fwd(const void* q, const void* k, const void* v, const uint32_t* bits_rows, const uint8_t* live, int64_t B,
+                                 int64_t H, int64_t T, int64_t hd, float scale, const int64_t* strides, const float* rel,
+                                 int64_t rel_stride_h, int64_t rel_T, float dropout_p, const void* seed, uint32_t salt, void* o,
+                                 float* lse, dalm_stream_t stream) {
+  const RelBias rb = {rel, rel_stride_h, rel_T, nullptr};
+  return dalm_attn_fwd_any(q, k, v, bits_rows, live, nullptr, B, H, H, T, hd, scale, strides, dropout_p, seed, salt, o, lse, stream,
+                           false, &rb);
+}
+
+extern "C" int dalm_attn_rel_fwd_packed(const void* q, const void* k, const void* v, const uint32_t* bits_rows, const uint8_t* live,
+                                        const int32_t* cu_seqlens, int64_t B, int64_t H, int64_t T, int64_t hd, float scale,
+                                        const int64_t* strides, const float* rel, int64_t rel_stride_h, int64_t rel_T,
+                                        const int32_t* cols, float dropout_p, const void* seed, uint32_t salt, void* o, float* lse,
+                                        dalm_stream_t stream) {
+  DALM_REQUIRE(cu_seqlens, DALM_E_NULL, "null pointer argument");
+  const RelBias rb = {rel, rel_stride_h, rel_T, cols};
+  return dalm_attn_fwd_any(q, k, v, bits_rows, live, cu_seqlens, B, H, H, T, hd, scale, strides, dropout_p, seed, salt, o, lse, stream,
+                           false, &rb);
+}
+
+extern "C" int dalm_attn_rel_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
+                                 const uint32_t* bits_rows, const uint32_t* bits_cols, const uint8_t* live, int64_t B, int64_t H,
+                                 int64_t T, int64_t hd, float scale, const int64_t* strides, const float* rel, int64_t rel_stride_h,
+                                 int64_t rel_T, float dropout_p, const void* seed, uint32_t salt, void* dq, void* dk, void* dv,
+                                 float* delta, dalm_stream_t stream) {
+  const RelBias rb = {rel, rel_stride_h, rel_T, nullptr};
+  return dalm_attn_bwd_any(q, k, v, o, d_o, lse, bits_rows, bits_cols, live, nullptr, B, H, H, T, hd, scale, strides, nullptr, nullptr,
+                           0, 0, dropout_p, seed, salt, dq, dk, dv, delta, stream, GqaSplit{1, nullptr, 0}, false, &rb);
+}
+
+extern "C" int dalm_attn_rel_bwd_packed(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
+                                        const uint32_t* bits_rows, const uint32_t* bits_cols, const uint8_t* live,
+                                        const int32_t* cu_seqlens, int64_t B, int64_t H, int64_t T, int64_t hd, float scale,
+                                        const int64_t* strides, const float* rel, int64_t rel_stride_h, int64_t rel_T,
+                                        const int32_t* cols, float dropout_p, const void* seed, uint32_t salt, void* dq, void* dk,
+                                        void* dv, float* delta, dalm_stream_t stream) {
+  DALM_REQUIRE(cu_seqlens, DALM_E_NULL, "null pointer argument");
+  const RelBias rb = {rel, rel_stride_h, rel_T, cols};
+  return dalm_attn_bwd_any(q, k, v, o, d_o, lse, bits_rows, bits_cols, live, cu_seqlens, B, H, H, T, hd, scale, strides, nullptr,
+                           nullptr, 0, 0, dropout_p, seed, salt, dq, dk, dv, delta, stream, GqaSplit{1, nullptr, 0}, false, &rb);
 }

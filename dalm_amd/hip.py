@@ -115,7 +115,15 @@ SIGNATURES = {
     "dalm_attn_fwd_packed": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _f32, _vp, C.c_uint32, _vp, _vp, _vp]),
     "dalm_attn_bwd_packed": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _i64,
                                     _f32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
-    "dalm_attn_gqa_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
+    "dalm_attn_rel_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp, _i64, _i64, _f32, _vp, C.c_uint32,
+                                 _vp, _vp, _vp]),
+    "dalm_attn_rel_fwd_packed": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp, _i64, _i64, _vp, _f32,
+                                        _vp, C.c_uint32, _vp, _vp, _vp]),
+    "dalm_attn_rel_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp, _i64, _i64,
+                                 _f32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "dalm_attn_rel_bwd_packed": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp,
+                                        _i64, _i64, _vp, _f32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "dalm_attn_gqa_fwd": (_int,[_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
     "dalm_attn_gqa_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _f32, _vp, _vp, _vp,
                                  _i64, _i64, _i64, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "dalm_attn_gqa_bwd_splits": (_i64, [_i64, _i64, _i64, _i64]),

@@ -24,6 +24,8 @@ Grouped-query heads (Llama-3 / Mistral / TinyLlama: k, v with Hkv < H heads) run
 summed over each group in f32 inside the kernel.  Elsewhere k / v are expanded by `repeat_kv` first.
 Qwen3 (q_norm / k_norm over the head dimension in front of the rotary embedding) runs norm + rotation + attention as one node,
 `norm_rope_sdpa`; a call that carries a `sliding_window` shorter than the sequence goes to transformers' own function.
+MPNet (a per-head relative-position bias by column difference on top of BERT's attention) runs on `dalm_attn_rel_*` with the bias
+as one [H, 2 Tc - 1] vector per forward: `rel_sdpa`, reached from fastpath's MPNetSelfAttention patch, not through "dalm_sdpa".
 Everything the kernels do not take (CPU tensors, other head widths, odd T with dropout, float masks, a KV cache, no gradient wanted) goes
 to transformers' own `sdpa_attention_forward`, unchanged.  DALM_ATTN_KERNEL=0 keeps the model on "sdpa".
 """
@@ -472,6 +474,226 @@ def dalm_sdpa_attention_forward(module, query, key, value, attention_mask, dropo
     salt = dropout_salt(module, "_dalm_attn_calls") if dropout > 0.0 else 0
     out = _SdpaHipBackward.apply(query, k2, v2, attention_mask, scale, causal, float(dropout), salt)
     return out.transpose(1, 2).contiguous(), None
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Relative-position bias (MPNet): score = scale q.k + rel[h][col(j) - col(i) + Tc - 1] on `dalm_attn_rel_*`
+# ---------------------------------------------------------------------------------------------------------------------------
+# MPNetEncoder.compute_position_bias builds relative_attention_bias(bucket(j - i))[h] from positions arange(T): it ignores
+# position_ids and padding, so the bias is a function of the head and the column difference only - a Toeplitz matrix per head.
+# One f32 vector [H, 2 Tc - 1] per forward (Tc = the padded column count) replaces the [B, H, T, T] tensor; the kernels index it.
+_bucket_index: dict = {}      # (encoder class, Tc, bucket count, device) -> int64 [2 Tc - 1]: bucket of every column difference
+
+
+def rel_bias_vector(encoder, Tc: int, device=None) -> torch.Tensor:
+    """[H, 2 Tc - 1] f32: entry [h, d + Tc - 1] = the bias of head h at column difference d = key column - query column, from the
+    encoder's OWN `relative_position_bucket` (the formula is not restated here) and its table as it is NOW (gathered on every
+    call; only the bucket index is cached per Tc)."""
+    import inspect
+
+    table = encoder.relative_attention_bias.weight
+    device = table.device if device is None else torch.device(device)
+    # the bucket count is compute_position_bias's default argument (the encoder calls it without one), not the table's row count
+    buckets = int(inspect.signature(type(encoder).compute_position_bias).parameters["num_buckets"].default)
+    key = (type(encoder), int(Tc), buckets, device)
+    idx = _bucket_index.get(key)
+    if idx is None:
+        d = torch.arange(-(Tc - 1), Tc, dtype=torch.long)
+        idx = type(encoder).relative_position_bucket(d, num_buckets=buckets).to(device)
+        _bucket_index[key] = idx
+    return table.detach().to(device=device, dtype=torch.float32).index_select(0, idx).t().contiguous()
+
+
+class RelBiasSource:
+    """What the routed `compute_position_bias` hands the layers in place of the [B, H, T, T] tensor: the encoder whose table holds
+    the bias, and the vectors built from it during THIS forward (every layer asks for the same Tc)."""
+
+    __slots__ = ("encoder", "_vec")
+
+    def __init__(self, encoder):
+        self.encoder, self._vec = encoder, {}
+
+    def vector(self, Tc: int, device) -> torch.Tensor:
+        key = (int(Tc), torch.device(device))
+        if key not in self._vec:
+            self._vec[key] = rel_bias_vector(self.encoder, Tc, device)
+        return self._vec[key]
+
+
+def tag_rel_bias(encoder) -> torch.Tensor:
+    """The tagged stand-in for MPNet's position bias: the [H, buckets] table view (small), carrying its `RelBiasSource`."""
+    t = encoder.relative_attention_bias.weight.detach().t()
+    t._dalm_rel = RelBiasSource(encoder)
+    return t
+
+
+def rel_source_of(position_bias) -> Optional[RelBiasSource]:
+    return getattr(position_bias, "_dalm_rel", None) if position_bias is not None else None
+
+
+def expand_rel_bias(rel: torch.Tensor, cols_q: torch.Tensor, cols_k: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rel [H, 2 Tc - 1] -> [..., H, Tq, Tk] with element rel[h, cols_k[j] - cols_q[i] + Tc - 1]; cols: int64 [..., T]."""
+    cols_k = cols_q if cols_k is None else cols_k
+    Tc = (rel.shape[1] + 1) // 2
+    idx = cols_k.unsqueeze(-2) - cols_q.unsqueeze(-1) + (Tc - 1)                       # [..., Tq, Tk]
+    return rel[:, idx].movedim(0, -3)
+
+
+def _bool_key_mask(mask: torch.Tensor) -> torch.Tensor:
+    """The boolean [B, 1, T, T] mask of an additive float mask (0 = attend), made ONCE per mask tensor: every layer of a forward
+    passes the same tensor object, and the mask-bits cache (`_pack`) is keyed by the object it is handed."""
+    if mask.dtype == torch.bool:
+        return mask
+    got = getattr(mask, "_dalm_bool", None)
+    if got is None or got[0] != mask._version:
+        got = (mask._version, mask == 0)
+        mask._dalm_bool = got
+    return got[1]
+
+
+def _rel_launch_forward(q, k, v, pk, scale, rel, cols, drop):
+    B, H, T, hd = q.shape
+    sq = pk.packed
+    nseq, Tm = (B, T) if sq is None else (sq.nseq, sq.T)
+    out = torch.empty(B, T, H, hd, dtype=q.dtype, device=q.device).transpose(1, 2)
+    lse = torch.empty(nseq, H, Tm, dtype=torch.float32, device=q.device)
+    flat = []
+    for t in (q, k, v, out):
+        flat += _strides3(t)
+    tail = (float(drop[0]), hip.ptr(drop[1]), int(drop[2]) & 0xFFFFFFFF, hip.ptr(out), hip.ptr(lse), hip.stream())
+    relargs = (hip.ptr(rel), rel.stride(0), (rel.shape[1] + 1) // 2)
+    if sq is None:
+        hip.call("dalm_attn_rel_fwd", hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(pk.rows), hip.ptr(pk.live), B, H, T, hd, float(scale),
+                 (C.c_int64 * 12)(*flat), *relargs, *tail)
+    else:
+        hip.call("dalm_attn_rel_fwd_packed", hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(pk.rows), hip.ptr(pk.live), hip.ptr(sq.cu),
+                 nseq, H, Tm, hd, float(scale), (C.c_int64 * 12)(*flat), *relargs, hip.ptr(cols), *tail)
+    return out, lse
+
+
+def _rel_launch_backward(q, k, v, out, lse, d_out, pk, scale, rel, cols, drop):
+    B, H, T, hd = q.shape
+    if d_out.stride(-1) != 1 or any(s % 8 for s in d_out.stride()[:3]):
+        d_out = d_out.contiguous()
+    sq = pk.packed
+    nseq, Tm = (B, T) if sq is None else (sq.nseq, sq.T)
+    dq, dk, dv = _dense_like(q), _dense_like(k), _dense_like(v)
+    delta = torch.empty(nseq, H, Tm, dtype=torch.float32, device=q.device)
+    flat = []
+    for t in (q, k, v, out, d_out, dq, dk, dv):
+        flat += _strides3(t)
+    head = (hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(out), hip.ptr(d_out), hip.ptr(lse), hip.ptr(pk.rows), hip.ptr(pk.cols),
+            hip.ptr(pk.live))
+    tail = (float(drop[0]), hip.ptr(drop[1]), int(drop[2]) & 0xFFFFFFFF, hip.ptr(dq), hip.ptr(dk), hip.ptr(dv), hip.ptr(delta),
+            hip.stream())
+    relargs = (hip.ptr(rel), rel.stride(0), (rel.shape[1] + 1) // 2)
+    if sq is None:
+        hip.call("dalm_attn_rel_bwd", *head, B, H, T, hd, float(scale), (C.c_int64 * 24)(*flat), *relargs, *tail)
+    else:
+        hip.call("dalm_attn_rel_bwd_packed", *head, hip.ptr(sq.cu), nseq, H, Tm, hd, float(scale), (C.c_int64 * 24)(*flat), *relargs,
+                 hip.ptr(cols), *tail)
+    return dq, dk, dv
+
+
+class _RelSdpaHip(torch.autograd.Function):
+    """The attention with a relative-position bias vector on `dalm_attn_rel_*` (padded, or - `mask` a packed descriptor - packed).
+    Shares the mask-bits cache (`_pack`) and the dropout salt counter with `_SdpaHipBackward`.  The bias is a constant of the step
+    (a frozen table): the backward reads it to recompute P and returns no gradient for it."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, rel, mask, scale, dropout_p=0.0, salt=0, cols=None):
+        B, H, T, hd = q.shape
+        pk = _pack(mask, B, H, T, False, q.dtype, q.device)
+        drop = (0.0, None, 0)
+        if dropout_p > 0.0:
+            from . import lora_ops
+
+            drop = (float(dropout_p), lora_ops.dropout_seed_snapshot(q.device), int(salt))
+        out, lse = _rel_launch_forward(q, k, v, pk, scale, rel, cols, drop)
+        ctx.save_for_backward(q, k, v, out, lse, rel, *([cols] if cols is not None else []))
+        ctx.pack, ctx.scale, ctx.drop = pk, scale, drop
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        q, k, v, out, lse, rel, *cols = ctx.saved_tensors
+        dq, dk, dv = _rel_launch_backward(q, k, v, out, lse, d_out, ctx.pack, ctx.scale, rel, cols[0] if cols else None, ctx.drop)
+        return dq, dk, dv, None, None, None, None, None, None
+
+
+def rel_supported(query, key, value, rel, mask, dropout: float) -> bool:
+    """What `dalm_attn_rel_*` take: bf16 GPU [B, H, T, 64] views with 16-byte rows, equal heads, 1 <= T <= 2048, an f32 vector
+    with Tc >= T, no mask / a boolean [B, 1, T, T] mask / a packed descriptor, dropout only with an even T."""
+    if _off("DALM_ATTN_KERNEL"):
+        return False
+    if not (query.is_cuda and query.dtype == torch.bfloat16 and key.dtype == query.dtype and value.dtype == query.dtype):
+        return False
+    if query.dim() != 4 or query.shape[-1] != 64 or key.shape != query.shape or value.shape != query.shape:
+        return False
+    seqs = packed_of(mask)
+    B, _, T, _ = query.shape
+    Tm = T if seqs is None else seqs.T
+    if not (rel.is_cuda and rel.dtype == torch.float32 and rel.dim() == 2 and rel.shape[0] == query.shape[1] and rel.stride(1) == 1
+            and Tm <= (rel.shape[1] + 1) // 2 <= 2048 and Tm >= 1):
+        return False
+    if dropout != 0.0 and not (0.0 < dropout < 1.0 and Tm % 2 == 0):
+        return False
+    if seqs is None and mask is not None and not (mask.dtype == torch.bool and tuple(mask.shape) == (B, 1, T, T) and mask.is_cuda):
+        return False
+    if seqs is not None and query.shape[0] != 1:
+        return False
+    return _views_ok(query, key, value)
+
+
+def _rel_sdpa_torch(query, key, value, rel, mask, seqs, scale: float, dropout: float):
+    """The same attention without the kernels (CPU tensors, fp32, what `rel_supported` declines): torch's SDPA with the bias
+    expanded into a float mask - per sequence for a packed call, at the tokens' original column differences."""
+    H = query.shape[1]
+    neg = torch.finfo(torch.float32).min
+    if seqs is None:
+        B, _, T, _ = query.shape
+        bias = expand_rel_bias(rel, torch.arange(T, device=query.device))[None]                    # [1, H, T, T]
+        if mask is not None:
+            bias = bias + (torch.zeros_like(mask, dtype=torch.float32).masked_fill(~mask, neg) if mask.dtype == torch.bool else mask)
+        return torch.nn.functional.scaled_dot_product_attention(query, key, value, attn_mask=bias.to(query.dtype), dropout_p=dropout,
+                                                                scale=scale)
+    _, _, n, hd = query.shape
+    slot, gather = seqs.padded_index()
+    nseq, T = seqs.nseq, seqs.T
+
+    def pad(t):                                                   # [1, H, n, hd] -> [nseq, H, T, hd]
+        rows = torch.cat((t[0].transpose(0, 1), t.new_zeros((1, H, hd))), dim=0)
+        return rows.index_select(0, gather).view(nseq, T, H, hd).transpose(1, 2)
+
+    cols = seqs.cols.to(torch.int64) if seqs.cols is not None else (torch.arange(n, device=query.device) - seqs.cu.to(torch.int64)[
+        torch.bucketize(torch.arange(n, device=query.device), seqs.cu[1:].to(torch.int64), right=True).clamp_max(nseq - 1)])
+    cpad = torch.cat((cols, cols.new_zeros((1,)))).index_select(0, gather).view(nseq, T)
+    kl = torch.cat((seqs.key_live != 0, seqs.key_live.new_zeros((1,), dtype=torch.bool))).index_select(0, gather).view(nseq, 1, 1, T)
+    live = kl.expand(nseq, 1, T, T)
+    has_key = live.any(dim=-1, keepdim=True)
+    live = live | (~has_key & torch.eye(T, dtype=torch.bool, device=query.device))
+    bias = expand_rel_bias(rel, cpad).masked_fill(~live, neg)                                      # [nseq, H, T, T]
+    out = torch.nn.functional.scaled_dot_product_attention(pad(query), pad(key), pad(value), attn_mask=bias.to(query.dtype),
+                                                           dropout_p=dropout, scale=scale)
+    out = torch.where(has_key, out, torch.zeros_like(out))
+    return out.transpose(1, 2).reshape(nseq * T, H, hd).index_select(0, slot).unsqueeze(0).transpose(1, 2)   # [1, H, n, hd]
+
+
+def rel_sdpa(module, query, key, value, source: RelBiasSource, mask, dropout: float = 0.0):
+    """softmax(q k^T / sqrt(hd) + bias + mask) v for [B, H, T, hd] q / k / v with MPNet's relative-position bias: on the kernels
+    where `rel_supported` holds, through torch's SDPA with a float mask elsewhere.  `mask`: None, transformers' additive float
+    mask or a boolean mask [B, 1, T, T], or a packed descriptor.  Returns [B, H, T, hd]."""
+    seqs = packed_of(mask)
+    Tc = query.shape[2] if seqs is None else seqs.T
+    rel = source.vector(Tc, query.device)
+    scale = float(query.shape[-1]) ** -0.5
+    if seqs is None and mask is not None:
+        mask = _bool_key_mask(mask)
+    if rel_supported(query, key, value, rel, mask, dropout):
+        salt = dropout_salt(module, "_dalm_attn_calls") if dropout > 0.0 else 0
+        cols = None if seqs is None else seqs.cols
+        return _RelSdpaHip.apply(query, key, value, rel, mask, scale, float(dropout), salt, cols)
+    return _rel_sdpa_torch(query, key, value, rel, mask, seqs, scale, float(dropout))
 
 
 _registered = [False]

@@ -532,17 +532,23 @@ def _bert_output_forward(self, hidden_states: torch.Tensor, input_tensor: torch.
 # BertSelfOutput / BertOutput and the classes of the RoBERTa family whose forward is the same three statements (xlm-roberta-xl's
 # `XLMRobertaXL*` classes are other code - no LayerNorm in the self-output - and are not named)
 _BERT_OUTPUT_CLASSES = tuple(f"{family}{kind}" for family in ("Bert", "Roberta", "XLMRoberta", "Camembert")
-                             for kind in ("SelfOutput", "Output"))
+                             for kind in ("SelfOutput", "Output")) + ("MPNetOutput",)      # MPNetOutput: "Copied from" BertOutput
 
 
 def use_bert_layer_kernels(model: torch.nn.Module) -> int:
-    """Patch {Bert,Roberta,XLMRoberta,Camembert}{SelfOutput,Output} modules whose forward is the three statements above (source
-    checked once per class) and whose LayerNorm is frozen.  Returns how many modules were patched."""
+    """Patch {Bert,Roberta,XLMRoberta,Camembert}{SelfOutput,Output} and MPNetOutput modules whose forward is the three statements
+    above (source checked once per class), and MPNetAttention modules (`_mpnet_attention_forward`: the same dropout + add +
+    LayerNorm behind the self-attention).  The kernel runs where the LayerNorm is frozen.  Returns how many modules were patched."""
     def dense_dropout_norm(mod) -> bool:
         return (isinstance(getattr(mod, "LayerNorm", None), torch.nn.LayerNorm)
                 and isinstance(getattr(mod, "dropout", None), torch.nn.Dropout) and hasattr(mod, "dense"))
 
-    return _install(model, _BERT_OUTPUT_CLASSES, dense_dropout_norm, "bert-output", _bert_output_forward)
+    def dropout_norm(mod) -> bool:                # MPNetAttention: the same statement without a dense of its own
+        return (isinstance(getattr(mod, "LayerNorm", None), torch.nn.LayerNorm)
+                and isinstance(getattr(mod, "dropout", None), torch.nn.Dropout) and hasattr(mod, "attn"))
+
+    return (_install(model, _BERT_OUTPUT_CLASSES, dense_dropout_norm, "bert-output", _bert_output_forward)
+            + _install(model, ("MPNetAttention",), dropout_norm, "mpnet-attn", _mpnet_attention_forward))
 
 
 _SOURCE_GUARDS["bert-output"] = (
@@ -741,6 +747,155 @@ _SOURCE_GUARDS["falcon-attn"] = (_restates(
     "attn_output = attn_output.permute(0, 2, 1, 3)",
     "attn_output = self.dense(attn_output)",
     "return attn_output, attention_scores"), _RESTATED)
+
+
+# ---------------------------------------------------------------------------
+# MPNet (all-mpnet-base-v2, multi-qa-mpnet-*, paraphrase-mpnet-*): the self-attention on dalm_attn_rel_* with the relative-position
+# bias as ONE small vector per forward, and MPNetAttention's dropout + add + LayerNorm on BERT's kernel
+# ---------------------------------------------------------------------------
+_MPNET_ATTN_PARAMS = ["self", "hidden_states", "attention_mask", "position_bias", "output_attentions", "kwargs"]
+
+
+def _mpnet_self_attention_forward(self, hidden_states, attention_mask=None, position_bias=None, output_attentions=False, **kwargs):
+    """transformers' MPNetSelfAttention.forward: the q / k / v projections, softmax(q k^T / sqrt(hd) + position_bias +
+    attention_mask), dropout, the product with v, `o` - with everything between the projections and `o` as `attention.rel_sdpa`
+    when `position_bias` is the routed encoder's tagged stand-in.  A real bias tensor (an unrouted encoder, explicit position ids)
+    or `output_attentions` runs transformers' own forward."""
+    from . import attention
+
+    source = attention.rel_source_of(position_bias)
+    if source is None or output_attentions:
+        if source is not None:
+            if attention.packed_of(attention_mask) is not None:
+                raise ValueError("dalm_amd: a packed MPNet call returns no attention probabilities (output_attentions)")
+            _warn_once("mpnet-output-attentions", "MPNet with output_attentions runs transformers' eager attention")
+            position_bias = source.encoder._dalm_orig_compute_position_bias(hidden_states)
+        return self._dalm_orig_attn_forward(hidden_states, attention_mask, position_bias, output_attentions=output_attentions, **kwargs)
+    input_shape = hidden_states.shape[:-1]
+    hidden_shape = (*input_shape, -1, self.attention_head_size)
+    q = self.q(hidden_states).view(hidden_shape).transpose(1, 2)
+    k = self.k(hidden_states).view(hidden_shape).transpose(1, 2)
+    v = self.v(hidden_states).view(hidden_shape).transpose(1, 2)
+    p = float(self.dropout.p) if self.training else 0.0
+    c = attention.rel_sdpa(self, q, k, v, source, attention_mask, p)                       # [B, H, T, hd]
+    c = c.permute(0, 2, 1, 3).contiguous()
+    new_c_shape = c.size()[:-2] + (self.all_head_size,)
+    c = c.view(*new_c_shape)
+    o = self.o(c)
+    return (o,)
+
+
+_SOURCE_GUARDS["mpnet-self-attn"] = (_restates(
+    _MPNET_ATTN_PARAMS,
+    "hidden_shape = (*input_shape, -1, self.attention_head_size)",
+    "q = self.q(hidden_states).view(hidden_shape).transpose(1, 2)",
+    "k = self.k(hidden_states).view(hidden_shape).transpose(1, 2)",
+    "v = self.v(hidden_states).view(hidden_shape).transpose(1, 2)",
+    "attention_scores = torch.matmul(q, k.transpose(-1, -2))",
+    "attention_scores = attention_scores / math.sqrt(self.attention_head_size)",
+    "attention_scores += position_bias",
+    "attention_scores = attention_scores + attention_mask",
+    "attention_probs = nn.functional.softmax(attention_scores, dim=-1)",
+    "attention_probs = self.dropout(attention_probs)",
+    "c = torch.matmul(attention_probs, v)",
+    "c = c.permute(0, 2, 1, 3).contiguous()",
+    "o = self.o(c)",
+    "outputs = (o, attention_probs) if output_attentions else (o,)"), _RESTATED)
+
+
+def _mpnet_compute_position_bias(self, x, position_ids=None, num_buckets=32):
+    """transformers' MPNetEncoder.compute_position_bias for the call the encoder makes (`compute_position_bias(hidden_states)`:
+    positions arange(T), so the bias depends on the head and the column difference only): returns the tagged stand-in
+    (`attention.tag_rel_bias`) from which the routed self-attention modules build ONE [H, 2 Tc - 1] vector per forward - no
+    [B, H, T, T] tensor.  Explicit `position_ids`, another bucket count or a table that has become trainable: the class's code."""
+    from . import attention
+
+    if position_ids is not None or num_buckets != 32 or self.relative_attention_bias.weight.requires_grad:
+        _warn_once("mpnet-bias-declined", "MPNet position bias from position_ids / a trainable table: transformers' own code")
+        return self._dalm_orig_compute_position_bias(x, position_ids, num_buckets)
+    return attention.tag_rel_bias(self)
+
+
+def _mpnet_bias_matches(cls) -> bool:
+    """The class's compute_position_bias / relative_position_bucket ARE what `_mpnet_compute_position_bias` and
+    `attention.rel_bias_vector` stand for: positions arange(T) unless ids are given, key column - query column, the class's bucket
+    function with `num_buckets`, one table row per bucket, [B, H, T, T]."""
+    import inspect
+
+    src = inspect.getsource(cls.compute_position_bias)
+    params = list(inspect.signature(cls.compute_position_bias).parameters)
+    dflt = inspect.signature(cls.compute_position_bias).parameters["num_buckets"].default
+    return (params == ["self", "x", "position_ids", "num_buckets"] and dflt == 32
+            and isinstance(inspect.getattr_static(cls, "relative_position_bucket"), staticmethod)
+            and list(inspect.signature(cls.relative_position_bucket).parameters) == ["relative_position", "num_buckets", "max_distance"]
+            and all(s in src for s in (
+                "context_position = torch.arange(qlen, dtype=torch.long)[:, None]",
+                "memory_position = torch.arange(klen, dtype=torch.long)[None, :]",
+                "relative_position = memory_position - context_position",
+                "rp_bucket = self.relative_position_bucket(relative_position, num_buckets=num_buckets)",
+                "values = self.relative_attention_bias(rp_bucket)",
+                "values = values.permute([2, 0, 1]).unsqueeze(0)",
+                "values = values.expand((bsz, -1, qlen, klen)).contiguous()")))
+
+
+def use_mpnet_attention_kernels(model: torch.nn.Module) -> int:
+    """Route MPNet encoders: every MPNetSelfAttention module (head width 64, forward = the code `_mpnet_self_attention_forward`
+    restates) and the encoder's compute_position_bias (source checked, table frozen) - all of an encoder or nothing, because the
+    routed modules exchange a stand-in for the bias that transformers' own forward cannot read.  The model stays on "eager";
+    `packed.attention_is_packable` recognises the routed modules.  DALM_ATTN_KERNEL=0 disables.  Returns the number of modules
+    patched (self-attention modules + encoders)."""
+    if _off("DALM_ATTN_KERNEL"):
+        return 0
+    n = 0
+    for enc in [m for m in model.modules() if type(m).__name__ == "MPNetEncoder"]:
+        cls = type(enc)
+        table = getattr(enc, "relative_attention_bias", None)
+        att = [m for m in enc.modules() if "MPNetSelfAttention" in [c.__name__ for c in type(m).__mro__]]
+        if not isinstance(table, torch.nn.Embedding) or not att:
+            continue
+        if table.weight.requires_grad:
+            _warn_once("mpnet-trainable-table", "MPNet's relative_attention_bias table is trainable: transformers' own attention stays")
+            continue
+        if any(getattr(m, "attention_head_size", None) != 64 for m in att):
+            _warn_once("mpnet-head-width", "MPNet head width is not 64: transformers' own attention stays")
+            continue
+        if not _guard(("mpnet-bias", cls), cls.__name__ + ".compute_position_bias", _RESTATED, lambda: _mpnet_bias_matches(cls)):
+            continue
+        if not all(_matches("mpnet-self-attn", type(m)) for m in att):
+            continue
+        for m in att:
+            m._dalm_orig_attn_forward = m.forward
+            m.forward = types.MethodType(_mpnet_self_attention_forward, m)
+        enc._dalm_orig_compute_position_bias = enc.compute_position_bias
+        enc.compute_position_bias = types.MethodType(_mpnet_compute_position_bias, enc)
+        n += len(att) + 1
+    return n
+
+
+def _mpnet_attention_forward(self, hidden_states, attention_mask=None, position_bias=None, output_attentions=False, **kwargs):
+    """transformers' MPNetAttention.forward:
+        self_outputs = self.attn(hidden_states, attention_mask, position_bias, output_attentions=output_attentions)
+        attention_output = self.LayerNorm(self.dropout(self_outputs[0]) + hidden_states)
+    with the second statement on `dalm_bert_add_norm_{fwd,bwd}` where `bert_ops.supported` holds (as `_bert_output_forward`)."""
+    from . import bert_ops
+    from .lora import dropout_salt
+
+    self_outputs = self.attn(hidden_states, attention_mask, position_bias, output_attentions=output_attentions)
+    if bert_ops.supported(self_outputs[0], hidden_states, self.LayerNorm):
+        p = float(self.dropout.p) if self.training else 0.0
+        attention_output = bert_ops.add_norm(self_outputs[0], hidden_states, self.LayerNorm, p, dropout_salt(self, "_dalm_calls"))
+    else:
+        attention_output = self.LayerNorm(self.dropout(self_outputs[0]) + hidden_states)
+    outputs = (attention_output,) + self_outputs[1:]
+    return outputs
+
+
+_SOURCE_GUARDS["mpnet-attn"] = (
+    lambda params, src: (params == _MPNET_ATTN_PARAMS and _body(src)[-9:] == [
+        "self_outputs = self.attn(", "hidden_states,", "attention_mask,", "position_bias,", "output_attentions=output_attentions,", ")",
+        "attention_output = self.LayerNorm(self.dropout(self_outputs[0]) + hidden_states)",
+        "outputs = (attention_output,) + self_outputs[1:]  # add attentions if we output them", "return outputs"]
+                         and src.count("self.") == 3), _RESTATED)
 
 
 # ---------------------------------------------------------------------------

@@ -263,7 +263,9 @@ def _matches(name: str, targets: Iterable[str]) -> bool:
 
 # peft's own per-architecture defaults for models without q_proj / v_proj (TRANSFORMERS_MODELS_TO_LORA_TARGET_MODULES_MAPPING)
 FUSED_QKV_FALLBACK = {"falcon": ["query_key_value"], "gpt_neox": ["query_key_value"], "bloom": ["query_key_value"],
-                      "gpt2": ["c_attn"], "mpt": ["Wqkv"]}
+                      "gpt2": ["c_attn"], "mpt": ["Wqkv"],
+                      # MPNet names its projections q / k / v: the retriever targets key / query / value find nothing there
+                      "mpnet": ["q", "k", "v"]}
 
 
 def resolve_targets(model: nn.Module, target_modules: List[str]) -> List[str]:

@@ -17,7 +17,8 @@ from . import lora
 from .attention import use_hip_attention_backward
 from .fastpath import (use_bert_layer_kernels, use_capturable_falcon_heads, use_falcon_attention_kernels, use_falcon_layer_kernels,
                        use_fused_residual_norm, use_geglu_kernel, use_gemma_rms_norm, use_llama_attention_node, use_native_rms_norm,
-                       use_qwen3_attention_node, use_relu2_kernel, use_roberta_embeddings, use_roll_rope, use_swiglu_kernel)
+                       use_mpnet_attention_kernels, use_qwen3_attention_node, use_relu2_kernel, use_roberta_embeddings, use_roll_rope,
+                       use_swiglu_kernel)
 
 
 class Mode(Enum):
@@ -184,6 +185,8 @@ class AutoModelForRagE2E(torch.nn.Module):
         use_transposed_dgrad(self.generator_model)
         use_transposed_dgrad(self.retriever_model)
         use_bert_layer_kernels(self.retriever_model)              # dropout + add + LayerNorm of a BERT layer: one launch each way
+        if not autoregressive:
+            use_mpnet_attention_kernels(self.retriever_model)     # MPNet: attention with the relative-position bias (frozen table)
         use_roberta_embeddings(self.retriever_model)              # RoBERTa family: ids -> first layer input in one launch
 
     # ---- retrieval tower ---------------------------------------------------------------

@@ -52,11 +52,13 @@ class AutoModelForSentenceEmbedding(torch.nn.Module):
             lora.inject_lora(self.model, ["key", "query", "value"] if not is_autoregressive else ["q_proj", "v_proj"])
         # frozen projections: backward GEMM through a transposed weight copy; BERT layers: dropout + add + LayerNorm in one launch
         # each way (both no-ops for a model that is fine-tuned in full: they look at requires_grad)
-        from .fastpath import use_bert_layer_kernels, use_roberta_embeddings
+        from .fastpath import use_bert_layer_kernels, use_mpnet_attention_kernels, use_roberta_embeddings
         from .frozen_linear import use_transposed_dgrad
 
         use_transposed_dgrad(self.model)
         use_bert_layer_kernels(self.model)
+        if not is_autoregressive:
+            use_mpnet_attention_kernels(self.model)   # MPNet: attention with the relative-position bias (frozen table only)
         use_roberta_embeddings(self.model)            # RoBERTa family: positions + tables + LayerNorm + dropout in one launch
         self.normalize = normalize
         self.is_autoregressive = is_autoregressive

@@ -99,6 +99,8 @@ class PackedSeqs:
     cols_bits: Optional[torch.Tensor] = None
     live_tiles: Optional[torch.Tensor] = None
     stream: int = 0
+    cols: Optional[torch.Tensor] = None    # int32 [n]: every row's ORIGINAL column, for a model whose attention adds a bias by
+                                           # column difference (MPNet, models/attention.py `rel_sdpa`); None for every other model
     _pad: dict = field(default_factory=dict)
 
     def bits(self):
@@ -141,15 +143,22 @@ def packed_of(mask) -> Optional[PackedSeqs]:
 
 
 # model types whose embeddings number positions from the DATA (transformers' create_position_ids_from_input_ids), not by column
-POSITIONS_FROM_IDS = ("roberta", "xlm-roberta", "camembert")
+POSITIONS_FROM_IDS = ("roberta", "xlm-roberta", "camembert", "mpnet")
+# MPNetEmbeddings hard-codes `self.padding_idx = 1` for its position rule - not config.pad_token_id
+_FIXED_PADDING_IDX = {"mpnet": 1}
+# model types whose attention adds a bias that depends on the column difference: the descriptor carries the rows' columns
+COLUMNS_IN_DESCRIPTOR = ("mpnet",)
 
 
 def position_padding_idx(model) -> Optional[int]:
-    """The `padding_idx` of a model of the RoBERTa family (its config's pad_token_id), None for every other model: BERT and the
-    decoders number positions by column."""
+    """The `padding_idx` of a model of the RoBERTa family (its config's pad_token_id) or of MPNet (1, whatever the config
+    says), None for every other model: BERT and the decoders number positions by column."""
     cfg = getattr(model, "config", None)
-    if getattr(cfg, "model_type", None) not in POSITIONS_FROM_IDS:
+    kind = getattr(cfg, "model_type", None)
+    if kind not in POSITIONS_FROM_IDS:
         return None
+    if kind in _FIXED_PADDING_IDX:
+        return _FIXED_PADDING_IDX[kind]
     return int(cfg.pad_token_id)
 
 
@@ -183,6 +192,8 @@ def packed_inputs(input_ids: torch.Tensor, attention_mask: torch.Tensor, rows: t
     pos = packed_positions(input_ids, rows, position_padding_idx(model))
     key_live = ((attention_mask.reshape(-1).index_select(0, r) != 0) & valid).to(torch.uint8)
     seqs = PackedSeqs(cu=cu.to(torch.int32), nseq=int(cu.numel()) - 1, T=int(T), n=int(rows.numel()), key_live=key_live, causal=causal)
+    if getattr(getattr(model, "config", None), "model_type", None) in COLUMNS_IN_DESCRIPTOR:
+        seqs.cols = packed_positions(input_ids, rows, None).to(torch.int32)
     desc = attach(torch.ones((1, 1, 1, 1), dtype=torch.bool, device=input_ids.device), seqs)
     return ids_p.unsqueeze(0), pos.unsqueeze(0), desc, valid
 
@@ -212,8 +223,17 @@ def attention_is_packable(model) -> bool:
         return True
     # Falcon (7B flavour) stays on "sdpa": its attention modules are patched one by one (fastpath.use_falcon_attention_kernels),
     # and the patched forward is the one that reads the descriptor
-    att = [m for m in model.modules() if type(m).__name__ == "FalconAttention"]
-    return bool(att) and all(getattr(getattr(m.forward, "__func__", None), "__name__", "") == "_falcon_attention_forward" for m in att)
+    # MPNet stays on "eager" in the same way (fastpath.use_mpnet_attention_kernels): every self-attention module AND the encoder's
+    # compute_position_bias must be the routed ones
+    for cls_name, fn_name in (("FalconAttention", "_falcon_attention_forward"), ("MPNetSelfAttention", "_mpnet_self_attention_forward")):
+        att = [m for m in model.modules() if type(m).__name__ == cls_name]
+        if att and all(getattr(getattr(m.forward, "__func__", None), "__name__", "") == fn_name for m in att):
+            if cls_name == "FalconAttention":
+                return True
+            enc = [m for m in model.modules() if type(m).__name__ == "MPNetEncoder"]
+            return bool(enc) and all(getattr(getattr(m.compute_position_bias, "__func__", None), "__name__", "")
+                                     == "_mpnet_compute_position_bias" for m in enc)
+    return False
 
 
 def generator_hidden(generator_model, input_ids, attention_mask, rows, cu):
@@ -251,6 +271,8 @@ def retrieval_hidden_pair(retriever_model, first, second):
     cu_all = torch.cat([parts[0][2].cu] + [(p[2].cu[1:] + p[6]) for p in parts[1:]])
     seqs = PackedSeqs(cu=cu_all.to(torch.int32), nseq=int(cu_all.numel()) - 1, T=int(T), n=off,
                       key_live=torch.cat([p[2].key_live for p in parts]), causal=False)
+    if all(p[2].cols is not None for p in parts):
+        seqs.cols = torch.cat([p[2].cols for p in parts])
     desc = attach(torch.ones((1, 1, 1, 1), dtype=torch.bool, device=cu_all.device), seqs)
     h = retriever_model(input_ids=torch.cat([p[0] for p in parts], dim=1), attention_mask=desc,
                         position_ids=torch.cat([p[1] for p in parts], dim=1))[0][0]                  # [n_first + n_second, D]

@@ -706,6 +706,35 @@ int dalm_attn_bwd_packed(const void* q, const void* k, const void* v, const void
                          const void* sin, int64_t cs_stride_t, float dropout_p, const void* seed, uint32_t salt, void* dq, void* dk,
                          void* dv, float* delta, dalm_stream_t stream);
 
+/* RELATIVE-POSITION BIAS forms (MPNet retrievers): dalm_attn_fwd / dalm_attn_bwd and their packed forms with a per-head additive
+ * score term that depends on the COLUMN DIFFERENCE of key and query only (a Toeplitz matrix per head):
+ *   score(i, j) of head h = scale q_i . k_j + rel[h * rel_stride_h + col(j) - col(i) + rel_T - 1]
+ * rel: f32, 2 rel_T - 1 entries per head in natural (not log2) units, entry rel_T - 1 = difference 0; T <= rel_T <= 2048.
+ * col(x): the row index within the sequence; in the packed forms cols[token] (int32 [n_tokens], each in [0, rel_T): the token's
+ * original column, so that a mask with holes keeps its differences) - cols NULL: the local row index.  The bias stays f32, is added
+ * inside the fma that forms the score, changes no tile's liveness, and gets no gradient (a frozen table); the backward recomputes
+ * P = exp(scale S + bias - lse).  With rel all zero the outputs are the bias-free entry points' bits.
+ * hd = 64 only (DALM_E_SHAPE "head width ..." otherwise), equal heads, no rotary epilogue; rel NULL -> DALM_E_NULL; rel_T < T or
+ * rel_stride_h < 2 rel_T - 1 -> DALM_E_SHAPE; rel (or cols) not 4-byte aligned -> DALM_E_ALIGN; every other rule as above.  The
+ * DALM_ATTN_FWD / DALM_ATTN_DKDV switches select nothing here. */
+int dalm_attn_rel_fwd(const void* q, const void* k, const void* v, const uint32_t* bits_rows, const uint8_t* live, int64_t B, int64_t H,
+                      int64_t T, int64_t hd, float scale, const int64_t* strides, const float* rel, int64_t rel_stride_h, int64_t rel_T,
+                      float dropout_p, const void* seed, uint32_t salt, void* o, float* lse, dalm_stream_t stream);
+int dalm_attn_rel_fwd_packed(const void* q, const void* k, const void* v, const uint32_t* bits_rows, const uint8_t* live,
+                             const int32_t* cu_seqlens, int64_t B, int64_t H, int64_t T, int64_t hd, float scale,
+                             const int64_t* strides, const float* rel, int64_t rel_stride_h, int64_t rel_T, const int32_t* cols,
+                             float dropout_p, const void* seed, uint32_t salt, void* o, float* lse, dalm_stream_t stream);
+int dalm_attn_rel_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
+                      const uint32_t* bits_rows, const uint32_t* bits_cols, const uint8_t* live, int64_t B, int64_t H, int64_t T,
+                      int64_t hd, float scale, const int64_t* strides, const float* rel, int64_t rel_stride_h, int64_t rel_T,
+                      float dropout_p, const void* seed, uint32_t salt, void* dq, void* dk, void* dv, float* delta,
+                      dalm_stream_t stream);
+int dalm_attn_rel_bwd_packed(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
+                             const uint32_t* bits_rows, const uint32_t* bits_cols, const uint8_t* live, const int32_t* cu_seqlens,
+                             int64_t B, int64_t H, int64_t T, int64_t hd, float scale, const int64_t* strides, const float* rel,
+                             int64_t rel_stride_h, int64_t rel_T, const int32_t* cols, float dropout_p, const void* seed,
+                             uint32_t salt, void* dq, void* dk, void* dv, float* delta, dalm_stream_t stream);
+
 /* GROUPED-QUERY forms (Llama-3 / Mistral / TinyLlama class generators: num_key_value_heads < num_attention_heads): q, o, d_o, dq
  * have H heads, k, v, dk, dv have Hkv heads (their head strides are strides over KV heads), H a multiple of Hkv.  Query head h reads
  * KV head h / (H / Hkv) - the order of transformers' repeat_kv: KV head j serves query heads j G .. j G + G - 1, G = H / Hkv.

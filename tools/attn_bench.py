@@ -9,7 +9,12 @@ left padding) and packed layouts, alternated in one process.  -> stdout (profile
 --dropout p): `dalm_attn_fwd` / `dalm_attn_bwd` against torch's SDPA on the same tensors and mask (what a model on "sdpa" runs),
 and the packed forms (`dalm_attn_*_packed` on the live rows) against `_packed_sdpa_torch` (re-pad, torch's SDPA, gather).  The two
 paths alternate --rounds times in one process; every figure is the median over rounds x 20 separately timed hipGraph replays
-(HIP events, --iters calls per graph, after warm-up replays).  -> stdout (profiles/attn_hd32_bench.txt, with --hd 32)"""
+(HIP events, --iters calls per graph, after warm-up replays).  -> stdout (profiles/attn_hd32_bench.txt, with --hd 32)
+
+--encoder --hd 64 --rel-bias (an MPNet layer: a per-head relative-position bias by column difference): the bias kernels
+(`dalm_attn_rel_*`) beside the bias-free kernels on the same tensors (their ratio is the cost of the bias), beside torch's SDPA
+with bias + key mask as a float mask, beside the eager MPNet chain (matmul, scale, += bias, + mask, softmax, dropout, matmul;
+padded layout only); all paths alternate in one process.  -> stdout (profiles/attn_rel_bench.txt)"""
 import argparse
 import sys
 from pathlib import Path
@@ -31,6 +36,7 @@ ap.add_argument("--rounds", type=int, default=3, help="--kv-heads: alternations 
 ap.add_argument("--encoder", action="store_true", help="encoder layer: bidirectional right-padding mask, padded and packed forms")
 ap.add_argument("--len-range", default="", help="--encoder: LO,HI - sequence lengths uniform in [LO, HI] (default T/2,T)")
 ap.add_argument("--dropout", type=float, default=0.0, help="--encoder: attention dropout probability (in-kernel / torch's own)")
+ap.add_argument("--rel-bias", action="store_true", help="--encoder --hd 64: dalm_attn_rel_* beside the bias-free kernels, torch, eager")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 B, H, T, hd = a.B, a.H, a.T, a.hd
@@ -216,6 +222,43 @@ def encoder_bench():
         "packed": (pk_qkv, pk_go, {"kernels": lambda x, y, z: attention.sdpa(x, y, z, desc, scale, False, p, 7),
                                    "torch": lambda x, y, z: attention._packed_sdpa_torch(x, y, z, seqs, scale, p).transpose(1, 2)}),
     }
+    if a.rel_bias:
+        assert hd == 64, "--rel-bias: head width 64"
+        rel = (torch.randn(H, 2 * T - 1, generator=g) * 0.5).to(dev)
+        cols = packed.packed_positions(torch.zeros(B, T, dtype=torch.long, device=dev), rows.to(dev), None).to(torch.int32)
+        fm = (attention.expand_rel_bias(rel, torch.arange(T, device=dev))[None]
+              + torch.zeros(B, 1, T, T, device=dev).masked_fill(~m4, torch.finfo(torch.float32).min)).to(torch.bfloat16)
+
+        def eager(x, y, z):
+            s = torch.matmul(x, y.transpose(-1, -2)) / (hd ** 0.5)
+            s += fm
+            return torch.matmul(F.dropout(F.softmax(s, dim=-1), p), z)
+
+        assert attention.rel_supported(q, k, v, rel, m4, p) and attention.rel_supported(*pk_qkv, rel, desc, p)
+        paths["padded"][2].update({
+            "rel": lambda x, y, z: attention._RelSdpaHip.apply(x, y, z, rel, m4, scale, p, 7),
+            "torch": lambda x, y, z: F.scaled_dot_product_attention(x, y, z, attn_mask=fm, dropout_p=p, scale=scale),
+            "eager": eager})
+        paths["packed"][2].update({
+            "rel": lambda x, y, z: attention._RelSdpaHip.apply(x, y, z, rel, desc, scale, p, 7, cols),
+            "torch": lambda x, y, z: attention._rel_sdpa_torch(x, y, z, rel, None, seqs, scale, p)})
+        print(f"# relative-position bias: B {B} H {H} T {T} hd {hd} dropout {p}; lengths U[{lo}, {hi}]: {int(ln.sum())} live tokens of "
+              f"{B * T}, {n} packed rows; median of {a.rounds} x 20 hipGraph replays ({a.iters} calls each) in us per call; "
+              "rel = dalm_attn_rel_*, kernels = the bias-free dalm_attn_* on the same tensors, torch = SDPA with bias + mask as a float "
+              "mask, eager = MPNet's statement chain")
+        for layout, (qkv, d_out, fns) in paths.items():
+            t = {(w, pas): [] for w in fns for pas in ("fwd", "bwd")}
+            for _ in range(a.rounds):
+                for pas in ("fwd", "bwd"):
+                    for w, fn in fns.items():                                        # all paths alternate
+                        t[(w, pas)] += replay_samples(fn, qkv, d_out, pas == "bwd")
+            med = {key: sorted(x)[len(x) // 2] for key, x in t.items()}
+            tot = {w: med[(w, "fwd")] + med[(w, "bwd")] for w in fns}
+            print(f"rel-bias B {B:3d} T {T:3d} p {p:.1f} {layout:6s}  "
+                  + "  ".join(f"{w} fwd {med[(w, 'fwd')]:6.1f} bwd {med[(w, 'bwd')]:6.1f} sum {tot[w]:6.1f}" for w in fns)
+                  + f"  |  rel / kernels {tot['rel'] / tot['kernels']:.3f}  torch / rel {tot['torch'] / tot['rel']:.2f}x"
+                  + (f"  eager / rel {tot['eager'] / tot['rel']:.2f}x" if "eager" in tot else ""))
+        return
     print(f"# encoder layer: B {B} H {H} T {T} hd {hd} dropout {p}; lengths U[{lo}, {hi}]: {int(ln.sum())} live tokens of {B * T}, "
           f"{n} packed rows; median of {a.rounds} x 20 hipGraph replays ({a.iters} calls each) in us per call (min .. max)")
     for layout, (qkv, d_out, fns) in paths.items():
