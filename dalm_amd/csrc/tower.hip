@@ -17,8 +17,8 @@
 //   swiglu backward:  ds = rb(da u);  du = rb(da s);  sig = 1 / (1 + exp(-g));  dg = rb(ds sig (1 + g (1 - sig)))
 // Algorithmic bytes: rope 2 * (|q| + |k|) * el (+ cos/sin, shared by all heads); swiglu forward 3 * n * el, backward 5 * n * el.
 // Further down: RMSNorm with the residual add (dalm_rms_norm_*), Qwen3's head norm + rotary (dalm_head_norm_*), and Gemma's two
-// formulas - GeGLU and the (1 + w) RMSNorm (dalm_geglu_*, dalm_gemma_norm_*) - and Arcee's ReLU^2 (dalm_relu2_*), each with its own
-// comment block.
+// formulas - GeGLU and the (1 + w) RMSNorm (dalm_geglu_*, dalm_gemma_norm_*) - Arcee's ReLU^2 (dalm_relu2_*), and OLMo-2's norm-then-add
+// and row-wide q / k norm + rotary (dalm_norm_add_*, dalm_row_norm_*), each with its own comment block.
 #include "dispatch.hpp"
 #include "relu2_math.hpp"
 #include "swiglu_math.hpp"
@@ -1126,7 +1126,9 @@ __global__ __launch_bounds__(256) void gemma_norm_fwd_kernel(const T* __restrict
   }
 }
 
-template <typename T, int NCH, bool ADD>
+// PLUS1: Gemma's (1 + w) weight; without it the plain weight in f32 - OLMo-2's norm (dalm_norm_add_bwd, further down), whose weight
+// dtype is its own as well
+template <typename T, int NCH, bool ADD, bool PLUS1 = true>
 __global__ __launch_bounds__(256) void gemma_norm_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ h,
                                                              const void* __restrict__ w, bool w_f32, const float* __restrict__ rstd_in,
                                                              const T* __restrict__ dres, T* __restrict__ dx, int R, int D,
@@ -1164,7 +1166,7 @@ __global__ __launch_bounds__(256) void gemma_norm_bwd_kernel(const T* __restrict
     dec16(rg[c], g); dec16(rh[c], xh);
     load_weight<N>(w, w_f32, d, wv);
 #pragma unroll
-    for (int e = 0; e < N; ++e) dot = fmaf(g[e] * (1.0f + wv[e]), xh[e] * rstd, dot);
+    for (int e = 0; e < N; ++e) dot = fmaf(g[e] * (PLUS1 ? 1.0f + wv[e] : wv[e]), xh[e] * rstd, dot);
   }
   dot = wave_sum(dot) / static_cast<float>(D);
 #pragma unroll
@@ -1175,7 +1177,7 @@ __global__ __launch_bounds__(256) void gemma_norm_bwd_kernel(const T* __restrict
     dec16(rg[c], g); dec16(rh[c], xh);
     load_weight<N>(w, w_f32, d, wv);
 #pragma unroll
-    for (int e = 0; e < N; ++e) o[e] = rstd * (g[e] * (1.0f + wv[e]) - (xh[e] * rstd) * dot);
+    for (int e = 0; e < N; ++e) o[e] = rstd * (g[e] * (PLUS1 ? 1.0f + wv[e] : wv[e]) - (xh[e] * rstd) * dot);
     if constexpr (ADD) {
       float r[N];
       dec16(rr[c], r);
@@ -1418,6 +1420,377 @@ extern "C" int dalm_relu2_bwd(const void* d_act, const void* y, void* d_y, int d
     using T = typename decltype(t)::type;
     hipLaunchKernelGGL((relu2_bwd_kernel<T>), grid, dim3(256), 0, as_stream(stream), static_cast<const T*>(d_act),
                        static_cast<const T*>(y), static_cast<T*>(d_y), n, ld, row_live);
+  });
+  return check_launch(__func__);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// OLMo-2 (modeling_olmo2.py): SwiGLU and the attention are Llama's; two row-wise formulas are not.
+//   Olmo2RMSNorm       (w * (x.float() * rsqrt(mean(x.float()^2) + eps))).to(x.dtype)   - the weight enters in f32, ONE rounding
+//   Olmo2DecoderLayer  h = residual + norm(sub_block(h)): the norm comes AFTER the sub-block, inside the residual   - dalm_norm_add_*
+//   Olmo2Attention     q_norm / k_norm over the WHOLE projection width (all heads of a token), in front of the head split and the
+//                      rotary embedding                                               - dalm_row_norm_rope_fwd / dalm_row_norm_bwd
+// Rounding points are the eager chain's (rb = a round trip through the tensor dtype):
+//   norm_add forward :  rstd = rsqrt(mean(x^2) + eps);  y = rb(w (x rstd));  out = rb(res + y)
+//   norm_add backward:  g = dy w;  xh = x rstd;  dx = rb(rstd (g - xh mean(g xh)));  the residual's gradient IS dy (no kernel).  With
+//                       the weight in the activation dtype this is dalm_rms_norm_bwd_live without dres, and the entry point calls it;
+//                       a weight of the other dtype goes through gemma_norm_bwd_kernel without its (1 + w)
+//   row_norm forward :  per (b, t): rstd = rsqrt(mean over H hd of x^2 + eps);  y = rb(w (x rstd));  out = rope forward of y per head
+//   row_norm backward:  gw = g w;  xh = x rstd (f32);  dx = rb(rstd (gw - xh mean over H hd of (gw xh)))
+// One wave per row, the row kept as raw 16-byte chunks between the reduction and the second pass (rms_norm_bwd_v2_kernel).  In the
+// row-norm kernels a chunk of 64 lanes holds 512 / hd whole heads, so the column inside the head - and with it a lane's cos / sin
+// vector and its rotary partner lane ^ (hd / 16) - is the same for every chunk: cos / sin are loaded once per lane.
+// Algorithmic bytes: norm_add forward 3 R D el, backward 3 R D el; row_norm forward 2 (|q| + |k|) el, backward 3 (|q| + |k|) el.
+// ---------------------------------------------------------------------------------------------------
+namespace {
+
+// The row statistic of the two forward kernels below: the sum of squares is accumulated in f64 (exact products of f32 values, a sum
+// that carries no visible error) and rsqrt(ss / n + eps) is rounded to f32 ONCE - the hardware's f32 estimate (2^-23) and one Newton
+// step in f64.  With f32 activations and f32 weights nothing downstream rounds coarser than f32 and torch's own mean and rsqrt are
+// that accurate: with an f32 fma chain and the bare instruction, weight gradients of one-row inputs came out at twice the eager
+// chain's error.  The arithmetic is a convert and an fma per element, far below the kernels' memory time; the rest is once per row.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+__device__ __forceinline__ float rstd_of(double ss, int n, float eps) {
+  const double v = ss / static_cast<double>(n) + static_cast<double>(eps);
+  const double r = static_cast<double>(rsqrtf(static_cast<float>(v)));
+  return static_cast<float>(r * (1.5 - 0.5 * v * r * r));
+}
+
+template <typename T, int NCH>
+__global__ __launch_bounds__(256) void norm_add_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res,
+                                                           const void* __restrict__ w, bool w_f32, T* __restrict__ out,
+                                                           float* __restrict__ rstd_out, int R, int D, float eps,
+                                                           const unsigned char* __restrict__ live) {
+#pragma clang fp contract(off)   // w (x rstd) and the add are separate eager kernels: in f32 a fused multiply-add would round once less
+  constexpr int N = Vec16<T>::VEC;
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= R) return;
+  const int64_t base = static_cast<int64_t>(row) * D;
+  const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+  if (live && !live[row]) {                      // a dead row (wave-uniform): nothing is read, out and rstd leave as zeros
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int d = (c * 64 + lane) * N;
+      if (d < D) *reinterpret_cast<uint4*>(out + base + d) = zero;
+    }
+    if (lane == 0) rstd_out[row] = 0.f;
+    return;
+  }
+  uint4 rx[NCH], rr[NCH];                        // both streams of the row in flight before the reduction
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * N;
+    const bool ok = d < D;
+    rx[c] = ok ? *reinterpret_cast<const uint4*>(x + base + d) : zero;
+    rr[c] = ok ? *reinterpret_cast<const uint4*>(res + base + d) : zero;
+  }
+  double ss = 0.0;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    float v[N];
+    dec16(rx[c], v);                             // past the row: zeros
+#pragma unroll
+    for (int e = 0; e < N; ++e) ss = fma(static_cast<double>(v[e]), static_cast<double>(v[e]), ss);
+  }
+  const float rstd = rstd_of(wave_sum_f64(ss), D, eps);
+  if (lane == 0) rstd_out[row] = rstd;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * N;
+    if (d >= D) continue;
+    float v[N], r[N], wv[N], o[N];
+    dec16(rx[c], v); dec16(rr[c], r);
+    load_weight<N>(w, w_f32, d, wv);
+#pragma unroll
+    for (int e = 0; e < N; ++e) o[e] = r[e] + Vec16<T>::rb(wv[e] * (v[e] * rstd));
+    Vec16<T>::store(out + base + d, o);          // the second rounding
+  }
+}
+
+// (a value, not a named constant: one whose address the two uses below take was kept in scratch memory)
+__device__ __forceinline__ uint4 zero16() { return make_uint4(0u, 0u, 0u, 0u); }
+
+struct RowNormTensor {
+  const void* x;                 // pre-norm projection output, [B, H, T, hd] view
+  const void* g;                 // backward: gradient of the normed, un-rotated value
+  void* o;                       // forward: normed + rotated; backward: gradient of x
+  const void* w;                 // [H hd]
+  float* rstd;                   // [B, T] f32: written by the forward, read by the backward
+  int64_t xs[3], gs[3], os[3];   // element strides of (b, h, t)
+  float eps;
+  int H;
+};
+struct RowNormParams {
+  RowNormTensor q, k;
+  const void* cos; const void* sin; int64_t cs[2];   // strides of (b, t); forward only
+  int B, T;
+  unsigned q_blocks;                                 // workgroups that serve q (4 tokens each); the rest serve k
+  bool w_f32;
+  const unsigned char* live;                         // [B * T] or NULL
+};
+
+// where a wave works: token (b, t) of q or of k (uniform per workgroup, as in head_row), and its lane inside every 64-lane chunk:
+// head c * (64 / G) + lane / G of the chunk c, column (lane % G) * 8 of that head
+template <int HD>
+struct RowNormAt {
+  static constexpr int G = HD / 8, HPC = 64 / G;
+  bool in, is_k;
+  unsigned bt;
+  int b, t, h0, hc;
+  __device__ __forceinline__ explicit RowNormAt(const RowNormParams& p) {
+    is_k = blockIdx.x >= p.q_blocks;
+    bt = (is_k ? blockIdx.x - p.q_blocks : blockIdx.x) * 4u + (threadIdx.x >> 6);
+    in = bt < static_cast<unsigned>(p.B) * p.T;
+    const int lane = threadIdx.x & 63;
+    t = static_cast<int>(bt % p.T); b = static_cast<int>(bt / p.T);
+    h0 = lane / G; hc = (lane % G) * 8;
+  }
+  // a [B, H, T, hd] view with strides s at this lane's (b, t, column): where head 0 starts and how far apart the heads lie
+  struct View { int64_t base, hs; __device__ __forceinline__ int64_t operator()(int head) const { return base + head * hs; } };
+  __device__ __forceinline__ View view(const int64_t (&s)[3]) const { return {b * s[0] + t * s[2] + hc, s[1]}; }
+};
+
+template <int HD, int NCH>
+__global__ __launch_bounds__(256) void row_norm_rope_fwd_kernel(const RowNormParams p) {
+#pragma clang fp contract(off)   // the eager chain is separate mul and add kernels (see rope_qk_kernel)
+  using V = Vec16<bf16_t>;
+  using At = RowNormAt<HD>;
+  const At r(p);
+  if (!r.in) return;                             // wave-uniform, and so is everything up to the lanes' `head < H`
+  const RowNormTensor& R = r.is_k ? p.k : p.q;
+  const int H = R.H;
+  const bf16_t* xp = static_cast<const bf16_t*>(R.x);
+  bf16_t* op = static_cast<bf16_t*>(R.o);
+  const typename At::View xv = r.view(R.xs), ov = r.view(R.os);
+  if (p.live && !p.live[r.bt]) {                 // a dead (b, t): nothing is read, the outputs and rstd leave as zeros
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int head = c * At::HPC + r.h0;
+      if (head < H) *reinterpret_cast<uint4*>(op + ov(head)) = zero16();
+    }
+    if ((threadIdx.x & 63) == 0) R.rstd[r.bt] = 0.f;
+    return;
+  }
+  uint4 rx[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int head = c * At::HPC + r.h0;
+    rx[c] = head < H ? *reinterpret_cast<const uint4*>(xp + xv(head)) : zero16();
+  }
+  float cs[8], sn[8];                            // one vector per lane: the column inside the head does not depend on the chunk
+  const int64_t ca = r.b * p.cs[0] + r.t * p.cs[1] + r.hc;
+  V::load(static_cast<const bf16_t*>(p.cos) + ca, cs);
+  V::load(static_cast<const bf16_t*>(p.sin) + ca, sn);
+  double ss = 0.0;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    float x[8];
+    dec8(rx[c], x);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ss = fma(static_cast<double>(x[e]), static_cast<double>(x[e]), ss);
+  }
+  const float rstd = rstd_of(wave_sum_f64(ss), H * HD, R.eps);
+  if ((threadIdx.x & 63) == 0) R.rstd[r.bt] = rstd;
+  const bool second = r.hc >= HD / 2;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    if (c * At::HPC >= H) break;                 // wave-uniform: every lane of the wave runs the shuffles below or none does
+    const int head = c * At::HPC + r.h0;
+    const bool ok = head < H;                    // a head's G lanes agree, and the rotary partner is one of them
+    float x[8], w[8], y[8], z[8], o[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) w[e] = 0.f;
+    dec8(rx[c], x);
+    if (ok) load_weight<8>(R.w, p.w_f32, head * HD + r.hc, w);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) y[e] = V::rb(w[e] * (x[e] * rstd));
+    // the other half of the head row: y is exact in bf16, so it travels as four packed words (head_norm_rope_fwd_kernel)
+    const uint4 mine = enc8(y);
+    dec8(make_uint4(__shfl_xor(mine.x, At::G / 2, 64), __shfl_xor(mine.y, At::G / 2, 64), __shfl_xor(mine.z, At::G / 2, 64),
+                    __shfl_xor(mine.w, At::G / 2, 64)), z);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float a = V::rb(y[e] * cs[e]), b = V::rb(z[e] * sn[e]);
+      o[e] = second ? a + b : a - b;
+    }
+    if (ok) V::store(op + ov(head), o);
+  }
+}
+
+template <int HD, int NCH>
+__global__ __launch_bounds__(256) void row_norm_bwd_kernel(const RowNormParams p) {
+  using V = Vec16<bf16_t>;
+  using At = RowNormAt<HD>;
+  const At r(p);
+  if (!r.in) return;
+  const RowNormTensor& R = r.is_k ? p.k : p.q;
+  const int H = R.H;
+  const bf16_t* gp = static_cast<const bf16_t*>(R.g);
+  const bf16_t* xp = static_cast<const bf16_t*>(R.x);
+  bf16_t* op = static_cast<bf16_t*>(R.o);
+  const typename At::View gv = r.view(R.gs), xv = r.view(R.xs), ov = r.view(R.os);
+  if (p.live && !p.live[r.bt]) {                 // a dead (b, t): nothing is read, dx leaves as zeros
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int head = c * At::HPC + r.h0;
+      if (head < H) *reinterpret_cast<uint4*>(op + ov(head)) = zero16();
+    }
+    return;
+  }
+  uint4 rg[NCH], rx[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int head = c * At::HPC + r.h0;
+    const bool ok = head < H;
+    rg[c] = ok ? *reinterpret_cast<const uint4*>(gp + gv(head)) : zero16();
+    rx[c] = ok ? *reinterpret_cast<const uint4*>(xp + xv(head)) : zero16();
+  }
+  const float rstd = R.rstd[r.bt];
+  float dot = 0.f;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int head = c * At::HPC + r.h0;
+    if (head >= H) continue;
+    float g[8], xh[8], w[8];
+    dec8(rg[c], g); dec8(rx[c], xh);
+    load_weight<8>(R.w, p.w_f32, head * HD + r.hc, w);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dot = fmaf(g[e] * w[e], xh[e] * rstd, dot);
+  }
+  dot = wave_sum(dot) / static_cast<float>(H * HD);
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int head = c * At::HPC + r.h0;
+    if (head >= H) continue;
+    float g[8], xh[8], w[8], o[8];
+    dec8(rg[c], g); dec8(rx[c], xh);
+    load_weight<8>(R.w, p.w_f32, head * HD + r.hc, w);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = rstd * (g[e] * w[e] - (xh[e] * rstd) * dot);
+    V::store(op + ov(head), o);                                                  // rounded once
+  }
+}
+
+// the checks the two row-norm entry points share; fills B, T, the head counts and the grid, returns the chunk count through `nch`
+int row_norm_shape(const char* fn, int64_t B, int64_t T, int64_t Hq, int64_t Hk, int64_t hd, int w_dtype, RowNormParams& p, dim3& grid,
+                   int& nch) {
+  if (!(w_dtype == DALM_F32 || w_dtype == DALM_BF16)) return fail(DALM_E_DTYPE, fn, "w_dtype must be DALM_F32 or DALM_BF16");
+  if (!(hd == 64 || hd == 128)) return fail(DALM_E_SHAPE, fn, "head width must be 64 or 128");
+  if (!(B > 0 && T > 0 && Hq > 0 && Hk > 0)) return fail(DALM_E_SHAPE, fn, "need B, T, Hq, Hk > 0");
+  if (!(Hq * hd <= 8192 && Hk * hd <= 8192)) return fail(DALM_E_SHAPE, fn, "a row (Hq hd, Hk hd) holds at most 8192 elements");
+  if (!(B <= 0x7fffffffLL && T <= 0x7fffffffLL && B * T <= 0x7fffffffLL && B * T * (Hq + Hk) * (hd / 8) <= 0x7fffffffLL))
+    return fail(DALM_E_SHAPE, fn, "tensor too large for one launch");
+  p.B = static_cast<int>(B); p.T = static_cast<int>(T); p.q.H = static_cast<int>(Hq); p.k.H = static_cast<int>(Hk);
+  p.w_f32 = w_dtype == DALM_F32;
+  const int64_t blocks = (B * T + 3) / 4, wide = (Hq > Hk ? Hq : Hk) * hd;
+  p.q_blocks = static_cast<unsigned>(blocks);
+  grid = dim3(static_cast<unsigned>(2 * blocks));
+  nch = static_cast<int>((wide + 511) / 512);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int dalm_norm_add_fwd(const void* x, const void* res, const void* w, int dtype, int w_dtype, int64_t R, int64_t D, float eps,
+                                 void* out, float* rstd, const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(x && res && w && out && rstd, DALM_E_NULL, "null pointer argument");
+  DALM_GEMMA_NORM_CHECKS;
+  DALM_REQUIRE(aligned16(x, res, w, out), DALM_E_ALIGN, "tensors must be 16-byte aligned");
+  if (R == 0) return 0;
+  const int Ri = static_cast<int>(R), Di = static_cast<int>(D);
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_ceil<1, 2, 4, 8, 16>(nch, [&](auto n) {
+      hipLaunchKernelGGL((norm_add_fwd_kernel<T, n>), grid, dim3(256), 0, as_stream(stream), static_cast<const T*>(x),
+                         static_cast<const T*>(res), w, w_dtype == DALM_F32, static_cast<T*>(out), rstd, Ri, Di, eps, row_live);
+    });
+  });
+  return check_launch(__func__);
+}
+
+extern "C" int dalm_norm_add_bwd(const void* dy, const void* x, const void* w, const float* rstd, int dtype, int w_dtype, int64_t R,
+                                 int64_t D, void* dx, const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(dy && x && w && rstd && dx, DALM_E_NULL, "null pointer argument");
+  DALM_GEMMA_NORM_CHECKS;
+  DALM_REQUIRE(aligned16(dy, x, w, dx), DALM_E_ALIGN, "tensors must be 16-byte aligned");
+  if (R == 0) return 0;
+  // the weight in the activation dtype: dalm_rms_norm_bwd's arithmetic without a residual-path gradient, rounded where it rounds
+  if (w_dtype == dtype) return dalm_rms_norm_bwd_live(dy, x, w, rstd, nullptr, dtype, R, D, dx, row_live, stream);
+  const int Ri = static_cast<int>(R), Di = static_cast<int>(D);
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_ceil<1, 2, 4, 8, 16>(nch, [&](auto n) {
+      hipLaunchKernelGGL((gemma_norm_bwd_kernel<T, n, false, false>), grid, dim3(256), 0, as_stream(stream), static_cast<const T*>(dy),
+                         static_cast<const T*>(x), w, w_dtype == DALM_F32, rstd, static_cast<const T*>(nullptr), static_cast<T*>(dx),
+                         Ri, Di, row_live);
+    });
+  });
+  return check_launch(__func__);
+}
+
+extern "C" int dalm_row_norm_rope_fwd(const void* q, const void* k, const void* wq, const void* wk, int w_dtype, float eps_q,
+                                      float eps_k, const void* cos, const void* sin, int64_t B, int64_t T, int64_t Hq, int64_t Hk,
+                                      int64_t hd, const int64_t* q_strides, const int64_t* k_strides, const int64_t* qo_strides,
+                                      const int64_t* ko_strides, const int64_t* cs_strides, void* q_out, void* k_out, float* rstd_q,
+                                      float* rstd_k, const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(q && k && wq && wk && cos && sin && q_strides && k_strides && qo_strides && ko_strides && cs_strides && q_out && k_out
+                   && rstd_q && rstd_k, DALM_E_NULL, "null pointer argument");
+  RowNormParams p;
+  dim3 grid;
+  int nch;
+  if (const int rc = row_norm_shape(__func__, B, T, Hq, Hk, hd, w_dtype, p, grid, nch)) return rc;
+  DALM_REQUIRE(aligned16(q, k, wq, wk, cos, sin, q_out, k_out) && reinterpret_cast<uintptr_t>(rstd_q) % 4 == 0
+                   && reinterpret_cast<uintptr_t>(rstd_k) % 4 == 0 && strides_mult8(q_strides, 3) && strides_mult8(k_strides, 3)
+                   && strides_mult8(qo_strides, 3) && strides_mult8(ko_strides, 3) && strides_mult8(cs_strides, 2),
+               DALM_E_ALIGN, "tensors must be 16-byte aligned and every stride a multiple of 8 elements");
+  p.q.x = q; p.q.g = nullptr; p.q.o = q_out; p.q.w = wq; p.q.rstd = rstd_q; p.q.eps = eps_q;
+  p.k.x = k; p.k.g = nullptr; p.k.o = k_out; p.k.w = wk; p.k.rstd = rstd_k; p.k.eps = eps_k;
+  for (int i = 0; i < 3; ++i) {
+    p.q.xs[i] = q_strides[i]; p.q.os[i] = qo_strides[i]; p.q.gs[i] = 0;
+    p.k.xs[i] = k_strides[i]; p.k.os[i] = ko_strides[i]; p.k.gs[i] = 0;
+  }
+  p.cos = cos; p.sin = sin; p.cs[0] = cs_strides[0]; p.cs[1] = cs_strides[1];
+  p.live = row_live;
+  by_exact<64, 128>(static_cast<int>(hd), [&](auto width) {
+    by_ceil<1, 2, 4, 8, 16>(nch, [&](auto n) {
+      hipLaunchKernelGGL((row_norm_rope_fwd_kernel<width, n>), grid, dim3(256), 0, as_stream(stream), p);
+    });
+  });
+  return check_launch(__func__);
+}
+
+extern "C" int dalm_row_norm_bwd(const void* gq, const void* gk, const void* q, const void* k, const void* wq, const void* wk,
+                                 int w_dtype, const float* rstd_q, const float* rstd_k, int64_t B, int64_t T, int64_t Hq, int64_t Hk,
+                                 int64_t hd, const int64_t* gq_strides, const int64_t* gk_strides, const int64_t* q_strides,
+                                 const int64_t* k_strides, const int64_t* dq_strides, const int64_t* dk_strides, void* dq, void* dk,
+                                 const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(gq && gk && q && k && wq && wk && rstd_q && rstd_k && gq_strides && gk_strides && q_strides && k_strides && dq_strides
+                   && dk_strides && dq && dk, DALM_E_NULL, "null pointer argument");
+  RowNormParams p;
+  dim3 grid;
+  int nch;
+  if (const int rc = row_norm_shape(__func__, B, T, Hq, Hk, hd, w_dtype, p, grid, nch)) return rc;
+  DALM_REQUIRE(aligned16(gq, gk, q, k, wq, wk, dq, dk) && reinterpret_cast<uintptr_t>(rstd_q) % 4 == 0
+                   && reinterpret_cast<uintptr_t>(rstd_k) % 4 == 0 && strides_mult8(gq_strides, 3) && strides_mult8(gk_strides, 3)
+                   && strides_mult8(q_strides, 3) && strides_mult8(k_strides, 3) && strides_mult8(dq_strides, 3)
+                   && strides_mult8(dk_strides, 3),
+               DALM_E_ALIGN, "tensors must be 16-byte aligned and every stride a multiple of 8 elements");
+  p.q.x = q; p.q.g = gq; p.q.o = dq; p.q.w = wq; p.q.rstd = const_cast<float*>(rstd_q); p.q.eps = 0.f;
+  p.k.x = k; p.k.g = gk; p.k.o = dk; p.k.w = wk; p.k.rstd = const_cast<float*>(rstd_k); p.k.eps = 0.f;
+  for (int i = 0; i < 3; ++i) {
+    p.q.xs[i] = q_strides[i]; p.q.gs[i] = gq_strides[i]; p.q.os[i] = dq_strides[i];
+    p.k.xs[i] = k_strides[i]; p.k.gs[i] = gk_strides[i]; p.k.os[i] = dk_strides[i];
+  }
+  p.cos = nullptr; p.sin = nullptr; p.cs[0] = p.cs[1] = 0;
+  p.live = row_live;
+  by_exact<64, 128>(static_cast<int>(hd), [&](auto width) {
+    by_ceil<1, 2, 4, 8, 16>(nch, [&](auto n) {
+      hipLaunchKernelGGL((row_norm_bwd_kernel<width, n>), grid, dim3(256), 0, as_stream(stream), p);
+    });
   });
   return check_launch(__func__);
 }

@@ -168,6 +168,13 @@ SIGNATURES = {
     # Arcee: ReLU^2 (ArceeMLP's activation), one entry point per direction (row liveness is an argument)
     "dalm_relu2_fwd": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _vp, _vp]),
     "dalm_relu2_bwd": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
+    # OLMo-2: norm-then-add (the post-norm of its decoder layer) and q_norm / k_norm over the whole projection width + rotary
+    "dalm_norm_add_fwd": (_int, [_vp, _vp, _vp, _int, _int, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
+    "dalm_norm_add_bwd": (_int, [_vp, _vp, _vp, _vp, _int, _int, _i64, _i64, _vp, _vp, _vp]),
+    "dalm_row_norm_rope_fwd": (_int, [_vp, _vp, _vp, _vp, _int, _f32, _f32, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dalm_row_norm_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
+                                 _vp, _vp, _vp, _vp, _vp]),
     "dalm_bert_add_norm_fwd_live": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _f32, _f32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _vp]),
     "dalm_bert_add_norm_bwd_live": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),

@@ -22,8 +22,8 @@ salt is a host call counter, a re-run forward would draw another mask.
 Grouped-query heads (Llama-3 / Mistral / TinyLlama: k, v with Hkv < H heads) run un-expanded on `dalm_attn_gqa_fwd` /
 `dalm_attn_gqa_bwd` where `grouped_supported` holds: query head h reads KV head h // (H // Hkv), dk / dv come back with Hkv heads,
 summed over each group in f32 inside the kernel.  Elsewhere k / v are expanded by `repeat_kv` first.
-Qwen3 (q_norm / k_norm over the head dimension in front of the rotary embedding) runs norm + rotation + attention as one node,
-`norm_rope_sdpa`; a call that carries a `sliding_window` shorter than the sequence goes to transformers' own function.
+Qwen3 (q_norm / k_norm over the head dimension in front of the rotary embedding) and OLMo-2 (q_norm / k_norm over the whole
+projection width, in front of the head split) run norm + rotation + attention as one node, `norm_rope_sdpa`; a call that carries a `sliding_window` shorter than the sequence goes to transformers' own function.
 MPNet (a per-head relative-position bias by column difference on top of BERT's attention) runs on `dalm_attn_rel_*` with the bias
 as one [H, 2 Tc - 1] vector per forward: `rel_sdpa`, reached from fastpath's MPNetSelfAttention patch, not through "dalm_sdpa".
 Everything the kernels do not take (CPU tensors, other head widths, odd T with dropout, float masks, a KV cache, no gradient wanted) goes
@@ -281,23 +281,26 @@ class _RopeSdpaHip(torch.autograd.Function):
 
 
 class _NormRopeSdpaHip(torch.autograd.Function):
-    """Qwen3: RMSNorm over the head dimension of q and of k + rotary embedding (`dalm_head_norm_rope_fwd`, one launch) + the
-    attention.  Backward: `dalm_attn_bwd` / `dalm_attn_gqa_bwd` un-rotate dq / dk in their epilogues (as for `_RopeSdpaHip`),
-    then `dalm_head_norm_bwd` (one launch) takes them through the two norms.  Equal and grouped heads, padded and packed; one
-    key / value head is not routed here (`supported` / `grouped_supported` decline it).  No host synchronisation."""
+    """q_norm / k_norm + rotary embedding (one launch) + the attention.  The norms are RMSNorms over the head dimension (Qwen3:
+    `dalm_head_norm_rope_fwd`) or - `row_wide` - over the whole projection width of a token, all heads (OLMo-2:
+    `dalm_row_norm_rope_fwd`).  Backward: `dalm_attn_bwd` / `dalm_attn_gqa_bwd` un-rotate dq / dk in their epilogues (as for
+    `_RopeSdpaHip`), then `dalm_head_norm_bwd` / `dalm_row_norm_bwd` (one launch) takes them through the two norms.  Equal and
+    grouped heads, padded and packed; one key / value head is not routed here (`supported` / `grouped_supported` decline it).  No
+    host synchronisation."""
 
     @staticmethod
-    def forward(ctx, q, k, v, wq, wk, eps_q, eps_k, cos, sin, mask, scale, causal):
+    def forward(ctx, q, k, v, wq, wk, eps_q, eps_k, cos, sin, mask, scale, causal, row_wide=False):
         from . import tower_ops
 
         B, H, T, hd = q.shape
         # dead (b, t) of a padded tower call leave norm + rotation as zeros (finite values for the attention kernels) and get
         # zero gradients from the norm's backward
-        q2, k2, rq, rk, live = tower_ops.head_norm_rope(q, k, wq, wk, eps_q, eps_k, cos, sin)
+        norm_rope = tower_ops.row_norm_rope if row_wide else tower_ops.head_norm_rope
+        q2, k2, rq, rk, live = norm_rope(q, k, wq, wk, eps_q, eps_k, cos, sin)
         pk = _pack(mask, B, H, T, causal, q.dtype, q.device)
         out, lse = _attn_forward(q2, k2, v, pk, scale, causal)
         ctx.save_for_backward(q, k, q2, k2, v, out, lse, cos, sin, wq, wk, rq, rk, *([live] if live is not None else []))
-        ctx.pack, ctx.scale = pk, scale
+        ctx.pack, ctx.scale, ctx.row_wide = pk, scale, row_wide
         return out
 
     @staticmethod
@@ -306,18 +309,22 @@ class _NormRopeSdpaHip(torch.autograd.Function):
 
         q, k, q2, k2, v, out, lse, cos, sin, wq, wk, rq, rk, *live = ctx.saved_tensors
         live = live[0] if live else None
+        norm_bwd, weight_grad = ((tower_ops.row_norm_bwd, tower_ops.row_norm_weight_grad) if ctx.row_wide
+                                 else (tower_ops.head_norm_bwd, tower_ops.head_norm_weight_grad))
         gq, gk, dv = _attn_backward(q2, k2, v, out, lse, d_out, ctx.pack, ctx.scale, cos, sin)    # of the normed, un-rotated q / k
-        dq, dk = tower_ops.head_norm_bwd(gq, gk, q, k, wq, wk, rq, rk, live)
-        dwq = tower_ops.head_norm_weight_grad(gq, q, rq, live).to(wq.dtype) if ctx.needs_input_grad[3] else None
-        dwk = tower_ops.head_norm_weight_grad(gk, k, rk, live).to(wk.dtype) if ctx.needs_input_grad[4] else None
-        return dq, dk, dv, dwq, dwk, None, None, None, None, None, None, None
+        dq, dk = norm_bwd(gq, gk, q, k, wq, wk, rq, rk, live)
+        dwq = weight_grad(gq, q, rq, live).to(wq.dtype) if ctx.needs_input_grad[3] else None
+        dwk = weight_grad(gk, k, rk, live).to(wk.dtype) if ctx.needs_input_grad[4] else None
+        return dq, dk, dv, dwq, dwk, None, None, None, None, None, None, None, None
 
 
-def norm_rope_sdpa(query, key, value, wq, wk, eps_q: float, eps_k: float, cos, sin, mask, scale: float, causal: bool):
+def norm_rope_sdpa(query, key, value, wq, wk, eps_q: float, eps_k: float, cos, sin, mask, scale: float, causal: bool,
+                   row_wide: bool = False):
     """sdpa(apply_rotary_pos_emb(rmsnorm(query) * wq, rmsnorm(key) * wk, cos, sin), value, ...) with the norms over the head
-    dimension (Qwen3's q_norm / k_norm), for what `tower_ops.head_norm_rope_supported`, `rope_fusable` and `node_supported`
-    accept.  The norm weights may require grad."""
-    return _NormRopeSdpaHip.apply(query, key, value, wq, wk, eps_q, eps_k, cos, sin, mask, scale, causal)
+    dimension (Qwen3's q_norm / k_norm) or, `row_wide`, over all heads of a token (OLMo-2's), for what
+    `tower_ops.head_norm_rope_supported` / `tower_ops.row_norm_rope_supported`, `rope_fusable` and `node_supported` accept.  The
+    norm weights may require grad."""
+    return _NormRopeSdpaHip.apply(query, key, value, wq, wk, eps_q, eps_k, cos, sin, mask, scale, causal, row_wide)
 
 
 def rope_fusable(q, k, cos, sin) -> bool:
@@ -731,7 +738,7 @@ def sdpa(query, key, value, mask, scale: float, causal: bool, dropout_p: float =
 
 
 def use_hip_attention_backward(model: torch.nn.Module) -> bool:
-    """Switch a Llama-family, Gemma, Arcee, BERT or RoBERTa-family (roberta, xlm-roberta, camembert: BERT's layer code) model of head
+    """Switch a Llama-family, Gemma, Arcee, OLMo-2, BERT or RoBERTa-family (roberta, xlm-roberta, camembert: BERT's layer code) model of head
     width 32, 64 or 128 from "sdpa" to "dalm_sdpa".  xlm-roberta-xl (pre-LayerNorm layers) is not taken, and neither is a Gemma of
     head width 256 (every released checkpoint) or an Arcee of head width 80 (`ArceeConfig()`'s defaults; AFM-4.5B has 128): it
     keeps transformers' SDPA and does not pack.  DALM_ATTN_KERNEL=0 disables."""
@@ -740,7 +747,7 @@ def use_hip_attention_backward(model: torch.nn.Module) -> bool:
     cfg = getattr(model, "config", None)
     if cfg is None or getattr(cfg, "_attn_implementation", None) != "sdpa":
         return False
-    if getattr(cfg, "model_type", "") not in ("llama", "mistral", "qwen2", "qwen3", "gemma", "arcee", "bert", "roberta",
+    if getattr(cfg, "model_type", "") not in ("llama", "mistral", "qwen2", "qwen3", "gemma", "arcee", "olmo2", "bert", "roberta",
                                               "xlm-roberta", "camembert"):
         return False
     hd = getattr(cfg, "head_dim", None) or (cfg.hidden_size // cfg.num_attention_heads)

@@ -250,7 +250,7 @@ def use_swiglu_kernel(model: torch.nn.Module) -> int:
         return (all(hasattr(mod, a) for a in ("gate_proj", "up_proj", "down_proj"))
                 and (isinstance(act, torch.nn.SiLU) or type(act).__name__ in ("SiLUActivation", "SiLU")))
 
-    return _install(model, ("LlamaMLP", "MistralMLP", "Qwen2MLP", "Qwen3MLP"), gated_silu, _mlp_matches, _swiglu_mlp_forward)
+    return _install(model, ("LlamaMLP", "MistralMLP", "Qwen2MLP", "Qwen3MLP", "Olmo2MLP"), gated_silu, _mlp_matches, _swiglu_mlp_forward)
 
 
 def _mlp_matches(mod: torch.nn.Module, forward=_swiglu_mlp_forward, what: str = "down(silu(gate(x)) * up(x)) here",
@@ -926,20 +926,25 @@ def _norm_eps(norm) -> float:
     return float(getattr(norm, "_dalm_eps", getattr(norm, "variance_epsilon", getattr(norm, "eps", 1e-6))))
 
 
-def _head_norm_ok(norm, hd: int) -> bool:
-    """A Qwen3RMSNorm over the head dimension: w * (x * rsqrt(mean(x^2) + eps)).to(dtype) with a plain weight [hd] - its own forward,
-    or `_native_forward` (`use_native_rms_norm`, the same formula behind its own run-time guard)."""
+def _qk_norm_ok(norm, row_wide: bool, width: int) -> bool:
+    """The q_norm / k_norm the fused node stands for, by class name, with a plain weight [width] - its own forward, or
+    `_native_forward` (`use_native_rms_norm`, the same formula behind its own run-time guard):
+      Qwen3RMSNorm over the head dimension            w * (x * rsqrt(mean(x^2) + eps)).to(dtype)
+      Olmo2RMSNorm over all heads of a token (row_wide)   (w * (x * rsqrt(mean(x^2) + eps))).to(dtype)"""
     w = getattr(norm, "weight", None)
-    return (type(norm).__name__ == "Qwen3RMSNorm" and w is not None and w.dim() == 1 and w.shape[0] == hd
-            and (hasattr(norm, "variance_epsilon") or hasattr(norm, "_dalm_eps")))
+    return (type(norm).__name__ == ("Olmo2RMSNorm" if row_wide else "Qwen3RMSNorm") and w is not None and w.dim() == 1
+            and w.shape[0] == width and (hasattr(norm, "variance_epsilon") or hasattr(norm, "_dalm_eps")))
 
 
-def _decoder_attention_forward(self, hidden_states, position_embeddings, attention_mask, past_key_values, kwargs, norms, window):
-    """transformers' LlamaAttention.forward / Qwen3Attention.forward for the training call ("dalm_sdpa", no KV cache, no dropout, no
-    sliding window): the same statements with (the head norms +) apply_rotary_pos_emb + the attention call as one node.  Every
-    other call goes to transformers' own forward.  The two classes differ in
-      norms   None, or Qwen3's (q_norm, k_norm) between the projections and the rotation;
-      window  the keyword Qwen3 adds to the attention call, `{"sliding_window": ...}`; `{}` for Llama."""
+def _decoder_attention_forward(self, hidden_states, position_embeddings, attention_mask, past_key_values, kwargs, norms, window,
+                               row_wide=False):
+    """transformers' LlamaAttention.forward / Qwen3Attention.forward / Olmo2Attention.forward for the training call ("dalm_sdpa", no
+    KV cache, no dropout, no sliding window): the same statements with (the q / k norms +) apply_rotary_pos_emb + the attention call
+    as one node.  Every other call goes to transformers' own forward.  The classes differ in
+      norms     None, or (q_norm, k_norm) between the projections and the rotation;
+      row_wide  where the norms act: on the head view, over the head dimension (Qwen3), or - True - on the projection's output in
+                front of the head view, over all heads of a token (OLMo-2);
+      window    the keyword Qwen3 adds to the attention call, `{"sliding_window": ...}`; `{}` for the others."""
     from . import attention, tower_ops
 
     cfg = self.config
@@ -959,26 +964,33 @@ def _decoder_attention_forward(self, hidden_states, position_embeddings, attenti
     causal = bool(q_t.shape[2] > 1 and attention_mask is None and getattr(self, "is_causal", True))
     # padded or packed (dalm_amd/packed.py: [1, H, n, hd] views, sequences from the descriptor), equal heads or grouped-query
     # heads left un-expanded: the same node
+    if row_wide and q_t.is_cuda and q_t.dtype == torch.bfloat16:
+        cos, sin = _tables_in_bf16(cos, sin)     # the node's tables; the fall-through below goes back to the module's own
     fused = (attention.node_supported(q_t, k_t, value_states, attention_mask, causal)
              and attention.rope_fusable(q_t, k_t, cos, sin))
     qn, kn = norms or (None, None)
     if fused and norms is not None:
-        fused = (_head_norm_ok(qn, self.head_dim) and _head_norm_ok(kn, self.head_dim)
-                 and tower_ops.head_norm_rope_supported(q_t, k_t, qn.weight, kn.weight, cos, sin))
+        wide = (q_t.shape[1] * self.head_dim, k_t.shape[1] * self.head_dim) if row_wide else (self.head_dim, self.head_dim)
+        norm_rope_supported = tower_ops.row_norm_rope_supported if row_wide else tower_ops.head_norm_rope_supported
+        fused = (_qk_norm_ok(qn, row_wide, wide[0]) and _qk_norm_ok(kn, row_wide, wide[1])
+                 and norm_rope_supported(q_t, k_t, qn.weight, kn.weight, cos, sin))
     if fused and norms is None:
         attn_output = attention.rope_sdpa(q_t, k_t, value_states, cos, sin, attention_mask, float(self.scaling), causal)
     elif fused:
         attn_output = attention.norm_rope_sdpa(q_t, k_t, value_states, qn.weight, kn.weight, _norm_eps(qn), _norm_eps(kn), cos, sin,
-                                               attention_mask, float(self.scaling), causal)
+                                               attention_mask, float(self.scaling), causal, row_wide)
     else:                      # CPU tensors, fp32, one KV head, other head widths, ...: transformers' own sequence from here on
         import importlib
 
         from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
 
-        if norms is not None:
+        if norms is not None and row_wide:       # the norm of the projection's output ([.., H hd]: the view undone), then the head view
+            q_t = qn(query_raw.flatten(-2)).view(hidden_shape).transpose(1, 2)
+            k_t = kn(key_raw.flatten(-2)).view(hidden_shape).transpose(1, 2)
+        elif norms is not None:
             q_t, k_t = qn(query_raw).transpose(1, 2), kn(key_raw).transpose(1, 2)
         rope = importlib.import_module(type(self).__module__).apply_rotary_pos_emb
-        query_states, key_states = rope(q_t, k_t, cos, sin)
+        query_states, key_states = rope(q_t, k_t, *position_embeddings)
         attn_output, _ = ALL_ATTENTION_FUNCTIONS[cfg._attn_implementation](
             self, query_states, key_states, value_states, attention_mask, dropout=0.0, scaling=self.scaling, **window, **kwargs)
     if fused:
@@ -996,6 +1008,26 @@ def _qwen3_attention_forward(self, hidden_states, position_embeddings=None, atte
     """Qwen3Attention.forward: q_norm + k_norm + rotary + attention as `attention.norm_rope_sdpa`."""
     return _decoder_attention_forward(self, hidden_states, position_embeddings, attention_mask, past_key_values, kwargs,
                                       (self.q_norm, self.k_norm), {"sliding_window": getattr(self, "sliding_window", None)})
+
+
+def _tables_in_bf16(cos, sin):
+    """Olmo2RotaryEmbedding hands every layer its tables in f32 (Llama's casts them to the activations' dtype itself) and
+    apply_rotary_pos_emb then multiplies in f32.  The fused node - like the rotation's backward inside `dalm_attn_bwd` - reads bf16
+    tables and rounds as Llama's chain does, so the routed OLMo-2 rotates with Llama's convention: tables rounded to bf16, ONCE per
+    forward (every layer is handed the same two tensors; the copies ride on the cos tensor)."""
+    if cos.dtype != torch.float32 or sin.dtype != torch.float32:
+        return cos, sin
+    got = getattr(cos, "_dalm_bf16", None)
+    if got is None or got[0] is not sin or got[1] != (cos._version, sin._version):
+        got = (sin, (cos._version, sin._version), cos.to(torch.bfloat16), sin.to(torch.bfloat16))
+        cos._dalm_bf16 = got
+    return got[2], got[3]
+
+
+def _olmo2_attention_forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
+    """Olmo2Attention.forward: q_norm + k_norm over the whole projection width + rotary + attention as `attention.norm_rope_sdpa`."""
+    return _decoder_attention_forward(self, hidden_states, position_embeddings, attention_mask, past_key_values, kwargs,
+                                      (self.q_norm, self.k_norm), {}, row_wide=True)
 
 
 def _use_attention_node(model: torch.nn.Module, name: str, attrs: tuple, guard: str, forward) -> int:
@@ -1018,6 +1050,34 @@ def use_qwen3_attention_node(model: torch.nn.Module) -> int:
     `_qwen3_attention_forward` restates.  Returns the count."""
     return _use_attention_node(model, "Qwen3Attention", ("q_proj", "k_proj", "v_proj", "o_proj", "q_norm", "k_norm", "scaling",
                                                          "sliding_window"), "qwen3-attn", _qwen3_attention_forward)
+
+
+def use_olmo2_attention_node(model: torch.nn.Module) -> int:
+    """Patch Olmo2Attention modules of a model that runs on "dalm_sdpa" (models/attention.py) and whose forward is the code
+    `_olmo2_attention_forward` restates; a biased projection (`attention_bias`) keeps transformers' code.  Returns the count."""
+    def plain(mod) -> bool:
+        return all(getattr(getattr(mod, a, None), "bias", 0) is None for a in ("q_proj", "k_proj", "v_proj", "o_proj"))
+
+    from . import attention
+
+    if getattr(getattr(model, "config", None), "_attn_implementation", None) != attention.NAME:
+        return 0
+    return _install(model, ("Olmo2Attention",),
+                    lambda mod: all(hasattr(mod, a) for a in ("q_norm", "k_norm", "scaling", "head_dim")) and plain(mod),
+                    "olmo2-attn", _olmo2_attention_forward, keep="_dalm_orig_attn_forward")
+
+
+# Olmo2Attention.forward: the norms sit on the projections' outputs, the head views come after them (other classes named Olmo*Attention
+# - olmo, olmo3, olmoe - are other code: no norm, a clamp, sliding windows; they are not named and would not pass)
+_SOURCE_GUARDS["olmo2-attn"] = (_restates(
+    _LLAMA_ATTN_PARAMS,
+    "query_states = self.q_norm(self.q_proj(hidden_states))",
+    "key_states = self.k_norm(self.k_proj(hidden_states))",
+    "value_states = self.v_proj(hidden_states)",
+    "query_states = query_states.view(hidden_shape).transpose(1, 2)",
+    "key_states = key_states.view(hidden_shape).transpose(1, 2)",
+    "value_states = value_states.view(hidden_shape).transpose(1, 2)",
+    *_LLAMA_ATTN_STATEMENTS[1:]), _RESTATED)
 
 
 # ---------------------------------------------------------------------------
@@ -1067,6 +1127,46 @@ def _two_norm_layer_forward(self, supported, add_norm, hidden_states, attention_
 
 
 
+def _olmo2_layer_forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_values=None, use_cache=False,
+                         position_embeddings=None, **kwargs):
+    """transformers' Olmo2DecoderLayer.forward - the norm comes AFTER each sub-block, inside the residual, and there is no
+    input_layernorm - with its two (RMSNorm, residual add) pairs on `dalm_norm_add_{fwd,bwd}`: one launch each way per pair instead
+    of Olmo2RMSNorm's f32 chain and the add.  Same values as the eager pair up to the f32 summation order of mean(x^2)."""
+    from . import tower_ops
+
+    n1, n2 = self.post_attention_layernorm, self.post_feedforward_layernorm
+    if not (tower_ops.norm_add_supported(hidden_states, hidden_states, n1.weight)
+            and tower_ops.norm_add_supported(hidden_states, hidden_states, n2.weight)):
+        return self._dalm_orig_forward(hidden_states, attention_mask=attention_mask, position_ids=position_ids,
+                                       past_key_values=past_key_values, use_cache=use_cache,
+                                       position_embeddings=position_embeddings, **kwargs)
+
+    def norm_add(norm, x, residual):             # a sub-block that answers in another dtype (autocast): the two statements as they are
+        if tower_ops.norm_add_supported(x, residual, norm.weight):
+            return tower_ops.norm_add(x, residual, norm.weight, _norm_eps(norm))
+        return residual + norm(x)
+
+    attn_out, _ = self.self_attn(hidden_states=hidden_states, attention_mask=attention_mask, position_ids=position_ids,
+                                 past_key_values=past_key_values, use_cache=use_cache,
+                                 position_embeddings=position_embeddings, **kwargs)
+    hidden_states = norm_add(n1, attn_out, hidden_states)
+    return norm_add(n2, self.mlp(hidden_states), hidden_states)
+
+
+def use_olmo2_layer(model: torch.nn.Module) -> int:
+    """Patch Olmo2DecoderLayer modules whose forward is, statement for statement, the code `_olmo2_layer_forward` restates and whose
+    two norms are Olmo2RMSNorm.  DALM_NORM_KERNEL=0 disables.  Returns how many layers were patched."""
+    if _off("DALM_NORM_KERNEL"):
+        return 0
+
+    def two_post_norms(mod) -> bool:
+        return (all(_qk_norm_ok(getattr(mod, a, None), True, getattr(mod, "hidden_size", -1))
+                    for a in ("post_attention_layernorm", "post_feedforward_layernorm"))
+                and not hasattr(mod, "input_layernorm") and all(hasattr(mod, a) for a in ("self_attn", "mlp")))
+
+    return _install(model, ("Olmo2DecoderLayer",), two_post_norms, "olmo2-layer", _olmo2_layer_forward, keep="_dalm_orig_forward")
+
+
 def use_fused_residual_norm(model: torch.nn.Module) -> int:
     """Patch LlamaDecoderLayer / Qwen3DecoderLayer / ArceeDecoderLayer / GemmaDecoderLayer modules whose forward has the signature this
     file was written against (transformers 5.x; Qwen3's, Arcee's and Gemma's are also compared statement for statement); DALM_NORM_KERNEL=0
@@ -1107,3 +1207,14 @@ _SOURCE_GUARDS["qwen3-layer"] = (
                          and _body(src)[-len(_QWEN3_LAYER_BODY) - 1].startswith(")")), _RESTATED)
 _SOURCE_GUARDS["gemma-layer"] = _SOURCE_GUARDS["qwen3-layer"]       # GemmaDecoderLayer.forward: the same whole body, the same check
 _SOURCE_GUARDS["arcee-layer"] = _SOURCE_GUARDS["qwen3-layer"]       # ArceeDecoderLayer.forward likewise
+# Olmo2DecoderLayer.forward: the whole body, behind the signature
+_OLMO2_LAYER_BODY = ["residual = hidden_states", "hidden_states, _ = self.self_attn(", "hidden_states=hidden_states,",
+                     "attention_mask=attention_mask,", "position_ids=position_ids,", "past_key_values=past_key_values,",
+                     "use_cache=use_cache,", "position_embeddings=position_embeddings,", "**kwargs,", ")",
+                     "hidden_states = self.post_attention_layernorm(hidden_states)", "hidden_states = residual + hidden_states",
+                     "residual = hidden_states", "hidden_states = self.mlp(hidden_states)",
+                     "hidden_states = self.post_feedforward_layernorm(hidden_states)", "hidden_states = residual + hidden_states",
+                     "return hidden_states"]
+_SOURCE_GUARDS["olmo2-layer"] = (
+    lambda params, src: (params == _LLAMA_LAYER_PARAMS and _body(src)[-len(_OLMO2_LAYER_BODY):] == _OLMO2_LAYER_BODY
+                         and _body(src)[-len(_OLMO2_LAYER_BODY) - 1].startswith(")")), _RESTATED)

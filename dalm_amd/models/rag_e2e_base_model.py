@@ -17,8 +17,8 @@ from . import lora
 from .attention import use_hip_attention_backward
 from .fastpath import (use_bert_layer_kernels, use_capturable_falcon_heads, use_falcon_attention_kernels, use_falcon_layer_kernels,
                        use_fused_residual_norm, use_geglu_kernel, use_gemma_rms_norm, use_llama_attention_node, use_native_rms_norm,
-                       use_mpnet_attention_kernels, use_qwen3_attention_node, use_relu2_kernel, use_roberta_embeddings, use_roll_rope,
-                       use_swiglu_kernel)
+                       use_mpnet_attention_kernels, use_olmo2_attention_node, use_olmo2_layer, use_qwen3_attention_node, use_relu2_kernel,
+                       use_roberta_embeddings, use_roll_rope, use_swiglu_kernel)
 
 
 class Mode(Enum):
@@ -97,8 +97,10 @@ def decoder_only(lm, T: Optional[int] = None) -> bool:
 _ROW_WISE_PATHS = (use_native_rms_norm, use_roll_rope, use_swiglu_kernel, use_geglu_kernel, use_relu2_kernel, use_gemma_rms_norm,
                    use_fused_residual_norm)
 _RETRIEVER_PATHS = _ROW_WISE_PATHS + (use_hip_attention_backward,)
-_GENERATOR_PATHS = _ROW_WISE_PATHS + (use_capturable_falcon_heads, use_falcon_layer_kernels, use_falcon_attention_kernels,
-                                      use_hip_attention_backward, use_llama_attention_node, use_qwen3_attention_node)
+# (OLMo-2 is a generator only: its post-norm layer and its attention node are installed here, not on retrievers)
+_GENERATOR_PATHS = _ROW_WISE_PATHS + (use_olmo2_layer, use_capturable_falcon_heads, use_falcon_layer_kernels,
+                                      use_falcon_attention_kernels, use_hip_attention_backward, use_llama_attention_node,
+                                      use_qwen3_attention_node, use_olmo2_attention_node)
 
 
 def use_causal_retriever_fast_paths(lm) -> dict:
@@ -111,8 +113,8 @@ def use_causal_retriever_fast_paths(lm) -> dict:
 
 
 def use_generator_fast_paths(lm) -> dict:
-    """Every tower patch of a generator: the retriever's list, the three Falcon installers and the two rotary + attention
-    nodes.  Returns what each installer returned, by its name."""
+    """Every tower patch of a generator: the retriever's list, OLMo-2's post-norm layer, the three Falcon installers and the three
+    rotary + attention nodes.  Returns what each installer returned, by its name."""
     return {use.__name__: use(lm) for use in _GENERATOR_PATHS}
 
 

@@ -8,7 +8,8 @@ are the eager chain's (tests/test_tower_ops_gpu.py asserts equality, not closene
 
 Also here: RMSNorm with the residual add, Qwen3's head norm + rotary, Gemma's GeGLU and (1 + w) RMSNorm (`dalm_geglu_*`,
 `dalm_gemma_norm_*`: modeling_gemma.py `GemmaMLP.forward`, `GemmaRMSNorm.forward`), Arcee's ReLU^2 (`dalm_relu2_*`: modeling_arcee.py
-`ArceeMLP.forward`), and Falcon's layer ops.
+`ArceeMLP.forward`), OLMo-2's norm-then-add and row-wide q / k norm + rotary (`dalm_norm_add_*`, `dalm_row_norm_*`: modeling_olmo2.py),
+and Falcon's layer ops.
 
 GPU tensors only: the callers in `fastpath.py` keep transformers' own code for CPU tensors.
 """
@@ -478,6 +479,140 @@ def head_norm_weight_grad(g, x, rstd, live=None):
         B, _, T, _ = x.shape
         prod = prod.masked_fill((live == 0).view(B, 1, T, 1), 0.0)
     return prod.sum((0, 1, 2))
+
+
+# ---------------------------------------------------------------------------
+# OLMo-2: the norm AFTER the sub-block, inside the residual (dalm_norm_add_{fwd,bwd}), and q_norm / k_norm over the whole projection
+# width + rotary embedding (dalm_row_norm_rope_fwd / dalm_row_norm_bwd, bf16).  modeling_olmo2.py `Olmo2DecoderLayer.forward`,
+# `Olmo2Attention.forward`, `Olmo2RMSNorm.forward`: (w * (x.float() * rstd)).to(x.dtype) - the weight enters in f32, one rounding
+# ---------------------------------------------------------------------------
+def _f32_weight_ok(w: torch.Tensor, D: int) -> bool:
+    return (w.is_cuda and w.dim() == 1 and w.shape[0] == D and w.dtype in (torch.float32, torch.bfloat16) and w.is_contiguous()
+            and w.data_ptr() % 16 == 0)
+
+
+def norm_add_supported(x: torch.Tensor, res: torch.Tensor, w: torch.Tensor) -> bool:
+    """What `dalm_norm_add_*` take: x (the sub-block's output) and res (the residual) of one shape and dtype (f32 or bf16) on the
+    GPU, `rms_norm_supported`'s widths; the weight f32 or bf16 under either activation dtype (Olmo2RMSNorm multiplies in f32)."""
+    D = x.shape[-1]
+    vec = 4 if x.dtype == torch.float32 else 8
+    return (x.is_cuda and res.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and res.dtype == x.dtype and res.shape == x.shape
+            and _f32_weight_ok(w, D) and D % vec == 0 and D <= 64 * vec * 16)
+
+
+class _NormAdd(torch.autograd.Function):
+    """res + rmsnorm(x) * w with Olmo2RMSNorm's rounding, one launch; backward: one launch for x (`dalm_norm_add_bwd`), the
+    residual's gradient is the incoming one itself, the weight's is computed in torch when it is wanted."""
+
+    @staticmethod
+    def forward(ctx, x, res, w, eps, live=None):
+        D = x.shape[-1]
+        x2, r2 = _as_rows(x, D, x.dtype), _as_rows(res, D, x.dtype)
+        R = x2.shape[0]
+        if live is None:
+            live = live_rows.current(R, x2.device)
+        w = w.detach()
+        out = torch.empty_like(x2)
+        rstd = torch.empty(R, device=x2.device, dtype=torch.float32)
+        hip.call("dalm_norm_add_fwd", hip.ptr(x2), hip.ptr(r2), hip.ptr(w), hip.dtype_code(x2), hip.dtype_code(w), R, D, float(eps),
+                 hip.ptr(out), hip.ptr(rstd), hip.ptr(live), hip.stream())
+        # (the liveness vector is kept: the backward runs after the tower call's context, on autograd's thread)
+        ctx.save_for_backward(x2, w, rstd, *([live] if live is not None else []))
+        ctx.shape = x.shape
+        return out.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, w, rstd, *keep = ctx.saved_tensors
+        live = keep[0] if keep else None
+        R, D = x2.shape
+        dy2 = _as_rows(dy, D, x2.dtype)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x2)
+            hip.call("dalm_norm_add_bwd", hip.ptr(dy2), hip.ptr(x2), hip.ptr(w), hip.ptr(rstd), hip.dtype_code(x2), hip.dtype_code(w), R,
+                     D, hip.ptr(dx), hip.ptr(live), hip.stream())
+            dx = dx.view(ctx.shape)
+        dead = None if live is None else (live == 0).unsqueeze(1)
+        dw = _olmo2_weight_grad(dy2, x2, rstd.unsqueeze(1), dead, 0).to(w.dtype) if ctx.needs_input_grad[2] else None
+        return dx, dy, dw, None, None
+
+
+def _olmo2_weight_grad(g, x, rstd, dead, dims):
+    """Sum over `dims` of g * (x * rstd), rstd and dead (a bool mask of the dead rows, or None) broadcastable against g: the gradient of an
+    Olmo2RMSNorm weight.  xh is not rounded (the eager chain multiplies with the weight in f32 before its one rounding), and the
+    products and the sum are taken in f64: the result is rounded once, so an f32 weight's gradient is at least as close to the
+    truth as the eager chain's.  Only a trainable norm weight pays for it (not the LoRA step)."""
+    prod = g.double() * (x.double() * rstd.double())
+    if dead is not None:                           # dead rows: g and x are whatever their producers left
+        prod = prod.masked_fill(dead, 0.0)
+    return prod.sum(dims).float()
+
+
+def norm_add(x, res, w, eps, live=None):
+    """res + Olmo2RMSNorm(x) in one launch (one more in the backward).  live: uint8 row liveness; None: that of the tower call in
+    progress (dalm_amd/live_rows.py), if any."""
+    return _NormAdd.apply(x, res, w, eps, live)
+
+
+def row_norm_rope_supported(q, k, wq, wk, cos, sin) -> bool:
+    """What `dalm_row_norm_rope_fwd` takes: `head_norm_rope_supported`'s q / k / cos / sin, rows of at most 8192 elements, and norm
+    weights [Hq hd] / [Hk hd] in f32 or bf16 (one dtype for both)."""
+    if not (q.is_cuda and q.dtype == torch.bfloat16 and q.dim() == 4 and k.dim() == 4 and q.shape[-1] in _HEAD_NORM_DIMS):
+        return False
+    if not rope_supported(q, k, cos, sin):
+        return False
+    hd = q.shape[-1]
+    if not (_f32_weight_ok(wq, q.shape[1] * hd) and _f32_weight_ok(wk, k.shape[1] * hd) and wq.dtype == wk.dtype
+            and q.shape[1] * hd <= 8192 and k.shape[1] * hd <= 8192):
+        return False
+    views = all(t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:3]) and t.data_ptr() % 16 == 0 for t in (q, k))
+    tables = all(t.data_ptr() % 16 == 0 and t.stride(1) % 8 == 0 and (t.shape[0] == 1 or t.stride(0) % 8 == 0) for t in (cos, sin))
+    return views and tables and q.shape[0] * q.shape[2] * (q.shape[1] + k.shape[1]) * (hd // 8) < 2 ** 31
+
+
+def row_norm_rope(q, k, wq, wk, eps_q, eps_k, cos, sin, live=None):
+    """(rope(rmsnorm_row(q) * wq), rope(rmsnorm_row(k) * wk), rstd_q [B, T], rstd_k [B, T]) in one launch, the norms over all heads of
+    a token; q / k are read in place (column slices of a q|k|v GEMM output included).  live: uint8 [B T] row liveness; None: that
+    of the tower call in progress (dalm_amd/live_rows.py), if any.  Returns the vector it used as the fifth value: the backward
+    needs the same one."""
+    hip.require_gpu(q, k, wq, wk, cos, sin)
+    B, Hq, T, hd = q.shape
+    Hk = k.shape[1]
+    if live is None:
+        live = live_rows.current(B * T, q.device)
+    qo, ko = _token_major(B, Hq, T, hd, q), _token_major(B, Hk, T, hd, k)
+    rq = torch.empty(B, T, dtype=torch.float32, device=q.device)
+    rk = torch.empty(B, T, dtype=torch.float32, device=q.device)
+    cs = (C.c_int64 * 2)(cos.stride(0) if cos.shape[0] > 1 else 0, cos.stride(1))
+    hip.call("dalm_row_norm_rope_fwd", hip.ptr(q), hip.ptr(k), hip.ptr(wq), hip.ptr(wk), hip.dtype_code(wq), float(eps_q), float(eps_k),
+             hip.ptr(cos), hip.ptr(sin), B, T, Hq, Hk, hd, _strides3(q), _strides3(k), _strides3(qo), _strides3(ko), cs, hip.ptr(qo),
+             hip.ptr(ko), hip.ptr(rq), hip.ptr(rk), hip.ptr(live), hip.stream())
+    return qo, ko, rq, rk, live
+
+
+def row_norm_bwd(gq, gk, q, k, wq, wk, rstd_q, rstd_k, live=None):
+    """`head_norm_bwd` for the row-wide norms: gradients of the pre-norm q / k from those of the normed, un-rotated ones, in
+    [B, T, H, hd] memory order.  live: the vector the forward used."""
+    B, Hq, T, hd = q.shape
+    Hk = k.shape[1]
+    if gq.stride(-1) != 1 or any(s % 8 for s in gq.stride()[:3]):
+        gq = gq.contiguous()
+    if gk.stride(-1) != 1 or any(s % 8 for s in gk.stride()[:3]):
+        gk = gk.contiguous()
+    dq, dk = _token_major(B, Hq, T, hd, q), _token_major(B, Hk, T, hd, k)
+    hip.call("dalm_row_norm_bwd", hip.ptr(gq), hip.ptr(gk), hip.ptr(q), hip.ptr(k), hip.ptr(wq), hip.ptr(wk), hip.dtype_code(wq),
+             hip.ptr(rstd_q), hip.ptr(rstd_k), B, T, Hq, Hk, hd, _strides3(gq), _strides3(gk), _strides3(q), _strides3(k), _strides3(dq),
+             _strides3(dk), hip.ptr(dq), hip.ptr(dk), hip.ptr(live), hip.stream())
+    return dq, dk
+
+
+def row_norm_weight_grad(g, x, rstd, live=None):
+    """Gradient of a row-norm weight [H hd] (the kernels produce none): sum over (b, t) of g * xh, `_olmo2_weight_grad`'s arithmetic.
+    g, x: [B, H, T, hd]; rstd: [B, T]."""
+    B, H, T, hd = x.shape
+    dead = None if live is None else (live == 0).view(B, 1, T, 1)      # dead rows: g is whatever the attention backward left
+    return _olmo2_weight_grad(g, x, rstd.view(B, 1, T, 1), dead, (0, 2)).reshape(H * hd)
 
 
 # ---------------------------------------------------------------------------

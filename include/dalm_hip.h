@@ -586,6 +586,51 @@ int dalm_relu2_fwd(const void* y, void* act, int dtype, int64_t R, int64_t C, in
 int dalm_relu2_bwd(const void* d_act, const void* y, void* d_y, int dtype, int64_t R, int64_t C, int64_t ld_dact, int64_t ld_y,
                    int64_t ld_dy, const uint8_t* row_live, dalm_stream_t stream);
 
+/* OLMo-2 (modeling_olmo2.py; `model_type` "olmo2"): SwiGLU MLP and attention are Llama's, two row-wise formulas are not.
+ *   Olmo2RMSNorm:       (w * (x.float() * rsqrt(mean(x.float()^2) + eps))).to(x.dtype) - the weight enters in f32, ONE rounding
+ *   Olmo2DecoderLayer:  h = residual + norm(sub_block(h)) - the norm comes AFTER the sub-block, inside the residual
+ *   Olmo2Attention:     q_norm / k_norm over the WHOLE projection width (all heads of a token) in front of the head split and
+ *                       apply_rotary_pos_emb
+ * One entry point per direction; row_live [R] (norm_add) / [B T] (row_norm) bytes or NULL (Row liveness, above: nothing of a dead
+ * row is loaded, freshly written outputs hold zeros there, live rows receive the same bits as without the vector).  `w_dtype` is
+ * the weights' own dtype: f32 or bf16 under either activation dtype (the product with the weight is taken in f32 either way).
+ *   dalm_norm_add_fwd: x (the sub-block's output) and res (the residual) [R, D] row-major, w [D]; dtype DALM_F32 or DALM_BF16.
+ *        rstd [R] f32 = rsqrt(mean_d(f32(x)^2) + eps);  y = round(f32(w) (f32(x) rstd));  out = round(f32(res) + f32(y))
+ *        - the two rounding points of `residual + norm(x)` on tensors of `dtype`; only the summation of the mean is the kernel's
+ *        own (here and in dalm_row_norm_rope_fwd the squares are summed in f64 and rstd is rounded to f32 once).  Writes out and rstd.  The D rules of dalm_rms_norm_* (a multiple of 16 bytes of `dtype`, at most 8192
+ *        (bf16) / 4096 (f32): DALM_E_SHAPE).  R == 0: nothing to do, 0.
+ *   dalm_norm_add_bwd: g = f32(dy) f32(w);  xh = f32(x) rstd;  dx = round(rstd (g - xh mean_d(g xh))).  The residual's gradient is
+ *        dy itself: no copy, no kernel.  No weight gradient is produced.  With w_dtype == dtype this IS dalm_rms_norm_bwd_live
+ *        with dres == NULL (the same arithmetic, one rounding) and the entry point calls it; a weight of the other dtype runs
+ *        dalm_gemma_norm_bwd's kernel without its (1 + w).
+ *   dalm_row_norm_rope_fwd: bf16; the conventions of dalm_head_norm_rope_fwd (q / k [B, H, T, hd] views with element strides
+ *        {b, h, t} and a contiguous last dimension, column slices of one q|k|v GEMM output read in place; outputs wherever the
+ *        out strides say - the callers pass token-major [B, T, H, hd] memory; cos / sin [B or 1, T, hd]).  Per live (b, t):
+ *        rstd_q = rsqrt(mean over all Hq hd elements of x^2 + eps_q);  y = bf16(f32(wq[c]) (f32(x[c]) rstd_q)), c the column in
+ *        [0, Hq hd);  per head out = bf16(bf16(y cos) + bf16(rotate_half(y) sin));  the same for k over Hk hd with wk, eps_k.
+ *        rstd_q, rstd_k [B, T] f32 are kept for the backward.  A dead (b, t): nothing loaded, q_out / k_out / rstd zeros.
+ *   dalm_row_norm_bwd: gq / gk are the gradients of the normed, UN-rotated q / k - what dalm_attn_bwd / dalm_attn_gqa_bwd leave
+ *        when given cos / sin - and q / k the forward's inputs:  dx = bf16(rstd (g w - xh mean_D(g w xh))),  xh = x rstd in f32,
+ *        D = H hd: the mean runs across all heads of the token.  A dead (b, t): nothing loaded, dq / dk zeros.  No weight gradient.
+ *   Row norms: wq [Hq hd], wk [Hk hd]; hd = 64 or 128, Hq hd and Hk hd <= 8192, B T (Hq + Hk) hd / 8 < 2^31 (DALM_E_SHAPE);
+ *   16-byte aligned tensors, strides multiples of 8 (DALM_E_ALIGN).  One wave per token and tensor; a row wider than one wave's
+ *   16-byte pass (512 elements) is held as up to 16 chunks in registers, a partial last chunk included.
+ * The checks run before anything is enqueued. */
+int dalm_norm_add_fwd(const void* x, const void* res, const void* w, int dtype, int w_dtype, int64_t R, int64_t D, float eps,
+                      void* out, float* rstd, const uint8_t* row_live, dalm_stream_t stream);
+int dalm_norm_add_bwd(const void* dy, const void* x, const void* w, const float* rstd, int dtype, int w_dtype, int64_t R, int64_t D,
+                      void* dx, const uint8_t* row_live, dalm_stream_t stream);
+int dalm_row_norm_rope_fwd(const void* q, const void* k, const void* wq, const void* wk, int w_dtype, float eps_q, float eps_k,
+                           const void* cos, const void* sin, int64_t B, int64_t T, int64_t Hq, int64_t Hk, int64_t hd,
+                           const int64_t* q_strides, const int64_t* k_strides, const int64_t* qo_strides,
+                           const int64_t* ko_strides, const int64_t* cs_strides, void* q_out, void* k_out, float* rstd_q,
+                           float* rstd_k, const uint8_t* row_live, dalm_stream_t stream);
+int dalm_row_norm_bwd(const void* gq, const void* gk, const void* q, const void* k, const void* wq, const void* wk, int w_dtype,
+                      const float* rstd_q, const float* rstd_k, int64_t B, int64_t T, int64_t Hq, int64_t Hk, int64_t hd,
+                      const int64_t* gq_strides, const int64_t* gk_strides, const int64_t* q_strides, const int64_t* k_strides,
+                      const int64_t* dq_strides, const int64_t* dk_strides, void* dq, void* dk, const uint8_t* row_live,
+                      dalm_stream_t stream);
+
 /* Elementwise chains of a Falcon-7B decoder layer (transformers modeling_falcon.py FalconDecoderLayer.forward /
  * FalconMLP.forward / dropout_add, reached by the reference through self.generator_model(...),
  * dalm/models/rag_e2e_base_model.py:104-106; BASELINE.json config 5).  bf16 tensors, 16-byte aligned.

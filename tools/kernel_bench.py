@@ -538,6 +538,110 @@ def bench_gemma_norm(R, D, rounds=3):
     return out
 
 
+def bench_norm_add(R, D, rounds=3):
+    """OLMo-2's post-norm pair, `residual + Olmo2RMSNorm(x)`: `dalm_norm_add_fwd` / `dalm_norm_add_bwd` on [R, D] bf16 rows with a bf16
+    weight, and beside them - alternating, in the same process - the two forms they replace: transformers' Olmo2RMSNorm.forward (an
+    f32 chain) + the add, and F.rms_norm + the add (what `use_native_rms_norm` alone leaves: the unrouted model of today), each with
+    autograd's backward.  Algorithmic bytes: forward 3 R D elements (+ rstd), backward 3 R D (+ rstd; the residual's gradient is the
+    incoming one: no traffic)."""
+    import torch.nn.functional as F
+    from transformers.models.olmo2.modeling_olmo2 import Olmo2RMSNorm
+
+    from dalm_amd import hip
+    from dalm_amd.models import tower_ops
+
+    dev = torch.device("cuda:0")
+    x = torch.randn(R, D, device=dev, dtype=torch.bfloat16)
+    res = torch.randn(R, D, device=dev, dtype=torch.bfloat16)
+    gy = torch.randn_like(x)
+    norm = Olmo2RMSNorm(D, eps=1e-6).to(dev).to(torch.bfloat16).requires_grad_(False)
+    with torch.no_grad():
+        norm.weight.copy_(1.0 + 0.1 * torch.randn(D, device=dev))
+    w = norm.weight
+    assert tower_ops.norm_add_supported(x, res, w)
+    rstd = torch.rsqrt(x.float().pow(2).mean(-1) + 1e-6)
+    dx = torch.empty_like(x)
+    xd, rd = x.clone().requires_grad_(True), res.clone().requires_grad_(True)
+
+    def kernel_fwd():
+        with torch.no_grad():
+            return tower_ops.norm_add(x, res, w, 1e-6)
+
+    def kernel_bwd():
+        hip.call("dalm_norm_add_bwd", hip.ptr(gy), hip.ptr(x), hip.ptr(w), hip.ptr(rstd), hip.dtype_code(x), hip.dtype_code(w), R, D,
+                 hip.ptr(dx), None, hip.stream())
+
+    def native(a, b):
+        return b + F.rms_norm(a, (D,), w, 1e-6)
+
+    def no_grad(fn):
+        def run():
+            with torch.no_grad():
+                return fn(x, res)
+        return run
+
+    fns = {"kernel fwd (1 launch)": kernel_fwd, "kernel bwd (1 launch)": kernel_bwd,
+           "eager fwd (f32 chain + add)": no_grad(lambda a, b: b + norm(a)),
+           "eager fwd + autograd bwd": lambda: torch.autograd.grad(rd + norm(xd), (xd, rd), gy),
+           "native fwd (F.rms_norm + add)": no_grad(native),
+           "native fwd + autograd bwd": lambda: torch.autograd.grad(native(xd, rd), (xd, rd), gy)}
+    n = R * D * 2
+    out = _alternating(fns, {"kernel fwd (1 launch)": 3 * n + 4 * R, "kernel bwd (1 launch)": 3 * n + 4 * R,
+                             "eager fwd (f32 chain + add)": 3 * n, "eager fwd + autograd bwd": 6 * n,
+                             "native fwd (F.rms_norm + add)": 3 * n, "native fwd + autograd bwd": 6 * n}, rounds)
+    k = out["kernel fwd (1 launch)"]["s"] + out["kernel bwd (1 launch)"]["s"]
+    for other in ("eager", "native"):
+        e = out[f"{other} fwd + autograd bwd"]["s"]
+        out[f"kernel fwd + bwd against {other}"] = {"kernel_s": k, f"{other}_s": e, f"{other}_over_kernel": e / k}
+    return out
+
+
+def bench_row_norm_rope(B, T, Hq, Hk, hd, rounds=3):
+    """OLMo-2's q_norm / k_norm over the whole projection width + rotary embedding: `dalm_row_norm_rope_fwd` / `dalm_row_norm_bwd` on
+    the q | k column slices of one [B T, (Hq + 2 Hk) hd] bf16 buffer, and beside them - alternating, in the same process - what runs
+    without them for the same math: F.rms_norm x 2 over the rows (what `use_native_rms_norm` leaves of Olmo2RMSNorm) + the head views
+    + transformers' eager rotary chain, and autograd's backward of that.  Algorithmic bytes as `bench_head_norm_rope`, one rstd per
+    token and tensor."""
+    import torch.nn.functional as F
+    from transformers.models.olmo2.modeling_olmo2 import apply_rotary_pos_emb
+
+    from dalm_amd.models import tower_ops
+
+    dev = torch.device("cuda:0")
+    R, W = B * T, (Hq + 2 * Hk) * hd
+    buf = torch.randn(R, W, device=dev, dtype=torch.bfloat16)
+    q = buf[:, :Hq * hd].view(B, T, Hq, hd).transpose(1, 2)
+    k = buf[:, Hq * hd:(Hq + Hk) * hd].view(B, T, Hk, hd).transpose(1, 2)
+    wq, wk = (1 + 0.1 * torch.randn(Hq * hd, device=dev)).bfloat16(), (1 + 0.1 * torch.randn(Hk * hd, device=dev)).bfloat16()
+    ang = torch.rand(1, T, hd // 2, device=dev) * 6.28
+    cos, sin = torch.cat((ang.cos(), ang.cos()), -1).bfloat16(), torch.cat((ang.sin(), ang.sin()), -1).bfloat16()
+    assert tower_ops.row_norm_rope_supported(q, k, wq, wk, cos, sin)
+    _, _, rq, rk, _ = tower_ops.row_norm_rope(q, k, wq, wk, 1e-6, 1e-6, cos, sin)
+    gq = torch.randn(B, T, Hq, hd, device=dev, dtype=torch.bfloat16).transpose(1, 2)
+    gk = torch.randn(B, T, Hk, hd, device=dev, dtype=torch.bfloat16).transpose(1, 2)
+    qf, kf = buf[:, :Hq * hd].view(B, T, Hq * hd), buf[:, Hq * hd:(Hq + Hk) * hd].view(B, T, Hk * hd)     # what q_norm / k_norm see
+    qg, kg = qf.detach().clone().requires_grad_(True), kf.detach().clone().requires_grad_(True)        # dense leaves for autograd
+
+    def eager_fwd(a, b):
+        a, b = F.rms_norm(a, (Hq * hd,), wq, 1e-6), F.rms_norm(b, (Hk * hd,), wk, 1e-6)
+        return apply_rotary_pos_emb(a.view(B, T, Hq, hd).transpose(1, 2), b.view(B, T, Hk, hd).transpose(1, 2), cos, sin)
+
+    def eager_both():
+        oq, ok = eager_fwd(qg, kg)
+        return torch.autograd.grad((oq, ok), (qg, kg), (gq, gk))
+
+    fns = {"kernel fwd (1 launch)": lambda: tower_ops.row_norm_rope(q, k, wq, wk, 1e-6, 1e-6, cos, sin),
+           "kernel bwd (1 launch)": lambda: tower_ops.row_norm_bwd(gq, gk, q, k, wq, wk, rq, rk),
+           "eager fwd (rms_norm x2 + rotary chain)": lambda: eager_fwd(qf, kf),
+           "eager fwd + autograd bwd": eager_both}
+    n = R * (Hq + Hk) * hd * 2
+    out = _alternating(fns, {"kernel fwd (1 launch)": 2 * n + 8 * R, "kernel bwd (1 launch)": 3 * n + 8 * R,
+                             "eager fwd (rms_norm x2 + rotary chain)": 2 * n + 8 * R, "eager fwd + autograd bwd": 5 * n + 16 * R}, rounds)
+    k_s, e_s = out["kernel fwd (1 launch)"]["s"] + out["kernel bwd (1 launch)"]["s"], out["eager fwd + autograd bwd"]["s"]
+    out["kernel fwd + bwd against eager"] = {"kernel_s": k_s, "eager_s": e_s, "eager_over_kernel": e_s / k_s}
+    return out
+
+
 def bench_linear_live(members, halves):
     """dalm_linear_live against the tuned library GEMM at 4608 padded rows under the first mask of the step bench
     (tools/linear_live_bench.py holds the arms and the timing; its own run covers every mask)."""
@@ -638,6 +742,13 @@ def main():
     if args.only in ("", "relu2"):
         res["relu2 AFM-4.5B rows 4608 x 18432 bf16"] = bench_relu2(4608, 18432)
         res["relu2 rows 4608 x 2560 bf16"] = bench_relu2(4608, 2560)
+    # the headline batch's rows (18 x 256) at OLMo-2-7B's widths: hidden 4096, 32 x 128 heads (MHA); and OLMo-2-13B's hidden 5120
+    if args.only in ("", "norm_add"):
+        res["norm_add OLMo-2-7B rows 4608 x 4096 bf16 (norm + add)"] = bench_norm_add(4608, 4096)
+        res["norm_add OLMo-2-13B rows 4608 x 5120 bf16 (norm + add)"] = bench_norm_add(4608, 5120)
+    if args.only in ("", "row_norm_rope"):
+        res["row_norm_rope OLMo-2-7B generator rows 18x256, 32+32 heads x 128"] = bench_row_norm_rope(18, 256, 32, 32, 128)
+        res["row_norm_rope OLMo-2-7B packed rows 1x3008, 32+32 heads x 128"] = bench_row_norm_rope(1, 3008, 32, 32, 128)
     Path("gpurun_out").mkdir(exist_ok=True)
     Path("gpurun_out/kernel_bench.json").write_text(json.dumps(res, indent=1))
     print_results(res)
