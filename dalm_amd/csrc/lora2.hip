@@ -27,6 +27,7 @@
 // mask stays a function of the LOGICAL element index row * C + c: a slice draws the mask its contiguous copy would draw.  The
 // entry points without `_ld` pass ld = C.
 #include "lora_common.hpp"
+#include "lora2_plan.hpp"
 
 namespace dalm {
 namespace {
@@ -542,31 +543,6 @@ __global__ __launch_bounds__(256, 2) void lora2_colacc_kernel(
   }
 }
 
-// ---- launch geometry ----
-struct ColaccGeom { int rows_per_split, S, slabs; size_t lds; int bits_off, live_off; };
-inline ColaccGeom colacc_geom(int64_t R, int64_t C, int rank, int nt, int nprob) {
-  ColaccGeom g;
-  g.slabs = static_cast<int>((C + 63) / 64);
-  int64_t S = (512 + static_cast<int64_t>(g.slabs) * nprob - 1) / (static_cast<int64_t>(g.slabs) * nprob);
-  const int64_t max_s = (R + 63) / 64;
-  if (S > max_s) S = max_s;
-  if (S < 1) S = 1;
-  int64_t rows = (R + S - 1) / S;
-  const int64_t cap = 16384 / (static_cast<int64_t>(nt) * rank);      // z stage <= 64 KB
-  if (rows > cap) rows = cap;
-  rows = (rows + 31) / 32 * 32;
-  g.rows_per_split = static_cast<int>(rows);
-  g.S = static_cast<int>((R + rows - 1) / rows);
-  const size_t stage = static_cast<size_t>(nt) * rows * rank * sizeof(float);
-  const size_t red = static_cast<size_t>(4) * 8 * nt * 8 * rank * sizeof(float);
-  g.lds = stage > red ? stage : red;
-  g.bits_off = static_cast<int>(g.lds);
-  g.lds += static_cast<size_t>(nt) * rows * 8;                          // the mask stage (used when the call carries masks)
-  g.live_off = static_cast<int>(g.lds);
-  g.lds += static_cast<size_t>(rows);                                   // the rows' liveness bytes (used when the call carries them)
-  return g;
-}
-
 }  // namespace
 }  // namespace dalm
 
@@ -647,22 +623,13 @@ extern "C" int dalm_lora2_rankupd_ld(void* y0, void* y1, const float* z0, const 
   const unsigned char* ba0 = static_cast<const unsigned char*>(bits0);
   const unsigned char* ba1 = static_cast<const unsigned char*>(two ? bits1 : bits0);
   const int Ri = static_cast<int>(R), Ci = static_cast<int>(C);
-  const int64_t slabs = (C + 511) / 512, nprob = mode == 3 ? 2 : 1;
-  // one resident round of workgroups (2 per CU with two terms' W slices in registers, 3 with one): every workgroup pays its W
-  // loads and mask stage once (1536 workgroups of 24 rows measured no faster than round 4's kernel)
-  int64_t S = (mode == 2 ? 512 : 768) / (slabs * nprob);
-  const int64_t max_s = (R + 3) / 4, min_s = (R + 255) / 256;       // at most 256 rows per workgroup (the LDS mask stage)
-  if (S > max_s) S = max_s;
-  if (S < min_s) S = min_s;
-  if (S < 1) S = 1;
-  int64_t rows = ((R + S - 1) / S + 3) / 4 * 4;
-  const int rows_per_wg = static_cast<int>(rows);
-  S = (R + rows - 1) / rows;
-  DALM_REQUIRE(S <= 65535, DALM_E_SHAPE, "too many rows for one launch");
-  const dim3 grid(static_cast<unsigned>(slabs), static_cast<unsigned>(S), static_cast<unsigned>(nprob));
+  const RankupdPlan pl = rankupd_plan(R, C, mode, bits);            // csrc/lora2_plan.hpp
+  DALM_REQUIRE(pl.ok, DALM_E_SHAPE, "too many rows for one launch");
+  const int rows_per_wg = pl.rows_per_wg;
+  const dim3 grid(static_cast<unsigned>(pl.slabs), static_cast<unsigned>(pl.S), static_cast<unsigned>(pl.nprob));
   hipStream_t s = as_stream(stream);
-  const bool stage = bits && C % 128 == 0;
-  const size_t lds = stage ? static_cast<size_t>(mode == 2 ? 2 : 1) * rows_per_wg * 64 : 0;
+  const bool stage = pl.stage;
+  const size_t lds = pl.lds;
 #define DALM_RU2(RK, NT, BT, TY, ST) hipLaunchKernelGGL((lora2_rankupd_kernel<RK, NT, BT, TY, ST>), grid, dim3(256), lds, s, ya0, ya1, \
     z0, za1, W0, Wa1, ba0, ba1, Ri, Ci, rows_per_wg, scale, row_live, static_cast<int>(ld))
 #define DALM_RU2_B(RK, NT, TY) do { if (stage) DALM_RU2(RK, NT, true, TY, true); else if (bits) DALM_RU2(RK, NT, true, TY, false); \
@@ -689,12 +656,23 @@ extern "C" int dalm_lora2_rankupd(void* y0, void* y1, const float* z0, const flo
 
 extern "C" size_t dalm_lora2_colacc_workspace_bytes(int64_t R, int64_t C, int rank, int mode) {
   if (R <= 0 || C <= 0 || rank <= 0 || mode < 1 || mode > 3) return 0;
-  const ColaccGeom g = colacc_geom(R, C, rank, mode == 2 ? 2 : 1, mode == 3 ? 2 : 1);
-  return static_cast<size_t>(2) * g.S * C * rank * sizeof(float);
+  return colacc_plan(R, C, rank, mode).ws_bytes;
 }
 extern "C" size_t dalm_lora2_colacc_ticket_words(int64_t C, int mode) {
   if (C <= 0) return 0;
-  return static_cast<size_t>((C + 63) / 64) * (mode == 3 ? 2 : 1);
+  return colacc_plan(1, C, 8, mode).ticket_words;
+}
+// which geometry a shape gets (tests assert the arm they are there for): 0 for a shape the launchers reject
+extern "C" int dalm_lora2_rankupd_rows_per_wg(int64_t R, int64_t C, int mode) {
+  if (R <= 0 || C <= 0 || C % 8 != 0 || R > 0x7fffffffll || C > 0x7fffffffll || mode < 1 || mode > 3) return 0;
+  const RankupdPlan pl = rankupd_plan(R, C, mode, false);
+  return pl.ok ? pl.rows_per_wg : 0;
+}
+extern "C" int dalm_lora2_colacc_rows_per_split(int64_t R, int64_t C, int rank, int mode) {
+  if (R <= 0 || C <= 0 || C % 8 != 0 || R > 0x7fffffffll || C > 0x7fffffffll || mode < 1 || mode > 3) return 0;
+  if ((rank != 8 && rank != 16) || (mode == 2 && rank != 8)) return 0;
+  const ColaccPlan g = colacc_plan(R, C, rank, mode);
+  return g.ok ? g.rows_per_split : 0;
 }
 
 extern "C" int dalm_lora2_colacc_ld(const void* x0, const void* x1, const float* z0, const float* z1, const void* bits0,
@@ -710,8 +688,8 @@ extern "C" int dalm_lora2_colacc_ld(const void* x0, const void* x1, const float*
   DALM_REQUIRE(ws_bytes >= dalm_lora2_colacc_workspace_bytes(R, C, rank, mode), DALM_E_WORKSPACE, "workspace too small");
   const bool bits = bits0 != nullptr;
   DALM_REQUIRE(!two || ((bits1 != nullptr) == bits), DALM_E_NULL, "either both terms carry a mask or neither");
-  const ColaccGeom g = colacc_geom(R, C, rank, mode == 2 ? 2 : 1, mode == 3 ? 2 : 1);
-  DALM_REQUIRE(g.S <= 65535, DALM_E_SHAPE, "too many rows for one launch");
+  const ColaccPlan g = colacc_plan(R, C, rank, mode);                // csrc/lora2_plan.hpp
+  DALM_REQUIRE(g.ok, DALM_E_SHAPE, "too many rows for one launch");
   const bf16_t* xa0 = static_cast<const bf16_t*>(x0);
   const bf16_t* xa1 = static_cast<const bf16_t*>(mode == 3 ? x1 : x0);
   const float* za1 = two ? z1 : z0;
@@ -720,7 +698,7 @@ extern "C" int dalm_lora2_colacc_ld(const void* x0, const void* x1, const float*
   float* oa1 = two ? out1 : out0;
   unsigned long long* part = static_cast<unsigned long long*>(ws);
   const int Ri = static_cast<int>(R), Ci = static_cast<int>(C);
-  const dim3 grid(static_cast<unsigned>(g.slabs), static_cast<unsigned>(g.S), mode == 3 ? 2u : 1u);
+  const dim3 grid(static_cast<unsigned>(g.slabs), static_cast<unsigned>(g.S), static_cast<unsigned>(g.nprob));
   hipStream_t s = as_stream(stream);
   const bool stage = bits && C % 64 == 0;
 #define DALM_CA2(RK, NT, BT, TX, ST) hipLaunchKernelGGL((lora2_colacc_kernel<RK, NT, BT, TX, ST>), grid, dim3(256), g.lds, s, xa0, xa1, \

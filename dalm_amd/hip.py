@@ -191,6 +191,9 @@ SIGNATURES = {
     "dalm_lora2_rankupd_ld": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _f32, _int, _vp, _i64, _vp]),
     "dalm_lora2_colacc_ld": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _f32, _int, _vp, _sz, _vp, _vp, _i64,
                                     _vp]),
+    # host-only queries of the launch geometry (csrc/lora2_plan.hpp)
+    "dalm_lora2_rankupd_rows_per_wg": (_int, [_i64, _i64, _int]),
+    "dalm_lora2_colacc_rows_per_split": (_int, [_i64, _i64, _int, _int]),
     # padded step: stable partition of the row-liveness vector and the frozen-projection GEMM over the live rows
     "dalm_row_partition": (_int, [_vp, _i64, _vp, _vp, _vp]),
     "dalm_linear_live": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _int, _vp]),

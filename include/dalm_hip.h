@@ -888,6 +888,11 @@ int dalm_lora2_rankupd_ld(void* y0, void* y1, const float* z0, const float* z1, 
 int dalm_lora2_colacc_ld(const void* x0, const void* x1, const float* z0, const float* z1, const void* bits0, const void* bits1,
                          float* out0, float* out1, int64_t R, int64_t C, int rank, float scale, int mode, void* ws,
                          size_t ws_bytes, uint32_t* tickets, const uint8_t* row_live, int64_t ld, dalm_stream_t stream);
+/* Host-only queries of the launch geometry (csrc/lora2_plan.hpp): the rows one workgroup of rankupd updates (a multiple of 4, at
+ * most 256) and the rows of one row split of colacc (a multiple of 32; its LDS stages stay within 64 KB).  0 for a shape the
+ * launchers reject.  Tests use them to assert which arm of the geometry a shape takes. */
+int dalm_lora2_rankupd_rows_per_wg(int64_t R, int64_t C, int mode);
+int dalm_lora2_colacc_rows_per_split(int64_t R, int64_t C, int rank, int mode);
 
 /* ---- round 5: backward of the fused lm_head + marginalised CE ---------------------------------------
  * Replaces, for a FROZEN bias-free head,   logits = lm_head(hidden); loss(logits).backward()

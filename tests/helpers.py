@@ -140,6 +140,96 @@ def assert_rows_close(name, got, torch_got, ref64, record=None):
     return rep
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# dalm_lora2_*: per-element rules (tests/test_lora2_forms_gpu.py, tests/test_lora2_rules.py).  Every bound is the worst case of
+# the arithmetic in dalm_amd/csrc/lora2.hip, in units of the float64 sum of magnitudes of the element's own terms - never a
+# measurement.  EVERY element is compared; an element whose bound is zero (a dead row, an all-zero sum) must be exact.
+# ---------------------------------------------------------------------------------------------------------------------------
+U_F32 = 2.0 ** -24      # unit roundoff of f32, round to nearest
+U_BF16 = 2.0 ** -8      # of bf16 (8 significant bits)
+
+
+def unpack_bits(bits, C):
+    """uint8 [R, C / 8] keep bits -> bool [R, C]: bit e of byte c = element 8 c + e (the layout dalm_lora2_rowdot writes)."""
+    sh = torch.arange(8, device=bits.device, dtype=torch.int32)
+    return ((bits.to(torch.int32).unsqueeze(-1) >> sh) & 1).bool().reshape(bits.shape[0], -1)[:, :C]
+
+
+def _worst(err, bound, exact_bad):
+    """max over ALL elements of err / bound (inf where an element that must be exact is not), and where."""
+    ratio = torch.nan_to_num(err / bound.clamp_min(1e-300), nan=float("inf"))      # bound 0: 0 / tiny = 0, anything else huge
+    ratio = ratio.masked_fill(exact_bad, float("inf"))
+    flat = int(ratio.argmax())
+    return {"ratio": float(ratio.flatten()[flat]), "at": [flat // ratio.shape[1], flat % ratio.shape[1]], "checked": ratio.numel()}
+
+
+def lora2_rowdot_report(got, x, W, scale, keep=None, live=None):
+    """z [R, rank] f32 = scale * (keep o x) W^T, x bf16 [R, K], W f32 [rank, K].  The kernel splits W into bf16 hi + bf16 lo (what is
+    left of W is at most 2^-16 |W|) and accumulates in f32 (fewer than K roundings per element):
+        |got - ref| <= (2^-16 + K 2^-24) |scale| sum_k |x_k| |W_k|          a dead row: exactly zero."""
+    x64 = x.double()
+    if keep is not None:
+        x64 = x64 * keep
+    if live is not None:
+        x64 = x64 * (live != 0).unsqueeze(1)
+    ref = scale * (x64 @ W.double().t())
+    bound = (2.0 ** -16 + x.shape[1] * U_F32) * abs(scale) * (x64.abs() @ W.double().abs().t())
+    assert got.shape == ref.shape and got.dtype == torch.float32
+    return _worst((got.double() - ref).abs(), bound, torch.zeros_like(bound, dtype=torch.bool))
+
+
+def lora2_rankupd_report(got, y, terms, scale, live=None):
+    """y [R, C] bf16 += scale * sum_t keep_t o (z_t W_t);  terms: [(z [R, rank] f32, W [rank, C] f32, keep bool [R, C] or None)].
+    Per term the kernel runs `rank` fmas and one fma onto y, all f32, then rounds ONCE to bf16:
+        |got - ref| <= 2^-8 |ref| + (rank + 1 + terms) 2^-24 (|y| + |scale| sum_t keep_t sum_j |z_tj| |W_tj|)
+    (one term: (rank + 2) 2^-24).  An element whose every keep bit is 0, and every element of a dead row, is y BIT FOR BIT."""
+    y64 = y.double()
+    upd, mag = torch.zeros_like(y64), torch.zeros_like(y64)
+    touched = torch.zeros_like(y64, dtype=torch.bool)
+    for z, W, keep in terms:
+        t, a = z.double() @ W.double(), z.double().abs() @ W.double().abs()
+        if keep is not None:
+            t, a = t * keep, a * keep
+        upd += t
+        mag += a
+        touched |= keep if keep is not None else torch.ones_like(touched)
+    if live is not None:
+        lv = (live != 0).unsqueeze(1)
+        upd, mag, touched = upd * lv, mag * lv, touched & lv
+    rank = terms[0][0].shape[1]
+    ref = y64 + scale * upd
+    bound = U_BF16 * ref.abs() + (rank + 1 + len(terms)) * U_F32 * (y64.abs() + abs(scale) * mag)
+    assert got.shape == ref.shape and got.dtype == torch.bfloat16
+    exact_bad = ~touched & (got.view(torch.int16) != y.view(torch.int16))
+    return _worst((got.double() - ref).abs(), bound, exact_bad)
+
+
+def lora2_colacc_report(got, x, z, scale, rows_per_split, keep=None, live=None):
+    """out [rank, C] f32 = scale * sum_row keep o x[row, c] z[row, j], x bf16 [R, C], z f32 [R, rank].  The stated rule is
+        |got - ref| <= R 2^-24 |scale| sum_row |x| |z|;
+    the kernel's own depth is smaller: a thread adds every 32nd row of its split (rows_per_split / 32 fmas), then 3 adds over
+    row lanes, 2 over waves, S over the splits and the multiplication with scale - depth = rows_per_split / 32 + S + 6 roundings.
+    The smaller of the two is applied (for R < depth the first would not be a worst case: such shapes are not for this rule)."""
+    R = x.shape[0]
+    S = -(-R // rows_per_split)
+    depth = -(-rows_per_split // 32) + S + 6
+    assert R >= depth, "the rule is derived for R >= rows_per_split / 32 + S + 6"
+    x64 = x.double()
+    if keep is not None:
+        x64 = x64 * keep
+    if live is not None:
+        x64 = x64 * (live != 0).unsqueeze(1)
+    ref = scale * (z.double().t() @ x64)
+    bound = min(R, depth) * U_F32 * abs(scale) * (z.double().abs().t() @ x64.abs())
+    assert got.shape == ref.shape and got.dtype == torch.float32
+    return _worst((got.double() - ref).abs(), bound, torch.zeros_like(bound, dtype=torch.bool))
+
+
+def assert_lora2(name, rep):
+    assert rep["ratio"] <= 1.0, f"{name}: error / bound = {rep['ratio']:.3e} at (row, column) = {tuple(rep['at'])}, {rep['checked']} elements checked"
+    return rep["ratio"]
+
+
 def synth_batch(seed, B, D, Tg, V, *, pad_side="right", dtype=torch.float32, logit_gain=1.0, full_mask=False):
     """Seeded synthetic (q, p, logits, ids, mask, qlen) as SURVEY section 8d describes."""
     g = torch.Generator().manual_seed(seed)

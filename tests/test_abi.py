@@ -28,7 +28,7 @@ def test_header_declares_expected_entry_points():
     names = header_functions()
     for required in ("dalm_marg_ce_fwd", "dalm_marg_ce_bwd", "dalm_sim_rowstats", "dalm_sim_grad",
                      "dalm_sim_matmul", "dalm_pool_l2norm_fwd", "dalm_pool_l2norm_bwd", "dalm_version",
-                     "dalm_last_error_string"):
+                     "dalm_last_error_string", "dalm_lora2_rankupd_rows_per_wg", "dalm_lora2_colacc_rows_per_split"):
         assert required in names
 
 
@@ -202,3 +202,18 @@ def test_gemm256_launch_plans(tmp_path):
     shapes.write_text("".join(f"{m} {n} {D}\n" for m, n, D in GRID))
     r = run_host_check(tmp_path, "gemm256_plan_check", shapes)
     assert r.returncode == 0 and r.stdout.strip() == f"gemm256 plans ok: {len(GRID)} shapes", (r.returncode, r.stdout, r.stderr)
+
+
+def test_lora2_launch_plans(tmp_path):
+    """csrc/lora2_plan.hpp, the launch geometry of the stacked LoRA kernels, is host-only C++17 as well: tests/lora2_plan_check.cpp
+    checks, over the grid of tests/test_lora2_sizes.py and every row count up to its largest, that rankupd's workgroups hold a
+    multiple of 4 rows and at most 256, that colacc's splits hold a multiple of 32 rows and never ask for more than 64 KB of LDS,
+    that both cover the rows exactly, the workspace and ticket sizes, and the literal plans of the benchmark's shape and of the
+    shapes tests/test_lora2_forms_gpu.py is built on."""
+    from test_lora2_sizes import GRID
+
+    shapes = tmp_path / "shapes.txt"
+    shapes.write_text("".join(f"{R} {C}\n" for R, C in GRID))
+    r = run_host_check(tmp_path, "lora2_plan_check", shapes)
+    want = f"lora2 plans ok: {len(GRID)} shapes, rows 1..{max(R for R, _ in GRID)} at {len({C for _, C in GRID})} widths"
+    assert r.returncode == 0 and r.stdout.strip() == want, (r.returncode, r.stdout, r.stderr)

@@ -90,7 +90,9 @@ def _nan_dead(t, dead):
 def _check(run, rowwise, other, live, fresh, inplace=(), bits=()):
     """run(**inputs, live=vec or None) -> dict of [R, ...] outputs.  `rowwise`: inputs with one row per liveness byte; `other`:
     weights and the like.  `fresh`: outputs that must be zero in dead rows; `inplace`: outputs that keep their input's dead rows
-    (name -> input name); `bits`: keep-bit outputs, which need not be written for dead rows."""
+    (name -> input name); `bits`: keep-bit outputs, which need not be written for dead rows.  The row count is the vector's
+    (tests/test_lora2_forms_gpu.py brings its own shapes)."""
+    R = live.shape[0]
     keep = live != 0
     dead = ~keep
     ref = run(**{k: v.clone() for k, v in rowwise.items()}, **other, live=None)
