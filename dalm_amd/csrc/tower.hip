@@ -18,7 +18,8 @@
 // Algorithmic bytes: rope 2 * (|q| + |k|) * el (+ cos/sin, shared by all heads); swiglu forward 3 * n * el, backward 5 * n * el.
 // Further down: RMSNorm with the residual add (dalm_rms_norm_*), Qwen3's head norm + rotary (dalm_head_norm_*), and Gemma's two
 // formulas - GeGLU and the (1 + w) RMSNorm (dalm_geglu_*, dalm_gemma_norm_*) - Arcee's ReLU^2 (dalm_relu2_*), and OLMo-2's norm-then-add
-// and row-wide q / k norm + rotary (dalm_norm_add_*, dalm_row_norm_*), each with its own comment block.
+// and row-wide q / k norm + rotary (dalm_norm_add_*, dalm_row_norm_*), and Granite's scaled residual add with and without the norm
+// behind it (dalm_rms_norm_scaled_*, dalm_scale_add), each with its own comment block.
 #include "dispatch.hpp"
 #include "relu2_math.hpp"
 #include "swiglu_math.hpp"
@@ -1790,6 +1791,268 @@ extern "C" int dalm_row_norm_bwd(const void* gq, const void* gk, const void* q, 
   by_exact<64, 128>(static_cast<int>(hd), [&](auto width) {
     by_ceil<1, 2, 4, 8, 16>(nch, [&](auto n) {
       hipLaunchKernelGGL((row_norm_bwd_kernel<width, n>), grid, dim3(256), 0, as_stream(stream), p);
+    });
+  });
+  return check_launch(__func__);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Granite (modeling_granite.py): a Llama layer whose sub-block outputs enter the residual stream scaled,
+//   hidden_states = residual + hidden_states * residual_multiplier        (twice per GraniteDecoderLayer.forward)
+// with the multiplier a Python float: torch forms the product in f32 and rounds it to the tensor dtype, then adds and rounds again.
+//   scaled norm forward :  t = rb(delta mult);  h = rb(x + t);  rstd = rsqrt(mean(h^2) + eps);  y = rb(w rb(h rstd))
+//   scaled norm backward:  g = dy w;  xh = h rstd;  dx = rb(rstd (g - xh mean(g xh)) [+ dres]);  ddelta = rb(dx mult), dx as rounded -
+//                          what autograd's backward of the eager multiply makes of the rounded dx, in the same launch
+//   scale_add           :  out = rb(res + rb(x mult)), or rb(x mult) without res: the layer's trailing add, its backward, and the
+//                          division of the logits by logits_scaling
+// With mult == 1 the two norm kernels give the bits of dalm_rms_norm_fwd_live / dalm_rms_norm_bwd_live: the sums run in their order,
+// and what the compiler fuses there - fma(-xh, mean, g) and fma(rstd, ., dres) - is written out here, with contraction off for the
+// rest (in f32 a fused delta mult + x would round once less than the eager pair).
+// One wave per row; the row's streams are requested as raw 16-byte chunks before the reduction (rms_norm_bwd_v2_kernel) and h stays
+// in registers, encoded, between the reduction and the scaling.  scale_add has no reduction: a flat grid over 16-byte vectors, four
+// in flight per lane.  Algorithmic bytes: forward 4 R D el, backward (4 or 5) R D el, scale_add (2 or 3) R D el.
+// ---------------------------------------------------------------------------------------------------
+namespace {
+
+__device__ __forceinline__ uint4 enc16(const float (&x)[8]) { return enc8(x); }
+__device__ __forceinline__ uint4 enc16(const float (&x)[4]) {
+  return make_uint4(__float_as_uint(x[0]), __float_as_uint(x[1]), __float_as_uint(x[2]), __float_as_uint(x[3]));
+}
+
+template <typename T, int NCH>
+__global__ __launch_bounds__(256) void rms_norm_scaled_fwd_kernel(const T* __restrict__ x, const T* __restrict__ delta, float mult,
+                                                                  const T* __restrict__ w, T* __restrict__ h_out, T* __restrict__ y,
+                                                                  float* __restrict__ rstd_out, int R, int D, float eps,
+                                                                  const unsigned char* __restrict__ live) {
+#pragma clang fp contract(off)
+  constexpr int N = Vec16<T>::VEC;
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= R) return;
+  const int64_t base = static_cast<int64_t>(row) * D;
+  if (live && !live[row]) {                      // a dead row (wave-uniform): nothing is read, h, y and rstd leave as zeros
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int d = (c * 64 + lane) * N;
+      if (d < D) {
+        *reinterpret_cast<uint4*>(h_out + base + d) = zero16();
+        *reinterpret_cast<uint4*>(y + base + d) = zero16();
+      }
+    }
+    if (lane == 0) rstd_out[row] = 0.f;
+    return;
+  }
+  uint4 rx[NCH], rd[NCH];                        // both streams of the row in flight before the reduction
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * N;
+    const bool ok = d < D;
+    rx[c] = ok ? *reinterpret_cast<const uint4*>(x + base + d) : zero16();
+    rd[c] = ok ? *reinterpret_cast<const uint4*>(delta + base + d) : zero16();
+  }
+  float ss = 0.f;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * N;
+    if (d >= D) continue;
+    float v[N], dl[N];
+    dec16(rx[c], v); dec16(rd[c], dl);
+#pragma unroll
+    for (int e = 0; e < N; ++e) v[e] += Vec16<T>::rb(dl[e] * mult);
+    rx[c] = enc16(v);                            // h, rounded: the chunk is kept encoded for the second pass
+    *reinterpret_cast<uint4*>(h_out + base + d) = rx[c];
+    dec16(rx[c], v);
+#pragma unroll
+    for (int e = 0; e < N; ++e) ss = fmaf(v[e], v[e], ss);
+  }
+  ss = wave_sum(ss);
+  const float rstd = rsqrtf(ss / static_cast<float>(D) + eps);
+  if (lane == 0) rstd_out[row] = rstd;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * N;
+    if (d >= D) continue;
+    float v[N], wv[N], o[N];
+    dec16(rx[c], v);
+    Vec16<T>::load(w + d, wv);
+#pragma unroll
+    for (int e = 0; e < N; ++e) o[e] = wv[e] * Vec16<T>::rb(v[e] * rstd);
+    Vec16<T>::store(y + base + d, o);
+  }
+}
+
+// EARLY (rows of up to 8 chunks per lane): the weight and the residual-path gradient are requested with dy and h, four streams in
+// flight; wider rows load them where they are used, as rms_norm_bwd_kernel does, and keep two streams in registers.
+template <typename T, int NCH, bool ADD>
+__global__ __launch_bounds__(256) void rms_norm_scaled_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ h,
+                                                                  const T* __restrict__ w, const float* __restrict__ rstd_in,
+                                                                  const T* __restrict__ dres, float mult, T* __restrict__ dx,
+                                                                  T* __restrict__ ddelta, int R, int D,
+                                                                  const unsigned char* __restrict__ live) {
+#pragma clang fp contract(off)
+  constexpr int N = Vec16<T>::VEC;
+  constexpr bool EARLY = NCH <= 8;
+  constexpr int NE = EARLY ? NCH : 1;
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= R) return;
+  const int64_t base = static_cast<int64_t>(row) * D;
+  if (live && !live[row]) {                      // a dead row (wave-uniform): dx and ddelta leave as zeros
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int d = (c * 64 + lane) * N;
+      if (d < D) {
+        *reinterpret_cast<uint4*>(dx + base + d) = zero16();
+        *reinterpret_cast<uint4*>(ddelta + base + d) = zero16();
+      }
+    }
+    return;
+  }
+  uint4 rg[NCH], rh[NCH], rr[NE], rw[NE];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * N;
+    const bool ok = d < D;
+    rg[c] = ok ? *reinterpret_cast<const uint4*>(dy + base + d) : zero16();
+    rh[c] = ok ? *reinterpret_cast<const uint4*>(h + base + d) : zero16();
+    if constexpr (EARLY) {
+      if constexpr (ADD) rr[c] = ok ? *reinterpret_cast<const uint4*>(dres + base + d) : zero16();
+      rw[c] = ok ? *reinterpret_cast<const uint4*>(w + d) : zero16();
+    }
+  }
+  const float rstd = rstd_in[row];
+  float dot = 0.f;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * N;
+    float g[N], xh[N], wv[N];
+    dec16(rg[c], g); dec16(rh[c], xh);           // past the row: zeros, which leave the sum as it is
+    if constexpr (EARLY) dec16(rw[c], wv);
+    else dec16(d < D ? *reinterpret_cast<const uint4*>(w + d) : zero16(), wv);
+#pragma unroll
+    for (int e = 0; e < N; ++e) dot = fmaf(g[e] * wv[e], xh[e] * rstd, dot);
+  }
+  dot = wave_sum(dot) / static_cast<float>(D);
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * N;
+    if (d >= D) continue;
+    float g[N], xh[N], wv[N], o[N];
+    dec16(rg[c], g); dec16(rh[c], xh);
+    if constexpr (EARLY) dec16(rw[c], wv);
+    else Vec16<T>::load(w + d, wv);
+#pragma unroll
+    for (int e = 0; e < N; ++e) o[e] = fmaf(-(xh[e] * rstd), dot, g[e] * wv[e]);
+    if constexpr (ADD) {
+      float r[N];
+      if constexpr (EARLY) dec16(rr[c], r);
+      else Vec16<T>::load(dres + base + d, r);
+#pragma unroll
+      for (int e = 0; e < N; ++e) o[e] = fmaf(rstd, o[e], r[e]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < N; ++e) o[e] *= rstd;
+    }
+    const uint4 q = enc16(o);                    // dx, rounded
+    *reinterpret_cast<uint4*>(dx + base + d) = q;
+    dec16(q, o);
+#pragma unroll
+    for (int e = 0; e < N; ++e) o[e] *= mult;
+    Vec16<T>::store(ddelta + base + d, o);
+  }
+}
+
+constexpr int kScaleAddVecs = 4;                 // 16-byte vectors per lane, all requested before the first is used
+
+template <typename T, bool RES>
+__global__ __launch_bounds__(256) void scale_add_kernel(const T* __restrict__ res, const T* __restrict__ x, float mult,
+                                                        T* __restrict__ out, unsigned int nvec, unsigned int vecs_per_row,
+                                                        const unsigned char* __restrict__ live) {
+#pragma clang fp contract(off)
+  constexpr int N = Vec16<T>::VEC, K = kScaleAddVecs;
+  const unsigned int i0 = blockIdx.x * (256u * K) + threadIdx.x;
+  uint4 rx[K], rr[K];
+  bool in[K], lv[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const unsigned int i = i0 + k * 256u;
+    in[k] = i < nvec;
+    lv[k] = in[k] && (!live || live[i / vecs_per_row]);
+    const int64_t at = static_cast<int64_t>(i) * N;
+    rx[k] = lv[k] ? *reinterpret_cast<const uint4*>(x + at) : zero16();
+    if constexpr (RES) rr[k] = lv[k] ? *reinterpret_cast<const uint4*>(res + at) : zero16();
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if (!in[k]) continue;
+    const int64_t at = static_cast<int64_t>(i0 + k * 256u) * N;
+    float v[N];
+    dec16(rx[k], v);
+#pragma unroll
+    for (int e = 0; e < N; ++e) v[e] *= mult;
+    if constexpr (RES) {
+      float r[N];
+      dec16(rr[k], r);
+#pragma unroll
+      for (int e = 0; e < N; ++e) v[e] = r[e] + Vec16<T>::rb(v[e]);
+    }
+    *reinterpret_cast<uint4*>(out + at) = lv[k] ? enc16(v) : zero16();      // a dead row: nothing was loaded, zeros leave
+  }
+}
+
+}  // namespace
+
+extern "C" int dalm_rms_norm_scaled_fwd(const void* x, const void* delta, float mult, const void* w, int dtype, int64_t R, int64_t D,
+                                        float eps, void* h_out, void* y, float* rstd, const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(x && delta && w && h_out && y && rstd, DALM_E_NULL, "null pointer argument");
+  DALM_RMS_CHECKS;
+  DALM_REQUIRE(aligned16(x, delta, w, h_out, y), DALM_E_ALIGN, "tensors must be 16-byte aligned");
+  const int Ri = static_cast<int>(R), Di = static_cast<int>(D);
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_ceil<1, 2, 4, 8, 16>(nch, [&](auto n) {
+      hipLaunchKernelGGL((rms_norm_scaled_fwd_kernel<T, n>), grid, dim3(256), 0, as_stream(stream), static_cast<const T*>(x),
+                         static_cast<const T*>(delta), mult, static_cast<const T*>(w), static_cast<T*>(h_out), static_cast<T*>(y),
+                         rstd, Ri, Di, eps, row_live);
+    });
+  });
+  return check_launch(__func__);
+}
+
+extern "C" int dalm_rms_norm_scaled_bwd(const void* dy, const void* h, const void* w, const float* rstd, const void* dres, float mult,
+                                        int dtype, int64_t R, int64_t D, void* dx, void* ddelta, const uint8_t* row_live,
+                                        dalm_stream_t stream) {
+  DALM_REQUIRE(dy && h && w && rstd && dx && ddelta, DALM_E_NULL, "null pointer argument");
+  DALM_RMS_CHECKS;
+  DALM_REQUIRE(aligned16(dy, h, w, dres, dx, ddelta), DALM_E_ALIGN, "tensors must be 16-byte aligned");
+  const int Ri = static_cast<int>(R), Di = static_cast<int>(D);
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_bool(dres != nullptr, [&](auto add) {
+      by_ceil<1, 2, 4, 8, 16>(nch, [&](auto n) {
+        hipLaunchKernelGGL((rms_norm_scaled_bwd_kernel<T, n, add>), grid, dim3(256), 0, as_stream(stream), static_cast<const T*>(dy),
+                           static_cast<const T*>(h), static_cast<const T*>(w), rstd, static_cast<const T*>(dres), mult,
+                           static_cast<T*>(dx), static_cast<T*>(ddelta), Ri, Di, row_live);
+      });
+    });
+  });
+  return check_launch(__func__);
+}
+
+extern "C" int dalm_scale_add(const void* res, const void* x, float mult, void* out, int dtype, int64_t R, int64_t D,
+                              const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(x && out, DALM_E_NULL, "null pointer argument");
+  DALM_REQUIRE(dtype == DALM_F32 || dtype == DALM_BF16, DALM_E_DTYPE, "dtype must be DALM_F32 or DALM_BF16");
+  const int vecn = dtype == DALM_F32 ? 4 : 8;
+  DALM_REQUIRE(R >= 0 && D >= 0 && D % vecn == 0 && (R == 0 || D / vecn <= 0x7fffffffll / R), DALM_E_SHAPE,
+               "need rows >= 0, a width that is a multiple of 16 bytes, and R D / (16 bytes) < 2^31");
+  DALM_REQUIRE(aligned16(res, x, out), DALM_E_ALIGN, "tensors must be 16-byte aligned");
+  if (R == 0 || D == 0) return 0;
+  const unsigned int vecs_per_row = static_cast<unsigned int>(D / vecn), nvec = static_cast<unsigned int>(R) * vecs_per_row;
+  const dim3 grid((nvec + 256u * kScaleAddVecs - 1) / (256u * kScaleAddVecs));
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_bool(res != nullptr, [&](auto with_res) {
+      hipLaunchKernelGGL((scale_add_kernel<T, with_res>), grid, dim3(256), 0, as_stream(stream), static_cast<const T*>(res),
+                         static_cast<const T*>(x), mult, static_cast<T*>(out), nvec, vecs_per_row, row_live);
     });
   });
   return check_launch(__func__);

@@ -175,6 +175,10 @@ SIGNATURES = {
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dalm_row_norm_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
                                  _vp, _vp, _vp, _vp, _vp]),
+    # Granite: the scaled residual add, with the RMSNorm behind it (forward, backward) and alone
+    "dalm_rms_norm_scaled_fwd": (_int, [_vp, _vp, _f32, _vp, _int, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "dalm_rms_norm_scaled_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _f32, _int, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "dalm_scale_add": (_int, [_vp, _vp, _f32, _vp, _int, _i64, _i64, _vp, _vp]),
     "dalm_bert_add_norm_fwd_live": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _f32, _f32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _vp]),
     "dalm_bert_add_norm_bwd_live": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),

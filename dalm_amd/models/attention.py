@@ -738,17 +738,18 @@ def sdpa(query, key, value, mask, scale: float, causal: bool, dropout_p: float =
 
 
 def use_hip_attention_backward(model: torch.nn.Module) -> bool:
-    """Switch a Llama-family, Gemma, Arcee, OLMo-2, BERT or RoBERTa-family (roberta, xlm-roberta, camembert: BERT's layer code) model of head
-    width 32, 64 or 128 from "sdpa" to "dalm_sdpa".  xlm-roberta-xl (pre-LayerNorm layers) is not taken, and neither is a Gemma of
-    head width 256 (every released checkpoint) or an Arcee of head width 80 (`ArceeConfig()`'s defaults; AFM-4.5B has 128): it
-    keeps transformers' SDPA and does not pack.  DALM_ATTN_KERNEL=0 disables."""
+    """Switch a Llama-family, Gemma, Arcee, OLMo-2, Granite, BERT or RoBERTa-family (roberta, xlm-roberta, camembert: BERT's layer
+    code) model of head width 32, 64 or 128 from "sdpa" to "dalm_sdpa".  xlm-roberta-xl (pre-LayerNorm layers) is not taken, and
+    neither is a Gemma of head width 256 (every released checkpoint) or an Arcee of head width 80 (`ArceeConfig()`'s defaults;
+    AFM-4.5B has 128): it keeps transformers' SDPA and does not pack.  Granite's softmax scale (`attention_multiplier`, not
+    hd ** -0.5) reaches the kernels as the `scaling` argument of the attention call, like any other.  DALM_ATTN_KERNEL=0 disables."""
     if _off("DALM_ATTN_KERNEL"):
         return False
     cfg = getattr(model, "config", None)
     if cfg is None or getattr(cfg, "_attn_implementation", None) != "sdpa":
         return False
-    if getattr(cfg, "model_type", "") not in ("llama", "mistral", "qwen2", "qwen3", "gemma", "arcee", "olmo2", "bert", "roberta",
-                                              "xlm-roberta", "camembert"):
+    if getattr(cfg, "model_type", "") not in ("llama", "mistral", "qwen2", "qwen3", "gemma", "arcee", "olmo2", "granite", "bert",
+                                              "roberta", "xlm-roberta", "camembert"):
         return False
     hd = getattr(cfg, "head_dim", None) or (cfg.hidden_size // cfg.num_attention_heads)
     if hd not in _HEAD_DIMS or not register():

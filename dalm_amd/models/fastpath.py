@@ -248,9 +248,16 @@ def use_swiglu_kernel(model: torch.nn.Module) -> int:
     def gated_silu(mod) -> bool:
         act = getattr(mod, "act_fn", None)
         return (all(hasattr(mod, a) for a in ("gate_proj", "up_proj", "down_proj"))
-                and (isinstance(act, torch.nn.SiLU) or type(act).__name__ in ("SiLUActivation", "SiLU")))
+                and (isinstance(act, torch.nn.SiLU) or type(act).__name__ in ("SiLUActivation", "SiLU"))
+                # a GraniteMLP with `mlp_bias` keeps transformers' code
+                and (type(mod).__name__ != "GraniteMLP" or _bias_free(mod, ("gate_proj", "up_proj", "down_proj"))))
 
-    return _install(model, ("LlamaMLP", "MistralMLP", "Qwen2MLP", "Qwen3MLP", "Olmo2MLP"), gated_silu, _mlp_matches, _swiglu_mlp_forward)
+    return _install(model, ("LlamaMLP", "MistralMLP", "Qwen2MLP", "Qwen3MLP", "Olmo2MLP", "GraniteMLP"), gated_silu, _mlp_matches,
+                    _swiglu_mlp_forward)
+
+
+def _bias_free(mod, names: tuple) -> bool:
+    return all(getattr(getattr(mod, a, None), "bias", 0) is None for a in names)
 
 
 def _mlp_matches(mod: torch.nn.Module, forward=_swiglu_mlp_forward, what: str = "down(silu(gate(x)) * up(x)) here",
@@ -1030,19 +1037,26 @@ def _olmo2_attention_forward(self, hidden_states, position_embeddings=None, atte
                                       (self.q_norm, self.k_norm), {}, row_wide=True)
 
 
-def _use_attention_node(model: torch.nn.Module, name: str, attrs: tuple, guard: str, forward) -> int:
+def _use_attention_node(model: torch.nn.Module, name: str, attrs: tuple, guard: str, forward, also=lambda mod: True) -> int:
     from . import attention
 
     if getattr(getattr(model, "config", None), "_attn_implementation", None) != attention.NAME:
         return 0
-    return _install(model, (name,), lambda mod: all(hasattr(mod, a) for a in attrs), guard, forward, keep="_dalm_orig_attn_forward")
+    return _install(model, (name,), lambda mod: all(hasattr(mod, a) for a in attrs) and also(mod), guard, forward,
+                    keep="_dalm_orig_attn_forward")
+
+
+_QKVO = ("q_proj", "k_proj", "v_proj", "o_proj")
 
 
 def use_llama_attention_node(model: torch.nn.Module) -> int:
-    """Patch LlamaAttention modules - and ArceeAttention ones, Llama's forward under the same source guard - of a model that runs on
-    "dalm_sdpa" (models/attention.py) and whose forward is the code `_llama_attention_forward` restates.  Returns the count."""
-    return sum(_use_attention_node(model, name, ("q_proj", "k_proj", "v_proj", "o_proj", "scaling"), "llama-attn",
-                                   _llama_attention_forward) for name in ("LlamaAttention", "ArceeAttention"))
+    """Patch LlamaAttention modules - and ArceeAttention and GraniteAttention ones, Llama's forward under the same source guard - of a
+    model that runs on "dalm_sdpa" (models/attention.py) and whose forward is the code `_llama_attention_forward` restates.  Granite's
+    softmax scale is `attention_multiplier`: the forward reads `self.scaling`, whatever the module put there.  A GraniteAttention
+    with biased projections (`attention_bias`) keeps transformers' code.  Returns the count."""
+    return sum(_use_attention_node(model, name, (*_QKVO, "scaling"), "llama-attn", _llama_attention_forward, also)
+               for name, also in (("LlamaAttention", lambda mod: True), ("ArceeAttention", lambda mod: True),
+                                  ("GraniteAttention", lambda mod: _bias_free(mod, _QKVO))))
 
 
 def use_qwen3_attention_node(model: torch.nn.Module) -> int:
@@ -1126,6 +1140,39 @@ def _two_norm_layer_forward(self, supported, add_norm, hidden_states, attention_
     return residual + self.mlp(normed)
 
 
+def _granite_layer_forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_values=None, use_cache=False,
+                           position_embeddings=None, **kwargs):
+    """transformers' GraniteDecoderLayer.forward - LlamaDecoderLayer.forward with `* self.residual_multiplier` on both sub-block
+    outputs - on `_two_norm_layer_forward`'s structure:
+      input_layernorm         : the norm alone forward; its backward kernel also adds the residual-path gradient (`add_rms_norm`)
+      post_attention_layernorm: residual + attention output * m and the norm in one launch; the backward's launch also makes the
+                                attention output's gradient, dx * m (`scaled_add_rms_norm`)
+      the trailing add        : residual + mlp output * m in one launch each way (`scale_add`)
+    The products round where the eager ones do.  A sub-block that answers in another dtype than the residual stream (autocast
+    over f32 weights) has its product formed by torch, in that dtype, as the eager statement forms it."""
+    from . import tower_ops
+
+    n1, n2 = self.input_layernorm, self.post_attention_layernorm
+    if not (tower_ops.scaled_add_rms_norm_supported(hidden_states, n1.weight)
+            and tower_ops.scaled_add_rms_norm_supported(hidden_states, n2.weight)):
+        return self._dalm_orig_forward(hidden_states, attention_mask=attention_mask, position_ids=position_ids,
+                                       past_key_values=past_key_values, use_cache=use_cache,
+                                       position_embeddings=position_embeddings, **kwargs)
+    m = float(self.residual_multiplier)
+    residual, normed = tower_ops.add_rms_norm(hidden_states, None, n1.weight, _norm_eps(n1))
+    attn_out, _ = self.self_attn(hidden_states=normed, attention_mask=attention_mask, position_ids=position_ids,
+                                 past_key_values=past_key_values, use_cache=use_cache,
+                                 position_embeddings=position_embeddings, **kwargs)
+    if attn_out.dtype == residual.dtype:
+        residual, normed = tower_ops.scaled_add_rms_norm(residual, attn_out, m, n2.weight, _norm_eps(n2))
+    else:
+        residual, normed = tower_ops.add_rms_norm(residual, attn_out * m, n2.weight, _norm_eps(n2))
+    mlp_out = self.mlp(normed)
+    if mlp_out.dtype == residual.dtype and tower_ops.scale_add_supported(mlp_out, residual):
+        return tower_ops.scale_add(residual, mlp_out, m)
+    return residual + mlp_out * m
+
+
 
 def _olmo2_layer_forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_values=None, use_cache=False,
                          position_embeddings=None, **kwargs):
@@ -1168,10 +1215,11 @@ def use_olmo2_layer(model: torch.nn.Module) -> int:
 
 
 def use_fused_residual_norm(model: torch.nn.Module) -> int:
-    """Patch LlamaDecoderLayer / Qwen3DecoderLayer / ArceeDecoderLayer / GemmaDecoderLayer modules whose forward has the signature this
-    file was written against (transformers 5.x; Qwen3's, Arcee's and Gemma's are also compared statement for statement); DALM_NORM_KERNEL=0
-    disables.  A Gemma layer's two norms must be GemmaRMSNorm by name and by value (`_gemma_norm_matches`); Gemma2 / Gemma3 layers
-    (four norms) are other code and are not taken.  Returns how many layers were patched."""
+    """Patch LlamaDecoderLayer / Qwen3DecoderLayer / ArceeDecoderLayer / GemmaDecoderLayer / GraniteDecoderLayer modules whose forward
+    has the signature this file was written against (transformers 5.x; Qwen3's, Arcee's, Gemma's and Granite's are also compared
+    statement for statement); DALM_NORM_KERNEL=0 disables.  A Gemma layer's two norms must be GemmaRMSNorm by name and by value
+    (`_gemma_norm_matches`); Gemma2 / Gemma3 layers (four norms) are other code and are not taken.  A Granite layer runs
+    `_granite_layer_forward` (the two scaled residual adds).  Returns how many layers were patched."""
     if _off("DALM_NORM_KERNEL"):
         return 0
 
@@ -1182,15 +1230,17 @@ def use_fused_residual_norm(model: torch.nn.Module) -> int:
     def gemma_rms_norm(nm) -> bool:
         return nm is not None and type(nm).__name__ == "GemmaRMSNorm" and _gemma_rms_norm(nm) and _gemma_norm_matches(nm)
 
-    def two_norms(is_norm):
+    def two_norms(is_norm, *more):
         return lambda mod: (is_norm(getattr(mod, "input_layernorm", None)) and is_norm(getattr(mod, "post_attention_layernorm", None))
-                            and all(hasattr(mod, a) for a in ("self_attn", "mlp")))
+                            and all(hasattr(mod, a) for a in ("self_attn", "mlp", *more)))
 
-    return sum(_install(model, (name,), two_norms(is_norm), guard, forward, keep="_dalm_orig_forward")
-               for name, guard, is_norm, forward in (("LlamaDecoderLayer", "llama-layer", plain_rms_norm, _llama_layer_forward),
-                                                     ("Qwen3DecoderLayer", "qwen3-layer", plain_rms_norm, _llama_layer_forward),
-                                                     ("ArceeDecoderLayer", "arcee-layer", plain_rms_norm, _llama_layer_forward),
-                                                     ("GemmaDecoderLayer", "gemma-layer", gemma_rms_norm, _gemma_layer_forward)))
+    return sum(_install(model, (name,), eligible, guard, forward, keep="_dalm_orig_forward")
+               for name, guard, eligible, forward in (
+                   ("LlamaDecoderLayer", "llama-layer", two_norms(plain_rms_norm), _llama_layer_forward),
+                   ("Qwen3DecoderLayer", "qwen3-layer", two_norms(plain_rms_norm), _llama_layer_forward),
+                   ("ArceeDecoderLayer", "arcee-layer", two_norms(plain_rms_norm), _llama_layer_forward),
+                   ("GemmaDecoderLayer", "gemma-layer", two_norms(gemma_rms_norm), _gemma_layer_forward),
+                   ("GraniteDecoderLayer", "granite-layer", two_norms(plain_rms_norm, "residual_multiplier"), _granite_layer_forward)))
 
 
 _SOURCE_GUARDS["llama-layer"] = (_restates(_LLAMA_LAYER_PARAMS), _RESTATED)
@@ -1207,6 +1257,25 @@ _SOURCE_GUARDS["qwen3-layer"] = (
                          and _body(src)[-len(_QWEN3_LAYER_BODY) - 1].startswith(")")), _RESTATED)
 _SOURCE_GUARDS["gemma-layer"] = _SOURCE_GUARDS["qwen3-layer"]       # GemmaDecoderLayer.forward: the same whole body, the same check
 _SOURCE_GUARDS["arcee-layer"] = _SOURCE_GUARDS["qwen3-layer"]       # ArceeDecoderLayer.forward likewise
+# GraniteDecoderLayer.forward: Qwen3's body with the two sub-block outputs scaled.  A docstring stands between the signature and the
+# body there, so the statements are compared as syntax trees, the docstring left out: nothing else may stand in the function
+_GRANITE_LAYER_BODY = [{"hidden_states = residual + hidden_states": "hidden_states = residual + hidden_states * self.residual_multiplier"}
+                       .get(s, s) for s in _QWEN3_LAYER_BODY]
+
+
+def _same_statements(src: str, body: list) -> bool:
+    """The function's statements, without its docstring, against the lines of `body` joined: equal as syntax trees."""
+    import ast
+    import textwrap
+
+    fn = ast.parse(textwrap.dedent(src)).body[0]
+    got = fn.body[1:] if ast.get_docstring(fn) is not None else fn.body
+    want = ast.parse("def f():\n" + textwrap.indent("\n".join(body), "    ")).body[0].body
+    return [ast.dump(s) for s in got] == [ast.dump(s) for s in want]
+
+
+_SOURCE_GUARDS["granite-layer"] = (
+    lambda params, src: params == _LLAMA_LAYER_PARAMS and _same_statements(src, _GRANITE_LAYER_BODY), _RESTATED)
 # Olmo2DecoderLayer.forward: the whole body, behind the signature
 _OLMO2_LAYER_BODY = ["residual = hidden_states", "hidden_states, _ = self.self_attn(", "hidden_states=hidden_states,",
                      "attention_mask=attention_mask,", "position_ids=position_ids,", "past_key_values=past_key_values,",

@@ -9,7 +9,8 @@ are the eager chain's (tests/test_tower_ops_gpu.py asserts equality, not closene
 Also here: RMSNorm with the residual add, Qwen3's head norm + rotary, Gemma's GeGLU and (1 + w) RMSNorm (`dalm_geglu_*`,
 `dalm_gemma_norm_*`: modeling_gemma.py `GemmaMLP.forward`, `GemmaRMSNorm.forward`), Arcee's ReLU^2 (`dalm_relu2_*`: modeling_arcee.py
 `ArceeMLP.forward`), OLMo-2's norm-then-add and row-wide q / k norm + rotary (`dalm_norm_add_*`, `dalm_row_norm_*`: modeling_olmo2.py),
-and Falcon's layer ops.
+Granite's scaled residual add with and without the norm behind it (`dalm_rms_norm_scaled_*`, `dalm_scale_add`: modeling_granite.py
+`GraniteDecoderLayer.forward`), and Falcon's layer ops.
 
 GPU tensors only: the callers in `fastpath.py` keep transformers' own code for CPU tensors.
 """
@@ -237,6 +238,101 @@ def add_rms_norm(x, delta, w, eps, live=None):
     delta = None: (x itself, rmsnorm(x) * w).  live: uint8 row liveness; None: that of the tower call in progress
     (dalm_amd/live_rows.py), if any."""
     return _AddRmsNorm.apply(x, delta, w, eps, live)
+
+
+# ---------------------------------------------------------------------------
+# Granite: the sub-block's output enters the residual stream scaled by a Python float (modeling_granite.py
+# `GraniteDecoderLayer.forward`: residual + hidden_states * self.residual_multiplier) - with the RMSNorm behind it
+# (dalm_rms_norm_scaled_{fwd,bwd}) and alone (dalm_scale_add).  The product is rounded to the tensor dtype before the add, as torch's
+# `tensor * float` is.
+# ---------------------------------------------------------------------------
+scaled_add_rms_norm_supported = rms_norm_supported       # the same rows, widths and weight dtype as `add_rms_norm`
+
+
+class _ScaledAddRmsNorm(torch.autograd.Function):
+    """(h, y) = (x + delta * mult, rmsnorm(h) * w), one launch; backward, one launch: dx (with the gradient that reaches h through
+    the residual path added inside) and ddelta = dx * mult, formed from the rounded dx as autograd's backward of the multiply would."""
+
+    @staticmethod
+    def forward(ctx, x, delta, mult, w, eps, live=None):
+        D = x.shape[-1]
+        w_c = w if w.dtype == x.dtype else w.to(x.dtype)
+        x2, d2 = _as_rows(x, D, x.dtype), _as_rows(delta, D, x.dtype)
+        R = x2.shape[0]
+        if live is None:
+            live = live_rows.current(R, x2.device)
+        h2, y2 = torch.empty_like(x2), torch.empty_like(x2)
+        rstd = torch.empty(R, device=x2.device, dtype=torch.float32)
+        hip.call("dalm_rms_norm_scaled_fwd", hip.ptr(x2), hip.ptr(d2), float(mult), hip.ptr(w_c), hip.dtype_code(x2), R, D, float(eps),
+                 hip.ptr(h2), hip.ptr(y2), hip.ptr(rstd), hip.ptr(live), hip.stream())
+        # (the liveness vector is kept: the backward runs after the tower call's context, on autograd's thread)
+        ctx.save_for_backward(h2, w_c, rstd, *([live] if live is not None else []))
+        ctx.shape, ctx.mult, ctx.w_dtype = x.shape, float(mult), w.dtype
+        return h2.view(x.shape), y2.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dh, dy):
+        h2, w_c, rstd, *live = ctx.saved_tensors
+        R, D = h2.shape
+        dy2 = _as_rows(dy, D, h2.dtype)
+        dres2 = _as_rows(dh, D, h2.dtype) if dh is not None else None
+        dx, dd = torch.empty_like(h2), torch.empty_like(h2)
+        hip.call("dalm_rms_norm_scaled_bwd", hip.ptr(dy2), hip.ptr(h2), hip.ptr(w_c), hip.ptr(rstd), hip.ptr(dres2), ctx.mult,
+                 hip.dtype_code(h2), R, D, hip.ptr(dx), hip.ptr(dd), hip.ptr(live[0] if live else None), hip.stream())
+        dw = _weight_grad(dy2, h2, rstd).to(ctx.w_dtype) if ctx.needs_input_grad[3] else None
+        return dx.view(ctx.shape), dd.view(ctx.shape), None, dw, None, None
+
+
+def scaled_add_rms_norm(x, delta, mult, w, eps, live=None):
+    """(x + delta * mult, its RMSNorm) in one launch, one more in the backward.  live: uint8 row liveness; None: that of the tower
+    call in progress (dalm_amd/live_rows.py), if any."""
+    return _ScaledAddRmsNorm.apply(x, delta, mult, w, eps, live)
+
+
+def scale_add_supported(x: torch.Tensor, res=None) -> bool:
+    """What `dalm_scale_add` takes: f32 or bf16 on the GPU, rows a multiple of 16 bytes wide (no upper limit), res of x's shape and
+    dtype."""
+    vec = 4 if x.dtype == torch.float32 else 8
+    return (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and x.dim() >= 1 and x.shape[-1] % vec == 0
+            and x.numel() // vec < 2 ** 31
+            and (res is None or (res.is_cuda and res.dtype == x.dtype and res.shape == x.shape)))
+
+
+def _scale_add_launch(r2, x2, mult, live):
+    out = torch.empty_like(x2)
+    hip.call("dalm_scale_add", hip.ptr(r2), hip.ptr(x2), float(mult), hip.ptr(out), hip.dtype_code(x2), x2.shape[0], x2.shape[1],
+             hip.ptr(live), hip.stream())
+    return out
+
+
+class _ScaleAdd(torch.autograd.Function):
+    """res + x * mult (res None: x * mult), one launch; backward: the same kernel without res on the incoming gradient, and the
+    incoming gradient itself for res."""
+
+    @staticmethod
+    def forward(ctx, res, x, mult, live=None):
+        D = x.shape[-1]
+        x2 = _as_rows(x, D, x.dtype)
+        r2 = _as_rows(res, D, x.dtype) if res is not None else None
+        if live is None:
+            live = live_rows.current(x2.shape[0], x2.device)
+        ctx.save_for_backward(*([live] if live is not None else []))
+        ctx.mult = float(mult)
+        return _scale_add_launch(r2, x2, ctx.mult, live).view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dout):
+        live = ctx.saved_tensors[0] if ctx.saved_tensors else None
+        dx = None
+        if ctx.needs_input_grad[1]:
+            dx = _scale_add_launch(None, _as_rows(dout, dout.shape[-1], dout.dtype), ctx.mult, live).view(dout.shape)
+        return (dout if ctx.needs_input_grad[0] else None), dx, None, None
+
+
+def scale_add(res, x, mult, live=None):
+    """res + x * mult in one launch - the product rounded to the dtype first, as the eager pair rounds - or x * mult with res None.
+    live: uint8 row liveness; None: that of the tower call in progress (dalm_amd/live_rows.py), if any."""
+    return _ScaleAdd.apply(res, x, mult, live)
 
 
 # ---------------------------------------------------------------------------

@@ -36,6 +36,21 @@ def _advance_dropout(batch) -> None:
         lora_ops.advance_dropout_seed(t.device)
 
 
+def _logits_scaled(hidden: torch.Tensor, generator_model) -> torch.Tensor:
+    """Hidden states that meet `lm_head.weight` WITHOUT the generator's own forward (fuse_lm_head, the packed route), for a generator
+    whose forward scales its logits: GraniteForCausalLM returns `lm_head(h) / config.logits_scaling`.  The head is linear and has no
+    bias on these routes, so the factor 1 / logits_scaling goes onto h in front of it - exact for the released powers of two (8,
+    16), one rounding of h in its dtype otherwise.  On the GPU one `dalm_scale_add` launch each way."""
+    s = getattr(getattr(generator_model, "config", None), "logits_scaling", None)
+    if s is None or float(s) == 1.0:
+        return hidden
+    from ..models import tower_ops
+
+    if tower_ops.scale_add_supported(hidden):
+        return tower_ops.scale_add(None, hidden, 1.0 / float(s))
+    return hidden * (1.0 / float(s))
+
+
 class _StepBase:
     def __init__(self, model, optimizer, lr_scheduler, logit_scale, comm=None, autocast_dtype=None, ops=None,
                  grad_overlap: bool = True, track_grad_norm: bool = False, grad_accum: int = 1, skip_dead_rows: bool = True):
@@ -305,6 +320,7 @@ class RagE2EStep(_StepBase):
         head = self.model.generator_model.get_output_embeddings()
         if getattr(head, "bias", None) is not None:
             raise NotImplementedError("the packed generator path and fuse_lm_head need a bias-free lm_head")
+        out = _logits_scaled(out, self.model.generator_model)
         if packed:
             labels, weights = _packed.packed_labels(ids, mask, batch["generator_pack_rows"])
             return rag_e2e_loss_packed(q_emb, p_emb, out, head.weight, labels, weights, mask, qp_len, self.logit_scale, **kw)

@@ -631,6 +631,31 @@ int dalm_row_norm_bwd(const void* gq, const void* gk, const void* q, const void*
                       const int64_t* dq_strides, const int64_t* dk_strides, void* dq, void* dk, const uint8_t* row_live,
                       dalm_stream_t stream);
 
+/* Granite (modeling_granite.py; `model_type` "granite"): Llama's layer with the sub-block outputs scaled on their way into the
+ * residual stream, `hidden_states = residual + hidden_states * residual_multiplier`, twice per layer.  `mult` is a float: the
+ * product is formed in f32 and rounded to `dtype`, as torch does for `tensor * python_float`; rb = that rounding (the identity
+ * for f32).  One entry point each; row_live [R] bytes or NULL (Row liveness, above: nothing of a dead row is loaded, every output
+ * holds zeros there, live rows receive the same bits as without the vector).
+ *   dalm_rms_norm_scaled_fwd: dalm_rms_norm_fwd_live with the delta scaled; delta and h_out are required.
+ *        t = rb(delta mult);  h_out = rb(x + t);  rstd = rsqrt(mean_d(h_out^2) + eps);  y = rb(w rb(h_out rstd)).
+ *   dalm_rms_norm_scaled_bwd: dx = rb(rstd (g - xh mean_d(g xh)) [+ dres]), g = dy w, xh = h rstd - dalm_rms_norm_bwd_live's
+ *        arithmetic, dres may be NULL - and, in the same launch, ddelta = rb(f32(dx as rounded) mult): what autograd's backward
+ *        of the eager multiply makes of dx.  No weight gradient is produced.
+ *   With mult == 1 both give the bits of dalm_rms_norm_fwd_live / dalm_rms_norm_bwd_live (ddelta == dx).  [R, D] row-major, one
+ *   wave per row, the D rules of dalm_rms_norm_* (a multiple of 16 bytes of `dtype`, at most 8192 (bf16) / 4096 (f32), R > 0:
+ *   DALM_E_SHAPE); 16-byte aligned tensors (DALM_E_ALIGN).
+ *   dalm_scale_add: out = rb(res + rb(x mult)), or out = rb(x mult) with res == NULL; [R, D] contiguous rows, D a multiple of 16
+ *        bytes of `dtype` with no upper limit (there is no reduction), R D / (16 bytes) < 2^31 (DALM_E_SHAPE); 16-byte aligned
+ *        tensors (DALM_E_ALIGN).  R == 0 or D == 0: nothing to do, 0.  The layer's trailing `residual + mlp_out * mult`, its
+ *        backward (res == NULL, x the incoming gradient) and the division of the logits' operand by `logits_scaling`.
+ * The checks run before anything is enqueued: a rejected call writes nothing. */
+int dalm_rms_norm_scaled_fwd(const void* x, const void* delta, float mult, const void* w, int dtype, int64_t R, int64_t D, float eps,
+                             void* h_out, void* y, float* rstd, const uint8_t* row_live, dalm_stream_t stream);
+int dalm_rms_norm_scaled_bwd(const void* dy, const void* h, const void* w, const float* rstd, const void* dres, float mult, int dtype,
+                             int64_t R, int64_t D, void* dx, void* ddelta, const uint8_t* row_live, dalm_stream_t stream);
+int dalm_scale_add(const void* res, const void* x, float mult, void* out, int dtype, int64_t R, int64_t D, const uint8_t* row_live,
+                   dalm_stream_t stream);
+
 /* Elementwise chains of a Falcon-7B decoder layer (transformers modeling_falcon.py FalconDecoderLayer.forward /
  * FalconMLP.forward / dropout_add, reached by the reference through self.generator_model(...),
  * dalm/models/rag_e2e_base_model.py:104-106; BASELINE.json config 5).  bf16 tensors, 16-byte aligned.

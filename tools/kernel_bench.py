@@ -596,6 +596,82 @@ def bench_norm_add(R, D, rounds=3):
     return out
 
 
+def bench_scaled_add_norm(R, D, mult=0.22, rounds=3):
+    """Granite's two scaled residual adds on [R, D] bf16 rows.  With the norm behind it, `residual + attn_out * m` then GraniteRMSNorm:
+    `dalm_rms_norm_scaled_fwd` / `dalm_rms_norm_scaled_bwd`, and beside them - alternating, in the same process - the two forms they
+    replace: the eager multiply and add + transformers' GraniteRMSNorm.forward (an f32 chain), and the eager multiply and add +
+    F.rms_norm (what `use_native_rms_norm` alone leaves: the unrouted model of today), each with autograd's backward, in which the
+    gradient through the residual path meets the norm's.  Alone, `residual + mlp_out * m`: `dalm_scale_add` each way against the eager
+    pair.  Algorithmic bytes: norm forward 4 R D elements (x, delta in; h, y out), backward 5 R D (dy, h, dres in; dx, ddelta out);
+    scale_add forward 3 R D, backward 2 R D (the residual's gradient is the incoming one: no traffic)."""
+    import torch.nn.functional as F
+    from transformers.models.granite.modeling_granite import GraniteRMSNorm
+
+    from dalm_amd import hip
+    from dalm_amd.models import tower_ops
+
+    dev = torch.device("cuda:0")
+    x, delta, gy, gh = (torch.randn(R, D, device=dev, dtype=torch.bfloat16) for _ in range(4))
+    norm = GraniteRMSNorm(D, eps=1e-6).to(dev).to(torch.bfloat16).requires_grad_(False)
+    with torch.no_grad():
+        norm.weight.copy_(1.0 + 0.1 * torch.randn(D, device=dev))
+    w = norm.weight
+    assert tower_ops.scaled_add_rms_norm_supported(x, w) and tower_ops.scale_add_supported(delta, x)
+    with torch.no_grad():
+        h, _ = tower_ops.scaled_add_rms_norm(x, delta, mult, w, 1e-6)
+    rstd = torch.rsqrt(h.float().pow(2).mean(-1) + 1e-6)
+    dx, dd = torch.empty_like(x), torch.empty_like(x)
+    xd, dl = x.clone().requires_grad_(True), delta.clone().requires_grad_(True)
+
+    def kernel_fwd():
+        with torch.no_grad():
+            return tower_ops.scaled_add_rms_norm(x, delta, mult, w, 1e-6)
+
+    def kernel_bwd():
+        hip.call("dalm_rms_norm_scaled_bwd", hip.ptr(gy), hip.ptr(h), hip.ptr(w), hip.ptr(rstd), hip.ptr(gh), mult, hip.dtype_code(h), R, D,
+                 hip.ptr(dx), hip.ptr(dd), None, hip.stream())
+
+    def pair(normed):
+        def fwd(a, b):
+            hh = a + b * mult
+            return hh, normed(hh)
+        return fwd
+
+    eager, native = pair(norm), pair(lambda t: F.rms_norm(t, (D,), w, 1e-6))
+
+    def no_grad(fn, *a):
+        def run():
+            with torch.no_grad():
+                return fn(*a)
+        return run
+
+    def add_kernel_bwd():
+        with torch.no_grad():
+            return tower_ops.scale_add(None, gy, mult)
+
+    n = R * D * 2
+    fns = {"norm kernel fwd (1 launch)": kernel_fwd, "norm kernel bwd (1 launch)": kernel_bwd,
+           "norm eager fwd (mul + add + f32 chain)": no_grad(eager, x, delta),
+           "norm eager fwd + autograd bwd": lambda: torch.autograd.grad(eager(xd, dl), (xd, dl), (gh, gy)),
+           "norm native fwd (mul + add + F.rms_norm)": no_grad(native, x, delta),
+           "norm native fwd + autograd bwd": lambda: torch.autograd.grad(native(xd, dl), (xd, dl), (gh, gy)),
+           "add kernel fwd (1 launch)": no_grad(tower_ops.scale_add, x, delta, mult), "add kernel bwd (1 launch)": add_kernel_bwd,
+           "add eager fwd (mul + add)": no_grad(lambda a, b: a + b * mult, x, delta),
+           "add eager fwd + autograd bwd": lambda: torch.autograd.grad(xd + dl * mult, (xd, dl), gy)}
+    out = _alternating(fns, {"norm kernel fwd (1 launch)": 4 * n + 4 * R, "norm kernel bwd (1 launch)": 5 * n + 4 * R,
+                             "norm eager fwd (mul + add + f32 chain)": 4 * n, "norm eager fwd + autograd bwd": 9 * n,
+                             "norm native fwd (mul + add + F.rms_norm)": 4 * n, "norm native fwd + autograd bwd": 9 * n,
+                             "add kernel fwd (1 launch)": 3 * n, "add kernel bwd (1 launch)": 2 * n, "add eager fwd (mul + add)": 3 * n,
+                             "add eager fwd + autograd bwd": 5 * n}, rounds)
+    k = out["norm kernel fwd (1 launch)"]["s"] + out["norm kernel bwd (1 launch)"]["s"]
+    for other in ("eager", "native"):
+        e = out[f"norm {other} fwd + autograd bwd"]["s"]
+        out[f"norm kernel fwd + bwd against {other}"] = {"kernel_s": k, f"{other}_s": e, f"{other}_over_kernel": e / k}
+    k, e = out["add kernel fwd (1 launch)"]["s"] + out["add kernel bwd (1 launch)"]["s"], out["add eager fwd + autograd bwd"]["s"]
+    out["add kernel fwd + bwd against eager"] = {"kernel_s": k, "eager_s": e, "eager_over_kernel": e / k}
+    return out
+
+
 def bench_row_norm_rope(B, T, Hq, Hk, hd, rounds=3):
     """OLMo-2's q_norm / k_norm over the whole projection width + rotary embedding: `dalm_row_norm_rope_fwd` / `dalm_row_norm_bwd` on
     the q | k column slices of one [B T, (Hq + 2 Hk) hd] bf16 buffer, and beside them - alternating, in the same process - what runs
@@ -749,6 +825,10 @@ def main():
     if args.only in ("", "row_norm_rope"):
         res["row_norm_rope OLMo-2-7B generator rows 18x256, 32+32 heads x 128"] = bench_row_norm_rope(18, 256, 32, 32, 128)
         res["row_norm_rope OLMo-2-7B packed rows 1x3008, 32+32 heads x 128"] = bench_row_norm_rope(1, 3008, 32, 32, 128)
+    # the headline batch's rows at Granite's widths: hidden 2048 (granite-3.x-2b) and 4096 (granite-3.x-8b)
+    if args.only in ("", "scaled_add_norm"):
+        res["scaled_add_norm Granite-2B rows 4608 x 2048 bf16"] = bench_scaled_add_norm(4608, 2048)
+        res["scaled_add_norm Granite-8B rows 4608 x 4096 bf16"] = bench_scaled_add_norm(4608, 4096)
     Path("gpurun_out").mkdir(exist_ok=True)
     Path("gpurun_out/kernel_bench.json").write_text(json.dumps(res, indent=1))
     print_results(res)
