@@ -19,7 +19,8 @@
 // Further down: RMSNorm with the residual add (dalm_rms_norm_*), Qwen3's head norm + rotary (dalm_head_norm_*), and Gemma's two
 // formulas - GeGLU and the (1 + w) RMSNorm (dalm_geglu_*, dalm_gemma_norm_*) - Arcee's ReLU^2 (dalm_relu2_*), and OLMo-2's norm-then-add
 // and row-wide q / k norm + rotary (dalm_norm_add_*, dalm_row_norm_*), and Granite's scaled residual add with and without the norm
-// behind it (dalm_rms_norm_scaled_*, dalm_scale_add), each with its own comment block.
+// behind it (dalm_rms_norm_scaled_*, dalm_scale_add), and Cohere's interleaved f32 rotary embedding, bias-free f32 LayerNorm and
+// three-way residual add (dalm_rope_il_qk, dalm_cohere_norm_*, dalm_add3_live), each with its own comment block.
 #include "dispatch.hpp"
 #include "relu2_math.hpp"
 #include "swiglu_math.hpp"
@@ -2054,6 +2055,375 @@ extern "C" int dalm_scale_add(const void* res, const void* x, float mult, void* 
       hipLaunchKernelGGL((scale_add_kernel<T, with_res>), grid, dim3(256), 0, as_stream(stream), static_cast<const T*>(res),
                          static_cast<const T*>(x), mult, static_cast<T*>(out), nvec, vecs_per_row, row_live);
     });
+  });
+  return check_launch(__func__);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Cohere (modeling_cohere.py; Command-R, Aya): a parallel block behind ONE norm, n = LayerNorm(x); out = x + attn(n) + mlp(n), with
+// an INTERLEAVED rotary embedding computed in f32 and a bias-free LayerNorm computed in f32:
+//   rope forward :  o[2i] = rb(f32(x[2i] c[2i]) - f32(x[2i+1] s[2i]))       o[2i+1] = rb(f32(x[2i+1] c[2i+1]) + f32(x[2i] s[2i+1]))
+//   rope backward:  d[2i] = rb(f32(g[2i] c[2i]) + f32(g[2i+1] s[2i+1]))     d[2i+1] = rb(f32(g[2i+1] c[2i+1]) - f32(g[2i] s[2i]))
+//                   apply_rotary_pos_emb up-casts q and k, multiplies with the tables in f32 (separate mul and add kernels: no
+//                   fused multiply-add here) and rounds once, at the end; its autograd backward rounds once as well.  The
+//                   tables may be f32 beside bf16 activations (autocast over f32 weights); cos[2i] and cos[2i+1] are read as
+//                   given.  A lane holds one 16-byte chunk of a head row: a pair never crosses a lane.
+//   norm forward :  mean = mean_d(x);  rstd = rsqrt(mean_d((x - mean)^2) + eps);  y = rb(f32(w) f32((x - mean) rstd))   - f32
+//                   throughout, one rounding (CohereLayerNorm.forward); only the summation order of the two means is the kernel's.
+//                   f32 rows: statistics and y in f64, rounded once (see cohere_norm_fwd_kernel)
+//   norm backward:  g = dy w;  xh = (x - mean) rstd;  dx = rb(rstd (g - mean_d(g) - xh mean_d(g xh)) [+ dres])
+//   add3_live    :  out = rb(rb(res + a) + b): the layer's `residual + attn + mlp`, two eager adds
+// The norms: one wave per row, the row kept as raw 16-byte chunks between the reductions (rms_norm_scaled_fwd_kernel).  The rotary
+// kernel and add3 have no reduction: flat grids.  Algorithmic bytes: rope 2 (|q| + |k|) el (+ tables, shared by all heads); norm
+// forward 2 R D el, backward (3 or 4) R D el; add3 4 R D el.
+// ---------------------------------------------------------------------------------------------------
+namespace {
+
+struct RopeIlParams {
+  RopeTensor q, k;
+  const void* cos; const void* sin; int64_t cs[2];   // strides of (b, t)
+  int B, T, Hq, Hk, backward;
+  const unsigned char* live;                         // [B * T] or NULL: a dead (b, t) is not read, its outputs are zeros
+};
+
+// N table values from p on: the activations' dtype (one 16-byte load) or f32 beside bf16 activations (two)
+template <typename T, bool TAB_F32>
+__device__ __forceinline__ void load_table(const void* tab, int64_t at, float (&v)[Vec16<T>::VEC]) {
+  if constexpr (TAB_F32) {
+    const float* p = static_cast<const float*>(tab) + at;
+#pragma unroll
+    for (int i = 0; i < Vec16<T>::VEC; i += 4) {
+      const float4 f = *reinterpret_cast<const float4*>(p + i);
+      v[i] = f.x; v[i + 1] = f.y; v[i + 2] = f.z; v[i + 3] = f.w;
+    }
+  } else {
+    Vec16<T>::load(static_cast<const T*>(tab) + at, v);
+  }
+}
+
+template <typename T, int HD, bool TAB_F32>
+__global__ __launch_bounds__(256) void rope_il_kernel(const RopeIlParams p) {
+#pragma clang fp contract(off)   // the eager chain is separate f32 mul and add kernels: a fused multiply-add would round once less
+  constexpr int N = Vec16<T>::VEC, G = HD / N;       // lanes per head row
+  const unsigned H = static_cast<unsigned>(p.Hq + p.Hk);
+  const unsigned gid = blockIdx.x * 256u + threadIdx.x;   // the launcher keeps rows * G below 2^31
+  const unsigned row = gid / G;
+  const int c = static_cast<int>(gid % G) * N;
+  if (row >= static_cast<unsigned>(p.B) * p.T * H) return;
+  const unsigned hh = row % H, bt = row / H;              // rows are walked head-fastest (rope_qk_kernel)
+  const int t = static_cast<int>(bt % p.T), b = static_cast<int>(bt / p.T);
+  const bool is_k = hh >= static_cast<unsigned>(p.Hq);
+  const RopeTensor& R = is_k ? p.k : p.q;
+  const int head = static_cast<int>(is_k ? hh - p.Hq : hh);
+  T* o = static_cast<T*>(R.o) + b * R.os[0] + head * R.os[1] + t * R.os[2] + c;
+  if (p.live && !p.live[bt]) {
+    *reinterpret_cast<uint4*>(o) = zero16();
+    return;
+  }
+  float x[N], cs[N], sn[N], out[N];
+  const int64_t ta = b * p.cs[0] + t * p.cs[1] + c;
+  Vec16<T>::load(static_cast<const T*>(R.x) + b * R.xs[0] + head * R.xs[1] + t * R.xs[2] + c, x);
+  load_table<T, TAB_F32>(p.cos, ta, cs);
+  load_table<T, TAB_F32>(p.sin, ta, sn);
+#pragma unroll
+  for (int e = 0; e < N; e += 2) {
+    // plain operators: the contract(off) pragma above governs this function's operations (see rope_qk_kernel)
+    const float a0 = x[e] * cs[e], a1 = x[e + 1] * cs[e + 1];
+    if (!p.backward) {
+      const float b0 = x[e + 1] * sn[e], b1 = x[e] * sn[e + 1];
+      out[e] = a0 - b0;
+      out[e + 1] = a1 + b1;
+    } else {
+      const float b0 = x[e + 1] * sn[e + 1], b1 = x[e] * sn[e];
+      out[e] = a0 + b0;
+      out[e + 1] = a1 - b1;
+    }
+  }
+  Vec16<T>::store(o, out);                           // rounded once
+}
+
+// every lane's partial sum and the shuffles across the wave, in the accumulator's type
+template <typename A>
+__device__ __forceinline__ A wave_sum_as(A v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// The statistics and the output are formed in A: float for bf16 rows - the eager chain's own f32 operations, whose roundings vanish
+// under the one rounding to bf16 - and double for f32 rows, where the chain's roundings ARE the result: there the kernel rounds
+// once, from the exact value (at most half an ulp, whatever the summation order of the eager means)
+template <typename T, int NCH>
+__global__ __launch_bounds__(256) void cohere_norm_fwd_kernel(const T* __restrict__ x, const void* __restrict__ w, bool w_f32,
+                                                              T* __restrict__ y, float* __restrict__ mean_out,
+                                                              float* __restrict__ rstd_out, int R, int D, float eps,
+                                                              const unsigned char* __restrict__ live) {
+#pragma clang fp contract(off)   // (x - mean) rstd and the weight product round separately in the eager chain
+  constexpr int N = Vec16<T>::VEC;
+  using A = std::conditional_t<std::is_same_v<T, float>, double, float>;
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= R) return;
+  const int64_t base = static_cast<int64_t>(row) * D;
+  if (live && !live[row]) {                      // a dead row (wave-uniform): nothing is read, y, mean and rstd leave as zeros
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int d = (c * 64 + lane) * N;
+      if (d < D) *reinterpret_cast<uint4*>(y + base + d) = zero16();
+    }
+    if (lane == 0) { mean_out[row] = 0.f; rstd_out[row] = 0.f; }
+    return;
+  }
+  uint4 rx[NCH];                                 // the row in flight before the first reduction, kept raw for the other two passes
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * N;
+    rx[c] = d < D ? *reinterpret_cast<const uint4*>(x + base + d) : zero16();
+  }
+  A s = 0;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    float v[N];
+    dec16(rx[c], v);                             // past the row: zeros, which leave the sum as it is
+#pragma unroll
+    for (int e = 0; e < N; ++e) s += static_cast<A>(v[e]);
+  }
+  const A mean = wave_sum_as(s) / static_cast<A>(D);
+  A ss = 0;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * N;
+    if (d >= D) continue;
+    float v[N];
+    dec16(rx[c], v);
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+      const A xc = static_cast<A>(v[e]) - mean;
+      ss = fma(xc, xc, ss);
+    }
+  }
+  const A var = wave_sum_as(ss) / static_cast<A>(D) + static_cast<A>(eps);
+  A rstd;
+  if constexpr (std::is_same_v<A, double>) rstd = 1.0 / sqrt(var);
+  else rstd = rsqrtf(var);
+  if (lane == 0) { mean_out[row] = static_cast<float>(mean); rstd_out[row] = static_cast<float>(rstd); }
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * N;
+    if (d >= D) continue;
+    float v[N], wv[N], o[N];
+    dec16(rx[c], v);
+    load_weight<N>(w, w_f32, d, wv);
+#pragma unroll
+    for (int e = 0; e < N; ++e) o[e] = static_cast<float>(static_cast<A>(wv[e]) * ((static_cast<A>(v[e]) - mean) * rstd));
+    Vec16<T>::store(y + base + d, o);              // rounded once
+  }
+}
+
+template <typename T, int NCH, bool ADD>
+__global__ __launch_bounds__(256) void cohere_norm_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
+                                                              const void* __restrict__ w, bool w_f32,
+                                                              const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
+                                                              const T* __restrict__ dres, T* __restrict__ dx, int R, int D,
+                                                              const unsigned char* __restrict__ live) {
+  constexpr int N = Vec16<T>::VEC;
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= R) return;
+  const int64_t base = static_cast<int64_t>(row) * D;
+  if (live && !live[row]) {                      // a dead row (wave-uniform): dx leaves as zeros
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int d = (c * 64 + lane) * N;
+      if (d < D) *reinterpret_cast<uint4*>(dx + base + d) = zero16();
+    }
+    return;
+  }
+  // the streams of a row are requested as raw 16-byte chunks before the wave reductions and decoded twice (gemma_norm_bwd_kernel)
+  uint4 rg[NCH], rh[NCH], rr[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * N;
+    const bool ok = d < D;
+    rg[c] = ok ? *reinterpret_cast<const uint4*>(dy + base + d) : zero16();
+    rh[c] = ok ? *reinterpret_cast<const uint4*>(x + base + d) : zero16();
+    if constexpr (ADD) rr[c] = ok ? *reinterpret_cast<const uint4*>(dres + base + d) : zero16();
+  }
+  const float mean = mean_in[row], rstd = rstd_in[row];
+  float sg = 0.f, dot = 0.f;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * N;
+    if (d >= D) continue;
+    float g[N], xv[N], wv[N];
+    dec16(rg[c], g); dec16(rh[c], xv);
+    load_weight<N>(w, w_f32, d, wv);
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+      const float gw = g[e] * wv[e];
+      sg += gw;
+      dot = fmaf(gw, (xv[e] - mean) * rstd, dot);
+    }
+  }
+  sg = wave_sum(sg) / static_cast<float>(D);
+  dot = wave_sum(dot) / static_cast<float>(D);
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int d = (c * 64 + lane) * N;
+    if (d >= D) continue;
+    float g[N], xv[N], wv[N], o[N];
+    dec16(rg[c], g); dec16(rh[c], xv);
+    load_weight<N>(w, w_f32, d, wv);
+#pragma unroll
+    for (int e = 0; e < N; ++e) o[e] = rstd * (g[e] * wv[e] - sg - ((xv[e] - mean) * rstd) * dot);
+    if constexpr (ADD) {
+      float r[N];
+      dec16(rr[c], r);
+#pragma unroll
+      for (int e = 0; e < N; ++e) o[e] += r[e];
+    }
+    Vec16<T>::store(dx + base + d, o);             // rounded once
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void add3_live_kernel(const T* __restrict__ res, const T* __restrict__ a, const T* __restrict__ b,
+                                                        T* __restrict__ out, unsigned int nvec, unsigned int vecs_per_row,
+                                                        const unsigned char* __restrict__ live) {
+  constexpr int N = Vec16<T>::VEC, K = kScaleAddVecs;
+  const unsigned int i0 = blockIdx.x * (256u * K) + threadIdx.x;
+  uint4 rr[K], ra[K], rb[K];
+  bool in[K], lv[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const unsigned int i = i0 + k * 256u;
+    in[k] = i < nvec;
+    lv[k] = in[k] && (!live || live[i / vecs_per_row]);
+    const int64_t at = static_cast<int64_t>(i) * N;
+    rr[k] = lv[k] ? *reinterpret_cast<const uint4*>(res + at) : zero16();
+    ra[k] = lv[k] ? *reinterpret_cast<const uint4*>(a + at) : zero16();
+    rb[k] = lv[k] ? *reinterpret_cast<const uint4*>(b + at) : zero16();
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if (!in[k]) continue;
+    const int64_t at = static_cast<int64_t>(i0 + k * 256u) * N;
+    float r[N], x[N], y[N];
+    dec16(rr[k], r); dec16(ra[k], x); dec16(rb[k], y);
+#pragma unroll
+    for (int e = 0; e < N; ++e) r[e] = Vec16<T>::rb(r[e] + x[e]) + y[e];
+    *reinterpret_cast<uint4*>(out + at) = lv[k] ? enc16(r) : zero16();      // a dead row: nothing was loaded, zeros leave
+  }
+}
+
+bool strides_mult(const int64_t* s, int n, int q) {
+  for (int i = 0; i < n; ++i)
+    if (s[i] % q != 0) return false;
+  return true;
+}
+
+}  // namespace
+
+extern "C" int dalm_rope_il_qk(const void* q, const void* k, void* q_out, void* k_out, const void* cos, const void* sin, int dtype,
+                               int tab_dtype, int64_t B, int64_t T, int64_t Hq, int64_t Hk, int64_t hd, const int64_t* q_strides,
+                               const int64_t* k_strides, const int64_t* qo_strides, const int64_t* ko_strides,
+                               const int64_t* cs_strides, int backward, const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(q && k && q_out && k_out && cos && sin && q_strides && k_strides && qo_strides && ko_strides && cs_strides,
+               DALM_E_NULL, "null pointer argument");
+  DALM_REQUIRE(dtype == DALM_F32 || dtype == DALM_BF16, DALM_E_DTYPE, "dtype must be DALM_F32 or DALM_BF16");
+  DALM_REQUIRE(tab_dtype == dtype || tab_dtype == DALM_F32, DALM_E_DTYPE, "the tables are of the activations' dtype or f32");
+  DALM_REQUIRE(hd == 32 || hd == 64 || hd == 128, DALM_E_SHAPE, "head width must be 32, 64 or 128");
+  DALM_REQUIRE(B > 0 && T > 0 && Hq > 0 && Hk >= 0 && Hq + Hk <= 65535, DALM_E_SHAPE, "need B, T, Hq > 0, Hk >= 0");
+  const int vec = dtype == DALM_F32 ? 4 : 8;
+  DALM_REQUIRE(B <= 0x7fffffffLL && T <= 0x7fffffffLL && B * T <= 0x7fffffffLL && B * T * (Hq + Hk) * (hd / vec) <= 0x7fffffffLL,
+               DALM_E_SHAPE, "tensor too large for one launch");
+  DALM_REQUIRE(aligned16(q, k, q_out, k_out, cos, sin) && strides_mult(q_strides, 3, vec) && strides_mult(k_strides, 3, vec)
+                   && strides_mult(qo_strides, 3, vec) && strides_mult(ko_strides, 3, vec) && strides_mult(cs_strides, 2, vec),
+               DALM_E_ALIGN, "tensors must be 16-byte aligned and every stride a multiple of 16 bytes of `dtype`");
+  RopeIlParams p;
+  p.q.x = q; p.q.o = q_out; p.k.x = k; p.k.o = k_out;
+  for (int i = 0; i < 3; ++i) {
+    p.q.xs[i] = q_strides[i]; p.k.xs[i] = k_strides[i]; p.q.os[i] = qo_strides[i]; p.k.os[i] = ko_strides[i];
+  }
+  p.cos = cos; p.sin = sin; p.cs[0] = cs_strides[0]; p.cs[1] = cs_strides[1];
+  p.B = static_cast<int>(B); p.T = static_cast<int>(T); p.Hq = static_cast<int>(Hq); p.Hk = static_cast<int>(Hk);
+  p.backward = backward != 0;
+  p.live = row_live;
+  const dim3 grid(static_cast<unsigned>((B * T * (Hq + Hk) * (hd / vec) + 255) / 256));
+  by_dtype(dtype, [&](auto t) {
+    using T_ = typename decltype(t)::type;
+    by_exact<32, 64, 128>(static_cast<int>(hd), [&](auto width) {
+      if constexpr (std::is_same_v<T_, float>) {       // f32 activations: the tables are f32, read as the activations are
+        hipLaunchKernelGGL((rope_il_kernel<T_, width, false>), grid, dim3(256), 0, as_stream(stream), p);
+      } else {
+        by_bool(tab_dtype == DALM_F32, [&](auto tab_f32) {
+          hipLaunchKernelGGL((rope_il_kernel<T_, width, tab_f32>), grid, dim3(256), 0, as_stream(stream), p);
+        });
+      }
+    });
+  });
+  return check_launch(__func__);
+}
+
+// dalm_rms_norm_*'s width rules and R > 0; the weight has a dtype of its own
+#define DALM_COHERE_NORM_CHECKS                                                                                          \
+  DALM_REQUIRE(dtype == DALM_F32 || dtype == DALM_BF16, DALM_E_DTYPE, "dtype must be DALM_F32 or DALM_BF16");             \
+  DALM_REQUIRE(w_dtype == DALM_F32 || w_dtype == DALM_BF16, DALM_E_DTYPE, "w_dtype must be DALM_F32 or DALM_BF16");       \
+  const int vecn = dtype == DALM_F32 ? 4 : 8;                                                                            \
+  DALM_REQUIRE(R > 0 && D > 0 && D % vecn == 0 && D <= 64ll * vecn * 16 && R <= 0x7ffffff0ll, DALM_E_SHAPE,               \
+               "need rows > 0 and a width that is a multiple of 16 bytes, at most 8192 (bf16) / 4096 (f32) elements");    \
+  const int nch = static_cast<int>((D + 64 * vecn - 1) / (64 * vecn));                                                   \
+  const dim3 grid(static_cast<unsigned>((R + 3) / 4))
+
+extern "C" int dalm_cohere_norm_fwd(const void* x, const void* w, int dtype, int w_dtype, int64_t R, int64_t D, float eps, void* y,
+                                    float* mean, float* rstd, const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(x && w && y && mean && rstd, DALM_E_NULL, "null pointer argument");
+  DALM_COHERE_NORM_CHECKS;
+  DALM_REQUIRE(aligned16(x, w, y), DALM_E_ALIGN, "tensors must be 16-byte aligned");
+  const int Ri = static_cast<int>(R), Di = static_cast<int>(D);
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_ceil<1, 2, 4, 8, 16>(nch, [&](auto n) {
+      hipLaunchKernelGGL((cohere_norm_fwd_kernel<T, n>), grid, dim3(256), 0, as_stream(stream), static_cast<const T*>(x), w,
+                         w_dtype == DALM_F32, static_cast<T*>(y), mean, rstd, Ri, Di, eps, row_live);
+    });
+  });
+  return check_launch(__func__);
+}
+
+extern "C" int dalm_cohere_norm_bwd(const void* dy, const void* x, const void* w, const float* mean, const float* rstd,
+                                    const void* dres, int dtype, int w_dtype, int64_t R, int64_t D, void* dx,
+                                    const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(dy && x && w && mean && rstd && dx, DALM_E_NULL, "null pointer argument");
+  DALM_COHERE_NORM_CHECKS;
+  DALM_REQUIRE(aligned16(dy, x, w, dres, dx), DALM_E_ALIGN, "tensors must be 16-byte aligned");
+  const int Ri = static_cast<int>(R), Di = static_cast<int>(D);
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_bool(dres != nullptr, [&](auto add) {
+      by_ceil<1, 2, 4, 8, 16>(nch, [&](auto n) {
+        hipLaunchKernelGGL((cohere_norm_bwd_kernel<T, n, add>), grid, dim3(256), 0, as_stream(stream), static_cast<const T*>(dy),
+                           static_cast<const T*>(x), w, w_dtype == DALM_F32, mean, rstd, static_cast<const T*>(dres),
+                           static_cast<T*>(dx), Ri, Di, row_live);
+      });
+    });
+  });
+  return check_launch(__func__);
+}
+
+extern "C" int dalm_add3_live(const void* res, const void* a, const void* b, void* out, int dtype, int64_t R, int64_t D,
+                              const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(res && a && b && out, DALM_E_NULL, "null pointer argument");
+  DALM_REQUIRE(dtype == DALM_F32 || dtype == DALM_BF16, DALM_E_DTYPE, "dtype must be DALM_F32 or DALM_BF16");
+  const int vecn = dtype == DALM_F32 ? 4 : 8;
+  DALM_REQUIRE(R >= 0 && D >= 0 && D % vecn == 0 && (R == 0 || D / vecn <= 0x7fffffffll / R), DALM_E_SHAPE,
+               "need rows >= 0, a width that is a multiple of 16 bytes, and R D / (16 bytes) < 2^31");
+  DALM_REQUIRE(aligned16(res, a, b, out), DALM_E_ALIGN, "tensors must be 16-byte aligned");
+  if (R == 0 || D == 0) return 0;
+  const unsigned int vecs_per_row = static_cast<unsigned int>(D / vecn), nvec = static_cast<unsigned int>(R) * vecs_per_row;
+  const dim3 grid((nvec + 256u * kScaleAddVecs - 1) / (256u * kScaleAddVecs));
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((add3_live_kernel<T>), grid, dim3(256), 0, as_stream(stream), static_cast<const T*>(res),
+                       static_cast<const T*>(a), static_cast<const T*>(b), static_cast<T*>(out), nvec, vecs_per_row, row_live);
   });
   return check_launch(__func__);
 }

@@ -179,6 +179,12 @@ SIGNATURES = {
     "dalm_rms_norm_scaled_fwd": (_int, [_vp, _vp, _f32, _vp, _int, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp]),
     "dalm_rms_norm_scaled_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _f32, _int, _i64, _i64, _vp, _vp, _vp, _vp]),
     "dalm_scale_add": (_int, [_vp, _vp, _f32, _vp, _int, _i64, _i64, _vp, _vp]),
+    # Cohere: the interleaved f32 rotary embedding of q and k, the bias-free f32 LayerNorm (forward, backward), residual + attn + mlp
+    "dalm_rope_il_qk": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _int,
+                               _vp, _vp]),
+    "dalm_cohere_norm_fwd": (_int, [_vp, _vp, _int, _int, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "dalm_cohere_norm_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _i64, _i64, _vp, _vp, _vp]),
+    "dalm_add3_live": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _vp, _vp]),
     "dalm_bert_add_norm_fwd_live": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _f32, _f32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _vp]),
     "dalm_bert_add_norm_bwd_live": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),

@@ -343,6 +343,44 @@ def rope_sdpa(query, key, value, cos, sin, mask, scale: float, causal: bool):
     return _RopeSdpaHip.apply(query, key, value, cos, sin, mask, scale, causal)
 
 
+class _RopeIlSdpaHip(torch.autograd.Function):
+    """Cohere's interleaved rotary embedding of q and k (`dalm_rope_il_qk`, one launch) + the attention.  The rotary epilogues of
+    `dalm_attn_bwd` are Llama's half-split rotation, so the backward calls it WITHOUT tables - dq / dk then are the gradients of
+    the rotated q / k - and un-rotates them with one more `dalm_rope_il_qk` launch (backward = 1, in place).  Equal and grouped
+    heads, padded and packed; one key / value head is not routed here (`supported` / `grouped_supported` decline it)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, cos, sin, mask, scale, causal):
+        from . import tower_ops
+        from .. import live_rows
+
+        B, H, T, hd = q.shape
+        # dead (b, t) of a padded tower call leave the rotation as zeros (the attention kernels read finite values) and get zero
+        # gradients from the un-rotation
+        live = live_rows.current(B * T, q.device)
+        q2, k2 = tower_ops._rope_il_launch(q, k, cos, sin, False, live)
+        pk = _pack(mask, B, H, T, causal, q.dtype, q.device)
+        out, lse = _attn_forward(q2, k2, v, pk, scale, causal)
+        ctx.save_for_backward(q2, k2, v, out, lse, cos, sin, *([live] if live is not None else []))
+        ctx.pack, ctx.scale = pk, scale
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        from . import tower_ops
+
+        q2, k2, v, out, lse, cos, sin, *live = ctx.saved_tensors
+        dq, dk, dv = _attn_backward(q2, k2, v, out, lse, d_out, ctx.pack, ctx.scale)       # of the ROTATED q / k: no tables
+        dq, dk = tower_ops._rope_il_launch(dq, dk, cos, sin, True, live[0] if live else None, in_place=True)
+        return dq, dk, dv, None, None, None, None, None
+
+
+def rope_il_sdpa(query, key, value, cos, sin, mask, scale: float, causal: bool):
+    """sdpa(modeling_cohere.apply_rotary_pos_emb(query, key, cos, sin), value, ...) for what `node_supported` and
+    `tower_ops.rope_il_supported` accept."""
+    return _RopeIlSdpaHip.apply(query, key, value, cos, sin, mask, scale, causal)
+
+
 def _views_ok(*ts) -> bool:
     return all(t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:3]) and t.data_ptr() % 16 == 0 for t in ts)
 
@@ -738,8 +776,8 @@ def sdpa(query, key, value, mask, scale: float, causal: bool, dropout_p: float =
 
 
 def use_hip_attention_backward(model: torch.nn.Module) -> bool:
-    """Switch a Llama-family, Gemma, Arcee, OLMo-2, Granite, BERT or RoBERTa-family (roberta, xlm-roberta, camembert: BERT's layer
-    code) model of head width 32, 64 or 128 from "sdpa" to "dalm_sdpa".  xlm-roberta-xl (pre-LayerNorm layers) is not taken, and
+    """Switch a Llama-family, Gemma, Arcee, OLMo-2, Granite, Cohere, BERT or RoBERTa-family (roberta, xlm-roberta, camembert: BERT's
+    layer code) model of head width 32, 64 or 128 from "sdpa" to "dalm_sdpa".  xlm-roberta-xl (pre-LayerNorm layers) is not taken, and
     neither is a Gemma of head width 256 (every released checkpoint) or an Arcee of head width 80 (`ArceeConfig()`'s defaults;
     AFM-4.5B has 128): it keeps transformers' SDPA and does not pack.  Granite's softmax scale (`attention_multiplier`, not
     hd ** -0.5) reaches the kernels as the `scaling` argument of the attention call, like any other.  DALM_ATTN_KERNEL=0 disables."""
@@ -748,8 +786,8 @@ def use_hip_attention_backward(model: torch.nn.Module) -> bool:
     cfg = getattr(model, "config", None)
     if cfg is None or getattr(cfg, "_attn_implementation", None) != "sdpa":
         return False
-    if getattr(cfg, "model_type", "") not in ("llama", "mistral", "qwen2", "qwen3", "gemma", "arcee", "olmo2", "granite", "bert",
-                                              "roberta", "xlm-roberta", "camembert"):
+    if getattr(cfg, "model_type", "") not in ("llama", "mistral", "qwen2", "qwen3", "gemma", "arcee", "olmo2", "granite", "cohere",
+                                              "bert", "roberta", "xlm-roberta", "camembert"):
         return False
     hd = getattr(cfg, "head_dim", None) or (cfg.hidden_size // cfg.num_attention_heads)
     if hd not in _HEAD_DIMS or not register():

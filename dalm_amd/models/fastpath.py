@@ -237,11 +237,14 @@ def _swiglu_mlp_forward(self, x):
     return self.down_proj(self.act_fn(gate) * up)
 
 
-def use_swiglu_kernel(model: torch.nn.Module) -> int:
+def use_swiglu_kernel(model: torch.nn.Module, cohere: bool = False) -> int:
     """Patch the `*MLP` modules that are exactly transformers' LlamaMLP formula - down(act(gate(x)) * up(x)) with
     act = SiLU - to evaluate silu(gate) * up through `dalm_swiglu_{fwd,bwd}`: 2 eager launches forward and 4 backward
     become 1 + 1, and the [tokens, intermediate] activation is recomputed instead of saved (101 MB per layer at cfg3).
-    Same rounding points as the eager chain.  DALM_SWIGLU_KERNEL=0 disables; returns how many modules were patched."""
+    Same rounding points as the eager chain.  DALM_SWIGLU_KERNEL=0 disables; returns how many modules were patched.
+    `cohere`: also name CohereMLP (Llama's formula, behind the same value probe).  Off unless asked for: in the Cohere layer
+    measurements leaving the SwiGLU kernels out cost less than the run-to-run spread in two runs of three (profiles/cohere_bench.txt),
+    so the installer lists do not ask."""
     if _off("DALM_SWIGLU_KERNEL"):
         return 0
 
@@ -252,8 +255,8 @@ def use_swiglu_kernel(model: torch.nn.Module) -> int:
                 # a GraniteMLP with `mlp_bias` keeps transformers' code
                 and (type(mod).__name__ != "GraniteMLP" or _bias_free(mod, ("gate_proj", "up_proj", "down_proj"))))
 
-    return _install(model, ("LlamaMLP", "MistralMLP", "Qwen2MLP", "Qwen3MLP", "Olmo2MLP", "GraniteMLP"), gated_silu, _mlp_matches,
-                    _swiglu_mlp_forward)
+    names = ("LlamaMLP", "MistralMLP", "Qwen2MLP", "Qwen3MLP", "Olmo2MLP", "GraniteMLP", *(("CohereMLP",) if cohere else ()))
+    return _install(model, names, gated_silu, _mlp_matches, _swiglu_mlp_forward)
 
 
 def _bias_free(mod, names: tuple) -> bool:
@@ -1287,3 +1290,176 @@ _OLMO2_LAYER_BODY = ["residual = hidden_states", "hidden_states, _ = self.self_a
 _SOURCE_GUARDS["olmo2-layer"] = (
     lambda params, src: (params == _LLAMA_LAYER_PARAMS and _body(src)[-len(_OLMO2_LAYER_BODY):] == _OLMO2_LAYER_BODY
                          and _body(src)[-len(_OLMO2_LAYER_BODY) - 1].startswith(")")), _RESTATED)
+
+
+# ---------------------------------------------------------------------------
+# Cohere (Command-R, Aya): a parallel block behind one bias-free f32 LayerNorm, an interleaved f32 rotary embedding
+# ---------------------------------------------------------------------------
+def _cohere_norm_forward(self, hidden_states: torch.Tensor) -> torch.Tensor:
+    """CohereLayerNorm.forward with a weight [D] on `dalm_cohere_norm_{fwd,bwd}`; CPU tensors and unsupported widths run the class's
+    own statements."""
+    from . import tower_ops
+
+    if tower_ops.cohere_norm_supported(hidden_states, self.weight):
+        return tower_ops.cohere_norm_res(hidden_states, self.weight, float(self.variance_epsilon))[1]
+    return type(self).forward(self, hidden_states)
+
+
+def _cohere_norm_matches(mod: torch.nn.Module) -> bool:
+    """The module's OWN forward against F.layer_norm in f32 with one rounding (the formula the kernel implements; on a GPU the
+    patched forward, i.e. the HIP kernel) on a small random tensor with a mean, once per class, dtype and device type.  On a GPU an
+    f32 weight is probed under f32 AND bf16 activations: under autocast the kernel sees the latter.  Leaves `mod` as it is."""
+    w = mod.weight
+
+    def formula(m, x):
+        return F.layer_norm(x.float(), (x.shape[-1],), m.weight.float(), None, float(m.variance_epsilon)).to(x.dtype)
+
+    def probe():
+        g = torch.Generator().manual_seed(0)
+        x = 0.3 + 1.5 * torch.randn(4, 3, w.shape[0], generator=g)
+        # at the initialisation (ones) the weight tells nothing: the probe runs on a twin of the module with a weight of its own
+        twin = copy.copy(mod)
+        twin._parameters = dict(mod._parameters)
+        twin.weight = torch.nn.Parameter((1.0 + 0.5 * torch.randn(w.shape, generator=g)).to(device=w.device, dtype=w.dtype),
+                                         requires_grad=False)
+        x_dtypes = {w.dtype, torch.bfloat16} if w.is_cuda else {w.dtype}
+        with torch.no_grad():
+            return all(_close(formula(twin, xd), type(mod).forward(twin, xd), 2.0)
+                       and _close(_cohere_norm_forward(twin, xd), type(mod).forward(twin, xd), 2.0)
+                       for xd in (x.to(device=w.device, dtype=dt) for dt in sorted(x_dtypes, key=str)))
+
+    return _guard(("cohere-norm", type(mod), w.dtype, w.device.type), type(mod).__name__ + ".forward",
+                  "(w.float() * layer_norm(x.float())).to(x.dtype), without a bias, here", probe)
+
+
+def _cohere_layer_norm(mod) -> bool:
+    w = getattr(mod, "weight", None)
+    return w is not None and w.dim() == 1 and getattr(mod, "bias", None) is None and hasattr(mod, "variance_epsilon")
+
+
+def use_cohere_layer_norm(model: torch.nn.Module) -> int:
+    """Patch every CohereLayerNorm with a weight [D] that is still on its own forward (the final `model.norm`; a layer's
+    input_layernorm is read by `_cohere_layer_forward` directly) onto `dalm_cohere_norm_{fwd,bwd}`: one launch each way instead of
+    the f32 chain of ~9.  The [H, hd] q / k norms of `use_qk_norm` are left alone.  DALM_NORM_KERNEL=0 disables; returns the count."""
+    if _off("DALM_NORM_KERNEL"):
+        return 0
+    routed = {id(m.input_layernorm) for m in model.modules()
+              if getattr(getattr(m.forward, "__func__", None), "__name__", "") == "_cohere_layer_forward"}
+    return _install(model, ("CohereLayerNorm",), lambda mod: _cohere_layer_norm(mod) and id(mod) not in routed, _cohere_norm_matches,
+                    _cohere_norm_forward)
+
+
+def _cohere_layer_forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_values=None, use_cache=False,
+                          position_embeddings=None, **kwargs):
+    """transformers' CohereDecoderLayer.forward - n = input_layernorm(x); x + self_attn(n) + mlp(n) - with
+      input_layernorm: `dalm_cohere_norm_fwd`; its backward kernel also adds the gradient that reaches x through the residual path
+      the two adds   : `dalm_add3_live`, (residual + attention output) + mlp output, rounded as the eager pair rounds
+    A sub-block that answers in another dtype than the residual stream (autocast over f32 weights), or tensors the kernels do not
+    take, run the eager statement."""
+    from . import tower_ops
+
+    ln = self.input_layernorm
+    if not tower_ops.cohere_norm_supported(hidden_states, ln.weight):
+        return self._dalm_orig_forward(hidden_states, attention_mask=attention_mask, position_ids=position_ids,
+                                       past_key_values=past_key_values, use_cache=use_cache,
+                                       position_embeddings=position_embeddings, **kwargs)
+    residual, normed = tower_ops.cohere_norm_res(hidden_states, ln.weight, float(ln.variance_epsilon))
+    attn_out, _ = self.self_attn(hidden_states=normed, attention_mask=attention_mask, position_ids=position_ids,
+                                 past_key_values=past_key_values, use_cache=use_cache,
+                                 position_embeddings=position_embeddings, **kwargs)
+    mlp_out = self.mlp(normed)
+    if attn_out.dtype == residual.dtype == mlp_out.dtype and tower_ops.add3_live_supported(residual, attn_out, mlp_out):
+        return tower_ops.add3_live(residual, attn_out, mlp_out)
+    return residual + attn_out + mlp_out
+
+
+def use_cohere_layer(model: torch.nn.Module) -> int:
+    """Patch CohereDecoderLayer modules whose forward is, statement for statement, the code `_cohere_layer_forward` restates and
+    whose one norm is a CohereLayerNorm with a weight [D] that passes the value probe.  DALM_NORM_KERNEL=0 disables.  Returns how
+    many layers were patched."""
+    if _off("DALM_NORM_KERNEL"):
+        return 0
+
+    def one_norm(mod) -> bool:
+        ln = getattr(mod, "input_layernorm", None)
+        return (type(ln).__name__ == "CohereLayerNorm" and _cohere_layer_norm(ln) and not hasattr(mod, "post_attention_layernorm")
+                and all(hasattr(mod, a) for a in ("self_attn", "mlp")) and _cohere_norm_matches(ln))
+
+    return _install(model, ("CohereDecoderLayer",), one_norm, "cohere-layer", _cohere_layer_forward, keep="_dalm_orig_forward")
+
+
+# CohereDecoderLayer.forward: the whole body (a docstring stands in front of it: `_same_statements`)
+_COHERE_LAYER_BODY = ["residual = hidden_states", "hidden_states = self.input_layernorm(hidden_states)",
+                      "hidden_states_attention, _ = self.self_attn(", "hidden_states=hidden_states,", "attention_mask=attention_mask,",
+                      "position_ids=position_ids,", "past_key_values=past_key_values,", "use_cache=use_cache,",
+                      "position_embeddings=position_embeddings,", "**kwargs,", ")", "hidden_states_mlp = self.mlp(hidden_states)",
+                      "hidden_states = residual + hidden_states_attention + hidden_states_mlp", "return hidden_states"]
+_SOURCE_GUARDS["cohere-layer"] = (
+    lambda params, src: params == _LLAMA_LAYER_PARAMS and _same_statements(src, _COHERE_LAYER_BODY), _RESTATED)
+
+
+def _cohere_attention_forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
+    """transformers' CohereAttention.forward for the training call ("dalm_sdpa", no q / k norm, no biases, no KV cache, no dropout):
+    the same statements with apply_rotary_pos_emb + the attention call as one node (`attention.rope_il_sdpa`: `dalm_rope_il_qk`
+    forward, the attention, and one more `dalm_rope_il_qk` launch that un-rotates dq / dk).  Tensors the attention kernels do not
+    take but the rotary kernel does (f32; grouped heads of width 32) get the rotary kernel as a node of its own in front of the
+    attention call.  Every other call goes to transformers' own forward."""
+    from . import attention, tower_ops
+
+    cfg = self.config
+    if (getattr(self, "use_qk_norm", False) or not _bias_free(self, _QKVO)
+            or past_key_values is not None or position_embeddings is None or getattr(cfg, "_attn_implementation", None) != attention.NAME
+            or (self.training and float(getattr(self, "attention_dropout", 0.0)) != 0.0)
+            or _off("DALM_FAST_ROPE") or _off("DALM_ATTN_KERNEL") or kwargs.get("output_attentions")):
+        return self._dalm_orig_attn_forward(hidden_states, position_embeddings=position_embeddings, attention_mask=attention_mask,
+                                            past_key_values=past_key_values, **kwargs)
+    input_shape = hidden_states.shape[:-1]
+    hidden_shape = (*input_shape, -1, self.head_dim)
+    query_states = self.q_proj(hidden_states).view(hidden_shape).transpose(1, 2)
+    key_states = self.k_proj(hidden_states).view(hidden_shape).transpose(1, 2)
+    value_states = self.v_proj(hidden_states).view(hidden_shape).transpose(1, 2)
+    cos, sin = position_embeddings
+    if not tower_ops.rope_il_supported(query_states, key_states, cos, sin):     # CPU tensors, ...: the class's own statements
+        return self._dalm_orig_attn_forward(hidden_states, position_embeddings=position_embeddings, attention_mask=attention_mask,
+                                            past_key_values=past_key_values, **kwargs)
+    causal = bool(query_states.shape[2] > 1 and attention_mask is None and getattr(self, "is_causal", True))
+    if attention.node_supported(query_states, key_states, value_states, attention_mask, causal):
+        attn_output = attention.rope_il_sdpa(query_states, key_states, value_states, cos, sin, attention_mask, float(self.scaling),
+                                             causal).transpose(1, 2)
+    else:
+        from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
+
+        query_states, key_states = tower_ops.rope_il_qk(query_states, key_states, cos, sin)
+        attn_output, _ = ALL_ATTENTION_FUNCTIONS[cfg._attn_implementation](
+            self, query_states, key_states, value_states, attention_mask, dropout=0.0, scaling=self.scaling, **kwargs)
+    attn_output = attn_output.reshape(*input_shape, -1).contiguous()
+    return self.o_proj(attn_output), None
+
+
+def use_cohere_attention_node(model: torch.nn.Module) -> int:
+    """Patch CohereAttention modules of a model that runs on "dalm_sdpa" (models/attention.py) and whose forward is, statement for
+    statement, the code `_cohere_attention_forward` restates.  A module with `use_qk_norm` or biased projections is patched too and
+    runs transformers' own forward at call time.  Returns the count."""
+    return _use_attention_node(model, "CohereAttention", (*_QKVO, "scaling", "head_dim", "use_qk_norm"), "cohere-attn",
+                               _cohere_attention_forward)
+
+
+# CohereAttention.forward: the whole body
+_COHERE_ATTN_BODY = [
+    "input_shape = hidden_states.shape[:-1]", "hidden_shape = (*input_shape, -1, self.head_dim)",
+    "query_states = self.q_proj(hidden_states).view(hidden_shape)", "key_states = self.k_proj(hidden_states).view(hidden_shape)",
+    "value_states = self.v_proj(hidden_states).view(hidden_shape)",
+    "if self.use_qk_norm:", "    query_states = self.q_norm(query_states)", "    key_states = self.k_norm(key_states)",
+    "query_states = query_states.transpose(1, 2)", "key_states = key_states.transpose(1, 2)",
+    "value_states = value_states.transpose(1, 2)", "cos, sin = position_embeddings",
+    "query_states, key_states = apply_rotary_pos_emb(query_states, key_states, cos, sin)",
+    "if past_key_values is not None:",
+    "    key_states, value_states = past_key_values.update(key_states, value_states, self.layer_idx)",
+    "attention_interface: Callable = ALL_ATTENTION_FUNCTIONS.get_interface(",
+    "    self.config._attn_implementation, eager_attention_forward", ")",
+    "attn_output, attn_weights = attention_interface(", "    self,", "    query_states,", "    key_states,", "    value_states,",
+    "    attention_mask,", "    dropout=0.0 if not self.training else self.attention_dropout,", "    scaling=self.scaling,",
+    "    **kwargs,", ")", "attn_output = attn_output.reshape(*input_shape, -1).contiguous()",
+    "attn_output = self.o_proj(attn_output)", "return attn_output, attn_weights"]
+_SOURCE_GUARDS["cohere-attn"] = (
+    lambda params, src: params == _LLAMA_ATTN_PARAMS and _same_statements(src, _COHERE_ATTN_BODY), _RESTATED)

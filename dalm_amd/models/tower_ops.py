@@ -10,7 +10,8 @@ Also here: RMSNorm with the residual add, Qwen3's head norm + rotary, Gemma's Ge
 `dalm_gemma_norm_*`: modeling_gemma.py `GemmaMLP.forward`, `GemmaRMSNorm.forward`), Arcee's ReLU^2 (`dalm_relu2_*`: modeling_arcee.py
 `ArceeMLP.forward`), OLMo-2's norm-then-add and row-wide q / k norm + rotary (`dalm_norm_add_*`, `dalm_row_norm_*`: modeling_olmo2.py),
 Granite's scaled residual add with and without the norm behind it (`dalm_rms_norm_scaled_*`, `dalm_scale_add`: modeling_granite.py
-`GraniteDecoderLayer.forward`), and Falcon's layer ops.
+`GraniteDecoderLayer.forward`), Cohere's interleaved f32 rotary embedding, f32 LayerNorm and three-way add (`dalm_rope_il_qk`,
+`dalm_cohere_norm_*`, `dalm_add3_live`: modeling_cohere.py), and Falcon's layer ops.
 
 GPU tensors only: the callers in `fastpath.py` keep transformers' own code for CPU tensors.
 """
@@ -333,6 +334,179 @@ def scale_add(res, x, mult, live=None):
     """res + x * mult in one launch - the product rounded to the dtype first, as the eager pair rounds - or x * mult with res None.
     live: uint8 row liveness; None: that of the tower call in progress (dalm_amd/live_rows.py), if any."""
     return _ScaleAdd.apply(res, x, mult, live)
+
+
+# ---------------------------------------------------------------------------
+# Cohere (modeling_cohere.py): the interleaved rotary embedding computed in f32 (dalm_rope_il_qk), CohereLayerNorm - bias-free, f32,
+# one rounding - with the residual-path gradient folded into its backward (dalm_cohere_norm_{fwd,bwd}), and the parallel block's
+# `residual + attn + mlp` (dalm_add3_live)
+# ---------------------------------------------------------------------------
+_ROPE_IL_DIMS = (32, 64, 128)
+
+
+def _il_strides(t: torch.Tensor, n: int) -> list:
+    """The first n strides, a dimension of size 1 counted as stride 0 (whatever torch kept there is never multiplied with anything)."""
+    return [t.stride(i) if t.shape[i] > 1 else 0 for i in range(n)]
+
+
+def rope_il_supported(q, k, cos, sin) -> bool:
+    """What `dalm_rope_il_qk` takes: q / k [B, H, T, hd] f32 or bf16 GPU views with a contiguous last dimension, 16-byte aligned rows,
+    head width 32, 64 or 128; cos / sin [B or 1, T, hd] of the activations' dtype or f32, laid out alike, no gradient."""
+    if not (q.is_cuda and q.dim() == 4 and k.dim() == 4 and cos.dim() == 3 and sin.shape == cos.shape
+            and q.dtype in (torch.float32, torch.bfloat16) and k.dtype == q.dtype and cos.dtype in (q.dtype, torch.float32)
+            and sin.dtype == cos.dtype and q.shape[-1] in _ROPE_IL_DIMS and k.shape[-1] == q.shape[-1]
+            and q.shape[0] == k.shape[0] and q.shape[2] == k.shape[2] and q.numel() > 0 and k.numel() > 0
+            and cos.shape[0] in (1, q.shape[0]) and cos.shape[1:] == (q.shape[2], q.shape[3])
+            and sin.stride() == cos.stride() and not cos.requires_grad and not sin.requires_grad):
+        return False
+    vec = 16 // q.element_size()
+    return (all(t.stride(-1) == 1 and t.data_ptr() % 16 == 0 for t in (q, k, cos, sin))
+            and all(s % vec == 0 for t, n in ((q, 3), (k, 3), (cos, 2)) for s in _il_strides(t, n)))
+
+
+def _rope_il_launch(q, k, cos, sin, backward: bool, live=None, in_place: bool = False):
+    """One `dalm_rope_il_qk` launch over what `rope_il_supported` took.  in_place: the results overwrite q and k (a lane reads the
+    16 bytes it writes and no others) - the un-rotation of gradients nobody else holds."""
+    hip.require_gpu(q, k, cos, sin)
+    if in_place:
+        qo, ko = q, k
+    else:
+        qo, ko = torch.empty_like(q), torch.empty_like(k)       # preserve_format: same strides as the (dense) views
+        if qo.stride(-1) != 1 or ko.stride(-1) != 1:            # overlapping / exotic input layout: plain contiguous outputs
+            qo = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+            ko = torch.empty(k.shape, dtype=k.dtype, device=k.device)
+    B, Hq, T, hd = q.shape
+    s3 = lambda t: (C.c_int64 * 3)(*_il_strides(t, 3))  # noqa: E731
+    hip.call("dalm_rope_il_qk", hip.ptr(q), hip.ptr(k), hip.ptr(qo), hip.ptr(ko), hip.ptr(cos), hip.ptr(sin), hip.dtype_code(q),
+             hip.dtype_code(cos), B, T, Hq, k.shape[1], hd, s3(q), s3(k), s3(qo), s3(ko), (C.c_int64 * 2)(*_il_strides(cos, 2)),
+             int(backward), hip.ptr(live), hip.stream())
+    return qo, ko
+
+
+def _il_gradient(g: torch.Tensor) -> torch.Tensor:
+    vec = 16 // g.element_size()
+    ok = g.stride(-1) == 1 and g.data_ptr() % 16 == 0 and all(s % vec == 0 for s in _il_strides(g, 3))
+    return g if ok else g.contiguous()
+
+
+class _RopeIlQK(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, cos, sin, live=None):
+        if live is None:
+            live = live_rows.current(q.shape[0] * q.shape[2], q.device)
+        ctx.save_for_backward(cos, sin, *([live] if live is not None else []))   # the backward runs after the tower call's context
+        return _rope_il_launch(q, k, cos, sin, False, live)
+
+    @staticmethod
+    def backward(ctx, gq, gk):
+        cos, sin, *live = ctx.saved_tensors
+        dq, dk = _rope_il_launch(_il_gradient(gq), _il_gradient(gk), cos, sin, True, live[0] if live else None)
+        return dq, dk, None, None, None
+
+
+def rope_il_qk(q, k, cos, sin, live=None):
+    """modeling_cohere.py's apply_rotary_pos_emb - (x.float() * cos + rotate_half(x.float()) * sin).to(dtype) with the interleaved
+    rotate_half - for q and k in one launch, one more backward; values and gradients are the eager chain's, bit for bit.
+    live: uint8 [B T] row liveness; None: that of the tower call in progress (dalm_amd/live_rows.py), if any."""
+    return _RopeIlQK.apply(q, k, cos, sin, live)
+
+
+def cohere_norm_supported(x: torch.Tensor, w: torch.Tensor) -> bool:
+    """What `dalm_cohere_norm_*` take: `rms_norm_supported`'s widths, at least one row; the weight [D], f32 or bf16 under either
+    activation dtype (CohereLayerNorm computes in f32 and casts once, whatever the weight's dtype is)."""
+    D = x.shape[-1] if x.dim() else 0
+    vec = 4 if x.dtype == torch.float32 else 8
+    return (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and x.numel() > 0 and w.is_cuda and w.dim() == 1
+            and w.shape[0] == D and w.dtype in (torch.float32, torch.bfloat16) and w.is_contiguous() and w.data_ptr() % 16 == 0
+            and D % vec == 0 and D <= 64 * vec * 16)
+
+
+class _CohereNormRes(torch.autograd.Function):
+    """(x, y) = (x, CohereLayerNorm(x)); x is handed back so that the gradient reaching it through the residual path is added INSIDE
+    the norm's backward kernel (as `_AddRmsNorm` with delta None)."""
+
+    @staticmethod
+    def forward(ctx, x, w, eps, live=None):
+        D = x.shape[-1]
+        x2 = _as_rows(x, D, x.dtype)
+        R = x2.shape[0]
+        if live is None:
+            live = live_rows.current(R, x2.device)
+        w = w.detach()
+        y2 = torch.empty_like(x2)
+        mean = torch.empty(R, device=x2.device, dtype=torch.float32)
+        rstd = torch.empty(R, device=x2.device, dtype=torch.float32)
+        hip.call("dalm_cohere_norm_fwd", hip.ptr(x2), hip.ptr(w), hip.dtype_code(x2), hip.dtype_code(w), R, D, float(eps), hip.ptr(y2),
+                 hip.ptr(mean), hip.ptr(rstd), hip.ptr(live), hip.stream())
+        # (the liveness vector is kept: the backward runs after the tower call's context, on autograd's thread)
+        ctx.save_for_backward(x2, w, mean, rstd, *([live] if live is not None else []))
+        ctx.shape, ctx.eps = x.shape, float(eps)
+        ctx.set_materialize_grads(False)           # no residual-path gradient: the backward kernel reads none, not a tensor of zeros
+        return x, y2.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dres, dy):
+        if dy is None:
+            return dres, None, None, None
+        x2, w, mean, rstd, *keep = ctx.saved_tensors
+        live = keep[0] if keep else None
+        R, D = x2.shape
+        dy2 = _as_rows(dy, D, x2.dtype)
+        dres2 = _as_rows(dres, D, x2.dtype) if dres is not None else None
+        dx = torch.empty_like(x2)
+        hip.call("dalm_cohere_norm_bwd", hip.ptr(dy2), hip.ptr(x2), hip.ptr(w), hip.ptr(mean), hip.ptr(rstd), hip.ptr(dres2),
+                 hip.dtype_code(x2), hip.dtype_code(w), R, D, hip.ptr(dx), hip.ptr(live), hip.stream())
+        dw = None
+        if ctx.needs_input_grad[1]:
+            # sum over the rows of dy * xh, formed by torch.  A rare path (LoRA freezes the norm weights), so it is taken in
+            # float64 from x itself: rounded once, whatever the number of rows
+            xd = x2.double()
+            xd = xd - xd.mean(1, keepdim=True)
+            prod = dy2.double() * (xd * torch.rsqrt(xd.pow(2).mean(1, keepdim=True) + ctx.eps))
+            if live is not None:                   # dead rows: dy and x are whatever their producers left
+                prod = prod.masked_fill((live == 0).unsqueeze(1), 0.0)
+            dw = prod.sum(0).to(w.dtype)
+        return dx.view(ctx.shape), dw, None, None
+
+
+def cohere_norm_res(x, w, eps, live=None):
+    """(x itself, CohereLayerNorm(x)): one launch forward, one backward (which also folds in the residual-path gradient).
+    live: uint8 row liveness; None: that of the tower call in progress (dalm_amd/live_rows.py), if any."""
+    return _CohereNormRes.apply(x, w, eps, live)
+
+
+def add3_live_supported(res, a, b) -> bool:
+    """What `dalm_add3_live` takes: three f32 or bf16 GPU tensors of one shape and dtype, rows a multiple of 16 bytes wide (no upper
+    limit)."""
+    vec = 4 if res.dtype == torch.float32 else 8
+    return (res.is_cuda and res.dtype in (torch.float32, torch.bfloat16) and res.dim() >= 1 and res.shape[-1] % vec == 0
+            and 0 < res.numel() // vec < 2 ** 31
+            and all(t.is_cuda and t.dtype == res.dtype and t.shape == res.shape for t in (a, b)))
+
+
+class _Add3Live(torch.autograd.Function):
+    """(res + a) + b, one launch; the backward hands the incoming gradient to all three without a launch."""
+
+    @staticmethod
+    def forward(ctx, res, a, b, live=None):
+        D = res.shape[-1]
+        r2, a2, b2 = (_as_rows(t, D, res.dtype) for t in (res, a, b))
+        if live is None:
+            live = live_rows.current(r2.shape[0], r2.device)
+        out = torch.empty_like(r2)
+        hip.call("dalm_add3_live", hip.ptr(r2), hip.ptr(a2), hip.ptr(b2), hip.ptr(out), hip.dtype_code(r2), r2.shape[0], D,
+                 hip.ptr(live), hip.stream())
+        return out.view(res.shape)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, g, g, None
+
+
+def add3_live(res, a, b, live=None):
+    """res + a + b as eager evaluates it - the first sum rounded to the dtype, then the second - in one launch.
+    live: uint8 row liveness; None: that of the tower call in progress (dalm_amd/live_rows.py), if any."""
+    return _Add3Live.apply(res, a, b, live)
 
 
 # ---------------------------------------------------------------------------

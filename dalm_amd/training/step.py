@@ -38,17 +38,20 @@ def _advance_dropout(batch) -> None:
 
 def _logits_scaled(hidden: torch.Tensor, generator_model) -> torch.Tensor:
     """Hidden states that meet `lm_head.weight` WITHOUT the generator's own forward (fuse_lm_head, the packed route), for a generator
-    whose forward scales its logits: GraniteForCausalLM returns `lm_head(h) / config.logits_scaling`.  The head is linear and has no
-    bias on these routes, so the factor 1 / logits_scaling goes onto h in front of it - exact for the released powers of two (8,
-    16), one rounding of h in its dtype otherwise.  On the GPU one `dalm_scale_add` launch each way."""
-    s = getattr(getattr(generator_model, "config", None), "logits_scaling", None)
-    if s is None or float(s) == 1.0:
+    whose forward scales its logits: GraniteForCausalLM returns `lm_head(h) / config.logits_scaling`, CohereForCausalLM
+    `lm_head(h) * config.logit_scale`.  The head is linear and has no bias on these routes, so the factor goes onto h in front of
+    it - exact for the released powers of two (Granite 8, 16; Cohere 0.0625), one rounding of h in its dtype otherwise.  On the
+    GPU one `dalm_scale_add` launch each way."""
+    cfg = getattr(generator_model, "config", None)
+    div, mul = getattr(cfg, "logits_scaling", None), getattr(cfg, "logit_scale", None)
+    s = (1.0 if div is None else 1.0 / float(div)) * (1.0 if mul is None else float(mul))
+    if s == 1.0:
         return hidden
     from ..models import tower_ops
 
     if tower_ops.scale_add_supported(hidden):
-        return tower_ops.scale_add(None, hidden, 1.0 / float(s))
-    return hidden * (1.0 / float(s))
+        return tower_ops.scale_add(None, hidden, s)
+    return hidden * s
 
 
 class _StepBase:

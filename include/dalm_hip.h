@@ -656,6 +656,47 @@ int dalm_rms_norm_scaled_bwd(const void* dy, const void* h, const void* w, const
 int dalm_scale_add(const void* res, const void* x, float mult, void* out, int dtype, int64_t R, int64_t D, const uint8_t* row_live,
                    dalm_stream_t stream);
 
+/* Cohere (modeling_cohere.py; `model_type` "cohere": Command-R, Aya): a parallel block behind one norm,
+ * `n = input_layernorm(x); out = x + self_attn(n) + mlp(n)`, whose rotary embedding is INTERLEAVED and computed in f32 and whose
+ * norm is a bias-free LayerNorm computed in f32.  round = the one rounding to `dtype` (the identity for f32); row_live as under
+ * Row liveness, above: nothing of a dead row is loaded, freshly written outputs hold zeros there, live rows receive the same bits
+ * as without the vector.
+ *   dalm_rope_il_qk: apply_rotary_pos_emb of modeling_cohere.py for q and k in one launch, and (backward != 0) its autograd
+ *        backward.  Conventions of dalm_rope_qk_live: q / k / outputs [B, H, T, hd] views with element strides {b, h, t} and a
+ *        contiguous last dimension (q with Hq heads, k with Hk; column slices of one q|k|v GEMM output are read in place); cos / sin
+ *        [B or 1, T, hd] with element strides {b, t} (b = 0 for one table); row_live [B T] bytes or NULL.  `tab_dtype` is the
+ *        tables' dtype: `dtype`, or DALM_F32 beside bf16 activations (autocast over f32 weights) (else DALM_E_DTYPE).
+ *        forward :  out[2i]   = round(f32(x[2i]) f32(cos[2i])     - f32(x[2i+1]) f32(sin[2i]))
+ *                   out[2i+1] = round(f32(x[2i+1]) f32(cos[2i+1]) + f32(x[2i]) f32(sin[2i+1]))
+ *        backward:  dx[2i]    = round(f32(g[2i]) f32(cos[2i])     + f32(g[2i+1]) f32(sin[2i+1]))
+ *                   dx[2i+1]  = round(f32(g[2i+1]) f32(cos[2i+1]) - f32(g[2i]) f32(sin[2i]))
+ *        Each product and the sum is rounded to f32 on its own (no fused multiply-add): the values of the eager chain and of its
+ *        autograd backward, bit for bit.  cos[2i] and cos[2i+1] are both read: they need not be equal.  q_out may be q and k_out
+ *        k (a lane reads the 16 bytes it writes and no others).  hd = 32, 64 or 128 and
+ *        B T (Hq + Hk) hd / (16 bytes) < 2^31 (DALM_E_SHAPE); 16-byte aligned tensors and every stride a multiple of 16 bytes of
+ *        `dtype` (8 elements for bf16, 4 for f32) (DALM_E_ALIGN).
+ *   dalm_cohere_norm_fwd / dalm_cohere_norm_bwd: CohereLayerNorm, one wave per row, [R, D] row-major, the D rules of
+ *        dalm_rms_norm_* (a multiple of 16 bytes of `dtype`, at most 8192 (bf16) / 4096 (f32), R > 0: DALM_E_SHAPE); `w_dtype` is the
+ *        weight's own dtype, f32 or bf16 under either activation dtype; 16-byte aligned tensors (DALM_E_ALIGN).
+ *        fwd: mean [R] f32 = mean_d(x);  rstd [R] f32 = rsqrt(mean_d((x - mean)^2) + eps);  y = round(f32(w) ((x - mean) rstd)) -
+ *             f32 throughout, no rounding in between; mean and rstd are kept for the backward.
+ *        bwd: g = f32(dy) f32(w);  xh = (x - mean) rstd;  dx = round(rstd (g - mean_d(g) - xh mean_d(g xh)) [+ dres]); dres, the
+ *             gradient that reaches x through the residual path, may be NULL.  No weight gradient is produced.
+ *   dalm_add3_live: out = round(round(res + a) + b) - eager's `residual + attn + mlp` - over [R, D] contiguous rows, D a multiple of
+ *        16 bytes of `dtype` with no upper limit, R D / (16 bytes) < 2^31 (DALM_E_SHAPE); 16-byte aligned tensors (DALM_E_ALIGN).
+ *        R == 0 or D == 0: nothing to do, 0.  (dalm_add3, further down, is Falcon's: bf16, flat, the other association.)
+ * The checks run before anything is enqueued: a rejected call writes nothing. */
+int dalm_rope_il_qk(const void* q, const void* k, void* q_out, void* k_out, const void* cos, const void* sin, int dtype,
+                    int tab_dtype, int64_t B, int64_t T, int64_t Hq, int64_t Hk, int64_t hd, const int64_t* q_strides,
+                    const int64_t* k_strides, const int64_t* qo_strides, const int64_t* ko_strides, const int64_t* cs_strides,
+                    int backward, const uint8_t* row_live, dalm_stream_t stream);
+int dalm_cohere_norm_fwd(const void* x, const void* w, int dtype, int w_dtype, int64_t R, int64_t D, float eps, void* y, float* mean,
+                         float* rstd, const uint8_t* row_live, dalm_stream_t stream);
+int dalm_cohere_norm_bwd(const void* dy, const void* x, const void* w, const float* mean, const float* rstd, const void* dres,
+                         int dtype, int w_dtype, int64_t R, int64_t D, void* dx, const uint8_t* row_live, dalm_stream_t stream);
+int dalm_add3_live(const void* res, const void* a, const void* b, void* out, int dtype, int64_t R, int64_t D, const uint8_t* row_live,
+                   dalm_stream_t stream);
+
 /* Elementwise chains of a Falcon-7B decoder layer (transformers modeling_falcon.py FalconDecoderLayer.forward /
  * FalconMLP.forward / dropout_add, reached by the reference through self.generator_model(...),
  * dalm/models/rag_e2e_base_model.py:104-106; BASELINE.json config 5).  bf16 tensors, 16-byte aligned.

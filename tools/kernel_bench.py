@@ -672,6 +672,103 @@ def bench_scaled_add_norm(R, D, mult=0.22, rounds=3):
     return out
 
 
+def _no_grad(fn, *a):
+    def run():
+        with torch.no_grad():
+            return fn(*a)
+    return run
+
+
+def bench_cohere_norm(R, D, rounds=3):
+    """CohereLayerNorm on [R, D] bf16 rows with the residual-path gradient folded into the backward: `dalm_cohere_norm_fwd` /
+    `dalm_cohere_norm_bwd`, and beside them - alternating, in the same process - transformers' CohereLayerNorm.forward (an f32 chain)
+    with autograd's backward, in which the gradient through the residual path meets the norm's.  Algorithmic bytes: forward 2 R D
+    elements (x in, y out), backward 4 R D (dy, x, dres in; dx out)."""
+    from transformers.models.cohere.modeling_cohere import CohereLayerNorm
+
+    from dalm_amd import hip
+    from dalm_amd.models import tower_ops
+
+    dev = torch.device("cuda:0")
+    x, gy, gh = (torch.randn(R, D, device=dev, dtype=torch.bfloat16) for _ in range(3))
+    norm = CohereLayerNorm(D, eps=1e-5).to(dev).to(torch.bfloat16).requires_grad_(False)
+    with torch.no_grad():
+        norm.weight.copy_(1.0 + 0.1 * torch.randn(D, device=dev))
+    w = norm.weight
+    assert tower_ops.cohere_norm_supported(x, w)
+    mean = x.float().mean(-1)
+    rstd = torch.rsqrt(x.float().var(-1, unbiased=False) + 1e-5)
+    dx = torch.empty_like(x)
+    xd = x.clone().requires_grad_(True)
+
+    def kernel_bwd():
+        hip.call("dalm_cohere_norm_bwd", hip.ptr(gy), hip.ptr(x), hip.ptr(w), hip.ptr(mean), hip.ptr(rstd), hip.ptr(gh), hip.dtype_code(x),
+                 hip.dtype_code(w), R, D, hip.ptr(dx), None, hip.stream())
+
+    n = R * D * 2
+    fns = {"kernel fwd (1 launch)": _no_grad(tower_ops.cohere_norm_res, x, w, 1e-5), "kernel bwd (1 launch)": kernel_bwd,
+           "eager fwd (f32 chain)": _no_grad(norm, x),
+           "eager fwd + autograd bwd": lambda: torch.autograd.grad((xd.view_as(xd), norm(xd)), (xd,), (gh, gy))}
+    out = _alternating(fns, {"kernel fwd (1 launch)": 2 * n + 8 * R, "kernel bwd (1 launch)": 4 * n + 8 * R, "eager fwd (f32 chain)": 2 * n,
+                             "eager fwd + autograd bwd": 6 * n}, rounds)
+    k, e = out["kernel fwd (1 launch)"]["s"] + out["kernel bwd (1 launch)"]["s"], out["eager fwd + autograd bwd"]["s"]
+    out["kernel fwd + bwd against eager"] = {"kernel_s": k, "eager_s": e, "eager_over_kernel": e / k}
+    return out
+
+
+def bench_rope_il(B, T, Hq, Hk, hd, rounds=3):
+    """Cohere's interleaved rotary embedding computed in f32: `dalm_rope_il_qk` forward and backward on the q | k column slices of one
+    [B T, (Hq + 2 Hk) hd] bf16 buffer, and beside them - alternating, in the same process - modeling_cohere.py's apply_rotary_pos_emb
+    with autograd's backward.  Algorithmic bytes: 2 (|q| + |k|) elements each way (+ the tables, shared by all heads)."""
+    from transformers.models.cohere.modeling_cohere import apply_rotary_pos_emb
+
+    from dalm_amd.models import tower_ops
+
+    dev = torch.device("cuda:0")
+    W = (Hq + 2 * Hk) * hd
+    buf = torch.randn(B, T, W, device=dev, dtype=torch.bfloat16)
+    q = buf[..., :Hq * hd].view(B, T, Hq, hd).transpose(1, 2)
+    k = buf[..., Hq * hd:(Hq + Hk) * hd].view(B, T, Hk, hd).transpose(1, 2)
+    inv = 1.0 / (10000.0 ** (torch.arange(0, hd, 2, device=dev).float() / hd))
+    emb = torch.repeat_interleave(torch.arange(T, device=dev).float()[None, :, None] * inv, 2, dim=-1)
+    cos, sin = emb.cos().to(torch.bfloat16), emb.sin().to(torch.bfloat16)
+    assert tower_ops.rope_il_supported(q, k, cos, sin)
+    gq, gk = torch.randn(B, T, Hq, hd, device=dev, dtype=torch.bfloat16).transpose(1, 2), \
+        torch.randn(B, T, Hk, hd, device=dev, dtype=torch.bfloat16).transpose(1, 2)
+    qf, kf = buf[..., :Hq * hd], buf[..., Hq * hd:(Hq + Hk) * hd]
+    qg, kg = qf.detach().clone().requires_grad_(True), kf.detach().clone().requires_grad_(True)        # dense leaves for autograd
+
+    def eager_both():
+        oq, ok = apply_rotary_pos_emb(qg.view(B, T, Hq, hd).transpose(1, 2), kg.view(B, T, Hk, hd).transpose(1, 2), cos, sin)
+        return torch.autograd.grad((oq, ok), (qg, kg), (gq, gk))
+
+    b = 2 * B * T * (Hq + Hk) * hd * 2 + 2 * T * hd * 2
+    fns = {"kernel fwd (1 launch)": lambda: tower_ops._rope_il_launch(q, k, cos, sin, False),
+           "kernel bwd (1 launch, in place)": lambda: tower_ops._rope_il_launch(gq, gk, cos, sin, True, None, in_place=True),
+           "eager fwd (f32 chain)": _no_grad(apply_rotary_pos_emb, q, k, cos, sin),
+           "eager fwd + autograd bwd": eager_both}
+    out = _alternating(fns, {name: (2 * b if "+" in name else b) for name in fns}, rounds)
+    k_s, e = out["kernel fwd (1 launch)"]["s"] + out["kernel bwd (1 launch, in place)"]["s"], out["eager fwd + autograd bwd"]["s"]
+    out["kernel fwd + bwd against eager"] = {"kernel_s": k_s, "eager_s": e, "eager_over_kernel": e / k_s}
+    return out
+
+
+def bench_add3(R, D, rounds=3):
+    """Cohere's `residual + attn + mlp` on [R, D] bf16 rows: `dalm_add3_live` (its backward hands the gradient on: no launch) against
+    the eager pair of adds.  Algorithmic bytes: 4 R D elements."""
+    from dalm_amd.models import tower_ops
+
+    dev = torch.device("cuda:0")
+    r, a, b = (torch.randn(R, D, device=dev, dtype=torch.bfloat16) for _ in range(3))
+    assert tower_ops.add3_live_supported(r, a, b)
+    n = R * D * 2
+    fns = {"kernel (1 launch)": _no_grad(tower_ops.add3_live, r, a, b), "eager (2 launches)": _no_grad(lambda x, y, z: x + y + z, r, a, b)}
+    out = _alternating(fns, {"kernel (1 launch)": 4 * n, "eager (2 launches)": 4 * n}, rounds)
+    out["kernel against eager"] = {"kernel_s": out["kernel (1 launch)"]["s"], "eager_s": out["eager (2 launches)"]["s"],
+                                   "eager_over_kernel": out["eager (2 launches)"]["s"] / out["kernel (1 launch)"]["s"]}
+    return out
+
+
 def bench_row_norm_rope(B, T, Hq, Hk, hd, rounds=3):
     """OLMo-2's q_norm / k_norm over the whole projection width + rotary embedding: `dalm_row_norm_rope_fwd` / `dalm_row_norm_bwd` on
     the q | k column slices of one [B T, (Hq + 2 Hk) hd] bf16 buffer, and beside them - alternating, in the same process - what runs
@@ -829,6 +926,14 @@ def main():
     if args.only in ("", "scaled_add_norm"):
         res["scaled_add_norm Granite-2B rows 4608 x 2048 bf16"] = bench_scaled_add_norm(4608, 2048)
         res["scaled_add_norm Granite-8B rows 4608 x 4096 bf16"] = bench_scaled_add_norm(4608, 4096)
+    # the headline batch's rows at a Cohere 8B-class layer shape: hidden 4096, 32 x 128 heads over 8 key / value heads
+    if args.only in ("", "cohere_norm"):
+        res["cohere_norm rows 4608 x 4096 bf16"] = bench_cohere_norm(4608, 4096)
+    if args.only in ("", "rope_il"):
+        res["rope_il generator rows 18x256, 32+8 heads x 128"] = bench_rope_il(18, 256, 32, 8, 128)
+        res["rope_il packed rows 1x3008, 32+8 heads x 128"] = bench_rope_il(1, 3008, 32, 8, 128)
+    if args.only in ("", "add3"):
+        res["add3 rows 4608 x 4096 bf16"] = bench_add3(4608, 4096)
     Path("gpurun_out").mkdir(exist_ok=True)
     Path("gpurun_out/kernel_bench.json").write_text(json.dumps(res, indent=1))
     print_results(res)
