@@ -20,7 +20,8 @@
 // formulas - GeGLU and the (1 + w) RMSNorm (dalm_geglu_*, dalm_gemma_norm_*) - Arcee's ReLU^2 (dalm_relu2_*), and OLMo-2's norm-then-add
 // and row-wide q / k norm + rotary (dalm_norm_add_*, dalm_row_norm_*), and Granite's scaled residual add with and without the norm
 // behind it (dalm_rms_norm_scaled_*, dalm_scale_add), and Cohere's interleaved f32 rotary embedding, bias-free f32 LayerNorm and
-// three-way residual add (dalm_rope_il_qk, dalm_cohere_norm_*, dalm_add3_live), each with its own comment block.
+// three-way residual add (dalm_rope_il_qk, dalm_cohere_norm_*, dalm_add3_live), and Phi-3's partial rotary embedding
+// (dalm_rope_partial_qk), each with its own comment block.
 #include "dispatch.hpp"
 #include "relu2_math.hpp"
 #include "swiglu_math.hpp"
@@ -2142,6 +2143,77 @@ __global__ __launch_bounds__(256) void rope_il_kernel(const RopeIlParams p) {
   Vec16<T>::store(o, out);                           // rounded once
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Phi-3 / Phi-4 (modeling_phi3.py apply_rotary_pos_emb): only the first `rot` = cos.shape[-1] elements of a head rotate, half-split
+// WITHIN those rot (i pairs with i + rot/2); the other hd - rot pass through.  The pair gets rope_qk_kernel's arithmetic and rounding
+// points - with rot == hd this kernel IS that one - and the pass part is copied as 16 raw bytes, forward and backward alike.
+// Lanes of a head row: rot/2 / VEC rotate (each loads its chunk and the partner's and writes both), then, out of place only,
+// (hd - rot) / VEC copy one chunk each: 6 + 4 of 10 at rot 96 / hd 128 bf16, none idle (a power-of-two 16 would idle 6).  The row
+// index comes from ONE 32-bit division by that lane count (the launcher keeps rows * lanes below 2^31).  In place (q_out == q and
+// k_out == k) the copying lanes do not exist and a dead row is left as it is.
+// ---------------------------------------------------------------------------------------------------
+struct RopePartialParams {
+  RopeTensor q, k;
+  const void* cos; const void* sin; int64_t cs[2];   // strides of (b, t); tables [B or 1, T, rot]
+  int B, T, Hq, Hk, hd, rot, backward, in_place;
+  const unsigned char* live;                         // [B * T] or NULL
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void rope_partial_kernel(const RopePartialParams p) {
+#pragma clang fp contract(off)   // the eager chain is separate mul and add kernels (see rope_qk_kernel)
+  constexpr int N = Vec16<T>::VEC;
+  const int h = p.rot >> 1;
+  const unsigned nrot = static_cast<unsigned>(h / N);
+  const unsigned lpr = nrot + (p.in_place ? 0u : static_cast<unsigned>((p.hd - p.rot) / N));   // lanes per head row
+  const unsigned H = static_cast<unsigned>(p.Hq + p.Hk);
+  const unsigned gid = blockIdx.x * 256u + threadIdx.x;
+  const unsigned row = gid / lpr, l = gid - row * lpr;
+  if (row >= static_cast<unsigned>(p.B) * p.T * H) return;
+  const unsigned bt = row / H, hh = row - bt * H;         // rows are walked head-fastest (rope_qk_kernel)
+  const unsigned b = bt / static_cast<unsigned>(p.T), t = bt - b * p.T;
+  const bool is_k = hh >= static_cast<unsigned>(p.Hq);
+  const RopeTensor& R = is_k ? p.k : p.q;
+  const int64_t head = is_k ? hh - p.Hq : hh;
+  const bool dead = p.live && !p.live[bt];
+  if (dead && p.in_place) return;
+  const bool rotates = l < nrot;
+  const int c = rotates ? static_cast<int>(l) * N : p.rot + static_cast<int>(l - nrot) * N;
+  const T* x = static_cast<const T*>(R.x) + b * R.xs[0] + head * R.xs[1] + t * R.xs[2] + c;
+  T* o = static_cast<T*>(R.o) + b * R.os[0] + head * R.os[1] + t * R.os[2] + c;
+  if (dead) {
+    *reinterpret_cast<uint4*>(o) = zero16();
+    if (rotates) *reinterpret_cast<uint4*>(o + h) = zero16();
+    return;
+  }
+  if (!rotates) {                                    // the pass part: bit for bit, in both directions
+    *reinterpret_cast<uint4*>(o) = *reinterpret_cast<const uint4*>(x);
+    return;
+  }
+  const int64_t ta = b * p.cs[0] + t * p.cs[1] + c;
+  const T* cs = static_cast<const T*>(p.cos) + ta;
+  const T* sn = static_cast<const T*>(p.sin) + ta;
+  float x1[N], x2[N], c1[N], c2[N], s1[N], s2[N], o1[N], o2[N];
+  Vec16<T>::load(x, x1); Vec16<T>::load(x + h, x2);
+  Vec16<T>::load(cs, c1); Vec16<T>::load(cs + h, c2);
+  Vec16<T>::load(sn, s1); Vec16<T>::load(sn + h, s2);
+#pragma unroll
+  for (int e = 0; e < N; ++e) {
+    // plain operators: the contract(off) pragma above governs this function's operations (see rope_qk_kernel)
+    const float a1 = Vec16<T>::rb(x1[e] * c1[e]), a2 = Vec16<T>::rb(x2[e] * c2[e]);
+    if (!p.backward) {
+      const float b1 = Vec16<T>::rb(x2[e] * s1[e]), b2 = Vec16<T>::rb(x1[e] * s2[e]);
+      o1[e] = Vec16<T>::rb(a1 - b1);
+      o2[e] = Vec16<T>::rb(a2 + b2);
+    } else {
+      const float b1 = Vec16<T>::rb(x2[e] * s2[e]), b2 = Vec16<T>::rb(x1[e] * s1[e]);
+      o1[e] = Vec16<T>::rb(a1 + b1);
+      o2[e] = Vec16<T>::rb(a2 - b2);
+    }
+  }
+  Vec16<T>::store(o, o1); Vec16<T>::store(o + h, o2);
+}
+
 // every lane's partial sum and the shuffles across the wave, in the accumulator's type
 template <typename A>
 __device__ __forceinline__ A wave_sum_as(A v) {
@@ -2363,8 +2435,51 @@ extern "C" int dalm_rope_il_qk(const void* q, const void* k, void* q_out, void* 
   return check_launch(__func__);
 }
 
+extern "C" int dalm_rope_partial_qk(const void* q, const void* k, void* q_out, void* k_out, const void* cos, const void* sin, int dtype,
+                                    int64_t B, int64_t T, int64_t Hq, int64_t Hk, int64_t hd, int64_t rot, const int64_t* q_strides,
+                                    const int64_t* k_strides, const int64_t* qo_strides, const int64_t* ko_strides,
+                                    const int64_t* cs_strides, int backward, const uint8_t* row_live, dalm_stream_t stream) {
+  DALM_REQUIRE(q && k && q_out && k_out && cos && sin && q_strides && k_strides && qo_strides && ko_strides && cs_strides,
+               DALM_E_NULL, "null pointer argument");
+  DALM_REQUIRE(dtype == DALM_F32 || dtype == DALM_BF16, DALM_E_DTYPE, "dtype must be DALM_F32 or DALM_BF16");
+  DALM_REQUIRE(hd == 32 || hd == 64 || hd == 128, DALM_E_SHAPE, "head width must be 32, 64 or 128");
+  const int vec = dtype == DALM_F32 ? 4 : 8;
+  DALM_REQUIRE(rot > 0 && rot <= hd && rot % (2 * vec) == 0, DALM_E_SHAPE,
+               "rotary width must be positive, at most the head width, and half of it a multiple of 16 bytes of `dtype`: "
+               "a multiple of 16 for bf16 (16, 32, 48, 64, 80, 96, 112, 128), of 8 for f32");
+  DALM_REQUIRE(B >= 0 && T >= 0 && Hq > 0 && Hk >= 0 && Hq + Hk <= 65535, DALM_E_SHAPE, "need B, T, Hk >= 0 and Hq > 0");
+  DALM_REQUIRE(B <= 0x7fffffffLL && T <= 0x7fffffffLL && B * T <= 0x7fffffffLL && B * T * (Hq + Hk) * (hd / vec) <= 0x7fffffffLL,
+               DALM_E_SHAPE, "tensor too large for one launch: need B T (Hq + Hk) hd / (16 bytes) < 2^31");
+  DALM_REQUIRE(aligned16(q, k, q_out, k_out, cos, sin) && strides_mult(q_strides, 3, vec) && strides_mult(k_strides, 3, vec)
+                   && strides_mult(qo_strides, 3, vec) && strides_mult(ko_strides, 3, vec) && strides_mult(cs_strides, 2, vec),
+               DALM_E_ALIGN, "tensors must be 16-byte aligned and every stride a multiple of 16 bytes of `dtype`");
+  const bool in_place = q_out == q && k_out == k;
+  if (in_place)
+    for (int i = 0; i < 3; ++i)
+      DALM_REQUIRE(qo_strides[i] == q_strides[i] && ko_strides[i] == k_strides[i], DALM_E_SHAPE,
+                   "in place (q_out == q, k_out == k) the output strides are the input strides");
+  if (B == 0 || T == 0) return 0;
+  RopePartialParams p;
+  p.q.x = q; p.q.o = q_out; p.k.x = k; p.k.o = k_out;
+  for (int i = 0; i < 3; ++i) {
+    p.q.xs[i] = q_strides[i]; p.k.xs[i] = k_strides[i]; p.q.os[i] = qo_strides[i]; p.k.os[i] = ko_strides[i];
+  }
+  p.cos = cos; p.sin = sin; p.cs[0] = cs_strides[0]; p.cs[1] = cs_strides[1];
+  p.B = static_cast<int>(B); p.T = static_cast<int>(T); p.Hq = static_cast<int>(Hq); p.Hk = static_cast<int>(Hk);
+  p.hd = static_cast<int>(hd); p.rot = static_cast<int>(rot);
+  p.backward = backward != 0; p.in_place = in_place;
+  p.live = row_live;
+  const int64_t lanes_per_row = (rot / 2 + (in_place ? 0 : hd - rot)) / vec;     // at most hd / vec: below 2^31 in all
+  const dim3 grid(static_cast<unsigned>((B * T * (Hq + Hk) * lanes_per_row + 255) / 256));
+  by_dtype(dtype, [&](auto t) {
+    using T_ = typename decltype(t)::type;
+    hipLaunchKernelGGL((rope_partial_kernel<T_>), grid, dim3(256), 0, as_stream(stream), p);
+  });
+  return check_launch(__func__);
+}
+
 // dalm_rms_norm_*'s width rules and R > 0; the weight has a dtype of its own
-#define DALM_COHERE_NORM_CHECKS                                                                                          \
+#define DALM_COHERE_NORM_CHECKS                                                                                         \
   DALM_REQUIRE(dtype == DALM_F32 || dtype == DALM_BF16, DALM_E_DTYPE, "dtype must be DALM_F32 or DALM_BF16");             \
   DALM_REQUIRE(w_dtype == DALM_F32 || w_dtype == DALM_BF16, DALM_E_DTYPE, "w_dtype must be DALM_F32 or DALM_BF16");       \
   const int vecn = dtype == DALM_F32 ? 4 : 8;                                                                            \

@@ -185,6 +185,9 @@ SIGNATURES = {
     "dalm_cohere_norm_fwd": (_int, [_vp, _vp, _int, _int, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp]),
     "dalm_cohere_norm_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _i64, _i64, _vp, _vp, _vp]),
     "dalm_add3_live": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _vp, _vp]),
+    # Phi-3: the partial rotary embedding of q and k (the first `rot` elements of a head rotate, the rest pass through)
+    "dalm_rope_partial_qk": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
+                                    _int, _vp, _vp]),
     "dalm_bert_add_norm_fwd_live": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _f32, _f32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _vp]),
     "dalm_bert_add_norm_bwd_live": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),

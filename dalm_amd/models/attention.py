@@ -381,6 +381,45 @@ def rope_il_sdpa(query, key, value, cos, sin, mask, scale: float, causal: bool):
     return _RopeIlSdpaHip.apply(query, key, value, cos, sin, mask, scale, causal)
 
 
+class _RopePartialSdpaHip(torch.autograd.Function):
+    """Phi-3's partial rotary embedding of q and k (`dalm_rope_partial_qk`, one launch) + the attention.  The rotary epilogues of
+    `dalm_attn_bwd` pair i with i + hd/2 over tables of width hd, so - as in `_RopeIlSdpaHip` - the backward calls it WITHOUT
+    tables and un-rotates dq / dk with one more `dalm_rope_partial_qk` launch (backward = 1, in place: the pass part of the
+    gradients is already what it has to be).  Equal and grouped heads, padded and packed; one key / value head is not routed
+    here (`supported` / `grouped_supported` decline it)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, cos, sin, mask, scale, causal):
+        from . import tower_ops
+        from .. import live_rows
+
+        B, H, T, hd = q.shape
+        # dead (b, t) of a padded tower call leave the rotation as zeros over the whole head (the attention kernels read finite
+        # values); their dq / dk rows are left as the attention backward wrote them
+        live = live_rows.current(B * T, q.device)
+        q2, k2 = tower_ops._rope_partial_launch(q, k, cos, sin, False, live)
+        pk = _pack(mask, B, H, T, causal, q.dtype, q.device)
+        out, lse = _attn_forward(q2, k2, v, pk, scale, causal)
+        ctx.save_for_backward(q2, k2, v, out, lse, cos, sin, *([live] if live is not None else []))
+        ctx.pack, ctx.scale = pk, scale
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        from . import tower_ops
+
+        q2, k2, v, out, lse, cos, sin, *live = ctx.saved_tensors
+        dq, dk, dv = _attn_backward(q2, k2, v, out, lse, d_out, ctx.pack, ctx.scale)       # of the ROTATED q / k: no tables
+        dq, dk = tower_ops._rope_partial_launch(dq, dk, cos, sin, True, live[0] if live else None, in_place=True)
+        return dq, dk, dv, None, None, None, None, None
+
+
+def rope_partial_sdpa(query, key, value, cos, sin, mask, scale: float, causal: bool):
+    """sdpa(modeling_phi3.apply_rotary_pos_emb(query, key, cos, sin), value, ...) with cos.shape[-1] < head_dim, for what
+    `node_supported` and `tower_ops.rope_partial_supported` accept."""
+    return _RopePartialSdpaHip.apply(query, key, value, cos, sin, mask, scale, causal)
+
+
 def _views_ok(*ts) -> bool:
     return all(t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:3]) and t.data_ptr() % 16 == 0 for t in ts)
 
@@ -776,19 +815,26 @@ def sdpa(query, key, value, mask, scale: float, causal: bool, dropout_p: float =
 
 
 def use_hip_attention_backward(model: torch.nn.Module) -> bool:
-    """Switch a Llama-family, Gemma, Arcee, OLMo-2, Granite, Cohere, BERT or RoBERTa-family (roberta, xlm-roberta, camembert: BERT's
+    """Switch a Llama-family, Gemma, Arcee, OLMo-2, Granite, Cohere, Phi-3, BERT or RoBERTa-family (roberta, xlm-roberta, camembert: BERT's
     layer code) model of head width 32, 64 or 128 from "sdpa" to "dalm_sdpa".  xlm-roberta-xl (pre-LayerNorm layers) is not taken, and
     neither is a Gemma of head width 256 (every released checkpoint) or an Arcee of head width 80 (`ArceeConfig()`'s defaults;
     AFM-4.5B has 128): it keeps transformers' SDPA and does not pack.  Granite's softmax scale (`attention_multiplier`, not
-    hd ** -0.5) reaches the kernels as the `scaling` argument of the attention call, like any other.  DALM_ATTN_KERNEL=0 disables."""
+    hd ** -0.5) reaches the kernels as the `scaling` argument of the attention call, like any other.  Phi-3 / Phi-4 (`model_type`
+    phi3) under the same head-width rule: Phi-3-mini and Phi-3.5-mini (width 96) keep "sdpa" and do not pack, Phi-3-medium, Phi-4
+    and Phi-4-mini (128) are switched; a phi3 config whose `sliding_window` is shorter than its positions is not switched (the
+    packed attention knows no window).  DALM_ATTN_KERNEL=0 disables."""
     if _off("DALM_ATTN_KERNEL"):
         return False
     cfg = getattr(model, "config", None)
     if cfg is None or getattr(cfg, "_attn_implementation", None) != "sdpa":
         return False
     if getattr(cfg, "model_type", "") not in ("llama", "mistral", "qwen2", "qwen3", "gemma", "arcee", "olmo2", "granite", "cohere",
-                                              "bert", "roberta", "xlm-roberta", "camembert"):
+                                              "phi3", "bert", "roberta", "xlm-roberta", "camembert"):
         return False
+    if cfg.model_type == "phi3":
+        window = getattr(cfg, "sliding_window", None)
+        if window is not None and window < getattr(cfg, "max_position_embeddings", 1 << 30):
+            return False
     hd = getattr(cfg, "head_dim", None) or (cfg.hidden_size // cfg.num_attention_heads)
     if hd not in _HEAD_DIMS or not register():
         return False

@@ -947,28 +947,35 @@ def _qk_norm_ok(norm, row_wide: bool, width: int) -> bool:
 
 
 def _decoder_attention_forward(self, hidden_states, position_embeddings, attention_mask, past_key_values, kwargs, norms, window,
-                               row_wide=False):
+                               row_wide=False, project=None):
     """transformers' LlamaAttention.forward / Qwen3Attention.forward / Olmo2Attention.forward for the training call ("dalm_sdpa", no
     KV cache, no dropout, no sliding window): the same statements with (the q / k norms +) apply_rotary_pos_emb + the attention call
     as one node.  Every other call goes to transformers' own forward.  The classes differ in
       norms     None, or (q_norm, k_norm) between the projections and the rotation;
       row_wide  where the norms act: on the head view, over the head dimension (Qwen3), or - True - on the projection's output in
                 front of the head view, over all heads of a token (OLMo-2);
-      window    the keyword Qwen3 adds to the attention call, `{"sliding_window": ...}`; `{}` for the others."""
+      window    the keyword Qwen3 adds to the attention call, `{"sliding_window": ...}`; `{}` for the others;
+      project   None: q_proj / k_proj / v_proj; Phi-3: `project(self, hidden_states, hidden_shape)` -> (query_raw, key_raw,
+                value_states) as column slices of the one qkv_proj output.  Only with it may the tables be narrower than the head
+                (modeling_phi3.py's apply_rotary_pos_emb rotates the first cos.shape[-1] elements): `attention.rope_partial_sdpa`."""
     from . import attention, tower_ops
 
     cfg = self.config
     if (past_key_values is not None or position_embeddings is None or getattr(cfg, "_attn_implementation", None) != attention.NAME
             or (self.training and float(getattr(self, "attention_dropout", 0.0)) != 0.0)
-            or window.get("sliding_window") is not None
+            # Qwen3: any window; Phi-3 (`project`): one shorter than the keys - a longer one changes nothing
+            or (window.get("sliding_window") is not None and (project is None or window["sliding_window"] < hidden_states.shape[-2]))
             or _off("DALM_FAST_ROPE") or _off("DALM_ATTN_KERNEL") or kwargs.get("output_attentions")):
         return self._dalm_orig_attn_forward(hidden_states, position_embeddings=position_embeddings, attention_mask=attention_mask,
                                             past_key_values=past_key_values, **kwargs)
     input_shape = hidden_states.shape[:-1]
     hidden_shape = (*input_shape, -1, self.head_dim)
-    query_raw = self.q_proj(hidden_states).view(hidden_shape)
-    key_raw = self.k_proj(hidden_states).view(hidden_shape)
-    value_states = self.v_proj(hidden_states).view(hidden_shape).transpose(1, 2)
+    if project is None:
+        query_raw = self.q_proj(hidden_states).view(hidden_shape)
+        key_raw = self.k_proj(hidden_states).view(hidden_shape)
+        value_states = self.v_proj(hidden_states).view(hidden_shape).transpose(1, 2)
+    else:
+        query_raw, key_raw, value_states = project(self, hidden_states, hidden_shape)
     cos, sin = position_embeddings
     q_t, k_t = query_raw.transpose(1, 2), key_raw.transpose(1, 2)          # [B, H, T, hd] views, in front of the norms
     causal = bool(q_t.shape[2] > 1 and attention_mask is None and getattr(self, "is_causal", True))
@@ -976,8 +983,11 @@ def _decoder_attention_forward(self, hidden_states, position_embeddings, attenti
     # heads left un-expanded: the same node
     if row_wide and q_t.is_cuda and q_t.dtype == torch.bfloat16:
         cos, sin = _tables_in_bf16(cos, sin)     # the node's tables; the fall-through below goes back to the module's own
-    fused = (attention.node_supported(q_t, k_t, value_states, attention_mask, causal)
+    narrow = project is not None and cos.shape[-1] < self.head_dim         # a partial rotation: never the fused epilogue
+    fused = (not narrow and attention.node_supported(q_t, k_t, value_states, attention_mask, causal)
              and attention.rope_fusable(q_t, k_t, cos, sin))
+    partial = (narrow and norms is None and attention.node_supported(q_t, k_t, value_states, attention_mask, causal)
+               and tower_ops.rope_partial_supported(q_t, k_t, cos, sin))
     qn, kn = norms or (None, None)
     if fused and norms is not None:
         wide = (q_t.shape[1] * self.head_dim, k_t.shape[1] * self.head_dim) if row_wide else (self.head_dim, self.head_dim)
@@ -989,6 +999,8 @@ def _decoder_attention_forward(self, hidden_states, position_embeddings, attenti
     elif fused:
         attn_output = attention.norm_rope_sdpa(q_t, k_t, value_states, qn.weight, kn.weight, _norm_eps(qn), _norm_eps(kn), cos, sin,
                                                attention_mask, float(self.scaling), causal, row_wide)
+    elif partial:
+        attn_output = attention.rope_partial_sdpa(q_t, k_t, value_states, cos, sin, attention_mask, float(self.scaling), causal)
     else:                      # CPU tensors, fp32, one KV head, other head widths, ...: transformers' own sequence from here on
         import importlib
 
@@ -1003,7 +1015,7 @@ def _decoder_attention_forward(self, hidden_states, position_embeddings, attenti
         query_states, key_states = rope(q_t, k_t, *position_embeddings)
         attn_output, _ = ALL_ATTENTION_FUNCTIONS[cfg._attn_implementation](
             self, query_states, key_states, value_states, attention_mask, dropout=0.0, scaling=self.scaling, **window, **kwargs)
-    if fused:
+    if fused or partial:
         attn_output = attn_output.transpose(1, 2)
     attn_output = attn_output.reshape(*input_shape, -1).contiguous()
     return self.o_proj(attn_output), None
@@ -1463,3 +1475,133 @@ _COHERE_ATTN_BODY = [
     "attn_output = self.o_proj(attn_output)", "return attn_output, attn_weights"]
 _SOURCE_GUARDS["cohere-attn"] = (
     lambda params, src: params == _LLAMA_ATTN_PARAMS and _same_statements(src, _COHERE_ATTN_BODY), _RESTATED)
+
+
+# ---------------------------------------------------------------------------
+# Phi-3 / Phi-4 (`model_type` phi3): Llama's layer with fused projections (one qkv_proj, one gate_up_proj), a rotary embedding over
+# the first cos.shape[-1] elements of a head only, and dropout on the two sub-block outputs (resid_pdrop, 0.0 in every released config)
+# ---------------------------------------------------------------------------
+def _phi3_projections(self, hidden_states, hidden_shape):
+    """Phi3Attention.forward's first statements: ONE qkv_proj call, q | k | v as column slices of its output, as head views."""
+    qkv = self.qkv_proj(hidden_states)
+    query_pos = self.config.num_attention_heads * self.head_dim
+    key_end = query_pos + self.num_key_value_heads * self.head_dim
+    return (qkv[..., :query_pos].view(hidden_shape), qkv[..., query_pos:key_end].view(hidden_shape),
+            qkv[..., key_end:].view(hidden_shape).transpose(1, 2))
+
+
+def _phi3_attention_forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
+    """Phi3Attention.forward on `_decoder_attention_forward`: full-width tables take `attention.rope_sdpa` (the rotation's backward in
+    the attention backward's epilogues: Phi-3-medium, Phi-4), narrower ones `attention.rope_partial_sdpa` (Phi-4-mini), anything
+    else the module's own apply_rotary_pos_emb and the registered attention function.  A `sliding_window` shorter than the keys
+    goes to transformers' own forward."""
+    return _decoder_attention_forward(self, hidden_states, position_embeddings, attention_mask, past_key_values, kwargs, None,
+                                      {"sliding_window": getattr(self.config, "sliding_window", None)}, project=_phi3_projections)
+
+
+def use_phi3_attention_node(model: torch.nn.Module) -> int:
+    """Patch Phi3Attention modules of a model that runs on "dalm_sdpa" (models/attention.py) and whose forward is, statement for
+    statement, the code `_phi3_attention_forward` restates.  Returns the count."""
+    return _use_attention_node(model, "Phi3Attention", ("qkv_proj", "o_proj", "scaling", "head_dim", "num_key_value_heads"),
+                               "phi3-attn", _phi3_attention_forward, lambda mod: _bias_free(mod, ("qkv_proj", "o_proj")))
+
+
+# Phi3Attention.forward: the whole body
+_PHI3_ATTN_BODY = [
+    "input_shape = hidden_states.shape[:-1]", "hidden_shape = (*input_shape, -1, self.head_dim)",
+    "qkv = self.qkv_proj(hidden_states)", "query_pos = self.config.num_attention_heads * self.head_dim",
+    "query_states = qkv[..., :query_pos]",
+    "key_states = qkv[..., query_pos : query_pos + self.num_key_value_heads * self.head_dim]",
+    "value_states = qkv[..., query_pos + self.num_key_value_heads * self.head_dim :]",
+    "query_states = query_states.view(hidden_shape).transpose(1, 2)", "key_states = key_states.view(hidden_shape).transpose(1, 2)",
+    "value_states = value_states.view(hidden_shape).transpose(1, 2)", "cos, sin = position_embeddings",
+    "query_states, key_states = apply_rotary_pos_emb(query_states, key_states, cos, sin)",
+    "if past_key_values is not None:",
+    "    key_states, value_states = past_key_values.update(key_states, value_states, self.layer_idx)",
+    "attention_interface: Callable = ALL_ATTENTION_FUNCTIONS.get_interface(",
+    "    self.config._attn_implementation, eager_attention_forward", ")",
+    "attn_output, attn_weights = attention_interface(", "    self,", "    query_states,", "    key_states,", "    value_states,",
+    "    attention_mask,", "    dropout=0.0 if not self.training else self.attention_dropout,", "    scaling=self.scaling,",
+    "    sliding_window=getattr(self.config, \"sliding_window\", None),", "    **kwargs,", ")",
+    "attn_output = attn_output.reshape(*input_shape, -1).contiguous()",
+    "attn_output = self.o_proj(attn_output)", "return attn_output, attn_weights"]
+_SOURCE_GUARDS["phi3-attn"] = (
+    lambda params, src: params == _LLAMA_ATTN_PARAMS and _same_statements(src, _PHI3_ATTN_BODY), _RESTATED)
+
+
+def _phi3_mlp_forward(self, x):
+    """Phi3MLP.forward with `up * silu(gate)` on the SwiGLU kernels: gate and up are the two halves of the one gate_up_proj output,
+    read in place (`dalm_swiglu_{fwd,bwd}_2d_live`).  The product commutes: the kernels' silu(gate) * up rounds identically."""
+    from . import tower_ops
+
+    gate, up = self.gate_up_proj(x).chunk(2, dim=-1)
+    if tower_ops.swiglu_supported(gate, up):
+        return self.down_proj(tower_ops.swiglu(gate, up))
+    return self.down_proj(up * self.activation_fn(gate))
+
+
+_PHI3_MLP_BODY = ["up_states = self.gate_up_proj(hidden_states)", "gate, up_states = up_states.chunk(2, dim=-1)",
+                  "up_states = up_states * self.activation_fn(gate)", "return self.down_proj(up_states)"]
+_SOURCE_GUARDS["phi3-mlp"] = (
+    lambda params, src: params == ["self", "hidden_states"] and _same_statements(src, _PHI3_MLP_BODY), _RESTATED)
+
+
+def use_phi3_mlp(model: torch.nn.Module) -> int:
+    """Patch the bias-free Phi3MLP modules with a SiLU activation whose forward is, statement for statement, the code
+    `_phi3_mlp_forward` restates and passes `_mlp_matches`' value probe.  DALM_SWIGLU_KERNEL=0 disables.  Returns the count."""
+    if _off("DALM_SWIGLU_KERNEL"):
+        return 0
+
+    def fused_silu(mod) -> bool:
+        act = getattr(mod, "activation_fn", None)
+        return (_bias_free(mod, ("gate_up_proj", "down_proj"))
+                and (isinstance(act, torch.nn.SiLU) or type(act).__name__ in ("SiLUActivation", "SiLU")))
+
+    def guard(mod) -> bool:
+        return _matches("phi3-mlp", type(mod)) and _mlp_matches(mod, _phi3_mlp_forward, "down(up * silu(gate)) of one gate_up GEMM here",
+                                                                "gate_up_proj")
+
+    return _install(model, ("Phi3MLP",), fused_silu, guard, _phi3_mlp_forward)
+
+
+def _phi3_layer_forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_values=None, use_cache=False,
+                        position_embeddings=None, **kwargs):
+    """Phi3DecoderLayer.forward - LlamaDecoderLayer.forward with a dropout on each sub-block's output - on `_llama_layer_forward`
+    while the two dropouts are the identity (eval, or resid_pdrop == 0: every released config); a training call with p != 0 goes
+    to transformers' own forward."""
+    if self.training and (float(self.resid_attn_dropout.p) != 0.0 or float(self.resid_mlp_dropout.p) != 0.0):
+        return self._dalm_orig_forward(hidden_states, attention_mask=attention_mask, position_ids=position_ids,
+                                       past_key_values=past_key_values, use_cache=use_cache,
+                                       position_embeddings=position_embeddings, **kwargs)
+    return _llama_layer_forward(self, hidden_states, attention_mask=attention_mask, position_ids=position_ids,
+                                past_key_values=past_key_values, use_cache=use_cache, position_embeddings=position_embeddings, **kwargs)
+
+
+def use_phi3_layer(model: torch.nn.Module) -> int:
+    """Patch Phi3DecoderLayer modules whose forward is, statement for statement, the code `_phi3_layer_forward` restates, with two
+    plain RMSNorms and two `nn.Dropout`s.  DALM_NORM_KERNEL=0 disables.  Returns how many layers were patched."""
+    if _off("DALM_NORM_KERNEL"):
+        return 0
+
+    def plain_rms_norm(nm) -> bool:
+        return (nm is not None and type(nm).__name__ == "Phi3RMSNorm" and getattr(nm, "weight", None) is not None
+                and nm.weight.dim() == 1)
+
+    def eligible(mod) -> bool:
+        return (plain_rms_norm(getattr(mod, "input_layernorm", None)) and plain_rms_norm(getattr(mod, "post_attention_layernorm", None))
+                and all(hasattr(mod, a) for a in ("self_attn", "mlp"))
+                and all(type(getattr(mod, a, None)) is torch.nn.Dropout for a in ("resid_attn_dropout", "resid_mlp_dropout")))
+
+    return _install(model, ("Phi3DecoderLayer",), eligible, "phi3-layer", _phi3_layer_forward, keep="_dalm_orig_forward")
+
+
+# Phi3DecoderLayer.forward: Qwen3's whole body with the attention weights named and the two sub-block outputs behind a dropout;
+# compared as syntax trees (`_same_statements`), as Granite's is
+_PHI3_LAYER_BODY = [{"hidden_states, _ = self.self_attn(": "hidden_states, self_attn_weights = self.self_attn("}.get(s, s)
+                    for s in _QWEN3_LAYER_BODY]
+_PHI3_LAYER_BODY[_PHI3_LAYER_BODY.index("hidden_states = residual + hidden_states")] = \
+    "hidden_states = residual + self.resid_attn_dropout(hidden_states)"
+_PHI3_LAYER_BODY[_PHI3_LAYER_BODY.index("hidden_states = residual + hidden_states")] = \
+    "hidden_states = residual + self.resid_mlp_dropout(hidden_states)"
+_SOURCE_GUARDS["phi3-layer"] = (
+    lambda params, src: params == _LLAMA_LAYER_PARAMS and _same_statements(src, _PHI3_LAYER_BODY), _RESTATED)

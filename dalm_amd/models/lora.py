@@ -265,7 +265,10 @@ def _matches(name: str, targets: Iterable[str]) -> bool:
 FUSED_QKV_FALLBACK = {"falcon": ["query_key_value"], "gpt_neox": ["query_key_value"], "bloom": ["query_key_value"],
                       "gpt2": ["c_attn"], "mpt": ["Wqkv"],
                       # MPNet names its projections q / k / v: the retriever targets key / query / value find nothing there
-                      "mpnet": ["q", "k", "v"]}
+                      "mpnet": ["q", "k", "v"],
+                      # Phi-3 / Phi-4: q and v live in the one qkv_proj (peft is not installed beside this project: its own table
+                      # entry for phi3 could not be compared)
+                      "phi3": ["qkv_proj"]}
 
 
 def resolve_targets(model: nn.Module, target_modules: List[str]) -> List[str]:

@@ -18,8 +18,9 @@ from .attention import use_hip_attention_backward
 from .fastpath import (use_bert_layer_kernels, use_capturable_falcon_heads, use_cohere_attention_node, use_cohere_layer,
                        use_cohere_layer_norm, use_falcon_attention_kernels, use_falcon_layer_kernels,
                        use_fused_residual_norm, use_geglu_kernel, use_gemma_rms_norm, use_llama_attention_node, use_native_rms_norm,
-                       use_mpnet_attention_kernels, use_olmo2_attention_node, use_olmo2_layer, use_qwen3_attention_node, use_relu2_kernel,
-                       use_roberta_embeddings, use_roll_rope, use_swiglu_kernel)
+                       use_mpnet_attention_kernels, use_olmo2_attention_node, use_olmo2_layer, use_phi3_attention_node, use_phi3_layer,
+                       use_phi3_mlp, use_qwen3_attention_node, use_relu2_kernel, use_roberta_embeddings, use_roll_rope,
+                       use_swiglu_kernel)
 
 
 class Mode(Enum):
@@ -98,12 +99,12 @@ def decoder_only(lm, T: Optional[int] = None) -> bool:
 _ROW_WISE_PATHS = (use_native_rms_norm, use_roll_rope, use_swiglu_kernel, use_geglu_kernel, use_relu2_kernel, use_gemma_rms_norm,
                    use_fused_residual_norm)
 _RETRIEVER_PATHS = _ROW_WISE_PATHS + (use_hip_attention_backward,)
-# (OLMo-2 and Cohere are generators only: their layers and attention nodes are installed here, not on retrievers; Cohere's layer
-# comes before its norm installer, which takes the norms the layers left over)
-_GENERATOR_PATHS = _ROW_WISE_PATHS + (use_olmo2_layer, use_cohere_layer, use_cohere_layer_norm, use_capturable_falcon_heads,
-                                      use_falcon_layer_kernels, use_falcon_attention_kernels, use_hip_attention_backward,
-                                      use_llama_attention_node, use_qwen3_attention_node, use_olmo2_attention_node,
-                                      use_cohere_attention_node)
+# (OLMo-2, Cohere and Phi-3 are generators only: their layers, Phi-3's MLP and the attention nodes are installed here, not on
+# retrievers; Cohere's layer comes before its norm installer, which takes the norms the layers left over)
+_GENERATOR_PATHS = _ROW_WISE_PATHS + (use_olmo2_layer, use_cohere_layer, use_cohere_layer_norm, use_phi3_layer, use_phi3_mlp,
+                                      use_capturable_falcon_heads, use_falcon_layer_kernels, use_falcon_attention_kernels,
+                                      use_hip_attention_backward, use_llama_attention_node, use_qwen3_attention_node,
+                                      use_olmo2_attention_node, use_cohere_attention_node, use_phi3_attention_node)
 
 
 def use_causal_retriever_fast_paths(lm) -> dict:
@@ -116,8 +117,9 @@ def use_causal_retriever_fast_paths(lm) -> dict:
 
 
 def use_generator_fast_paths(lm) -> dict:
-    """Every tower patch of a generator: the retriever's list, OLMo-2's post-norm layer, Cohere's parallel layer and LayerNorm, the
-    three Falcon installers and the four rotary + attention nodes.  Returns what each installer returned, by its name."""
+    """Every tower patch of a generator: the retriever's list, OLMo-2's post-norm layer, Cohere's parallel layer and LayerNorm, Phi-3's
+    layer and fused-projection MLP, the three Falcon installers and the five rotary + attention nodes (Phi-3's last: full-width
+    tables on the fused node, narrower ones on the partial-rotary kernel).  Returns what each installer returned, by its name."""
     return {use.__name__: use(lm) for use in _GENERATOR_PATHS}
 
 

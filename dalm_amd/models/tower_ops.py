@@ -11,7 +11,8 @@ Also here: RMSNorm with the residual add, Qwen3's head norm + rotary, Gemma's Ge
 `ArceeMLP.forward`), OLMo-2's norm-then-add and row-wide q / k norm + rotary (`dalm_norm_add_*`, `dalm_row_norm_*`: modeling_olmo2.py),
 Granite's scaled residual add with and without the norm behind it (`dalm_rms_norm_scaled_*`, `dalm_scale_add`: modeling_granite.py
 `GraniteDecoderLayer.forward`), Cohere's interleaved f32 rotary embedding, f32 LayerNorm and three-way add (`dalm_rope_il_qk`,
-`dalm_cohere_norm_*`, `dalm_add3_live`: modeling_cohere.py), and Falcon's layer ops.
+`dalm_cohere_norm_*`, `dalm_add3_live`: modeling_cohere.py), Phi-3's partial rotary embedding (`dalm_rope_partial_qk`:
+modeling_phi3.py `apply_rotary_pos_emb`), and Falcon's layer ops.
 
 GPU tensors only: the callers in `fastpath.py` keep transformers' own code for CPU tensors.
 """
@@ -409,6 +410,69 @@ def rope_il_qk(q, k, cos, sin, live=None):
     rotate_half - for q and k in one launch, one more backward; values and gradients are the eager chain's, bit for bit.
     live: uint8 [B T] row liveness; None: that of the tower call in progress (dalm_amd/live_rows.py), if any."""
     return _RopeIlQK.apply(q, k, cos, sin, live)
+
+
+# ---------------------------------------------------------------------------
+# Phi-3 / Phi-4 (modeling_phi3.py): the partial rotary embedding (dalm_rope_partial_qk) - the first rot = cos.shape[-1] elements of
+# a head rotate, half-split within those rot; the rest pass through
+# ---------------------------------------------------------------------------
+def rope_partial_supported(q, k, cos, sin) -> bool:
+    """What `dalm_rope_partial_qk` takes: q / k [B, H, T, hd] f32 or bf16 GPU views with a contiguous last dimension, 16-byte
+    aligned rows, head width 32, 64 or 128; cos / sin [B or 1, T, rot] of the activations' dtype, laid out alike, no gradient;
+    0 < rot <= hd with rot / 2 a multiple of 16 bytes (rot a multiple of 16 for bf16, of 8 for f32)."""
+    if not (q.is_cuda and q.dim() == 4 and k.dim() == 4 and cos.dim() == 3 and sin.shape == cos.shape
+            and q.dtype in (torch.float32, torch.bfloat16) and k.dtype == q.dtype and cos.dtype == q.dtype
+            and sin.dtype == q.dtype and q.shape[-1] in _ROPE_IL_DIMS and k.shape[-1] == q.shape[-1]
+            and q.shape[0] == k.shape[0] and q.shape[2] == k.shape[2] and q.numel() > 0 and k.numel() > 0
+            and cos.shape[0] in (1, q.shape[0]) and cos.shape[1] == q.shape[2]
+            and sin.stride() == cos.stride() and not cos.requires_grad and not sin.requires_grad):
+        return False
+    vec = 16 // q.element_size()
+    rot = cos.shape[-1]
+    return (0 < rot <= q.shape[-1] and rot % (2 * vec) == 0
+            and all(t.stride(-1) == 1 and t.data_ptr() % 16 == 0 for t in (q, k, cos, sin))
+            and all(s % vec == 0 for t, n in ((q, 3), (k, 3), (cos, 2)) for s in _il_strides(t, n)))
+
+
+def _rope_partial_launch(q, k, cos, sin, backward: bool, live=None, in_place: bool = False):
+    """One `dalm_rope_partial_qk` launch over what `rope_partial_supported` took.  in_place: the rotated part of live rows is
+    overwritten in q and k, the pass part and dead rows stay as they are - the un-rotation of gradients nobody else holds."""
+    hip.require_gpu(q, k, cos, sin)
+    if in_place:
+        qo, ko = q, k
+    else:
+        qo, ko = torch.empty_like(q), torch.empty_like(k)       # preserve_format: same strides as the (dense) views
+        if qo.stride(-1) != 1 or ko.stride(-1) != 1:            # overlapping / exotic input layout: plain contiguous outputs
+            qo = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+            ko = torch.empty(k.shape, dtype=k.dtype, device=k.device)
+    B, Hq, T, hd = q.shape
+    s3 = lambda t: (C.c_int64 * 3)(*_il_strides(t, 3))  # noqa: E731
+    hip.call("dalm_rope_partial_qk", hip.ptr(q), hip.ptr(k), hip.ptr(qo), hip.ptr(ko), hip.ptr(cos), hip.ptr(sin),
+             hip.dtype_code(q), B, T, Hq, k.shape[1], hd, cos.shape[-1], s3(q), s3(k), s3(qo), s3(ko),
+             (C.c_int64 * 2)(*_il_strides(cos, 2)), int(backward), hip.ptr(live), hip.stream())
+    return qo, ko
+
+
+class _RopePartialQK(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, cos, sin, live=None):
+        if live is None:
+            live = live_rows.current(q.shape[0] * q.shape[2], q.device)
+        ctx.save_for_backward(cos, sin, *([live] if live is not None else []))   # the backward runs after the tower call's context
+        return _rope_partial_launch(q, k, cos, sin, False, live)
+
+    @staticmethod
+    def backward(ctx, gq, gk):
+        cos, sin, *live = ctx.saved_tensors
+        dq, dk = _rope_partial_launch(_il_gradient(gq), _il_gradient(gk), cos, sin, True, live[0] if live else None)
+        return dq, dk, None, None, None
+
+
+def rope_partial_qk(q, k, cos, sin, live=None):
+    """modeling_phi3.py's apply_rotary_pos_emb - cat([x_rot * cos + rotate_half(x_rot) * sin, x_pass]) with x_rot the first
+    cos.shape[-1] elements of each head - for q and k in one launch, one more backward; values and gradients are the eager
+    chain's, bit for bit.  live: uint8 [B T] row liveness; None: that of the tower call in progress (dalm_amd/live_rows.py), if any."""
+    return _RopePartialQK.apply(q, k, cos, sin, live)
 
 
 def cohere_norm_supported(x: torch.Tensor, w: torch.Tensor) -> bool:

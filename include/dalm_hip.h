@@ -697,6 +697,34 @@ int dalm_cohere_norm_bwd(const void* dy, const void* x, const void* w, const flo
 int dalm_add3_live(const void* res, const void* a, const void* b, void* out, int dtype, int64_t R, int64_t D, const uint8_t* row_live,
                    dalm_stream_t stream);
 
+/* Phi-3 / Phi-4 (modeling_phi3.py; `model_type` "phi3"): apply_rotary_pos_emb rotates only the first rot = cos.shape[-1] elements of
+ * each head, half-split WITHIN those rot - i pairs with i + rot/2 - and passes the other hd - rot through (Phi-4-mini:
+ * partial_rotary_factor 0.75, hd 128, rot 96).  dalm_rope_partial_qk is that for q and k in one launch, and (backward != 0) its
+ * autograd backward.  Conventions of dalm_rope_qk_live: q / k / outputs [B, H, T, hd] views with element strides {b, h, t} and a
+ * contiguous last dimension (q with Hq heads, k with Hk; column slices of the one qkv_proj output are read in place); cos / sin
+ * [B or 1, T, rot] of `dtype` with element strides {b, t} (b = 0 for one table).  round = the rounding to `dtype` (the identity for
+ * f32).  For i < rot/2, with 1 = element i and 2 = element i + rot/2 of x, cos and sin:
+ *        forward :  out1 = round(round(x1 cos1) - round(x2 sin1))     out2 = round(round(x2 cos2) + round(x1 sin2))
+ *        backward:  dx1  = round(round(g1 cos1) + round(g2 sin2))     dx2  = round(round(g2 cos2) - round(g1 sin1))
+ *        elements [rot, hd): out = x, dx = g, copied bit for bit.
+ * Each product and each sum is rounded on its own (no fused multiply-add): the values of the eager chain and of its autograd
+ * backward, bit for bit.  Both table halves are read: they need not be equal.  With rot == hd the call produces dalm_rope_qk_live's
+ * bits (the rot == hd identity: the same pairs, the same arithmetic, no pass part).
+ * Row liveness (above), row_live [B T] bytes or NULL: a dead (b, t) is not read, and its freshly written outputs are zeros across
+ * the WHOLE head, pass part included; live rows receive the same bits as without the vector.
+ * In place: q_out == q and k_out == k (then with the inputs' strides) is the in-place form - a lane reads only the 16 bytes it writes
+ * and its partner's, which it writes as well; the pass part and dead rows are left untouched (nothing is written there).  One of the
+ * two alone aliasing is the out-of-place form, which writes every element of both outputs.
+ * Limits: hd = 32, 64 or 128; 0 < rot <= hd with rot/2 a multiple of 16 bytes of `dtype` - rot a multiple of 16 for bf16 (96, 64, 48,
+ * 32, 16, ...), of 8 for f32 (24 as well) - so hd - rot is a multiple of 16 bytes too; B, T >= 0 (no rows: nothing to do, 0), Hq > 0,
+ * Hk >= 0; B T (Hq + Hk) hd / (16 bytes) < 2^31 (all DALM_E_SHAPE).  16-byte aligned tensors and every stride a multiple of 16 bytes
+ * of `dtype` (DALM_E_ALIGN).  NULL tensors or stride arrays: DALM_E_NULL.  There is no element-wise form: the caller declines what
+ * this does not take.  The checks run before anything is enqueued: a rejected call writes nothing. */
+int dalm_rope_partial_qk(const void* q, const void* k, void* q_out, void* k_out, const void* cos, const void* sin, int dtype,
+                         int64_t B, int64_t T, int64_t Hq, int64_t Hk, int64_t hd, int64_t rot, const int64_t* q_strides,
+                         const int64_t* k_strides, const int64_t* qo_strides, const int64_t* ko_strides, const int64_t* cs_strides,
+                         int backward, const uint8_t* row_live, dalm_stream_t stream);
+
 /* Elementwise chains of a Falcon-7B decoder layer (transformers modeling_falcon.py FalconDecoderLayer.forward /
  * FalconMLP.forward / dropout_add, reached by the reference through self.generator_model(...),
  * dalm/models/rag_e2e_base_model.py:104-106; BASELINE.json config 5).  bf16 tensors, 16-byte aligned.

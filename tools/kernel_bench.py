@@ -753,6 +753,49 @@ def bench_rope_il(B, T, Hq, Hk, hd, rounds=3):
     return out
 
 
+def bench_rope_partial(B, T, Hq, Hk, hd, rot, rounds=3):
+    """Phi-3's partial rotary embedding: `dalm_rope_partial_qk` forward and backward on the q | k column slices of one
+    [B T, (Hq + 2 Hk) hd] bf16 buffer - qkv_proj's output -, and beside them - alternating, in the same process - modeling_phi3.py's
+    apply_rotary_pos_emb with autograd's backward.  Algorithmic bytes: (|q| + |k|) elements read and as many written each way (+ the
+    tables [T, rot], shared by all heads); the in-place backward - the attention node's un-rotation - moves the rotated part only."""
+    from transformers.models.phi3.modeling_phi3 import apply_rotary_pos_emb
+
+    from dalm_amd.models import tower_ops
+
+    dev = torch.device("cuda:0")
+    W = (Hq + 2 * Hk) * hd
+    buf = torch.randn(B, T, W, device=dev, dtype=torch.bfloat16)
+    q = buf[..., :Hq * hd].view(B, T, Hq, hd).transpose(1, 2)
+    k = buf[..., Hq * hd:(Hq + Hk) * hd].view(B, T, Hk, hd).transpose(1, 2)
+    inv = 1.0 / (10000.0 ** (torch.arange(0, rot, 2, device=dev).float() / rot))
+    ang = torch.arange(T, device=dev).float()[None, :, None] * inv
+    emb = torch.cat((ang, ang), dim=-1)
+    cos, sin = emb.cos().to(torch.bfloat16), emb.sin().to(torch.bfloat16)
+    assert tower_ops.rope_partial_supported(q, k, cos, sin)
+    gq, gk = torch.randn(B, T, Hq, hd, device=dev, dtype=torch.bfloat16).transpose(1, 2), \
+        torch.randn(B, T, Hk, hd, device=dev, dtype=torch.bfloat16).transpose(1, 2)
+    qg = buf[..., :Hq * hd].detach().clone().requires_grad_(True)                                      # dense leaves for autograd
+    kg = buf[..., Hq * hd:(Hq + Hk) * hd].detach().clone().requires_grad_(True)
+
+    def eager_both():
+        oq, ok = apply_rotary_pos_emb(qg.view(B, T, Hq, hd).transpose(1, 2), kg.view(B, T, Hk, hd).transpose(1, 2), cos, sin)
+        return torch.autograd.grad((oq, ok), (qg, kg), (gq, gk))
+
+    tables = 2 * T * rot * 2
+    b = 2 * B * T * (Hq + Hk) * hd * 2 + tables
+    b_rot = 2 * B * T * (Hq + Hk) * rot * 2 + tables
+    fns = {"kernel fwd (1 launch)": lambda: tower_ops._rope_partial_launch(q, k, cos, sin, False),
+           "kernel bwd (1 launch)": lambda: tower_ops._rope_partial_launch(gq, gk, cos, sin, True),
+           "kernel bwd (1 launch, in place)": lambda: tower_ops._rope_partial_launch(gq, gk, cos, sin, True, None, in_place=True),
+           "eager fwd": _no_grad(apply_rotary_pos_emb, q, k, cos, sin),
+           "eager fwd + autograd bwd": eager_both}
+    nbytes = {name: (2 * b if "+" in name else b_rot if "in place" in name else b) for name in fns}
+    out = _alternating(fns, nbytes, rounds)
+    k_s, e = out["kernel fwd (1 launch)"]["s"] + out["kernel bwd (1 launch)"]["s"], out["eager fwd + autograd bwd"]["s"]
+    out["kernel fwd + bwd against eager"] = {"kernel_s": k_s, "eager_s": e, "eager_over_kernel": e / k_s}
+    return out
+
+
 def bench_add3(R, D, rounds=3):
     """Cohere's `residual + attn + mlp` on [R, D] bf16 rows: `dalm_add3_live` (its backward hands the gradient on: no launch) against
     the eager pair of adds.  Algorithmic bytes: 4 R D elements."""
@@ -934,6 +977,10 @@ def main():
         res["rope_il packed rows 1x3008, 32+8 heads x 128"] = bench_rope_il(1, 3008, 32, 8, 128)
     if args.only in ("", "add3"):
         res["add3 rows 4608 x 4096 bf16"] = bench_add3(4608, 4096)
+    # the headline batch's rows in Phi-4-mini's layout: 24 + 8 heads of 128, the first 96 of each rotated
+    if args.only in ("", "rope_partial"):
+        res["rope_partial generator rows 18x256, 24+8 heads x 128, rot 96"] = bench_rope_partial(18, 256, 24, 8, 128, 96)
+        res["rope_partial packed rows 1x3008, 24+8 heads x 128, rot 96"] = bench_rope_partial(1, 3008, 24, 8, 128, 96)
     Path("gpurun_out").mkdir(exist_ok=True)
     Path("gpurun_out/kernel_bench.json").write_text(json.dumps(res, indent=1))
     print_results(res)
